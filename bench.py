@@ -1,14 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the two hot paths on MI355X (contract: see the task's bench section).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
-A "step" is one ParticleSystem.Update over the whole synthetic particle system (BASELINE.json configs[1]:
-1 M particles in 16 chunks of 256^2, Spawner + Gravity(4 attractors) + Noise + UpdatePositions, fp32).
+At N = 1 the headline is cfg4 whole on the GPU: a "step" is one ParticleSystem.Update over 64 chunks of 1024^2
+(67 M particles, Gravity(4 attractors) + Noise + UpdatePositions, fp32, 5.4 GB of state in HBM), K steps timed in
+one block after max(W, 20) untimed ones; `value` = Mparticle-steps/s, `ms_per_step` = wall time of the block / K.
+A plain run measures that and nothing else.  --full measures what the record carried beside it as well: cfg2
+(BASELINE.json configs[1]: 1 M particles in 16 chunks of 256^2 with a Spawner, cache-resident), cfg4's per-GPU
+share, both lit frames, the next rows, the CPU baselines and the HBM calibration.  --dump-outputs DIR writes a fixed
+sample of the particle state the last timed step left (dump_particle_outputs).
+
 `value` = whole-job Mparticle-steps/s with all inputs resident in HBM.  With N > 1 every rank owns the same
-number of chunks (chunks never interact, ParticleSystem.cs:743-745): no data-path collective, weak scaling.
-The second hot path (sphere-light SDF cone trace) is measured after the timed particle region and reported
-in the same JSON line under "lighting" (1080p/64 lights and 4K/256 lights fp16; screen strips + RCCL
+number of chunks (chunks never interact, ParticleSystem.cs:743-745): weak scaling over cfg4's per-GPU share
+(finalize_record).  That headline is measured by the full record's machinery (rows with collectives, ratios
+against rows rank 0 takes alone), so N > 1 implies --full.
+With --full the second hot path (sphere-light SDF cone trace) is measured after the timed particle region and
+reported in the same JSON line under "lighting" (1080p/64 lights and 4K/256 lights fp16; screen strips + RCCL
 all-gather of the lightmap when N > 1).
 
 The host side is the C++ mirror of the reference's ParticleSystem / LightingRenderer (illuminant_amd/host),
@@ -46,6 +54,7 @@ TRACE_LOOP_INSTRUCTIONS = {"fp16": 56, "unorm16": 52}      # with the visibility
 # skip went in, docs/experiments.md 3.2): 0.82 x 44 + 0.18 x 56 and 0.82 x 40 + 0.18 x 52.  This is the PRIMARY work-based figure since r04.
 TRACE_LOOP_WEIGHTED = {"fp16": 46.0, "unorm16": 42.0}
 INFINITY_CACHE_MB = 256
+METRIC = "Mparticle-steps/sec + lit Mpixels/sec (4K, 256 point lights) at 1/2/4/8 GPUs"
 
 
 def kernel_sources_sha256():
@@ -269,12 +278,34 @@ def parse_args():
     ap.add_argument("--dry-collectives", action="store_true", help="N > 1 (or ILM_BENCH_FORCE_DIST): walk the whole branch once at minimal repetition and print the ordered list of "
                     "collectives with their byte counts instead of the record (profiles/r06_collective_schedule.txt)")
     ap.add_argument("--no-particle-collective-rows", action="store_true", help="N > 1: skip the particle rows with collectives (live counts, Pos+Life all-gather)")
-    ap.add_argument("--blocks", type=int, default=0, help="timed K-step blocks (0: as many as fill ~50 ms of GPU time, 3..15); "
-                                                          "the headline is the median block, min / max are reported beside it")
+    ap.add_argument("--blocks", type=int, default=0, help="--full: timed K-step blocks of cfg2 (0: as many as fill ~50 ms of GPU time, 3..15); "
+                                                          "cfg2's figure is the median block, min / max are reported beside it")
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline too: cfg2, cfg4's share, both lit frames, the next rows, "
+                                                        "the CPU baselines and the HBM calibration (without it a one-GPU run measures the headline alone; "
+                                                        "implied with --gpus N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="one GPU: after the timed steps, write what the last one computed as DIR/<name>.npy "
+                                                                        "(a fixed sample of the particle planes, float32; see dump_particle_outputs)")
     args = ap.parse_args()
     if args.dry_collectives:
         args.steps, args.warmup, args.blocks, args.light_frames, args.light_ms, args.sustain_s = 5, 0, 1, 1, 0.0, 0.0
         args.no_cpu_baseline = args.no_next_rows = True
+        args.full = True
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.gpus > 1 or os.environ.get("ILM_BENCH_FORCE_DIST"):
+        # N > 1 (or its one-GPU form): the record's headline is cfg4's share WITH its collectives, measured last under the watchdog and
+        # divided by rank-0-alone rows (finalize_record, scaling_detail) -- the whole record, so --full is implied
+        args.full = True
+    if not args.full:
+        # a run without --full is the one-GPU headline alone: switches that select the rows beside it would be ignored, so they are refused
+        given = [flag for flag, on in (("--no-lighting", args.no_lighting), ("--no-cfg4", args.no_cfg4), ("--no-cfg4-64m", args.no_cfg4_64m),
+                                       ("--no-next-rows", args.no_next_rows), ("--no-cpu-baseline", args.no_cpu_baseline),
+                                       ("--no-store-mode-row", args.no_store_mode_row), ("--no-particle-collective-rows", args.no_particle_collective_rows),
+                                       ("--blocks", args.blocks != 0)) if on]
+        if given:
+            ap.error("%s select(s) rows of --full; a run without --full measures the one-GPU headline alone" % ", ".join(given))
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("ILM_BENCH_FORCE_DIST") or args.no_cfg4 or args.no_cfg4_64m):
+        ap.error("--dump-outputs needs one plain GPU and the 64 M row: the outputs are those of the one-GPU headline")
     return args
 
 
@@ -376,7 +407,7 @@ def particle_row(world_units, live_per_rank, k, blocks, kernel, traffic=None):
     gbs_wall = live_per_rank * PARTICLE_BYTES_PER_SLOT / (w / k) / 1e9      # the same bytes over ms_per_step (wall clock, max over ranks, barriers included)
     return {"mparticle_steps_per_s": round(world_units * live_per_rank * k / w / 1e6, 1), "ms_per_step": round(w / k * 1e3, 5), "steps": k,
             "particles_per_gpu": live_per_rank,
-            "timed_blocks": {"blocks": len(blocks), "steps_per_block": k, "headline": "median block", "ms_per_step_min": round(blocks[0][0] / k * 1e3, 5),
+            "timed_blocks": {"blocks": len(blocks), "steps_per_block": k, "headline": "median block" if len(blocks) > 1 else "the one block", "ms_per_step_min": round(blocks[0][0] / k * 1e3, 5),
                              "ms_per_step_max": round(blocks[-1][0] / k * 1e3, 5)},
             "roofline": {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
                          "frac_from_ms_per_step": round(gbs_wall / HBM_PEAK_GBS, 4),
@@ -761,6 +792,63 @@ def cfg4_images(scenes, rank):
     return CHUNK_1024_IMAGES[rank]
 
 
+STREAM_KERNEL = "ilm::step_lean_kernel<no spawn, streaming> (two launches per step: the chunk range halved over the context's two streams)"
+HEADLINE_SETTLE_STEPS = 20      # untimed steps the 64 M system takes at least: the first steps after its 5.4 GB upload run slower (clocks settle)
+DUMP_SLOTS_PER_CHUNK = 8192     # --dump-outputs: 64 chunks x 8192 slots x 4 planes x 16 B = 32 MB, + 4 MB of slot numbers
+DUMP_SEED = 2024
+
+
+def cfg4_64m_row(H, ctx, scenes, abi, ranks, k, warm, n_blocks, dump_dir=None):
+    """cfg4 WHOLE on one device: 64 chunks of 1024^2 = 67 M particles, the reference's own ceiling (MaxChunkCount = 64, ParticleSystem.cs:49),
+    5.4 GB of state.  `warm` untimed steps, then `n_blocks` timed blocks of EXACTLY k steps (time_blocks; `ranks`: who steps together).
+    With dump_dir, the state the last timed step left is written there (dump_particle_outputs).  Returns (row, the step descriptor the GPU ran
+    last: the CPU baseline replays it)."""
+    F = build_particle_system(H, ctx, scenes, abi, 1024, 64, 0, with_spawner=False, replicate_cfg4_images=True)
+    ps, tp, frame = F["ps"], F["tp"], [0]
+
+    def one():
+        tp.Advance(1.0 / 60.0); ps.Update(frame[0]); frame[0] += 1
+    for _ in range(warm):
+        one()
+    row = particle_row(1, F["live"], k, time_blocks(ctx, ranks, one, k, n_blocks), STREAM_KERNEL, profiled_traffic("ilm::step_lean_kernel<false, true>"))
+    row["workload"] = ("cfg4 whole on ONE GPU: 64 chunks of 1024^2 = %d particles (5.4 GB of state), Gravity(4 attractors)+Noise+UpdatePositions; "
+                       "chunk c = image c mod 8 of the share's eight, moved by (3, 2) x (c div 8) px" % F["live"])
+    row["roofline"]["resident"] = "hbm (5.4 GB of particle state)"
+    if dump_dir:
+        dump_particle_outputs(ps, abi, len(ps.Chunks), dump_dir)
+    return row, ps.LastStepBytes()
+
+
+def dump_particle_outputs(ps, abi, n_chunks, out_dir):
+    """--dump-outputs: what a caller of the timed step receives -- the four planes ParticleSystem.Update writes (position + life, velocity,
+    render colour, render data), read back chunk by chunk after the last timed step.  The whole state is 4 GB, so the same seeded sample of
+    DUMP_SLOTS_PER_CHUNK slots of every chunk is kept in every run: particles_<plane>.npy (float32, chunk-major rows of 4) and
+    particles_slot.npy (float64: chunk x slots per chunk + slot of each row)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    names = ("position", "velocity", "render_color", "render_data")
+    picks, slots = {name: [] for name in names}, []
+    for c in range(n_chunks):
+        planes = [ps.Readback(c, plane) for plane in (abi.PLANE_POSITION, abi.PLANE_VELOCITY, abi.PLANE_RENDER_COLOR, abi.PLANE_RENDER_DATA)]
+        idx = np.sort(rng.choice(planes[0].shape[0], DUMP_SLOTS_PER_CHUNK, replace=False))
+        slots.append(c * planes[0].shape[0] + idx.astype(np.float64))
+        for name, data in zip(names, planes):
+            picks[name].append(data[idx])
+    for name in names:
+        np.save(os.path.join(out_dir, "particles_%s.npy" % name), np.concatenate(picks[name]).astype(np.float32))
+    np.save(os.path.join(out_dir, "particles_slot.npy"), np.concatenate(slots))
+
+
+def headline_record(args, row):
+    """The one-GPU result line: cfg4-64M particle steps (the figure finalize_record puts in `value` at N = 1), nothing measured beside it."""
+    return {"metric": METRIC, "value": row["mparticle_steps_per_s"], "unit": "Mparticle-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": row["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "cfg4-64M on one GPU: " + row["workload"].split(": ", 1)[1], "particles_per_gpu": row["particles_per_gpu"],
+                       "parallelism": "one GPU: 64 chunks in one launch pair per step (the chunk range halved over the context's two streams)",
+                       "ranks": 1, "rccl_communicator_ranks": 0, "warmup_steps_run": max(args.warmup, HEADLINE_SETTLE_STEPS)},
+            "timed_blocks": row["timed_blocks"], "roofline": row["roofline"]}
+
+
 def build_particle_system(H, ctx, scenes, abi, chunk_size, n_chunks, rank, with_spawner=True, replicate_cfg4_images=False):
     """cfg2: n_chunks full chunks uploaded through Spawn(initializers) + a Spawner-fed chunk, Gravity x4 + Noise.
     replicate_cfg4_images (chunk_size 1024): chunk c holds image c mod 8 of the rank's eight cfg4 images, its particles moved by
@@ -996,6 +1084,22 @@ def main():
     forced_dist = bool(os.environ.get("ILM_BENCH_FORCE_DIST"))
     multi = world > 1 or forced_dist        # the N > 1 shape of the record (ILM_BENCH_FORCE_DIST: the same code at world 1, for one-GPU boxes)
 
+    def emit(o):
+        sys.stdout.flush()
+        os.dup2(stdout_fd, 1)
+        if rank == 0:
+            print(json.dumps(o), flush=True)
+        os.dup2(2, 1)
+
+    # ---- the headline at N = 1: cfg4 whole on the GPU, warm-up, EXACTLY --steps timed steps in one block -------------------------
+    # Without --full that is the whole run.  With --full the same row is taken where the 64 M row always stood (after cfg2 and cfg4's
+    # share) and finalize_record makes it `value` as before.
+    headline_warm = max(args.warmup, HEADLINE_SETTLE_STEPS)
+    if not multi and not args.full:
+        row, _ = cfg4_64m_row(H, ctx, scenes, abi, ranks.solo(), args.steps, headline_warm, 1, dump_dir=args.dump_outputs)
+        emit(headline_record(args, row))
+        return
+
     # ---- particles (the timed region of the contract) ------------------------------------------------------------
     COLLECTIVES.phase("particles: cfg2, all ranks (barriers and max-over-ranks of the timed blocks)")
     P = build_particle_system(H, ctx, scenes, abi, args.chunk_size, args.chunks, rank)
@@ -1039,7 +1143,7 @@ def main():
     step_traffic = profiled_traffic("ilm::step_lean_kernel<true, false>", "ilm::step_lean_kernel<false, false>")
 
     out = {
-        "metric": "Mparticle-steps/sec + lit Mpixels/sec (4K, 256 point lights) at 1/2/4/8 GPUs",
+        "metric": METRIC,
         "value": round(value, 2),
         "unit": "Mparticle-steps/s",
         "n_gpus": n_gpus,
@@ -1204,7 +1308,7 @@ def main():
     scaling_particles = None
     if not args.no_cfg4:
         del P, ps, spawner          # free cfg2's chunks before the 0.9 GB system is built
-        stream_kernel = "ilm::step_lean_kernel<no spawn, streaming> (two launches per step: the chunk range halved over the context's two streams)"
+        stream_kernel = STREAM_KERNEL
         stream_traffic = profiled_traffic("ilm::step_lean_kernel<false, true>")
         k4 = args.steps if multi else 30      # N > 1: this row is the headline -> EXACTLY K steps per block
 
@@ -1243,13 +1347,11 @@ def main():
         if not args.no_cfg4_64m:
             k64 = args.steps
             if rank == 0:
-                F = build_particle_system(H, ctx, scenes, abi, 1024, 64, rank, with_spawner=False, replicate_cfg4_images=True)
-                full_64m = particle_row(1, F["live"], k64, time_blocks(ctx, ranks.solo(), stepper(F, 20), k64, 5), stream_kernel, stream_traffic)
-                cfg4_desc_bytes = F["ps"].LastStepBytes()
-                full_64m["workload"] = ("cfg4 whole on ONE GPU: 64 chunks of 1024^2 = %d particles (5.4 GB of state), Gravity(4 attractors)+Noise+UpdatePositions; "
-                                        "chunk c = image c mod 8 of the share's eight, moved by (3, 2) x (c div 8) px" % F["live"])
-                full_64m["roofline"]["resident"] = "hbm (5.4 GB of particle state)"
-                del F
+                # N = 1: the headline, taken exactly as a run without --full takes it; N > 1: five blocks on rank 0 alone
+                if multi:
+                    full_64m, cfg4_desc_bytes = cfg4_64m_row(H, ctx, scenes, abi, ranks.solo(), k64, 20, 5)
+                else:
+                    full_64m, cfg4_desc_bytes = cfg4_64m_row(H, ctx, scenes, abi, ranks.solo(), k64, headline_warm, 1, dump_dir=args.dump_outputs)
                 out["cfg4_full_64m_one_gpu"] = full_64m
             if multi:
                 barrier()
@@ -1861,7 +1963,7 @@ def main():
     collective_rows = {}
 
     # ---- the box's own HBM rate beside the spec figure ("a calibration run ... the calibrated number next to the spec number") ----
-    if rank == 0 and not args.dry_collectives:
+    if rank == 0 and args.full and not args.dry_collectives:
         try:
             cal = calibrate_hbm_copy(native, local_rank, ctx)
             out["hbm_calibration"] = cal
@@ -1888,13 +1990,6 @@ def main():
             if optional_rows_note:
                 o["scaling_detail"]["optional_rows"] = optional_rows_note
         return finalize_record(o, world, forced_dist, step_ms_gpu * 1e3, copy.deepcopy(collective_rows))
-
-    def emit(o):
-        sys.stdout.flush()
-        os.dup2(stdout_fd, 1)
-        if rank == 0:
-            print(json.dumps(o), flush=True)
-        os.dup2(2, 1)
 
     particle_rows = None
     if multi and scaling_particles and not args.no_particle_collective_rows:

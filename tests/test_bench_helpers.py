@@ -168,3 +168,83 @@ def test_the_particle_rows_with_collectives_run_first_under_the_watchdog():
     finally:
         bench.particle_collective_rows, bench.exchange_variant_rows = old_p, old_x
     assert order == ["particles", "frames", "barrier"] and rows == {"with_live_counts": {"mparticle_steps_per_s": 1.0}} and "store_mode" in frames["cfg3"]
+
+
+def test_a_plain_run_measures_the_headline_and_full_is_opt_in(monkeypatch):
+    """Without --full a run is the headline alone; --full (implied by --dry-collectives) adds everything else; --dump-outputs belongs to
+    the one-GPU headline, so it is refused where that row is not taken."""
+    import pytest
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "3"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--dry-collectives"])
+    assert bench.parse_args().full
+    # N > 1 is the whole record: --full is implied, and the row switches keep their meaning there
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--no-cfg4-64m"])
+    a = bench.parse_args()
+    assert a.full and a.no_cfg4_64m
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cfg4", "--no-lighting", "--blocks", "3"])
+    assert bench.parse_args().no_cfg4
+    # one GPU without --full measures the headline alone: a switch that selects --full rows would be ignored, so it is refused
+    for argv in (["--gpus", "2", "--dump-outputs", "out"], ["--full", "--no-cfg4-64m", "--dump-outputs", "out"], ["--steps", "0"],
+                 ["--no-cfg4"], ["--no-cfg4-64m"], ["--no-lighting"], ["--no-next-rows"], ["--no-cpu-baseline"], ["--blocks", "3"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            bench.parse_args()
+
+
+def test_the_plain_line_carries_the_figures_a_full_record_leads_with():
+    """headline_record (a run without --full) and finalize_record (--full, N = 1) put the same 64 M row in metric / value / unit /
+    higher_is_better / dtype / ms_per_step / roofline; the plain line is a few hundred bytes."""
+    import json
+    import types
+    c64 = _row(0, 1.25, live=67108864)
+    c64["workload"] = "cfg4 whole on ONE GPU: 64 chunks of 1024^2 = 67108864 particles"
+    rec = bench.headline_record(types.SimpleNamespace(steps=4, warmup=0), c64)
+    out = {"metric": bench.METRIC, "value": 55000.0, "unit": "Mparticle-steps/s", "n_gpus": 1, "steps": 4, "warmup": 0, "ms_per_step": 0.02,
+           "higher_is_better": True, "dtype": "f32", "config": {"workload": "cfg2: ..."}, "timed_blocks": {"blocks": 3},
+           "roofline": {"bound": "hbm", "frac": 0.8}, "cfg4_full_64m_one_gpu": c64}
+    full = bench.finalize_record(out, 1, False, 20.0)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "timed_blocks"):
+        assert rec[k] == full[k], k
+    assert rec["config"]["workload"] == full["config"]["workload"] and rec["steps"] == 4
+    assert rec["value"] == c64["mparticle_steps_per_s"] and rec["unit"] == "Mparticle-steps/s" and rec["dtype"] == "f32"
+    assert len(json.dumps(rec)) < 4096
+    # one timed block is not called a median
+    assert c64["timed_blocks"]["headline"] == "median block" and bench.particle_row(1, 10, 4, [(1e-3, 1.0)], "k")["timed_blocks"]["headline"] == "the one block"
+
+
+class _StandInSystem:
+    """ParticleSystem.Readback(chunk, plane) of `n_chunks` chunks of `m` slots whose values name chunk, slot, plane and component."""
+
+    def __init__(self, n_chunks, m):
+        import numpy as np
+        self.Chunks, self.m, self.np = [None] * n_chunks, m, np
+
+    def Readback(self, chunk, plane):
+        np = self.np
+        return (np.arange(self.m, dtype=np.float32)[:, None] * 8 + np.arange(4, dtype=np.float32) + plane * 0.25 + chunk * 1e6).astype(np.float32)
+
+
+def test_the_output_dump_is_a_fixed_sample_of_the_planes_the_step_writes(tmp_path):
+    import numpy as np
+    from illuminant_amd import abi
+    ps = _StandInSystem(3, 3 * bench.DUMP_SLOTS_PER_CHUNK)
+    bench.dump_particle_outputs(ps, abi, 3, str(tmp_path / "a"))
+    bench.dump_particle_outputs(ps, abi, 3, str(tmp_path / "b"))
+    names = ("position", "velocity", "render_color", "render_data")
+    slot = np.load(str(tmp_path / "a" / "particles_slot.npy"))
+    assert slot.dtype == np.float64 and slot.shape == (3 * bench.DUMP_SLOTS_PER_CHUNK,) and len(np.unique(slot)) == len(slot)
+    chunk, idx = (slot // ps.m).astype(np.int64), (slot % ps.m).astype(np.int64)
+    assert list(np.bincount(chunk)) == [bench.DUMP_SLOTS_PER_CHUNK] * 3
+    for name, plane in zip(names, (abi.PLANE_POSITION, abi.PLANE_VELOCITY, abi.PLANE_RENDER_COLOR, abi.PLANE_RENDER_DATA)):
+        a = np.load(str(tmp_path / "a" / ("particles_%s.npy" % name)))
+        assert a.dtype == np.float32 and a.shape == (len(slot), 4)
+        want = np.stack([ps.Readback(c, plane)[i] for c, i in zip(chunk, idx)])
+        assert np.array_equal(a, want), name
+        assert np.array_equal(a, np.load(str(tmp_path / "b" / ("particles_%s.npy" % name)))), "the sample must not change from run to run"
+    # the headline's 64 chunks stay within the 64 MB the option may write
+    assert 64 * bench.DUMP_SLOTS_PER_CHUNK * (4 * 4 * 4 + 8) <= 64 << 20

@@ -51,7 +51,7 @@ def test_bench_runs_its_whole_n_gpu_branch_at_two_ranks(fake_rccl):
     the instrumented counts summed over the ranks equal the oracle's totals for the whole frames, the composite call and the pipelined
     exchange reproduce the frame, and the line carries the self-describing scaling block."""
     env = dict(os.environ, ILM_RCCL_LIB=fake_rccl, ILM_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--light-frames", "2", "--light-ms", "0",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "5", "--warmup", "1", "--light-frames", "2", "--light-ms", "0",
                         "--sustain-s", "0"], env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -91,7 +91,7 @@ def test_a_hang_in_an_optional_row_costs_the_record_that_row_only(fake_rccl):
     rank 0 prints the record as it stood -- every mandatory figure, the count checks, the serial composited frames -- with a note, and
     every rank leaves with status 0."""
     env = dict(os.environ, ILM_RCCL_LIB=fake_rccl, ILM_BENCH_ONE_GPU="1", ILM_BENCH_HANG_OPTIONAL="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--light-frames", "2", "--light-ms", "0",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4", "--warmup", "1", "--light-frames", "2", "--light-ms", "0",
                         "--sustain-s", "0", "--no-cfg4-64m", "--optional-rows-timeout", "8"], env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

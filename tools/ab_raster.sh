@@ -3,7 +3,7 @@
 cd "$(cd "$(dirname "$0")/.." && pwd)"
 for round in 1 2; do
 for tag in "$@"; do
-  LD_LIBRARY_PATH=$PWD/tools/ab/$tag:${LD_LIBRARY_PATH:-} python bench.py --no-cpu-baseline --no-cfg4 --no-lighting --steps 200 2>/dev/null | \
+  LD_LIBRARY_PATH=$PWD/tools/ab/$tag:${LD_LIBRARY_PATH:-} python bench.py --full --no-cpu-baseline --no-cfg4 --no-lighting --steps 200 2>/dev/null | \
     python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$tag', d['next_rows']['rasterize_cfg2_1080p']['ms_per_frame'])"
 done
 done

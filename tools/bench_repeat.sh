@@ -5,9 +5,9 @@ round=${1:-r05}; runs=${2:-5}
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 out=gpurun_out/${round}_bench_repeat.txt
-echo "# python bench.py (defaults), $runs runs back to back on one box: $(date -u +%FT%TZ)" > $out
+echo "# python bench.py --full (defaults), $runs runs back to back on one box: $(date -u +%FT%TZ)" > $out
 for i in $(seq 1 $runs); do
-    python bench.py 2>/dev/null | python -c "
+    python bench.py --full 2>/dev/null | python -c "
 import json, sys
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 L = d['lighting']

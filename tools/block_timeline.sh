@@ -4,7 +4,7 @@
 cd "$(cd "$(dirname "$0")/.." && pwd)"
 export TMPDIR=/tmp
 rm -rf /tmp/btl
-timeout 250 rocprofv3 --kernel-trace --output-format csv -d /tmp/btl -o t -- python bench.py --steps ${1:-20} --warmup 5 --no-cpu-baseline --no-lighting --no-cfg4 --no-next-rows > /tmp/btl.json 2>/tmp/btl.log
+timeout 250 rocprofv3 --kernel-trace --output-format csv -d /tmp/btl -o t -- python bench.py --full --steps ${1:-20} --warmup 5 --no-cpu-baseline --no-lighting --no-cfg4 --no-next-rows > /tmp/btl.json 2>/tmp/btl.log
 python3 - <<'PY'
 import csv, glob
 ev = []

@@ -7,7 +7,7 @@ cd "$(cd "$(dirname "$0")/.." && pwd)"
 export TMPDIR=/tmp
 OUT=gpurun_out/gap_${1:-x}
 rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --kernel-trace --output-format csv -d "$OUT/p" -o t -- python bench.py --steps 40 --warmup 5 --blocks 3 --no-cpu-baseline --no-lighting --no-cfg4 --no-next-rows > "$OUT/bench.json" 2> "$OUT/log"
+rocprofv3 --kernel-trace --output-format csv -d "$OUT/p" -o t -- python bench.py --full --steps 40 --warmup 5 --blocks 3 --no-cpu-baseline --no-lighting --no-cfg4 --no-next-rows > "$OUT/bench.json" 2> "$OUT/log"
 python - "$OUT" <<'PY'
 import csv, glob, sys, collections
 rows = []

@@ -10,7 +10,7 @@ OUT=gpurun_out/marker_$TAG
 S=gpurun_out/profiles_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT" "$S"
 ILM_TRACE=1 rocprofv3 --marker-trace --kernel-trace --stats --output-format csv -d "$OUT" -o trace -- \
-  python bench.py --steps 5 --warmup 2 --blocks 3 --light-frames 2 --light-ms 0 --sustain-s 0 --no-cpu-baseline --no-cfg4 > "$OUT/bench.json" 2> "$OUT/bench.err"
+  python bench.py --full --steps 5 --warmup 2 --blocks 3 --light-frames 2 --light-ms 0 --sustain-s 0 --no-cpu-baseline --no-cfg4 > "$OUT/bench.json" 2> "$OUT/bench.err"
 python - "$OUT" "$S/${TAG}_marker_trace.txt" <<'PY'
 import csv, glob, sys, collections
 out, dst = sys.argv[1], sys.argv[2]
@@ -27,7 +27,7 @@ for r in rows:
     except (KeyError, ValueError):
         pass
 with open(dst, "w") as f:
-    f.write("# ILM_TRACE=1 rocprofv3 --marker-trace --kernel-trace -- python bench.py --steps 5 --warmup 2 --blocks 3 --light-frames 2 ... (tools/marker_trace.sh)\n")
+    f.write("# ILM_TRACE=1 rocprofv3 --marker-trace --kernel-trace -- python bench.py --full --steps 5 --warmup 2 --blocks 3 --light-frames 2 ... (tools/marker_trace.sh)\n")
     f.write("# roctx ranges pushed by the C ABI's entry points: calls, host microseconds inside the range (total, mean)\n")
     for n, c in names.most_common():
         f.write("%-40s %7d %12.1f %10.2f\n" % (n, c, dur[n], dur[n] / max(c, 1)))

@@ -7,7 +7,7 @@ cd "$(cd "$(dirname "$0")/.." && pwd)"
 export TMPDIR=/tmp
 OUT=gpurun_out/pmc_collision_${1:-x}
 rm -rf "$OUT"; mkdir -p "$OUT"
-CMD="python bench.py --steps 20 --warmup 5 --no-lighting --no-cfg4 --no-cpu-baseline"
+CMD="python bench.py --full --steps 20 --warmup 5 --no-lighting --no-cfg4 --no-cpu-baseline"
 rocprofv3 --kernel-trace --output-format csv --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_SMEM -d "$OUT/p1" -o pmc -- $CMD > "$OUT/p1.json" 2> "$OUT/p1.log"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o s -- $CMD > "$OUT/stats.json" 2> "$OUT/stats.log"
 {

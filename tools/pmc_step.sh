@@ -8,7 +8,7 @@ cd "$ROOT"
 export TMPDIR=/tmp
 OUT=gpurun_out/pmc_step_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
-CMD="python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-lighting --no-cfg4 --no-next-rows"
+CMD="python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-lighting --no-cfg4 --no-next-rows"
 i=0
 for pass in "SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT SQ_INSTS_BRANCH" \
             "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_FLAT SQ_INST_CYCLES_SALU SQ_INST_CYCLES_SMEM SQ_THREAD_CYCLES_VALU" \

@@ -12,9 +12,9 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 SUM=gpurun_out/profiles_$TAG
 rm -rf "$OUT" "$SUM"; mkdir -p "$OUT" "$SUM"
-# the driver's exact command (kernel durations do not carry over between --steps 200 and --steps 20)
-BENCH="python bench.py --steps 20 --warmup 5"
-SHORT="python bench.py --steps 40 --warmup 5 --light-frames 1 --light-ms 0 --no-cpu-baseline"
+# the driver's command with --full, so that every row's kernels run (kernel durations do not carry over between --steps 200 and --steps 20)
+BENCH="python bench.py --full --steps 20 --warmup 5"
+SHORT="python bench.py --full --steps 40 --warmup 5 --light-frames 1 --light-ms 0 --no-cpu-baseline"
 
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- $BENCH > "$SUM/bench_under_rocprof.json" 2> "$OUT/stats.log"
 for pass in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum" \

@@ -11,8 +11,8 @@ bash tools/pmc_light.sh $TAG > "$S/${TAG}_light_lane_activity.txt" 2>&1
 bash tools/pmc_bound.sh $TAG > /dev/null 2>&1; cp gpurun_out/pmc_bound_$TAG/summary.txt "$S/${TAG}_pmc_bound_cell_array.txt"
 bash tools/pmc_collision.sh $TAG > /dev/null 2>&1; cp gpurun_out/pmc_collision_$TAG/summary.txt "$S/${TAG}_collision_step.txt"
 python tools/working_set_sweep.py > "$S/${TAG}_step_working_set_sweep.txt" 2>/dev/null
-python bench.py > "$S/${TAG}_bench_default.json" 2> /dev/null
-ILM_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$S/${TAG}_bench_forced_dist_world1.json" 2> /dev/null
+python bench.py --full > "$S/${TAG}_bench_default.json" 2> /dev/null
+ILM_BENCH_FORCE_DIST=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$S/${TAG}_bench_forced_dist_world1.json" 2> /dev/null
 # r05: one rank's strips under every light-split setting, the store-mode exchange on one device, the roctx ranges of a short run
 python tools/strip_probe.py --gbuffer > "$S/${TAG}_strip_probe.txt" 2>&1
 python tools/store_mode_probe.py 8 20 > "$S/${TAG}_store_mode_probe.txt" 2>&1

@@ -10,7 +10,7 @@ mkdir -p gpurun_out
 lib=/tmp/libfake_rccl.so
 g++ -O1 -std=c++17 -shared -fPIC -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include tests/fake_rccl.cpp -o $lib -L/opt/rocm/lib -lamdhip64 -lrt -lpthread || exit 1
 for n in $worlds; do
-    ILM_RCCL_LIB=$lib ILM_BENCH_ONE_GPU=1 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 1500 python bench.py --gpus $n --steps 6 --warmup 2 --light-frames 4 --light-ms 0 --sustain-s 0 \
+    ILM_RCCL_LIB=$lib ILM_BENCH_ONE_GPU=1 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 1500 python bench.py --full --gpus $n --steps 6 --warmup 2 --light-frames 4 --light-ms 0 --sustain-s 0 \
         > gpurun_out/${round}_bench_${n}_ranks_one_gpu_stand_in.json 2> gpurun_out/${round}_bench_${n}_ranks_one_gpu_stand_in.err
     echo "world $n: rc $? $(python - <<PY
 import json

@@ -40,7 +40,7 @@ def main():
             for r in rows:
                 w.writerow([r["Name"], r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["Percentage"], r["MinNs"], r["MaxNs"], r["StdDev"]])
                 kernel_avg[short(r["Name"])] = (int(r["Calls"]), float(r["AverageNs"]))
-        lines += ["## kernel trace (`rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5`, the driver's exact command; PMC passes: `--steps 40 --warmup 5 --light-frames 1 --light-ms 0 --no-cpu-baseline`)", "",
+        lines += ["## kernel trace (`rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5`, the driver's command with every row; PMC passes: `--steps 40 --warmup 5 --light-frames 1 --light-ms 0 --no-cpu-baseline`)", "",
                   "| kernel | calls | average us | % of GPU time |", "|---|---|---|---|"]
         for r in rows[:8]:
             lines.append("| `%s` | %s | %.2f | %s |" % (short(r["Name"]), r["Calls"], float(r["AverageNs"]) / 1e3, r["Percentage"]))
