@@ -93,7 +93,7 @@ struct Ctx {
     // pinned ring for small asynchronous parameter uploads (light arrays)
     static constexpr int kRing = 4;
     void* pinned[kRing] = {}; size_t pinned_bytes[kRing] = {}; hipEvent_t pinned_ev[kRing] = {}; int ring_pos = 0;
-    IlmLightVertex* d_lights = nullptr; void* d_recs = nullptr; int light_cap = 0;
+    void* d_recs = nullptr; int light_cap = 0;      // prepared light records (kLightRecBytes each) of the last light or probe call
     unsigned long long* d_stats = nullptr;
     // light split (plan_light_split): the tiles' per-part sums and their tickets
     int last_light_blocks = 0, last_light_split = 1, last_light_macro = 0;       // the last tile-kernel launch (ilm_debug_last_light_launch)
@@ -156,9 +156,6 @@ struct Shared {
 };
 // the owner is about to write: its stream waits for the sibling contexts' queued reads
 inline hipError_t shared_before_write(Shared& sh, Ctx* owner) {
-#ifdef ILM_EXP_NO_SHARED_ORDER      // EXPERIMENT (negative control of tests/test_frames_in_flight_gpu.py: without the ordering the test must fail)
-    return hipSuccess;
-#endif
     for (size_t i = 0; i < sh.readers.size(); i++)
         if (sh.pending[i]) {
             const hipError_t e = hipStreamWaitEvent(owner->main(), sh.readers[i].second, 0);
@@ -169,9 +166,6 @@ inline hipError_t shared_before_write(Shared& sh, Ctx* owner) {
 }
 // `reader` (a sibling of the owner) is about to queue a read on its own stream: behind whatever the owner has queued
 inline hipError_t shared_before_read(Shared& sh, Ctx* owner, Ctx* reader) {
-#ifdef ILM_EXP_NO_SHARED_ORDER
-    return hipSuccess;
-#endif
     if (!sh.owner_ev) { const hipError_t e = hipEventCreateWithFlags(&sh.owner_ev, hipEventDisableTiming); if (e != hipSuccess) return e; }
     hipError_t e = hipEventRecord(sh.owner_ev, owner->main());
     if (e != hipSuccess) return e;
@@ -213,7 +207,7 @@ struct Sdf {
     // slices past that have no cells anyway).  The reference regenerates MaximumFieldUpdatesPerFrame = 1 slice triplet per frame
     // (LightingRenderer.Configuration.cs:91, LightingRenderer.DistanceField.cs:415-464): the cells of slice v hold the channel pairs
     // (v, v + 1), so a triplet [s, s + 3) invalidates the cells of slices s - 1 .. s + 2 -- 4 of cfg5's 33, not all 138 MB.
-    static constexpr int kDirtyWords = (kMaxTableSlices + 63) / 64;     // (sized by the build's table limit: -DILM_MAX_TABLE_SLICES may raise it)
+    static constexpr int kDirtyWords = (kMaxTableSlices + 63) / 64;     // (sized by the table limit, hlsl_math.hpp)
     uint64_t dirty[kDirtyWords];
     Sdf() { for (uint64_t& w : dirty) w = ~0ull; }      // nothing has cells yet
     void mark_all_dirty() { for (uint64_t& w : dirty) w = ~0ull; version++; }
@@ -298,8 +292,7 @@ SdfView make_sdf_view(const Sdf* f, const IlmDistanceFieldUniforms* df) {
     // x0 + 1 <= sliceW - 1, likewise y), z between the offset and the last valid / tabulated slice.
     v.table_slices = 0; v.columns = 1;
     v.box_x0 = v.box_y0 = v.box_z0 = 1.0f; v.box_x1 = v.box_y1 = v.box_z1 = 0.0f;      // an empty box
-    static const bool table_off = [] { const char* e = getenv("ILM_SDF_TABLE"); return e && e[0] == '0'; }();     // A/B switch
-    if (df && v.width > 0 && !table_off) {
+    if (df && v.width > 0) {
         const double cols = df->TextureSliceCount.x, rows = df->TextureSliceCount.y, slices = df->TextureSliceCount.w;
         const double isx = df->ConeAndMisc.w, isy = df->StepAndMisc2.w, ex = df->Extent.x, ey = df->Extent.y, ez = df->Extent.z;
         // ConeAndMisc.w is float(VirtualWidth / SliceWidth) (Uniforms.cs:108-109): for a resolution that is not a dyadic ratio the
@@ -513,8 +506,7 @@ __global__ __launch_bounds__(256) void copy_from_pinned_kernel(const uint4* __re
     }
 }
 int32_t upload_small_commit(Ctx* c, void* dst, int slot, size_t bytes) {
-    static const int by_kernel = [] { const char* e = getenv("ILM_UPLOAD_BY_KERNEL"); return e ? atoi(e) : 1; }();
-    if (by_kernel && bytes > 4096 && bytes <= ((size_t)2 << 20) && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+    if (bytes > 4096 && bytes <= ((size_t)2 << 20) && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
         void* dv = nullptr;
         HIP_TRY(hipHostGetDevicePointer(&dv, c->pinned[slot], 0));
         const size_t words = bytes / 16;
@@ -1314,7 +1306,6 @@ int32_t ilm_ctx_destroy(IlmHandle h) {
         if (c->pinned[i]) (void)hipHostFree(c->pinned[i]);
         if (c->pinned_ev[i]) (void)hipEventDestroy(c->pinned_ev[i]);
     }
-    if (c->d_lights) (void)hipFree(c->d_lights);
     if (c->d_recs) (void)hipFree(c->d_recs);
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->d_light_partials) (void)hipFree(c->d_light_partials);
@@ -1398,8 +1389,7 @@ int32_t ilm_engine_create(IlmHandle hctx, int32_t chunk_size, const IlmFloat4* r
     // Component planes a power of two apart land on the same memory channels: every wave of the step touches the same 256 bytes of
     // 20 planes, and a bare copy of cfg2's planes runs 16 % faster once consecutive planes are offset by a kilobyte
     // (tools/ubench/stream <slots> 0 <pad>: 1 M slots 18.9 -> 15.8 us).
-    static const int pad = [] { const char* v = getenv("ILM_PLANE_PAD"); return v ? atoi(v) : kPlanePad; }();
-    e->stride = (int64_t)e->span + (pad / 64) * 64;
+    e->stride = (int64_t)e->span + kPlanePad;
     e->rw = rw; e->rh = rh;
     const size_t bytes = sizeof(float4) * (size_t)rw * (size_t)rh;
     const IlmHandle h = to_handle(e);
@@ -2448,7 +2438,8 @@ int32_t ilm_gbuffer_render_meshes(IlmHandle h, const IlmGBufferMeshDesc* d,
         HIP_TRY(hipMalloc(&c->d_field_params, cap));
         c->field_params_bytes = cap;
     }
-    // the frame's inputs are gathered straight into a pinned slot of the ring (one host copy) and go to the device as one block
+    // the frame's inputs are gathered straight into a pinned slot of the ring (one host copy) and read by the setup kernel where they lie
+    // (one device operation and one dependent-launch gap less than a copy: the vertices are read once, by the one kernel that digests them)
     unsigned char* block = nullptr;
     int slot = -1;
     int32_t rc = upload_small_begin(c, inputs, reinterpret_cast<void**>(&block), &slot);
@@ -2458,19 +2449,10 @@ int32_t ilm_gbuffer_render_meshes(IlmHandle h, const IlmGBufferMeshDesc* d,
     if (billboard_vertex_count) memcpy(block + off_bb, billboard_vertices, sizeof(IlmBillboardVertex) * (size_t)billboard_vertex_count);
     if (!quads.empty()) memcpy(block + off_quads, quads.data(), sizeof(int4) * quads.size());
     if (!textures.empty()) memcpy(block + off_tex, textures.data(), sizeof(GBufferTex) * textures.size());
-    // ... or is read by the setup kernel where it lies (the default: one device operation and one dependent-launch gap less; the
-    // vertices are read once, by the one kernel that digests them; ILM_GBUFFER_IN_PLACE=0 copies)
-    static const int in_place = [] { const char* e = getenv("ILM_GBUFFER_IN_PLACE"); return e ? atoi(e) : 1; }();
     char* base = static_cast<char*>(c->d_field_params);
-    const char* in = base;
-    if (in_place) {
-        void* dv = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&dv, block, 0));
-        in = static_cast<const char*>(dv);
-    } else {
-        rc = upload_small_commit(c, c->d_field_params, slot, inputs);
-        if (rc != ILM_OK) return rc;
-    }
+    void* dv = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&dv, block, 0));
+    const char* in = static_cast<const char*>(dv);
     GBufferMeshLaunch a;
     a.texels = g->texels; a.width = g->width; a.height = g->height; a.format = g->format;
     a.desc = *d;
@@ -2479,7 +2461,7 @@ int32_t ilm_gbuffer_render_meshes(IlmHandle h, const IlmGBufferMeshDesc* d,
     a.billboards = reinterpret_cast<const IlmBillboardVertex*>(in + off_bb);
     a.quads = reinterpret_cast<const int4*>(in + off_quads);
     a.textures = reinterpret_cast<const GBufferTex*>(base + off_tex);
-    a.textures_in = in_place ? reinterpret_cast<const GBufferTex*>(in + off_tex) : nullptr; a.texture_count = (int32_t)textures.size();
+    a.textures_in = reinterpret_cast<const GBufferTex*>(in + off_tex); a.texture_count = (int32_t)textures.size();
     a.prims = reinterpret_cast<GBufferPrim*>(base + inputs); a.prim_count = (int32_t)prim_count;
     a.bounds = reinterpret_cast<int4*>(base + off_bounds);
     a.verts = reinterpret_cast<int4*>(base + off_verts);
@@ -2488,8 +2470,7 @@ int32_t ilm_gbuffer_render_meshes(IlmHandle h, const IlmGBufferMeshDesc* d,
     a.block_count = reinterpret_cast<int32_t*>(base + off_block_count);
     a.block_list = reinterpret_cast<int32_t*>(base + off_block_list);
     HIP_TRY(launch_gbuffer_meshes(a, c->main()));
-    if (in_place) return staged_small_done(c, slot);           // the slot is free again once the setup kernel has run
-    return ILM_OK;
+    return staged_small_done(c, slot);           // the slot is free again once the setup kernel has run
 }
 
 int32_t ilm_gbuffer_destroy(IlmHandle h) {
@@ -2592,36 +2573,27 @@ namespace {
 // XCDs, each XCD walking its groups in turn: the tiles an XCD runs side by side lie side by side, their rays towards a light cross the
 // same cells and read the same light records, and with ~100 groups per XCD the balance holds.  Identity 0.623 | 9.41; M = 2 0.624 | 9.11,
 // 3 0.618 | 9.00, 4 0.632 | 9.06, 5 0.649 | 8.84, **6 0.618 | 8.78**, 7 0.630 | 8.88, 8 0.642 | 8.98, 10 0.664 | 9.19, 12 0.625 | 8.98,
-// 16 0.808 | 9.14 (tools/ab_tilemap.sh; small frames lose balance as the groups grow, large ones gain locality until the groups get
+// 16 0.808 | 9.14 (A/B builds; small frames lose balance as the groups grow, large ones gain locality until the groups get
 // few).  Dealing a group row's groups out with the start rotated by the row (diagonal stripes) 0.636 | 8.93; whole group columns per
 // XCD, walked top to bottom, 0.70 | 8.72 (cfg5's 40 columns divide by 8, cfg3's 20 do not); the eight groups in flight as a 4 x 2 block
 // of groups 0.618 | 9.00 against 0.611 | 8.74 beside it; groups dealt out heaviest first (one-workgroup cost + bitonic sort) 0.618 | 8.96
 // against 0.613 | 8.73; single tiles sorted heaviest first 0.70 | 9.96.  Every form of "balance first" lost to "neighbours together".
-// On the eight-wave build the XCDs of a cfg3 frame end 12 % apart (tools/light_trace_probe.py), so the groups were also handed out
+// On the eight-wave build the XCDs of a cfg3 frame end 12 % apart (per-wave timestamps), so the groups were also handed out
 // dynamically -- a workgroup draws a ticket on the XCD it runs on (XCC_ID), every run of M * M tickets opens the next group off a global
 // counter, idle XCDs complete the others' last runs; exact for any dispatch order, 88 light tests green -- 0.601 | 8.56 against
 // 0.600 | 8.53: nothing, and taken out again.
-// Default: 4 with M = 6.
-// (function-local statics initialised by a lambda: thread-safe, contexts may be driven from different threads)
-int light_tile_map() {
-    static const int v = [] { const char* e = getenv("ILM_LIGHT_TILE_MAP"); return e ? atoi(e) : 4; }();
-    return v;
-}
-int light_tile_macro() {
-    static const int v = [] { const char* e = getenv("ILM_LIGHT_TILE_MACRO"); const int m = e ? atoi(e) : 6; return m < 1 ? 1 : m; }();
-    return v;
-}
-int light_split_target_waves();
-// ... and per launch: SHORT launches (at most ILM_LIGHT_SPLIT_WAVES tile-kernel waves: the ones that end tapered) are dealt in groups of
+// Shipped: (4) with M = 6, the only mapping lighting.hip implements.
+constexpr int kLightTileMacro = 6;
+// Launches of at most this many tile-kernel waves are short: they end tapered (plan_light_split) and are dealt in smaller groups.
+constexpr int64_t kLightSplitWaves = 24576;
+// ... and per launch: SHORT launches (at most kLightSplitWaves tile-kernel waves: the ones that end tapered) are dealt in groups of
 // 4 x 4 tiles instead of 6 x 6 -- a strip of a 4K frame is 120 groups of 6 x 6, fifteen per XCD, and the XCDs end several per cent
 // apart; with 4 x 4 groups (264 of them) cfg5's eight cost-balanced strips take 10.0 ms summed instead of 10.3, 1.31 instead of 1.36
 // at most (3 x 3: 10.0 | 1.33, 2 x 2: 10.0 | 1.33; r04, tools/strip_probe.py).  Whole frames keep 6 (4: 8.86 against 8.69 ms).
-// ILM_LIGHT_TILE_MACRO, when set, is used for every launch.
 int light_tile_macro_for(int width, int rows) {
-    static const bool forced = getenv("ILM_LIGHT_TILE_MACRO") != nullptr;
-    if (forced || rows <= 0 || width <= 0) return light_tile_macro();
+    if (rows <= 0 || width <= 0) return kLightTileMacro;
     const int64_t waves = (int64_t)((width + kLightTile - 1) / kLightTile) * (int64_t)((rows + kLightTile - 1) / kLightTile) * (kLightTileThreads / 64);
-    return (waves <= (int64_t)light_split_target_waves()) ? 4 : light_tile_macro();
+    return (waves <= kLightSplitWaves) ? 4 : kLightTileMacro;
 }
 // Light split: how many workgroups serve a tile of this launch (LightLaunch::split / taper, lighting.hip).
 // A wave of the light pass lives as long as its pixels' lights take, one after the other (~0.5 ms on cfg5, ~0.15 on cfg3), and the chip
@@ -2635,28 +2607,9 @@ int light_tile_macro_for(int width, int rows) {
 // tiles an XCD starts first are served whole, later ones by 2, then 4, the last by 8 workgroups -- the drain is made of the shortest
 // waves, the overhead is paid on the part of the launch that needs it.  On cfg5's cost-balanced strips (one GPU standing in for each
 // of 8 ranks, tools/strip_probe.py): at most 1.65 ms and 12.0 ms summed untouched, 1.44 | 10.8 at K = 2 throughout, 1.36 | 10.3 tapered, 1.31 | 10.0 tapered in 4 x 4 groups.
-//   chosen per launch: launches of at most one device fill split every tile (2 | 4 | 8 by halves), up to ILM_LIGHT_SPLIT_WAVES waves
-//   (default 24 576, three fills) the second half tapers 2 | 4 | 8, longer ones (whole frames) are not split.
-//   ILM_LIGHT_SPLIT = 1 / 2 / 4 / 8 or ilm_ctx_set_light_split force one K for every tile; ILM_LIGHT_TAPER = f1,f2,f3 forces the taper.
-int light_split_env() {
-    static const int v = [] { const char* e = getenv("ILM_LIGHT_SPLIT"); return e ? atoi(e) : 0; }();
-    return v;
-}
-int light_split_target_waves() {
-    static const int v = [] { const char* e = getenv("ILM_LIGHT_SPLIT_WAVES"); return e ? atoi(e) : 24576; }();
-    return v;
-}
-// ILM_LIGHT_TAPER = "f1,f2,f3": the fractions of an XCD's tiles from which on a tile is served by 2, 4 and 8 workgroups (1 = never)
-void light_taper_env(double f[3], bool* set) {
-    static double v[3]; static bool have = false;
-    static const bool once = [] {
-        const char* e = getenv("ILM_LIGHT_TAPER");
-        if (e && sscanf(e, "%lf,%lf,%lf", &v[0], &v[1], &v[2]) == 3) have = true;
-        return true;
-    }();
-    (void)once;
-    *set = have; f[0] = v[0]; f[1] = v[1]; f[2] = v[2];
-}
+//   chosen per launch: launches of at most one device fill split every tile (2 | 4 | 8 by halves), up to kLightSplitWaves waves
+//   (three fills) the second half tapers 2 | 4 | 8, longer ones (whole frames) are not split.
+//   ilm_ctx_set_light_split = 1 / 2 / 4 / 8 forces one K for every tile.
 int32_t plan_light_split(Ctx* c, LightLaunch* a) {
     a->split = 1; a->partials = nullptr; a->tickets = nullptr;
     const int rows = a->row_end - a->row_begin;
@@ -2666,27 +2619,22 @@ int32_t plan_light_split(Ctx* c, LightLaunch* a) {
     const int64_t tiles = (int64_t)((a->width + kLightTile - 1) / kLightTile) * (int64_t)((rows + kLightTile - 1) / kLightTile);
     // one list per tile (<= 1 024 lights; device-side counts are particle lights: thousands), and no per-light fp16 rounding chain
     if (a->blend_fp16 || a->light_count_ptr != nullptr || a->light_count > 1024 || a->light_count < 16) return ILM_OK;
-    int k = c->light_split ? c->light_split : light_split_env();
-    double f[3] = { 1.0, 1.0, 1.0 };
-    bool taper_set = false;
-    light_taper_env(f, &taper_set);
+    // f[i]: the fraction of an XCD's tiles from which on a tile is served by 2, 4 and 8 workgroups (1 = never)
+    const int k = c->light_split;
+    double f[3];
     if (k == 1) return ILM_OK;
     if (k == 2 || k == 4 || k == 8) {
         // every tile of the launch by k workgroups
         f[0] = 0.0; f[1] = (k >= 4) ? 0.0 : 1.0; f[2] = (k == 8) ? 0.0 : 1.0;
-    } else if (!taper_set) {
+    } else {
         // chosen per launch: short launches end tapered, whole frames are left alone
         const int64_t waves = tiles * (kLightTileThreads / 64);
-        if (waves > (int64_t)light_split_target_waves()) return ILM_OK;
+        if (waves > kLightSplitWaves) return ILM_OK;
         if (waves <= 8192) { f[0] = 0.0; f[1] = 0.5; f[2] = 0.75; }     // everything starts at once: the longest wave is the launch
         else { f[0] = 0.5; f[1] = 0.75; f[2] = 0.875; }
     }
     int t[3];
-    for (int i = 0; i < 3; i++) {
-        double v = f[i] < 0.0 ? 0.0 : (f[i] > 1.0 ? 1.0 : f[i]);
-        t[i] = (int)(v * (double)slots + 0.5);
-        if (i > 0 && t[i] < t[i - 1]) t[i] = t[i - 1];
-    }
+    for (int i = 0; i < 3; i++) t[i] = (int)(f[i] * (double)slots + 0.5);      // (f is non-decreasing in [0, 1]: so is t)
     if (t[0] >= slots) return ILM_OK;
     a->taper[0] = t[0]; a->taper[1] = t[1]; a->taper[2] = t[2];
     a->split = (t[2] < slots) ? 8 : (t[1] < slots) ? 4 : 2;
@@ -2722,26 +2670,17 @@ int32_t plan_light_split(Ctx* c, LightLaunch* a) {
 // The groups of tiles dealt out heaviest first (r04).  Cost of a group = summed area of the lights' footprint boxes inside it (host
 // arithmetic on the frame's light vertices, redone only when the lights, the view or the rows change).  A whole cfg5 frame (920 groups):
 // 8.85 -> 8.69 ms, three A/B pairs on one box (-1.8 %); cfg3's 240 groups and the strips of either frame do not respond, so launches
-// of fewer than ILM_LIGHT_GROUP_ORDER_MIN groups (default 512) keep the row-major deal.  ILM_LIGHT_GROUP_ORDER=0 switches it off, =1 on
-// for every launch.  (r03 had measured "heaviest first" as a loss: that was single TILES sorted, which tears neighbours apart; whole
-// 6 x 6 groups keep the locality and only change which group an XCD takes next.)
-int light_group_order_env() {
-    static const int v = [] { const char* e = getenv("ILM_LIGHT_GROUP_ORDER"); return e ? atoi(e) : -1; }();
-    return v;
-}
-int light_group_order_min() {
-    static const int v = [] { const char* e = getenv("ILM_LIGHT_GROUP_ORDER_MIN"); return e ? atoi(e) : 512; }();
-    return v;
-}
+// of fewer than kLightGroupOrderMin groups keep the row-major deal.  (r03 had measured "heaviest first" as a loss: that was single
+// TILES sorted, which tears neighbours apart; whole 6 x 6 groups keep the locality and only change which group an XCD takes next.)
+constexpr int kLightGroupOrderMin = 512;
 int32_t plan_group_order(Ctx* c, LightLaunch* a, const IlmLightVertex* lights, int light_count, int group_edge_px) {
     a->group_order = nullptr;
     uint64_t pending_key = 0;
-    const int mode = light_group_order_env();
-    if (mode == 0 || a->tile_map != 4 || light_count <= 0) return ILM_OK;
+    if (light_count <= 0) return ILM_OK;
     const int rows = a->row_end - a->row_begin;
     const int gx = (a->width + group_edge_px - 1) / group_edge_px, gy = (rows + group_edge_px - 1) / group_edge_px;
     const int groups = gx * gy;
-    if (groups < 2 || groups > 65535 || (mode < 0 && groups < light_group_order_min())) return ILM_OK;
+    if (groups < kLightGroupOrderMin || groups > 65535) return ILM_OK;
     // the same lights over the same rows through the same view: the table on the device is still right
     {
         uint64_t key = 1469598103934665603ull;
@@ -2801,6 +2740,18 @@ int32_t plan_group_order(Ctx* c, LightLaunch* a, const IlmLightVertex* lights, i
     return ILM_OK;
 }
 
+// room for light_count prepared light records in c->d_recs (sphere lights and probes)
+int32_t reserve_light_recs(Ctx* c, int light_count) {
+    if (light_count <= c->light_cap) return ILM_OK;
+    HIP_TRY(hipStreamSynchronize(c->main()));
+    if (c->d_recs) HIP_TRY(hipFree(c->d_recs));
+    c->d_recs = nullptr; c->light_cap = 0;
+    const int cap = light_count < 256 ? 256 : light_count * 2;
+    HIP_TRY(hipMalloc(&c->d_recs, kLightRecBytes * (size_t)cap));
+    c->light_cap = cap;
+    return ILM_OK;
+}
+
 // shared by the three light passes: resource checks + the launch descriptor
 int32_t fill_light_launch(Ctx* c, const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf,
                           IlmHandle hlightmap, int32_t row_begin, int32_t row_end, LightLaunch* a) {
@@ -2815,7 +2766,7 @@ int32_t fill_light_launch(Ctx* c, const IlmEnvironment* env, const IlmDistanceFi
     if (row_begin < 0 || row_end > m->height || row_begin > row_end)
         return fail(ILM_ERR_OUT_OF_RANGE, "rows [%d, %d) outside [0, %d]", row_begin, row_end, m->height);
     { char why[256]; if (field_uniforms_mismatch(f, df, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
-    a->lights = nullptr; a->light_count = 0;
+    a->light_count = 0;
     a->env = *env; a->df = *df;
     a->gbuffer.texels = g ? g->texels : nullptr;
     a->gbuffer.width = g ? g->width : 0; a->gbuffer.height = g ? g->height : 0; a->gbuffer.format = g ? g->format : 0;
@@ -2827,7 +2778,6 @@ int32_t fill_light_launch(Ctx* c, const IlmEnvironment* env, const IlmDistanceFi
     a->stats = nullptr; a->light_count_ptr = nullptr; a->accumulate = 0;
     a->ramp = RampView{ nullptr, 0, 0 };      // particle lights have no ramp technique (LightingRenderer.cs:176-178)
     a->blend_fp16 = (c->lightmap_blend == ILM_BLEND_FP16_PER_LIGHT) ? 1 : 0;
-    a->tile_map = light_tile_map();
     a->tile_macro = light_tile_macro_for(m->width, row_end - row_begin);
     a->split = 1; a->partials = nullptr; a->tickets = nullptr; a->group_order = nullptr;
     { const int32_t rc = set_launch_mirrors(m, a); if (rc != ILM_OK) return rc; }
@@ -2913,7 +2863,7 @@ int32_t ilm_render_particle_lights(IlmHandle hctx, IlmHandle hsystem, const int3
         HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
         a.stats = c->d_stats;
     }
-    c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = (a.tile_map == 4) ? a.tile_macro : 0;
+    c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
     HIP_TRY(launch_sphere_lights_prepared(a, c->d_pl_recs, c->main()));
     HIP_TRY(light_pass_queued(c, hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr, hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr));
     if (stats) {
@@ -2940,16 +2890,7 @@ int32_t ilm_render_light_probes(IlmHandle hctx, const IlmLightVertex* lights, in
     { char why[256]; if (field_uniforms_mismatch(f, df, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
     if (probe_count == 0) return ILM_OK;
     HIP_TRY(hipSetDevice(c->device));
-    if (light_count > c->light_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_lights) HIP_TRY(hipFree(c->d_lights));
-        if (c->d_recs) HIP_TRY(hipFree(c->d_recs));
-        c->d_lights = nullptr; c->d_recs = nullptr;
-        int cap = light_count < 256 ? 256 : light_count * 2;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_lights), sizeof(IlmLightVertex) * (size_t)cap));
-        HIP_TRY(hipMalloc(&c->d_recs, kLightRecBytes * (size_t)cap));
-        c->light_cap = cap;
-    }
+    { const int32_t rc = reserve_light_recs(c, light_count); if (rc != ILM_OK) return rc; }
     // One pinned block [lights | positions | normals | values]: the kernels read their inputs where it lies (each word once) and the
     // last one writes the values into it -- no copy command on either side of the two kernels (r04; three uploads and a read-back before)
     auto align64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
@@ -3326,35 +3267,18 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     TraceSdfView trace_view;
     HIP_TRY(borrowed_trace_view(c, f, g, df, &trace_view));
 
-    if (light_count > c->light_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_lights) HIP_TRY(hipFree(c->d_lights));
-        if (c->d_recs) HIP_TRY(hipFree(c->d_recs));
-        c->d_lights = nullptr; c->d_recs = nullptr;
-        int cap = light_count < 256 ? 256 : light_count * 2;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_lights), sizeof(IlmLightVertex) * (size_t)cap));
-        HIP_TRY(hipMalloc(&c->d_recs, kLightRecBytes * (size_t)cap));
-        c->light_cap = cap;
-    }
+    { const int32_t rc = reserve_light_recs(c, light_count); if (rc != ILM_OK) return rc; }
     if (light_count > 0) {
-        static const int in_place = [] { const char* e = getenv("ILM_LIGHTS_IN_PLACE"); return e ? atoi(e) : 1; }();
-        if (in_place) {
-            // the vertices are read where the host left them (pinned ring): prepare_lights_kernel is their only reader
-            const void* staged = nullptr; int slot = 0;
-            int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
-            if (rc != ILM_OK) return rc;
-            HIP_TRY(launch_prepare_lights(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, trace_view, c->d_recs, c->main()));
-            rc = staged_small_done(c, slot);
-            if (rc != ILM_OK) return rc;
-        } else {
-            int32_t rc = upload_small(c, c->d_lights, lights, sizeof(IlmLightVertex) * (size_t)light_count);
-            if (rc != ILM_OK) return rc;
-            HIP_TRY(launch_prepare_lights(c->d_lights, light_count, *env, *df, trace_view, c->d_recs, c->main()));
-        }
+        // the vertices are read where the host left them (pinned ring): prepare_lights_kernel is their only reader
+        const void* staged = nullptr; int slot = 0;
+        int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
+        if (rc != ILM_OK) return rc;
+        HIP_TRY(launch_prepare_lights(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, trace_view, c->d_recs, c->main()));
+        rc = staged_small_done(c, slot);
+        if (rc != ILM_OK) return rc;
     }
 
     LightLaunch a = {};
-    a.lights = c->d_lights;
     a.light_count = light_count;
     a.env = *env;
     a.df = *df;
@@ -3368,7 +3292,6 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     a.accumulate = ambient ? 0 : 1;          // a further light group of the frame: added to what the lightmap holds
     a.ramp = RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h };
     a.blend_fp16 = (c->lightmap_blend == ILM_BLEND_FP16_PER_LIGHT) ? 1 : 0;
-    a.tile_map = light_tile_map();
     a.tile_macro = light_tile_macro_for(m->width, row_end - row_begin);
     if (stats) {
         HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
@@ -3378,7 +3301,7 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     { const int32_t rc = set_launch_mirrors(m, &a); if (rc != ILM_OK) return rc; }      // store-mode exchange of a group lightmap
     { const int32_t rc = plan_light_split(c, &a); if (rc != ILM_OK) return rc; }
     { const int32_t rc = plan_group_order(c, &a, lights, light_count, 16 * a.tile_macro); if (rc != ILM_OK) return rc; }
-    c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = (a.tile_map == 4) ? a.tile_macro : 0;
+    c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
     HIP_TRY(launch_sphere_lights_prepared(a, c->d_recs, c->main()));
     HIP_TRY(light_pass_queued(c, f, g));
     if (stats) {

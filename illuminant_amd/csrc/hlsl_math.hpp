@@ -324,21 +324,9 @@ ILM_DEV float sample_distance_field(f3 position, const IlmDistanceFieldUniforms&
     float a00, b00, a10, b10, a01, b01, a11, b11;
     if (CELLS0) {
         // one cell = channel r of the four taps, wrap and clamp folded in at build time: row yi + 1 (yi = -1 .. height - 1), column x0
-#ifndef ILM_CELLS0_UNTYPED
         // ONE typed load (16_16_16_16 unorm): the four channels arrive decoded by the texture path, as the 16_16 taps do (sdf_unorm_rsrc)
         const f32x4 t = ilm_llvm_buffer_load_format_xyzw(sdf_cells0_rsrc(sdf), (int)(__umul24((uint32_t)(yi + 1), pitch) + ((uint32_t)x0 << 3)), 0, 0);
         a00 = t.x; a10 = t.y; a01 = t.z; a11 = t.w;
-#else
-        // (A/B: an untyped 8-byte load and the exact decode on the vector ALU -- unorm16_to_float is the texture path's conversion bit for
-        // bit; 2-3 % slower on both sizes of tools/collision_probe.py)
-        typedef const char __attribute__((address_space(1))) gbyte0;
-        typedef uint32_t u32x2c __attribute__((ext_vector_type(2)));
-        typedef const u32x2c __attribute__((address_space(1), aligned(8))) gcell0;
-        gbyte0* cbase = (gbyte0*)uniform_u64((uint64_t)sdf.cells0);
-        const u32x2c t = *(gcell0*)(cbase + (__umul24((uint32_t)(yi + 1), pitch) + ((uint32_t)x0 << 3)));
-        a00 = unorm16_to_float((float)(t.x & 0xFFFFu)); a10 = unorm16_to_float((float)(t.x >> 16));
-        a01 = unorm16_to_float((float)(t.y & 0xFFFFu)); a11 = unorm16_to_float((float)(t.y >> 16));
-#endif
         b00 = b10 = b01 = b11 = 0.0f;
     } else if (SLICE0 && FORMAT == ILM_SDF_UNORM16) {
         const __amdgpu_buffer_rsrc_t rsrc = sdf_unorm_rsrc(sdf);       // channel r of the four taps (the pair's second channel is not needed)
@@ -383,10 +371,7 @@ ILM_DEV float sample_distance_field(f3 position, const IlmDistanceFieldUniforms&
 // 78 % busy on cfg3, its address path 56 %); the cell array holds them side by side, so an fp16 sample is ONE 16-byte load with the
 // f16 pairs already in place, a unorm16 sample two 8-byte typed loads whose channels arrive decoded (see sdf_unorm_rsrc).
 // ---------------------------------------------------------------------------------------------
-#ifndef ILM_MAX_TABLE_SLICES
-#define ILM_MAX_TABLE_SLICES 256
-#endif
-constexpr int kMaxTableSlices = ILM_MAX_TABLE_SLICES;
+constexpr int kMaxTableSlices = 256;
 struct __attribute__((aligned(16))) SliceEntry {
     float column_index;   // floor(vslice / 3) as float
     float row_index;      // floor(vslice * DistanceFieldPacked1.x): the reference's float form

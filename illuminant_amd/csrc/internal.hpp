@@ -20,16 +20,9 @@ constexpr int kComponents = 20;
 constexpr int kSlotsPerThread = 4;         // widest variant; strides are padded for it
 // 128-thread blocks: a block's slot is refilled when its slowest wave ends, and the spawning variant (74 VGPRs, 6 waves per SIMD) fills the
 // CU more evenly in pairs of waves than in fours (tools/step_ab.py r02: cfg2 with the spawner 22.1 -> 20.9 us per step, others unchanged)
-#ifndef ILM_STEP_THREADS
-#define ILM_STEP_THREADS 128
-#endif
-constexpr int kStepThreads = ILM_STEP_THREADS;
+constexpr int kStepThreads = 128;
 constexpr int kSlotsPerBlock = 1024;       // strides are padded to this
-#ifndef ILM_STEP_UNITS
-#define ILM_STEP_UNITS 1
-#endif
-constexpr int kUnitsPerWave = ILM_STEP_UNITS;   // units (64 slots each) a wave loads up front and then processes in turn: 1, 2 or 4
-constexpr int kDefaultStepMinWaves = 1;   // __launch_bounds__ min waves/SIMD of the main step variant (override: ILM_STEP_MINWAVES=6|7|8)
+constexpr int kUnitsPerWave = 1;           // units (64 slots each) a wave loads up front and then processes in turn
 
 // Values every wave would otherwise recompute on the vector ALU from uniform inputs (gfx950 has no scalar float
 // unit): filled on the host with the SAME IEEE single-precision operations, in the same order, as the per-slot
@@ -167,7 +160,6 @@ struct GBufferView {
 struct RampView { const float4* texels; int32_t width, height; };
 
 struct LightLaunch {
-    const IlmLightVertex* lights;   // device
     int32_t light_count;
     IlmEnvironment env;
     IlmDistanceFieldUniforms df;
@@ -178,16 +170,14 @@ struct LightLaunch {
     int32_t row_begin, row_end;
     unsigned long long* stats;      // device, 3 counters, or nullptr
     const int32_t* light_count_ptr; // device: when non-null the record count is read from here (particle lights are counted on the device)
-    int32_t tile_map;               // block -> tile mapping: 0 contiguous band per XCD, 1 tile rows round-robin over the XCDs, 2 identity,
-                                    // 4 groups of tile_macro x tile_macro tiles round-robin over the XCDs
     int32_t accumulate;             // != 0: start from the lightmap's contents instead of `ambient` (additive blend onto an earlier pass)
     int32_t blend_fp16;             // != 0: the reference's HalfVector4 render target -- round through fp16 after every light (ilm_ctx_set_lightmap_blend)
     RampView ramp;
-    int32_t tile_macro;             // tile_map 4: edge of the square groups of tiles dealt round-robin to the XCDs
+    int32_t tile_macro;             // edge of the square groups of tiles dealt round-robin to the XCDs (sphere_lights_kernel's tile map)
     // Light split (lighting.hip, "parts"): `split` workgroups serve one tile, each walking kLightParts / split consecutive parts of the
     // tile's light list; their per-part sums meet in `partials` (float4 per pixel, tile-major, part, thread) and the workgroup that
     // draws the tile's last ticket adds them up in part order.  split == 1: one workgroup per tile, nothing leaves the registers / LDS.
-    const uint16_t* group_order;    // tile_map 4: the groups in the order they are dealt out (heaviest first), or nullptr: row-major
+    const uint16_t* group_order;    // the groups in the order they are dealt out (heaviest first), or nullptr: row-major
     int32_t split;                  // the largest number of workgroups per tile in this launch (1: no split anywhere)
     // Tapered split: of the `taper_slots` tiles an XCD is dealt (block slots, padding included), the first taper[0] are served by one
     // workgroup each, those up to taper[1] by two, up to taper[2] by four, the rest by eight -- the work that starts last comes in the
@@ -204,11 +194,8 @@ struct LightLaunch {
 // light order, the parts added onto the clear colour in part order: the sum's bits depend on the tile and its list only, not on how
 // many workgroups computed the parts.
 constexpr int kLightParts = 8;
-// Tile edge of the light pass in pixels: 16 = four waves per workgroup (one 8 x 8 quadrant each), 8 = one wave per workgroup (EXPERIMENT, -DILM_LIGHT_TILE=8)
-#ifndef ILM_LIGHT_TILE
-#define ILM_LIGHT_TILE 16
-#endif
-constexpr int kLightTile = ILM_LIGHT_TILE;
+// Tile edge of the light pass in pixels: four waves per workgroup, one 8 x 8 quadrant each
+constexpr int kLightTile = 16;
 constexpr int kLightTileThreads = (kLightTile / 8) * (kLightTile / 8) * 64;
 
 constexpr size_t kLightRecBytes = 128;   // sizeof(LightRec) in lighting.hip
@@ -330,7 +317,7 @@ struct GBufferMeshLaunch {
     const IlmBillboardVertex* billboards;
     const int4* quads;            // (quad, texture, kind, -) per billboard quad in draw order
     const GBufferTex* textures;   // device copy (read by the raster kernel)
-    const GBufferTex* textures_in; int32_t texture_count;   // where the setup kernel copies it from (the pinned slot), or nullptr
+    const GBufferTex* textures_in; int32_t texture_count;   // where the setup kernel copies it from (the pinned slot)
     GBufferPrim* prims; int32_t prim_count;
     int4* bounds;                 // (i0, i1, j0, j1) per record: what the binning passes read
     int4* verts;                  // (x0, y0, x1, y1), (x2, y2, kind, texture) per record: what a wave's coverage test reads

@@ -464,46 +464,18 @@ ILM_DEV bool shade_light(const Pixel& P, const LightRec& L, const IlmEnvironment
 
 constexpr int kTile = kLightTile;                   // internal.hpp
 constexpr int kLightThreads = kLightTileThreads;
-constexpr int kListCapacity = (kTile == 16) ? 1024 : 256;
+constexpr int kListCapacity = 1024;
 
 // Eight waves per SIMD (64 VGPRs; the fp16 kernel without scratch, the unorm16 one with 8 bytes outside the loop).  History, tools/ab_lib.sh:
 // r02, table-driven sampler: five waves (81 VGPRs, the allocator's own need) cfg5 11.93 ms, six 11.26, seven 10.89, eight (48 bytes of
 // scratch) 10.93.  r03, cell array + exact skips + tile groups: six 9.29, seven 8.82, eight 8.67 on cfg5 but 0.61 -> 0.66 on cfg3 (spills
 // in the per-pair code).  With the launch descriptor read where it is needed (the light loop below) the spills are gone:
 // seven 0.616 | 8.93, **eight 0.602 | 8.54**.
-#ifndef ILM_LIGHT_WAVES
-#define ILM_LIGHT_WAVES 8
-#endif
-// the wave-level skip of uncovered list entries (sphere_lights_kernel's walk): 1 = the wide-binning instantiations, 2 = all, 0 = none
-#ifndef ILM_WAVE_SKIP
-#define ILM_WAVE_SKIP 1
-#endif
-#ifndef ILM_LIGHT_SGPRS
-#define ILM_LIGHT_SGPRS
-#endif
-// circle cull (sphere_lights_kernel): the particle-light instantiation (WIDE) and the sphere-light ones, switchable for A/B builds
-#ifndef ILM_LIGHT_CIRCLE_CULL_WIDE
-#define ILM_LIGHT_CIRCLE_CULL_WIDE 1
-#endif
-#ifndef ILM_LIGHT_CIRCLE_CULL
-#define ILM_LIGHT_CIRCLE_CULL 0
-#endif
-#if ILM_LIGHT_WAVES > 0
-#define ILM_LIGHT_OCCUPANCY __attribute__((amdgpu_waves_per_eu(ILM_LIGHT_WAVES, ILM_LIGHT_WAVES))) ILM_LIGHT_SGPRS
-#else
-#define ILM_LIGHT_OCCUPANCY
-#endif
-#ifdef ILM_LIGHT_TRACE     // EXPERIMENT (tools/light_trace_probe.py): per-wave start / end of the last launch (100 MHz clock), tile and XCC / CU / SIMD
-__device__ unsigned long long g_light_trace[4 * 262144];
-extern "C" int ilm_experiment_light_trace(unsigned long long* out, int n) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_light_trace), sizeof(unsigned long long) * (size_t)n);
-}
-#endif
 // WIDE_BIN: the tile list is built by all the workgroup's waves, 256 lights per round (frames of particle lights: thousands per tile);
 // otherwise by wave 0 alone, 64 per round, while the others wait -- a frame of a few hundred lights bins in 1-4 rounds either way, and
 // the wide form's extra code costs the sphere-light frames 1-2 % through register allocation, so it is its own instantiation.
 template <int FMT, bool STATS, bool WIDE_BIN>
-__global__ __launch_bounds__(kLightThreads) ILM_LIGHT_OCCUPANCY void sphere_lights_kernel(const LightLaunch a, const LightRec* __restrict__ recs, int tiles_x, int tiles_y, int tile_count) {
+__global__ __launch_bounds__(kLightThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void sphere_lights_kernel(const LightLaunch a, const LightRec* __restrict__ recs, int tiles_x, int tiles_y, int tile_count) {
     __shared__ uint16_t list[kListCapacity];
     __shared__ int list_count;
     __shared__ int bin_count[2][kLightThreads / 64];
@@ -512,10 +484,8 @@ __global__ __launch_bounds__(kLightThreads) ILM_LIGHT_OCCUPANCY void sphere_ligh
     __shared__ float4 wave_box[kLightThreads / 64];  // circle cull: (min x, max x, min y, max y) of the shaded points of each wave's 8 x 8 pixels
 
     // The dispatcher places block b on XCD b % 8.  Which tiles an XCD gets decides both its L2 locality and its share of the work
-    // (lights are not spread evenly): see light_tile_map() in api.hip for the measurements; groups of 6 x 6 tiles (tile_map 4) are the default.
-#ifdef ILM_LIGHT_TRACE
-    const unsigned long long trace_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    // (lights are not spread evenly): square groups of tile_macro x tile_macro tiles, dealt round-robin to the XCDs (api.hip has the
+    // measurements of this and the other mappings tried).
     // Light split: consecutive blocks of an XCD serve one tile (they share its L2: cells, light records, the tile's partial sums);
     // b is the tile's block number as the maps below see it, `member` which of the tile's workgroups this is.
     // (the launch descriptor through a pointer the compiler cannot see through -- see the light loop: what is read here is not kept
@@ -538,26 +508,16 @@ __global__ __launch_bounds__(kLightThreads) ILM_LIGHT_OCCUPANCY void sphere_ligh
         if (k < b2) { slot = t1 + (k - b1) / 4; member = (k - b1) % 4; return 4; }
         slot = t2 + (k - b2) / 8; member = (k - b2) % 8; return 8;
     };
-    int member, nb, b;
+    int member, b;
     {
         int slot;
         (void)tile_split(slot, member);
-        nb = a.taper_slots * 8;
         b = slot * 8 + ((int)blockIdx.x % 8);
     }
-    const int per_xcd = nb / 8;
     int tile;
-    if (a.tile_map == 1) {
-        // tile rows dealt round-robin to the XCDs: row r -> XCD r % 8 (balances a frame whose lights cluster vertically)
-        const int xcd = b % 8, k = b / 8;                  // k-th block of this XCD
-        const int rows_here = (tiles_y - xcd + 7) / 8;     // rows r with r % 8 == xcd
-        const int r_local = k / tiles_x, cx_ = k - r_local * tiles_x;
-        tile = (r_local < rows_here) ? (r_local * 8 + xcd) * tiles_x + cx_ : tile_count;
-    } else if (a.tile_map == 2) {
-        tile = b;
-    } else if (a.tile_map == 4) {
+    {
         // square groups of M x M tiles, dealt round-robin to the XCDs; an XCD walks its groups one after the other, so the tiles it
-        // runs side by side lie side by side (api.hip light_tile_map has the measurements)
+        // runs side by side lie side by side
         const int M = a.tile_macro, MM = M * M;
         const int xcd = b % 8, k = b / 8;
         int g = (k / MM) * 8 + xcd;
@@ -566,18 +526,12 @@ __global__ __launch_bounds__(kLightThreads) ILM_LIGHT_OCCUPANCY void sphere_ligh
         if (a.group_order != nullptr && g < mx * ((tiles_y + M - 1) / M)) g = (int)a.group_order[g];
         const int ty = (g / mx) * M + t / M, tx = (g % mx) * M + t % M;
         tile = (tx < tiles_x && ty < tiles_y) ? ty * tiles_x + tx : tile_count;
-    } else {
-        tile = (b % 8) * per_xcd + (b / 8);
     }
     if (tile >= tile_count)
         return;
     // the in-volume sampler's per-slice table (hlsl_math.hpp): one entry per virtual slice, visible to the tile's waves after the
     // first barrier of the light loop below
-#ifdef ILM_EXP_NO_TABLE            // EXPERIMENT (timing of the prologue only)
-    const int table_n = 0;
-#else
     const int table_n = a.sdf.table_slices;
-#endif
     for (int i = (int)threadIdx.x; i < table_n; i += kLightThreads) slice_table[i] = make_slice_entry((uint32_t)i, a.df, a.sdf);
     const InsideConsts inside = make_inside_consts(a.df, a.sdf);
     const int tx0 = (tile % tiles_x) * kTile, ty0 = a.row_begin + (tile / tiles_x) * kTile;
@@ -599,8 +553,9 @@ __global__ __launch_bounds__(kLightThreads) ILM_LIGHT_OCCUPANCY void sphere_ligh
     // box of the SHADED POINTS of its 8 x 8 pixels (whatever the G-buffer made of them: no assumption about ZToY or relativeY), and the
     // binning marks, per list entry, the waves whose box lies wholly outside the light's circle (4 bits of the 16-bit entry): those waves
     // skip the entry on a scalar test, an entry no wave needs is not listed.  Not in the statistics variant, whose pair count is the
-    // raster footprint's (so that variant is also the reference the culled frames are held to, bit for bit).
-    constexpr bool kCircleCull = !STATS && (kTile == 16) && (WIDE_BIN ? (ILM_LIGHT_CIRCLE_CULL_WIDE != 0) : (ILM_LIGHT_CIRCLE_CULL != 0));
+    // raster footprint's (so that variant is also the reference the culled frames are held to, bit for bit).  Only in the wide-binning
+    // (particle-light) instantiations.
+    constexpr bool kCircleCull = !STATS && WIDE_BIN;
     if constexpr (kCircleCull) {
         const bool finite_xy = (fabsf(P.shaded.x) <= 0x1p100f) && (fabsf(P.shaded.y) <= 0x1p100f);
         const float inf = __builtin_inff();
@@ -708,11 +663,7 @@ __global__ __launch_bounds__(kLightThreads) ILM_LIGHT_OCCUPANCY void sphere_ligh
     int part_bound = blend_fp16 ? 0x7FFFFFFF : (int)(((long long)light_count * (part + 1)) / kLightParts);   // first light of the next part
 
     for (int batch = light_lo, batch_step = kListCapacity; batch < light_hi; batch += batch_step) {
-#ifdef ILM_EXP_NO_BIN              // EXPERIMENT (timing of the prologue only): no light is looked at
-        int batch_n = 0;
-#else
         int batch_n = min(BIG ? 4096 : kListCapacity, light_hi - batch);
-#endif
         if constexpr (WIDE_BIN) {
         __syncthreads();                                        // the previous batch's list has been walked
         {
@@ -828,10 +779,10 @@ __global__ __launch_bounds__(kLightThreads) ILM_LIGHT_OCCUPANCY void sphere_ligh
             // pair code masked off -- the compiler only branches around blocks it finds long enough -- ~31 vector instructions per
             // list entry on the particle-light frame (the tile lists a light whose footprint misses this quadrant, and the cull's box
             // test did not catch it): 468 M -> 429 M vector instructions per launch, **0.979 -> 0.931 ms per frame**
-            // (profiles/r06_particle_lights_wave_skip_ab.txt).  On the sphere-light instantiations (ILM_WAVE_SKIP=2) it changes nothing
+            // (profiles/r06_particle_lights_wave_skip_ab.txt).  On the sphere-light instantiations it changes nothing
             // -- cfg3 0.625 / 0.625 -> 0.625 / 0.622, cfg5 8.691 / 8.695 -> 8.701 / 8.704 ms -- their lists are short and their lights
             // large: the branch is paid by every entry and almost never taken.
-            if ((WIDE_BIN ? (ILM_WAVE_SKIP >= 1) : (ILM_WAVE_SKIP >= 2)) && __builtin_amdgcn_ballot_w64(covered) == 0ull)
+            if (WIDE_BIN && __builtin_amdgcn_ballot_w64(covered) == 0ull)
                 continue;
             if (!covered)
                 continue;
@@ -864,9 +815,6 @@ __global__ __launch_bounds__(kLightThreads) ILM_LIGHT_OCCUPANCY void sphere_ligh
         // subtree's sums (device-scope stores, sc1: written through this XCD's L2), waits until the write is acknowledged, draws the
         // quadrant's ticket (device-scope atomic); the one that draws the last reads the K sums back with device-scope loads -- no cache
         // write-back or invalidate is involved, the light pass's L2 contents (the field's cells) stay where they are.
-#ifdef ILM_SPLIT_NO_COMBINE      // EXPERIMENT (timing only, wrong pixels): what the members cost without their meeting
-        goto tile_done;
-#endif
         // (scratch is indexed by the tile's place among the SPLIT block slots of the launch -- slot - taper[0] of this XCD -- not by the tile:
         // the untapered head of a launch needs none, api.hip plan_light_split sizes it so)
         const size_t split_slot = (size_t)(slot_end - kernargs().taper[0]) * 8u + (size_t)((int)blockIdx.x % 8);
@@ -916,16 +864,6 @@ __global__ __launch_bounds__(kLightThreads) ILM_LIGHT_OCCUPANCY void sphere_ligh
     }
 
 tile_done:
-#ifdef ILM_LIGHT_TRACE
-    if (lane == 0) {
-        const unsigned w = ((unsigned)blockIdx.x * (unsigned)(kLightThreads / 64) + (unsigned)wave) & 262143u;
-        unsigned hw_id, xcc_id;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));
-        g_light_trace[4 * w] = trace_t0; g_light_trace[4 * w + 1] = __builtin_amdgcn_s_memrealtime();
-        g_light_trace[4 * w + 2] = (unsigned long long)tile; g_light_trace[4 * w + 3] = ((unsigned long long)xcc_id << 32) | hw_id;
-    }
-#endif
     if (STATS) {
         // wave reduce, one atomic per wave and counter
         for (int off = 32; off > 0; off >>= 1) {
@@ -1260,14 +1198,8 @@ int light_block_slots(const LightLaunch& a) {
     const int rows = a.row_end - a.row_begin;
     if (rows <= 0 || a.width <= 0) return 0;
     const int tiles_x = (a.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
-    const int tile_count = tiles_x * tiles_y;
-    int blocks = ((tile_count + 7) / 8) * 8;
-    if (a.tile_map == 1) blocks = ((tiles_y + 7) / 8) * tiles_x * 8;   // every XCD gets ceil(rows / 8) rows' worth of blocks
-    if (a.tile_map == 4) {
-        const int M = a.tile_macro, groups = ((tiles_x + M - 1) / M) * ((tiles_y + M - 1) / M);
-        blocks = ((groups + 7) / 8) * 8 * M * M;
-    }
-    return blocks / 8;
+    const int M = a.tile_macro, groups = ((tiles_x + M - 1) / M) * ((tiles_y + M - 1) / M);
+    return ((groups + 7) / 8) * M * M;
 }
 
 // workgroups the tile kernel is launched with for `a` (split and taper as planned; what SQ_WAVES / 4 of the launch counts)

@@ -852,29 +852,18 @@ ILM_DEV UnitPlanes unit_planes(const float* chunk_base, int64_t stride, int firs
 // Cache policy bits of the plane accesses (buffer intrinsic aux word on gfx94x / gfx950: 1 = sc0, 2 = nt, 16 = sc1).
 // Stores of the cache-resident variant carry sc1: they write through the XCD's L2 instead of leaving dirty lines there.  Every L2 is
 // private to its XCD, so a kernel's release writes back whatever is still dirty before the next launch of the stream may start --
-// up to 8 x 4 MB after a cfg2 step, ~6 us during which nothing runs (per-wave timestamps, tools/step_trace_probe.py: the waves of a
+// up to 8 x 4 MB after a cfg2 step, ~6 us during which nothing runs (per-wave timestamps of an instrumented build: the waves of a
 // 16-chunk launch span 17.5 us, back-to-back launches took 24).  The written planes are read next by another launch, on whichever XCD,
 // after an invalidate: keeping them in this L2 buys nothing.  tools/step_ab.py: cfg2 without a spawner 20.3 -> 17.5 us per step, with
 // 23.4 -> 22.0 (21.0 -> 19.4 / 24.5 -> 23.5 on one stream); sc0, nt, nt + sc1 and non-temporal loads all lose on a resident working set.
-#ifndef ILM_LD_AUX
-#define ILM_LD_AUX 0
-#endif
-#ifndef ILM_ST_AUX
-#define ILM_ST_AUX 16
-#endif
-#ifndef ILM_LD_AUX_STREAM
-#define ILM_LD_AUX_STREAM 2
-#endif
-#ifndef ILM_ST_AUX_STREAM
-#define ILM_ST_AUX_STREAM 2
-#endif
+constexpr int kLdAux = 0, kStAux = 16, kLdAuxStream = 2, kStAuxStream = 2;
 template <bool STREAM>
 ILM_DEV float ld_plane(const UnitPlanes& u, int c, unsigned lane4) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(u.rsrc, (int)lane4, (int)u.so[c], STREAM ? ILM_LD_AUX_STREAM : ILM_LD_AUX));
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(u.rsrc, (int)lane4, (int)u.so[c], STREAM ? kLdAuxStream : kLdAux));
 }
 template <bool STREAM>
 ILM_DEV void st_plane(const UnitPlanes& u, int c, unsigned lane4, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), u.rsrc, (int)lane4, (int)u.so[c], STREAM ? ILM_ST_AUX_STREAM : ILM_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), u.rsrc, (int)lane4, (int)u.so[c], STREAM ? kStAuxStream : kStAux);
 }
 
 template <bool ATTR, bool STREAM>
@@ -1319,19 +1308,9 @@ typedef const LeanStep __attribute__((address_space(4))) CLeanStep;
 static_assert(sizeof(LeanStep) >= 0xc84 && sizeof(LeanStep) <= 0xcc0, "touch_kernarg_lines_lean reads one dword of each 64-byte line of LeanStep");
 
 
-#ifdef ILM_STEP_TRACE      // EXPERIMENT (tools/step_trace_probe.py): per-wave start / loaded / end times of the last launch, 100 MHz clock
-__device__ unsigned long long g_step_trace[5 * 131072];
-extern "C" int ilm_experiment_step_trace(unsigned long long* out, int n) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_step_trace), sizeof(unsigned long long) * (size_t)n);
-}
-#endif
 template <bool SPAWN, bool STREAM>
 __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep a_) {
     __shared__ uint32_t wave_live[kStepThreads / 64];
-#ifdef ILM_STEP_TRACE
-    const unsigned long long trace_t0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long trace_t1 = trace_t0, trace_t2 = trace_t0, trace_t3 = trace_t0;
-#endif
     const LeanStep& a = *(const LeanStep*)(CLeanStep*)__builtin_amdgcn_kernarg_segment_ptr();
     // (only the launch's first generation of blocks can be the first to read a line; for the others the loads would just load the
     // scalar cache: one lookup per line per wave)
@@ -1373,10 +1352,6 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
             float4 pos = mk4(cur.px, cur.py, cur.pz, cur.life);
             float4 vel = mk4(cur.vx, cur.vy, cur.vz, cur.ct);
             float4 attr = mk4(cur.ar, cur.ag, cur.ab, cur.aa);
-#ifdef ILM_STEP_TRACE
-            asm volatile("s_waitcnt vmcnt(0)");
-            trace_t1 = __builtin_amdgcn_s_memrealtime();
-#endif
             bool spawn_here = false, spawned = false;
             if constexpr (SPAWN) {
                 for (int s = 0; s < a.spawn_count; s++) {
@@ -1407,10 +1382,6 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
                         else
                             apply_fma(pos, vel, a.sys, a.op[o].fma, a.dop[o]);
                     }
-#ifdef ILM_STEP_TRACE
-                    asm volatile("" : "+v"(pos.x), "+v"(vel.x));
-                    trace_t2 = __builtin_amdgcn_s_memrealtime();
-#endif
                     if (pos.w <= 0.0f) {
                         pos = vel = zero;  // readStateOrDiscard: discard => cleared target
                     } else {
@@ -1423,10 +1394,6 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
             } else {
                 pos = vel = zero;
             }
-#ifdef ILM_STEP_TRACE
-            asm volatile("" : "+v"(pos.x), "+v"(rd.x), "+v"(rc.x));
-            trace_t3 = __builtin_amdgcn_s_memrealtime();
-#endif
             st_plane<STREAM>(up, 0, lane4, pos.x); st_plane<STREAM>(up, 1, lane4, pos.y); st_plane<STREAM>(up, 2, lane4, pos.z); st_plane<STREAM>(up, 3, lane4, pos.w);
             st_plane<STREAM>(up, 4, lane4, vel.x); st_plane<STREAM>(up, 5, lane4, vel.y); st_plane<STREAM>(up, 6, lane4, vel.z); st_plane<STREAM>(up, 7, lane4, vel.w);
             if constexpr (SPAWN) {
@@ -1439,13 +1406,6 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
             n_live = (uint32_t)__popcll(__ballot(pos.w > 0.0f));
         }
     }
-#ifdef ILM_STEP_TRACE
-    if (lane == 0) {
-        const unsigned w = (blockIdx.x * (kStepThreads / 64) + (unsigned)wave) & 131071u;
-        g_step_trace[5 * w] = trace_t0; g_step_trace[5 * w + 1] = trace_t1; g_step_trace[5 * w + 2] = __builtin_amdgcn_s_memrealtime();
-        g_step_trace[5 * w + 3] = trace_t2; g_step_trace[5 * w + 4] = trace_t3;
-    }
-#endif
     if (a.flags & ILM_STEP_COUNT_LIVE)
         publish_block_count(wave_live, n_live, lane, wave, v < a.total_units, a.first_chunk + (v >> a.upc_shift),
                             (v & ((1 << a.upc_shift) - 1)) / (kStepThreads / 64), (1 << a.upc_shift) / (kStepThreads / 64), a.count_buckets,
@@ -1824,7 +1784,9 @@ static bool build_lean_step(const StepLaunch& a, LeanStep& f) {
     const IlmStepDesc& d = a.desc;
     if (kUnitsPerWave != 1) return false;
     if (d.UpdateMode != ILM_UPDATE_POSITIONS && d.UpdateMode != ILM_UPDATE_WITH_DISTANCE_FIELD) return false;   // (the collision update: launch_lean_df_step adds the field)
-    if (a.derived.cs_shift < 6 || a.upc_shift < 0) return false;                   // power-of-two chunk size >= 64: no stride padding, a unit lies in one row
+    // power-of-two chunk size >= 64: no stride padding, a unit lies in one row, and units_per_chunk is a power of two >= 64, so every
+    // block size of the lean kernels (kStepThreads / 64 x K units, K <= 4) divides it
+    if (a.derived.cs_shift < 6 || a.upc_shift < 0) return false;
     if (a.slots != a.span) return false;
     if (a.derived.noise_may_revive != 0) return false;
     if (a.derived.update_bits & 1u) return false;                                   // life ramp
@@ -1898,15 +1860,12 @@ static bool build_lean_step(const StepLaunch& a, LeanStep& f) {
 static hipError_t launch_lean_step(const LeanStep& f, bool spawning, bool streaming, hipStream_t stream) {
     const int units_per_block = kStepThreads / 64;
     const dim3 grid((unsigned)((f.total_units + units_per_block - 1) / units_per_block), 1, 1), block(kStepThreads, 1, 1);
-    // experiment switch: resident waves per SIMD capped through dynamic LDS (blocks per CU); 0 = no cap
-    static const int occ = [] { const char* e = getenv("ILM_STEP_OCC"); return e ? atoi(e) : 0; }();
-    const unsigned lds = (occ > 0) ? (unsigned)(160 * 1024 / occ - 64) : 0u;
     if (spawning) {
-        if (streaming) hipLaunchKernelGGL((step_lean_kernel<true, true>), grid, block, lds, stream, f);
-        else hipLaunchKernelGGL((step_lean_kernel<true, false>), grid, block, lds, stream, f);
+        if (streaming) hipLaunchKernelGGL((step_lean_kernel<true, true>), grid, block, 0, stream, f);
+        else hipLaunchKernelGGL((step_lean_kernel<true, false>), grid, block, 0, stream, f);
     } else {
-        if (streaming) hipLaunchKernelGGL((step_lean_kernel<false, true>), grid, block, lds, stream, f);
-        else hipLaunchKernelGGL((step_lean_kernel<false, false>), grid, block, lds, stream, f);
+        if (streaming) hipLaunchKernelGGL((step_lean_kernel<false, true>), grid, block, 0, stream, f);
+        else hipLaunchKernelGGL((step_lean_kernel<false, false>), grid, block, 0, stream, f);
     }
     return hipGetLastError();
 }
@@ -1921,8 +1880,7 @@ static_assert((ILM_SDF_UNORM16 | ILM_SDF_FP16) == 1, "the format is bit 0 of the
 // inf / NaN (hi = inf gives NaN in the general form and in the oracle) and keeps the general sampler.  The uniforms whose fma(0, ., .)
 // terms the slice-0 form drops (Packed1.x, .z, TextureSliceAndTexelSize.xy) must be finite for the same reason.
 static bool field_is_slice0(const IlmDistanceFieldUniforms& df, int format) {
-    static const int enabled = [] { const char* e = getenv("ILM_DF_SLICE0"); return e ? atoi(e) : 1; }();
-    return enabled && (format == ILM_SDF_UNORM16) && (df.Packed1.y == 0.0f) && std::isfinite(df.Packed1.x) && std::isfinite(df.Packed1.z) &&
+    return (format == ILM_SDF_UNORM16) && (df.Packed1.y == 0.0f) && std::isfinite(df.Packed1.x) && std::isfinite(df.Packed1.z) &&
            std::isfinite(df.TextureSliceAndTexelSize.x) && std::isfinite(df.TextureSliceAndTexelSize.y);
 }
 // SdfView::cells0 from the atlas: cell (x0, yr) = channel r of the taps (x0, y0), (x1, y0), (x0, y1), (x1, y1) of a bilinear fetch whose
@@ -1969,8 +1927,7 @@ static hipError_t launch_lean_df_step(LeanStepDf& f, const StepLaunch& a, bool s
     const bool streaming = a.streaming != 0;
     int k = (forced_k == 1 || forced_k == 2 || forced_k == 4) ? forced_k : ((f.base.total_units >= 65536) ? 4 : 2);
     if (streaming) k = 4;
-    const int upb = (kStepThreads / 64) * k;                            // units per block
-    while (k > 1 && (a.units_per_chunk % ((kStepThreads / 64) * k)) != 0) k >>= 1;       // (units per chunk is a power of two >= 64: never taken)
+    const int upb = (kStepThreads / 64) * k;                            // units per block: divides units_per_chunk (build_lean_step)
     // the grid's bookkeeping for blocks of upb units (launch_step laid it out for blocks of kStepThreads / 64)
     f.base.total_padded = (f.base.total_units + upb - 1) / upb * upb;
     f.base.unit_rotate = f.base.unit_rotate / upb * upb;
@@ -2004,9 +1961,7 @@ static bool needs_extended_variant(const StepLaunch& a) {
 
 // Collision variants: six waves per SIMD (79 VGPRs, no scratch) 37.5-38.3 us on bench.py's collision row against 38.6-39.4 for the
 // allocator's own 86 VGPRs / five waves; seven (72 VGPRs, 24 B of scratch) 44.4, eight (64 VGPRs, 76 B) 55.2 (tools/ab_collision.sh)
-#ifndef ILM_DF_MINW
-#define ILM_DF_MINW 6
-#endif
+constexpr int kDfMinWaves = 6;
 template <bool SPAWN>
 static hipError_t launch_step_variant(const StepLaunch& a, hipStream_t stream) {
     const int units = a.unit_end - a.unit_begin;
@@ -2026,34 +1981,22 @@ static hipError_t launch_step_variant(const StepLaunch& a, hipStream_t stream) {
         }
         return hipGetLastError();
     }
-    static int minw = -1;
-    if (minw < 0) {
-        const char* e = getenv("ILM_STEP_MINWAVES");
-        minw = e ? atoi(e) : kDefaultStepMinWaves;
-    }
     const int units_per_block = (kStepThreads / 64) * kUnitsPerWave;
     const dim3 grid((unsigned)((units + units_per_block - 1) / units_per_block), 1, 1), block(kStepThreads, 1, 1);
     if (a.desc.UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD) {
-        // waves per SIMD requested for the collision variants (ILM_DF_MINW; measured in docs/experiments.md 3.1)
+        // waves per SIMD requested for the collision variants (kDfMinWaves; measured in docs/experiments.md 3.1)
         switch ((int)a.sdf.format | (field_is_slice0(a.desc.DistanceField, (int)a.sdf.format) ? kFieldSlice0 : 0)) {
-            case ILM_SDF_FP16: hipLaunchKernelGGL((step_kernel<ILM_SDF_FP16, true, SPAWN, ILM_DF_MINW>), grid, block, 0, stream, a); break;
-            case ILM_SDF_UNORM16: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, true, SPAWN, ILM_DF_MINW>), grid, block, 0, stream, a); break;
-            case ILM_SDF_FP16 | kFieldSlice0: hipLaunchKernelGGL((step_kernel<ILM_SDF_FP16 | kFieldSlice0, true, SPAWN, ILM_DF_MINW>), grid, block, 0, stream, a); break;
-            default: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16 | kFieldSlice0, true, SPAWN, ILM_DF_MINW>), grid, block, 0, stream, a); break;
+            case ILM_SDF_FP16: hipLaunchKernelGGL((step_kernel<ILM_SDF_FP16, true, SPAWN, kDfMinWaves>), grid, block, 0, stream, a); break;
+            case ILM_SDF_UNORM16: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, true, SPAWN, kDfMinWaves>), grid, block, 0, stream, a); break;
+            case ILM_SDF_FP16 | kFieldSlice0: hipLaunchKernelGGL((step_kernel<ILM_SDF_FP16 | kFieldSlice0, true, SPAWN, kDfMinWaves>), grid, block, 0, stream, a); break;
+            default: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16 | kFieldSlice0, true, SPAWN, kDfMinWaves>), grid, block, 0, stream, a); break;
         }
     } else if (a.streaming) {
         hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, false, SPAWN, 1, false, true>), grid, block, 0, stream, a);
-    } else if (SPAWN) {
+    } else {
         // (bounding this variant to 7 / 8 waves per SIMD -- 72 / 64 VGPRs with 8 / 24 bytes of scratch in the cold spawn path --
         // measured 3.5 % / 14 % SLOWER on cfg2: the step is VALU-issue-bound, not occupancy-bound; DESIGN.md "experiments")
         hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, false, SPAWN, 1>), grid, block, 0, stream, a);
-    } else {
-        switch (minw) {
-            case 8: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, false, false, 8>), grid, block, 0, stream, a); break;
-            case 7: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, false, false, 7>), grid, block, 0, stream, a); break;
-            case 6: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, false, false, 6>), grid, block, 0, stream, a); break;
-            default: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, false, false, 1>), grid, block, 0, stream, a); break;
-        }
     }
     return hipGetLastError();
 }

@@ -258,29 +258,12 @@ __global__ __launch_bounds__(1024) void raster_tile_scan_kernel(const RasterLaun
 // 8 x 8 quadrants of the tile; a ballot + prefix count per quadrant turns that into four slot-ordered index lists, and wave q then
 // walks only the sprites that can touch its quadrant (for 8 x 8-pixel sprites about a third of the tile's), the next record
 // already in flight while the current one is shaded.
-#ifdef ILM_RASTER_TRACE    // EXPERIMENT (tools/raster_trace_probe.py): per-workgroup start / end of the last launch (100 MHz clock), sprite count, segment
-__device__ unsigned long long g_raster_trace[4 * 131072];
-extern "C" int ilm_experiment_raster_trace(unsigned long long* out, int n) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_raster_trace), sizeof(unsigned long long) * (size_t)n);
-}
-#endif
 // Eight waves per SIMD (64 VGPRs, no scratch once only the next sprite's geometry is prefetched).  Per-workgroup timestamps
-// (-DILM_RASTER_TRACE, tools/raster_trace_probe.py) showed 4.7 workgroups per CU in flight at 78 VGPRs and the pass waiting on LDS /
+// (instrumentation since removed; see git history) showed 4.7 workgroups per CU in flight at 78 VGPRs and the pass waiting on LDS /
 // barriers rather than issuing: cfg2's frame 1.155 -> 1.062 ms (tools/ab_raster.sh).  Sprite records through scalar loads straight
 // from global memory instead of the LDS batch: 1.30 ms.
-#ifndef ILM_RASTER_WAVES
-#define ILM_RASTER_WAVES 8
-#endif
-#if ILM_RASTER_WAVES > 0
-#define ILM_RASTER_OCCUPANCY __attribute__((amdgpu_waves_per_eu(ILM_RASTER_WAVES, ILM_RASTER_WAVES)))
-#else
-#define ILM_RASTER_OCCUPANCY
-#endif
 template <int FORMAT>
-__global__ __launch_bounds__(256) ILM_RASTER_OCCUPANCY void raster_tiles_kernel(const RasterLaunch a) {
-#ifdef ILM_RASTER_TRACE
-    const unsigned long long trace_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void raster_tiles_kernel(const RasterLaunch a) {
     __shared__ Sprite batch[256];
     __shared__ uint8_t list[4][256];
     __shared__ int wave_count[4][4];          // [loader wave][quadrant]
@@ -429,13 +412,6 @@ __global__ __launch_bounds__(256) ILM_RASTER_OCCUPANCY void raster_tiles_kernel(
         for (int off = 32; off > 0; off >>= 1) shaded += __shfl_down(shaded, off);
         if ((lane == 0) && shaded != 0u) atomicAdd(&a.stats[2], (unsigned long long)shaded);
     }
-#ifdef ILM_RASTER_TRACE
-    if (tid == 0) {
-        const unsigned w = item & 131071u;
-        g_raster_trace[4 * w] = trace_t0; g_raster_trace[4 * w + 1] = __builtin_amdgcn_s_memrealtime();
-        g_raster_trace[4 * w + 2] = (unsigned long long)(end - begin); g_raster_trace[4 * w + 3] = ((unsigned long long)segments << 32) | segment;
-    }
-#endif
 }
 
 // crowded tiles: dst = C_j + T_j * dst for the segments j in order

@@ -89,7 +89,7 @@ def heavy_obstructions(k):
 def test_frames_in_flight_over_a_field_that_changes_every_frame(ctx, sfmt):
     """Seven frames, the field regenerated in front of each (on the owner's stream; first with a decoy set, then with the frame's own), the
     frames alternating between the owner and its sibling, no synchronisation anywhere until the end: frame k must be the frame a single
-    context renders after generating field k.  (Negative control: a build without the ordering, -DILM_EXP_NO_SHARED_ORDER, fails this.)"""
+    context renders after generating field k.  (Negative control: a build whose shared-resource ordering was switched off failed this.)"""
     layout, dfu, lights, w, h = heavy_scene()
     desc = scenes.render_desc(layout)
     triplets = list(range(0, layout.slice_count, 3))

@@ -251,7 +251,7 @@ def test_the_trace_follows_the_atlas_when_it_changes(ctx, oracle, sfmt):
 @pytest.mark.parametrize("width,height,rows", [(96, 96, None), (97, 95, None), (112, 208, None), (193, 97, None), (16, 16, None), (5, 3, None),
                                                 (300, 220, (32, 176)), (208, 400, (96, 112)), (1, 1, None)])
 def test_every_pixel_of_any_frame_size_is_rendered_once(ctx, oracle, width, height, rows):
-    """The light pass deals its 16 x 16 tiles to the XCDs in groups of 6 x 6 (lighting.hip, tile_map 4): frames whose tile counts are
+    """The light pass deals its 16 x 16 tiles to the XCDs in groups of 6 x 6 (lighting.hip sphere_lights_kernel): frames whose tile counts are
     multiples of the group edge, one more, one less, smaller than a group, and strips that begin and end inside a group.  A tile rendered
     twice would be harmless; one never rendered keeps the poison the lightmap is filled with."""
     lights = scenes.random_lights(width * 1000 + height, 5, width, height, z=(8.0, 48.0), radius=10.0, ramp=(60.0, 200.0))

@@ -1,4 +1,4 @@
-"""The light pass's block -> tile mapping (lighting.hip sphere_lights_kernel, tile_map 4; launch_sphere_lights_prepared sizes the grid):
+"""The light pass's block -> tile mapping (lighting.hip sphere_lights_kernel; launch_sphere_lights_prepared sizes the grid):
 square groups of M x M tiles dealt round-robin to the eight XCDs (block b runs on XCD b % 8).  The arithmetic restated here must send
 exactly one block to every tile of any frame -- the GPU test test_every_pixel_of_any_frame_size_is_rendered_once checks the kernel
 against the same property on the device."""
