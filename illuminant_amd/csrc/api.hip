@@ -333,6 +333,21 @@ SdfView make_sdf_view(const Sdf* f, const IlmDistanceFieldUniforms* df) {
     return v;
 }
 
+// Extent.xyz is the field's virtual size (DistanceField.cs: VirtualWidth / VirtualHeight / MaximumZ), never negative.  The sampler clamps a
+// position into [0, Extent] with one median-of-three and takes p - clamp as the distance to the volume: the restated min / max form
+// (DistanceFieldCommon.fxh:319-321) gives the same bits only for a finite Extent >= 0.  Every entry point that samples a field refuses
+// the others.
+static const char* field_extent_unusable(const IlmDistanceFieldUniforms* df, char* text, size_t n) {
+    if (!df) return nullptr;
+    const float e[3] = { df->Extent.x, df->Extent.y, df->Extent.z };
+    for (int k = 0; k < 3; k++) {
+        if (std::isfinite(e[k]) && e[k] >= 0.0f) continue;
+        snprintf(text, n, "the distance-field Extent.%c is %g: the field's extent must be finite and >= 0", "xyz"[k], (double)e[k]);
+        return text;
+    }
+    return nullptr;
+}
+
 // The uniforms of a light / probe pass must describe the atlas that is bound: columns x slice width = atlas width, rows x slice height
 // = atlas height (DistanceField ctor, SDF/DistanceField.cs:91-109; slice size = virtual size / InvScaleFactor, Uniforms.cs:108-109).  The
 // sampler wraps / clamps its taps into the real atlas whatever the uniforms say, but a frame traced through mismatched uniforms is
@@ -340,6 +355,7 @@ SdfView make_sdf_view(const Sdf* f, const IlmDistanceFieldUniforms* df) {
 // them) are not judged.
 const char* field_uniforms_mismatch(const Sdf* f, const IlmDistanceFieldUniforms* df, char* text, size_t n) {
     if (!f || !df) return nullptr;
+    if (field_extent_unusable(df, text, n)) return text;
     const double cols = df->TextureSliceCount.x, rows = df->TextureSliceCount.y;
     const double sw = (double)df->Extent.x / (double)df->ConeAndMisc.w, sh = (double)df->Extent.y / (double)df->StepAndMisc2.w;
     if (!(cols >= 1 && rows >= 1 && sw >= 1 && sh >= 1) || !std::isfinite(cols * sw) || !std::isfinite(rows * sh)) return nullptr;
@@ -650,6 +666,10 @@ int32_t validate_step(const System* s, const IlmStepDesc* d, int* first, int* co
     if (d->UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD && from_handle<Sdf>(s->sdf_handle, kMagicSdf) == nullptr)
         // ParticleSystem.cs:835-836
         return fail(ILM_ERR_STATE, "UpdateWithDistanceField requires a distance field (ilm_system_set_distance_field)");
+    if (d->UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD) {
+        char why[256];
+        if (field_extent_unusable(&d->DistanceField, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why);
+    }
     int f = d->FirstChunk, c = d->ChunkCount;
     if (c < 0) { f = 0; c = n; }
     if (f < 0 || f + c > n)
@@ -1935,6 +1955,7 @@ int32_t ilm_sdf_sample(IlmHandle h, const IlmDistanceFieldUniforms* df, const fl
     Sdf* f = from_handle<Sdf>(h, kMagicSdf);
     if (!f) return fail(ILM_ERR_INVALID_HANDLE, "not a distance field handle");
     if (!df || count < 0 || (count > 0 && (!positions || !out_distances))) return fail(ILM_ERR_INVALID_ARGUMENT, "bad arguments");
+    { char why[256]; if (field_extent_unusable(df, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
     if (count == 0) return ILM_OK;
     Ctx* c = f->ctx;
     HIP_TRY(hipSetDevice(c->device));
@@ -1973,6 +1994,7 @@ int32_t ilm_debug_sdf_sample_inside(IlmHandle h, const IlmDistanceFieldUniforms*
     Sdf* f = from_handle<Sdf>(h, kMagicSdf);
     if (!f) return fail(ILM_ERR_INVALID_HANDLE, "not a distance field handle");
     if (!df || count < 0 || (count > 0 && (!positions || !out_distances || !out_used_table))) return fail(ILM_ERR_INVALID_ARGUMENT, "bad arguments");
+    { char why[256]; if (field_extent_unusable(df, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
     if (count == 0) return ILM_OK;
     Ctx* c = f->ctx;
     HIP_TRY(hipSetDevice(c->device));

@@ -1907,7 +1907,14 @@ bool step_wants_slice0_cells(const IlmStepDesc& d, int format) {
     if (e && atoi(e) == 0) return false;
     const char* lean = getenv("ILM_DF_LEAN");
     if ((lean && atoi(lean) == 0) || step_interpreter_forced()) return false;
-    return d.UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD && format == ILM_SDF_UNORM16 && field_is_slice0(d.DistanceField, format);
+    if (!(d.UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD && format == ILM_SDF_UNORM16 && field_is_slice0(d.DistanceField, format))) return false;
+    // A cell row is yi + 1 with no clamp (hlsl_math.hpp), and the array has rows 0 .. height: only uniforms that keep every v in [0, 1]
+    // may use it.  cy is in [0, Extent.y] and fl(cy * TexelSize.w) is monotone in cy, so v <= fl(Extent.y * TexelSize.w) -- the product
+    // the device forms, in fp32 -- and -1 <= yi <= height - 1.  Any other uniforms (V past the atlas, a negative or non-finite texel
+    // size) take the four-tap form, which clamps V like the reference's sampler.
+    const float ey = d.DistanceField.Extent.y, tw = d.DistanceField.TextureSliceAndTexelSize.w;
+    const float v_max = ey * tw;
+    return std::isfinite(ey) && std::isfinite(tw) && std::isfinite(v_max) && ey >= 0.0f && tw >= 0.0f && v_max <= 1.0f;
 }
 
 // The lean collision step.  K = units per wave: the more units a wave walks, the fuller its long passes run -- and the longer it lives, so

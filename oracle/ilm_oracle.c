@@ -70,11 +70,21 @@ static inline f4 mul_point(f3 v, const IlmMatrix* M) {
 }
 
 static inline int wrap_index(float t, int size) {
-    /* D3D WRAP addressing of a POINT/LINEAR tap index */
-    int i = (int)t;
-    i %= size;
-    if (i < 0) i += size;
-    return i;
+    /* D3D WRAP addressing of a POINT/LINEAR tap index t (integer-valued: a floor).  Decided in double before any cast, so it is
+     * defined for every float: fmod of integer-valued doubles is exact, and for |t| < 2^31 this is (int)t % size folded positive.
+     * NaN / infinite t name no texel; tap 0 stands in (the sampler's weights are NaN there, so the tap is never seen). */
+    if (!isfinite(t)) return 0;
+    double r = fmod((double)t, (double)size);
+    if (r < 0.0) r += (double)size;
+    return (int)r;
+}
+
+/* D3D CLAMP addressing of a tap index t (integer-valued), decided in double before any cast: defined for every float */
+static inline int clamp_index(double t, int size) {
+    if (t != t) return 0;
+    if (t < 0.0) return 0;
+    if (t > (double)(size - 1)) return size - 1;
+    return (int)t;
 }
 
 /* IEEE half -> float */
@@ -666,10 +676,9 @@ static void sdf_sample_linear(const OrcTexture* t, float u, float v, float out[4
     float y = h_fma(v, (float)t->height, -0.5f);
     float x0f = floorf(x), y0f = floorf(y);
     float fx = x - x0f, fy = y - y0f;
-    int x0 = wrap_index(x0f, t->width), x1 = wrap_index(x0f + 1.0f, t->width);
-    int y0 = (int)y0f, y1 = (int)y0f + 1;
-    if (y0 < 0) y0 = 0; if (y0 > t->height - 1) y0 = t->height - 1;
-    if (y1 < 0) y1 = 0; if (y1 > t->height - 1) y1 = t->height - 1;
+    /* the second column is the integer x0 + 1 wrapped (x0f + 1.0f would round back onto x0f from 2^24 on) */
+    int x0 = wrap_index(x0f, t->width), x1 = (x0 + 1 == t->width) ? 0 : x0 + 1;
+    int y0 = clamp_index((double)y0f, t->height), y1 = clamp_index((double)y0f + 1.0, t->height);
     float t00[4], t10[4], t01[4], t11[4];
     sdf_texel(t, x0, y0, t00); sdf_texel(t, x1, y0, t10);
     sdf_texel(t, x0, y1, t01); sdf_texel(t, x1, y1, t11);

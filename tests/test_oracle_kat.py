@@ -8,6 +8,7 @@ substitute pin.  Runs without a GPU.
 """
 import ctypes as C
 import json
+import math
 import os
 import subprocess
 import sys
@@ -337,3 +338,102 @@ def test_oracle_is_test_infrastructure_only():
                 if "oracle" in text and ("import oracle" in text or "from oracle" in text or "ilm_oracle" in text or "libilm_oracle" in text):
                     bad.append(os.path.join(base, f))
     assert not bad, bad
+
+
+# ---- the oracle's distance-field sampler against a float64 restatement of LINEAR / U WRAP / V CLAMP ----------------------------
+
+def _sampler_kat_field():
+    """A 13 x 11 UNORM16 atlas whose channel r holds a distinct code per texel (row * 13 + column, 200 codes apart, all in the upper
+    half): a wrong row or column is an error of at least 0.003, never a rounding difference."""
+    w, h = 13, 11
+    codes = 32768 + 200 * np.arange(w * h, dtype=np.int64).reshape(h, w)
+    atlas = np.random.default_rng(17).integers(0, 65536, size=(h, w, 4), dtype=np.uint16)
+    atlas[..., 0] = codes.astype(np.uint16)
+    return atlas, codes
+
+
+def _sampler_kat_uniforms(texel_u, texel_v):
+    """Slice-0 uniforms that put the sampler's texture coordinate at (u, v) = (x * texel_u, y * texel_v) for any position inside a huge
+    extent: Packed1 = 0 (virtual slice 0, z weight 0), no slice offsets, Extent.w = 1 -- the result is DISTANCE_ZERO - r exactly."""
+    u = abi.DistanceFieldUniforms()
+    u.TextureSliceAndTexelSize = abi.f4(0.0, 0.0, texel_u, texel_v)
+    u.Extent = abi.f4(3e38, 3e38, 0.0, 1.0)
+    return u
+
+
+def _reference_tap(codes, u, v):
+    """D3D's LINEAR filter with U WRAP and V CLAMP (DistanceFieldCommon.fxh:273-281), in float64 and Python integers: texel centres at
+    +0.5, the tap origin floor(u * W - 0.5) -- the coordinate itself rounded once to fp32, as the sampler's fused multiply-add forms
+    it -- wrapped modulo W, clamped to [0, H - 1].  Returns (blended channel r, the four taps)."""
+    h, w = codes.shape
+    x = float(np.float32(u * w - 0.5))       # u * w - 0.5 is exact in float64 for the coordinates drawn below
+    y = float(np.float32(v * h - 0.5))
+    x0f, y0f = math.floor(x), math.floor(y)
+    fx, fy = x - x0f, y - y0f
+    x0, x1 = x0f % w, (x0f + 1) % w
+    y0, y1 = min(max(y0f, 0), h - 1), min(max(y0f + 1, 0), h - 1)
+    c = codes / 65535.0
+    top = (1.0 - fx) * c[y0, x0] + fx * c[y0, x1]
+    bot = (1.0 - fx) * c[y1, x0] + fx * c[y1, x1]
+    return (1.0 - fy) * top + fy * bot, (fx, fy, c[y0, x0])
+
+
+def _kat_coordinates(rng):
+    """(u, v) pairs: many U wraps both ways, V below 0 and above 1, and tap coordinates at and beyond 2^31 on both axes."""
+    w, h = 13, 11
+    us, vs = [], []
+    small_u = rng.uniform(-40.0, 40.0, 400).astype(np.float32)           # +-40 atlas widths: hundreds of wraps, negative U
+    small_v = rng.uniform(-3.0, 4.0, 400).astype(np.float32)             # V below 0, inside, above 1
+    us += list(small_u); vs += list(small_v)
+    # texel centres and texel edges: the tap origin and its neighbour exactly, on both sides of every wrap seam and clamp edge
+    for i in range(-2 * w, 2 * w + 1):
+        for j in (-3, -1, 0, 1, h - 1, h, h + 2):
+            us += [np.float32((i + 0.5) / w), np.float32(i / w)]
+            vs += [np.float32((j + 0.5) / h), np.float32(j / h)]
+    # at and beyond 2^31 texels: integer-valued coordinates with few significant bits, so u * W is exact in fp32
+    big = [2.0 ** 31, 2.0 ** 31 + 2.0 ** 16, 3.0 * 2.0 ** 31, 2.0 ** 32 - 2.0 ** 12, 2.0 ** 40, 12345.0 * 2.0 ** 30, 2.0 ** 53]
+    for b in big:
+        for s in (1.0, -1.0):
+            for k in (0.0, 1.0, 7.0):
+                us.append(np.float32(s * (b + k * 2.0 ** 20) / 2.0 ** 3)); vs.append(np.float32(rng.uniform(0.0, 1.0)))   # U only
+                us.append(np.float32(rng.uniform(0.0, 1.0))); vs.append(np.float32(s * (b + k * 2.0 ** 20) / 2.0 ** 3))   # V only
+        us.append(np.float32(b / 2.0 ** 3)); vs.append(np.float32(-b / 2.0 ** 3))
+    us += [np.float32(2.0 ** 31 / w), np.float32(-(2.0 ** 31) / w)]; vs += [np.float32(2.0 ** 31 / h), np.float32(-(2.0 ** 31) / h)]
+    return np.array(us, np.float32), np.array(vs, np.float32)
+
+
+def test_distance_field_sampler_wraps_u_and_clamps_v_for_every_coordinate(oracle):
+    """oracle.sample_distance_field's texture fetch against _reference_tap, written from the sampler state (LINEAR, U WRAP, V CLAMP)
+    and not from the oracle: the taps must be the exact texels for every coordinate -- hundreds of wraps, negative U, V outside
+    [0, 1], tap indices at and beyond 2^31, where a cast of the float to int is undefined -- and the blend within 1e-6."""
+    atlas, codes = _sampler_kat_field()
+    tex = oracle.make_texture(np.ascontiguousarray(atlas), abi.SDF_UNORM16)
+    zero = np.float32(192.0) / np.float32(255.0)                           # DISTANCE_ZERO (DistanceFieldCommon.fxh:8), correctly rounded
+    us, vs = _kat_coordinates(np.random.default_rng(23))
+    n_exact = n_huge = 0
+    for u, v in zip(us, vs):
+        # u = x * texel_u with x >= 0 inside the extent: a negative coordinate through a negative texel size, exactly
+        dfu = _sampler_kat_uniforms(-1.0 if u < 0 else 1.0, -1.0 if v < 0 else 1.0)
+        got = np.float32(oracle.sample_distance_field((abs(float(u)), abs(float(v)), 0.0), dfu, tex))
+        want, (fx, fy, c00) = _reference_tap(codes, float(u), float(v))
+        blended = float(zero) - float(got)
+        assert abs(blended - want) <= 1e-6 * abs(want), (u, v, blended, want)
+        if fx == 0.0 and fy == 0.0:
+            # the sample is the origin tap itself: bit for bit (the decode is code / 65535 rounded once)
+            assert got == np.float32(zero - np.float32(np.float32(c00 * 65535.0) / np.float32(65535.0))), (u, v, got)
+            n_exact += 1
+        n_huge += abs(float(u)) * 13 >= 2.0 ** 31 or abs(float(v)) * 11 >= 2.0 ** 31
+    assert n_exact > 300 and n_huge > 80, (n_exact, n_huge)
+
+
+def test_distance_field_sampler_gives_nan_for_nan_coordinates(oracle):
+    """A NaN or infinite texture coordinate (a NaN / infinite texel size, 0 x inf) names no texel: the sample is NaN, whatever tap the
+    index arithmetic falls on."""
+    atlas, _ = _sampler_kat_field()
+    tex = oracle.make_texture(np.ascontiguousarray(atlas), abi.SDF_UNORM16)
+    nan, inf = float("nan"), float("inf")
+    cases = [((5.0, 3.0), (nan, 1.0)), ((5.0, 3.0), (1.0, nan)), ((5.0, 3.0), (inf, 1.0)), ((5.0, 3.0), (1.0, -inf)),
+             ((0.0, 3.0), (inf, 1.0)), ((5.0, 0.0), (1.0, inf)), ((5.0, 3.0), (nan, nan)), ((2e38, 3.0), (1e30, 1.0))]
+    for (x, y), (tu, tv) in cases:
+        got = oracle.sample_distance_field((x, y, 0.0), _sampler_kat_uniforms(tu, tv), tex)
+        assert math.isnan(got), ((x, y), (tu, tv), got)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from illuminant_amd import abi, native, scenes
+from tests.util import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -228,3 +229,110 @@ def test_divisions_by_the_light_pass_constants_are_exact_for_every_numerator(ctx
     results = ctx.debug_divide_by_constants()
     assert [round(d, 4) for d, _, _ in results] == [0.15, 0.875]
     assert all(inside == 0 for _, inside, _ in results), results
+
+
+# ---- the general sampler at uniforms that do not describe the atlas ------------------------------------------------------------
+
+def _mismatched(case, packed1):
+    """The uniforms of a 128 x 72 single-slice field (atlas 128 x 72), changed so that the texture coordinate leaves [0, 1]."""
+    layout = scenes.DistanceFieldLayout(128, 72, 32.0, 3, 1.0)
+    u = layout.uniforms(packed1=packed1)
+    t = u.TextureSliceAndTexelSize
+    nan, inf = float("nan"), float("inf")
+    if case == "v_1.5":
+        t.w *= 1.5
+    elif case == "v_40":
+        t.w *= 40.0
+    elif case == "v_negative":
+        t.w = -t.w
+    elif case == "u_3.7":
+        t.z *= 3.7
+    elif case == "u_negative":
+        t.z *= -2.0
+    elif case == "z_zero":
+        u.Extent.z = 0.0
+    elif case == "huge":
+        u.Extent.x = u.Extent.y = u.Extent.z = 1e10
+    else:
+        comp, value = case.split("_")
+        setattr(t, comp, {"nan": nan, "inf": inf, "-inf": -inf}[value])
+    return u
+
+
+SAMPLE_CASES = ["v_1.5", "v_40", "v_negative", "u_3.7", "u_negative", "z_zero", "huge",
+                "z_nan", "w_nan", "z_inf", "w_inf", "z_-inf", "w_-inf"]
+
+
+def _edge_positions(extent, rng):
+    """Positions all over [-10 %, 110 %] of the extent, and on and just beyond each clamp boundary of each axis."""
+    n = 3000
+    ext = np.array(extent, np.float64)
+    pos = (rng.uniform(-0.1, 1.1, (n, 3)) * ext).astype(np.float32)
+    k = 0
+    for axis in range(3):
+        e = np.float32(ext[axis])
+        for b in (np.float32(0.0), np.float32(-0.0), np.nextafter(np.float32(0.0), np.float32(-1)), np.float32(-1e-3), np.float32(-1.0),
+                  e, np.nextafter(e, np.float32(0)), np.nextafter(e, np.float32(np.inf)), e + np.float32(1e-3) * max(e, 1), e + np.float32(1.0) * max(e, 1) / 100):
+            pos[k:k + 40, axis] = b
+            k += 40
+    return pos
+
+
+@pytest.mark.parametrize("fmt", [abi.SDF_UNORM16, abi.SDF_FP16])
+@pytest.mark.parametrize("packed1", [True, False])
+@pytest.mark.parametrize("case", SAMPLE_CASES)
+def test_uniforms_that_do_not_describe_the_atlas_match_the_oracle_bit_for_bit(ctx, oracle, fmt, packed1, case):
+    """ilm_sdf_sample passes the caller's uniforms to the kernel unjudged, and the reference defines the result for any of them:
+    LINEAR, U WRAP, V CLAMP on the real atlas.  V past 1 (x 1.5, x 40) and below 0, U past 1 and negative, a flat volume, a volume
+    of 1e10 with positions that far out, NaN / infinite texel sizes -- with the lighting path's Packed1 and with the particle path's
+    zero -- must all give the oracle's bits."""
+    rng = np.random.default_rng(SAMPLE_CASES.index(case) + 100 * fmt + 1000 * packed1)
+    atlas = rng.integers(0, 65536, size=(72, 128, 4), dtype=np.uint16)
+    if fmt == abi.SDF_FP16:
+        atlas = rng.uniform(0.0, 1.5, size=atlas.shape).astype(np.float16).view(np.uint16)
+    dfu = _mismatched(case, packed1)
+    sdf = native.DistanceFieldTexture(ctx, atlas, fmt)
+    pos = _edge_positions((dfu.Extent.x, dfu.Extent.y, dfu.Extent.z), rng)
+    got = sdf.sample(dfu, pos)
+    want = oracle_samples(oracle, pos, dfu, oracle.make_texture(atlas, fmt))
+    assert_bits_equal(got, want, "%s, packed1=%s, format %d" % (case, packed1, fmt))
+    if case in ("z_nan", "w_nan", "z_inf", "w_inf", "z_-inf", "w_-inf"):
+        assert np.isnan(got).any()           # (the texture coordinate is not finite for some positions: those samples are NaN)
+    sdf.close()
+
+
+@pytest.mark.parametrize("component", ["x", "y", "z"])
+@pytest.mark.parametrize("value", [-3.0, -0.5, float("nan"), float("inf"), float("-inf")])
+def test_an_extent_that_is_negative_or_not_finite_is_refused_by_every_sampling_entry_point(ctx, component, value):
+    """Extent.xyz is the field's virtual size.  The device clamps with one median-of-three and takes p - clamp as the distance to the
+    volume; the reference's min / max form gives the same only for a finite Extent >= 0 (p = 5, Extent = -3: 5 against 8).  The point
+    query, the in-volume diagnostic, the sphere lights, the light probes and the particle lights refuse every other Extent with
+    ILM_ERR_INVALID_ARGUMENT and say which component (the particle step: tests/test_sdf_uniform_edges_gpu.py)."""
+    from tests.lights_common import particle_light_params
+    layout = scenes.DistanceFieldLayout(128, 72, 32.0, 3, 1.0)
+    atlas = np.zeros((72, 128, 4), np.uint16)
+    sdf = native.DistanceFieldTexture(ctx, atlas)
+    dfu = layout.uniforms()
+    setattr(dfu.Extent, component, value)
+    pos = np.array([[5.0, 5.0, 5.0]], np.float32)
+    calls = {
+        "ilm_sdf_sample": lambda: sdf.sample(dfu, pos),
+        "ilm_debug_sdf_sample_inside": lambda: sdf.sample_inside(dfu, pos),
+    }
+    env = scenes.environment()
+    lights = scenes.random_lights(4, 2, 16, 8, z=(8.0, 16.0), radius=6.0, ramp=(30.0, 60.0))
+    lm = native.Lightmap(ctx, 16, 8)
+    eng = native.Engine(ctx, 64, scenes.randomness_table(7))
+    system = native.System(eng)
+    system.add_chunk()
+    system.upload(0, abi.PLANE_POSITION, scenes.make_particles(2, 64 * 64)[0])
+    probe = np.array([[5.0, 5.0, 5.0, 1.0]], np.float32), np.array([[0.0, 0.0, 1.0, 0.0]], np.float32)
+    calls["ilm_render_sphere_lights"] = lambda: native.render_sphere_lights(ctx, lights, env, dfu, None, sdf, (0, 0, 0, 0), lm)
+    calls["ilm_render_light_probes"] = lambda: native.render_light_probes(ctx, lights, probe[0], probe[1], env, dfu, sdf)
+    calls["ilm_render_particle_lights"] = lambda: native.render_particle_lights(ctx, system, particle_light_params(6.0, 30.0), env, dfu,
+                                                                                None, sdf, lm)
+    for name, call in calls.items():
+        with pytest.raises(native.IlluminantError) as e:
+            call()
+        assert e.value.code == abi.ERR_INVALID_ARGUMENT and ("Extent." + component) in str(e.value), (name, str(e.value))
+    system.close(); eng.close(); lm.close(); sdf.close()
