@@ -223,142 +223,209 @@ int32_t ensure_comms(Group* g) {
     return ILM_OK;
 }
 
-// In-place all-gather; see the header.  All work is stream-ordered on the members' context streams.
-int32_t all_gather(Group* g, void* const* buffers, size_t bytes, int gather, bool async = false) {
-    if (gather == ILM_GATHER_NONE || g->world == 1 || bytes == 0) return ILM_OK;
-    std::vector<hipEvent_t>& events = async ? g->xevents : g->events;
-    auto S = [&](size_t i) { return g->exchange_stream(i, async); };
-    if (gather == ILM_GATHER_PEER) {
-        if (g->rank_mode)
-            return api_fail(ILM_ERR_INVALID_ARGUMENT, "ILM_GATHER_PEER needs every member in this process; a group that spans processes gathers with RCCL");
-        const int n = g->n_local;
-        // 1. nobody may overwrite a slot that its owner's earlier work (the previous frame's consumers) still reads, and nobody's push may
-        //    start before the destination has finished the work queued before this call: every stream waits for every other's "here" event
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            HIP_TRY(hipEventRecord(events[(size_t)i], S((size_t)i)));
-        }
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            for (int j = 0; j < n; j++)
-                if (j != i) HIP_TRY(hipStreamWaitEvent(S((size_t)i), events[(size_t)j], 0));
-        }
-        // 2. member i pushes its slot to the n - 1 others on its own stream: on a full xGMI mesh that is one transfer per link
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            const size_t off = (size_t)(g->first_rank + i) * bytes;
-            for (int k = 1; k < n; k++) {
-                const int j = (i + k) % n;            // staggered destinations: no two members start on the same target
-                HIP_TRY(hipMemcpyPeerAsync(static_cast<char*>(buffers[j]) + off, g->devices[(size_t)j],
-                                           static_cast<const char*>(buffers[i]) + off, g->devices[(size_t)i], bytes, S((size_t)i)));
-            }
-            HIP_TRY(hipEventRecord(events[(size_t)i], S((size_t)i)));
-        }
-        // 3. a member's later work sees the whole frame: its stream waits for every push
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            for (int j = 0; j < n; j++)
-                if (j != i) HIP_TRY(hipStreamWaitEvent(S((size_t)i), events[(size_t)j], 0));
-        }
-        return ILM_OK;
-    }
-    if (gather != ILM_GATHER_RCCL) return api_fail(ILM_ERR_INVALID_ARGUMENT, "unknown gather mode %d", gather);
-    const int32_t rc = ensure_comms(g);
-    if (rc != ILM_OK) return rc;
-    Rccl& r = rccl();
-    NCCL_TRY(r.GroupStart());
-    for (int i = 0; i < g->n_local; i++) {
-        HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-        char* buf = static_cast<char*>(buffers[i]);
-        // in place: the send buffer is this rank's slot of the receive buffer
-        NCCL_TRY(r.AllGather(buf + (size_t)(g->first_rank + i) * bytes, buf, bytes, ncclInt8, g->comms[(size_t)i], S((size_t)i)));
-    }
-    NCCL_TRY(r.GroupEnd());
-    return ILM_OK;
-}
-
-// The exchange for strips of unequal size: rank r owns `bytes[r]` at `offset[r]` of every member's buffer and every other member needs
-// them.  Peer mode: as all_gather, every local member pushes its range to the others (one transfer per xGMI link).  RCCL: one group of
-// point-to-point transfers -- rank r sends its range to each of the world - 1 others and receives theirs in place; on the fully
-// connected xGMI mesh of one node that is again one transfer per link and direction, with no ring hop in between.
-int32_t exchange_ranges(Group* g, void* const* buffers, const std::vector<size_t>& offset, const std::vector<size_t>& bytes, int32_t gather, bool async = false) {
-    if (gather == ILM_GATHER_NONE || g->world == 1) return ILM_OK;
-    std::vector<hipEvent_t>& events = async ? g->xevents : g->events;
-    auto S = [&](size_t i) { return g->exchange_stream(i, async); };
-    if (gather == ILM_GATHER_PEER) {
-        if (g->rank_mode) return api_fail(ILM_ERR_STATE, "ILM_GATHER_PEER needs every member in this process: use ILM_GATHER_RCCL");
-        const int n = g->n_local;
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            HIP_TRY(hipEventRecord(events[(size_t)i], S((size_t)i)));
-        }
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            for (int j = 0; j < n; j++)
-                if (j != i) HIP_TRY(hipStreamWaitEvent(S((size_t)i), events[(size_t)j], 0));
-        }
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            const size_t off = offset[(size_t)(g->first_rank + i)], len = bytes[(size_t)(g->first_rank + i)];
-            for (int k = 1; k < n && len > 0; k++) {
-                const int j = (i + k) % n;
-                HIP_TRY(hipMemcpyPeerAsync(static_cast<char*>(buffers[j]) + off, g->devices[(size_t)j],
-                                           static_cast<const char*>(buffers[i]) + off, g->devices[(size_t)i], len, S((size_t)i)));
-            }
-            HIP_TRY(hipEventRecord(events[(size_t)i], S((size_t)i)));
-        }
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            for (int j = 0; j < n; j++)
-                if (j != i) HIP_TRY(hipStreamWaitEvent(S((size_t)i), events[(size_t)j], 0));
-        }
-        return ILM_OK;
-    }
-    if (gather != ILM_GATHER_RCCL) return api_fail(ILM_ERR_INVALID_ARGUMENT, "unknown gather mode %d", gather);
-    const int32_t rc = ensure_comms(g);
-    if (rc != ILM_OK) return rc;
-    Rccl& r = rccl();
-    NCCL_TRY(r.GroupStart());
-    for (int i = 0; i < g->n_local; i++) {
-        HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-        char* buf = static_cast<char*>(buffers[i]);
-        const int me = g->first_rank + i;
-        for (int k = 1; k < g->world; k++) {
-            const int to = (me + k) % g->world, from = (me - k + g->world) % g->world;      // staggered: no two ranks start on the same peer
-            if (bytes[(size_t)me] > 0) NCCL_TRY(r.Send(buf + offset[(size_t)me], bytes[(size_t)me], ncclInt8, to, g->comms[(size_t)i], S((size_t)i)));
-            if (bytes[(size_t)from] > 0) NCCL_TRY(r.Recv(buf + offset[(size_t)from], bytes[(size_t)from], ncclInt8, from, g->comms[(size_t)i], S((size_t)i)));
-        }
-    }
-    NCCL_TRY(r.GroupEnd());
-    return ILM_OK;
-}
-
-int32_t host_all_gather(Group* g, const void* local, void* out, size_t bytes);
-int32_t ensure_counts_scratch(Group* g, size_t total);
-
-// Every local member's stream waits for everything queued on every other member's stream so far (events; nothing blocks the host).
-// A group that spans processes has no common events: there the fence is an 8-byte in-place all-gather on the context streams -- a rank's
-// collective cannot complete before every rank has started its own, which its stream does only after the work queued in front of it.
-int32_t fence_members(Group* g) {
-    if (g->rank_mode) {
-        if (g->world < 2) return ILM_OK;
-        const int32_t rc = ensure_counts_scratch(g, 8u * (size_t)g->world);
-        if (rc != ILM_OK) return rc;
-        void* bufs[1] = { g->d_counts };
-        return all_gather(g, bufs, 8, ILM_GATHER_RCCL);
-    }
+// Every local member's stream waits for everything queued on every other member's stream so far: each records its event, then each
+// waits for the others' (nothing blocks the host).  The context streams with Group::events or, async, the exchange streams with theirs.
+int32_t fence(Group* g, bool async) {
     const int n = g->n_local;
     if (n < 2) return ILM_OK;
+    std::vector<hipEvent_t>& events = async ? g->xevents : g->events;
     for (int i = 0; i < n; i++) {
         HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-        HIP_TRY(hipEventRecord(g->events[(size_t)i], g->stream((size_t)i)));
+        HIP_TRY(hipEventRecord(events[(size_t)i], g->exchange_stream((size_t)i, async)));
     }
     for (int i = 0; i < n; i++) {
         HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
         for (int j = 0; j < n; j++)
-            if (j != i) HIP_TRY(hipStreamWaitEvent(g->stream((size_t)i), g->events[(size_t)j], 0));
+            if (j != i) HIP_TRY(hipStreamWaitEvent(g->exchange_stream((size_t)i, async), events[(size_t)j], 0));
     }
     return ILM_OK;
+}
+
+// every member's queued work has finished: its context stream and, once ILM_GATHER_ASYNC has made one, its exchange stream
+int32_t drain_members(Group* g) {
+    for (int i = 0; i < g->n_local; i++) {
+        const int32_t rc = ilm_ctx_sync(g->ctx[(size_t)i]);
+        if (rc != ILM_OK) return rc;
+        if ((size_t)i < g->xstream.size()) { HIP_TRY(hipSetDevice(g->devices[(size_t)i])); HIP_TRY(hipStreamSynchronize(g->xstream[(size_t)i])); }
+    }
+    return ILM_OK;
+}
+
+// An exchange: every rank of the world owns an ordered list of ranges that every other member needs.  Range::at[i] is the range's
+// address in local member i's memory -- the source on the member that owns it, the destination on every other.  Several transfers
+// between one pair of ranks match in this order, the same on both sides.
+struct Range { size_t bytes; std::vector<char*> at; };
+using Exchange = std::vector<std::vector<Range>>;        // [rank] -> that rank's ranges
+
+// rank r owns `bytes[r]` at `offset[r]` of every member's buffer
+Exchange buffer_ranges(const Group* g, void* const* buffers, const std::vector<size_t>& offset, const std::vector<size_t>& bytes) {
+    Exchange x((size_t)g->world);
+    for (int r = 0; r < g->world; r++) {
+        Range c = { bytes[(size_t)r], {} };
+        for (int i = 0; i < g->n_local; i++) c.at.push_back(static_cast<char*>(buffers[i]) + offset[(size_t)r]);
+        x[(size_t)r].push_back(c);
+    }
+    return x;
+}
+
+// Peer fan-out, every member in this process.  1. Nobody may overwrite a range that its owner's earlier work (the previous frame's
+// consumers) still reads, and nobody's push may start before the destination has finished the work queued before this call: a fence.
+// 2. Member i pushes each of its ranges to the n - 1 others on its own stream, destinations staggered so that no two members start on the
+// same target (on a full xGMI mesh: one transfer per link).  3. A member's later work sees every push: a fence.
+int32_t push_ranges(Group* g, const Exchange& x, bool async) {
+    const int n = g->n_local;
+    { const int32_t rc = fence(g, async); if (rc != ILM_OK) return rc; }
+    for (int i = 0; i < n; i++) {
+        HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
+        for (const Range& c : x[(size_t)(g->first_rank + i)])
+            for (int k = 1; k < n && c.bytes > 0; k++) {
+                const int j = (i + k) % n;
+                HIP_TRY(hipMemcpyPeerAsync(c.at[(size_t)j], g->devices[(size_t)j], c.at[(size_t)i], g->devices[(size_t)i], c.bytes,
+                                           g->exchange_stream((size_t)i, async)));
+            }
+    }
+    return fence(g, async);
+}
+
+// RCCL: one group of point-to-point transfers.  At step k every rank sends each of its ranges to rank (me + k) % world and receives each
+// of rank (me - k) % world's in place -- staggered, so no two ranks start on the same peer; on the fully connected xGMI mesh of one node
+// that is one transfer per link and direction, with no ring hop in between.
+int32_t send_recv_ranges(Group* g, const Exchange& x, bool async) {
+    { const int32_t rc = ensure_comms(g); if (rc != ILM_OK) return rc; }
+    Rccl& r = rccl();
+    const int world = g->world;
+    NCCL_TRY(r.GroupStart());
+    for (int i = 0; i < g->n_local; i++) {
+        HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
+        const int me = g->first_rank + i;
+        const hipStream_t s = g->exchange_stream((size_t)i, async);
+        for (int k = 1; k < world; k++) {
+            const int to = (me + k) % world, from = (me - k + world) % world;
+            for (const Range& c : x[(size_t)me])
+                if (c.bytes > 0) NCCL_TRY(r.Send(c.at[(size_t)i], c.bytes, ncclInt8, to, g->comms[(size_t)i], s));
+            for (const Range& c : x[(size_t)from])
+                if (c.bytes > 0) NCCL_TRY(r.Recv(c.at[(size_t)i], c.bytes, ncclInt8, from, g->comms[(size_t)i], s));
+        }
+    }
+    NCCL_TRY(r.GroupEnd());
+    return ILM_OK;
+}
+
+// How an exchange travels, decided before anything is queued: not at all (ILM_GATHER_NONE, or any mode in a group of one rank), by the
+// peer fan-out (every member in this process) or by RCCL.  The refusals keep the wording each entry point has always had.
+enum class Route { none, peer, rccl };
+struct Refusals { int32_t peer_code; const char* peer; const char* unknown; };
+const Refusals kAllGatherRefusals = { ILM_ERR_INVALID_ARGUMENT, "ILM_GATHER_PEER needs every member in this process; a group that spans processes gathers with RCCL",
+                                      "unknown gather mode %d" };
+const Refusals kRangeRefusals = { ILM_ERR_STATE, "ILM_GATHER_PEER needs every member in this process: use ILM_GATHER_RCCL", "unknown gather mode %d" };
+const Refusals kChunkRefusals = { ILM_ERR_STATE, kRangeRefusals.peer, "ilm_group_gather_chunks exchanges with ILM_GATHER_PEER or ILM_GATHER_RCCL (mode %d)" };
+
+int32_t route_of(const Group* g, int32_t gather, const Refusals& no, Route* out) {
+    *out = Route::none;
+    if (gather == ILM_GATHER_NONE || g->world == 1) return ILM_OK;
+    if (gather == ILM_GATHER_RCCL) *out = Route::rccl;
+    else if (gather != ILM_GATHER_PEER) return api_fail(ILM_ERR_INVALID_ARGUMENT, no.unknown, gather);
+    else if (g->rank_mode) return api_fail(no.peer_code, "%s", no.peer);
+    else *out = Route::peer;
+    return ILM_OK;
+}
+
+int32_t run_exchange(Group* g, const Exchange& x, Route route, bool async) {
+    if (route == Route::peer) return push_ranges(g, x, async);
+    if (route == Route::rccl) return send_recv_ranges(g, x, async);
+    return ILM_OK;
+}
+
+// In-place all-gather; see the header.  All work is stream-ordered on the members' context streams (async: their exchange streams).
+// RCCL gathers with ncclAllGather, the send buffer being this rank's slot of the receive buffer.
+int32_t all_gather(Group* g, void* const* buffers, size_t bytes, int gather, bool async = false) {
+    if (bytes == 0) return ILM_OK;
+    Route route;
+    { const int32_t rc = route_of(g, gather, kAllGatherRefusals, &route); if (rc != ILM_OK) return rc; }
+    if (route == Route::peer) {
+        std::vector<size_t> offset((size_t)g->world), len((size_t)g->world, bytes);
+        for (int r = 0; r < g->world; r++) offset[(size_t)r] = (size_t)r * bytes;
+        return push_ranges(g, buffer_ranges(g, buffers, offset, len), async);
+    }
+    if (route == Route::none) return ILM_OK;
+    { const int32_t rc = ensure_comms(g); if (rc != ILM_OK) return rc; }
+    Rccl& r = rccl();
+    NCCL_TRY(r.GroupStart());
+    for (int i = 0; i < g->n_local; i++) {
+        HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
+        char* buf = static_cast<char*>(buffers[i]);
+        NCCL_TRY(r.AllGather(buf + (size_t)(g->first_rank + i) * bytes, buf, bytes, ncclInt8, g->comms[(size_t)i], g->exchange_stream((size_t)i, async)));
+    }
+    NCCL_TRY(r.GroupEnd());
+    return ILM_OK;
+}
+
+// The exchange for strips of unequal size: rank r owns `bytes[r]` at `offset[r]` of every member's buffer and every other member needs them.
+int32_t exchange_ranges(Group* g, void* const* buffers, const std::vector<size_t>& offset, const std::vector<size_t>& bytes, int32_t gather, bool async = false) {
+    Route route;
+    const int32_t rc = route_of(g, gather, kRangeRefusals, &route);
+    if (rc != ILM_OK || route == Route::none) return rc;
+    return run_exchange(g, buffer_ranges(g, buffers, offset, bytes), route, async);
+}
+
+// device scratch of the small collectives (member 0's device)
+int32_t ensure_counts_scratch(Group* g, size_t total) {
+    HIP_TRY(hipSetDevice(g->devices[0]));
+    if (total > g->counts_bytes) {
+        if (g->d_counts) { HIP_TRY(hipStreamSynchronize(g->stream((size_t)0))); HIP_TRY(hipFree(g->d_counts)); g->d_counts = nullptr; g->counts_bytes = 0; }
+        const size_t cap = total < 4096 ? 4096 : total;
+        HIP_TRY(hipMalloc(&g->d_counts, cap));
+        g->counts_bytes = cap;
+    }
+    return ILM_OK;
+}
+
+// Small host payloads (liveness counters, timings): rank r's `bytes` land at out + r * bytes on every process.  Members of this
+// process are copied; a group that spans processes stages its slot in device memory and all-gathers it with RCCL.  Synchronises.
+int32_t host_all_gather(Group* g, const void* local, void* out, size_t bytes) {
+    if (bytes == 0) return ILM_OK;
+    char* o = static_cast<char*>(out);
+    const size_t mine = (size_t)g->first_rank * bytes;
+    if (o + mine != local) memmove(o + mine, local, bytes * (size_t)g->n_local);
+    if (!(g->rank_mode && g->world > 1)) return ILM_OK;
+    const size_t total = bytes * (size_t)g->world;
+    { const int32_t rc = ensure_counts_scratch(g, total); if (rc != ILM_OK) return rc; }
+    char* d = static_cast<char*>(g->d_counts);
+    HIP_TRY(hipMemcpyAsync(d + mine, o + mine, bytes, hipMemcpyHostToDevice, g->stream((size_t)0)));
+    void* bufs[1] = { g->d_counts };
+    const int32_t rc = all_gather(g, bufs, bytes, ILM_GATHER_RCCL);
+    if (rc != ILM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(o, d, total, hipMemcpyDeviceToHost, g->stream((size_t)0)));
+    HIP_TRY(hipStreamSynchronize(g->stream((size_t)0)));
+    return ILM_OK;
+}
+
+// The cross-rank verdict: every rank puts in one word and learns every rank's (`all`, when asked) and the lowest rank whose word differs
+// from `expect` (`differs`, -1 if none).  A group that spans processes at world size > 1 all-gathers the words (8 bytes per rank);
+// elsewhere there is one caller for every member and nothing to exchange.  With a constant word it is a barrier.
+int32_t verdict(Group* g, uint64_t word, uint64_t expect = 0, int* differs = nullptr, std::vector<uint64_t>* all = nullptr) {
+    std::vector<uint64_t> words((size_t)g->world, word);
+    if (g->rank_mode && g->world > 1) {
+        const int32_t rc = host_all_gather(g, &words[(size_t)g->first_rank], words.data(), sizeof(uint64_t));
+        if (rc != ILM_OK) return rc;
+    }
+    if (differs) *differs = -1;
+    for (int r = 0; r < g->world && differs && *differs < 0; r++)
+        if (words[(size_t)r] != expect) *differs = r;
+    if (all) all->swap(words);
+    return ILM_OK;
+}
+
+// Every local member's stream waits for everything queued on every other member's stream so far (fence).  A group that spans processes
+// has no common events: there the fence is an 8-byte in-place all-gather on the context streams -- a rank's collective cannot complete
+// before every rank has started its own, which its stream does only after the work queued in front of it.
+int32_t fence_members(Group* g) {
+    if (!g->rank_mode) return fence(g, false);
+    if (g->world < 2) return ILM_OK;
+    const int32_t rc = ensure_counts_scratch(g, 8u * (size_t)g->world);
+    if (rc != ILM_OK) return rc;
+    void* bufs[1] = { g->d_counts };
+    return all_gather(g, bufs, 8, ILM_GATHER_RCCL);
 }
 
 // Proof that every mapping made by hipIpcOpenMemHandle addresses the buffer it was exported for (a collective, once per group lightmap,
@@ -374,7 +441,6 @@ int32_t prove_ipc_mappings(GroupLightmap* m, const std::vector<void*>& peers) {
     char* own = static_cast<char*>(m->buffers[0]);
     const size_t at[2] = { 0, (bytes - span) & ~(size_t)15 };             // (16-byte stores: aligned)
     std::vector<unsigned char> saved(2 * span), seen(2 * span);
-    uint64_t token = 0; std::vector<uint64_t> all((size_t)world, 0);
     // From here to the last collective a LOCAL failure (a copy, a memset, the stamping kernel) never returns: it folds into this rank's
     // verdict word and the rank keeps walking the same three all-gathers as the others -- a rank that left early would pair its next
     // collective with the wrong one of its peers and hang them.
@@ -384,32 +450,27 @@ int32_t prove_ipc_mappings(GroupLightmap* m, const std::vector<void*>& peers) {
     for (int k = 0; k < 2; k++) soft(hipMemcpy(saved.data() + (size_t)k * span, own + at[k], span, hipMemcpyDeviceToHost));
     const bool have_saved = ok != 0;
     for (int k = 0; k < 2 && ok; k++) soft(hipMemset(own + at[k], 0, span));
-    { const int32_t rc = host_all_gather(g, &token, all.data(), sizeof(uint64_t)); if (rc != ILM_OK) return rc; }      // everybody's slots are blank
+    { const int32_t rc = verdict(g, 0); if (rc != ILM_OK) return rc; }      // everybody's slots are blank
     const uint32_t serial = ++g->ipc_proofs;
     const uint32_t stamp[4] = { 0x494c4d00u, serial, (uint32_t)me, ~serial ^ (uint32_t)me };
     for (void* p : peers)
         for (int k = 0; k < 2 && ok; k++)
             soft(launch_stamp16(static_cast<char*>(p) + at[k] + 16u * (size_t)me, stamp, g->stream(0)));
     soft(hipStreamSynchronize(g->stream(0)));
-    { const int32_t rc = host_all_gather(g, &token, all.data(), sizeof(uint64_t)); if (rc != ILM_OK) return rc; }      // everybody has stamped
+    { const int32_t rc = verdict(g, 0); if (rc != ILM_OK) return rc; }      // everybody has stamped
     for (int k = 0; k < 2 && ok; k++) soft(hipMemcpy(seen.data() + (size_t)k * span, own + at[k], span, hipMemcpyDeviceToHost));
-    int missing = -1;
     for (int k = 0; k < 2 && ok; k++)
         for (int r = 0; r < world; r++) {
-            if (r == me) continue;
             const uint32_t want[4] = { 0x494c4d00u, serial, (uint32_t)r, ~serial ^ (uint32_t)r };
-            if (memcmp(seen.data() + (size_t)k * span + 16u * (size_t)r, want, 16) != 0 && missing < 0) missing = r;
+            if (r != me && memcmp(seen.data() + (size_t)k * span + 16u * (size_t)r, want, 16) != 0) ok = 0;
         }
-    if (missing >= 0) ok = 0;
-    std::vector<uint64_t> verdicts((size_t)world, 0);
-    verdicts[(size_t)me] = ok;
-    { const int32_t rc = host_all_gather(g, &verdicts[(size_t)me], verdicts.data(), sizeof(uint64_t)); if (rc != ILM_OK) return rc; }
+    int failed = -1;
+    { const int32_t rc = verdict(g, ok, 1, &failed); if (rc != ILM_OK) return rc; }
     if (have_saved)
         for (int k = 0; k < 2; k++)
             if (hipMemcpy(own + at[k], saved.data() + (size_t)k * span, span, hipMemcpyHostToDevice) != hipSuccess) (void)hipGetLastError();
-    for (int r = 0; r < world; r++)
-        if (!verdicts[(size_t)r])
-            return api_fail(ILM_ERR_STATE, "ILM_GATHER_STORE: the IPC mappings do not address the ranks' lightmaps (rank %d did not find every other rank's stamp in its buffer): no rank arms the mode", r);
+    if (failed >= 0)
+        return api_fail(ILM_ERR_STATE, "ILM_GATHER_STORE: the IPC mappings do not address the ranks' lightmaps (rank %d did not find every other rank's stamp in its buffer): no rank arms the mode", failed);
     return ILM_OK;
 }
 
@@ -432,8 +493,7 @@ int32_t set_store_mode(GroupLightmap* m, bool enable) {
             int32_t rc = lightmap_set_mirrors(m->lightmaps[0], nullptr, 0);          // (drains this rank's stream: its stores into the others are done)
             m->store_mode = false;                                                   // (the mappings stay: see below)
             // nobody frees a buffer another rank may still be storing into: all ranks have drained when this returns
-            uint64_t token = 0; std::vector<uint64_t> all((size_t)world, 0);
-            const int32_t rb = host_all_gather(g, &token, all.data(), sizeof(uint64_t));
+            const int32_t rb = verdict(g, 0);
             return rc != ILM_OK ? rc : rb;
         }
         // The mappings are made ONCE per group lightmap (the buffers never move) and live until the GROUP is destroyed: re-arming reuses
@@ -443,15 +503,14 @@ int32_t set_store_mode(GroupLightmap* m, bool enable) {
         // faulted) -- deterministic with bench.py's second lit frame, gone with no unmap in between.
         static_assert(sizeof(hipIpcMemHandle_t) == 64, "the handle travels as 64 bytes");
         const bool mapped = world > 1 && m->ipc_peers.size() == (size_t)(world - 1);
-        std::vector<hipIpcMemHandle_t> handles((size_t)world);
-        hipIpcMemHandle_t mine;
         uint64_t ok = 1;
         std::vector<void*> peers = m->ipc_peers;
         if (world > 1 && !mapped) {
             peers.clear();
+            std::vector<hipIpcMemHandle_t> handles((size_t)world);
+            hipIpcMemHandle_t& mine = handles[(size_t)me];
             if (hipIpcGetMemHandle(&mine, m->buffers[0]) != hipSuccess) { (void)hipGetLastError(); ok = 0; memset(&mine, 0, sizeof(mine)); }
-            handles[(size_t)me] = mine;
-            const int32_t rc = host_all_gather(g, &handles[(size_t)me], handles.data(), sizeof(hipIpcMemHandle_t));
+            const int32_t rc = host_all_gather(g, &mine, handles.data(), sizeof(hipIpcMemHandle_t));
             if (rc != ILM_OK) return rc;
             for (int r = 0; r < world && ok; r++) {
                 if (r == me) continue;
@@ -460,36 +519,29 @@ int32_t set_store_mode(GroupLightmap* m, bool enable) {
                 peers.push_back(p);
             }
         }
-        // every rank learns whether every rank could map every buffer
-        std::vector<uint64_t> verdicts((size_t)world, 0);
-        verdicts[(size_t)me] = ok;
-        if (world > 1) {
-            const int32_t rc = host_all_gather(g, &verdicts[(size_t)me], verdicts.data(), sizeof(uint64_t));
-            if (rc != ILM_OK) { if (!mapped) for (void* p : peers) g->ipc_retired.push_back(p); return rc; }
-        }
+        // every rank learns whether every rank could map every buffer; from here every failure leaves through the one exit below
         int failed = -1;
-        for (int r = 0; r < world; r++) if (!verdicts[(size_t)r] && failed < 0) failed = r;
-        if (failed >= 0) {
-            if (!mapped) for (void* p : peers) g->ipc_retired.push_back(p);
-            return api_fail(ILM_ERR_STATE, "ILM_GATHER_STORE: rank %d could not map the other ranks' lightmaps through IPC handles: no rank arms the mode", failed);
-        }
-        if (!mapped && world > 1) {
+        int32_t rc = verdict(g, ok, 1, &failed);
+        if (rc == ILM_OK && failed >= 0)
+            rc = api_fail(ILM_ERR_STATE, "ILM_GATHER_STORE: rank %d could not map the other ranks' lightmaps through IPC handles: no rank arms the mode", failed);
+        if (rc == ILM_OK && !mapped && world > 1) {
             // NEGATIVE CONTROL of the proof below (tests/test_two_ranks_one_gpu.py): rank 0's first mapping addresses memory of its own
-            if (ok && me == 0 && !peers.empty() && getenv("ILM_EXP_IPC_BOGUS_MAPPING")) {
+            if (me == 0 && !peers.empty() && getenv("ILM_EXP_IPC_BOGUS_MAPPING")) {
                 void* elsewhere = nullptr;
                 if (hipMalloc(&elsewhere, m->row_bytes * (size_t)m->slot_rows * (size_t)world) == hipSuccess) {
                     g->ipc_retired.push_back(peers[0]); g->ipc_decoys.push_back(elsewhere); peers[0] = elsewhere;
                 }
             }
-            const int32_t rc = prove_ipc_mappings(m, peers);
-            if (rc != ILM_OK) {
+            rc = prove_ipc_mappings(m, peers);
+        }
+        if (rc == ILM_OK) rc = lightmap_set_mirrors(m->lightmaps[0], peers.data(), (int)peers.size());
+        if (rc != ILM_OK) {
+            // the mappings this call made are retired, not unmapped (see above); a decoy of the negative control is no mapping
+            if (!mapped)
                 for (void* p : peers)
                     if (std::find(g->ipc_decoys.begin(), g->ipc_decoys.end(), p) == g->ipc_decoys.end()) g->ipc_retired.push_back(p);
-                return rc;
-            }
+            return rc;
         }
-        const int32_t rc = lightmap_set_mirrors(m->lightmaps[0], peers.data(), (int)peers.size());
-        if (rc != ILM_OK) { if (!mapped) for (void* p : peers) g->ipc_retired.push_back(p); return rc; }
         m->ipc_peers = peers;
         m->store_mode = true;
         return ILM_OK;
@@ -615,60 +667,34 @@ int32_t wait_lightmap_exchange(GroupLightmap* m) {
     return ILM_OK;
 }
 
-// device scratch of the small collectives (member 0's device)
-int32_t ensure_counts_scratch(Group* g, size_t total) {
-    HIP_TRY(hipSetDevice(g->devices[0]));
-    if (total > g->counts_bytes) {
-        if (g->d_counts) { HIP_TRY(hipStreamSynchronize(g->stream((size_t)0))); HIP_TRY(hipFree(g->d_counts)); g->d_counts = nullptr; g->counts_bytes = 0; }
-        const size_t cap = total < 4096 ? 4096 : total;
-        HIP_TRY(hipMalloc(&g->d_counts, cap));
-        g->counts_bytes = cap;
-    }
-    return ILM_OK;
-}
-
-// Small host payloads (liveness counters, timings): rank r's `bytes` land at out + r * bytes on every process.  Members of this
-// process are copied; a group that spans processes stages its slot in device memory and all-gathers it with RCCL.  Synchronises.
-int32_t host_all_gather(Group* g, const void* local, void* out, size_t bytes) {
-    if (bytes == 0) return ILM_OK;
-    char* o = static_cast<char*>(out);
-    const size_t mine = (size_t)g->first_rank * bytes;
-    if (o + mine != local) memmove(o + mine, local, bytes * (size_t)g->n_local);
-    if (!(g->rank_mode && g->world > 1)) return ILM_OK;
-    const size_t total = bytes * (size_t)g->world;
-    { const int32_t rc = ensure_counts_scratch(g, total); if (rc != ILM_OK) return rc; }
-    char* d = static_cast<char*>(g->d_counts);
-    HIP_TRY(hipMemcpyAsync(d + mine, o + mine, bytes, hipMemcpyHostToDevice, g->stream((size_t)0)));
-    void* bufs[1] = { g->d_counts };
-    const int32_t rc = all_gather(g, bufs, bytes, ILM_GATHER_RCCL);
+// rank `rank`'s system holds exactly the chunks it owns of a table of `total_chunks`: chunk c lives on rank c % world
+int32_t owned_chunks(const Group* g, int rank, IlmHandle system, int total_chunks, int* out_owned) {
+    const int owned = (total_chunks - rank + g->world - 1) / g->world;
+    int32_t have = 0;
+    const int32_t rc = ilm_system_chunk_count(system, &have);
     if (rc != ILM_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(o, d, total, hipMemcpyDeviceToHost, g->stream((size_t)0)));
-    HIP_TRY(hipStreamSynchronize(g->stream((size_t)0)));
+    if (have != owned)
+        return api_fail(ILM_ERR_STATE, "rank %d holds %d chunks but owns %d of a table of %d (chunk c lives on rank c %% %d)", rank, have, owned, total_chunks, g->world);
+    *out_owned = owned;
     return ILM_OK;
 }
-
 
 // ilm_group_gather_chunks: the sharded particle state made whole.  Chunk c of the table lives on rank c % world as chunk c / world of
 // that member's source system; afterwards chunk c of every member's `gathered` system holds `count` consecutive component planes of it.
 // The planes of a chunk are contiguous (count * stride floats), so a chunk travels as ONE range straight from the owner's planes into
-// the destination's planes -- no pack, no unpack.  Peer mode: the owner pushes to the n - 1 others (one transfer per xGMI link and
-// chunk).  RCCL: one group of ncclSend / ncclRecv, rank r sends each of its chunks to every other rank and receives theirs in place,
-// peers staggered as in exchange_ranges; several transfers between one pair match in issue order (chunk order on both sides).
-struct ChunkRange { char* base; size_t bytes; };
+// the destination's planes -- no pack, no unpack: rank r's ranges are its chunks in table order.
 int32_t gather_chunks(Group* g, const IlmHandle* sources, const IlmHandle* gathered, int total_chunks, int first, int count, int32_t gather) {
     const int world = g->world, n = g->n_local;
     if (total_chunks == 0) return ILM_OK;
-    // every local member's view of its own chunks and of the whole table, validated before anything is queued
-    std::vector<std::vector<ChunkRange>> src((size_t)n), dst((size_t)n);
+    // every local member's view of its own chunks and of the whole table, and the mode, checked before anything is queued or marked
+    std::vector<std::vector<char*>> src((size_t)n), dst((size_t)n);
     int64_t stride0 = 0; int32_t size0 = 0;
     for (int i = 0; i < n; i++) {
         const int rank = g->first_rank + i;
-        const int owned = (total_chunks - rank + world - 1) / world;
-        int32_t have = 0;
-        int32_t rc = ilm_system_chunk_count(sources[i], &have);
+        int owned = 0;
+        int32_t rc = owned_chunks(g, rank, sources[i], total_chunks, &owned);
         if (rc != ILM_OK) return rc;
-        if (have != owned)
-            return api_fail(ILM_ERR_STATE, "rank %d holds %d chunks but owns %d of a table of %d (chunk c lives on rank c %% %d)", rank, have, owned, total_chunks, world);
+        int32_t have = 0;
         rc = ilm_system_chunk_count(gathered[i], &have);
         if (rc != ILM_OK) return rc;
         if (have != total_chunks)
@@ -678,77 +704,67 @@ int32_t gather_chunks(Group* g, const IlmHandle* sources, const IlmHandle* gathe
             const int chunks = pass ? total_chunks : owned;
             for (int k = 0; k < chunks; k++) {
                 float* base = nullptr; int64_t stride = 0; int32_t size = 0; IlmHandle ctx = 0;
-                rc = system_chunk_view(sys, k, pass != 0, &base, &stride, &size, &ctx);
+                rc = system_chunk_view(sys, k, false, &base, &stride, &size, &ctx);
                 if (rc != ILM_OK) return rc;
                 if (ctx != g->ctx[(size_t)i])
                     return api_fail(ILM_ERR_INVALID_ARGUMENT, "the %s system of member %d lives on another context than the member's", pass ? "gathered" : "source", i);
                 if (stride0 == 0) { stride0 = stride; size0 = size; }
                 if (stride != stride0 || size != size0)
                     return api_fail(ILM_ERR_INVALID_ARGUMENT, "the systems' engines differ in chunk size (%d / %d): one chunk geometry per table", size, size0);
-                ChunkRange r = { reinterpret_cast<char*>(base + (int64_t)first * stride), sizeof(float) * (size_t)count * (size_t)stride };
-                (pass ? dst : src)[(size_t)i].push_back(r);
+                (pass ? dst : src)[(size_t)i].push_back(reinterpret_cast<char*>(base + (int64_t)first * stride));
             }
         }
     }
-    auto S = [&](size_t i) { return g->stream(i); };
+    Route route;
+    { const int32_t rc = route_of(g, gather, kChunkRefusals, &route); if (rc != ILM_OK) return rc; }
+    if (route == Route::rccl) { const int32_t rc = ensure_comms(g); if (rc != ILM_OK) return rc; }
+    // every check has passed: the gathered chunks are written from here on (their high-water marks go to the top)
+    for (int i = 0; i < n; i++)
+        for (int c = 0; c < total_chunks; c++) (void)system_chunk_view(gathered[i], c, true, nullptr, nullptr, nullptr, nullptr);
+    const size_t bytes = sizeof(float) * (size_t)count * (size_t)stride0;
     // a member's own chunks: device-local copies into its gathered system
     for (int i = 0; i < n; i++) {
         HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
         const int rank = g->first_rank + i;
         for (size_t k = 0; k < src[(size_t)i].size(); k++) {
-            const ChunkRange& from = src[(size_t)i][k]; const ChunkRange& to = dst[(size_t)i][k * (size_t)world + (size_t)rank];
-            if (to.base != from.base) HIP_TRY(hipMemcpyAsync(to.base, from.base, from.bytes, hipMemcpyDeviceToDevice, S((size_t)i)));
+            char* to = dst[(size_t)i][k * (size_t)world + (size_t)rank];
+            if (to != src[(size_t)i][k]) HIP_TRY(hipMemcpyAsync(to, src[(size_t)i][k], bytes, hipMemcpyDeviceToDevice, g->stream((size_t)i)));
         }
     }
-    if (gather == ILM_GATHER_NONE || world == 1) return ILM_OK;
-    if (gather == ILM_GATHER_PEER) {
-        if (g->rank_mode) return api_fail(ILM_ERR_STATE, "ILM_GATHER_PEER needs every member in this process: use ILM_GATHER_RCCL");
-        // as all_gather: nobody pushes into a member before the work that member queued earlier (readers of the old table) is done
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            HIP_TRY(hipEventRecord(g->events[(size_t)i], S((size_t)i)));
-        }
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            for (int j = 0; j < n; j++)
-                if (j != i) HIP_TRY(hipStreamWaitEvent(S((size_t)i), g->events[(size_t)j], 0));
-        }
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            for (size_t k = 0; k < src[(size_t)i].size(); k++)
-                for (int step = 1; step < n; step++) {
-                    const int j = (i + step) % n;
-                    const ChunkRange& from = src[(size_t)i][k]; const ChunkRange& to = dst[(size_t)j][k * (size_t)world + (size_t)(g->first_rank + i)];
-                    HIP_TRY(hipMemcpyPeerAsync(to.base, g->devices[(size_t)j], from.base, g->devices[(size_t)i], from.bytes, S((size_t)i)));
-                }
-            HIP_TRY(hipEventRecord(g->events[(size_t)i], S((size_t)i)));
-        }
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-            for (int j = 0; j < n; j++)
-                if (j != i) HIP_TRY(hipStreamWaitEvent(S((size_t)i), g->events[(size_t)j], 0));
-        }
-        return ILM_OK;
+    if (route == Route::none) return ILM_OK;
+    Exchange x((size_t)world);
+    for (int c = 0; c < total_chunks; c++) {
+        Range range = { bytes, std::vector<char*>((size_t)n) };
+        for (int i = 0; i < n; i++)
+            range.at[(size_t)i] = g->first_rank + i == c % world ? src[(size_t)i][(size_t)(c / world)] : dst[(size_t)i][(size_t)c];
+        x[(size_t)(c % world)].push_back(range);
     }
-    if (gather != ILM_GATHER_RCCL) return api_fail(ILM_ERR_INVALID_ARGUMENT, "ilm_group_gather_chunks exchanges with ILM_GATHER_PEER or ILM_GATHER_RCCL (mode %d)", gather);
-    const int32_t rc = ensure_comms(g);
-    if (rc != ILM_OK) return rc;
-    Rccl& r = rccl();
-    NCCL_TRY(r.GroupStart());
-    for (int i = 0; i < n; i++) {
-        HIP_TRY(hipSetDevice(g->devices[(size_t)i]));
-        const int me = g->first_rank + i;
-        for (int step = 1; step < world; step++) {
-            const int to = (me + step) % world, from = (me - step + world) % world;
-            for (const ChunkRange& c : src[(size_t)i]) NCCL_TRY(r.Send(c.base, c.bytes, ncclInt8, to, g->comms[(size_t)i], S((size_t)i)));
-            const int theirs = (total_chunks - from + world - 1) / world;
-            for (int k = 0; k < theirs; k++) {
-                const ChunkRange& c = dst[(size_t)i][(size_t)k * (size_t)world + (size_t)from];
-                NCCL_TRY(r.Recv(c.base, c.bytes, ncclInt8, from, g->comms[(size_t)i], S((size_t)i)));
-            }
+    return run_exchange(g, x, route, false);
+}
+
+// No chunk holds this many particles (chunk_size <= 4096, ilm_engine_create: at most 2^24 slots), so a rank's slot of the liveness table
+// filled with it says "this rank failed" (ilm_group_live_counts).
+constexpr uint32_t kFailedSlot = 0xFFFFFFFFu;
+static_assert(4096ull * 4096ull < kFailedSlot, "a live count never equals the failure marker");
+
+// this process's part of ilm_group_live_counts: every local member's counts into its rank's slot of `table` (rank-major, per_rank words each)
+int32_t local_live_counts(Group* g, const IlmHandle* systems, int total_chunks, const uint32_t* out_counts, int capacity, int saturate16,
+                          std::vector<uint32_t>& table, int per_rank) {
+    if (!systems || (!out_counts && total_chunks > 0)) return api_fail(ILM_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (total_chunks < 0 || capacity < total_chunks) return api_fail(ILM_ERR_OUT_OF_RANGE, "capacity %d < chunk count %d", capacity, total_chunks);
+    if (per_rank == 0) return ILM_OK;
+    std::vector<uint32_t> local((size_t)per_rank, 0u);
+    for (int i = 0; i < g->n_local; i++) {
+        const int rank = g->first_rank + i;
+        int owned = 0;
+        int32_t rc = owned_chunks(g, rank, systems[i], total_chunks, &owned);
+        if (rc != ILM_OK) return rc;
+        if (owned > 0) {
+            rc = ilm_system_step_counts(systems[i], local.data(), per_rank, saturate16);
+            if (rc != ILM_OK) return rc;
+            memcpy(&table[(size_t)rank * (size_t)per_rank], local.data(), sizeof(uint32_t) * (size_t)owned);
         }
     }
-    NCCL_TRY(r.GroupEnd());
     return ILM_OK;
 }
 
@@ -862,12 +878,7 @@ int32_t ilm_group_ctx(IlmHandle h, int32_t local_index, IlmHandle* out_ctx) {
 int32_t ilm_group_sync(IlmHandle h) {
     Group* g = group_from(h);
     if (!g) return api_fail(ILM_ERR_INVALID_HANDLE, "not a group handle");
-    for (int i = 0; i < g->n_local; i++) {
-        const int32_t rc = ilm_ctx_sync(g->ctx[(size_t)i]);
-        if (rc != ILM_OK) return rc;
-        if ((size_t)i < g->xstream.size()) { HIP_TRY(hipSetDevice(g->devices[(size_t)i])); HIP_TRY(hipStreamSynchronize(g->xstream[(size_t)i])); }
-    }
-    return ILM_OK;
+    return drain_members(g);
 }
 
 int32_t ilm_group_all_gather(IlmHandle h, void* const* buffers, uint64_t bytes_per_rank, int32_t gather) {
@@ -888,12 +899,8 @@ int32_t ilm_group_host_all_gather(IlmHandle h, const void* local, void* out_all,
     if (bytes_per_rank > (1u << 20)) return api_fail(ILM_ERR_OUT_OF_RANGE, "host payloads are small (<= 1 MiB per rank): use ilm_group_all_gather for device buffers");
     // every member's queued work is finished first: the call doubles as the barrier between timed regions (the exchange streams of
     // ILM_GATHER_ASYNC included: one communicator never has two operations in flight on two streams)
-    for (int i = 0; i < g->n_local; i++) {
-        const int32_t rc = ilm_ctx_sync(g->ctx[(size_t)i]);
-        if (rc != ILM_OK) return rc;
-        if ((size_t)i < g->xstream.size()) { HIP_TRY(hipSetDevice(g->devices[(size_t)i])); HIP_TRY(hipStreamSynchronize(g->xstream[(size_t)i])); }
-    }
-    return host_all_gather(g, local, out_all, (size_t)bytes_per_rank);
+    const int32_t rc = drain_members(g);
+    return rc != ILM_OK ? rc : host_all_gather(g, local, out_all, (size_t)bytes_per_rank);
 }
 
 int32_t ilm_group_lightmap_create(IlmHandle h, int32_t width, int32_t height, int32_t format, IlmHandle* out) {
@@ -1019,20 +1026,13 @@ int32_t ilm_group_lightmap_set_strips(IlmHandle h, const int32_t* row_begins, co
         for (int r = 0; r < world; r++)
             for (const int v : { row_begins[r], row_ends[r] })
                 for (int b = 0; b < 4; b++) { hash ^= (uint64_t)((v >> (8 * b)) & 0xFF); hash *= 1099511628211ull; }
-    int disagree = -1, invalid_rank = valid ? -1 : g->first_rank;
-    if (g->rank_mode && world > 1) {
-        std::vector<uint64_t> all((size_t)world, 0);
-        all[(size_t)g->first_rank] = hash;
-        const int32_t rc = host_all_gather(g, &all[(size_t)g->first_rank], all.data(), sizeof(uint64_t));
-        if (rc != ILM_OK) return rc;
-        for (int r = 0; r < world; r++) {
-            if (all[(size_t)r] == kTableInvalid && invalid_rank < 0) invalid_rank = r;
-            if (all[(size_t)r] != hash && disagree < 0) disagree = r;
-        }
-    }
+    int disagree = -1;
+    std::vector<uint64_t> all;
+    { const int32_t rc = verdict(g, hash, hash, &disagree, &all); if (rc != ILM_OK) return rc; }
+    const int invalid_rank = (int)(std::find(all.begin(), all.end(), (uint64_t)kTableInvalid) - all.begin());
     // 3. all ranks reach the same verdict from the same gathered words; a failed installation leaves every rank's table as it was
     if (!valid) return api_fail(ILM_ERR_INVALID_ARGUMENT, "%s", why);
-    if (invalid_rank >= 0) return api_fail(ILM_ERR_STATE, "rank %d was handed a malformed strip table: no rank installs one", invalid_rank);
+    if (invalid_rank < world) return api_fail(ILM_ERR_STATE, "rank %d was handed a malformed strip table: no rank installs one", invalid_rank);
     if (disagree >= 0)
         return api_fail(ILM_ERR_STATE, "rank %d installed a different strip table than rank %d: every rank must pass the same strips", disagree, g->first_rank);
     bool equal = true;
@@ -1119,33 +1119,26 @@ int32_t ilm_group_live_counts(IlmHandle hgroup, const IlmHandle* systems, int32_
     ILM_TRACE_RANGE("ilm_group_live_counts");
     Group* g = group_from(hgroup);
     if (!g) return api_fail(ILM_ERR_INVALID_HANDLE, "not a group handle");
-    if (!systems || (!out_counts && total_chunks > 0)) return api_fail(ILM_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (total_chunks < 0 || capacity < total_chunks) return api_fail(ILM_ERR_OUT_OF_RANGE, "capacity %d < chunk count %d", capacity, total_chunks);
     const int world = g->world;
-    const int per_rank = (total_chunks + world - 1) / world;
-    if (per_rank == 0) return ILM_OK;
+    const int per_rank = total_chunks > 0 ? (total_chunks + world - 1) / world : 0;
     // this process's slots of the table, rank-major: slot (r, k) = chunk k * world + r
     std::vector<uint32_t> table((size_t)world * (size_t)per_rank, 0u);
-    std::vector<uint32_t> local((size_t)per_rank, 0u);
-    for (int i = 0; i < g->n_local; i++) {
-        const int rank = g->first_rank + i;
-        const int owned = (total_chunks - rank + world - 1) / world;          // chunks c < total with c % world == rank
-        int32_t have = 0;
-        int32_t rc = ilm_system_chunk_count(systems[i], &have);
+    const int32_t rc = local_live_counts(g, systems, total_chunks, out_counts, capacity, saturate16, table, per_rank);
+    if (per_rank == 0 || !(g->rank_mode && world > 1)) {
         if (rc != ILM_OK) return rc;
-        if (have != owned)
-            return api_fail(ILM_ERR_STATE, "rank %d holds %d chunks but owns %d of a table of %d (chunk c lives on rank c %% %d)", rank, have, owned,
-                            total_chunks, world);
-        if (owned > 0) {
-            rc = ilm_system_step_counts(systems[i], local.data(), per_rank, saturate16);
-            if (rc != ILM_OK) return rc;
-            memcpy(&table[(size_t)rank * (size_t)per_rank], local.data(), sizeof(uint32_t) * (size_t)owned);
-        }
-    }
-    if (g->rank_mode && world > 1) {
-        // the one exchange of the particle path: world * per_rank counters through RCCL
-        const int32_t rc = host_all_gather(g, &table[(size_t)g->first_rank * (size_t)per_rank], table.data(), sizeof(uint32_t) * (size_t)per_rank);
-        if (rc != ILM_OK) return rc;
+    } else {
+        // the one exchange of the particle path: world * per_rank counters through RCCL.  A rank whose own part failed still takes part, its
+        // slot filled with kFailedSlot -- leaving early would leave its peers in the all-gather -- and every rank fails: this
+        // one with its own error, the others naming the lowest failing rank.
+        uint32_t* mine = &table[(size_t)g->first_rank * (size_t)per_rank];
+        char why[512] = "";
+        if (rc != ILM_OK) { snprintf(why, sizeof(why), "%s", ilm_last_error()); std::fill(mine, mine + per_rank, kFailedSlot); }
+        const int32_t rg = host_all_gather(g, mine, table.data(), sizeof(uint32_t) * (size_t)per_rank);
+        if (rc != ILM_OK) return api_fail(rc, "%s", why);
+        if (rg != ILM_OK) return rg;
+        for (int r = 0; r < world; r++)
+            if (table[(size_t)r * (size_t)per_rank] == kFailedSlot)
+                return api_fail(ILM_ERR_STATE, "rank %d could not count the live particles of its chunks: no rank returns a liveness table", r);
     }
     for (int c = 0; c < total_chunks; c++)
         out_counts[c] = table[(size_t)(c % world) * (size_t)per_rank + (size_t)(c / world)];

@@ -162,6 +162,20 @@ def main():
             k = sysm.add_chunk()
             sysm.upload(k, abi.PLANE_POSITION, pos); sysm.upload(k, abi.PLANE_VELOCITY, vel); sysm.upload(k, abi.PLANE_ATTRIBUTES, attr)
     sysm.step(d)
+    # a rank whose own part fails still takes part in the table's all-gather: every rank raises -- that rank with its own error, the others
+    # with ERR_STATE naming it -- and the valid call below is paired as before.  The failing rank is the last one that owns a chunk (at
+    # world 8 the last ranks own none of the 5): its system holds the right chunks but has never run a counting step.
+    bad = min(world, total_chunks) - 1
+    idle = native.System(eng)
+    for _ in (range(rank, total_chunks, world) if rank == bad else ()):
+        idle.add_chunk()
+    try:
+        g.live_counts([idle if rank == bad else sysm], total_chunks)
+        raise SystemExit("rank %d: a liveness table was returned although rank %d failed" % (rank, bad))
+    except native.IlluminantError as refusal:
+        assert refusal.code == abi.ERR_STATE, refusal
+        assert ("no step with ILM_STEP_COUNT_LIVE" if rank == bad else "rank %d could not count" % bad) in str(refusal), refusal
+    idle.close()
     counts = g.live_counts([sysm], total_chunks)
     mine = sysm.step_counts()
     for i, ch in enumerate(range(rank, total_chunks, world)):

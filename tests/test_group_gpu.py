@@ -542,6 +542,7 @@ def test_gather_chunks_lights_every_strip_with_every_ranks_particles(ctx, member
             gathered[r].add_chunk()
     sdfs = [native.DistanceFieldTexture(c, atlas) for c in g.contexts]
     glm = native.GroupLightmap(g, w, h, abi.LIGHTMAP_FLOAT4)
+    fresh = []
     try:
         g.gather_chunks(sources, gathered, n_chunks, 0, 4, gather)          # Pos+Life
         g.gather_chunks(sources, gathered, n_chunks, 12, 4, gather)         # RenderColor
@@ -568,9 +569,23 @@ def test_gather_chunks_lights_every_strip_with_every_ranks_particles(ctx, member
                 g.gather_chunks(sources, sources, n_chunks, 0, 4, gather)
         with pytest.raises(native.IlluminantError):
             g.gather_chunks(sources, gathered, n_chunks, 18, 4, gather)
+        if members > 1:
+            # a gather mode that does not exist is refused before anything is queued: gathered systems whose planes still differ from the
+            # sources (fresh zero chunks) stay as they were on every member
+            fresh = [native.System(e) for e in engines]
+            for s_ in fresh:
+                for _ in range(n_chunks):
+                    s_.add_chunk()
+            with pytest.raises(native.IlluminantError) as refusal:
+                g.gather_chunks(sources, fresh, n_chunks, 0, 4, 7)
+            assert refusal.value.code == abi.ERR_INVALID_ARGUMENT
+            g.sync()
+            for i in range(members):
+                for c in range(n_chunks):
+                    assert not fresh[i].download(c, abi.PLANE_POSITION).any(), "member %d, chunk %d" % (i, c)
     finally:
         g.sync()
         glm.close()
-        for x in sdfs + sources + gathered + engines:
+        for x in sdfs + sources + gathered + fresh + engines:
             x.close()
         g.close()
