@@ -609,6 +609,41 @@ int32_t refresh_table(System* s) {
     return ILM_OK;
 }
 
+// randomCustom (POINT, WRAP) indexes the randomness table with wrap_index_fast, exact only for |tap| < 2^23 (hlsl_math.hpp).  A tap is
+// an offset plus a coordinate below 65533, so offsets with |offset| < 2^22 keep it there; the reference draws them in [0, 253) x
+// [0, 127) (Transforms.cs:260-264, ParticleSpawner.cs).  The others -- NaN and infinity included -- are refused.
+static bool randomness_offset_unusable(const float off[2], const char* owner, int k, const char* what, char* text, size_t n) {
+    for (int a = 0; a < 2; a++) {
+        if (std::fabs(off[a]) < 4194304.0f) continue;
+        snprintf(text, n, "%s %d: %s.%c is %g, outside (-2^22, 2^22)", owner, k, what, "xy"[a], (double)off[a]);
+        return true;
+    }
+    return false;
+}
+
+// The position-constant index of the inline and position-buffer spawners (Spawn_Stage1, SpawnerCommon.fxh:138-156).  In the reference
+// .w is TotalSpawned % count, an integer in [0, count), or with a polygon rate (TotalSpawned / rate) % count, a float in [0, count)
+// (ParticleSpawner.cs:361-373); PositionConstantCount is the number of positions, an integer.  Any other .w, count or a non-finite
+// PolygonRate would index before or past the positions (or truncate a fractional count where HLSL's % does not): refused.
+static bool position_index_unusable(const IlmSpawnParams& p, int k, char* text, size_t n) {
+    const float w = p.ChunkSizeAndIndices[3], count = p.PositionConstantCount, rate = p.PolygonRate;
+    if (!std::isfinite(rate)) {
+        snprintf(text, n, "spawn record %d: PolygonRate %g is not finite", k, (double)rate);
+        return true;
+    }
+    if (count != std::floor(count)) {
+        snprintf(text, n, "spawn record %d: PositionConstantCount %g is not an integer", k, (double)count);
+        return true;
+    }
+    const bool polygon = rate > 0.05f;
+    if (!(w >= 0.0f && w < count) || (!polygon && w != std::floor(w))) {
+        snprintf(text, n, "spawn record %d: ChunkSizeAndIndices.w %g is not %s in [0, PositionConstantCount = %g)", k, (double)w,
+                 polygon ? "a number" : "an integer", (double)count);
+        return true;
+    }
+    return false;
+}
+
 int32_t validate_step(const System* s, const IlmStepDesc* d, int* first, int* count) {
     const int n = (int)s->chunks.size();
     if (d->OpCount < 0 || d->OpCount > ILM_MAX_OPS)
@@ -623,7 +658,12 @@ int32_t validate_step(const System* s, const IlmStepDesc* d, int* first, int* co
             // Transforms.cs:348-349: "Maximum number of attractors per instance is 16"
             if (op.u.Gravity.AttractorCount > ILM_MAX_ATTRACTORS || op.u.Gravity.AttractorCount < 0)
                 return fail(ILM_ERR_TOO_MANY, "Maximum number of attractors per instance is %d", ILM_MAX_ATTRACTORS);
-        } else if (op.Type != ILM_OP_NOISE && op.Type != ILM_OP_FMA && op.Type != ILM_OP_MATRIX_MULTIPLY && op.Type != ILM_OP_SPATIAL_NOISE) {
+        } else if (op.Type == ILM_OP_NOISE) {
+            char why[256];
+            if (randomness_offset_unusable(op.u.Noise.RandomnessOffset, "op", o, "RandomnessOffset", why, sizeof(why)) ||
+                randomness_offset_unusable(op.u.Noise.NextRandomnessOffset, "op", o, "NextRandomnessOffset", why, sizeof(why)))
+                return fail(ILM_ERR_OUT_OF_RANGE, "%s", why);
+        } else if (op.Type != ILM_OP_FMA && op.Type != ILM_OP_MATRIX_MULTIPLY && op.Type != ILM_OP_SPATIAL_NOISE) {
             return fail(ILM_ERR_INVALID_ARGUMENT, "unknown transform type %d", op.Type);
         }
     }
@@ -662,6 +702,11 @@ int32_t validate_step(const System* s, const IlmStepDesc* d, int* first, int* co
             (r.Params.PositionConstantCount < 1.0f || r.Params.PositionConstantCount > (float)ILM_MAX_INLINE_POSITION_CONSTANTS))
             return fail(ILM_ERR_OUT_OF_RANGE, "PositionConstantCount %g outside [1, %d]", (double)r.Params.PositionConstantCount,
                         ILM_MAX_INLINE_POSITION_CONSTANTS);
+        char why[256];
+        if (randomness_offset_unusable(r.Params.RandomnessOffset, "spawn record", k, "RandomnessOffset", why, sizeof(why)))
+            return fail(ILM_ERR_OUT_OF_RANGE, "%s", why);
+        if ((r.Kind == ILM_SPAWN_INLINE || r.Kind == ILM_SPAWN_POSITION_BUFFER) && position_index_unusable(r.Params, k, why, sizeof(why)))
+            return fail(ILM_ERR_OUT_OF_RANGE, "%s", why);
     }
     if (d->UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD && from_handle<Sdf>(s->sdf_handle, kMagicSdf) == nullptr)
         // ParticleSystem.cs:835-836

@@ -62,9 +62,9 @@ ILM_DEV float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 ILM_DEV float len3_fast(f3 a) { return fast_sqrt(dot3(a, a)); }
 ILM_DEV f3 norm3_fast(f3 a) { const float r = fast_rsq(dot3(a, a)); return mk3(a.x * r, a.y * r, a.z * r); }
 
-// positive modulo of an integer-valued float without integer division.  Domain: |t| < 2^23, which the
-// callers guarantee (randomness-table coordinates are bounded by the table offsets a*253, b*127 and the
-// per-index offsets < 65531).  q may be off by one after the reciprocal multiply; the remainder t - q*size is
+// positive modulo of an integer-valued float without integer division.  Domain: |t| < 2^23, which the callers guarantee:
+// randomness-table coordinates are the offsets (|offset| < 2^22, validate_step refuses the others) plus the per-index offsets
+// < 65533 or Noise's slot coordinate times the texel size; the spawner's position index takes it only below 2^23 (spawn_stage1).  q may be off by one after the reciprocal multiply; the remainder t - q*size is
 // exact in fp32 and is folded back into [0, size), so the result equals the integer modulo bit for bit.
 ILM_DEV int wrap_index_fast(float t, int size) {
 #pragma clang fp contract(off)
@@ -84,8 +84,30 @@ ILM_DEV float pow_pos(float x, float y) { return (y == 0.0f) ? 1.0f : __builtin_
 // sign(d) * m for m >= 0 (HLSL sign() is 0 at 0)
 ILM_DEV float sign_times(float d, float m) { return (d == 0.0f) ? 0.0f * m : copysignf(m, d); }
 
-// positive modulo of a float tap index (D3D WRAP addressing)
+// wrap_index for |t| >= 2^31 and for NaN / infinity.  Every such finite float is an integer m * 2^e with a 24-bit m and e >= 8: the
+// remainder of m, doubled e times, each doubling folded back below size (size < 2^30: no overflow).  A NaN or infinite t names no
+// texel: tap 0.
+ILM_DEV int wrap_index_wide(float t, int size) {
+    if (!__builtin_isfinite(t)) return 0;
+    const uint32_t bits = __builtin_bit_cast(uint32_t, t), n = (uint32_t)size;
+    const int e = (int)((bits >> 23) & 0xFFu) - 150;
+    uint32_t r = ((bits & 0x7FFFFFu) | 0x800000u) % n;
+#pragma nounroll
+    for (int k = 0; k < e; k++) {
+        r <<= 1;
+        r = (r >= n) ? r - n : r;
+    }
+    return (int)(((bits >> 31) != 0u && r != 0u) ? n - r : r);
+}
+
+// D3D CLAMP addressing of an integer-valued float tap index, decided in float before the cast: NaN and -inf give tap 0, +inf the last.
+ILM_DEV int clamp_tap(float t, int size) { return (int)fminf(fmaxf(t, 0.0f), (float)(size - 1)); }
+
+// positive modulo of an integer-valued float tap index (D3D WRAP addressing), exact for every finite t; NaN / infinity give tap 0.
+// |t| < 2^31 -- every tap of a coordinate near the table -- is one cast (in range: exact) and an integer remainder; the rest take a
+// branch of their own (wrap_index_wide) instead of the saturating cast.
 ILM_DEV int wrap_index(float t, int size) {
+    if (__builtin_expect(!(__builtin_fabsf(t) < 0x1p31f), 0)) return wrap_index_wide(t, size);
     int i = (int)t;
     i %= size;
     if (i < 0) i += size;
@@ -291,12 +313,16 @@ ILM_DEV float sample_distance_field(f3 position, const IlmDistanceFieldUniforms&
         // (x0f + 0.5) / width * 2^-23 of it: for x0f < 2^22 the floor is the exact quotient and no fold is needed.  x0f >= -1 (u >= 0).
         const float q = floorf(__builtin_fmaf(x0f, sdf.inv_wf, sdf.wrap_half));
         x0 = (int)__builtin_fmaf(-q, sdf.wf, x0f);
-    } else {
+    } else if (__builtin_expect(__builtin_fabsf(x0f) < 0x1p22f, 1)) {
         const float q = floorf(x0f * sdf.inv_wf);
         float r = __builtin_fmaf(-q, sdf.wf, x0f);
         r = (r < 0.0f) ? r + sdf.wf : r;
         r = (r >= sdf.wf) ? r - sdf.wf : r;
         x0 = (int)r;
+    } else {
+        // from 2^22 on q * width need not be exact and one fold need not reach [0, width): the exact WRAP (NaN / infinity: tap 0,
+        // whose weight is NaN)
+        x0 = wrap_index(x0f, sdf.width);
     }
     int x1 = x0 + 1;
     x1 = (x1 == sdf.width) ? 0 : x1;

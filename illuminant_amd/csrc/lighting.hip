@@ -133,8 +133,8 @@ ILM_DEV Pixel sample_gbuffer(float spx, float spy, const IlmEnvironment& env, co
         }
         const float u = (sx + 0.5f) * env.GBufferTexelSizeAndMisc.x;
         const float v = (sy + 0.5f) * env.GBufferTexelSizeAndMisc.y;
-        const int tx = min(max((int)floorf(u * (float)g.width), 0), g.width - 1);
-        const int ty = min(max((int)floorf(v * (float)g.height), 0), g.height - 1);
+        const int tx = clamp_tap(floorf(u * (float)g.width), g.width);
+        const int ty = clamp_tap(floorf(v * (float)g.height), g.height);
         float4 s;
         if (g.format == ILM_GBUFFER_HALF4) {
             const uint2 raw = reinterpret_cast<const uint2*>(g.texels)[(size_t)ty * (size_t)g.width + (size_t)tx];
@@ -434,8 +434,10 @@ ILM_DEV bool shade_light(const Pixel& P, const LightRec& L, const IlmEnvironment
         float x1f = x0f + 1.0f;
         x0f = (x0f >= 0.0f) ? x0f : 0.0f; x0f = fminf(x0f, (float)(w - 1));
         x1f = (x1f >= 0.0f) ? x1f : 0.0f; x1f = fminf(x1f, (float)(w - 1));
+        // U is clamped in float before the cast (NaN: column 0).  V WRAP is exact for every float; y1 is the integer y0 + 1 wrapped, the
+        // tap the sampler takes (y0f + 1.0f would round back onto y0f from 2^24 on).
         const int x0 = (int)x0f, x1 = (int)x1f;
-        const int y0 = wrap_index(y0f, h), y1 = wrap_index(y0f + 1.0f, h);
+        const int y0 = wrap_index(y0f, h), y1 = (y0 + 1 == h) ? 0 : y0 + 1;
         const float4 t00 = ramp.texels[y0 * w + x0], t10 = ramp.texels[y0 * w + x1], t01 = ramp.texels[y1 * w + x0], t11 = ramp.texels[y1 * w + x1];
         opacity_r = lerp(lerp(t00.x, t10.x, fx), lerp(t01.x, t11.x, fx), fy) * cone_opacity;
         opacity_g = lerp(lerp(t00.y, t10.y, fx), lerp(t01.y, t11.y, fx), fy) * cone_opacity;

@@ -265,6 +265,8 @@ ILM_DEV float4 smooth_random_custom(const uint2* __restrict__ lp, int rw, int rh
     const float sx = u * (float)rw - 0.5f, sy = v * (float)rh - 0.5f;
     const float x0f = floorf(sx), y0f = floorf(sy);
     const float fx = sx - x0f, fy = sy - y0f;
+    // The index follows particle positions (state, not a uniform), so it is decided exactly for every float.  x1 is the integer x0 + 1
+    // wrapped (x0f + 1.0f would round back onto x0f from 2^24 on, where the fraction is 0).
     const int x0 = wrap_index(x0f, rw), y0 = wrap_index(y0f, rh);
     const int x1 = (x0 + 1 == rw) ? 0 : x0 + 1, y1 = (y0 + 1 == rh) ? 0 : y0 + 1;
     const uint2 t00 = lp[y0 * rw + x0], t10 = lp[y0 * rw + x1], t01 = lp[y1 * rw + x0], t11 = lp[y1 * rw + x1];
@@ -393,14 +395,19 @@ ILM_DEV bool spawn_stage1(float x, float y, const float4* __restrict__ rnd, int 
         const float divisor = p.PositionConstantCount;
         float position_index_i;
         position_index_t = modff(position_index_f, &position_index_i);
+        // position_index_i is finite and >= 0 and divisor an integer in [1, count] (validate_step): fmodf is exact and in [0, divisor)
         index1 = (int)fmodf(position_index_i, divisor);
         if (p.PolygonLoop != 0.0f)
             index2 = (int)fmodf(position_index_i + 1.0f, divisor);
         else
             index2 = (int)fminf((float)(index1 + 1), divisor - 1.0f);
     } else {
-        // integer-valued operands (slot index + TotalSpawned % count, the position count): exact either way
-        index1 = index2 = wrap_index_fast(relative_index + p.ChunkSizeAndIndices[3], (int)p.PositionConstantCount);
+        // integer-valued operands (slot index + TotalSpawned % count, the position count; validate_step refuses any other .w or
+        // count), >= 0 and below 2^24 + 2^20.  wrap_index_fast is exact below 2^23 (every inline spawner); a position buffer's larger
+        // indices take the exact integer remainder.
+        const float t = relative_index + p.ChunkSizeAndIndices[3];
+        const int count = (int)p.PositionConstantCount;
+        index1 = index2 = (t < 0x1p23f) ? wrap_index_fast(t, count) : wrap_index(t, count);
         position_index_t = 0.0f;
     }
     return true;
@@ -464,7 +471,7 @@ ILM_DEV float4 position_constant_fetch(const float4* __restrict__ positions, int
     const int width = (count + 127) / 128 * 128;
     const float texel = 1.0f / (float)width;
     const float u = (float)index * texel;
-    const int tx = min(max((int)floorf(u * (float)width), 0), width - 1);
+    const int tx = clamp_tap(floorf(u * (float)width), width);
     return (tx < count) ? positions[tx] : mk4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
@@ -494,8 +501,8 @@ ILM_DEV bool spawn_slot_feedback(float4& pos, float4& vel, float4& attr, float x
     float source_y;
     const float source_x = modff(source_index / size, &source_y) * size;
     // readStateUv: POINT / CLAMP at uv = sourceXy * texel
-    const int tx = min(max((int)floorf((source_x * texel) * size), 0), chunk_size - 1);
-    const int ty = min(max((int)floorf((source_y * texel) * size), 0), chunk_size - 1);
+    const int tx = clamp_tap(floorf((source_x * texel) * size), chunk_size);
+    const int ty = clamp_tap(floorf((source_y * texel) * size), chunk_size);
     const int si = ty * chunk_size + tx;
     const float4 source_position = mk4(src[si], src[S + si], src[2 * S + si], src[3 * S + si]);
     if ((source_position.w <= fb.SourceLifeRange[0]) || (source_position.w >= fb.SourceLifeRange[1]))
@@ -540,7 +547,7 @@ ILM_DEV bool spawn_slot_feedback(float4& pos, float4& vel, float4& attr, float x
 // levels back to back (include/illuminant_hip.h, ilm_system_set_spawn_pattern); texel centres sit at integer + 0.5.
 ILM_DEV float4 pattern_fetch(const float4* __restrict__ tex, int w, int h, int levels, float u, float v, float lod) {
 #pragma clang fp contract(off)
-    const int level = min(max((int)floorf(lod + 0.5f), 0), levels - 1);
+    const int level = clamp_tap(floorf(lod + 0.5f), levels);
     int lw = w, lh = h;
     for (int l = 0; l < level; l++) {
         tex += lw * lh;
@@ -648,7 +655,8 @@ ILM_DEV void render_data(float vx, float vy, float4 position, float4 velocity, f
         const float v = index / p.LifeRampSettings.w;
         float4 texel = mk4(1.0f, 1.0f, 1.0f, 1.0f);
         if (ramp != nullptr && ramp_w > 0 && ramp_h > 0) {
-            const int tx = min(max((int)floorf(u * (float)ramp_w), 0), ramp_w - 1);   // U CLAMP
+            // U CLAMP, decided in float before the cast (NaN: column 0); V WRAP, exact for every float
+            const int tx = clamp_tap(floorf(u * (float)ramp_w), ramp_w);
             const int ty = wrap_index(floorf(v * (float)ramp_h), ramp_h);             // V WRAP
             texel = ramp[ty * ramp_w + tx];
         }

@@ -79,12 +79,20 @@ static inline int wrap_index(float t, int size) {
     return (int)r;
 }
 
-/* D3D CLAMP addressing of a tap index t (integer-valued), decided in double before any cast: defined for every float */
+/* D3D CLAMP addressing of a tap index t (integer-valued), decided in double before any cast: defined for every float.
+ * NaN gives tap 0, -inf tap 0, +inf the last tap. */
 static inline int clamp_index(double t, int size) {
     if (t != t) return 0;
     if (t < 0.0) return 0;
     if (t > (double)(size - 1)) return size - 1;
     return (int)t;
+}
+
+/* A spawner's position-constant index, HLSL `int = float % float` (SpawnerCommon.fxh:138-156): fmod (exact) then truncation.  validate_step
+ * admits only operands whose result is an integer in [0, count); anything else is decided in double and clamped to [0, limit), so that no
+ * unchecked value is cast and no position outside the table is read. */
+static inline int position_slot(float t, float divisor, int limit) {
+    return clamp_index(trunc(fmod((double)t, (double)divisor)), limit);
 }
 
 /* IEEE half -> float */
@@ -501,14 +509,14 @@ static void spawn_slot(f4* pos, f4* vel, f4* attr, float x, float y,
         float position_index_i;
         position_index_t = modff(position_index_f, &position_index_i);
         if (p->PolygonLoop != 0.0f) {
-            index1 = (int)fmodf(position_index_i, divisor);
-            index2 = (int)fmodf(position_index_i + 1.0f, divisor);
+            index1 = position_slot(position_index_i, divisor, ILM_MAX_INLINE_POSITION_CONSTANTS);
+            index2 = position_slot(position_index_i + 1.0f, divisor, ILM_MAX_INLINE_POSITION_CONSTANTS);
         } else {
-            index1 = (int)fmodf(position_index_i, divisor);
-            index2 = (int)fminf((float)(index1 + 1), divisor - 1.0f);
+            index1 = position_slot(position_index_i, divisor, ILM_MAX_INLINE_POSITION_CONSTANTS);
+            index2 = clamp_index(trunc((double)fminf((float)(index1 + 1), divisor - 1.0f)), ILM_MAX_INLINE_POSITION_CONSTANTS);
         }
     } else {
-        index1 = index2 = (int)fmodf(relative_index + csi[3], p->PositionConstantCount);
+        index1 = index2 = position_slot(relative_index + csi[3], p->PositionConstantCount, ILM_MAX_INLINE_POSITION_CONSTANTS);
         position_index_t = 0.0f;
     }
 
@@ -767,8 +775,7 @@ static f3 apply_friction_and_maximum(f3 velocity, const IlmParticleSystemUniform
 static f4 read_life_ramp(const f4* ramp, int w, int h, float u, float v) {
     if (!ramp || w <= 0 || h <= 0)
         return v4(1, 1, 1, 1);
-    int tx = (int)floorf(u * (float)w);
-    if (tx < 0) tx = 0; if (tx > w - 1) tx = w - 1;
+    int tx = clamp_index((double)floorf(u * (float)w), w);
     int ty = wrap_index(floorf(v * (float)h), h);
     return ramp[ty * w + tx];
 }
@@ -1130,7 +1137,7 @@ static f3 sample_gbuffer(float spx, float spy, const IlmEnvironment* env, const 
         float v = (sy + 0.5f) * env->GBufferTexelSizeAndMisc.y;
         float sample[4];
         /* POINT / CLAMP sampler (LightCommon.fxh:35-43) */
-        gbuffer_texel(g, (int)floorf(u * (float)g->width), (int)floorf(v * (float)g->height), sample);
+        gbuffer_texel(g, clamp_index((double)floorf(u * (float)g->width), g->width), clamp_index((double)floorf(v * (float)g->height), g->height), sample);
 
         float relative_y = sample[2];
         float world_z = sample[3];
@@ -1317,8 +1324,9 @@ static f4 sample_from_ramp2(float u, float v) {
     float x1f = x0f + 1.0f;
     if (!(x0f >= 0.0f)) x0f = 0.0f; if (x0f > (float)(w - 1)) x0f = (float)(w - 1);
     if (!(x1f >= 0.0f)) x1f = 0.0f; if (x1f > (float)(w - 1)) x1f = (float)(w - 1);
-    const int x0 = (int)x0f, x1 = (int)x1f;
-    const int y0 = wrap_index(y0f, h), y1 = wrap_index(y0f + 1.0f, h);
+    const int x0 = (int)x0f, x1 = (int)x1f;       /* clamped in float above (NaN: 0) */
+    /* the second row is the integer y0 + 1 wrapped (y0f + 1.0f would round back onto y0f from 2^24 on) */
+    const int y0 = wrap_index(y0f, h), y1 = (y0 + 1 == h) ? 0 : y0 + 1;
     return v4lerp(v4lerp(g_light_ramp[y0 * w + x0], g_light_ramp[y0 * w + x1], fx),
                   v4lerp(g_light_ramp[y1 * w + x0], g_light_ramp[y1 * w + x1], fx), fy);
 }
@@ -1568,4 +1576,31 @@ int32_t orc_num_threads(void) {
 #else
     return 1;
 #endif
+}
+
+/* One table lookup of the particle or light path, for the addressing checks of tests/test_oracle_kat.py.  kind: 0 readLifeRamp (u, v) =
+ * (a, b); 1 SampleFromRamp2 (u, v) = (a, b); 2 randomCustom at (a, b) with offset (c, d), rate 1; 3 smoothRandomCustom at (a, b) with
+ * offset (c, d), rate 1, on the Rgba64 copy of `table`; 4 the spawner's position index a % b into a table of (int)c positions
+ * (out[0] = the index).  The same static functions the passes call. */
+void orc_table_lookup(int32_t kind, const IlmFloat4* table, int32_t w, int32_t h, float a, float b, float c, float d, float out[4]) {
+    f4 r = v4(0, 0, 0, 0);
+    const float off[2] = { c, d };
+    if (kind == 0) {
+        r = read_life_ramp((const f4*)table, w, h, a, b);
+    } else if (kind == 1) {
+        const IlmFloat4* saved = g_light_ramp; const int sw = g_light_ramp_w, sh = g_light_ramp_h;
+        orc_set_light_ramp(table, w, h);
+        r = sample_from_ramp2(a, b);
+        g_light_ramp = saved; g_light_ramp_w = sw; g_light_ramp_h = sh;
+    } else if (kind == 2) {
+        r = random_custom((const f4*)table, w, h, a, b, off, 1.0f, 1.0f);
+    } else if (kind == 3) {
+        uint16_t* lp = (uint16_t*)malloc((size_t)w * h * 4 * sizeof(uint16_t));
+        orc_low_precision_randomness(table, w * h, lp);
+        r = smooth_random_custom(lp, w, h, a, b, off, 1.0f, 1.0f);
+        free(lp);
+    } else if (kind == 4) {
+        r.x = (float)position_slot(a, b, (int)c);
+    }
+    out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
 }

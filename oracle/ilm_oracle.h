@@ -103,6 +103,9 @@ float orc_evaluate_area(int32_t type_id, const float pos[3], const float center[
 /* RampTexture of the light group rendered by the following orc_render_sphere_lights / orc_render_light_probes calls (width * height
  * float4, kept by reference); NULL unbinds (techniques without a distance ramp) */
 void orc_set_light_ramp(const IlmFloat4* texels, int32_t width, int32_t height);
+/* one table lookup through the passes' own addressing (readLifeRamp, SampleFromRamp2, randomCustom, smoothRandomCustom, the spawner's
+ * position index): ilm_oracle.c orc_table_lookup */
+void orc_table_lookup(int32_t kind, const IlmFloat4* table, int32_t w, int32_t h, float a, float b, float c, float d, float out[4]);
 /* 0: fp32 accumulation over the lights (default); 1: the reference's HalfVector4 lightmap, rounded by the ROP after every light
  * (LightingRenderer.cs:476-479) -- see ilm_ctx_set_lightmap_blend */
 void orc_set_lightmap_blend(int32_t mode);

@@ -59,8 +59,9 @@ static f4 smooth_random_custom(const uint16_t* lp, int rw, int rh, float x, floa
     float sx = u * (float)rw - 0.5f, sy = v * (float)rh - 0.5f;
     float x0f = floorf(sx), y0f = floorf(sy);
     float fx = sx - x0f, fy = sy - y0f;
-    int x0 = wrap_index(x0f, rw), x1 = wrap_index(x0f + 1.0f, rw);
-    int y0 = wrap_index(y0f, rh), y1 = wrap_index(y0f + 1.0f, rh);
+    /* the second tap is the integer x0 + 1 wrapped (x0f + 1.0f would round back onto x0f from 2^24 on) */
+    int x0 = wrap_index(x0f, rw), x1 = (x0 + 1 == rw) ? 0 : x0 + 1;
+    int y0 = wrap_index(y0f, rh), y1 = (y0 + 1 == rh) ? 0 : y0 + 1;
     float r[4];
     for (int c = 0; c < 4; c++) {
         float t00 = (float)lp[((size_t)y0 * rw + x0) * 4 + c] / 65535.0f, t10 = (float)lp[((size_t)y0 * rw + x1) * 4 + c] / 65535.0f;
@@ -131,9 +132,7 @@ static f4 position_constant_fetch(const IlmFloat4* positions, int count, int ind
     const int width = (count + 127) / 128 * 128;
     const float texel = 1.0f / (float)width;
     float u = (float)index * texel;
-    int tx = (int)floorf(u * (float)width);
-    if (tx < 0) tx = 0;
-    if (tx > width - 1) tx = width - 1;
+    int tx = clamp_index((double)floorf(u * (float)width), width);
     if (tx >= count)
         return v4(0, 0, 0, 0);              /* the padding of Temp4 stays zero */
     return positions[tx];
@@ -154,13 +153,13 @@ static void spawn_position_buffer_slot(f4* pos, f4* vel, f4* attr, float x, floa
         float divisor = p->PositionConstantCount;
         float position_index_i;
         position_index_t = modff(position_index_f, &position_index_i);
-        index1 = (int)fmodf(position_index_i, divisor);
+        index1 = position_slot(position_index_i, divisor, position_count);
         if (p->PolygonLoop != 0.0f)
-            index2 = (int)fmodf(position_index_i + 1.0f, divisor);
+            index2 = position_slot(position_index_i + 1.0f, divisor, position_count);
         else
-            index2 = (int)fminf((float)(index1 + 1), divisor - 1.0f);
+            index2 = clamp_index(trunc((double)fminf((float)(index1 + 1), divisor - 1.0f)), position_count);
     } else {
-        index1 = index2 = (int)fmodf(relative_index + csi[3], p->PositionConstantCount);
+        index1 = index2 = position_slot(relative_index + csi[3], p->PositionConstantCount, position_count);
         position_index_t = 0.0f;
     }
     /* Spawn_Stage2 (SpawnerCommon.fxh:162-190) on the two fetched constants */
@@ -206,9 +205,8 @@ static void spawn_feedback_slot(f4* pos, f4* vel, f4* attr, float x, float y, co
     float source_y;
     float source_x = modff(source_index / size, &source_y) * size;
     /* readStateUv: POINT / CLAMP at uv = sourceXy * texel */
-    int tx = (int)floorf((source_x * texel) * size), ty = (int)floorf((source_y * texel) * size);
-    if (tx < 0) tx = 0; if (tx > source_chunk_size - 1) tx = source_chunk_size - 1;
-    if (ty < 0) ty = 0; if (ty > source_chunk_size - 1) ty = source_chunk_size - 1;
+    const int tx = clamp_index((double)floorf((source_x * texel) * size), source_chunk_size);
+    const int ty = clamp_index((double)floorf((source_y * texel) * size), source_chunk_size);
     const int si = ty * source_chunk_size + tx;
     f4 source_position = src_pos[si], source_velocity = src_vel[si], source_attributes = src_attr[si];
     if ((source_position.w <= fb->SourceLifeRange[0]) || (source_position.w >= fb->SourceLifeRange[1]))
@@ -245,9 +243,7 @@ static void spawn_feedback_slot(f4* pos, f4* vel, f4* attr, float x, float y, co
  * filter.  The explicit LOD picks the nearest level, floor(lod + 0.5) clamped to the chain; bilinear weights come from
  * uv * size - 0.5 (texel centres at integer + 0.5).  The mip chain itself is an input (the reference's texture loader makes it). */
 static f4 pattern_fetch(const IlmFloat4* tex, int w, int h, int levels, float u, float v, float lod) {
-    int level = (int)floorf(lod + 0.5f);
-    if (level < 0) level = 0;
-    if (level > levels - 1) level = levels - 1;
+    int level = clamp_index((double)floorf(lod + 0.5f), levels);
     int lw = w, lh = h;
     for (int l = 0; l < level; l++) {
         tex += lw * lh;
@@ -258,11 +254,7 @@ static f4 pattern_fetch(const IlmFloat4* tex, int w, int h, int levels, float u,
     float x0f = floorf(sx), y0f = floorf(sy);
     float fx = sx - x0f, fy = sy - y0f;
     float x1f = x0f + 1.0f, y1f = y0f + 1.0f;
-    if (x0f < 0.0f) x0f = 0.0f; if (x0f > (float)(lw - 1)) x0f = (float)(lw - 1);
-    if (x1f < 0.0f) x1f = 0.0f; if (x1f > (float)(lw - 1)) x1f = (float)(lw - 1);
-    if (y0f < 0.0f) y0f = 0.0f; if (y0f > (float)(lh - 1)) y0f = (float)(lh - 1);
-    if (y1f < 0.0f) y1f = 0.0f; if (y1f > (float)(lh - 1)) y1f = (float)(lh - 1);
-    const int x0 = (int)x0f, x1 = (int)x1f, y0 = (int)y0f, y1 = (int)y1f;
+    const int x0 = clamp_index((double)x0f, lw), x1 = clamp_index((double)x1f, lw), y0 = clamp_index((double)y0f, lh), y1 = clamp_index((double)y1f, lh);
     return v4lerp(v4lerp(tex[y0 * lw + x0], tex[y0 * lw + x1], fx), v4lerp(tex[y1 * lw + x0], tex[y1 * lw + x1], fx), fy);
 }
 

@@ -222,6 +222,17 @@ def bezier4(b, value):
     return out.tuple()
 
 
+def table_lookup(kind, table, a, b, c=0.0, d=0.0):
+    """One lookup through the oracle's own addressing (orc_table_lookup): 0 life ramp (u, v) = (a, b); 1 light ramp (u, v) = (a, b);
+    2 randomCustom at (a, b), offset (c, d); 3 smoothRandomCustom at (a, b), offset (c, d); 4 position index a % b into c positions.
+    table: (h, w, 4) float32.  Returns 4 float32."""
+    t = np.ascontiguousarray(table, np.float32)
+    out = np.zeros(4, np.float32)
+    lib().orc_table_lookup(C.c_int32(kind), _p(t), C.c_int32(t.shape[1]), C.c_int32(t.shape[0]), C.c_float(a), C.c_float(b),
+                           C.c_float(c), C.c_float(d), _p(out))
+    return out
+
+
 def sample_distance_field(pos, df, sdf):
     a = (C.c_float * 3)(*[float(x) for x in pos])
     return float(lib().orc_sample_distance_field(a, C.byref(df), C.byref(sdf)))

@@ -437,3 +437,175 @@ def test_distance_field_sampler_gives_nan_for_nan_coordinates(oracle):
     for (x, y), (tu, tv) in cases:
         got = oracle.sample_distance_field((x, y, 0.0), _sampler_kat_uniforms(tu, tv), tex)
         assert math.isnan(got), ((x, y), (tu, tv), got)
+
+
+# ---- every other table lookup of the particle and light paths against a float64 / Python-integer restatement -------------------------
+
+F32 = np.float32
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def _ulp_neighbours(t):
+    """t and its two fp32 neighbours."""
+    t = F32(t)
+    return [np.nextafter(t, F32(-np.inf)), t, np.nextafter(t, F32(np.inf))]
+
+
+def lookup_tap_matrix(size):
+    """The tap indices (fp32) every lookup is driven across: 0, -0, +-denormal, just below and above each table edge, +-(2^22, 2^23, 2^24)
+    +- 1 ulp, +-2^31 +- 1 ulp, +-2^40, +-FLT_MAX, +-inf and NaN."""
+    den = float(np.finfo(np.float32).smallest_subnormal)
+    taps = [0.0, -0.0, den, -den]
+    for edge in (0.0, 1.0, float(size - 1), float(size), float(2 * size)):
+        taps += [edge - 0.5, edge + 0.5] + [float(x) for x in _ulp_neighbours(edge)] + [-edge]
+    for e in (22, 23, 24, 31):
+        for s in (1.0, -1.0):
+            taps += [s * float(x) for x in _ulp_neighbours(2.0 ** e)]
+    taps += [2.0 ** 40, -(2.0 ** 40), FLT_MAX, -FLT_MAX, math.inf, -math.inf, math.nan]
+    return [F32(t) for t in taps]
+
+
+def _wrap(t, size):
+    """WRAP of an integer-valued tap (a Python float): exact for every finite value; NaN / infinity name no texel, tap 0."""
+    return int(t) % size if math.isfinite(t) else 0
+
+
+def _clamp(t, size):
+    """CLAMP of an integer-valued tap: NaN gives tap 0, -inf tap 0, +inf the last."""
+    if math.isnan(t):
+        return 0
+    return int(min(max(t, 0.0), float(size - 1))) if math.isfinite(t) else (0 if t < 0 else size - 1)
+
+
+def _floor(t):
+    return math.floor(t) if math.isfinite(t) else t
+
+
+def _coded_table(w, h):
+    """(h, w, 4) float32: texel (x, y) = (x / 64, y / 64, (x + 1) / 1024, 1) -- every texel names its own column and row."""
+    ys, xs = np.mgrid[0:h, 0:w]
+    t = np.zeros((h, w, 4), np.float32)
+    t[..., 0], t[..., 1], t[..., 2], t[..., 3] = xs / 64.0, ys / 64.0, (xs + 1) / 1024.0, 1.0
+    return t
+
+
+def _lerp64(a, b, t):
+    return a + (b - a) * t
+
+
+def _linear64(texel, sx, sy, col, row):
+    """float64 LINEAR blend at the fp32 tap coordinates (sx, sy); col / row map an integer tap to a texel column / row."""
+    x0f, y0f = _floor(sx), _floor(sy)
+    fx, fy = sx - x0f, sy - y0f
+    if not (math.isfinite(fx) and math.isfinite(fy)):
+        return None                                           # NaN weights: the sample is NaN
+    x0, y0 = int(x0f), int(y0f)
+    c0, c1, r0, r1 = col(x0), col(x0 + 1), row(y0), row(y0 + 1)
+    return _lerp64(_lerp64(texel(c0, r0), texel(c1, r0), fx), _lerp64(texel(c0, r1), texel(c1, r1), fx), fy)
+
+
+def _check_linear(got, want, what):
+    if want is None:
+        assert np.all(np.isnan(got[:3])), (what, got)
+    else:
+        assert np.allclose(got[:3].astype(np.float64), want[:3], rtol=1e-6, atol=1e-7), (what, got, want)
+
+
+def test_life_ramp_point_clamp_u_wrap_v_for_every_coordinate(oracle):
+    """readLifeRamp (POINT, U CLAMP, V WRAP): the texel is floor(u * w) clamped and floor(v * h) wrapped, exactly, for every float.  A
+    cast of u * w to int is undefined from 2^31 on (x86 gives INT_MIN, which clamped to column 0 instead of the last)."""
+    w, h = 7, 5
+    table = _coded_table(w, h)
+    n = 0
+    for tu in lookup_tap_matrix(w):
+        for tv in lookup_tap_matrix(h):
+            u, v = F32(tu) / F32(w), F32(tv) / F32(h)
+            got = oracle.table_lookup(0, table, u, v)
+            x = _clamp(_floor(float(F32(u * F32(w)))), w)
+            y = _wrap(_floor(float(F32(v * F32(h)))), h)
+            assert np.array_equal(got, table[y, x]), (u, v, got, (x, y))
+            n += 1
+    assert n > 1500
+
+
+def test_light_ramp_linear_clamp_u_wrap_v_for_every_coordinate(oracle):
+    """SampleFromRamp2 (LINEAR, U CLAMP, V WRAP, texel centres at +0.5) against a float64 blend of the exact taps."""
+    w, h = 6, 9
+    table = _coded_table(w, h)
+    texel = lambda c, r: table[r, c].astype(np.float64)
+    for tu in lookup_tap_matrix(w):
+        for tv in lookup_tap_matrix(h):
+            u, v = F32(tu) / F32(w), F32(tv) / F32(h)
+            got = oracle.table_lookup(1, table, u, v)
+            sx, sy = float(F32(F32(u * F32(w)) - F32(0.5))), float(F32(F32(v * F32(h)) - F32(0.5)))
+            want = _linear64(texel, sx, sy, lambda i: _clamp(float(i), w), lambda i: _wrap(float(i), h))
+            _check_linear(got, want, (u, v))
+
+
+def test_random_custom_point_wrap_for_every_offset(oracle):
+    """randomCustom (POINT, WRAP) at coordinate 0 with the offset driving the tap: floor(((0 + offset) * texel) * size) wrapped, for
+    every float offset (the ABI refuses |offset| >= 2^22; the oracle still decides the rest exactly)."""
+    rw, rh = 13, 7
+    table = _coded_table(rw, rh)
+    for ox in lookup_tap_matrix(rw):
+        for oy in lookup_tap_matrix(rh):
+            got = oracle.table_lookup(2, table, 0.0, 0.0, ox, oy)
+            tx = _floor(float(F32(F32(F32(F32(0.0) + ox) * (F32(1.0) / F32(rw))) * F32(rw))))
+            ty = _floor(float(F32(F32(F32(F32(0.0) + oy) * (F32(1.0) / F32(rh))) * F32(rh))))
+            want = table[_wrap(ty, rh), _wrap(tx, rw)]
+            assert np.array_equal(got, want), (ox, oy, got, want)
+
+
+def test_smooth_random_custom_linear_wrap_for_every_coordinate(oracle):
+    """smoothRandomCustom (LINEAR, WRAP on both axes, on the Rgba64 copy) at coordinates that run to +-FLT_MAX and past: the taps are the
+    exact wrapped texels; from 2^24 on the fraction is 0 and the second tap carries no weight."""
+    rw, rh = 11, 5
+    table = _coded_table(rw, rh)
+    lp = np.round(np.clip(table, 0, 1) * 65535.0) / 65535.0
+    texel = lambda c, r: lp[r, c].astype(np.float64)
+    for tx in lookup_tap_matrix(rw):
+        for ty in lookup_tap_matrix(rh):
+            got = oracle.table_lookup(3, table, tx, ty)
+            sx = float(F32(F32(F32(F32(tx * F32(1.0)) + F32(0.0)) * (F32(1.0) / F32(rw))) * F32(rw)) - F32(0.5))
+            sy = float(F32(F32(F32(F32(ty * F32(1.0)) + F32(0.0)) * (F32(1.0) / F32(rh))) * F32(rh)) - F32(0.5))
+            want = _linear64(texel, sx, sy, lambda i: _wrap(float(i), rw), lambda i: _wrap(float(i), rh))
+            _check_linear(got, want, (tx, ty))
+
+
+def test_spawner_position_index_stays_inside_the_positions(oracle):
+    """The position index t % count (HLSL: fmod, then truncation) for every float t and count 1 .. 4: the exact remainder where the
+    reference can produce it (t >= 0), and never an index outside [0, count) for what the ABI refuses."""
+    table = _coded_table(1, 1)
+    for count in (1.0, 2.0, 3.0, 4.0):
+        for t in lookup_tap_matrix(4):
+            got = int(oracle.table_lookup(4, table, t, count, count)[0])
+            assert 0 <= got < int(count), (t, count, got)
+            if math.isfinite(t) and t >= 0:
+                assert got == int(math.fmod(float(t), count)), (t, count, got)
+
+
+def _wrap_index_fast(t, size, rcp_ulps):
+    """hlsl_math.hpp wrap_index_fast in fp32 without contraction, with v_rcp_f32 modelled as 1 / size moved by rcp_ulps ulps."""
+    fs = F32(size)
+    rcp = F32(1.0) / fs
+    for _ in range(abs(rcp_ulps)):
+        rcp = np.nextafter(rcp, F32(np.inf) if rcp_ulps > 0 else F32(-np.inf))
+    q = np.floor(F32(t) * rcp)
+    r = F32(F32(t) - F32(q * fs))
+    r = F32(r + fs) if r < 0 else r
+    r = F32(r - fs) if r >= fs else r
+    return r
+
+
+def test_wrap_index_fast_is_exact_only_below_the_refusal_bound():
+    """randomCustom's fast WRAP is exact for |tap| < 2^23 whichever way the reciprocal errs by an ulp, which is what the ABI's refusal of
+    |RandomnessOffset| >= 2^22 keeps it to; beyond, the single fold can even leave [0, size), a read outside the randomness table."""
+    rng = np.random.default_rng(5)
+    with np.errstate(all="ignore"):
+        for size in (807, 653, 253, 127, 13, 4, 3):
+            for t in list(rng.integers(-(2 ** 23) + 1, 2 ** 23, 3000)) + [0, 1, -1, size, -size, 2 ** 23 - 1, -(2 ** 23) + 1]:
+                for ulps in (-1, 0, 1):
+                    assert int(_wrap_index_fast(F32(t), size, ulps)) == int(t) % size, (size, t, ulps)
+        outside = [(t, ulps) for t in (F32(2.0 ** 30 + 256.0 * k) for k in range(1, 64)) for ulps in (-1, 0, 1)
+                   if not 0 <= _wrap_index_fast(t, 253, ulps) < 253]
+    assert outside, "the fold stayed inside the table beyond 2^24: the refusal bound would no longer need its proof"
