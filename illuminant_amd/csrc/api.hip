@@ -237,6 +237,18 @@ struct Lightmap {
     void** d_mirrors = nullptr; int mirror_count = 0;
 };
 
+// The render key (internal.hpp, kElideDerived): everything render_data reads besides the particle itself -- the update pass's four
+// curves, RotationFromLifeAndIndex, LifeRampSettings and getVelocityRotation() (bezier_codes / update_bits follow from these).  Not dt:
+// it may change every frame without touching a render plane.  Floats only, so comparing the bytes compares every field.
+struct RenderKey {
+    IlmClampedBezier4 color_from_life, color_from_velocity;
+    IlmClampedBezier1 size_from_life, size_from_velocity;
+    float rotation_from_life_and_index[2];
+    IlmFloat4 life_ramp;
+    float velocity_rotation;
+};
+static_assert(sizeof(RenderKey) == sizeof(float) * (2 * 20 + 2 * 8 + 2 + 4 + 1), "RenderKey has no padding");
+
 struct System {
     uint32_t magic = kMagicSystem;
     Engine* engine = nullptr;
@@ -245,6 +257,14 @@ struct System {
     // erased, so every plane of theirs is zero and a step leaves them exactly as they are -- the launch skips their units.
     // Raised by uploads and spawn ranges; a chunk whose device pointer was handed out is treated as fully used.
     std::vector<int32_t> used;
+    // Render-plane record per chunk: render_gen[i] == render_key_gen when the chunk is render-current under render_key (its render
+    // colour / render data planes hold what step_lean_kernel's store path writes for its stored state), 0 when that is not known.  Set by
+    // a lean step with its update pass; cleared by every other step and every other writer of the chunk.  A chunk whose device pointer was
+    // handed out (ptr_out) is never render-current again, nor is any chunk once a step of the system has been captured into a graph.
+    std::vector<uint64_t> render_gen;
+    std::vector<uint8_t> ptr_out;
+    RenderKey render_key; uint64_t render_key_gen = 0;
+    bool render_captured = false;
     float** d_table = nullptr; int table_cap = 0; bool table_dirty = true;
     // Five counter regions of 64-bit words.  Regions 0-3 belong to the step kernels, kCountLines lines per chunk (internal.hpp),
     // index = parity * 2 + half: a counting launch of half h accumulates into (parity, h) and zeroes (parity ^ 1, h) for the next
@@ -928,6 +948,27 @@ static const void* ensure_slice0_cells(Sdf* f, Ctx* c) {
     return f->cells0;
 }
 
+// The generation of the step's render key: a new one whenever the key's bytes differ from the last step's that had an update pass.
+static uint64_t render_key_generation(System* s, const IlmStepDesc* d) {
+    RenderKey k;
+    memset(&k, 0, sizeof(k));
+    k.color_from_life = d->Update.ColorFromLife; k.color_from_velocity = d->Update.ColorFromVelocity;
+    k.size_from_life = d->Update.SizeFromLife; k.size_from_velocity = d->Update.SizeFromVelocity;
+    k.rotation_from_life_and_index[0] = d->Update.RotationFromLifeAndIndex[0]; k.rotation_from_life_and_index[1] = d->Update.RotationFromLifeAndIndex[1];
+    k.life_ramp = d->Update.LifeRampSettings;
+    k.velocity_rotation = d->System.AnimationRateAndRotationAndZToY.z;
+    if (s->render_key_gen == 0 || memcmp(&k, &s->render_key, sizeof(k)) != 0) {
+        s->render_key = k;
+        s->render_key_gen++;
+    }
+    return s->render_key_gen;
+}
+static bool stream_capturing(hipStream_t stream) {
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &status) != hipSuccess) { (void)hipGetLastError(); return true; }    // (unknown: assume so)
+    return status != hipStreamCaptureStatusNone;
+}
+
 int32_t run_step(System* s, const IlmStepDesc* d) {
     int first = 0, count = 0;
     int32_t rc = validate_step(s, d, &first, &count);
@@ -1078,8 +1119,24 @@ int32_t run_step(System* s, const IlmStepDesc* d) {
             }
         }
     }
+    // Render-plane records of the range (System::render_gen): a launch may leave the render planes alone where every chunk of it is
+    // render-current under this step's key.  The records are cleared before the launches and set again for what a lean step refreshed.
+    const uint64_t key = (d->UpdateMode == ILM_UPDATE_POSITIONS) ? render_key_generation(s, d) : 0;
+    if (stream_capturing(c->stream_) || stream_capturing(c->aux)) s->render_captured = true;     // a replay would not keep the records
+    auto render_elide = [&](int lo, int hi) -> uint32_t {
+        bool current = key != 0 && !s->render_captured;
+        for (int ci = lo; current && ci < hi; ci++) current = (s->render_gen[(size_t)ci] == key) && !s->ptr_out[(size_t)ci];
+        return current ? kElideDerived : 0u;
+    };
+    auto render_refreshed = [&](int lo, int hi, bool refreshed) {
+        for (int ci = lo; ci < hi; ci++) s->render_gen[(size_t)ci] = (refreshed && key != 0 && !s->render_captured && !s->ptr_out[(size_t)ci]) ? key : 0;
+    };
+    const uint32_t elide_a = render_elide(first, (mid < 0) ? first + count : mid), elide_b = (mid < 0) ? 0u : render_elide(mid, first + count);
+    render_refreshed(first, first + count, false);
+    bool fresh_a = false, fresh_b = false;
     if (mid < 0) {
-        HIP_TRY(launch_step(a, c->main()));
+        HIP_TRY(launch_step(a, c->main(), elide_a, &fresh_a));
+        render_refreshed(first, first + count, fresh_a);
     } else {
         if (s->split_at != mid) { (void)c->main(); s->split_at = mid; }      // a chunk changes streams: join first
         if (c->main_pending) {
@@ -1099,14 +1156,16 @@ int32_t run_step(System* s, const IlmStepDesc* d) {
         bool spawn_in_b = false;
         for (int k = 0; k < d->SpawnCount; k++) spawn_in_b = spawn_in_b || (d->Spawns[k].ChunkIndex >= mid);
         if (spawn_in_b) {
-            HIP_TRY(launch_step(b, c->aux));
+            HIP_TRY(launch_step(b, c->aux, elide_b, &fresh_b));
             c->aux_pending = true;
-            HIP_TRY(launch_step(a, c->stream_));
+            HIP_TRY(launch_step(a, c->stream_, elide_a, &fresh_a));
         } else {
-            HIP_TRY(launch_step(a, c->stream_));
-            HIP_TRY(launch_step(b, c->aux));
+            HIP_TRY(launch_step(a, c->stream_, elide_a, &fresh_a));
+            HIP_TRY(launch_step(b, c->aux, elide_b, &fresh_b));
             c->aux_pending = true;
         }
+        render_refreshed(first, mid, fresh_a);
+        render_refreshed(mid, first + count, fresh_b);
     }
     if (d->UpdateMode == ILM_UPDATE_ERASE)
         for (int ci = first; ci < first + count; ci++) s->used[(size_t)ci] = 0;   // position, velocity and render planes are zero again
@@ -1199,7 +1258,10 @@ int32_t system_chunk_view(IlmHandle system, int chunk, bool written, float** out
     if (out_stride) *out_stride = s->engine->stride;
     if (out_chunk_size) *out_chunk_size = s->engine->chunk_size;
     if (out_ctx) *out_ctx = to_handle(s->engine->ctx);
-    if (written) s->used[(size_t)chunk] = s->engine->slots;
+    if (written) {
+        s->used[(size_t)chunk] = s->engine->slots;
+        s->render_gen[(size_t)chunk] = 0;
+    }
     return ILM_OK;
 }
 hipStream_t ctx_stream_joined(IlmHandle h) {
@@ -1576,6 +1638,8 @@ int32_t ilm_system_add_chunk(IlmHandle h, int32_t* out_index) {
     { const int32_t rc = acquire_chunk(e, &base); if (rc != ILM_OK) return rc; }
     s->chunks.push_back(base);
     s->used.push_back(0);
+    s->render_gen.push_back(0);
+    s->ptr_out.push_back(0);
     s->table_dirty = true;
     if (out_index) *out_index = (int32_t)s->chunks.size() - 1;
     return ILM_OK;
@@ -1592,6 +1656,8 @@ int32_t ilm_system_remove_chunk(IlmHandle h, int32_t index) {
     release_chunk(s->engine, s->chunks[(size_t)index]);
     s->chunks.erase(s->chunks.begin() + index);
     s->used.erase(s->used.begin() + index);
+    s->render_gen.erase(s->render_gen.begin() + index);
+    s->ptr_out.erase(s->ptr_out.begin() + index);
     s->table_dirty = true;
     return ILM_OK;
 }
@@ -1627,6 +1693,7 @@ int32_t ilm_chunk_upload(IlmHandle h, int32_t chunk, int32_t plane, const IlmFlo
     if (rc != ILM_OK) return rc;
     HIP_TRY(hipMemcpyAsync(c->staging, src, bytes, hipMemcpyHostToDevice, c->main()));
     s->used[(size_t)chunk] = std::max(s->used[(size_t)chunk], first_slot + count);
+    s->render_gen[(size_t)chunk] = 0;
     HIP_TRY(launch_aos_to_soa(reinterpret_cast<const float4*>(c->staging), s->chunks[(size_t)chunk] + (int64_t)plane * 4 * e->stride,
                               e->stride, first_slot, count, c->main()));
     HIP_TRY(hipStreamSynchronize(c->main()));   // staging is reused by the next call
@@ -1659,6 +1726,8 @@ int32_t ilm_chunk_device_ptr(IlmHandle h, int32_t chunk, int32_t component, void
         return fail(ILM_ERR_OUT_OF_RANGE, "chunk/component out of range");
     if (out_ptr) *out_ptr = s->chunks[(size_t)chunk] + (int64_t)component * s->engine->stride;
     s->used[(size_t)chunk] = s->engine->slots;     // the caller may write through the pointer
+    s->render_gen[(size_t)chunk] = 0;
+    s->ptr_out[(size_t)chunk] = 1;
     if (out_stride) *out_stride = s->engine->stride;
     return ILM_OK;
 }

@@ -115,7 +115,15 @@ static_assert(sizeof(StepLaunch) <= 4096, "StepLaunch travels in the kernarg seg
 // per-chunk live counters are kCountStride 64-bit words apart (one 128-byte line each)
 constexpr int kCountStride = 16;     // in 64-bit words
 constexpr int kCountLines = 17;      // per chunk in the step kernels' counter regions: the chunk's line + 16 bucket lines
-hipError_t launch_step(StepLaunch& a, hipStream_t stream);
+// Store elision of step_lean_kernel<.., STREAM = true> (particles.hip; the HBM-resident variant: the cache-resident one stores everything).
+// Position and velocity planes are stored by a wave only when some lane changed their bits; that needs no bookkeeping.  The render colour / render data planes of a chunk may also be left alone when the host knows them to
+// be RENDER-CURRENT under the step's render key (api.hip, System::render_gen): they hold exactly what the lean step's store path writes
+// for the chunk's stored position, velocity and attributes under that key.  `render_elide` of launch_step: kElideDerived when every chunk
+// of the launch is render-current.  `refreshed`: set when the lean step with its update pass ran, so that every chunk of the range is
+// render-current under the key afterwards; left false by every other kernel (the records of the range must then be cleared).
+constexpr uint32_t kElideDerived = 1u;
+constexpr uint32_t kElideColor = 2u;     // (set by build_lean_step) the colour curves cannot produce a NaN factor: renderColor may be elided
+hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide = 0u, bool* refreshed = nullptr);
 hipError_t step_sdf_sample_counter(int enable, unsigned long long* out);   // ilm_debug_step_sdf_samples
 // the slice-0 cells of a UNORM16 field (SdfView::cells0): does this step's collision update use them, and their build
 bool step_wants_slice0_cells(const IlmStepDesc& d, int format);

@@ -634,6 +634,14 @@ ILM_DEV f3 friction_and_maximum(f3 velocity, const IlmParticleSystemUniforms& sy
     return velocity * (inv_l * l);
 }
 
+// Pieces of computeRenderData that step_lean_kernel also evaluates for the state it loaded (its store elision).
+ILM_DEV float render_index(float vx, float vy) { return vx + (vy * ref::kRenderDataIndexRowPitch); }   // reference quirk: 256 regardless of ChunkSize (:107)
+// getRotationForVelocity x getVelocityRotation() when the latter is 0 (update_bits bit 1): 0, or NaN for a NaN velocity (see render_data)
+ILM_DEV float rotation_unscaled(float vx, float vy) { return ((vx != vx) || (vy != vy)) ? __builtin_nanf("") : 0.0f; }
+ILM_DEV float render_rotation(float rotation, float life, float index, const IlmParticleSystemUniforms& sys, const IlmUpdateParams& p) {
+    return (rotation * sys.AnimationRateAndRotationAndZToY.z) + ((life * p.RotationFromLifeAndIndex[0]) + (index * p.RotationFromLifeAndIndex[1]));
+}
+
 // computeRenderData, UpdateCommon.fxh:96-117.  `codes` / `bits`: the uniform decisions of the four curves, the life ramp and the
 // velocity rotation, taken on the host (StepDerived::bezier_codes / update_bits).
 ILM_DEV void render_data(float vx, float vy, float4 position, float4 velocity, float4 attributes,
@@ -644,7 +652,7 @@ ILM_DEV void render_data(float vx, float vy, float4 position, float4 velocity, f
         render_color = rdata = mk4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
-    const float index = vx + (vy * ref::kRenderDataIndexRowPitch);  // reference quirk: 256 regardless of ChunkSize (:107)
+    const float index = render_index(vx, vy);
     const float velocity_length = fmaxf(len3_fast(xyz(velocity)), 0.0001f);
 
     float4 color = mul4(bezier4_coded(p.ColorFromLife, position.w, codes & 0xFFu), bezier4_coded(p.ColorFromVelocity, velocity_length, (codes >> 8) & 0xFFu));
@@ -673,15 +681,14 @@ ILM_DEV void render_data(float vx, float vy, float4 position, float4 velocity, f
     // the angle is multiplied by getVelocityRotation(): skipping atan2 when that is 0 is exact for every finite or infinite velocity
     // (the angle is finite); a NaN velocity (normalize(0) upstream) makes the angle NaN and NaN * 0 stays NaN
     if (bits & 2u) {    // sys.AnimationRateAndRotationAndZToY.z == 0
-        rotation = ((velocity.x != velocity.x) || (velocity.y != velocity.y)) ? __builtin_nanf("") : 0.0f;
+        rotation = rotation_unscaled(velocity.x, velocity.y);
     } else if (!((fabsf(velocity.x) < 0.01f) && (fabsf(velocity.y) < 0.01f))) {
         rotation = atan2f(velocity.y, velocity.x);
         if (rotation < 0.0f)
             rotation += 2.0f * kPi;
     }
     rdata.x = bezier1_coded(p.SizeFromLife, position.w, (codes >> 16) & 0xFFu) * bezier1_coded(p.SizeFromVelocity, velocity_length, codes >> 24);
-    rdata.y = (rotation * sys.AnimationRateAndRotationAndZToY.z) +
-              ((position.w * p.RotationFromLifeAndIndex[0]) + (index * p.RotationFromLifeAndIndex[1]));
+    rdata.y = render_rotation(rotation, position.w, index, sys, p);
     rdata.z = velocity_length;
     rdata.w = velocity.w;
 }
@@ -1189,7 +1196,7 @@ struct LeanStep {
     int32_t first_chunk, cs_shift, zero_n; uint32_t flags;
     uint32_t count_seq; int32_t count_buckets; int32_t _pad3[2];
     int32_t partial_chunk[kMaxPartialChunks], partial_units[kMaxPartialChunks];     // unused entries: chunk -1
-    int32_t partial_count, op_count, spawn_count, _pad0;
+    int32_t partial_count, op_count, spawn_count; uint32_t elide;      // elide: kElideDerived / kElideColor (step_lean_kernel)
     int32_t op_type[ILM_MAX_OPS];
     int32_t spawn_chunk[ILM_MAX_SPAWNS], spawn_unit_lo[ILM_MAX_SPAWNS], spawn_unit_hi[ILM_MAX_SPAWNS];   // segments of the target chunk a record touches
     int32_t _pad1[2];
@@ -1315,6 +1322,74 @@ static_assert(offsetof(StepDerived::NoiseFast, velocity) == offsetof(StepDerived
 typedef const LeanStep __attribute__((address_space(4))) CLeanStep;
 static_assert(sizeof(LeanStep) >= 0xc84 && sizeof(LeanStep) <= 0xcc0, "touch_kernarg_lines_lean reads one dword of each 64-byte line of LeanStep");
 
+// ---- store elision (internal.hpp, kElideDerived) -------------------------------------------------------------------------------
+// A wave stores a plane only when it has to: writing the bits memory already holds changes nothing, and at cfg4's size every plane
+// access is HBM traffic.  When it stores, it stores all 64 lanes (an unchanged lane rewrites its own bits; a lane-masked store saves
+// no burst).
+ILM_DEV bool same_bits(float a, float b) { return __builtin_bit_cast(uint32_t, a) == __builtin_bit_cast(uint32_t, b); }
+// Only the STREAM variant elides.  The cache-resident one keeps every store: its planes live in the Infinity Cache from one step to the
+// next, its time follows the issue of its instructions rather than its bytes (see step_lean_kernel), and the compares would be added work.
+template <bool STREAM>
+ILM_DEV void st_plane_changed(const UnitPlanes& u, int c, unsigned lane4, float v, float loaded) {
+    if (!STREAM || __ballot(!same_bits(v, loaded)) != 0ull) st_plane<STREAM>(u, c, lane4, v);
+}
+// A curve of the update pass gives the same value for two inputs whose t (tForScaledBezier) is the same bits and no NaN: the rest of
+// evaluateBezier is a function of t and of the curve (part of the render key).  A constant curve reads no t at all.
+ILM_DEV bool same_curve_t(const IlmFloat4& rc, float v0, float v1, uint32_t code) {
+    if ((code & 3u) == 0u) return true;
+    const float t1 = t_for_coded_bezier(rc, v1, code);
+    return same_bits(t_for_coded_bezier(rc, v0, code), t1) && (t1 == t1);
+}
+// The render planes of a render-current chunk (every chunk of the launch; api.hip, System::render_gen) hold what render_data gives for the
+// state this wave loaded.  Per lane, a component keeps its bits when
+//   - the slot is dead before and after the step: all eight components are 0 and stay 0; or, for a slot alive before and after,
+//   - its inputs have the same bits (rd.z: the velocity; rd.w: the category, no NaN), or
+//   - a value that decides it is the same bits for the loaded and the new state and no NaN: renderColor by the two colour curves' t, with
+//     the attributes not spawned over and colour curves that cannot give a NaN factor (kElideColor, host-checked); rd.x by the size
+//     curves' t, rd.x itself no NaN; rd.y, when getVelocityRotation() == 0, by itself (recomputed for the loaded state, no NaN).
+// Anything else -- liveness changed, rotation from velocity, a NaN -- stores.  A plane is stored when any lane of the wave needs it;
+// the attributes are loaded only by a wave that stores renderColor.  (No life ramp here: build_lean_step.)
+template <bool SPAWN, bool STREAM>
+ILM_DEV void store_changed_render_planes(const LeanStep& a, const UnitPlanes& up, unsigned lane4, float fx, float fy, const SlotIn& cur,
+                                         float4 pos, float4 vel, float4 attr, bool spawned) {
+    const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    const IlmUpdateParams& p = a.update;
+    const uint32_t codes = a.bezier_codes;
+    const bool live0 = !(cur.life <= 0.0f), live1 = !(pos.w <= 0.0f);
+    const bool dead = !live0 && !live1, both = live0 && live1;
+    float4 rc, rd;
+    render_data(fx, fy, pos, vel, zero, a.sys, p, codes, a.update_bits, nullptr, 0, 0, rc, rd);     // (rc: not used)
+    // the speed the velocity curves read, for the loaded state, only where a velocity curve is not constant
+    float speed0 = 0.0f, speed1 = 0.0f;
+    if ((codes & 0x03000300u) != 0u) {
+        speed0 = fmaxf(len3_fast(mk3(cur.vx, cur.vy, cur.vz)), 0.0001f);
+        speed1 = fmaxf(len3_fast(xyz(vel)), 0.0001f);
+    }
+    const bool same_v = same_bits(cur.vx, vel.x) && same_bits(cur.vy, vel.y) && same_bits(cur.vz, vel.z);
+    const bool rc_same = dead || (both && !spawned && ((a.elide & kElideColor) != 0u) && same_curve_t(p.ColorFromLife.RangeAndCount, cur.life, pos.w, codes & 0xFFu) &&
+                                  same_curve_t(p.ColorFromVelocity.RangeAndCount, speed0, speed1, (codes >> 8) & 0xFFu));
+    const bool rdx_same = dead || (both && same_curve_t(p.SizeFromLife.RangeAndCount, cur.life, pos.w, (codes >> 16) & 0xFFu) &&
+                                   same_curve_t(p.SizeFromVelocity.RangeAndCount, speed0, speed1, codes >> 24) && (rd.x == rd.x));
+    bool rdy_same = dead;
+    if (a.update_bits & 2u) {
+        const float y0 = render_rotation(rotation_unscaled(cur.vx, cur.vy), cur.life, render_index(fx, fy), a.sys, p);
+        rdy_same = rdy_same || (both && same_bits(y0, rd.y) && (rd.y == rd.y));
+    }
+    const bool rdz_same = dead || (both && same_v);
+    const bool rdw_same = dead || (both && same_bits(cur.ct, vel.w) && (vel.w == vel.w));
+    if (__ballot(!rc_same) != 0ull) {
+        const float4 stored = mk4(ld_plane<STREAM>(up, 8, lane4), ld_plane<STREAM>(up, 9, lane4), ld_plane<STREAM>(up, 10, lane4), ld_plane<STREAM>(up, 11, lane4));
+        if (!SPAWN || !spawned) attr = stored;
+        float4 rd_unused;
+        render_data(fx, fy, pos, vel, attr, a.sys, p, codes, a.update_bits, nullptr, 0, 0, rc, rd_unused);
+        st_plane<STREAM>(up, 12, lane4, rc.x); st_plane<STREAM>(up, 13, lane4, rc.y); st_plane<STREAM>(up, 14, lane4, rc.z); st_plane<STREAM>(up, 15, lane4, rc.w);
+    }
+    if (__ballot(!rdx_same) != 0ull) st_plane<STREAM>(up, 16, lane4, rd.x);
+    if (__ballot(!rdy_same) != 0ull) st_plane<STREAM>(up, 17, lane4, rd.y);
+    if (__ballot(!rdz_same) != 0ull) st_plane<STREAM>(up, 18, lane4, rd.z);
+    if (__ballot(!rdw_same) != 0ull) st_plane<STREAM>(up, 19, lane4, rd.w);
+}
+
 
 template <bool SPAWN, bool STREAM>
 __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep a_) {
@@ -1346,7 +1421,13 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
             // a waterfall loop over a "divergent" buffer resource: +160 vector instructions per wave); the table is written by a copy
             // that precedes the launch on its stream and never during one
             const UnitPlanes up = unit_planes(((CBase*)a.chunk_bases)[chunk], a.stride, seg * 64);
-            const SlotIn cur = load_slot<true, STREAM>(up, lane4);
+            // a render-current chunk needs its attributes only where renderColor is recomputed: loaded below, by the waves that do
+            const bool elide = STREAM && (a.elide & kElideDerived) != 0u;
+            SlotIn cur = load_slot<false, STREAM>(up, lane4);
+            if (!elide) {
+                cur.ar = ld_plane<STREAM>(up, 8, lane4); cur.ag = ld_plane<STREAM>(up, 9, lane4);
+                cur.ab = ld_plane<STREAM>(up, 10, lane4); cur.aa = ld_plane<STREAM>(up, 11, lane4);
+            }
             // slot (x, y): the unit lies in one row (chunk size a multiple of 64)
             const int first = seg * 64;
             const int row = first >> a.cs_shift;
@@ -1394,7 +1475,8 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
                         pos = vel = zero;  // readStateOrDiscard: discard => cleared target
                     } else {
                         update_positions(pos, vel, a.sys, a.dt_s);
-                        render_data(fx, fy, pos, vel, attr, a.sys, a.update, a.bezier_codes, a.update_bits, nullptr, 0, 0, rc, rd);
+                        if (!elide)
+                            render_data(fx, fy, pos, vel, attr, a.sys, a.update, a.bezier_codes, a.update_bits, nullptr, 0, 0, rc, rd);
                     }
                 } else {
                     pos = vel = zero;
@@ -1402,15 +1484,22 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
             } else {
                 pos = vel = zero;
             }
-            st_plane<STREAM>(up, 0, lane4, pos.x); st_plane<STREAM>(up, 1, lane4, pos.y); st_plane<STREAM>(up, 2, lane4, pos.z); st_plane<STREAM>(up, 3, lane4, pos.w);
-            st_plane<STREAM>(up, 4, lane4, vel.x); st_plane<STREAM>(up, 5, lane4, vel.y); st_plane<STREAM>(up, 6, lane4, vel.z); st_plane<STREAM>(up, 7, lane4, vel.w);
+            // STREAM: a plane is stored when some lane of the wave changed its bits (integer compares: NaN and -0.0 exactly), at full width
+            st_plane_changed<STREAM>(up, 0, lane4, pos.x, cur.px); st_plane_changed<STREAM>(up, 1, lane4, pos.y, cur.py);
+            st_plane_changed<STREAM>(up, 2, lane4, pos.z, cur.pz); st_plane_changed<STREAM>(up, 3, lane4, pos.w, cur.life);
+            st_plane_changed<STREAM>(up, 4, lane4, vel.x, cur.vx); st_plane_changed<STREAM>(up, 5, lane4, vel.y, cur.vy);
+            st_plane_changed<STREAM>(up, 6, lane4, vel.z, cur.vz); st_plane_changed<STREAM>(up, 7, lane4, vel.w, cur.ct);
             if constexpr (SPAWN) {
                 if (spawned) {
                     st_plane<STREAM>(up, 8, lane4, attr.x); st_plane<STREAM>(up, 9, lane4, attr.y); st_plane<STREAM>(up, 10, lane4, attr.z); st_plane<STREAM>(up, 11, lane4, attr.w);
                 }
             }
-            st_plane<STREAM>(up, 12, lane4, rc.x); st_plane<STREAM>(up, 13, lane4, rc.y); st_plane<STREAM>(up, 14, lane4, rc.z); st_plane<STREAM>(up, 15, lane4, rc.w);
-            st_plane<STREAM>(up, 16, lane4, rd.x); st_plane<STREAM>(up, 17, lane4, rd.y); st_plane<STREAM>(up, 18, lane4, rd.z); st_plane<STREAM>(up, 19, lane4, rd.w);
+            if (!elide) {
+                st_plane<STREAM>(up, 12, lane4, rc.x); st_plane<STREAM>(up, 13, lane4, rc.y); st_plane<STREAM>(up, 14, lane4, rc.z); st_plane<STREAM>(up, 15, lane4, rc.w);
+                st_plane<STREAM>(up, 16, lane4, rd.x); st_plane<STREAM>(up, 17, lane4, rd.y); st_plane<STREAM>(up, 18, lane4, rd.z); st_plane<STREAM>(up, 19, lane4, rd.w);
+            } else {
+                store_changed_render_planes<SPAWN, STREAM>(a, up, lane4, fx, fy, cur, pos, vel, attr, spawned);
+            }
             n_live = (uint32_t)__popcll(__ballot(pos.w > 0.0f));
         }
     }
@@ -1865,6 +1954,18 @@ static bool build_lean_step(const StepLaunch& a, LeanStep& f) {
     return true;
 }
 
+// kElideColor: every point of the two colour curves is finite and at most 2^60 in magnitude, so each curve's value is finite (|t| <= 16
+// for every range and shaping mode: < 2^76) and the colour factor renderColor is formed from is never a NaN.  A NaN in renderColor then
+// comes from one attribute or is the default NaN of 0 x inf, so equal factors and unchanged attributes give the same bits, NaN payloads
+// included.
+static bool color_curves_bounded(const IlmUpdateParams& u) {
+    for (const IlmClampedBezier4* b : { &u.ColorFromLife, &u.ColorFromVelocity })
+        for (const IlmFloat4* q : { &b->A, &b->B, &b->C, &b->D })
+            for (const float x : { q->x, q->y, q->z, q->w })
+                if (!(std::fabs(x) <= 0x1p60f)) return false;
+    return true;
+}
+
 static hipError_t launch_lean_step(const LeanStep& f, bool spawning, bool streaming, hipStream_t stream) {
     const int units_per_block = kStepThreads / 64;
     const dim3 grid((unsigned)((f.total_units + units_per_block - 1) / units_per_block), 1, 1), block(kStepThreads, 1, 1);
@@ -2032,7 +2133,8 @@ int set_step_interpreter(int on) {
 
 // One launch per ParticleSystem.Update: the unit range covers every chunk of the step; when spawn records are
 // present the SPAWN variant runs (for every unit) and the grid is rotated to start at the first spawn range.
-hipError_t launch_step(StepLaunch& a, hipStream_t stream) {
+hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide, bool* refreshed) {
+    if (refreshed) *refreshed = false;
     a.units_per_chunk = a.span / 64;
     a.upc_shift = -1;
     for (int b = 0; b < 31; b++)
@@ -2069,8 +2171,12 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream) {
             }
         } else {
             LeanStep f;
-            if (build_lean_step(a, f))
-                return launch_lean_step(f, spawning, a.streaming != 0, stream);
+            if (build_lean_step(a, f)) {
+                f.elide = ((render_elide & kElideDerived) && a.streaming) ? (kElideDerived | (color_curves_bounded(a.desc.Update) ? kElideColor : 0u)) : 0u;
+                const hipError_t e = launch_lean_step(f, spawning, a.streaming != 0, stream);
+                if (refreshed) *refreshed = (e == hipSuccess);
+                return e;
+            }
         }
     }
     return spawning ? launch_step_variant<true>(a, stream) : launch_step_variant<false>(a, stream);
