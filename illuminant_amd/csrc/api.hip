@@ -2150,6 +2150,7 @@ int32_t ilm_debug_divide_by_constants(IlmHandle hctx, float* out_divisors, uint6
 }
 
 int32_t ilm_debug_step_interpreter(int32_t interpreter) { return (int32_t)set_step_interpreter(interpreter); }
+int32_t ilm_debug_last_step_kernel(void) { return (int32_t)last_step_kernel(); }
 int32_t ilm_debug_step_streams(int32_t streams) { return (int32_t)set_step_streams(streams); }
 int32_t ilm_debug_last_light_launch(IlmHandle hctx, int32_t* out_workgroups, int32_t* out_split, int32_t* out_tile_macro) {
     Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);

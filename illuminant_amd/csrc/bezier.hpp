@@ -85,6 +85,33 @@ ILM_DEV float t_for_coded_bezier(const IlmFloat4& rc, float value, uint32_t code
         t = t * t;
     return t;
 }
+// The clamp range with no shaping (code & ~0x13 == 0): t_for_coded_bezier's operations on that path, for callers whose launch has
+// established the class (particles.hip, step_lean_kernel<.., kCurvesClamp>) -- no fmodf or sinf code exists in them.
+ILM_DEV float t_for_clamp_bezier(const IlmFloat4& rc, float value, uint32_t code) {
+    const float t = (value - rc.x) * fabsf(rc.y);
+    return ((code & 16u) != 0u) ? (1.0f - sat(t)) : sat(t);
+}
+// evaluateBezier past its t: the value of a non-constant curve (count class 1-3) at a t already formed
+ILM_DEV float bezier1_at(const IlmClampedBezier1& bz, float t, uint32_t cls) {
+    const float a = bz.ABCD.x, b = bz.ABCD.y;
+    const float ab = lerp(a, b, t);
+    if (cls == 1u) return ab;
+    const float c = bz.ABCD.z;
+    if (cls == 2u) return (t <= 0.0f) ? a : ((t >= 1.0f) ? c : b);
+    const float d = bz.ABCD.w;
+    const float bc = lerp(b, c, t), cd = lerp(c, d, t);
+    return lerp(lerp(ab, bc, t), lerp(bc, cd, t), t);
+}
+ILM_DEV float4 bezier4_at(const IlmClampedBezier4& bz, float t, uint32_t cls) {
+    const float4 a = ld4(bz.A), b = ld4(bz.B);
+    const float4 ab = lerp4(a, b, t);
+    if (cls == 1u) return ab;
+    const float4 c = ld4(bz.C);
+    if (cls == 2u) return (t <= 0.0f) ? a : ((t >= 1.0f) ? c : b);
+    const float4 d = ld4(bz.D);
+    const float4 bc = lerp4(b, c, t), cd = lerp4(c, d, t);
+    return lerp4(lerp4(ab, bc, t), lerp4(bc, cd, t), t);
+}
 ILM_DEV float bezier1_coded(const IlmClampedBezier1& bz, float value, uint32_t code) {
     const uint32_t cls = code & 3u;
     const float a = bz.ABCD.x;

@@ -129,6 +129,7 @@ hipError_t step_sdf_sample_counter(int enable, unsigned long long* out);   // il
 bool step_wants_slice0_cells(const IlmStepDesc& d, int format);
 hipError_t launch_build_slice0_cells(const uint2* texels, int width, int height, void* cells, hipStream_t stream);
 int set_step_interpreter(int on);     // ilm_debug_step_interpreter: returns the previous setting
+int last_step_kernel();               // ilm_debug_last_step_kernel: ILM_STEP_KERNEL_* of the process's latest launch_step
 int set_step_streams(int n);          // ilm_debug_step_streams: 1 keeps every step on the context stream, 2 (default) lets large steps use two; returns the previous setting
 // the context's stream for work that is not a particle step: ordered after everything the context's second stepping stream holds (api.hip)
 hipStream_t ctx_stream_joined(IlmHandle ctx);

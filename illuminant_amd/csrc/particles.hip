@@ -705,6 +705,16 @@ ILM_DEV void update_positions(float4& pos, float4& vel, const IlmParticleSystemU
         vel = mk4(velocity.x, velocity.y, velocity.z, vel.w);
     }
 }
+// The same for every lane at once: `live` says which lanes are a live slot after the transforms, the others (and a life that runs out
+// here) come out as the cleared target's zeros.  One select per component where nested lane-divergent branches would each zero all eight.
+ILM_DEV void update_positions_select(float4& pos, float4& vel, const IlmParticleSystemUniforms& sys, float dts, bool live) {
+#pragma clang fp contract(off)   // life arithmetic is bit-exact
+    const f3 velocity = friction_and_maximum(xyz(vel), sys, dts);
+    const float new_life = pos.w - (sys.GlobalSettings.w * dts);
+    const bool keep = live && !(new_life <= 0.0f);
+    pos = mk4(keep ? pos.x + velocity.x * dts : 0.0f, keep ? pos.y + velocity.y * dts : 0.0f, keep ? pos.z + velocity.z * dts : 0.0f, keep ? new_life : 0.0f);
+    vel = mk4(keep ? velocity.x : 0.0f, keep ? velocity.y : 0.0f, keep ? velocity.z : 0.0f, keep ? vel.w : 0.0f);
+}
 
 // Diagnostic (ilm_debug_step_sdf_samples): how many sampleDistanceFieldEx calls the collision update makes -- the unit of its roofline
 // (bench.py collision_step_1m).  The flag is read by a scalar load; the counter costs nothing while it is off.
@@ -1390,9 +1400,79 @@ ILM_DEV void store_changed_render_planes(const LeanStep& a, const UnitPlanes& up
     if (__ballot(!rdw_same) != 0ull) st_plane<STREAM>(up, 19, lane4, rd.w);
 }
 
+// The curve classes of the streaming lean step (launch_lean_step selects, ilm_debug_last_step_kernel reports): compile-time
+// instantiations of step_lean_block (step_lean_kernel<..> / step_lean_clamp_kernel).  kCurvesClamp: every
+// curve of the update pass is constant or has the clamp range and no shaping (bezier_codes & ~kClampCodes == 0), the velocity rotation
+// is zero and there is no life ramp (update_bits == 2), the launch elides (kElideDerived) and has no spawner (the spawning kernel's
+// registers are the spawn path's: a class of it would gain little).  The instantiation holds no fmodf, sinf or atan2f code; which curves
+// are constant stays a scalar test.
+constexpr int kCurvesGeneral = 0, kCurvesClamp = 1;
+constexpr uint32_t kClampCodes = 0x13131313u;      // per curve: the count class (bits 0-1) and the sign of the inverse divisor (bit 4)
 
-template <bool SPAWN, bool STREAM>
-__global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep a_) {
+// One curve's part in the elision proof and in the value: t for the loaded and the new state, formed once.
+struct CurveT { float t1; bool same; };
+ILM_DEV CurveT clamp_curve_t(const IlmFloat4& rc, float v0, float v1, uint32_t code) {
+    CurveT c = { 0.0f, true };      // a constant curve reads no t
+    if ((code & 3u) != 0u) {
+        c.t1 = t_for_clamp_bezier(rc, v1, code);
+        c.same = same_bits(t_for_clamp_bezier(rc, v0, code), c.t1) && (c.t1 == c.t1);
+    }
+    return c;
+}
+// store_changed_render_planes for kCurvesClamp: the same stores of the same bits (the rules above, render_data's operations on the same
+// operands), with each t and the new state's speed formed once and shared by the proof and the value, and the dead lanes selected at
+// the end instead of branched around.  (No spawner: the attributes are the stored ones.)
+ILM_DEV void store_changed_render_planes_clamp(const LeanStep& a, const UnitPlanes& up, unsigned lane4, float fx, float fy, const SlotIn& cur,
+                                               float4 pos, float4 vel) {
+    const IlmUpdateParams& p = a.update;
+    const uint32_t codes = a.bezier_codes & kClampCodes;
+    const uint32_t c_cl = codes & 0xFFu, c_cv = (codes >> 8) & 0xFFu, c_sl = (codes >> 16) & 0xFFu, c_sv = codes >> 24;
+    const bool live0 = !(cur.life <= 0.0f), live1 = !(pos.w <= 0.0f);
+    const bool dead = !live0 && !live1, both = live0 && live1;
+    const float index = render_index(fx, fy);
+    const float speed1 = fmaxf(len3_fast(xyz(vel)), 0.0001f);
+    float speed0 = 0.0f;
+    if ((codes & 0x03000300u) != 0u)        // the loaded state's speed, only where a velocity curve is not constant
+        speed0 = fmaxf(len3_fast(mk3(cur.vx, cur.vy, cur.vz)), 0.0001f);
+    const CurveT cl = clamp_curve_t(p.ColorFromLife.RangeAndCount, cur.life, pos.w, c_cl);
+    const CurveT cv = clamp_curve_t(p.ColorFromVelocity.RangeAndCount, speed0, speed1, c_cv);
+    const CurveT sl = clamp_curve_t(p.SizeFromLife.RangeAndCount, cur.life, pos.w, c_sl);
+    const CurveT sv = clamp_curve_t(p.SizeFromVelocity.RangeAndCount, speed0, speed1, c_sv);
+    const float size_l = ((c_sl & 3u) == 0u) ? p.SizeFromLife.ABCD.x : bezier1_at(p.SizeFromLife, sl.t1, c_sl & 3u);
+    const float size_v = ((c_sv & 3u) == 0u) ? p.SizeFromVelocity.ABCD.x : bezier1_at(p.SizeFromVelocity, sv.t1, c_sv & 3u);
+    float4 rd;
+    rd.x = live1 ? size_l * size_v : 0.0f;
+    rd.y = live1 ? render_rotation(rotation_unscaled(vel.x, vel.y), pos.w, index, a.sys, p) : 0.0f;
+    rd.z = live1 ? speed1 : 0.0f;
+    rd.w = live1 ? vel.w : 0.0f;
+    const float y0 = render_rotation(rotation_unscaled(cur.vx, cur.vy), cur.life, index, a.sys, p);
+    const bool same_v = same_bits(cur.vx, vel.x) && same_bits(cur.vy, vel.y) && same_bits(cur.vz, vel.z);
+    const bool rc_same = dead || (both && ((a.elide & kElideColor) != 0u) && cl.same && cv.same);
+    const bool rdx_same = dead || (both && sl.same && sv.same && (rd.x == rd.x));
+    const bool rdy_same = dead || (both && same_bits(y0, rd.y) && (rd.y == rd.y));
+    const bool rdz_same = dead || (both && same_v);
+    const bool rdw_same = dead || (both && same_bits(cur.ct, vel.w) && (vel.w == vel.w));
+    if (__ballot(!rc_same) != 0ull) {
+        const float4 attr = mk4(ld_plane<true>(up, 8, lane4), ld_plane<true>(up, 9, lane4), ld_plane<true>(up, 10, lane4), ld_plane<true>(up, 11, lane4));
+        const float4 color_l = ((c_cl & 3u) == 0u) ? ld4(p.ColorFromLife.A) : bezier4_at(p.ColorFromLife, cl.t1, c_cl & 3u);
+        const float4 color_v = ((c_cv & 3u) == 0u) ? ld4(p.ColorFromVelocity.A) : bezier4_at(p.ColorFromVelocity, cv.t1, c_cv & 3u);
+        float4 rc = mul4(attr, mul4(color_l, color_v));
+        rc.w = sat(rc.w);
+        rc.x *= rc.w; rc.y *= rc.w; rc.z *= rc.w;
+        st_plane<true>(up, 12, lane4, live1 ? rc.x : 0.0f); st_plane<true>(up, 13, lane4, live1 ? rc.y : 0.0f);
+        st_plane<true>(up, 14, lane4, live1 ? rc.z : 0.0f); st_plane<true>(up, 15, lane4, live1 ? rc.w : 0.0f);
+    }
+    if (__ballot(!rdx_same) != 0ull) st_plane<true>(up, 16, lane4, rd.x);
+    if (__ballot(!rdy_same) != 0ull) st_plane<true>(up, 17, lane4, rd.y);
+    if (__ballot(!rdz_same) != 0ull) st_plane<true>(up, 18, lane4, rd.z);
+    if (__ballot(!rdw_same) != 0ull) st_plane<true>(up, 19, lane4, rd.w);
+}
+
+
+// One block of the lean step, for one curve class (the kernels below).
+template <bool SPAWN, bool STREAM, int CURVES>
+ILM_DEV void step_lean_block() {
+    static_assert(CURVES == kCurvesGeneral || (STREAM && !SPAWN), "the curve classes are instantiations of the streaming variant without spawners");
     __shared__ uint32_t wave_live[kStepThreads / 64];
     const LeanStep& a = *(const LeanStep*)(CLeanStep*)__builtin_amdgcn_kernarg_segment_ptr();
     // (only the launch's first generation of blocks can be the first to read a line; for the others the loads would just load the
@@ -1422,7 +1502,7 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
             // that precedes the launch on its stream and never during one
             const UnitPlanes up = unit_planes(((CBase*)a.chunk_bases)[chunk], a.stride, seg * 64);
             // a render-current chunk needs its attributes only where renderColor is recomputed: loaded below, by the waves that do
-            const bool elide = STREAM && (a.elide & kElideDerived) != 0u;
+            const bool elide = STREAM && ((CURVES == kCurvesClamp) || (a.elide & kElideDerived) != 0u);
             SlotIn cur = load_slot<false, STREAM>(up, lane4);
             if (!elide) {
                 cur.ar = ld_plane<STREAM>(up, 8, lane4); cur.ag = ld_plane<STREAM>(up, 9, lane4);
@@ -1459,7 +1539,29 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
             const bool process = !(cur.life <= 0.0f) || spawn_here;
             const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
             float4 rc = zero, rd = zero;
-            if (__ballot(process) != 0ull) {
+            if constexpr (CURVES == kCurvesClamp) {
+                if (__ballot(process) != 0ull) {
+                    // Every lane goes through the transforms and the update, and one select at the end keeps the live ones: a slot the
+                    // step does not process comes out as zeros whatever was computed for it.  The transforms are dispatched from
+                    // unrolled positions so that position and velocity stay in their registers from one to the next.
+#pragma unroll
+                    for (int o = 0; o < ILM_MAX_OPS; o++) {
+                        if (o < a.op_count) {
+                            const int type = a.op_type[o];
+                            if (type == ILM_OP_GRAVITY)
+                                apply_gravity_lean(pos, vel, a.op[o].gravity, a.sys.GlobalSettings.x, a.sys.GlobalSettings.z);
+                            else if (type == ILM_OP_NOISE)
+                                apply_noise(pos, vel, fx, fy, a.rnd, a.rw, a.rh, a.sys, a.op[o].noise, a.inv_rw, a.inv_rh, a.dop[o],
+                                            (o == a.noise_op) ? noise : NoiseDeltas{ false, zero, zero });
+                            else
+                                apply_fma(pos, vel, a.sys, a.op[o].fma, a.dop[o]);
+                        }
+                    }
+                    update_positions_select(pos, vel, a.sys, a.dt_s, process && !(pos.w <= 0.0f));
+                } else {
+                    pos = vel = zero;
+                }
+            } else if (__ballot(process) != 0ull) {
                 if (process) {
                     for (int o = 0; o < a.op_count; o++) {
                         const int type = a.op_type[o];
@@ -1497,6 +1599,8 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
             if (!elide) {
                 st_plane<STREAM>(up, 12, lane4, rc.x); st_plane<STREAM>(up, 13, lane4, rc.y); st_plane<STREAM>(up, 14, lane4, rc.z); st_plane<STREAM>(up, 15, lane4, rc.w);
                 st_plane<STREAM>(up, 16, lane4, rd.x); st_plane<STREAM>(up, 17, lane4, rd.y); st_plane<STREAM>(up, 18, lane4, rd.z); st_plane<STREAM>(up, 19, lane4, rd.w);
+            } else if constexpr (CURVES == kCurvesClamp) {
+                store_changed_render_planes_clamp(a, up, lane4, fx, fy, cur, pos, vel);
             } else {
                 store_changed_render_planes<SPAWN, STREAM>(a, up, lane4, fx, fy, cur, pos, vel, attr, spawned);
             }
@@ -1508,6 +1612,13 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep 
                             (v & ((1 << a.upc_shift) - 1)) / (kStepThreads / 64), (1 << a.upc_shift) / (kStepThreads / 64), a.count_buckets,
                             a.live_counts, a.zero_counts, a.zero_n, a.host_counts, a.count_seq);
 }
+
+// The general instantiations keep the kernel names the profiles and bench.py's traffic figures are keyed by; the class is a kernel of
+// its own (a class selected inside step_lean_kernel<false, true> by a launch-uniform word took the kernel from 8 waves per SIMD to 7 and
+// the headline from 0.78 to 0.89 ms).
+template <bool SPAWN, bool STREAM>
+__global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep a_) { step_lean_block<SPAWN, STREAM, kCurvesGeneral>(); }
+__global__ __launch_bounds__(kStepThreads) void step_lean_clamp_kernel(const LeanStep a_) { step_lean_block<false, true, kCurvesClamp>(); }
 
 // ---------------------------------------------------------------------------------------------
 // the lean collision step (r06) -- UpdateParticleSystemWithDistanceField.fx:29-147 on the lean descriptor
@@ -1966,16 +2077,29 @@ static bool color_curves_bounded(const IlmUpdateParams& u) {
     return true;
 }
 
+// Which kernel the process's latest launch_step ran (ilm_debug_last_step_kernel): a diagnostic, like g_step_interpreter below.
+static std::atomic<int> g_last_step_kernel{ILM_STEP_KERNEL_NONE};
+int last_step_kernel() { return g_last_step_kernel; }
+
+// kCurvesClamp's rule (see the constants): a streaming launch without spawners that elides, whose curves all have the clamp range and no
+// shaping, with no velocity rotation and no life ramp.  Everything else runs the general instantiation.
+static bool curves_clamp(const LeanStep& f, bool spawning, bool streaming) {
+    return streaming && !spawning && (f.elide & kElideDerived) != 0u && (f.bezier_codes & ~kClampCodes) == 0u && f.update_bits == 2u;
+}
+
 static hipError_t launch_lean_step(const LeanStep& f, bool spawning, bool streaming, hipStream_t stream) {
     const int units_per_block = kStepThreads / 64;
     const dim3 grid((unsigned)((f.total_units + units_per_block - 1) / units_per_block), 1, 1), block(kStepThreads, 1, 1);
+    const bool clamp = curves_clamp(f, spawning, streaming);
     if (spawning) {
         if (streaming) hipLaunchKernelGGL((step_lean_kernel<true, true>), grid, block, 0, stream, f);
         else hipLaunchKernelGGL((step_lean_kernel<true, false>), grid, block, 0, stream, f);
     } else {
-        if (streaming) hipLaunchKernelGGL((step_lean_kernel<false, true>), grid, block, 0, stream, f);
+        if (clamp) hipLaunchKernelGGL(step_lean_clamp_kernel, grid, block, 0, stream, f);
+        else if (streaming) hipLaunchKernelGGL((step_lean_kernel<false, true>), grid, block, 0, stream, f);
         else hipLaunchKernelGGL((step_lean_kernel<false, false>), grid, block, 0, stream, f);
     }
+    g_last_step_kernel = clamp ? ILM_STEP_KERNEL_LEAN_CLAMP : ILM_STEP_KERNEL_LEAN;
     return hipGetLastError();
 }
 
@@ -2167,6 +2291,7 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide,
             if (lean_df && build_lean_step(a, f.base)) {
                 f.df = a.desc.DistanceField;
                 f.sdf = a.sdf;
+                g_last_step_kernel = ILM_STEP_KERNEL_LEAN_DF;
                 return launch_lean_df_step(f, a, spawning, stream);
             }
         } else {
@@ -2179,6 +2304,7 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide,
             }
         }
     }
+    g_last_step_kernel = ILM_STEP_KERNEL_INTERPRETER;
     return spawning ? launch_step_variant<true>(a, stream) : launch_step_variant<false>(a, stream);
 }
 

@@ -76,6 +76,7 @@ SYMBOLS = {
     "ilm_debug_sdf_sample_inside": (_I, [_H, _P, _P, _I, _P, _P]),
     "ilm_debug_divide": (_I, [_H, _P, _P, _I, _P, _P]),
     "ilm_debug_step_interpreter": (_I, [_I]),
+    "ilm_debug_last_step_kernel": (_I, []),
     "ilm_debug_step_streams": (_I, [_I]),
     "ilm_debug_step_sdf_samples": (_I, [_H, _I, C.POINTER(C.c_uint64)]),
     "ilm_debug_last_light_launch": (_I, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

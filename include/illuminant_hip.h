@@ -502,6 +502,15 @@ int32_t ilm_debug_divide_by_constants(IlmHandle ctx, float* out_divisors, uint64
  * per-slot arithmetic is the same.  interpreter != 0 forces the interpreting kernel for every later step of this process (0: the
  * default choice) so that a test can hold the two bit-equal; returns the previous setting.  Environment: ILM_STEP_LEAN=0. */
 int32_t ilm_debug_step_interpreter(int32_t interpreter);
+/* Diagnostic: which kernel the latest ilm_system_step launch of this process ran, so that a test can tell that the case it built
+ * reached the instantiation it is meant to hold bit-equal.  LEAN_CLAMP: the streaming specialised kernel's class for update passes
+ * whose curves are all constant or clamp-ranged without shaping, with no velocity rotation and no life ramp. */
+#define ILM_STEP_KERNEL_NONE         0   /* no step launched yet */
+#define ILM_STEP_KERNEL_INTERPRETER  1
+#define ILM_STEP_KERNEL_LEAN         2   /* the specialised kernel, general instantiation (cache-resident or streaming) */
+#define ILM_STEP_KERNEL_LEAN_CLAMP   3
+#define ILM_STEP_KERNEL_LEAN_DF      4   /* the specialised collision step */
+int32_t ilm_debug_last_step_kernel(void);
 /* A step over at least two chunks and half a million slots puts the second half of its chunk range on a second stream of the context
  * (chunks never interact, ParticleSystem.cs:743-745; every other entry point waits for both streams before it touches anything).
  * streams == 1 keeps every later step of this process on the context stream, 2 restores the default; returns the previous setting.

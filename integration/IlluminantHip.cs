@@ -33,6 +33,11 @@ namespace Squared.Illuminant.Native {
         public const int RANDOMNESS_HEIGHT = 653;
         public const int RANDOMNESS_WIDTH = 807;
         public const int STEP_COUNT_LIVE = 1;
+        public const int STEP_KERNEL_INTERPRETER = 1;
+        public const int STEP_KERNEL_LEAN = 2;
+        public const int STEP_KERNEL_LEAN_CLAMP = 3;
+        public const int STEP_KERNEL_LEAN_DF = 4;
+        public const int STEP_KERNEL_NONE = 0;
         public const float DISTANCE_LIMIT = 520.0f;
         public const int OP_GRAVITY = 1;
         public const int OP_NOISE = 2;
@@ -513,6 +518,7 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_divide (ulong ctx, float* numerators, float* denominators, int count, float* outFast, float* outIeee);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_divide_by_constants (ulong ctx, float* outDivisors, ulong* outMismatches, int capacity, int* outCount);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_step_interpreter (int interpreter);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_last_step_kernel ();
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_step_streams (int streams);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_step_sdf_samples (ulong ctx, int enable, ulong* outSamples);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_last_light_launch (ulong ctx, int* outWorkgroups, int* outSplit, int* outTileMacro);
