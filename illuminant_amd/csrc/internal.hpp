@@ -22,7 +22,6 @@ constexpr int kSlotsPerThread = 4;         // widest variant; strides are padded
 // CU more evenly in pairs of waves than in fours (tools/step_ab.py r02: cfg2 with the spawner 22.1 -> 20.9 us per step, others unchanged)
 constexpr int kStepThreads = 128;
 constexpr int kSlotsPerBlock = 1024;       // strides are padded to this
-constexpr int kUnitsPerWave = 1;           // units (64 slots each) a wave loads up front and then processes in turn
 
 // Values every wave would otherwise recompute on the vector ALU from uniform inputs (gfx950 has no scalar float
 // unit): filled on the host with the SAME IEEE single-precision operations, in the same order, as the per-slot

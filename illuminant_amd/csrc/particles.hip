@@ -4,16 +4,29 @@
 // the spawner pass, every active transform and the update pass are applied to a
 // slot in registers, in the reference's pass order, so a chunk streams through
 // HBM once (48 B read + 64 B written per live slot) instead of once per pass.
-// State is SoA; a wave owns 64 consecutive slots (one lane = one slot), so every
+// State is SoA; one wave = one unit of 64 consecutive slots (one lane = one slot), so every
 // access is one dword per lane on an SGPR plane base: 256 contiguous bytes per instruction.
+// The hardware dispatcher balances the waves; nothing is persistent or software-pipelined.
 //
-// HBM-bound integer/float streaming work: no MFMA, no LDS (no cross-slot reuse).
+// Three kernels run a step (launch_step chooses; ilm_debug_last_step_kernel reports):
+//   step_kernel            interprets any IlmStepDesc: every transform, spawner kind and update mode.  Runs what
+//                          the lean kernels do not accept, and everything under ILM_STEP_LEAN=0 / ILM_DF_LEAN=0.
+//   step_lean_kernel,      the common shape of a step (power-of-two chunks, UpdatePositions, Gravity / Noise /
+//   step_lean_clamp_kernel FMA, inline spawners) from a pre-digested descriptor; the clamp class is the
+//                          streaming launch whose curves all have the clamp range.
+//   step_lean_df_kernel    the same shape with UpdateWithDistanceField: K units per wave, the colliding
+//                          lanes parked and finished at full width.
+// The per-slot arithmetic is stated once and shared by all three (gravity_term, apply_noise, apply_fma,
+// spawn_slot, df_long, render_data): the GPU tests hold the kernels to each other bit for bit.
+//
+// HBM-bound integer/float streaming work: no MFMA; LDS only for the parked lanes of the collision kernel.
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
 
 #include <atomic>
+#include <type_traits>
 #include "internal.hpp"
 #include "distance_functions.hpp"
 #include "bezier.hpp"
@@ -78,52 +91,45 @@ ILM_DEV void area_weight_and_t(const IlmAreaParams& a, const StepDerived::Op& dv
 // PS_Gravity, Gravity.fx:12-61.  Every +, -, * rounds as the oracle's (this file is compiled with -ffp-contract=off like the rest of
 // the library), so d^2 and the type-0 branch's d^2 - radius are bit-identical to it.  normalize(toCenter), distance / radius and the
 // acceleration cap use v_rsq_f32 / v_rcp_f32 (1 ulp -- the accuracy Direct3D itself grants the reference's rcp / rsq / div): relative
-// error of each attractor's term <= 4e-7, velocities only.  -DILM_GRAVITY_EXACT builds the IEEE sqrt / division form, bit-identical to
-// the oracle, at +14 % step time on cfg2 and cfg4 (measured r02: 25.9 -> 29.3 us, 175 -> 201 us).
-ILM_DEV void apply_gravity(float4& pos, float4& vel, const IlmParticleSystemUniforms& sys, const IlmGravityParams& p, const StepDerived::Op& dv) {
-    if ((pos.w <= 0.0f) || !category_ok(vel.w, p.CategoryFilter))
-        return;
-    const float dt_ms = sys.GlobalSettings.x;
-    f3 acceleration = mk3(0.0f, 0.0f, 0.0f);
-    for (int i = 0; i < p.AttractorCount; i++) {
-        const f3 apos = mk3(p.AttractorPositions[i][0], p.AttractorPositions[i][1], p.AttractorPositions[i][2]);
-        const float radius = p.AttractorRadiusesAndStrengths[i][0];
-        const float strength = p.AttractorRadiusesAndStrengths[i][1];
-        const float type = p.AttractorRadiusesAndStrengths[i][2];
-        const f3 to_center = apos - xyz(pos);
-        float attraction;
-        const float d2 = dot3(to_center, to_center);
+// error of each attractor's term <= 4e-7, velocities only.  The gravity-exact build (the Makefile's second library) takes the IEEE
+// sqrt / division form, bit-identical to the oracle, at +14 % step time on cfg2 and cfg4 (measured r02: 25.9 -> 29.3 us, 175 -> 201 us).
+// One attractor's term of the acceleration (Gravity.fx:36-52); type 0 physical, 1 linear, 2 squared.  The interpreter, the lean
+// kernels' loop and their four-at-a-time block all form it here.
+ILM_DEV f3 gravity_term(f3 to_center, uint32_t type, float radius, float strength, float dt_ms) {
+    float attraction;
+    const float d2 = dot3(to_center, to_center);
 #ifndef ILM_GRAVITY_EXACT
-        const float inv_len = fast_rsq(d2);
-        if (type >= 0.5f) {
-            const float distance = d2 * inv_len;
-            attraction = 1.0f - sat(distance * fast_rcp(radius));
-            if (type >= 1.5f)
-                attraction *= attraction;
-            attraction = attraction * dt_ms * (1.0f / kVelocityConstantScale);
-        } else {
-            // the one place of this pass where an operand can cancel (d^2 - radius just above its 0.001 floor): the reference's own
-            // operations, IEEE division included (the attractor type is uniform: physical-type attractors pay, the others do not)
-            const float distance_squared = fmaxf(d2 - radius, 0.001f);
-            attraction = 1.0f / distance_squared;
-        }
-        acceleration = acceleration + (((to_center * inv_len) * attraction) * strength);
-#else
-        const float distance = sqrtf(d2);
-        if (type >= 0.5f) {
-            attraction = 1.0f - sat(distance / radius);
-            if (type >= 1.5f)
-                attraction *= attraction;
-            attraction = attraction * dt_ms / kVelocityConstantScale;
-        } else {
-            const float distance_squared = fmaxf(d2 - radius, 0.001f);
-            attraction = 1.0f / distance_squared;
-        }
-        const f3 n = mk3(to_center.x / distance, to_center.y / distance, to_center.z / distance);
-        acceleration = acceleration + ((n * attraction) * strength);
-#endif
+    const float inv_len = fast_rsq(d2);
+    if (type != 0u) {
+        const float distance = d2 * inv_len;
+        attraction = 1.0f - sat(distance * fast_rcp(radius));
+        if (type == 2u)
+            attraction *= attraction;
+        attraction = attraction * dt_ms * (1.0f / kVelocityConstantScale);
+    } else {
+        // the one place of this pass where an operand can cancel (d^2 - radius just above its 0.001 floor): the reference's own
+        // operations, IEEE division included (the attractor type is uniform: physical-type attractors pay, the others do not)
+        const float distance_squared = fmaxf(d2 - radius, 0.001f);
+        attraction = 1.0f / distance_squared;
     }
-    const float maximum_acceleration = dv.max_accel;
+    return ((to_center * inv_len) * attraction) * strength;
+#else
+    const float distance = sqrtf(d2);
+    if (type != 0u) {
+        attraction = 1.0f - sat(distance / radius);
+        if (type == 2u)
+            attraction *= attraction;
+        attraction = attraction * dt_ms / kVelocityConstantScale;
+    } else {
+        const float distance_squared = fmaxf(d2 - radius, 0.001f);
+        attraction = 1.0f / distance_squared;
+    }
+    const f3 n = mk3(to_center.x / distance, to_center.y / distance, to_center.z / distance);
+    return (n * attraction) * strength;
+#endif
+}
+// The acceleration cap and the clamped add to the velocity (Gravity.fx:54-60); mv = the system's maximum velocity
+ILM_DEV void gravity_finish(float4& vel, f3 acceleration, float maximum_acceleration, float mv) {
 #ifndef ILM_GRAVITY_EXACT
     const float a2 = dot3(acceleration, acceleration);
     if (a2 > maximum_acceleration * maximum_acceleration)
@@ -133,10 +139,22 @@ ILM_DEV void apply_gravity(float4& pos, float4& vel, const IlmParticleSystemUnif
     if (current_length > maximum_acceleration)
         acceleration = mk3(acceleration.x / current_length, acceleration.y / current_length, acceleration.z / current_length) * maximum_acceleration;
 #endif
-    const float mv = sys.GlobalSettings.z;
     vel.x = fminf(mv, vel.x + acceleration.x);
     vel.y = fminf(mv, vel.y + acceleration.y);
     vel.z = fminf(mv, vel.z + acceleration.z);
+}
+ILM_DEV void apply_gravity(float4& pos, float4& vel, const IlmParticleSystemUniforms& sys, const IlmGravityParams& p, const StepDerived::Op& dv) {
+    if ((pos.w <= 0.0f) || !category_ok(vel.w, p.CategoryFilter))
+        return;
+    const float dt_ms = sys.GlobalSettings.x;
+    f3 acceleration = mk3(0.0f, 0.0f, 0.0f);
+    for (int i = 0; i < p.AttractorCount; i++) {
+        const f3 apos = mk3(p.AttractorPositions[i][0], p.AttractorPositions[i][1], p.AttractorPositions[i][2]);
+        const float type = p.AttractorRadiusesAndStrengths[i][2];
+        acceleration = acceleration + gravity_term(apos - xyz(pos), (type >= 1.5f) ? 2u : ((type >= 0.5f) ? 1u : 0u),
+                                                   p.AttractorRadiusesAndStrengths[i][0], p.AttractorRadiusesAndStrengths[i][1], dt_ms);
+    }
+    gravity_finish(vel, acceleration, dv.max_accel, sys.GlobalSettings.z);
 }
 
 ILM_DEV float fma_term_exact(float v, float m, float a) {
@@ -210,28 +228,27 @@ ILM_DEV void apply_noise(float4& pos, float4& vel, float x, float y, const float
 }
 
 // The wave-uniform form of the four lookups (StepDerived::NoiseFast): (x0, row) = slot coordinates of the wave's first lane, the wave
-// covers x0 .. x0 + 63 of that row (chunk size a multiple of 64).  Scalar integer code only; the deltas arrive in SGPRs.
-ILM_DEV NoiseDeltas noise_prepare(const StepDerived::NoiseFast& nf, const IlmStepDesc& desc, int x0, int row) {
+// covers x0 .. x0 + 63 of that row (chunk size a multiple of 64).  Scalar integer code only; the deltas arrive in SGPRs.  The class
+// counts are sign bits (2 scalar instructions per boundary); `big` = where the launch keeps the 5 x 5 tables (kNoiseBigClasses).
+ILM_DEV NoiseDeltas noise_prepare(const StepDerived::NoiseFast& nf, const IlmFloat4* big, int x0, int row) {
     NoiseDeltas out;
     const uint32_t code = nf.wcode[x0 >> 6];
     out.valid = (code & 64u) != 0u;
-    int yc0 = 0, yc1 = 0;
+    uint32_t yc0 = 0, yc1 = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        yc0 += (row >= nf.yb[k]) ? 1 : 0;
-        yc1 += (row + 1 >= nf.yb[k]) ? 1 : 0;
+        const int b = nf.yb[k];                              // a row >= 0 or INT32_MAX
+        yc0 += (uint32_t)(b - 1 - row) >> 31;                // row >= b
+        yc1 += (uint32_t)(b - 2 - row) >> 31;                // row + 1 >= b
     }
-    const int xc0 = (int)(code & 7u), xc1 = (int)((code >> 3) & 7u);
-    if (nf.classes == kNoiseBigClasses) {
-        const IlmFloat4* table = reinterpret_cast<const IlmFloat4*>(&desc.Spawns[0]);
-        out.position = ld4(table[yc0 * kNoiseBigClasses + xc0]);
-        out.velocity = ld4(table[kNoiseBigClasses * kNoiseBigClasses + yc1 * kNoiseBigClasses + xc1]);
-    } else {
-        out.position = ld4(nf.position[yc0][xc0]);
-        out.velocity = ld4(nf.velocity[yc1][xc1]);
-    }
+    const uint32_t xc0 = code & 7u, xc1 = (code >> 3) & 7u;
+    const uint32_t n = (uint32_t)nf.classes;
+    const IlmFloat4* table = (n == (uint32_t)kNoiseBigClasses) ? big : &nf.position[0][0];   // position[n][n] then velocity[n][n]
+    out.position = ld4(table[yc0 * n + xc0]);
+    out.velocity = ld4(table[n * n + yc1 * n + xc1]);
     return out;
 }
+static_assert(offsetof(StepDerived::NoiseFast, velocity) == offsetof(StepDerived::NoiseFast, position) + 9 * sizeof(IlmFloat4), "velocity[3][3] follows position[3][3]");
 
 // mul3, ParticleCommon.fxh:183-196
 ILM_DEV float4 mul_point(f3 v, const IlmMatrix& M);
@@ -737,977 +754,10 @@ ILM_DEV f3 estimate_normal4(f3 position, const IlmDistanceFieldUniforms& df, con
     return norm3(result);
 }
 
-// PS_Update, UpdateParticleSystemWithDistanceField.fx:29-147 (live slot)
-template <int FMT>
-ILM_DEV void update_with_distance_field(float4& pos, float4& vel, float x, float y, const IlmParticleSystemUniforms& sys, float dts,
-                                        const IlmDistanceFieldUniforms& df, const SdfView& sdf, int& samples) {
-#pragma clang fp contract(off)   // discontinuous collision state machine + life arithmetic: keep IEEE-exact
-    const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
-    float new_life = pos.w - (sys.GlobalSettings.w * dts);
-    if (new_life <= 0.0f) {
-        pos = vel = zero;
-        return;
-    }
-    const float collision_distance = sys.CollisionSettings.z;
-    const float max_velocity = sys.GlobalSettings.z;
-    const f3 old_xyz = xyz(pos);
-    const f3 unit_vector = norm3(xyz(vel));
-    const f3 velocity = friction_and_maximum(xyz(vel), sys, dts);
-    const f3 scaled_velocity = velocity * dts;
-
-    bool collided = false, escaping = false;
-    f3 collision_position = mk3(0.0f, 0.0f, 0.0f), new_position = old_xyz;
-    float4 new_velocity = zero;
-
-    const float initial_distance = sample_distance_field<(FMT & 1), true, (FMT & 2) != 0>(old_xyz, df, sdf);
-    samples++;
-    const bool was_colliding = initial_distance < collision_distance;
-    float travel_distance = fmaxf(0.0f, fminf(initial_distance, len3(scaled_velocity)));
-    int step_count = ref::kMaxStepCount;
-    if (was_colliding)
-        step_count = 1;
-    else if (travel_distance <= 0.001f)
-        step_count = 0;
-
-    for (int i = 0; i < step_count; i++) {
-        const f3 test_position = old_xyz + (unit_vector * travel_distance);
-        const float step_distance = sample_distance_field<(FMT & 1), true, (FMT & 2) != 0>(test_position, df, sdf);
-        samples++;
-        if (step_distance < collision_distance) {
-            collided = true;
-            collision_position = test_position;
-        }
-        escaping = step_distance > initial_distance;
-        if (collided && !escaping) {
-            collision_position = test_position;
-            const float offset = clampf(step_distance + collision_distance, 0.05f, 16.0f);
-            travel_distance = fmaxf(0.0f, travel_distance - offset);
-        } else
-            step_count = 0;
-        if (travel_distance <= 0.001f)
-            step_count = 0;
-    }
-
-    if (collided) {
-        const bool bounce = vel.w <= 0.0f;
-        const bool redirect = was_colliding && !escaping;
-        f3 normal = mk3(0.0f, 0.0f, 0.0f);
-        if (bounce || redirect) {
-            normal = estimate_normal4<FMT>(collision_position, df, sdf);
-            samples += 4;
-        }
-        const float escape_speed = fminf(max_velocity, sys.CollisionSettings.x);
-        if (redirect) {
-            normal = normal * mk3(1.0f, 1.0f, 0.0f);  // ESCAPE_MASK
-            if (len3(normal) < ref::kNoNormalThreshold) {
-                const float a = (x / 67.0f) + (y / 13.0f);
-                normal = mk3(sinf(a), cosf(a), 0.0f);
-            }
-            const f3 nv = (norm3(normal) * escape_speed) * ref::kInitialEscapeSpeed;
-            new_velocity = mk4(nv.x, nv.y, nv.z, ref::kBounceDelay);
-            new_position = old_xyz + (nv * dts);
-        } else if (bounce) {
-            const float d2 = 2.0f * dot3(normal, unit_vector);
-            f3 bounce_vector = ((normal - unit_vector) * d2) * -1.0f;
-            if (len3(bounce_vector) < ref::kNoNormalThreshold)
-                bounce_vector = unit_vector * -1.0f;
-            else
-                bounce_vector = norm3(bounce_vector);
-            new_position = collision_position;
-            const f3 nv = bounce_vector * fminf(max_velocity, len3(velocity) * sys.CollisionSettings.y);
-            new_velocity = mk4(nv.x, nv.y, nv.z, ref::kBounceDelay);
-            new_life -= sys.CollisionSettings.w;
-        } else {
-            const float new_speed = fmaxf(len3(xyz(vel)) * ref::kEscapeSpeedAcceleration, escape_speed);
-            const f3 nv = unit_vector * new_speed;
-            new_velocity = mk4(nv.x, nv.y, nv.z, 0.0f);
-            new_position = old_xyz + (unit_vector * travel_distance);
-        }
-    } else {
-        new_velocity = mk4(velocity.x, velocity.y, velocity.z, fmaxf(vel.w - 1.0f, 0.0f));
-        new_position = old_xyz + (unit_vector * travel_distance);
-    }
-    if (new_life <= 0.0f) {
-        new_position = mk3(0.0f, 0.0f, 0.0f);
-        new_velocity = zero;
-    }
-    pos = mk4(new_position.x, new_position.y, new_position.z, new_life);
-    vel = new_velocity;
-}
-
-// ---------------------------------------------------------------------------------------------
-// the fused step kernel
-// ---------------------------------------------------------------------------------------------
-// Persistent, software-pipelined: every wave walks units of 64 consecutive slots (u, u + W, u + 2W, ...);
-// the 12 input loads of the next unit are issued before the current unit is computed, so HBM loads stay
-// in flight during the arithmetic (the chunk base pointers are cast to the global address space so the
-// compiler can use counted vmcnt waits instead of the flat-address vmcnt(0)).  One lane = one slot:
-// a wave reads/writes 256 contiguous bytes of each component plane per instruction.
-typedef float __attribute__((address_space(1))) gfloat;
-
-struct SlotIn {
-    float px, py, pz, life, vx, vy, vz, ct, ar, ag, ab, aa;
-};
-
-// The 20 planes of one unit through ONE buffer resource (the chunk's allocation) and one lane offset: plane c of the unit is
-// `buffer_load/store_dword v, v_lane_offset, s[rsrc], s_plane_offset offen` with s_plane_offset = (first slot + c * stride) * 4 in an
-// SGPR -- twenty 32-bit scalar adds per wave.  (The flat form, `global_load_dword v, v_lane_offset, s[base:base+1]`, needs a 64-bit
-// base per plane: 2 scalar instructions per plane, computed once for the loads and again for the stores -- 80 of the ~370 scalar
-// instructions a wave issued, and the scalar pipe, one instruction per cycle per CU against the four SIMDs' vector issue, is what
-// the step's issue phase is bound by: tools/ubench/salu.)
-struct UnitPlanes {
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t so[kComponents];
-};
-
-ILM_DEV UnitPlanes unit_planes(const float* chunk_base, int64_t stride, int first_slot) {
-    UnitPlanes u;
-    // raw buffer (stride 0), num_records = the chunk's bytes, DATA_FORMAT = 32 bits (0x00020000, the word gfx9 wants for untyped access)
-    u.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)chunk_base, 0, (int)(stride * (kComponents * 4)), 0x00020000);
-    const uint32_t s4 = (uint32_t)stride * 4u;
-    u.so[0] = (uint32_t)first_slot * 4u;
-#pragma unroll
-    for (int c = 1; c < kComponents; c++) u.so[c] = u.so[c - 1] + s4;
-    return u;
-}
-
-// STREAM: the launch's working set is larger than the Infinity Cache (api.hip decides), every plane is touched once per step: loads and
-// stores carry the non-temporal hint so they do not evict each other on the way through (tools/ubench/stream: 8.4 M slots 187 -> 170 us;
-// on a cache-resident working set the same hint costs 25 %, so small systems keep the default policy).
-// Cache policy bits of the plane accesses (buffer intrinsic aux word on gfx94x / gfx950: 1 = sc0, 2 = nt, 16 = sc1).
-// Stores of the cache-resident variant carry sc1: they write through the XCD's L2 instead of leaving dirty lines there.  Every L2 is
-// private to its XCD, so a kernel's release writes back whatever is still dirty before the next launch of the stream may start --
-// up to 8 x 4 MB after a cfg2 step, ~6 us during which nothing runs (per-wave timestamps of an instrumented build: the waves of a
-// 16-chunk launch span 17.5 us, back-to-back launches took 24).  The written planes are read next by another launch, on whichever XCD,
-// after an invalidate: keeping them in this L2 buys nothing.  tools/step_ab.py: cfg2 without a spawner 20.3 -> 17.5 us per step, with
-// 23.4 -> 22.0 (21.0 -> 19.4 / 24.5 -> 23.5 on one stream); sc0, nt, nt + sc1 and non-temporal loads all lose on a resident working set.
-constexpr int kLdAux = 0, kStAux = 16, kLdAuxStream = 2, kStAuxStream = 2;
-template <bool STREAM>
-ILM_DEV float ld_plane(const UnitPlanes& u, int c, unsigned lane4) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(u.rsrc, (int)lane4, (int)u.so[c], STREAM ? kLdAuxStream : kLdAux));
-}
-template <bool STREAM>
-ILM_DEV void st_plane(const UnitPlanes& u, int c, unsigned lane4, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), u.rsrc, (int)lane4, (int)u.so[c], STREAM ? kStAuxStream : kStAux);
-}
-
-template <bool ATTR, bool STREAM>
-ILM_DEV SlotIn load_slot(const UnitPlanes& u, unsigned lane4) {
-    SlotIn s;
-    s.life = ld_plane<STREAM>(u, 3, lane4);
-    s.px = ld_plane<STREAM>(u, 0, lane4); s.py = ld_plane<STREAM>(u, 1, lane4); s.pz = ld_plane<STREAM>(u, 2, lane4);
-    s.vx = ld_plane<STREAM>(u, 4, lane4); s.vy = ld_plane<STREAM>(u, 5, lane4); s.vz = ld_plane<STREAM>(u, 6, lane4); s.ct = ld_plane<STREAM>(u, 7, lane4);
-    if (ATTR) {
-        s.ar = ld_plane<STREAM>(u, 8, lane4); s.ag = ld_plane<STREAM>(u, 9, lane4); s.ab = ld_plane<STREAM>(u, 10, lane4); s.aa = ld_plane<STREAM>(u, 11, lane4);
-    } else {
-        s.ar = s.ag = s.ab = s.aa = 0.0f;
-    }
-    return s;
-}
-
-// The launch descriptor lives in the kernarg segment (constant address space) and the per-unit body reads
-// every parameter through a pointer to it (s_load from a uniform address).  The persistent loop launders
-// that pointer through an empty asm each iteration: otherwise LICM hoists all ~150 scalar parameters out
-// of the loop, overflows the 102 SGPRs and spills them into VGPR lanes and scratch.
-typedef const StepLaunch __attribute__((address_space(4))) CStepLaunch;
-
-// DF: the update pass is UpdateWithDistanceField (pulls in the SDF sampler); SPAWN: spawn records present.
-// Both are compile-time so the common no-field / no-spawn step does not pay their registers.
-template <int FMT, bool DF, bool SPAWN, bool EXT, bool STREAM>
-ILM_DEV bool process_unit(CStepLaunch* ap, const UnitPlanes& up, int chunk, int i, unsigned lane, int seg, SlotIn cur, const NoiseDeltas& noise) {
-    const StepLaunch& a = *(const StepLaunch*)ap;
-    const IlmStepDesc& d = a.desc;
-    const int64_t S = a.stride;
-    const unsigned lane4 = lane * 4u;
-    const int mode = d.UpdateMode;
-    const bool need_attr = (mode == ILM_UPDATE_POSITIONS) || (mode == ILM_UPDATE_WITH_DISTANCE_FIELD);
-    // Noise has no life check (Noise.fx:40): dead slots go through it.  That only matters when its result survives --
-    // no update pass follows (single-pass ilm_noise), or the op can bring a dead slot back to life (StepDerived).
-    const uint32_t noise_ops = EXT ? ((1u << ILM_OP_NOISE) | (1u << ILM_OP_SPATIAL_NOISE)) : (1u << ILM_OP_NOISE);
-    const bool has_noise = ((a.op_mask & noise_ops) != 0u) && ((mode == ILM_UPDATE_NONE) || (a.derived.noise_may_revive != 0));
-    const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
-
-    bool spawn_here = false;
-    if constexpr (SPAWN) {
-        for (int s = 0; s < d.SpawnCount; s++) {
-            const IlmSpawnRecord& r = d.Spawns[s];
-            if (r.ChunkIndex == chunk && (float)i >= r.Params.ChunkSizeAndIndices[1] && (float)i <= r.Params.ChunkSizeAndIndices[2])
-                spawn_here = true;
-        }
-    }
-    bool live_after = false;
-    int sdf_samples = 0;
-    // Stride padding (chunk sizes whose square is not a multiple of 1024: 10, 16, 48 ...): not a slot of the chunk.  Noise has no life
-    // check, so without this a padding lane could be given a life, be updated and be counted (CountLiveParticles.fx counts ChunkSize^2 pixels).
-    if (i >= a.slots)
-        return false;
-    if (mode == ILM_UPDATE_ERASE) {
-        // PS_Erase, UpdateParticleSystem.fx:40-49
-#pragma unroll
-        for (int c = 0; c < 8; c++) st_plane<STREAM>(up, c, lane4, 0.0f);
-#pragma unroll
-        for (int c = 12; c < 20; c++) st_plane<STREAM>(up, c, lane4, 0.0f);
-    } else if ((cur.life <= 0.0f) && !spawn_here && !has_noise) {     // `<= 0` as the shaders test it: a NaN life is not dead
-        // dead and nothing writes it: the update pass leaves the cleared target
-        // (UpdateHandler._BeforeDraw clears, ParticleTransform.cs:164-165; readStateOrDiscard discards)
-        if (mode != ILM_UPDATE_NONE) {
-#pragma unroll
-            for (int c = 0; c < 8; c++) st_plane<STREAM>(up, c, lane4, 0.0f);
-#pragma unroll
-            for (int c = 12; c < 20; c++) st_plane<STREAM>(up, c, lane4, 0.0f);
-        } else {
-            live_after = cur.life > 0.0f;   // untouched slots keep their liveness when no update pass ran
-        }
-    } else {
-        float4 pos = mk4(cur.px, cur.py, cur.pz, cur.life);
-        float4 vel = mk4(cur.vx, cur.vy, cur.vz, cur.ct);
-        float4 attr = mk4(cur.ar, cur.ag, cur.ab, cur.aa);
-        // slot (x, y): the unit's first slot is divided on the scalar unit, lanes only fold the row wrap
-        const int cs = a.chunk_size;
-        const int row0 = (a.derived.cs_shift >= 0) ? ((seg * 64) >> a.derived.cs_shift) : __builtin_amdgcn_readfirstlane((seg * 64) / cs);
-        int sy = row0, sx = (seg * 64 - row0 * cs) + (int)lane;
-        while (sx >= cs) { sx -= cs; sy++; }
-        const float fx = (float)sx, fy = (float)sy;
-        bool spawned = false;
-
-        if constexpr (SPAWN) {
-            if (spawn_here) {
-                for (int s = 0; s < d.SpawnCount; s++) {
-                    if (d.Spawns[s].ChunkIndex == chunk) {
-                        bool wrote;
-                        if (EXT && d.Spawns[s].Kind == ILM_SPAWN_POSITION_BUFFER)
-                            wrote = spawn_slot_position_buffer(pos, vel, attr, fx, fy, a.rnd, a.rw, a.rh, a.derived.inv_rw, a.derived.inv_rh,
-                                                               d.Spawns[s].Params, a.spawn_positions[s], a.spawn_position_count[s]);
-                        else if (EXT && d.Spawns[s].Kind == ILM_SPAWN_FEEDBACK)
-                            wrote = spawn_slot_feedback(pos, vel, attr, fx, fy, a.rnd, a.rw, a.rh, a.derived.inv_rw, a.derived.inv_rh,
-                                                        d.Spawns[s].Params, d.Spawns[s].Feedback, a.source_base[s], S, cs);
-                        else if (EXT && d.Spawns[s].Kind == ILM_SPAWN_PATTERN)
-                            wrote = spawn_slot_pattern(pos, vel, attr, fx, fy, a.rnd, a.rw, a.rh, a.derived.inv_rw, a.derived.inv_rh,
-                                                       d.Spawns[s].Params, d.Spawns[s].Pattern, a.spawn_pattern[s], a.pattern_w[s],
-                                                       a.pattern_h[s], a.pattern_levels[s]);
-                        else
-                            wrote = spawn_slot(pos, vel, attr, fx, fy, a.rnd, a.rw, a.rh, a.derived.inv_rw, a.derived.inv_rh, d.Spawns[s].Params);
-                        if (wrote)
-                            spawned = true;
-                    }
-                }
-            }
-        }
-
-        for (int o = 0; o < d.OpCount; o++) {
-            const IlmTransformOp& op = d.Ops[o];
-            if (op.Type == ILM_OP_GRAVITY)
-                apply_gravity(pos, vel, d.System, op.u.Gravity, a.derived.op[o]);
-            else if (op.Type == ILM_OP_NOISE)
-                apply_noise(pos, vel, fx, fy, a.rnd, a.rw, a.rh, d.System, op.u.Noise, a.derived.inv_rw, a.derived.inv_rh, a.derived.op[o],
-                            (o == a.derived.noise.op) ? noise : NoiseDeltas{ false, zero, zero });
-            else if (op.Type == ILM_OP_FMA)
-                apply_fma(pos, vel, d.System, op.u.FMA, a.derived.op[o]);
-            else if (EXT && op.Type == ILM_OP_MATRIX_MULTIPLY)
-                apply_matrix_multiply(pos, vel, d.System, op.u.MatrixMultiply);
-            else if (EXT && op.Type == ILM_OP_SPATIAL_NOISE)
-                apply_spatial_noise(pos, vel, a.rnd_lp, a.rw, a.rh, d.System, op.u.SpatialNoise, a.derived);
-        }
-
-        float4 rc = zero, rd = zero;
-        if (need_attr) {
-            if (pos.w <= 0.0f) {
-                pos = vel = zero;  // readStateOrDiscard: discard => cleared target
-            } else {
-                if constexpr (DF)
-                    update_with_distance_field<FMT>(pos, vel, fx, fy, d.System, a.derived.dt_s, d.DistanceField, a.sdf, sdf_samples);
-                else
-                    update_positions(pos, vel, d.System, a.derived.dt_s);
-                render_data(fx, fy, pos, vel, attr, d.System, d.Update, a.derived.bezier_codes, a.derived.update_bits, a.ramp, a.ramp_w, a.ramp_h, rc, rd);
-            }
-        }
-        st_plane<STREAM>(up, 0, lane4, pos.x); st_plane<STREAM>(up, 1, lane4, pos.y); st_plane<STREAM>(up, 2, lane4, pos.z); st_plane<STREAM>(up, 3, lane4, pos.w);
-        st_plane<STREAM>(up, 4, lane4, vel.x); st_plane<STREAM>(up, 5, lane4, vel.y); st_plane<STREAM>(up, 6, lane4, vel.z); st_plane<STREAM>(up, 7, lane4, vel.w);
-        if (spawned) {
-            st_plane<STREAM>(up, 8, lane4, attr.x); st_plane<STREAM>(up, 9, lane4, attr.y); st_plane<STREAM>(up, 10, lane4, attr.z); st_plane<STREAM>(up, 11, lane4, attr.w);
-        }
-        if (need_attr) {
-            st_plane<STREAM>(up, 12, lane4, rc.x); st_plane<STREAM>(up, 13, lane4, rc.y); st_plane<STREAM>(up, 14, lane4, rc.z); st_plane<STREAM>(up, 15, lane4, rc.w);
-            st_plane<STREAM>(up, 16, lane4, rd.x); st_plane<STREAM>(up, 17, lane4, rd.y); st_plane<STREAM>(up, 18, lane4, rd.z); st_plane<STREAM>(up, 19, lane4, rd.w);
-        }
-        live_after = pos.w > 0.0f;
-    }
-    if constexpr (DF) {
-        // diagnostic count (one atomic per lane: only ever on while bench.py takes the collision row's sample count)
-        if ((__builtin_amdgcn_readfirstlane(g_step_count_sdf_samples) != 0) && (sdf_samples != 0))
-            atomicAdd(&g_step_sdf_samples, (unsigned long long)sdf_samples);
-    }
-
-    return live_after;
-}
-
-// CountLiveParticles.fx for a block of the step kernels: LDS sum over the block's waves, ONE 64-bit atomic per block on a bucket
-// counter of its chunk (live particles in the low word, a ticket in the high word); the block that draws a bucket's last ticket
-// carries the bucket's sum to the chunk's counter the same way, and the one that completes the chunk stores the total, tagged with
-// the step's sequence number, straight into the host's table.  (Per-wave atomics on one address serialise at ~11 ns each: 1024 of
-// them per chunk made the step 7x slower; one per block on ONE address per chunk still queued 4096 deep on 1024^2 chunks.)  The
-// units of a block always belong to one chunk.
-ILM_DEV void publish_block_count(uint32_t* wave_live, uint32_t n_live, unsigned lane, int wave, bool block_in_range, int chunk, int block_in_chunk,
-                                 int blocks_per_chunk, int buckets, unsigned long long* live_counts, unsigned long long* zero_counts, int zero_n,
-                                 unsigned long long* host_counts, uint32_t seq) {
-    if (blockIdx.x == 0)
-        for (int i = (int)threadIdx.x; i < zero_n; i += kStepThreads) zero_counts[i * kCountStride] = 0ull;
-    if (lane == 0) wave_live[wave] = n_live;
-    __syncthreads();
-    if (threadIdx.x == 0 && block_in_range) {
-        uint32_t block_live = 0;
-#pragma unroll
-        for (int w = 0; w < kStepThreads / 64; w++) block_live += wave_live[w];
-        unsigned long long* lines = live_counts + (size_t)chunk * (kCountLines * kCountStride);
-        const int bucket = block_in_chunk & (buckets - 1);
-        const unsigned long long old = atomicAdd(&lines[(1 + bucket) * kCountStride], (1ull << 32) | (unsigned long long)block_live);
-        if ((int)(old >> 32) + 1 == blocks_per_chunk / buckets) {
-            const unsigned long long sum = (old & 0xFFFFFFFFull) + (unsigned long long)block_live;
-            const unsigned long long old2 = atomicAdd(&lines[0], (1ull << 32) | sum);
-            if ((int)(old2 >> 32) + 1 == buckets) {
-                const unsigned long long total = (old2 & 0xFFFFFFFFull) + sum;
-                __hip_atomic_store(&host_counts[chunk], ((unsigned long long)seq << 32) | (total & 0xFFFFFFFFull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
-}
-
-// The launch descriptor is written by the host into the kernarg ring just before the launch, so the first wave of every scalar cache
-// misses on each of its 64-byte lines all the way to memory -- and the step reads them one dependent phase after another (decode,
-// planes, noise tables, each transform, the update pass): a chain of ~20 serial misses at the head of every launch.  One load per
-// line, all in flight at once, turns the chain into a single miss; for every later wave they are ~60 cache hits the scalar pipe has
-// room for (tools/step_ab.py with 200 extra scalar instructions per wave: no change in step time).  Measured (r02): a one-chunk launch
-// 7.7 -> 6.0 us back to back (10.8 -> 8.3 us when it spawns), cfg2 without a spawner 24.0 -> 21.4 us per step.
-constexpr int kTouchBlocks = 2048 / (kStepThreads / 64);      // the launch's first 2 048 waves
-// The chunk table is read through the constant address space in both kernels: see step_lean_kernel.
-typedef float* const __attribute__((address_space(4))) CBase;
-#define ILM_T1(o) "s_load_dword %0, %1, " #o "\n"
-#define ILM_T4(o) ILM_T1(o) ILM_T1(o + 0x40) ILM_T1(o + 0x80) ILM_T1(o + 0xc0)
-#define ILM_T16(o) ILM_T4(o) ILM_T4(o + 0x100) ILM_T4(o + 0x200) ILM_T4(o + 0x300)
-ILM_DEV void touch_kernarg_lines_lean() {       // LeanStep: 51 lines
-    const auto kp = __builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t sink;
-    asm volatile(ILM_T16(0x0) ILM_T16(0x400) ILM_T16(0x800) ILM_T1(0xc00) ILM_T1(0xc40) ILM_T1(0xc80) "s_waitcnt lgkmcnt(0)"
-                 : "=&s"(sink) : "s"(kp));
-}
-ILM_DEV void touch_kernarg_lines_step() {       // StepLaunch: 63 lines
-    const auto kp = __builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t sink;
-    asm volatile(ILM_T16(0x0) ILM_T16(0x400) ILM_T16(0x800) ILM_T4(0xc00) ILM_T4(0xd00) ILM_T4(0xe00) ILM_T1(0xf00) ILM_T1(0xf40) ILM_T1(0xf80)
-                 "s_waitcnt lgkmcnt(0)" : "=&s"(sink) : "s"(kp));
-}
-static_assert(sizeof(StepLaunch) >= 0xf84 && sizeof(StepLaunch) <= 0xfc0, "touch_kernarg_lines_step reads one dword of each 64-byte line of StepLaunch");
-
-// One wave = one unit of 64 consecutive slots; the hardware dispatcher balances the waves.  (A persistent,
-// software-pipelined variant of this kernel measured 12-25 % slower: the body is a long dependent chain --
-// state loads, scalar parameter fetches, randomness gathers -- whose latency is hidden by wave occupancy,
-// not by prefetching; see DESIGN.md.)  MINW = minimum waves per SIMD requested from the register allocator.
-template <int FMT, bool DF, bool SPAWN, int MINW, bool EXT = false, bool STREAM = false>
-__global__ __launch_bounds__(kStepThreads, MINW) void step_kernel(const StepLaunch a) {
-    __shared__ uint32_t wave_live[kStepThreads / 64];
-    CStepLaunch* ap = (CStepLaunch*)__builtin_amdgcn_kernarg_segment_ptr();
-    if (blockIdx.x < kTouchBlocks) touch_kernarg_lines_step();
-    // the wave index is uniform by construction; saying so keeps the unit / chunk / base-pointer arithmetic on the
-    // scalar unit and lets every plane access use the SGPR-base + 32-bit lane-offset addressing form
-    const unsigned lane = threadIdx.x & 63u;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    // Blocks are rotated so that block 0 holds the first unit of the first spawn range: a spawning wave is a long
-    // dependent chain (randomness gathers, sin/cos/acos), so it has to start first to finish under the cover of
-    // the streaming waves instead of forming the tail of the launch.  unit_rotate is a multiple of the units per block.
-    constexpr int K = kUnitsPerWave;
-    int v = (int)blockIdx.x * (kStepThreads / 64) * K + a.unit_rotate;      // first unit of the block
-    const int total = a.unit_end - a.unit_begin;
-    if (v >= a.total_padded) v -= a.total_padded;
-    const int u = a.unit_begin + v + wave * K;                               // first of this wave's K consecutive units
-    // units_per_chunk is a multiple of 16 = (4 waves) x (K <= 4): the K units of a wave (and the whole block) lie in
-    // one chunk, and `total` is a multiple of 16, so the K units are active or inactive together
-    const bool active = (v + wave * K) < total;
-    uint32_t n_live = 0;
-    if (active) {
-        // (a scalar integer division costs ~35 instructions per wave)
-        const int chunk_rel = (a.upc_shift >= 0) ? (u >> a.upc_shift) : (u / a.units_per_chunk);
-        const int seg = u - chunk_rel * a.units_per_chunk;
-        const int chunk = a.first_chunk + chunk_rel;
-        // never-written tail of a spawn-target chunk: all planes are zero and stay zero (scalar compares, uniform branch)
-        bool untouched = false;
-        for (int k = 0; k < a.partial_count; k++)
-            untouched = untouched || ((a.partial_chunk[k] == chunk) && (seg >= a.partial_units[k]));
-        if (!untouched) {
-        const float* chunk_base = ((CBase*)a.chunk_bases)[chunk];
-        const unsigned lane4 = lane * 4u;
-        UnitPlanes up[K];
-#pragma unroll
-        for (int j = 0; j < K; j++) up[j] = unit_planes(chunk_base, a.stride, (seg + j) * 64);
-        // K > 1 issues the state loads of all K units before any arithmetic (K x 12 loads in flight per wave).  Measured
-        // on cfg2 ("experiments"): K = 1 26.1 us, K = 2 30.5 us, K = 4 36.5 us per step -- the extra
-        // registers cost more occupancy than the memory-level parallelism returns, so K = 1 ships.
-        SlotIn q[K];
-#pragma unroll
-        for (int j = 0; j < K; j++) q[j] = load_slot<true, STREAM>(up[j], lane4);
-#pragma nounroll
-        for (int j = 0; j < K; j++) {
-            const SlotIn cur = q[0];
-#pragma unroll
-            for (int r = 0; r + 1 < K; r++) q[r] = q[r + 1];
-            NoiseDeltas noise;
-            noise.valid = false;
-            if (a.derived.noise.op >= 0) {
-                // first slot of the unit -> (x0, y): scalar; the unit lies in one row (chunk size a multiple of 64)
-                const int first = (seg + j) * 64;
-                const int row = (a.derived.cs_shift >= 0) ? (first >> a.derived.cs_shift) : (first / a.chunk_size);
-                noise = noise_prepare(((const StepLaunch*)ap)->derived.noise, ((const StepLaunch*)ap)->desc, first - row * a.chunk_size, row);
-            }
-            const bool live_after = process_unit<FMT, DF, SPAWN, EXT, STREAM>(ap, up[j], chunk, (seg + j) * 64 + (int)lane, lane, seg + j, cur, noise);
-            n_live += (uint32_t)__popcll(__ballot(live_after));
-        }
-        }
-    }
-    if (a.desc.Flags & ILM_STEP_COUNT_LIVE) {
-        const int first_unit = a.unit_begin + v;
-        const int chunk_rel = (a.upc_shift >= 0) ? (first_unit >> a.upc_shift) : (first_unit / a.units_per_chunk);
-        constexpr int kUnitsPerBlock = (kStepThreads / 64) * K;
-        publish_block_count(wave_live, n_live, lane, wave, v < total, a.first_chunk + chunk_rel, (first_unit - chunk_rel * a.units_per_chunk) / kUnitsPerBlock,
-                            a.units_per_chunk / kUnitsPerBlock, a.count_buckets, a.live_counts, a.zero_counts, a.zero_n, a.host_counts, a.count_seq);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// the lean step kernel
-// ---------------------------------------------------------------------------------------------
-// step_kernel above interprets an arbitrary IlmStepDesc: per wave ~370 scalar-ALU instructions, ~70 scalar loads and ~60 branches next
-// to ~365 vector instructions.  The scalar pipe issues one instruction per cycle per CU against the four SIMDs' vector issue
-// (tools/ubench/salu: ~550 G/s against ~950 G/s), and every dependent scalar load the interpreter waits for is latency in the life of
-// a wave whose whole launch is only two to three wave generations long -- so on a cache-resident system (cfg2) the step's time
-// follows the scalar work, not the bytes.  step_lean_kernel runs the common shape of a step -- power-of-two chunk size >= 64,
-// UpdatePositions, Gravity / Noise (no area, wave-uniform deltas available) / FMA (no area) in any order, inline spawners, no life
-// ramp, no Noise that can revive a slot -- from a pre-digested descriptor (LeanStep, built by launch_step from the same StepLaunch):
-// every uniform decision arrives as an integer, the attractors as one 32-byte record each, the spawn ranges as unit ranges.  The
-// per-slot arithmetic is the interpreter's own (same functions or the same operations in the same order): ILM_STEP_LEAN=0 runs the
-// interpreter instead and tests/test_properties_gpu.py requires the two to agree bit for bit.
-struct LeanAttractor { float x, y, z, radius, strength, _p0, _p1, _p2; };
-constexpr int kLeanMaxAttractors = 8;
-struct LeanGravity {
-    int32_t count; uint32_t types;   // 2 bits per attractor: 0 physical (ars.z < 0.5), 1 linear, 2 squared (Gravity.fx:36-52)
-    float max_accel, _pad0;
-    float cat_lo, cat_hi, _pad1, _pad2;
-    LeanAttractor a[kLeanMaxAttractors];
-};
-union LeanOp {
-    LeanGravity gravity;
-    IlmNoiseParams noise;
-    IlmFMAParams fma;
-};
-struct LeanStep {
-    // decode
-    float* const* chunk_bases;
-    unsigned long long* live_counts; unsigned long long* zero_counts; unsigned long long* host_counts;
-    int64_t stride;
-    int32_t upc_shift, unit_rotate, total_padded, total_units;
-    int32_t first_chunk, cs_shift, zero_n; uint32_t flags;
-    uint32_t count_seq; int32_t count_buckets; int32_t _pad3[2];
-    int32_t partial_chunk[kMaxPartialChunks], partial_units[kMaxPartialChunks];     // unused entries: chunk -1
-    int32_t partial_count, op_count, spawn_count; uint32_t elide;      // elide: kElideDerived / kElideColor (step_lean_kernel)
-    int32_t op_type[ILM_MAX_OPS];
-    int32_t spawn_chunk[ILM_MAX_SPAWNS], spawn_unit_lo[ILM_MAX_SPAWNS], spawn_unit_hi[ILM_MAX_SPAWNS];   // segments of the target chunk a record touches
-    int32_t _pad1[2];
-    // update pass
-    float dt_s; uint32_t bezier_codes, update_bits; int32_t noise_op;
-    IlmParticleSystemUniforms sys;
-    IlmUpdateParams update;
-    // transforms
-    StepDerived::Op dop[ILM_MAX_OPS];
-    LeanOp op[ILM_MAX_OPS];
-    StepDerived::NoiseFast noise;
-    // spawners (inline kind only) -- or, in a launch without them, the 5 x 5 noise tables (kNoiseBigClasses)
-    const float4* rnd; int32_t rw, rh; float inv_rw, inv_rh; int32_t _pad2[2];
-    union {
-        IlmSpawnRecord spawns[ILM_MAX_SPAWNS];
-        IlmFloat4 noise_big[2 * kNoiseBigClasses * kNoiseBigClasses];
-    };
-};
-static_assert(sizeof(LeanStep) <= 4096, "LeanStep travels in the kernarg segment (4 KB)");
-
-// PS_Gravity with the attractor records and type codes of LeanGravity: the operations of apply_gravity, in its order
-ILM_DEV void apply_gravity_lean(float4& pos, float4& vel, const LeanGravity& g, float dt_ms, float mv) {
-    if ((pos.w <= 0.0f) || !((vel.w >= g.cat_lo) && (vel.w <= g.cat_hi)))
-        return;
-    f3 acceleration = mk3(0.0f, 0.0f, 0.0f);
-    const uint32_t types = g.types;
-    int i = 0;
-#ifndef ILM_GRAVITY_EXACT
-    // Four attractors at a time while none of the four is of the physical type (the one with the IEEE division): their records come
-    // in together, every decision is a select on a uniform mask, so the four dependent chains (subtract, dot, rsq, rcp, ...) sit in
-    // one basic block and the scheduler interleaves them.  The same operations per attractor, the terms added in index order: the
-    // same bits as the loop below.  (A wave alone on its SIMD spent 1.24 us of its 3.4 in the transforms, one attractor after the
-    // other behind a scalar load each -- and that latency is what the head and the tail of every launch consist of.)
-    for (; i + 4 <= g.count && ((((types >> (2 * i)) | (types >> (2 * i + 1))) & 0x55u) == 0x55u); i += 4) {
-        f3 term[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const LeanAttractor A = g.a[i + k];
-            const bool squared = ((types >> (2 * (i + k))) & 2u) != 0u;
-            const f3 to_center = mk3(A.x, A.y, A.z) - xyz(pos);
-            const float d2 = dot3(to_center, to_center);
-            const float inv_len = fast_rsq(d2);
-            const float distance = d2 * inv_len;
-            float attraction = 1.0f - sat(distance * fast_rcp(A.radius));
-            attraction = squared ? attraction * attraction : attraction;
-            attraction = attraction * dt_ms * (1.0f / kVelocityConstantScale);
-            term[k] = ((to_center * inv_len) * attraction) * A.strength;
-        }
-        acceleration = (((acceleration + term[0]) + term[1]) + term[2]) + term[3];
-    }
-#endif
-    for (; i < g.count; i++) {
-        const LeanAttractor A = g.a[i];
-        const uint32_t type = (types >> (2 * i)) & 3u;
-        const f3 to_center = mk3(A.x, A.y, A.z) - xyz(pos);
-        float attraction;
-        const float d2 = dot3(to_center, to_center);
-#ifndef ILM_GRAVITY_EXACT
-        const float inv_len = fast_rsq(d2);
-        if (type != 0u) {
-            const float distance = d2 * inv_len;
-            attraction = 1.0f - sat(distance * fast_rcp(A.radius));
-            if (type == 2u)
-                attraction *= attraction;
-            attraction = attraction * dt_ms * (1.0f / kVelocityConstantScale);
-        } else {
-            const float distance_squared = fmaxf(d2 - A.radius, 0.001f);
-            attraction = 1.0f / distance_squared;
-        }
-        acceleration = acceleration + (((to_center * inv_len) * attraction) * A.strength);
-#else
-        const float distance = sqrtf(d2);
-        if (type != 0u) {
-            attraction = 1.0f - sat(distance / A.radius);
-            if (type == 2u)
-                attraction *= attraction;
-            attraction = attraction * dt_ms / kVelocityConstantScale;
-        } else {
-            const float distance_squared = fmaxf(d2 - A.radius, 0.001f);
-            attraction = 1.0f / distance_squared;
-        }
-        const f3 n = mk3(to_center.x / distance, to_center.y / distance, to_center.z / distance);
-        acceleration = acceleration + ((n * attraction) * A.strength);
-#endif
-    }
-    const float maximum_acceleration = g.max_accel;
-#ifndef ILM_GRAVITY_EXACT
-    const float a2 = dot3(acceleration, acceleration);
-    if (a2 > maximum_acceleration * maximum_acceleration)
-        acceleration = acceleration * (fast_rsq(a2) * maximum_acceleration);
-#else
-    const float current_length = len3(acceleration);
-    if (current_length > maximum_acceleration)
-        acceleration = mk3(acceleration.x / current_length, acceleration.y / current_length, acceleration.z / current_length) * maximum_acceleration;
-#endif
-    vel.x = fminf(mv, vel.x + acceleration.x);
-    vel.y = fminf(mv, vel.y + acceleration.y);
-    vel.z = fminf(mv, vel.z + acceleration.z);
-}
-
-// noise_prepare on LeanStep: class counts as sign bits (2 scalar instructions per boundary), one table for both class counts
-ILM_DEV NoiseDeltas noise_prepare_lean(const LeanStep& a, int x0, int row) {
-    const StepDerived::NoiseFast& nf = a.noise;
-    NoiseDeltas out;
-    const uint32_t code = nf.wcode[x0 >> 6];
-    out.valid = (code & 64u) != 0u;
-    uint32_t yc0 = 0, yc1 = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int b = nf.yb[k];                              // a row >= 0 or INT32_MAX
-        yc0 += (uint32_t)(b - 1 - row) >> 31;                // row >= b
-        yc1 += (uint32_t)(b - 2 - row) >> 31;                // row + 1 >= b
-    }
-    const uint32_t xc0 = code & 7u, xc1 = (code >> 3) & 7u;
-    const uint32_t n = (uint32_t)nf.classes;
-    const IlmFloat4* table = (n == (uint32_t)kNoiseBigClasses) ? a.noise_big : &nf.position[0][0];   // position[n][n] then velocity[n][n]
-    out.position = ld4(table[yc0 * n + xc0]);
-    out.velocity = ld4(table[n * n + yc1 * n + xc1]);
-    return out;
-}
-static_assert(offsetof(StepDerived::NoiseFast, velocity) == offsetof(StepDerived::NoiseFast, position) + 9 * sizeof(IlmFloat4), "velocity[3][3] follows position[3][3]");
-
-typedef const LeanStep __attribute__((address_space(4))) CLeanStep;
-static_assert(sizeof(LeanStep) >= 0xc84 && sizeof(LeanStep) <= 0xcc0, "touch_kernarg_lines_lean reads one dword of each 64-byte line of LeanStep");
-
-// ---- store elision (internal.hpp, kElideDerived) -------------------------------------------------------------------------------
-// A wave stores a plane only when it has to: writing the bits memory already holds changes nothing, and at cfg4's size every plane
-// access is HBM traffic.  When it stores, it stores all 64 lanes (an unchanged lane rewrites its own bits; a lane-masked store saves
-// no burst).
-ILM_DEV bool same_bits(float a, float b) { return __builtin_bit_cast(uint32_t, a) == __builtin_bit_cast(uint32_t, b); }
-// Only the STREAM variant elides.  The cache-resident one keeps every store: its planes live in the Infinity Cache from one step to the
-// next, its time follows the issue of its instructions rather than its bytes (see step_lean_kernel), and the compares would be added work.
-template <bool STREAM>
-ILM_DEV void st_plane_changed(const UnitPlanes& u, int c, unsigned lane4, float v, float loaded) {
-    if (!STREAM || __ballot(!same_bits(v, loaded)) != 0ull) st_plane<STREAM>(u, c, lane4, v);
-}
-// A curve of the update pass gives the same value for two inputs whose t (tForScaledBezier) is the same bits and no NaN: the rest of
-// evaluateBezier is a function of t and of the curve (part of the render key).  A constant curve reads no t at all.
-ILM_DEV bool same_curve_t(const IlmFloat4& rc, float v0, float v1, uint32_t code) {
-    if ((code & 3u) == 0u) return true;
-    const float t1 = t_for_coded_bezier(rc, v1, code);
-    return same_bits(t_for_coded_bezier(rc, v0, code), t1) && (t1 == t1);
-}
-// The render planes of a render-current chunk (every chunk of the launch; api.hip, System::render_gen) hold what render_data gives for the
-// state this wave loaded.  Per lane, a component keeps its bits when
-//   - the slot is dead before and after the step: all eight components are 0 and stay 0; or, for a slot alive before and after,
-//   - its inputs have the same bits (rd.z: the velocity; rd.w: the category, no NaN), or
-//   - a value that decides it is the same bits for the loaded and the new state and no NaN: renderColor by the two colour curves' t, with
-//     the attributes not spawned over and colour curves that cannot give a NaN factor (kElideColor, host-checked); rd.x by the size
-//     curves' t, rd.x itself no NaN; rd.y, when getVelocityRotation() == 0, by itself (recomputed for the loaded state, no NaN).
-// Anything else -- liveness changed, rotation from velocity, a NaN -- stores.  A plane is stored when any lane of the wave needs it;
-// the attributes are loaded only by a wave that stores renderColor.  (No life ramp here: build_lean_step.)
-template <bool SPAWN, bool STREAM>
-ILM_DEV void store_changed_render_planes(const LeanStep& a, const UnitPlanes& up, unsigned lane4, float fx, float fy, const SlotIn& cur,
-                                         float4 pos, float4 vel, float4 attr, bool spawned) {
-    const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
-    const IlmUpdateParams& p = a.update;
-    const uint32_t codes = a.bezier_codes;
-    const bool live0 = !(cur.life <= 0.0f), live1 = !(pos.w <= 0.0f);
-    const bool dead = !live0 && !live1, both = live0 && live1;
-    float4 rc, rd;
-    render_data(fx, fy, pos, vel, zero, a.sys, p, codes, a.update_bits, nullptr, 0, 0, rc, rd);     // (rc: not used)
-    // the speed the velocity curves read, for the loaded state, only where a velocity curve is not constant
-    float speed0 = 0.0f, speed1 = 0.0f;
-    if ((codes & 0x03000300u) != 0u) {
-        speed0 = fmaxf(len3_fast(mk3(cur.vx, cur.vy, cur.vz)), 0.0001f);
-        speed1 = fmaxf(len3_fast(xyz(vel)), 0.0001f);
-    }
-    const bool same_v = same_bits(cur.vx, vel.x) && same_bits(cur.vy, vel.y) && same_bits(cur.vz, vel.z);
-    const bool rc_same = dead || (both && !spawned && ((a.elide & kElideColor) != 0u) && same_curve_t(p.ColorFromLife.RangeAndCount, cur.life, pos.w, codes & 0xFFu) &&
-                                  same_curve_t(p.ColorFromVelocity.RangeAndCount, speed0, speed1, (codes >> 8) & 0xFFu));
-    const bool rdx_same = dead || (both && same_curve_t(p.SizeFromLife.RangeAndCount, cur.life, pos.w, (codes >> 16) & 0xFFu) &&
-                                   same_curve_t(p.SizeFromVelocity.RangeAndCount, speed0, speed1, codes >> 24) && (rd.x == rd.x));
-    bool rdy_same = dead;
-    if (a.update_bits & 2u) {
-        const float y0 = render_rotation(rotation_unscaled(cur.vx, cur.vy), cur.life, render_index(fx, fy), a.sys, p);
-        rdy_same = rdy_same || (both && same_bits(y0, rd.y) && (rd.y == rd.y));
-    }
-    const bool rdz_same = dead || (both && same_v);
-    const bool rdw_same = dead || (both && same_bits(cur.ct, vel.w) && (vel.w == vel.w));
-    if (__ballot(!rc_same) != 0ull) {
-        const float4 stored = mk4(ld_plane<STREAM>(up, 8, lane4), ld_plane<STREAM>(up, 9, lane4), ld_plane<STREAM>(up, 10, lane4), ld_plane<STREAM>(up, 11, lane4));
-        if (!SPAWN || !spawned) attr = stored;
-        float4 rd_unused;
-        render_data(fx, fy, pos, vel, attr, a.sys, p, codes, a.update_bits, nullptr, 0, 0, rc, rd_unused);
-        st_plane<STREAM>(up, 12, lane4, rc.x); st_plane<STREAM>(up, 13, lane4, rc.y); st_plane<STREAM>(up, 14, lane4, rc.z); st_plane<STREAM>(up, 15, lane4, rc.w);
-    }
-    if (__ballot(!rdx_same) != 0ull) st_plane<STREAM>(up, 16, lane4, rd.x);
-    if (__ballot(!rdy_same) != 0ull) st_plane<STREAM>(up, 17, lane4, rd.y);
-    if (__ballot(!rdz_same) != 0ull) st_plane<STREAM>(up, 18, lane4, rd.z);
-    if (__ballot(!rdw_same) != 0ull) st_plane<STREAM>(up, 19, lane4, rd.w);
-}
-
-// The curve classes of the streaming lean step (launch_lean_step selects, ilm_debug_last_step_kernel reports): compile-time
-// instantiations of step_lean_block (step_lean_kernel<..> / step_lean_clamp_kernel).  kCurvesClamp: every
-// curve of the update pass is constant or has the clamp range and no shaping (bezier_codes & ~kClampCodes == 0), the velocity rotation
-// is zero and there is no life ramp (update_bits == 2), the launch elides (kElideDerived) and has no spawner (the spawning kernel's
-// registers are the spawn path's: a class of it would gain little).  The instantiation holds no fmodf, sinf or atan2f code; which curves
-// are constant stays a scalar test.
-constexpr int kCurvesGeneral = 0, kCurvesClamp = 1;
-constexpr uint32_t kClampCodes = 0x13131313u;      // per curve: the count class (bits 0-1) and the sign of the inverse divisor (bit 4)
-
-// One curve's part in the elision proof and in the value: t for the loaded and the new state, formed once.
-struct CurveT { float t1; bool same; };
-ILM_DEV CurveT clamp_curve_t(const IlmFloat4& rc, float v0, float v1, uint32_t code) {
-    CurveT c = { 0.0f, true };      // a constant curve reads no t
-    if ((code & 3u) != 0u) {
-        c.t1 = t_for_clamp_bezier(rc, v1, code);
-        c.same = same_bits(t_for_clamp_bezier(rc, v0, code), c.t1) && (c.t1 == c.t1);
-    }
-    return c;
-}
-// store_changed_render_planes for kCurvesClamp: the same stores of the same bits (the rules above, render_data's operations on the same
-// operands), with each t and the new state's speed formed once and shared by the proof and the value, and the dead lanes selected at
-// the end instead of branched around.  (No spawner: the attributes are the stored ones.)
-ILM_DEV void store_changed_render_planes_clamp(const LeanStep& a, const UnitPlanes& up, unsigned lane4, float fx, float fy, const SlotIn& cur,
-                                               float4 pos, float4 vel) {
-    const IlmUpdateParams& p = a.update;
-    const uint32_t codes = a.bezier_codes & kClampCodes;
-    const uint32_t c_cl = codes & 0xFFu, c_cv = (codes >> 8) & 0xFFu, c_sl = (codes >> 16) & 0xFFu, c_sv = codes >> 24;
-    const bool live0 = !(cur.life <= 0.0f), live1 = !(pos.w <= 0.0f);
-    const bool dead = !live0 && !live1, both = live0 && live1;
-    const float index = render_index(fx, fy);
-    const float speed1 = fmaxf(len3_fast(xyz(vel)), 0.0001f);
-    float speed0 = 0.0f;
-    if ((codes & 0x03000300u) != 0u)        // the loaded state's speed, only where a velocity curve is not constant
-        speed0 = fmaxf(len3_fast(mk3(cur.vx, cur.vy, cur.vz)), 0.0001f);
-    const CurveT cl = clamp_curve_t(p.ColorFromLife.RangeAndCount, cur.life, pos.w, c_cl);
-    const CurveT cv = clamp_curve_t(p.ColorFromVelocity.RangeAndCount, speed0, speed1, c_cv);
-    const CurveT sl = clamp_curve_t(p.SizeFromLife.RangeAndCount, cur.life, pos.w, c_sl);
-    const CurveT sv = clamp_curve_t(p.SizeFromVelocity.RangeAndCount, speed0, speed1, c_sv);
-    const float size_l = ((c_sl & 3u) == 0u) ? p.SizeFromLife.ABCD.x : bezier1_at(p.SizeFromLife, sl.t1, c_sl & 3u);
-    const float size_v = ((c_sv & 3u) == 0u) ? p.SizeFromVelocity.ABCD.x : bezier1_at(p.SizeFromVelocity, sv.t1, c_sv & 3u);
-    float4 rd;
-    rd.x = live1 ? size_l * size_v : 0.0f;
-    rd.y = live1 ? render_rotation(rotation_unscaled(vel.x, vel.y), pos.w, index, a.sys, p) : 0.0f;
-    rd.z = live1 ? speed1 : 0.0f;
-    rd.w = live1 ? vel.w : 0.0f;
-    const float y0 = render_rotation(rotation_unscaled(cur.vx, cur.vy), cur.life, index, a.sys, p);
-    const bool same_v = same_bits(cur.vx, vel.x) && same_bits(cur.vy, vel.y) && same_bits(cur.vz, vel.z);
-    const bool rc_same = dead || (both && ((a.elide & kElideColor) != 0u) && cl.same && cv.same);
-    const bool rdx_same = dead || (both && sl.same && sv.same && (rd.x == rd.x));
-    const bool rdy_same = dead || (both && same_bits(y0, rd.y) && (rd.y == rd.y));
-    const bool rdz_same = dead || (both && same_v);
-    const bool rdw_same = dead || (both && same_bits(cur.ct, vel.w) && (vel.w == vel.w));
-    if (__ballot(!rc_same) != 0ull) {
-        const float4 attr = mk4(ld_plane<true>(up, 8, lane4), ld_plane<true>(up, 9, lane4), ld_plane<true>(up, 10, lane4), ld_plane<true>(up, 11, lane4));
-        const float4 color_l = ((c_cl & 3u) == 0u) ? ld4(p.ColorFromLife.A) : bezier4_at(p.ColorFromLife, cl.t1, c_cl & 3u);
-        const float4 color_v = ((c_cv & 3u) == 0u) ? ld4(p.ColorFromVelocity.A) : bezier4_at(p.ColorFromVelocity, cv.t1, c_cv & 3u);
-        float4 rc = mul4(attr, mul4(color_l, color_v));
-        rc.w = sat(rc.w);
-        rc.x *= rc.w; rc.y *= rc.w; rc.z *= rc.w;
-        st_plane<true>(up, 12, lane4, live1 ? rc.x : 0.0f); st_plane<true>(up, 13, lane4, live1 ? rc.y : 0.0f);
-        st_plane<true>(up, 14, lane4, live1 ? rc.z : 0.0f); st_plane<true>(up, 15, lane4, live1 ? rc.w : 0.0f);
-    }
-    if (__ballot(!rdx_same) != 0ull) st_plane<true>(up, 16, lane4, rd.x);
-    if (__ballot(!rdy_same) != 0ull) st_plane<true>(up, 17, lane4, rd.y);
-    if (__ballot(!rdz_same) != 0ull) st_plane<true>(up, 18, lane4, rd.z);
-    if (__ballot(!rdw_same) != 0ull) st_plane<true>(up, 19, lane4, rd.w);
-}
-
-
-// One block of the lean step, for one curve class (the kernels below).
-template <bool SPAWN, bool STREAM, int CURVES>
-ILM_DEV void step_lean_block() {
-    static_assert(CURVES == kCurvesGeneral || (STREAM && !SPAWN), "the curve classes are instantiations of the streaming variant without spawners");
-    __shared__ uint32_t wave_live[kStepThreads / 64];
-    const LeanStep& a = *(const LeanStep*)(CLeanStep*)__builtin_amdgcn_kernarg_segment_ptr();
-    // (only the launch's first generation of blocks can be the first to read a line; for the others the loads would just load the
-    // scalar cache: one lookup per line per wave)
-    if (blockIdx.x < kTouchBlocks) touch_kernarg_lines_lean();
-    const unsigned lane = threadIdx.x & 63u;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    int v = (int)blockIdx.x * (kStepThreads / 64) + a.unit_rotate;      // first unit of the block (rotation: see step_kernel)
-    if (v >= a.total_padded) v -= a.total_padded;
-    const int u = v + wave;
-    uint32_t n_live = 0;
-    if (u < a.total_units) {
-        const int chunk_rel = u >> a.upc_shift;
-        const int seg = u - (chunk_rel << a.upc_shift);
-        const int chunk = a.first_chunk + chunk_rel;
-        bool untouched = false;
-        if (a.partial_count != 0) {
-#pragma unroll
-            for (int k = 0; k < kMaxPartialChunks; k++)
-                untouched = untouched || ((a.partial_chunk[k] == chunk) && (seg >= a.partial_units[k]));
-        }
-        if (!untouched) {
-            const unsigned lane4 = lane * 4u;
-            // the chunk table through the constant address space: a scalar load whatever the optimiser thinks may alias (behind the
-            // volatile asm of touch_kernarg_lines it would otherwise fetch the base with a VECTOR load and wrap every plane access in
-            // a waterfall loop over a "divergent" buffer resource: +160 vector instructions per wave); the table is written by a copy
-            // that precedes the launch on its stream and never during one
-            const UnitPlanes up = unit_planes(((CBase*)a.chunk_bases)[chunk], a.stride, seg * 64);
-            // a render-current chunk needs its attributes only where renderColor is recomputed: loaded below, by the waves that do
-            const bool elide = STREAM && ((CURVES == kCurvesClamp) || (a.elide & kElideDerived) != 0u);
-            SlotIn cur = load_slot<false, STREAM>(up, lane4);
-            if (!elide) {
-                cur.ar = ld_plane<STREAM>(up, 8, lane4); cur.ag = ld_plane<STREAM>(up, 9, lane4);
-                cur.ab = ld_plane<STREAM>(up, 10, lane4); cur.aa = ld_plane<STREAM>(up, 11, lane4);
-            }
-            // slot (x, y): the unit lies in one row (chunk size a multiple of 64)
-            const int first = seg * 64;
-            const int row = first >> a.cs_shift;
-            const int x0 = first - (row << a.cs_shift);
-            const float fx = (float)(x0 + (int)lane), fy = (float)row;
-            NoiseDeltas noise;
-            noise.valid = false;
-            if (a.noise_op >= 0)
-                noise = noise_prepare_lean(a, x0, row);
-
-            float4 pos = mk4(cur.px, cur.py, cur.pz, cur.life);
-            float4 vel = mk4(cur.vx, cur.vy, cur.vz, cur.ct);
-            float4 attr = mk4(cur.ar, cur.ag, cur.ab, cur.aa);
-            bool spawn_here = false, spawned = false;
-            if constexpr (SPAWN) {
-                for (int s = 0; s < a.spawn_count; s++) {
-                    if (a.spawn_chunk[s] == chunk && seg >= a.spawn_unit_lo[s] && seg <= a.spawn_unit_hi[s]) {
-                        const IlmSpawnRecord& r = a.spawns[s];
-                        const float fi = (float)(first + (int)lane);
-                        if (fi >= r.Params.ChunkSizeAndIndices[1] && fi <= r.Params.ChunkSizeAndIndices[2]) {
-                            spawn_here = true;
-                            if (spawn_slot(pos, vel, attr, fx, fy, a.rnd, a.rw, a.rh, a.inv_rw, a.inv_rh, r.Params))
-                                spawned = true;
-                        }
-                    }
-                }
-            }
-            // `<= 0` as the shaders test it: a NaN life is not dead.  A dead slot nothing writes keeps the cleared target's zeros.
-            const bool process = !(cur.life <= 0.0f) || spawn_here;
-            const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
-            float4 rc = zero, rd = zero;
-            if constexpr (CURVES == kCurvesClamp) {
-                if (__ballot(process) != 0ull) {
-                    // Every lane goes through the transforms and the update, and one select at the end keeps the live ones: a slot the
-                    // step does not process comes out as zeros whatever was computed for it.  The transforms are dispatched from
-                    // unrolled positions so that position and velocity stay in their registers from one to the next.
-#pragma unroll
-                    for (int o = 0; o < ILM_MAX_OPS; o++) {
-                        if (o < a.op_count) {
-                            const int type = a.op_type[o];
-                            if (type == ILM_OP_GRAVITY)
-                                apply_gravity_lean(pos, vel, a.op[o].gravity, a.sys.GlobalSettings.x, a.sys.GlobalSettings.z);
-                            else if (type == ILM_OP_NOISE)
-                                apply_noise(pos, vel, fx, fy, a.rnd, a.rw, a.rh, a.sys, a.op[o].noise, a.inv_rw, a.inv_rh, a.dop[o],
-                                            (o == a.noise_op) ? noise : NoiseDeltas{ false, zero, zero });
-                            else
-                                apply_fma(pos, vel, a.sys, a.op[o].fma, a.dop[o]);
-                        }
-                    }
-                    update_positions_select(pos, vel, a.sys, a.dt_s, process && !(pos.w <= 0.0f));
-                } else {
-                    pos = vel = zero;
-                }
-            } else if (__ballot(process) != 0ull) {
-                if (process) {
-                    for (int o = 0; o < a.op_count; o++) {
-                        const int type = a.op_type[o];
-                        if (type == ILM_OP_GRAVITY)
-                            apply_gravity_lean(pos, vel, a.op[o].gravity, a.sys.GlobalSettings.x, a.sys.GlobalSettings.z);
-                        else if (type == ILM_OP_NOISE)
-                            apply_noise(pos, vel, fx, fy, a.rnd, a.rw, a.rh, a.sys, a.op[o].noise, a.inv_rw, a.inv_rh, a.dop[o],
-                                        (o == a.noise_op) ? noise : NoiseDeltas{ false, zero, zero });
-                        else
-                            apply_fma(pos, vel, a.sys, a.op[o].fma, a.dop[o]);
-                    }
-                    if (pos.w <= 0.0f) {
-                        pos = vel = zero;  // readStateOrDiscard: discard => cleared target
-                    } else {
-                        update_positions(pos, vel, a.sys, a.dt_s);
-                        if (!elide)
-                            render_data(fx, fy, pos, vel, attr, a.sys, a.update, a.bezier_codes, a.update_bits, nullptr, 0, 0, rc, rd);
-                    }
-                } else {
-                    pos = vel = zero;
-                }
-            } else {
-                pos = vel = zero;
-            }
-            // STREAM: a plane is stored when some lane of the wave changed its bits (integer compares: NaN and -0.0 exactly), at full width
-            st_plane_changed<STREAM>(up, 0, lane4, pos.x, cur.px); st_plane_changed<STREAM>(up, 1, lane4, pos.y, cur.py);
-            st_plane_changed<STREAM>(up, 2, lane4, pos.z, cur.pz); st_plane_changed<STREAM>(up, 3, lane4, pos.w, cur.life);
-            st_plane_changed<STREAM>(up, 4, lane4, vel.x, cur.vx); st_plane_changed<STREAM>(up, 5, lane4, vel.y, cur.vy);
-            st_plane_changed<STREAM>(up, 6, lane4, vel.z, cur.vz); st_plane_changed<STREAM>(up, 7, lane4, vel.w, cur.ct);
-            if constexpr (SPAWN) {
-                if (spawned) {
-                    st_plane<STREAM>(up, 8, lane4, attr.x); st_plane<STREAM>(up, 9, lane4, attr.y); st_plane<STREAM>(up, 10, lane4, attr.z); st_plane<STREAM>(up, 11, lane4, attr.w);
-                }
-            }
-            if (!elide) {
-                st_plane<STREAM>(up, 12, lane4, rc.x); st_plane<STREAM>(up, 13, lane4, rc.y); st_plane<STREAM>(up, 14, lane4, rc.z); st_plane<STREAM>(up, 15, lane4, rc.w);
-                st_plane<STREAM>(up, 16, lane4, rd.x); st_plane<STREAM>(up, 17, lane4, rd.y); st_plane<STREAM>(up, 18, lane4, rd.z); st_plane<STREAM>(up, 19, lane4, rd.w);
-            } else if constexpr (CURVES == kCurvesClamp) {
-                store_changed_render_planes_clamp(a, up, lane4, fx, fy, cur, pos, vel);
-            } else {
-                store_changed_render_planes<SPAWN, STREAM>(a, up, lane4, fx, fy, cur, pos, vel, attr, spawned);
-            }
-            n_live = (uint32_t)__popcll(__ballot(pos.w > 0.0f));
-        }
-    }
-    if (a.flags & ILM_STEP_COUNT_LIVE)
-        publish_block_count(wave_live, n_live, lane, wave, v < a.total_units, a.first_chunk + (v >> a.upc_shift),
-                            (v & ((1 << a.upc_shift) - 1)) / (kStepThreads / 64), (1 << a.upc_shift) / (kStepThreads / 64), a.count_buckets,
-                            a.live_counts, a.zero_counts, a.zero_n, a.host_counts, a.count_seq);
-}
-
-// The general instantiations keep the kernel names the profiles and bench.py's traffic figures are keyed by; the class is a kernel of
-// its own (a class selected inside step_lean_kernel<false, true> by a launch-uniform word took the kernel from 8 waves per SIMD to 7 and
-// the headline from 0.78 to 0.89 ms).
-template <bool SPAWN, bool STREAM>
-__global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep a_) { step_lean_block<SPAWN, STREAM, kCurvesGeneral>(); }
-__global__ __launch_bounds__(kStepThreads) void step_lean_clamp_kernel(const LeanStep a_) { step_lean_block<false, true, kCurvesClamp>(); }
-
-// ---------------------------------------------------------------------------------------------
-// the lean collision step (r06) -- UpdateParticleSystemWithDistanceField.fx:29-147 on the lean descriptor
-// ---------------------------------------------------------------------------------------------
-// The collision update is two things in one shader.  EVERY live particle samples the field where it is and where it is going (the
-// first iteration of the sweep): two dependent lookups, the same for all lanes.  A particle whose first sweep lookup lands inside an
-// obstacle (14 % of them on the demo's field) goes on: up to two more sweep lookups, estimateNormal4 (four more), the bounce / redirect
-// / escape arithmetic -- about as many vector instructions again as the whole rest of the step, run by a wave for its few such lanes
-// (the interpreter's step_kernel<.., DF>: 1 071 instructions per wave at 39.4 of 64 lanes, profiles/r06_collision_step.txt).
-// Here a wave walks K consecutive units in three phases.
-//   A  per unit: load, spawn, transforms, the common path at full width.  The lanes that collided are PARKED -- their state after the
-//      transforms and the two distances already sampled, eleven words, in a ring of 128 entries the wave owns in LDS (no barrier: the
-//      ring is private to the wave).  The unit's position and velocity stay in registers; nothing is stored yet.
-//   L  whenever 64 are parked, and once more after the last unit: the parked particles, one per lane, through the rest of the reference
-//      update (df_long: the operations of update_with_distance_field behind its first lookup); the results go back into
-//      the same ring entries.
-//   B  per unit: the parked lanes take their results from the ring, then computeRenderData and all sixteen stores at FULL width.
-// So the long path runs at 64 lanes -- or, for the remainder, at whatever K units leave -- instead of at ~9 lanes once per unit, and
-// every plane of a unit is still written by ONE full-width store (a first form of this kernel stored the finished lanes at once and
-// the parked ones later, from the long pass: two partial writes per line, and cfg4's share took 507-597 us against the interpreter's
-// 394 -- masked and scattered 4-byte stores cost a read-modify-write each once the line has left the L2).
-// A ring that would overflow (more than 128 of a wave's K x 64 particles colliding) is not waited for: that unit's parked lanes take the
-// long path in place, as the interpreter does.
-struct LeanStepDf {
-    LeanStep base;
-    IlmDistanceFieldUniforms df;
-    SdfView sdf;
-};
-static_assert(sizeof(LeanStepDf) <= 4096, "LeanStepDf travels in the kernarg segment (4 KB)");
-static_assert(sizeof(LeanStepDf) > 0xd40 && sizeof(LeanStepDf) <= 0xe00, "touch_kernarg_lines_lean_df reads one dword of each 64-byte line of LeanStepDf");
-ILM_DEV void touch_kernarg_lines_lean_df() {       // LeanStepDf: 54 .. 56 lines
-    const auto kp = __builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t sink;
-    asm volatile(ILM_T16(0x0) ILM_T16(0x400) ILM_T16(0x800) ILM_T4(0xc00) ILM_T1(0xd00) ILM_T1(0xd40) "s_waitcnt lgkmcnt(0)"
-                 : "=&s"(sink) : "s"(kp));
-}
-typedef const LeanStepDf __attribute__((address_space(4))) CLeanStepDf;
-
-constexpr int kDfRing = 128;                     // parked particles per wave
-struct DfParked { float px[kDfRing], py[kDfRing], pz[kDfRing], life[kDfRing], vx[kDfRing], vy[kDfRing], vz[kDfRing], ct[kDfRing], d0[kDfRing], d1[kDfRing]; uint32_t slot[kDfRing]; };   // slot: bit 31 = d1 is the first iteration's lookup
-
-// The common path of PS_Update (distance field) for a live slot (life > 0 on entry): everything a particle needs that meets no obstacle.
-// The reference samples the field at the particle (initial_distance) and then at old + unit * travel with travel = max(0, min(
-// initial_distance, |velocity| dt)) -- two DEPENDENT lookups.  Away from obstacles travel IS |velocity| dt, known before any lookup: both
-// positions are sampled at once, and when min() did pick |velocity| dt (bit for bit) the second sample is the sweep's first
-// step_distance -- same position, same bits.  Returns 0 when the particle is finished (position and velocity final; zeros for one that
-// died); 1 when it must go on with the sweep's first iteration still to do (travel is not |velocity| dt: it sits at or inside an
-// obstacle); 2 when the first iteration is done and collided (step_distance valid).  For 1 and 2 position and velocity are left as they
-// came: the caller parks them for df_long.  Same operations in the same order as update_with_distance_field takes on these paths
-// (tests/test_step_kernels_gpu.py holds the kernels bit-equal, sample counts included).
-template <int FMT>
-ILM_DEV int df_common_path(float4& pos, float4& vel, const IlmParticleSystemUniforms& sys, float dts, const IlmDistanceFieldUniforms& df, const SdfView& sdf, int& samples,
-                           float& initial_distance, float& step_distance) {
-#pragma clang fp contract(off)
-    const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
-    const float new_life = pos.w - (sys.GlobalSettings.w * dts);
-    initial_distance = step_distance = 0.0f;
-    if (new_life <= 0.0f) {
-        pos = vel = zero;
-        return 0;
-    }
-    const float collision_distance = sys.CollisionSettings.z;
-    const f3 old_xyz = xyz(pos);
-    const f3 unit_vector = norm3(xyz(vel));
-    const f3 velocity = friction_and_maximum(xyz(vel), sys, dts);
-    const f3 scaled_velocity = velocity * dts;
-    const float reach = len3(scaled_velocity);
-    const f3 ahead = old_xyz + (unit_vector * reach);
-    initial_distance = sample_distance_field<(FMT & 1), true, (FMT & 2) != 0, (FMT & 4) != 0>(old_xyz, df, sdf);
-    step_distance = sample_distance_field<(FMT & 1), true, (FMT & 2) != 0, (FMT & 4) != 0>(ahead, df, sdf);        // (independent of the first: both in flight together)
-    samples++;
-    const bool was_colliding = initial_distance < collision_distance;
-    const float travel_distance = fmaxf(0.0f, fminf(initial_distance, reach));
-    if (__builtin_bit_cast(uint32_t, travel_distance) != __builtin_bit_cast(uint32_t, reach))
-        return 1;                                                 // the sweep starts somewhere else than `ahead`
-    if (was_colliding || !(travel_distance <= 0.001f)) {          // step_count 1 or MAX_STEP_COUNT: the sweep's first iteration runs, at `ahead`
-        samples++;
-        if (step_distance < collision_distance)
-            return 2;
-    }
-    pos = mk4(ahead.x, ahead.y, ahead.z, new_life);
-    vel = mk4(velocity.x, velocity.y, velocity.z, fmaxf(vel.w - 1.0f, 0.0f));
-    return 0;
-}
-
-// The rest of PS_Update (distance field) for a parked particle: update_with_distance_field with its first lookup (initial_distance) given
-// and, when `first_done`, the first iteration's lookup (step_distance0) too.  Operation for operation the function above -- the uniform
-// values and the vectors that depend on the inputs alone (unit vector, velocity after friction, travel distance) are formed again by
-// the same operations.
+// PS_Update, UpdateParticleSystemWithDistanceField.fx:29-147, behind its first lookup: the sweep and the bounce / redirect / escape
+// arithmetic for a live slot whose life does not run out in this step, given initial_distance (the field at the particle) and, when
+// `first_done`, the lookup of the sweep's first iteration (step_distance0) too.  The only statement of them: the interpreter comes
+// here from update_with_distance_field, the lean collision kernel with a parked particle (df_common_path made its lookups).
 template <int FMT>
 ILM_DEV void df_long(float4& pos, float4& vel, float x, float y, float initial_distance, float step_distance0, bool first_done,
                      const IlmParticleSystemUniforms& sys, float dts, const IlmDistanceFieldUniforms& df, const SdfView& sdf, int& samples) {
@@ -1802,6 +852,818 @@ ILM_DEV void df_long(float4& pos, float4& vel, float x, float y, float initial_d
     vel = new_velocity;
 }
 
+// PS_Update with the distance field for a live slot: the life test, the first lookup, then df_long
+template <int FMT>
+ILM_DEV void update_with_distance_field(float4& pos, float4& vel, float x, float y, const IlmParticleSystemUniforms& sys, float dts,
+                                        const IlmDistanceFieldUniforms& df, const SdfView& sdf, int& samples) {
+#pragma clang fp contract(off)   // discontinuous collision state machine + life arithmetic: keep IEEE-exact
+    if (pos.w - (sys.GlobalSettings.w * dts) <= 0.0f) {
+        pos = vel = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const float initial_distance = sample_distance_field<(FMT & 1), true, (FMT & 2) != 0, (FMT & 4) != 0>(xyz(pos), df, sdf);
+    samples++;
+    df_long<FMT>(pos, vel, x, y, initial_distance, 0.0f, false, sys, dts, df, sdf, samples);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the fused step kernel
+// ---------------------------------------------------------------------------------------------
+// One wave = one unit of 64 consecutive slots, one lane = one slot: a wave reads / writes 256 contiguous bytes of each component
+// plane per instruction.
+
+struct SlotIn {
+    float px, py, pz, life, vx, vy, vz, ct, ar, ag, ab, aa;
+};
+
+// The 20 planes of one unit through ONE buffer resource (the chunk's allocation) and one lane offset: plane c of the unit is
+// `buffer_load/store_dword v, v_lane_offset, s[rsrc], s_plane_offset offen` with s_plane_offset = (first slot + c * stride) * 4 in an
+// SGPR -- twenty 32-bit scalar adds per wave.  (The flat form, `global_load_dword v, v_lane_offset, s[base:base+1]`, needs a 64-bit
+// base per plane: 2 scalar instructions per plane, computed once for the loads and again for the stores -- 80 of the ~370 scalar
+// instructions a wave issued, and the scalar pipe, one instruction per cycle per CU against the four SIMDs' vector issue, is what
+// the step's issue phase is bound by: tools/ubench/salu.)
+struct UnitPlanes {
+    __amdgpu_buffer_rsrc_t rsrc;
+    uint32_t so[kComponents];
+};
+
+ILM_DEV UnitPlanes unit_planes(const float* chunk_base, int64_t stride, int first_slot) {
+    UnitPlanes u;
+    // raw buffer (stride 0), num_records = the chunk's bytes, DATA_FORMAT = 32 bits (0x00020000, the word gfx9 wants for untyped access)
+    u.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)chunk_base, 0, (int)(stride * (kComponents * 4)), 0x00020000);
+    const uint32_t s4 = (uint32_t)stride * 4u;
+    u.so[0] = (uint32_t)first_slot * 4u;
+#pragma unroll
+    for (int c = 1; c < kComponents; c++) u.so[c] = u.so[c - 1] + s4;
+    return u;
+}
+
+// STREAM: the launch's working set is larger than the Infinity Cache (api.hip decides), every plane is touched once per step: loads and
+// stores carry the non-temporal hint so they do not evict each other on the way through (tools/ubench/stream: 8.4 M slots 187 -> 170 us;
+// on a cache-resident working set the same hint costs 25 %, so small systems keep the default policy).
+// Cache policy bits of the plane accesses (buffer intrinsic aux word on gfx94x / gfx950: 1 = sc0, 2 = nt, 16 = sc1).
+// Stores of the cache-resident variant carry sc1: they write through the XCD's L2 instead of leaving dirty lines there.  Every L2 is
+// private to its XCD, so a kernel's release writes back whatever is still dirty before the next launch of the stream may start --
+// up to 8 x 4 MB after a cfg2 step, ~6 us during which nothing runs (per-wave timestamps of an instrumented build: the waves of a
+// 16-chunk launch span 17.5 us, back-to-back launches took 24).  The written planes are read next by another launch, on whichever XCD,
+// after an invalidate: keeping them in this L2 buys nothing.  tools/step_ab.py: cfg2 without a spawner 20.3 -> 17.5 us per step, with
+// 23.4 -> 22.0 (21.0 -> 19.4 / 24.5 -> 23.5 on one stream); sc0, nt, nt + sc1 and non-temporal loads all lose on a resident working set.
+constexpr int kLdAux = 0, kStAux = 16, kLdAuxStream = 2, kStAuxStream = 2;
+template <bool STREAM>
+ILM_DEV float ld_plane(const UnitPlanes& u, int c, unsigned lane4) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(u.rsrc, (int)lane4, (int)u.so[c], STREAM ? kLdAuxStream : kLdAux));
+}
+template <bool STREAM>
+ILM_DEV void st_plane(const UnitPlanes& u, int c, unsigned lane4, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), u.rsrc, (int)lane4, (int)u.so[c], STREAM ? kStAuxStream : kStAux);
+}
+
+// The plane groups of a unit (internal.hpp): position and velocity, the attributes, renderColor and renderData
+template <bool STREAM>
+ILM_DEV float4 load_attributes(const UnitPlanes& u, unsigned lane4) {
+    return mk4(ld_plane<STREAM>(u, 8, lane4), ld_plane<STREAM>(u, 9, lane4), ld_plane<STREAM>(u, 10, lane4), ld_plane<STREAM>(u, 11, lane4));
+}
+template <bool STREAM>
+ILM_DEV void store_state(const UnitPlanes& u, unsigned lane4, float4 pos, float4 vel) {
+    st_plane<STREAM>(u, 0, lane4, pos.x); st_plane<STREAM>(u, 1, lane4, pos.y); st_plane<STREAM>(u, 2, lane4, pos.z); st_plane<STREAM>(u, 3, lane4, pos.w);
+    st_plane<STREAM>(u, 4, lane4, vel.x); st_plane<STREAM>(u, 5, lane4, vel.y); st_plane<STREAM>(u, 6, lane4, vel.z); st_plane<STREAM>(u, 7, lane4, vel.w);
+}
+template <bool STREAM>
+ILM_DEV void store_attributes(const UnitPlanes& u, unsigned lane4, float4 attr) {
+    st_plane<STREAM>(u, 8, lane4, attr.x); st_plane<STREAM>(u, 9, lane4, attr.y); st_plane<STREAM>(u, 10, lane4, attr.z); st_plane<STREAM>(u, 11, lane4, attr.w);
+}
+template <bool STREAM>
+ILM_DEV void store_render_color(const UnitPlanes& u, unsigned lane4, float4 rc) {
+    st_plane<STREAM>(u, 12, lane4, rc.x); st_plane<STREAM>(u, 13, lane4, rc.y); st_plane<STREAM>(u, 14, lane4, rc.z); st_plane<STREAM>(u, 15, lane4, rc.w);
+}
+template <bool STREAM>
+ILM_DEV void store_render(const UnitPlanes& u, unsigned lane4, float4 rc, float4 rd) {
+    store_render_color<STREAM>(u, lane4, rc);
+    st_plane<STREAM>(u, 16, lane4, rd.x); st_plane<STREAM>(u, 17, lane4, rd.y); st_plane<STREAM>(u, 18, lane4, rd.z); st_plane<STREAM>(u, 19, lane4, rd.w);
+}
+// the cleared target of the update pass (the attributes keep what they hold)
+template <bool STREAM>
+ILM_DEV void store_zero_state_and_render(const UnitPlanes& u, unsigned lane4) {
+    const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    store_state<STREAM>(u, lane4, zero, zero);
+    store_render<STREAM>(u, lane4, zero, zero);
+}
+
+template <bool ATTR, bool STREAM>
+ILM_DEV SlotIn load_slot(const UnitPlanes& u, unsigned lane4) {
+    SlotIn s;
+    s.life = ld_plane<STREAM>(u, 3, lane4);
+    s.px = ld_plane<STREAM>(u, 0, lane4); s.py = ld_plane<STREAM>(u, 1, lane4); s.pz = ld_plane<STREAM>(u, 2, lane4);
+    s.vx = ld_plane<STREAM>(u, 4, lane4); s.vy = ld_plane<STREAM>(u, 5, lane4); s.vz = ld_plane<STREAM>(u, 6, lane4); s.ct = ld_plane<STREAM>(u, 7, lane4);
+    const float4 attr = ATTR ? load_attributes<STREAM>(u, lane4) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    s.ar = attr.x; s.ag = attr.y; s.ab = attr.z; s.aa = attr.w;
+    return s;
+}
+
+// The launch descriptor lives in the kernarg segment (constant address space) and the per-unit body reads
+// every parameter through a pointer to it (s_load from a uniform address).
+typedef const StepLaunch __attribute__((address_space(4))) CStepLaunch;
+
+// DF: the update pass is UpdateWithDistanceField (pulls in the SDF sampler); SPAWN: spawn records present.
+// Both are compile-time so the common no-field / no-spawn step does not pay their registers.
+template <int FMT, bool DF, bool SPAWN, bool EXT, bool STREAM>
+ILM_DEV bool process_unit(CStepLaunch* ap, const UnitPlanes& up, int chunk, int i, unsigned lane, int seg, SlotIn cur, const NoiseDeltas& noise) {
+    const StepLaunch& a = *(const StepLaunch*)ap;
+    const IlmStepDesc& d = a.desc;
+    const int64_t S = a.stride;
+    const unsigned lane4 = lane * 4u;
+    const int mode = d.UpdateMode;
+    const bool need_attr = (mode == ILM_UPDATE_POSITIONS) || (mode == ILM_UPDATE_WITH_DISTANCE_FIELD);
+    // Noise has no life check (Noise.fx:40): dead slots go through it.  That only matters when its result survives --
+    // no update pass follows (single-pass ilm_noise), or the op can bring a dead slot back to life (StepDerived).
+    const uint32_t noise_ops = EXT ? ((1u << ILM_OP_NOISE) | (1u << ILM_OP_SPATIAL_NOISE)) : (1u << ILM_OP_NOISE);
+    const bool has_noise = ((a.op_mask & noise_ops) != 0u) && ((mode == ILM_UPDATE_NONE) || (a.derived.noise_may_revive != 0));
+    const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+
+    bool spawn_here = false;
+    if constexpr (SPAWN) {
+        for (int s = 0; s < d.SpawnCount; s++) {
+            const IlmSpawnRecord& r = d.Spawns[s];
+            if (r.ChunkIndex == chunk && (float)i >= r.Params.ChunkSizeAndIndices[1] && (float)i <= r.Params.ChunkSizeAndIndices[2])
+                spawn_here = true;
+        }
+    }
+    bool live_after = false;
+    int sdf_samples = 0;
+    // Stride padding (chunk sizes whose square is not a multiple of 1024: 10, 16, 48 ...): not a slot of the chunk.  Noise has no life
+    // check, so without this a padding lane could be given a life, be updated and be counted (CountLiveParticles.fx counts ChunkSize^2 pixels).
+    if (i >= a.slots)
+        return false;
+    if (mode == ILM_UPDATE_ERASE) {
+        // PS_Erase, UpdateParticleSystem.fx:40-49
+        store_zero_state_and_render<STREAM>(up, lane4);
+    } else if ((cur.life <= 0.0f) && !spawn_here && !has_noise) {     // `<= 0` as the shaders test it: a NaN life is not dead
+        // dead and nothing writes it: the update pass leaves the cleared target
+        // (UpdateHandler._BeforeDraw clears, ParticleTransform.cs:164-165; readStateOrDiscard discards)
+        if (mode != ILM_UPDATE_NONE)
+            store_zero_state_and_render<STREAM>(up, lane4);
+        else {
+            live_after = cur.life > 0.0f;   // untouched slots keep their liveness when no update pass ran
+        }
+    } else {
+        float4 pos = mk4(cur.px, cur.py, cur.pz, cur.life);
+        float4 vel = mk4(cur.vx, cur.vy, cur.vz, cur.ct);
+        float4 attr = mk4(cur.ar, cur.ag, cur.ab, cur.aa);
+        // slot (x, y): the unit's first slot is divided on the scalar unit, lanes only fold the row wrap
+        const int cs = a.chunk_size;
+        const int row0 = (a.derived.cs_shift >= 0) ? ((seg * 64) >> a.derived.cs_shift) : __builtin_amdgcn_readfirstlane((seg * 64) / cs);
+        int sy = row0, sx = (seg * 64 - row0 * cs) + (int)lane;
+        while (sx >= cs) { sx -= cs; sy++; }
+        const float fx = (float)sx, fy = (float)sy;
+        bool spawned = false;
+
+        if constexpr (SPAWN) {
+            if (spawn_here) {
+                for (int s = 0; s < d.SpawnCount; s++) {
+                    if (d.Spawns[s].ChunkIndex == chunk) {
+                        bool wrote;
+                        if (EXT && d.Spawns[s].Kind == ILM_SPAWN_POSITION_BUFFER)
+                            wrote = spawn_slot_position_buffer(pos, vel, attr, fx, fy, a.rnd, a.rw, a.rh, a.derived.inv_rw, a.derived.inv_rh,
+                                                               d.Spawns[s].Params, a.spawn_positions[s], a.spawn_position_count[s]);
+                        else if (EXT && d.Spawns[s].Kind == ILM_SPAWN_FEEDBACK)
+                            wrote = spawn_slot_feedback(pos, vel, attr, fx, fy, a.rnd, a.rw, a.rh, a.derived.inv_rw, a.derived.inv_rh,
+                                                        d.Spawns[s].Params, d.Spawns[s].Feedback, a.source_base[s], S, cs);
+                        else if (EXT && d.Spawns[s].Kind == ILM_SPAWN_PATTERN)
+                            wrote = spawn_slot_pattern(pos, vel, attr, fx, fy, a.rnd, a.rw, a.rh, a.derived.inv_rw, a.derived.inv_rh,
+                                                       d.Spawns[s].Params, d.Spawns[s].Pattern, a.spawn_pattern[s], a.pattern_w[s],
+                                                       a.pattern_h[s], a.pattern_levels[s]);
+                        else
+                            wrote = spawn_slot(pos, vel, attr, fx, fy, a.rnd, a.rw, a.rh, a.derived.inv_rw, a.derived.inv_rh, d.Spawns[s].Params);
+                        if (wrote)
+                            spawned = true;
+                    }
+                }
+            }
+        }
+
+        for (int o = 0; o < d.OpCount; o++) {
+            const IlmTransformOp& op = d.Ops[o];
+            if (op.Type == ILM_OP_GRAVITY)
+                apply_gravity(pos, vel, d.System, op.u.Gravity, a.derived.op[o]);
+            else if (op.Type == ILM_OP_NOISE)
+                apply_noise(pos, vel, fx, fy, a.rnd, a.rw, a.rh, d.System, op.u.Noise, a.derived.inv_rw, a.derived.inv_rh, a.derived.op[o],
+                            (o == a.derived.noise.op) ? noise : NoiseDeltas{ false, zero, zero });
+            else if (op.Type == ILM_OP_FMA)
+                apply_fma(pos, vel, d.System, op.u.FMA, a.derived.op[o]);
+            else if (EXT && op.Type == ILM_OP_MATRIX_MULTIPLY)
+                apply_matrix_multiply(pos, vel, d.System, op.u.MatrixMultiply);
+            else if (EXT && op.Type == ILM_OP_SPATIAL_NOISE)
+                apply_spatial_noise(pos, vel, a.rnd_lp, a.rw, a.rh, d.System, op.u.SpatialNoise, a.derived);
+        }
+
+        float4 rc = zero, rd = zero;
+        if (need_attr) {
+            if (pos.w <= 0.0f) {
+                pos = vel = zero;  // readStateOrDiscard: discard => cleared target
+            } else {
+                if constexpr (DF)
+                    update_with_distance_field<FMT>(pos, vel, fx, fy, d.System, a.derived.dt_s, d.DistanceField, a.sdf, sdf_samples);
+                else
+                    update_positions(pos, vel, d.System, a.derived.dt_s);
+                render_data(fx, fy, pos, vel, attr, d.System, d.Update, a.derived.bezier_codes, a.derived.update_bits, a.ramp, a.ramp_w, a.ramp_h, rc, rd);
+            }
+        }
+        store_state<STREAM>(up, lane4, pos, vel);
+        if (spawned)
+            store_attributes<STREAM>(up, lane4, attr);
+        if (need_attr)
+            store_render<STREAM>(up, lane4, rc, rd);
+        live_after = pos.w > 0.0f;
+    }
+    if constexpr (DF) {
+        // diagnostic count (one atomic per lane: only ever on while bench.py takes the collision row's sample count)
+        if ((__builtin_amdgcn_readfirstlane(g_step_count_sdf_samples) != 0) && (sdf_samples != 0))
+            atomicAdd(&g_step_sdf_samples, (unsigned long long)sdf_samples);
+    }
+
+    return live_after;
+}
+
+// CountLiveParticles.fx for a block of the step kernels: LDS sum over the block's waves, ONE 64-bit atomic per block on a bucket
+// counter of its chunk (live particles in the low word, a ticket in the high word); the block that draws a bucket's last ticket
+// carries the bucket's sum to the chunk's counter the same way, and the one that completes the chunk stores the total, tagged with
+// the step's sequence number, straight into the host's table.  (Per-wave atomics on one address serialise at ~11 ns each: 1024 of
+// them per chunk made the step 7x slower; one per block on ONE address per chunk still queued 4096 deep on 1024^2 chunks.)  The
+// units of a block always belong to one chunk.
+ILM_DEV void publish_block_count(uint32_t* wave_live, uint32_t n_live, unsigned lane, int wave, bool block_in_range, int chunk, int block_in_chunk,
+                                 int blocks_per_chunk, int buckets, unsigned long long* live_counts, unsigned long long* zero_counts, int zero_n,
+                                 unsigned long long* host_counts, uint32_t seq) {
+    if (blockIdx.x == 0)
+        for (int i = (int)threadIdx.x; i < zero_n; i += kStepThreads) zero_counts[i * kCountStride] = 0ull;
+    if (lane == 0) wave_live[wave] = n_live;
+    __syncthreads();
+    if (threadIdx.x == 0 && block_in_range) {
+        uint32_t block_live = 0;
+#pragma unroll
+        for (int w = 0; w < kStepThreads / 64; w++) block_live += wave_live[w];
+        unsigned long long* lines = live_counts + (size_t)chunk * (kCountLines * kCountStride);
+        const int bucket = block_in_chunk & (buckets - 1);
+        const unsigned long long old = atomicAdd(&lines[(1 + bucket) * kCountStride], (1ull << 32) | (unsigned long long)block_live);
+        if ((int)(old >> 32) + 1 == blocks_per_chunk / buckets) {
+            const unsigned long long sum = (old & 0xFFFFFFFFull) + (unsigned long long)block_live;
+            const unsigned long long old2 = atomicAdd(&lines[0], (1ull << 32) | sum);
+            if ((int)(old2 >> 32) + 1 == buckets) {
+                const unsigned long long total = (old2 & 0xFFFFFFFFull) + sum;
+                __hip_atomic_store(&host_counts[chunk], ((unsigned long long)seq << 32) | (total & 0xFFFFFFFFull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
+// The launch descriptor is written by the host into the kernarg ring just before the launch, so the first wave of every scalar cache
+// misses on each of its 64-byte lines all the way to memory -- and the step reads them one dependent phase after another (decode,
+// planes, noise tables, each transform, the update pass): a chain of ~20 serial misses at the head of every launch.  One load per
+// line, all in flight at once, turns the chain into a single miss; for every later wave they are ~60 cache hits the scalar pipe has
+// room for (tools/step_ab.py with 200 extra scalar instructions per wave: no change in step time).  Measured (r02): a one-chunk launch
+// 7.7 -> 6.0 us back to back (10.8 -> 8.3 us when it spawns), cfg2 without a spawner 24.0 -> 21.4 us per step.
+constexpr int kTouchBlocks = 2048 / (kStepThreads / 64);      // the launch's first 2 048 waves
+// The chunk table is read through the constant address space in both kernels: see step_lean_kernel.
+typedef float* const __attribute__((address_space(4))) CBase;
+#define ILM_T1(o) "s_load_dword %0, %1, " #o "\n"
+#define ILM_T4(o) ILM_T1(o) ILM_T1(o + 0x40) ILM_T1(o + 0x80) ILM_T1(o + 0xc0)
+#define ILM_T16(o) ILM_T4(o) ILM_T4(o + 0x100) ILM_T4(o + 0x200) ILM_T4(o + 0x300)
+ILM_DEV void touch_kernarg_lines_lean() {       // LeanStep: 51 lines
+    const auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    uint32_t sink;
+    asm volatile(ILM_T16(0x0) ILM_T16(0x400) ILM_T16(0x800) ILM_T1(0xc00) ILM_T1(0xc40) ILM_T1(0xc80) "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(sink) : "s"(kp));
+}
+ILM_DEV void touch_kernarg_lines_step() {       // StepLaunch: 63 lines
+    const auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    uint32_t sink;
+    asm volatile(ILM_T16(0x0) ILM_T16(0x400) ILM_T16(0x800) ILM_T4(0xc00) ILM_T4(0xd00) ILM_T4(0xe00) ILM_T1(0xf00) ILM_T1(0xf40) ILM_T1(0xf80)
+                 "s_waitcnt lgkmcnt(0)" : "=&s"(sink) : "s"(kp));
+}
+static_assert(sizeof(StepLaunch) >= 0xf84 && sizeof(StepLaunch) <= 0xfc0, "touch_kernarg_lines_step reads one dword of each 64-byte line of StepLaunch");
+
+// One wave = one unit of 64 consecutive slots; the hardware dispatcher balances the waves.  (A persistent,
+// software-pipelined variant of this kernel measured 12-25 % slower: the body is a long dependent chain --
+// state loads, scalar parameter fetches, randomness gathers -- whose latency is hidden by wave occupancy,
+// not by prefetching; see DESIGN.md.)  MINW = minimum waves per SIMD requested from the register allocator.
+template <int FMT, bool DF, bool SPAWN, int MINW, bool EXT = false, bool STREAM = false>
+__global__ __launch_bounds__(kStepThreads, MINW) void step_kernel(const StepLaunch a) {
+    __shared__ uint32_t wave_live[kStepThreads / 64];
+    CStepLaunch* ap = (CStepLaunch*)__builtin_amdgcn_kernarg_segment_ptr();
+    if (blockIdx.x < kTouchBlocks) touch_kernarg_lines_step();
+    // the wave index is uniform by construction; saying so keeps the unit / chunk / base-pointer arithmetic on the
+    // scalar unit and lets every plane access use the SGPR-base + 32-bit lane-offset addressing form
+    const unsigned lane = threadIdx.x & 63u;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    // Blocks are rotated so that block 0 holds the first unit of the first spawn range: a spawning wave is a long
+    // dependent chain (randomness gathers, sin/cos/acos), so it has to start first to finish under the cover of
+    // the streaming waves instead of forming the tail of the launch.  unit_rotate is a multiple of the units per block; those
+    // divide units_per_chunk (a multiple of 16), so a block lies in one chunk.
+    int v = (int)blockIdx.x * (kStepThreads / 64) + a.unit_rotate;          // first unit of the block
+    const int total = a.unit_end - a.unit_begin;
+    if (v >= a.total_padded) v -= a.total_padded;
+    const int u = a.unit_begin + v + wave;
+    uint32_t n_live = 0;
+    if (v + wave < total) {
+        // (a scalar integer division costs ~35 instructions per wave)
+        const int chunk_rel = (a.upc_shift >= 0) ? (u >> a.upc_shift) : (u / a.units_per_chunk);
+        const int seg = u - chunk_rel * a.units_per_chunk;
+        const int chunk = a.first_chunk + chunk_rel;
+        // never-written tail of a spawn-target chunk: all planes are zero and stay zero (scalar compares, uniform branch)
+        bool untouched = false;
+        for (int k = 0; k < a.partial_count; k++)
+            untouched = untouched || ((a.partial_chunk[k] == chunk) && (seg >= a.partial_units[k]));
+        if (!untouched) {
+            const UnitPlanes up = unit_planes(((CBase*)a.chunk_bases)[chunk], a.stride, seg * 64);
+            // (a wave that loads K > 1 units up front and processes them in turn loses more occupancy to the extra registers than the
+            // loads in flight return: cfg2 26.1 / 30.5 / 36.5 us per step for K = 1 / 2 / 4, docs/experiments.md)
+            const SlotIn cur = load_slot<true, STREAM>(up, lane * 4u);
+            NoiseDeltas noise;
+            noise.valid = false;
+            if (a.derived.noise.op >= 0) {
+                // first slot of the unit -> (x0, y): scalar; the unit lies in one row (chunk size a multiple of 64)
+                const int first = seg * 64;
+                const int row = (a.derived.cs_shift >= 0) ? (first >> a.derived.cs_shift) : (first / a.chunk_size);
+                noise = noise_prepare(((const StepLaunch*)ap)->derived.noise, reinterpret_cast<const IlmFloat4*>(&((const StepLaunch*)ap)->desc.Spawns[0]), first - row * a.chunk_size, row);
+            }
+            const bool live_after = process_unit<FMT, DF, SPAWN, EXT, STREAM>(ap, up, chunk, seg * 64 + (int)lane, lane, seg, cur, noise);
+            n_live = (uint32_t)__popcll(__ballot(live_after));
+        }
+    }
+    if (a.desc.Flags & ILM_STEP_COUNT_LIVE) {
+        const int first_unit = a.unit_begin + v;
+        const int chunk_rel = (a.upc_shift >= 0) ? (first_unit >> a.upc_shift) : (first_unit / a.units_per_chunk);
+        constexpr int kUnitsPerBlock = kStepThreads / 64;
+        publish_block_count(wave_live, n_live, lane, wave, v < total, a.first_chunk + chunk_rel, (first_unit - chunk_rel * a.units_per_chunk) / kUnitsPerBlock,
+                            a.units_per_chunk / kUnitsPerBlock, a.count_buckets, a.live_counts, a.zero_counts, a.zero_n, a.host_counts, a.count_seq);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// the lean step kernel
+// ---------------------------------------------------------------------------------------------
+// step_kernel above interprets an arbitrary IlmStepDesc: per wave ~370 scalar-ALU instructions, ~70 scalar loads and ~60 branches next
+// to ~365 vector instructions.  The scalar pipe issues one instruction per cycle per CU against the four SIMDs' vector issue
+// (tools/ubench/salu: ~550 G/s against ~950 G/s), and every dependent scalar load the interpreter waits for is latency in the life of
+// a wave whose whole launch is only two to three wave generations long -- so on a cache-resident system (cfg2) the step's time
+// follows the scalar work, not the bytes.  step_lean_kernel runs the common shape of a step -- power-of-two chunk size >= 64,
+// UpdatePositions, Gravity / Noise (no area, wave-uniform deltas available) / FMA (no area) in any order, inline spawners, no life
+// ramp, no Noise that can revive a slot -- from a pre-digested descriptor (LeanStep, built by launch_step from the same StepLaunch):
+// every uniform decision arrives as an integer, the attractors as one 32-byte record each, the spawn ranges as unit ranges.  The
+// per-slot arithmetic is the interpreter's own (same functions or the same operations in the same order): ILM_STEP_LEAN=0 runs the
+// interpreter instead and tests/test_properties_gpu.py requires the two to agree bit for bit.
+struct LeanAttractor { float x, y, z, radius, strength, _p0, _p1, _p2; };
+constexpr int kLeanMaxAttractors = 8;
+struct LeanGravity {
+    int32_t count; uint32_t types;   // 2 bits per attractor: 0 physical (ars.z < 0.5), 1 linear, 2 squared (Gravity.fx:36-52)
+    float max_accel, _pad0;
+    float cat_lo, cat_hi, _pad1, _pad2;
+    LeanAttractor a[kLeanMaxAttractors];
+};
+union LeanOp {
+    LeanGravity gravity;
+    IlmNoiseParams noise;
+    IlmFMAParams fma;
+};
+struct LeanStep {
+    // decode
+    float* const* chunk_bases;
+    unsigned long long* live_counts; unsigned long long* zero_counts; unsigned long long* host_counts;
+    int64_t stride;
+    int32_t upc_shift, unit_rotate, total_padded, total_units;
+    int32_t first_chunk, cs_shift, zero_n; uint32_t flags;
+    uint32_t count_seq; int32_t count_buckets; int32_t _pad3[2];
+    int32_t partial_chunk[kMaxPartialChunks], partial_units[kMaxPartialChunks];     // unused entries: chunk -1
+    int32_t partial_count, op_count, spawn_count; uint32_t elide;      // elide: kElideDerived / kElideColor (step_lean_kernel)
+    int32_t op_type[ILM_MAX_OPS];
+    int32_t spawn_chunk[ILM_MAX_SPAWNS], spawn_unit_lo[ILM_MAX_SPAWNS], spawn_unit_hi[ILM_MAX_SPAWNS];   // segments of the target chunk a record touches
+    int32_t _pad1[2];
+    // update pass
+    float dt_s; uint32_t bezier_codes, update_bits; int32_t noise_op;
+    IlmParticleSystemUniforms sys;
+    IlmUpdateParams update;
+    // transforms
+    StepDerived::Op dop[ILM_MAX_OPS];
+    LeanOp op[ILM_MAX_OPS];
+    StepDerived::NoiseFast noise;
+    // spawners (inline kind only) -- or, in a launch without them, the 5 x 5 noise tables (kNoiseBigClasses)
+    const float4* rnd; int32_t rw, rh; float inv_rw, inv_rh; int32_t _pad2[2];
+    union {
+        IlmSpawnRecord spawns[ILM_MAX_SPAWNS];
+        IlmFloat4 noise_big[2 * kNoiseBigClasses * kNoiseBigClasses];
+    };
+};
+static_assert(sizeof(LeanStep) <= 4096, "LeanStep travels in the kernarg segment (4 KB)");
+
+// PS_Gravity with the attractor records and type codes of LeanGravity: apply_gravity's terms (gravity_term), added in its order
+ILM_DEV void apply_gravity_lean(float4& pos, float4& vel, const LeanGravity& g, float dt_ms, float mv) {
+    if ((pos.w <= 0.0f) || !((vel.w >= g.cat_lo) && (vel.w <= g.cat_hi)))
+        return;
+    f3 acceleration = mk3(0.0f, 0.0f, 0.0f);
+    const uint32_t types = g.types;
+    int i = 0;
+#ifndef ILM_GRAVITY_EXACT
+    // Four attractors at a time while none of the four is of the physical type (the one with the IEEE division): their records come
+    // in together, every decision is a select on a uniform mask, so the four dependent chains (subtract, dot, rsq, rcp, ...) sit in
+    // one basic block and the scheduler interleaves them.  The same operations per attractor, the terms added in index order: the
+    // same bits as the loop below.  (A wave alone on its SIMD spent 1.24 us of its 3.4 in the transforms, one attractor after the
+    // other behind a scalar load each -- and that latency is what the head and the tail of every launch consist of.)
+    for (; i + 4 <= g.count && ((((types >> (2 * i)) | (types >> (2 * i + 1))) & 0x55u) == 0x55u); i += 4) {
+        f3 term[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const LeanAttractor A = g.a[i + k];
+            const bool squared = ((types >> (2 * (i + k))) & 2u) != 0u;
+            term[k] = gravity_term(mk3(A.x, A.y, A.z) - xyz(pos), squared ? 2u : 1u, A.radius, A.strength, dt_ms);
+        }
+        acceleration = (((acceleration + term[0]) + term[1]) + term[2]) + term[3];
+    }
+#endif
+    for (; i < g.count; i++) {
+        const LeanAttractor A = g.a[i];
+        acceleration = acceleration + gravity_term(mk3(A.x, A.y, A.z) - xyz(pos), (types >> (2 * i)) & 3u, A.radius, A.strength, dt_ms);
+    }
+    gravity_finish(vel, acceleration, g.max_accel, mv);
+}
+
+typedef const LeanStep __attribute__((address_space(4))) CLeanStep;
+static_assert(sizeof(LeanStep) >= 0xc84 && sizeof(LeanStep) <= 0xcc0, "touch_kernarg_lines_lean reads one dword of each 64-byte line of LeanStep");
+
+// Slot (x, y) of a lean unit's lanes, and the unit's first slot, row and first column.  The unit lies in one row (chunk size a
+// multiple of 64).
+ILM_DEV void lean_unit_slot(const LeanStep& a, int seg, unsigned lane, int& first, int& row, int& x0, float& fx, float& fy) {
+    first = seg * 64;
+    row = first >> a.cs_shift;
+    x0 = first - (row << a.cs_shift);
+    fx = (float)(x0 + (int)lane); fy = (float)row;
+}
+
+// ---- store elision (internal.hpp, kElideDerived) -------------------------------------------------------------------------------
+// A wave stores a plane only when it has to: writing the bits memory already holds changes nothing, and at cfg4's size every plane
+// access is HBM traffic.  When it stores, it stores all 64 lanes (an unchanged lane rewrites its own bits; a lane-masked store saves
+// no burst).
+ILM_DEV bool same_bits(float a, float b) { return __builtin_bit_cast(uint32_t, a) == __builtin_bit_cast(uint32_t, b); }
+// Only the STREAM variant elides.  The cache-resident one keeps every store: its planes live in the Infinity Cache from one step to the
+// next, its time follows the issue of its instructions rather than its bytes (see step_lean_kernel), and the compares would be added work.
+template <bool STREAM>
+ILM_DEV void st_plane_changed(const UnitPlanes& u, int c, unsigned lane4, float v, float loaded) {
+    if (!STREAM || __ballot(!same_bits(v, loaded)) != 0ull) st_plane<STREAM>(u, c, lane4, v);
+}
+// A curve of the update pass gives the same value for two inputs whose t (tForScaledBezier) is the same bits and no NaN: the rest of
+// evaluateBezier is a function of t and of the curve (part of the render key).  A constant curve reads no t at all.
+ILM_DEV bool same_curve_t(const IlmFloat4& rc, float v0, float v1, uint32_t code) {
+    if ((code & 3u) == 0u) return true;
+    const float t1 = t_for_coded_bezier(rc, v1, code);
+    return same_bits(t_for_coded_bezier(rc, v0, code), t1) && (t1 == t1);
+}
+// The render planes of a render-current chunk (every chunk of the launch; api.hip, System::render_gen) hold what render_data gives for the
+// state this wave loaded.  Per lane, a component keeps its bits when
+//   - the slot is dead before and after the step: all eight components are 0 and stay 0; or, for a slot alive before and after,
+//   - its inputs have the same bits (rd.z: the velocity; rd.w: the category, no NaN), or
+//   - a value that decides it is the same bits for the loaded and the new state and no NaN: renderColor by the two colour curves' t, with
+//     the attributes not spawned over and colour curves that cannot give a NaN factor (kElideColor, host-checked); rd.x by the size
+//     curves' t, rd.x itself no NaN; rd.y, when getVelocityRotation() == 0, by itself (recomputed for the loaded state, no NaN).
+// Anything else -- liveness changed, rotation from velocity, a NaN -- stores.  A plane is stored when any lane of the wave needs it;
+// the attributes are loaded only by a wave that stores renderColor.  (No life ramp here: build_lean_step.)
+template <bool SPAWN, bool STREAM>
+ILM_DEV void store_changed_render_planes(const LeanStep& a, const UnitPlanes& up, unsigned lane4, float fx, float fy, const SlotIn& cur,
+                                         float4 pos, float4 vel, float4 attr, bool spawned) {
+    const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    const IlmUpdateParams& p = a.update;
+    const uint32_t codes = a.bezier_codes;
+    const bool live0 = !(cur.life <= 0.0f), live1 = !(pos.w <= 0.0f);
+    const bool dead = !live0 && !live1, both = live0 && live1;
+    float4 rc, rd;
+    render_data(fx, fy, pos, vel, zero, a.sys, p, codes, a.update_bits, nullptr, 0, 0, rc, rd);     // (rc: not used)
+    // the speed the velocity curves read, for the loaded state, only where a velocity curve is not constant
+    float speed0 = 0.0f, speed1 = 0.0f;
+    if ((codes & 0x03000300u) != 0u) {
+        speed0 = fmaxf(len3_fast(mk3(cur.vx, cur.vy, cur.vz)), 0.0001f);
+        speed1 = fmaxf(len3_fast(xyz(vel)), 0.0001f);
+    }
+    const bool same_v = same_bits(cur.vx, vel.x) && same_bits(cur.vy, vel.y) && same_bits(cur.vz, vel.z);
+    const bool rc_same = dead || (both && !spawned && ((a.elide & kElideColor) != 0u) && same_curve_t(p.ColorFromLife.RangeAndCount, cur.life, pos.w, codes & 0xFFu) &&
+                                  same_curve_t(p.ColorFromVelocity.RangeAndCount, speed0, speed1, (codes >> 8) & 0xFFu));
+    const bool rdx_same = dead || (both && same_curve_t(p.SizeFromLife.RangeAndCount, cur.life, pos.w, (codes >> 16) & 0xFFu) &&
+                                   same_curve_t(p.SizeFromVelocity.RangeAndCount, speed0, speed1, codes >> 24) && (rd.x == rd.x));
+    bool rdy_same = dead;
+    if (a.update_bits & 2u) {
+        const float y0 = render_rotation(rotation_unscaled(cur.vx, cur.vy), cur.life, render_index(fx, fy), a.sys, p);
+        rdy_same = rdy_same || (both && same_bits(y0, rd.y) && (rd.y == rd.y));
+    }
+    const bool rdz_same = dead || (both && same_v);
+    const bool rdw_same = dead || (both && same_bits(cur.ct, vel.w) && (vel.w == vel.w));
+    if (__ballot(!rc_same) != 0ull) {
+        const float4 stored = load_attributes<STREAM>(up, lane4);
+        if (!SPAWN || !spawned) attr = stored;
+        float4 rd_unused;
+        render_data(fx, fy, pos, vel, attr, a.sys, p, codes, a.update_bits, nullptr, 0, 0, rc, rd_unused);
+        store_render_color<STREAM>(up, lane4, rc);
+    }
+    if (__ballot(!rdx_same) != 0ull) st_plane<STREAM>(up, 16, lane4, rd.x);
+    if (__ballot(!rdy_same) != 0ull) st_plane<STREAM>(up, 17, lane4, rd.y);
+    if (__ballot(!rdz_same) != 0ull) st_plane<STREAM>(up, 18, lane4, rd.z);
+    if (__ballot(!rdw_same) != 0ull) st_plane<STREAM>(up, 19, lane4, rd.w);
+}
+
+// The curve classes of the streaming lean step (launch_lean_step selects, ilm_debug_last_step_kernel reports): compile-time
+// instantiations of step_lean_block (step_lean_kernel<..> / step_lean_clamp_kernel).  kCurvesClamp: every
+// curve of the update pass is constant or has the clamp range and no shaping (bezier_codes & ~kClampCodes == 0), the velocity rotation
+// is zero and there is no life ramp (update_bits == 2), the launch elides (kElideDerived) and has no spawner (the spawning kernel's
+// registers are the spawn path's: a class of it would gain little).  The instantiation holds no fmodf, sinf or atan2f code; which curves
+// are constant stays a scalar test.
+constexpr int kCurvesGeneral = 0, kCurvesClamp = 1;
+constexpr uint32_t kClampCodes = 0x13131313u;      // per curve: the count class (bits 0-1) and the sign of the inverse divisor (bit 4)
+
+// One curve's part in the elision proof and in the value: t for the loaded and the new state, formed once.
+struct CurveT { float t1; bool same; };
+ILM_DEV CurveT clamp_curve_t(const IlmFloat4& rc, float v0, float v1, uint32_t code) {
+    CurveT c = { 0.0f, true };      // a constant curve reads no t
+    if ((code & 3u) != 0u) {
+        c.t1 = t_for_clamp_bezier(rc, v1, code);
+        c.same = same_bits(t_for_clamp_bezier(rc, v0, code), c.t1) && (c.t1 == c.t1);
+    }
+    return c;
+}
+// store_changed_render_planes for kCurvesClamp: the same stores of the same bits (the rules above, render_data's operations on the same
+// operands), with each t and the new state's speed formed once and shared by the proof and the value, and the dead lanes selected at
+// the end instead of branched around.  (No spawner: the attributes are the stored ones.)
+ILM_DEV void store_changed_render_planes_clamp(const LeanStep& a, const UnitPlanes& up, unsigned lane4, float fx, float fy, const SlotIn& cur,
+                                               float4 pos, float4 vel) {
+    const IlmUpdateParams& p = a.update;
+    const uint32_t codes = a.bezier_codes & kClampCodes;
+    const uint32_t c_cl = codes & 0xFFu, c_cv = (codes >> 8) & 0xFFu, c_sl = (codes >> 16) & 0xFFu, c_sv = codes >> 24;
+    const bool live0 = !(cur.life <= 0.0f), live1 = !(pos.w <= 0.0f);
+    const bool dead = !live0 && !live1, both = live0 && live1;
+    const float index = render_index(fx, fy);
+    const float speed1 = fmaxf(len3_fast(xyz(vel)), 0.0001f);
+    float speed0 = 0.0f;
+    if ((codes & 0x03000300u) != 0u)        // the loaded state's speed, only where a velocity curve is not constant
+        speed0 = fmaxf(len3_fast(mk3(cur.vx, cur.vy, cur.vz)), 0.0001f);
+    const CurveT cl = clamp_curve_t(p.ColorFromLife.RangeAndCount, cur.life, pos.w, c_cl);
+    const CurveT cv = clamp_curve_t(p.ColorFromVelocity.RangeAndCount, speed0, speed1, c_cv);
+    const CurveT sl = clamp_curve_t(p.SizeFromLife.RangeAndCount, cur.life, pos.w, c_sl);
+    const CurveT sv = clamp_curve_t(p.SizeFromVelocity.RangeAndCount, speed0, speed1, c_sv);
+    const float size_l = ((c_sl & 3u) == 0u) ? p.SizeFromLife.ABCD.x : bezier1_at(p.SizeFromLife, sl.t1, c_sl & 3u);
+    const float size_v = ((c_sv & 3u) == 0u) ? p.SizeFromVelocity.ABCD.x : bezier1_at(p.SizeFromVelocity, sv.t1, c_sv & 3u);
+    float4 rd;
+    rd.x = live1 ? size_l * size_v : 0.0f;
+    rd.y = live1 ? render_rotation(rotation_unscaled(vel.x, vel.y), pos.w, index, a.sys, p) : 0.0f;
+    rd.z = live1 ? speed1 : 0.0f;
+    rd.w = live1 ? vel.w : 0.0f;
+    const float y0 = render_rotation(rotation_unscaled(cur.vx, cur.vy), cur.life, index, a.sys, p);
+    const bool same_v = same_bits(cur.vx, vel.x) && same_bits(cur.vy, vel.y) && same_bits(cur.vz, vel.z);
+    const bool rc_same = dead || (both && ((a.elide & kElideColor) != 0u) && cl.same && cv.same);
+    const bool rdx_same = dead || (both && sl.same && sv.same && (rd.x == rd.x));
+    const bool rdy_same = dead || (both && same_bits(y0, rd.y) && (rd.y == rd.y));
+    const bool rdz_same = dead || (both && same_v);
+    const bool rdw_same = dead || (both && same_bits(cur.ct, vel.w) && (vel.w == vel.w));
+    if (__ballot(!rc_same) != 0ull) {
+        const float4 attr = load_attributes<true>(up, lane4);
+        const float4 color_l = ((c_cl & 3u) == 0u) ? ld4(p.ColorFromLife.A) : bezier4_at(p.ColorFromLife, cl.t1, c_cl & 3u);
+        const float4 color_v = ((c_cv & 3u) == 0u) ? ld4(p.ColorFromVelocity.A) : bezier4_at(p.ColorFromVelocity, cv.t1, c_cv & 3u);
+        float4 rc = mul4(attr, mul4(color_l, color_v));
+        rc.w = sat(rc.w);
+        rc.x *= rc.w; rc.y *= rc.w; rc.z *= rc.w;
+        st_plane<true>(up, 12, lane4, live1 ? rc.x : 0.0f); st_plane<true>(up, 13, lane4, live1 ? rc.y : 0.0f);
+        st_plane<true>(up, 14, lane4, live1 ? rc.z : 0.0f); st_plane<true>(up, 15, lane4, live1 ? rc.w : 0.0f);
+    }
+    if (__ballot(!rdx_same) != 0ull) st_plane<true>(up, 16, lane4, rd.x);
+    if (__ballot(!rdy_same) != 0ull) st_plane<true>(up, 17, lane4, rd.y);
+    if (__ballot(!rdz_same) != 0ull) st_plane<true>(up, 18, lane4, rd.z);
+    if (__ballot(!rdw_same) != 0ull) st_plane<true>(up, 19, lane4, rd.w);
+}
+
+
+// One block of the lean step, for one curve class (the kernels below).
+template <bool SPAWN, bool STREAM, int CURVES>
+ILM_DEV void step_lean_block() {
+    static_assert(CURVES == kCurvesGeneral || (STREAM && !SPAWN), "the curve classes are instantiations of the streaming variant without spawners");
+    __shared__ uint32_t wave_live[kStepThreads / 64];
+    const LeanStep& a = *(const LeanStep*)(CLeanStep*)__builtin_amdgcn_kernarg_segment_ptr();
+    // (only the launch's first generation of blocks can be the first to read a line; for the others the loads would just load the
+    // scalar cache: one lookup per line per wave)
+    if (blockIdx.x < kTouchBlocks) touch_kernarg_lines_lean();
+    const unsigned lane = threadIdx.x & 63u;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    int v = (int)blockIdx.x * (kStepThreads / 64) + a.unit_rotate;      // first unit of the block (rotation: see step_kernel)
+    if (v >= a.total_padded) v -= a.total_padded;
+    const int u = v + wave;
+    uint32_t n_live = 0;
+    if (u < a.total_units) {
+        const int chunk_rel = u >> a.upc_shift;
+        const int seg = u - (chunk_rel << a.upc_shift);
+        const int chunk = a.first_chunk + chunk_rel;
+        bool untouched = false;
+        if (a.partial_count != 0) {
+#pragma unroll
+            for (int k = 0; k < kMaxPartialChunks; k++)
+                untouched = untouched || ((a.partial_chunk[k] == chunk) && (seg >= a.partial_units[k]));
+        }
+        if (!untouched) {
+            const unsigned lane4 = lane * 4u;
+            // the chunk table through the constant address space: a scalar load whatever the optimiser thinks may alias (behind the
+            // volatile asm of touch_kernarg_lines it would otherwise fetch the base with a VECTOR load and wrap every plane access in
+            // a waterfall loop over a "divergent" buffer resource: +160 vector instructions per wave); the table is written by a copy
+            // that precedes the launch on its stream and never during one
+            const UnitPlanes up = unit_planes(((CBase*)a.chunk_bases)[chunk], a.stride, seg * 64);
+            // a render-current chunk needs its attributes only where renderColor is recomputed: loaded below, by the waves that do
+            const bool elide = STREAM && ((CURVES == kCurvesClamp) || (a.elide & kElideDerived) != 0u);
+            SlotIn cur = load_slot<false, STREAM>(up, lane4);
+            if (!elide) {
+                const float4 stored = load_attributes<STREAM>(up, lane4);
+                cur.ar = stored.x; cur.ag = stored.y; cur.ab = stored.z; cur.aa = stored.w;
+            }
+            int first, row, x0; float fx, fy;
+            lean_unit_slot(a, seg, lane, first, row, x0, fx, fy);
+            NoiseDeltas noise;
+            noise.valid = false;
+            if (a.noise_op >= 0)
+                noise = noise_prepare(a.noise, a.noise_big, x0, row);
+
+            float4 pos = mk4(cur.px, cur.py, cur.pz, cur.life);
+            float4 vel = mk4(cur.vx, cur.vy, cur.vz, cur.ct);
+            float4 attr = mk4(cur.ar, cur.ag, cur.ab, cur.aa);
+            bool spawn_here = false, spawned = false;
+            if constexpr (SPAWN) {
+                for (int s = 0; s < a.spawn_count; s++) {
+                    if (a.spawn_chunk[s] == chunk && seg >= a.spawn_unit_lo[s] && seg <= a.spawn_unit_hi[s]) {
+                        const IlmSpawnRecord& r = a.spawns[s];
+                        const float fi = (float)(first + (int)lane);
+                        if (fi >= r.Params.ChunkSizeAndIndices[1] && fi <= r.Params.ChunkSizeAndIndices[2]) {
+                            spawn_here = true;
+                            if (spawn_slot(pos, vel, attr, fx, fy, a.rnd, a.rw, a.rh, a.inv_rw, a.inv_rh, r.Params))
+                                spawned = true;
+                        }
+                    }
+                }
+            }
+            // `<= 0` as the shaders test it: a NaN life is not dead.  A dead slot nothing writes keeps the cleared target's zeros.
+            const bool process = !(cur.life <= 0.0f) || spawn_here;
+            const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+            float4 rc = zero, rd = zero;
+            if constexpr (CURVES == kCurvesClamp) {
+                if (__ballot(process) != 0ull) {
+                    // Every lane goes through the transforms and the update, and one select at the end keeps the live ones: a slot the
+                    // step does not process comes out as zeros whatever was computed for it.  The transforms are dispatched from
+                    // unrolled positions so that position and velocity stay in their registers from one to the next.
+#pragma unroll
+                    for (int o = 0; o < ILM_MAX_OPS; o++) {
+                        if (o < a.op_count) {
+                            const int type = a.op_type[o];
+                            if (type == ILM_OP_GRAVITY)
+                                apply_gravity_lean(pos, vel, a.op[o].gravity, a.sys.GlobalSettings.x, a.sys.GlobalSettings.z);
+                            else if (type == ILM_OP_NOISE)
+                                apply_noise(pos, vel, fx, fy, a.rnd, a.rw, a.rh, a.sys, a.op[o].noise, a.inv_rw, a.inv_rh, a.dop[o],
+                                            (o == a.noise_op) ? noise : NoiseDeltas{ false, zero, zero });
+                            else
+                                apply_fma(pos, vel, a.sys, a.op[o].fma, a.dop[o]);
+                        }
+                    }
+                    update_positions_select(pos, vel, a.sys, a.dt_s, process && !(pos.w <= 0.0f));
+                } else {
+                    pos = vel = zero;
+                }
+            } else if (__ballot(process) != 0ull) {
+                if (process) {
+                    for (int o = 0; o < a.op_count; o++) {
+                        const int type = a.op_type[o];
+                        if (type == ILM_OP_GRAVITY)
+                            apply_gravity_lean(pos, vel, a.op[o].gravity, a.sys.GlobalSettings.x, a.sys.GlobalSettings.z);
+                        else if (type == ILM_OP_NOISE)
+                            apply_noise(pos, vel, fx, fy, a.rnd, a.rw, a.rh, a.sys, a.op[o].noise, a.inv_rw, a.inv_rh, a.dop[o],
+                                        (o == a.noise_op) ? noise : NoiseDeltas{ false, zero, zero });
+                        else
+                            apply_fma(pos, vel, a.sys, a.op[o].fma, a.dop[o]);
+                    }
+                    if (pos.w <= 0.0f) {
+                        pos = vel = zero;  // readStateOrDiscard: discard => cleared target
+                    } else {
+                        update_positions(pos, vel, a.sys, a.dt_s);
+                        if (!elide)
+                            render_data(fx, fy, pos, vel, attr, a.sys, a.update, a.bezier_codes, a.update_bits, nullptr, 0, 0, rc, rd);
+                    }
+                } else {
+                    pos = vel = zero;
+                }
+            } else {
+                pos = vel = zero;
+            }
+            // STREAM: a plane is stored when some lane of the wave changed its bits (integer compares: NaN and -0.0 exactly), at full width
+            st_plane_changed<STREAM>(up, 0, lane4, pos.x, cur.px); st_plane_changed<STREAM>(up, 1, lane4, pos.y, cur.py);
+            st_plane_changed<STREAM>(up, 2, lane4, pos.z, cur.pz); st_plane_changed<STREAM>(up, 3, lane4, pos.w, cur.life);
+            st_plane_changed<STREAM>(up, 4, lane4, vel.x, cur.vx); st_plane_changed<STREAM>(up, 5, lane4, vel.y, cur.vy);
+            st_plane_changed<STREAM>(up, 6, lane4, vel.z, cur.vz); st_plane_changed<STREAM>(up, 7, lane4, vel.w, cur.ct);
+            if constexpr (SPAWN) {
+                if (spawned)
+                    store_attributes<STREAM>(up, lane4, attr);
+            }
+            if (!elide) {
+                store_render<STREAM>(up, lane4, rc, rd);
+            } else if constexpr (CURVES == kCurvesClamp) {
+                store_changed_render_planes_clamp(a, up, lane4, fx, fy, cur, pos, vel);
+            } else {
+                store_changed_render_planes<SPAWN, STREAM>(a, up, lane4, fx, fy, cur, pos, vel, attr, spawned);
+            }
+            n_live = (uint32_t)__popcll(__ballot(pos.w > 0.0f));
+        }
+    }
+    if (a.flags & ILM_STEP_COUNT_LIVE)
+        publish_block_count(wave_live, n_live, lane, wave, v < a.total_units, a.first_chunk + (v >> a.upc_shift),
+                            (v & ((1 << a.upc_shift) - 1)) / (kStepThreads / 64), (1 << a.upc_shift) / (kStepThreads / 64), a.count_buckets,
+                            a.live_counts, a.zero_counts, a.zero_n, a.host_counts, a.count_seq);
+}
+
+// The general instantiations keep the kernel names the profiles and bench.py's traffic figures are keyed by; the class is a kernel of
+// its own (a class selected inside step_lean_kernel<false, true> by a launch-uniform word took the kernel from 8 waves per SIMD to 7 and
+// the headline from 0.78 to 0.89 ms).
+template <bool SPAWN, bool STREAM>
+__global__ __launch_bounds__(kStepThreads) void step_lean_kernel(const LeanStep a_) { step_lean_block<SPAWN, STREAM, kCurvesGeneral>(); }
+__global__ __launch_bounds__(kStepThreads) void step_lean_clamp_kernel(const LeanStep a_) { step_lean_block<false, true, kCurvesClamp>(); }
+
+// ---------------------------------------------------------------------------------------------
+// the lean collision step (r06) -- UpdateParticleSystemWithDistanceField.fx:29-147 on the lean descriptor
+// ---------------------------------------------------------------------------------------------
+// The collision update is two things in one shader.  EVERY live particle samples the field where it is and where it is going (the
+// first iteration of the sweep): two dependent lookups, the same for all lanes.  A particle whose first sweep lookup lands inside an
+// obstacle (14 % of them on the demo's field) goes on: up to two more sweep lookups, estimateNormal4 (four more), the bounce / redirect
+// / escape arithmetic -- about as many vector instructions again as the whole rest of the step, run by a wave for its few such lanes
+// (the interpreter's step_kernel<.., DF>: 1 071 instructions per wave at 39.4 of 64 lanes, profiles/r06_collision_step.txt).
+// Here a wave walks K consecutive units in three phases.
+//   A  per unit: load, spawn, transforms, the common path at full width.  The lanes that collided are PARKED -- their state after the
+//      transforms and the two distances already sampled, eleven words, in a ring of 128 entries the wave owns in LDS (no barrier: the
+//      ring is private to the wave).  The unit's position and velocity stay in registers; nothing is stored yet.
+//   L  whenever 64 are parked, and once more after the last unit: the parked particles, one per lane, through the rest of the reference
+//      update (df_long, which the interpreter's update_with_distance_field runs too); the results go back into the same ring
+//      entries.
+//   B  per unit: the parked lanes take their results from the ring, then computeRenderData and all sixteen stores at FULL width.
+// So the long path runs at 64 lanes -- or, for the remainder, at whatever K units leave -- instead of at ~9 lanes once per unit, and
+// every plane of a unit is still written by ONE full-width store (a first form of this kernel stored the finished lanes at once and
+// the parked ones later, from the long pass: two partial writes per line, and cfg4's share took 507-597 us against the interpreter's
+// 394 -- masked and scattered 4-byte stores cost a read-modify-write each once the line has left the L2).
+// A ring that would overflow (more than 128 of a wave's K x 64 particles colliding) is not waited for: that unit's parked lanes take the
+// long path in place, as the interpreter does.
+struct LeanStepDf {
+    LeanStep base;
+    IlmDistanceFieldUniforms df;
+    SdfView sdf;
+};
+static_assert(sizeof(LeanStepDf) <= 4096, "LeanStepDf travels in the kernarg segment (4 KB)");
+static_assert(sizeof(LeanStepDf) > 0xd40 && sizeof(LeanStepDf) <= 0xe00, "touch_kernarg_lines_lean_df reads one dword of each 64-byte line of LeanStepDf");
+ILM_DEV void touch_kernarg_lines_lean_df() {       // LeanStepDf: 54 .. 56 lines
+    const auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    uint32_t sink;
+    asm volatile(ILM_T16(0x0) ILM_T16(0x400) ILM_T16(0x800) ILM_T4(0xc00) ILM_T1(0xd00) ILM_T1(0xd40) "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(sink) : "s"(kp));
+}
+typedef const LeanStepDf __attribute__((address_space(4))) CLeanStepDf;
+
+constexpr int kDfRing = 128;                     // parked particles per wave
+struct DfParked { float px[kDfRing], py[kDfRing], pz[kDfRing], life[kDfRing], vx[kDfRing], vy[kDfRing], vz[kDfRing], ct[kDfRing], d0[kDfRing], d1[kDfRing]; uint32_t slot[kDfRing]; };   // slot: bit 31 = d1 is the first iteration's lookup
+
+// The common path of PS_Update (distance field) for a live slot (life > 0 on entry): everything a particle needs that meets no obstacle.
+// The reference samples the field at the particle (initial_distance) and then at old + unit * travel with travel = max(0, min(
+// initial_distance, |velocity| dt)) -- two DEPENDENT lookups.  Away from obstacles travel IS |velocity| dt, known before any lookup: both
+// positions are sampled at once, and when min() did pick |velocity| dt (bit for bit) the second sample is the sweep's first
+// step_distance -- same position, same bits.  Returns 0 when the particle is finished (position and velocity final; zeros for one that
+// died); 1 when it must go on with the sweep's first iteration still to do (travel is not |velocity| dt: it sits at or inside an
+// obstacle); 2 when the first iteration is done and collided (step_distance valid).  For 1 and 2 position and velocity are left as they
+// came: the caller parks them for df_long.  Same operations in the same order as update_with_distance_field takes on these paths
+// (tests/test_step_kernels_gpu.py holds the kernels bit-equal, sample counts included).
+template <int FMT>
+ILM_DEV int df_common_path(float4& pos, float4& vel, const IlmParticleSystemUniforms& sys, float dts, const IlmDistanceFieldUniforms& df, const SdfView& sdf, int& samples,
+                           float& initial_distance, float& step_distance) {
+#pragma clang fp contract(off)
+    const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float new_life = pos.w - (sys.GlobalSettings.w * dts);
+    initial_distance = step_distance = 0.0f;
+    if (new_life <= 0.0f) {
+        pos = vel = zero;
+        return 0;
+    }
+    const float collision_distance = sys.CollisionSettings.z;
+    const f3 old_xyz = xyz(pos);
+    const f3 unit_vector = norm3(xyz(vel));
+    const f3 velocity = friction_and_maximum(xyz(vel), sys, dts);
+    const f3 scaled_velocity = velocity * dts;
+    const float reach = len3(scaled_velocity);
+    const f3 ahead = old_xyz + (unit_vector * reach);
+    initial_distance = sample_distance_field<(FMT & 1), true, (FMT & 2) != 0, (FMT & 4) != 0>(old_xyz, df, sdf);
+    step_distance = sample_distance_field<(FMT & 1), true, (FMT & 2) != 0, (FMT & 4) != 0>(ahead, df, sdf);        // (independent of the first: both in flight together)
+    samples++;
+    const bool was_colliding = initial_distance < collision_distance;
+    const float travel_distance = fmaxf(0.0f, fminf(initial_distance, reach));
+    if (__builtin_bit_cast(uint32_t, travel_distance) != __builtin_bit_cast(uint32_t, reach))
+        return 1;                                                 // the sweep starts somewhere else than `ahead`
+    if (was_colliding || !(travel_distance <= 0.001f)) {          // step_count 1 or MAX_STEP_COUNT: the sweep's first iteration runs, at `ahead`
+        samples++;
+        if (step_distance < collision_distance)
+            return 2;
+    }
+    pos = mk4(ahead.x, ahead.y, ahead.z, new_life);
+    vel = mk4(velocity.x, velocity.y, velocity.z, fmaxf(vel.w - 1.0f, 0.0f));
+    return 0;
+}
+
 template <int FMT, bool SPAWN, bool STREAM, int K>
 __global__ __launch_bounds__(kStepThreads) void step_lean_df_kernel(const LeanStepDf a_) {
     static_assert(K == 1 || K == 2 || K == 4, "units per wave");
@@ -1866,14 +1728,12 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_df_kernel(const LeanSt
             const int seg = seg0 + j;
             const UnitPlanes up = unit_planes(chunk_base, a.stride, seg * 64);
             const SlotIn cur = load_slot<true, STREAM>(up, lane4);
-            const int first = seg * 64;
-            const int row = first >> a.cs_shift;
-            const int x0 = first - (row << a.cs_shift);
-            const float fx = (float)(x0 + (int)lane), fy = (float)row;
+            int first, row, x0; float fx, fy;
+            lean_unit_slot(a, seg, lane, first, row, x0, fx, fy);
             NoiseDeltas noise;
             noise.valid = false;
             if (a.noise_op >= 0)
-                noise = noise_prepare_lean(a, x0, row);
+                noise = noise_prepare(a.noise, a.noise_big, x0, row);
             float4 pos = mk4(cur.px, cur.py, cur.pz, cur.life);
             float4 vel = mk4(cur.vx, cur.vy, cur.vz, cur.ct);
             float4 attr = mk4(cur.ar, cur.ag, cur.ab, cur.aa);
@@ -1955,6 +1815,8 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_df_kernel(const LeanSt
         for (int j = 0; j < units; j++) {
             const int seg = seg0 + j;
             const UnitPlanes up = unit_planes(chunk_base, a.stride, seg * 64);
+            // (the plane accesses of this kernel stay written out: through the plane-group helpers the spawning cache-resident instantiations
+            // come out with other scalar registers and another order of their mask operations)
             const float4 attr = mk4(ld_plane<STREAM>(up, 8, lane4), ld_plane<STREAM>(up, 9, lane4), ld_plane<STREAM>(up, 10, lane4), ld_plane<STREAM>(up, 11, lane4));
             float4 pos, vel; unsigned long long pm; uint32_t pb;
             if (K == 1 || j == 0) { pos = hp0; vel = hv0; pm = pm0; pb = pb0; }
@@ -1990,7 +1852,6 @@ __global__ __launch_bounds__(kStepThreads) void step_lean_df_kernel(const LeanSt
 // LeanStep from a StepLaunch whose launch_step fields are filled; false when the step is not of the lean shape
 static bool build_lean_step(const StepLaunch& a, LeanStep& f) {
     const IlmStepDesc& d = a.desc;
-    if (kUnitsPerWave != 1) return false;
     if (d.UpdateMode != ILM_UPDATE_POSITIONS && d.UpdateMode != ILM_UPDATE_WITH_DISTANCE_FIELD) return false;   // (the collision update: launch_lean_df_step adds the field)
     // power-of-two chunk size >= 64: no stride padding, a unit lies in one row, and units_per_chunk is a power of two >= 64, so every
     // block size of the lean kernels (kStepThreads / 64 x K units, K <= 4) divides it
@@ -2116,6 +1977,33 @@ static bool field_is_slice0(const IlmDistanceFieldUniforms& df, int format) {
     return (format == ILM_SDF_UNORM16) && (df.Packed1.y == 0.0f) && std::isfinite(df.Packed1.x) && std::isfinite(df.Packed1.z) &&
            std::isfinite(df.TextureSliceAndTexelSize.x) && std::isfinite(df.TextureSliceAndTexelSize.y);
 }
+// A launch's field as the collision kernels' first template argument: launch(std::integral_constant<int, FMT>()).  CELLS: the caller
+// has kernels for kFieldCells0 (the lean collision kernel; the interpreter has none, and none is instantiated for it).
+template <bool CELLS, class Launch>
+static hipError_t with_field_format(const StepLaunch& a, Launch launch) {
+    int fmt = (int)a.sdf.format | (field_is_slice0(a.desc.DistanceField, (int)a.sdf.format) ? kFieldSlice0 : 0);
+    if (CELLS && fmt == (ILM_SDF_UNORM16 | kFieldSlice0) && a.sdf.cells0 != nullptr) fmt |= kFieldCells0;
+    switch (fmt) {
+        case ILM_SDF_UNORM16: return launch(std::integral_constant<int, ILM_SDF_UNORM16>());
+        case ILM_SDF_FP16: return launch(std::integral_constant<int, ILM_SDF_FP16>());
+        case ILM_SDF_UNORM16 | kFieldSlice0: return launch(std::integral_constant<int, ILM_SDF_UNORM16 | kFieldSlice0>());
+        case ILM_SDF_FP16 | kFieldSlice0: return launch(std::integral_constant<int, ILM_SDF_FP16 | kFieldSlice0>());
+        case ILM_SDF_UNORM16 | kFieldSlice0 | kFieldCells0:
+            if constexpr (CELLS) return launch(std::integral_constant<int, ILM_SDF_UNORM16 | kFieldSlice0 | kFieldCells0>());
+    }
+    return hipErrorInvalidValue;      // (no field is created with another format)
+}
+// The block lay-out of a launch whose blocks hold `upb` units (upb divides units_per_chunk): the padded unit count the rotation wraps
+// at, the rotation rounded down to a block, the live-count buckets of a chunk (publish_block_count)
+struct BlockLayout { int total_padded, unit_rotate, count_buckets; };
+static BlockLayout block_layout(int total_units, int unit_rotate, int units_per_chunk, int upb) {
+    BlockLayout l;
+    l.total_padded = (total_units + upb - 1) / upb * upb;
+    l.unit_rotate = unit_rotate / upb * upb;
+    l.count_buckets = 1;
+    while (l.count_buckets * 2 <= kCountLines - 1 && (units_per_chunk / upb) % (l.count_buckets * 2) == 0) l.count_buckets *= 2;
+    return l;
+}
 // SdfView::cells0 from the atlas: cell (x0, yr) = channel r of the taps (x0, y0), (x1, y0), (x0, y1), (x1, y1) of a bilinear fetch whose
 // upper-left tap is column x0 (already wrapped) of row yi = yr - 1 -- x1 = x0 + 1 with U WRAP, y0 = clamp(yi), y1 = the next row exactly
 // when 0 <= yi < height - 1: the integer bookkeeping of sample_distance_field, done once per texel instead of once per lookup.
@@ -2169,25 +2057,12 @@ static hipError_t launch_lean_df_step(LeanStepDf& f, const StepLaunch& a, bool s
     if (streaming) k = 4;
     const int upb = (kStepThreads / 64) * k;                            // units per block: divides units_per_chunk (build_lean_step)
     // the grid's bookkeeping for blocks of upb units (launch_step laid it out for blocks of kStepThreads / 64)
-    f.base.total_padded = (f.base.total_units + upb - 1) / upb * upb;
-    f.base.unit_rotate = f.base.unit_rotate / upb * upb;
-    int buckets = 1;
-    while (buckets * 2 <= kCountLines - 1 && (a.units_per_chunk / upb) % (buckets * 2) == 0) buckets *= 2;
-    f.base.count_buckets = buckets;
-    const dim3 grid((unsigned)(f.base.total_padded / upb), 1, 1);
-    int fmt = (int)a.sdf.format | (field_is_slice0(a.desc.DistanceField, (int)a.sdf.format) ? kFieldSlice0 : 0);
-    if (fmt == (ILM_SDF_UNORM16 | kFieldSlice0) && a.sdf.cells0 != nullptr) fmt |= kFieldCells0;
-    switch (fmt) {
-        case ILM_SDF_UNORM16 | kFieldSlice0 | kFieldCells0:
-            return spawning ? launch_lean_df_variant<ILM_SDF_UNORM16 | kFieldSlice0 | kFieldCells0, true>(f, k, streaming, grid, stream)
-                            : launch_lean_df_variant<ILM_SDF_UNORM16 | kFieldSlice0 | kFieldCells0, false>(f, k, streaming, grid, stream);
-        case ILM_SDF_FP16: return spawning ? launch_lean_df_variant<ILM_SDF_FP16, true>(f, k, streaming, grid, stream) : launch_lean_df_variant<ILM_SDF_FP16, false>(f, k, streaming, grid, stream);
-        case ILM_SDF_UNORM16: return spawning ? launch_lean_df_variant<ILM_SDF_UNORM16, true>(f, k, streaming, grid, stream) : launch_lean_df_variant<ILM_SDF_UNORM16, false>(f, k, streaming, grid, stream);
-        case ILM_SDF_FP16 | kFieldSlice0: return spawning ? launch_lean_df_variant<ILM_SDF_FP16 | kFieldSlice0, true>(f, k, streaming, grid, stream)
-                                                          : launch_lean_df_variant<ILM_SDF_FP16 | kFieldSlice0, false>(f, k, streaming, grid, stream);
-        default: return spawning ? launch_lean_df_variant<ILM_SDF_UNORM16 | kFieldSlice0, true>(f, k, streaming, grid, stream)
-                                 : launch_lean_df_variant<ILM_SDF_UNORM16 | kFieldSlice0, false>(f, k, streaming, grid, stream);
-    }
+    const BlockLayout l = block_layout(f.base.total_units, f.base.unit_rotate, a.units_per_chunk, upb);
+    f.base.total_padded = l.total_padded; f.base.unit_rotate = l.unit_rotate; f.base.count_buckets = l.count_buckets;
+    const dim3 grid((unsigned)(l.total_padded / upb), 1, 1);
+    return with_field_format<true>(a, [&](auto fmt) {
+        return spawning ? launch_lean_df_variant<decltype(fmt)::value, true>(f, k, streaming, grid, stream) : launch_lean_df_variant<decltype(fmt)::value, false>(f, k, streaming, grid, stream);
+    });
 }
 
 // The extended variant carries the rarely used techniques (MatrixMultiply, SpatialNoise, the position-buffer and feedback spawners) so
@@ -2206,31 +2081,22 @@ template <bool SPAWN>
 static hipError_t launch_step_variant(const StepLaunch& a, hipStream_t stream) {
     const int units = a.unit_end - a.unit_begin;
     if (units <= 0) return hipSuccess;
-    if (needs_extended_variant(a)) {
-        const int upb = (kStepThreads / 64) * kUnitsPerWave;
-        const dim3 g((unsigned)((units + upb - 1) / upb), 1, 1), b(kStepThreads, 1, 1);
-        if (a.desc.UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD) {
-            switch ((int)a.sdf.format | (field_is_slice0(a.desc.DistanceField, (int)a.sdf.format) ? kFieldSlice0 : 0)) {
-                case ILM_SDF_FP16: hipLaunchKernelGGL((step_kernel<ILM_SDF_FP16, true, true, 1, true>), g, b, 0, stream, a); break;
-                case ILM_SDF_UNORM16: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, true, true, 1, true>), g, b, 0, stream, a); break;
-                case ILM_SDF_FP16 | kFieldSlice0: hipLaunchKernelGGL((step_kernel<ILM_SDF_FP16 | kFieldSlice0, true, true, 1, true>), g, b, 0, stream, a); break;
-                default: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16 | kFieldSlice0, true, true, 1, true>), g, b, 0, stream, a); break;
-            }
-        } else {
-            hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, false, true, 1, true>), g, b, 0, stream, a);
-        }
-        return hipGetLastError();
-    }
-    const int units_per_block = (kStepThreads / 64) * kUnitsPerWave;
+    const int units_per_block = kStepThreads / 64;
     const dim3 grid((unsigned)((units + units_per_block - 1) / units_per_block), 1, 1), block(kStepThreads, 1, 1);
-    if (a.desc.UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD) {
+    const bool df = a.desc.UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD;
+    if (needs_extended_variant(a)) {
+        if (df)
+            return with_field_format<false>(a, [&](auto fmt) {
+                hipLaunchKernelGGL((step_kernel<decltype(fmt)::value, true, true, 1, true>), grid, block, 0, stream, a);
+                return hipGetLastError();
+            });
+        hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, false, true, 1, true>), grid, block, 0, stream, a);
+    } else if (df) {
         // waves per SIMD requested for the collision variants (kDfMinWaves; measured in docs/experiments.md 3.1)
-        switch ((int)a.sdf.format | (field_is_slice0(a.desc.DistanceField, (int)a.sdf.format) ? kFieldSlice0 : 0)) {
-            case ILM_SDF_FP16: hipLaunchKernelGGL((step_kernel<ILM_SDF_FP16, true, SPAWN, kDfMinWaves>), grid, block, 0, stream, a); break;
-            case ILM_SDF_UNORM16: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, true, SPAWN, kDfMinWaves>), grid, block, 0, stream, a); break;
-            case ILM_SDF_FP16 | kFieldSlice0: hipLaunchKernelGGL((step_kernel<ILM_SDF_FP16 | kFieldSlice0, true, SPAWN, kDfMinWaves>), grid, block, 0, stream, a); break;
-            default: hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16 | kFieldSlice0, true, SPAWN, kDfMinWaves>), grid, block, 0, stream, a); break;
-        }
+        return with_field_format<false>(a, [&](auto fmt) {
+            hipLaunchKernelGGL((step_kernel<decltype(fmt)::value, true, SPAWN, kDfMinWaves>), grid, block, 0, stream, a);
+            return hipGetLastError();
+        });
     } else if (a.streaming) {
         hipLaunchKernelGGL((step_kernel<ILM_SDF_UNORM16, false, SPAWN, 1, false, true>), grid, block, 0, stream, a);
     } else {
@@ -2265,11 +2131,7 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide,
         if ((1 << b) == a.units_per_chunk) a.upc_shift = b;
     a.unit_begin = 0;
     a.unit_end = a.chunk_count * a.units_per_chunk;
-    const int waves_per_block = (kStepThreads / 64) * kUnitsPerWave;   // units per block
-    a.total_padded = (a.unit_end + waves_per_block - 1) / waves_per_block * waves_per_block;
-    a.unit_rotate = 0;
-    a.count_buckets = 1;
-    while (a.count_buckets * 2 <= kCountLines - 1 && (a.units_per_chunk / waves_per_block) % (a.count_buckets * 2) == 0) a.count_buckets *= 2;
+    int first_spawn_unit = 0;
     bool spawning = false;
     for (int s = 0; s < a.desc.SpawnCount; s++) {
         const IlmSpawnRecord& r = a.desc.Spawns[s];
@@ -2277,12 +2139,12 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide,
             continue;
         if (r.Params.ChunkSizeAndIndices[2] < r.Params.ChunkSizeAndIndices[1])
             continue;
-        if (!spawning) {
-            const int unit = (r.ChunkIndex - a.first_chunk) * a.units_per_chunk + (int)r.Params.ChunkSizeAndIndices[1] / 64;
-            a.unit_rotate = unit / waves_per_block * waves_per_block;
-        }
+        if (!spawning)
+            first_spawn_unit = (r.ChunkIndex - a.first_chunk) * a.units_per_chunk + (int)r.Params.ChunkSizeAndIndices[1] / 64;
         spawning = true;
     }
+    const BlockLayout l = block_layout(a.unit_end, first_spawn_unit, a.units_per_chunk, kStepThreads / 64);
+    a.total_padded = l.total_padded; a.unit_rotate = l.unit_rotate; a.count_buckets = l.count_buckets;
     if (!step_interpreter_forced() && a.unit_end > a.unit_begin) {
         if (a.desc.UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD) {
             const char* lean_env = getenv("ILM_DF_LEAN");                 // A/B switch, read per launch: 0 = the interpreter
