@@ -7,7 +7,7 @@ offsets against the C header by compiling a probe.
 """
 import ctypes as C
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 OK = 0
 ERR_INVALID_ARGUMENT = -1
@@ -312,6 +312,21 @@ class RenderStats(C.Structure):
     _fields_ = [("SdfSamples", C.c_uint64), ("PixelLightPairs", C.c_uint64), ("TracedPairs", C.c_uint64)]
 
 
+class HistogramBucket(C.Structure):
+    """BucketState, Illuminant/Histogram.cs:32-35"""
+    _fields_ = [("Count", i32), ("Min", f32), ("Max", f32), ("Sum", f32)]
+
+
+class HistogramParams(C.Structure):
+    _fields_ = [("RenderWidth", i32), ("RenderHeight", i32), ("AccuracyFactor", i32), ("BucketCount", i32), ("IgnoreZeroes", i32),
+                ("ScaleFactor", f32)]
+
+
+class HistogramResult(C.Structure):
+    _fields_ = [("SampleCount", i32), ("LevelIndex", i32), ("Width", i32), ("Height", i32),
+                ("Min", f32), ("Max", f32), ("Mean", f32), ("Median", f32), ("Sum", f32)]
+
+
 # expected sizes (bytes) -- checked against the C header in tests
 EXPECTED_SIZES = {
     "IlmFloat4": (Float4, 16), "IlmMatrix": (Matrix, 64),
@@ -333,4 +348,5 @@ EXPECTED_SIZES = {
     "IlmDistanceFieldRenderDesc": (DistanceFieldRenderDesc, 64),
     "IlmHeightVolumeVertex": (HeightVolumeVertex, 36), "IlmBillboardVertex": (BillboardVertex, 48),
     "IlmBillboardRun": (BillboardRun, 24), "IlmGBufferMeshDesc": (GBufferMeshDesc, 64),
+    "IlmHistogramBucket": (HistogramBucket, 16), "IlmHistogramParams": (HistogramParams, 24), "IlmHistogramResult": (HistogramResult, 36),
 }

@@ -113,6 +113,7 @@ struct Ctx {
     IlmReadbackDrawCall* h_rb = nullptr; size_t h_rb_cap = 0;    // pinned host buffer the read-back records land in
     // light probes
     float4* d_probe_pairs = nullptr; size_t probe_pairs_cap = 0;   // one contribution per (light, probe)
+    BrightnessScratch brightness;                                  // brightness estimation: the luminance level and the statistics' scratch (brightness.hip)
     // parameter block of the distance-field generation pass (slice list, obstruction records, volumes, polygon vertices)
     void* d_field_params = nullptr; size_t field_params_bytes = 0;
 };
@@ -1447,6 +1448,10 @@ int32_t ilm_ctx_destroy(IlmHandle h) {
     if (c->d_light_ramp) (void)hipFree(c->d_light_ramp);
     if (c->d_raster_quads) (void)hipFree(c->d_raster_quads);
     if (c->d_probe_pairs) (void)hipFree(c->d_probe_pairs);
+    if (c->brightness.level) (void)hipFree(c->brightness.level);
+    if (c->brightness.mip) (void)hipFree(c->brightness.mip);
+    if (c->brightness.work) (void)hipFree(c->brightness.work);
+    if (c->brightness.partials) (void)hipFree(c->brightness.partials);
     if (c->d_rb) (void)hipFree(c->d_rb);
     if (c->d_rb_count) (void)hipFree(c->d_rb_count);
     if (c->d_rb_blocks) (void)hipFree(c->d_rb_blocks);
@@ -3378,6 +3383,143 @@ int32_t ilm_resolve_lighting_with_albedo(IlmHandle hsrc, IlmHandle halbedo, IlmH
     const float maximum_luminance = clamp(hdr->MaximumLuminance, min_v, max_v);
     a.inv_maximum_luminance_squared = 1.0f / (maximum_luminance * maximum_luminance);
     HIP_TRY(launch_resolve(a, c->main()));
+    return ILM_OK;
+}
+
+namespace {
+// Which level brightness estimation reads and its size: L = min(accuracyFactor, LevelCount - 1), LevelCount of the half-size luminance
+// target made for the lightmap's own size (LightingRenderer.HDR.cs:164-167,176-177; LightingRenderer.cs:527-537).  Writes nothing on refusal.
+int32_t plan_luminance_level(const Lightmap* m, int32_t rw, int32_t rh, int32_t accuracy, int32_t* level, int32_t* w, int32_t* h) {
+    if (rw < 2 || rh < 2 || rw > m->width || rh > m->height)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "render size %dx%d outside [2x2, %dx%d] (the lightmap)", rw, rh, m->width, m->height);
+    if (accuracy < 0) return fail(ILM_ERR_INVALID_ARGUMENT, "accuracy factor %d < 0", accuracy);
+    const int largest = std::max(m->width / 2, m->height / 2);
+    int level_count = 0;
+    while ((largest >> level_count) > 0) level_count++;         // floor(log2(largest)) + 1
+    const int l = std::min(accuracy, level_count - 1);
+    const int lw = (rw / 2) >> l, lh = (rh / 2) >> l;
+    if (lw <= 0 || lh <= 0)
+        return fail(ILM_ERR_OUT_OF_RANGE, "level %d of a %dx%d luminance target has no texels (%dx%d)", l, rw / 2, rh / 2, lw, lh);
+    *level = l; *w = lw; *h = lh;
+    return ILM_OK;
+}
+
+// the luminance pass of the frame into the context's level buffer
+int32_t queue_luminance_level(Lightmap* m, int32_t rw, int32_t rh, int32_t level, int32_t w, int32_t h) {
+    Ctx* c = m->ctx;
+    BrightnessScratch& b = c->brightness;
+    const size_t n = (size_t)w * (size_t)h;
+    if (n > b.level_cap) {
+        HIP_TRY(hipStreamSynchronize(c->main()));
+        if (b.level) HIP_TRY(hipFree(b.level));
+        b.level = nullptr; b.level_cap = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.level), sizeof(float) * n));
+        b.level_cap = n;
+    }
+    const size_t level3 = (size_t)((rw / 2) >> 3) * (size_t)((rh / 2) >> 3);
+    if (level > 3 && 2 * level3 > b.mip_cap) {
+        HIP_TRY(hipStreamSynchronize(c->main()));
+        if (b.mip) HIP_TRY(hipFree(b.mip));
+        b.mip = nullptr; b.mip_cap = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.mip), sizeof(float) * 2 * level3));
+        b.mip_cap = 2 * level3;
+    }
+    LuminanceLaunch a;
+    a.texels = m->texels; a.format = m->format; a.pitch = m->width;
+    a.rw = rw; a.rh = rh; a.w0 = rw / 2; a.h0 = rh / 2; a.level = level;
+    a.out = b.level;
+    a.mip[0] = b.mip; a.mip[1] = b.mip ? b.mip + b.mip_cap / 2 : nullptr;
+    HIP_TRY(launch_luminance_level(a, c->main()));
+    return ILM_OK;
+}
+}  // namespace
+
+int32_t ilm_lightmap_luminance(IlmHandle h, int32_t render_width, int32_t render_height, int32_t accuracy_factor,
+                               float* out_values, int32_t capacity, int32_t* out_level, int32_t* out_width, int32_t* out_height) {
+    ILM_TRACE_RANGE("ilm_lightmap_luminance");
+    Lightmap* m = from_handle<Lightmap>(h, kMagicLightmap);
+    if (!m) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
+    int32_t level = 0, w = 0, ht = 0;
+    { const int32_t rc = plan_luminance_level(m, render_width, render_height, accuracy_factor, &level, &w, &ht); if (rc != ILM_OK) return rc; }
+    if (out_values && (int64_t)capacity < (int64_t)w * (int64_t)ht)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "capacity %d below the level's %d x %d values", capacity, w, ht);
+    if (out_values) {
+        HIP_TRY(hipSetDevice(m->ctx->device));
+        { const int32_t rc = queue_luminance_level(m, render_width, render_height, level, w, ht); if (rc != ILM_OK) return rc; }
+        HIP_TRY(hipMemcpyAsync(out_values, m->ctx->brightness.level, sizeof(float) * (size_t)w * (size_t)ht, hipMemcpyDeviceToHost, m->ctx->main()));
+        HIP_TRY(hipStreamSynchronize(m->ctx->main()));
+    }
+    if (out_level) *out_level = level;
+    if (out_width) *out_width = w;
+    if (out_height) *out_height = ht;
+    return ILM_OK;
+}
+
+int32_t ilm_debug_queue_luminance(IlmHandle h, int32_t render_width, int32_t render_height, int32_t accuracy_factor) {
+    Lightmap* m = from_handle<Lightmap>(h, kMagicLightmap);
+    if (!m) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
+    int32_t level = 0, w = 0, ht = 0;
+    { const int32_t rc = plan_luminance_level(m, render_width, render_height, accuracy_factor, &level, &w, &ht); if (rc != ILM_OK) return rc; }
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    return queue_luminance_level(m, render_width, render_height, level, w, ht);
+}
+
+int32_t ilm_lightmap_histogram(IlmHandle h, const IlmHistogramParams* params, const float* bucket_max_values,
+                               IlmHistogramBucket* out_buckets, IlmHistogramResult* out) {
+    ILM_TRACE_RANGE("ilm_lightmap_histogram");
+    Lightmap* m = from_handle<Lightmap>(h, kMagicLightmap);
+    if (!m) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
+    if (!params || !bucket_max_values || !out_buckets || !out) return fail(ILM_ERR_INVALID_ARGUMENT, "NULL argument");
+    // BucketMaxValues[BucketCount - 2] must exist (Histogram.cs:78); 256 buckets are what the workgroup's tables hold
+    if (params->BucketCount < 2 || params->BucketCount > 256)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "BucketCount %d outside [2, 256]", params->BucketCount);
+    for (int i = 0; i < params->BucketCount; i++) {
+        if (bucket_max_values[i] != bucket_max_values[i]) return fail(ILM_ERR_INVALID_ARGUMENT, "bucket_max_values[%d] is NaN", i);
+        if (i > 0 && !(bucket_max_values[i] > bucket_max_values[i - 1]))
+            return fail(ILM_ERR_INVALID_ARGUMENT, "bucket_max_values[%d] = %g does not exceed its predecessor %g", i, (double)bucket_max_values[i], (double)bucket_max_values[i - 1]);
+    }
+    int32_t level = 0, w = 0, ht = 0;
+    { const int32_t rc = plan_luminance_level(m, params->RenderWidth, params->RenderHeight, params->AccuracyFactor, &level, &w, &ht); if (rc != ILM_OK) return rc; }
+    if ((int64_t)w * (int64_t)ht > (int64_t)INT32_MAX / 2) return fail(ILM_ERR_OUT_OF_RANGE, "level of %d x %d values is too large", w, ht);
+    Ctx* c = m->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    { const int32_t rc = queue_luminance_level(m, params->RenderWidth, params->RenderHeight, level, w, ht); if (rc != ILM_OK) return rc; }
+    BrightnessScratch& b = c->brightness;
+    const int n = w * ht, blocks = histogram_blocks(n), buckets = params->BucketCount;
+    if (!b.work) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.work), histogram_work_bytes()));
+    if ((size_t)blocks * 256 > b.partials_cap) {
+        HIP_TRY(hipStreamSynchronize(c->main()));
+        if (b.partials) HIP_TRY(hipFree(b.partials));
+        b.partials = nullptr; b.partials_cap = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.partials), sizeof(double) * 256 + sizeof(float) * (size_t)blocks * 256));
+        b.partials_cap = (size_t)blocks * 256;
+    }
+    // the results leave through one pinned block the last kernel writes: [bucket states | totals], read after the call's one synchronisation
+    const size_t off_totals = sizeof(IlmHistogramBucket) * (size_t)buckets;
+    unsigned char* block = nullptr;
+    int slot = -1;
+    int32_t rc = upload_small_begin(c, off_totals + 8 * sizeof(float), reinterpret_cast<void**>(&block), &slot);
+    if (rc != ILM_OK) return rc;
+    void* dv = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&dv, block, 0));
+    HistogramLaunch a;
+    a.values = b.level; a.n = n;
+    a.bucket_count = buckets; a.ignore_zeroes = params->IgnoreZeroes != 0 ? 1 : 0; a.scale = params->ScaleFactor;
+    for (int i = 0; i < 256; i++) a.table[i] = i < buckets ? bucket_max_values[i] : 0.0f;
+    a.work = b.work; a.sums = reinterpret_cast<double*>(b.partials); a.partials = b.partials + 512; a.blocks = blocks;
+    a.out_buckets = static_cast<IlmHistogramBucket*>(dv);
+    a.out_totals = reinterpret_cast<float*>(static_cast<unsigned char*>(dv) + off_totals);
+    HIP_TRY(launch_histogram(a, c->main()));
+    rc = staged_small_done(c, slot);
+    if (rc != ILM_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(c->main()));
+    memcpy(out_buckets, block, off_totals);
+    float totals[5];
+    memcpy(totals, block + off_totals, sizeof(totals));
+    memcpy(&out->SampleCount, &totals[0], sizeof(int32_t));
+    out->LevelIndex = level; out->Width = w; out->Height = ht;
+    out->Min = totals[1]; out->Max = totals[2]; out->Sum = totals[3]; out->Median = totals[4];
+    out->Mean = out->SampleCount > 0 ? out->Sum / (float)out->SampleCount : 0.0f;       // Histogram.cs:203-206
     return ILM_OK;
 }
 

@@ -359,6 +359,34 @@ struct ResolveLaunch {
 };
 hipError_t launch_resolve(const ResolveLaunch& a, hipStream_t stream);
 
+// ---- brightness estimation (brightness.hip) ---------------------------------------------------------------------
+struct LuminanceLaunch {
+    const void* texels; int32_t format, pitch;      // the lightmap, pitch in texels
+    int32_t rw, rh, w0, h0;                          // render size and level-0 size (rw / 2, rh / 2)
+    int32_t level;                                   // the level to produce: (w0 >> level) x (h0 >> level) floats at `out`
+    float* out;
+    float* mip[2];                                   // levels past 3: level 3 goes to mip[0], level k to mip[(k + 1) & 1] (each >= level 3's size)
+};
+hipError_t launch_luminance_level(const LuminanceLaunch& a, hipStream_t stream);
+struct HistogramLaunch {
+    const float* values; int32_t n;                  // the level
+    int32_t bucket_count, ignore_zeroes; float scale;
+    float table[256];                                // BucketMaxValues
+    uint32_t* work;                                  // histogram_work_bytes() of device scratch
+    float* partials; int32_t blocks;                 // bucket_count x histogram_blocks(n) partial sums
+    double* sums;                                    // 256: each bucket's sum
+    IlmHistogramBucket* out_buckets; float* out_totals;     // device-visible: bucket_count states, then SampleCount (bits), Min, Max, Sum, Median
+};
+int histogram_blocks(int n);
+size_t histogram_work_bytes();
+hipError_t launch_histogram(const HistogramLaunch& a, hipStream_t stream);
+struct BrightnessScratch {
+    float* level = nullptr; size_t level_cap = 0;    // floats
+    float* mip = nullptr; size_t mip_cap = 0;        // floats, both halves
+    uint32_t* work = nullptr;
+    float* partials = nullptr; size_t partials_cap = 0;      // floats; 256 doubles (the buckets' sums) lie in front of them
+};
+
 // ---- particle rasterisation (raster.hip) ------------------------------------------------------------------------
 struct Sprite;
 struct RasterLaunch {

@@ -487,7 +487,31 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("MaximumLightProbeCount", &RendererConfiguration::MaximumLightProbeCount)
         .def_readwrite("EnableGBuffer", &RendererConfiguration::EnableGBuffer).def_readwrite("RenderGroundPlane", &RendererConfiguration::RenderGroundPlane)
         .def_readwrite("HighQualityGBuffer", &RendererConfiguration::HighQualityGBuffer)
-        .def_readwrite("FloatLightmap", &RendererConfiguration::FloatLightmap);
+        .def_readwrite("FloatLightmap", &RendererConfiguration::FloatLightmap)
+        .def_readwrite("EnableBrightnessEstimation", &RendererConfiguration::EnableBrightnessEstimation);
+    py::class_<Histogram>(m, "Histogram")
+        .def(py::init<float, float, int, bool>(), py::arg("maxValue"), py::arg("power"), py::arg("bucketCount") = 64, py::arg("ignoreZeroes") = false)
+        .def_readonly("BucketCount", &Histogram::BucketCount).def_readonly("MaxInputValue", &Histogram::MaxInputValue)
+        .def_readwrite("IgnoreZeroes", &Histogram::IgnoreZeroes)
+        .def_property_readonly("SampleCount", &Histogram::SampleCount).def_property_readonly("Min", &Histogram::Min)
+        .def_property_readonly("Max", &Histogram::Max).def_property_readonly("Mean", &Histogram::Mean)
+        .def_property_readonly("Median", &Histogram::Median)
+        .def_property_readonly("BucketMaxValues", [](const Histogram& h) { return farray((py::ssize_t)h.BucketMaxValues().size(), h.BucketMaxValues().data()); })
+        .def("Clear", &Histogram::Clear)
+        .def("GetPercentile", [](const Histogram& h, float percent) {
+            int bucket = 0; float value = 0;
+            const bool ok = h.GetPercentile(percent, bucket, value);
+            return py::make_tuple(ok, bucket, value); })
+        .def_property_readonly("States", [](const Histogram& h) {
+            return py::bytes((const char*)h.States().data(), h.States().size() * sizeof(IlmHistogramBucket)); })
+        .def_property_readonly("Buckets", [](const Histogram& h) {
+            py::list out;
+            for (const Histogram::Bucket& b : h.Buckets()) out.append(py::make_tuple(b.BucketStart, b.BucketEnd, b.Min, b.Max, b.Mean, b.Count));
+            return out; })
+        .def("Update", [](Histogram& h, IlmHandle lightmap, int renderWidth, int renderHeight, int accuracyFactor, float scaleFactor) {
+            IlmHistogramResult r;
+            h.Update(lightmap, renderWidth, renderHeight, accuracyFactor, scaleFactor, &r);
+            return py::bytes((const char*)&r, sizeof(r)); });
     py::class_<LightingRenderer>(m, "LightingRenderer")
         .def(py::init([](DeviceContext& ctx, const RendererConfiguration& cfg, LightingEnvironment* env, uintptr_t externalLightmap) {
             return new LightingRenderer(ctx, cfg, env, reinterpret_cast<void*>(externalLightmap));
@@ -583,6 +607,7 @@ PYBIND11_MODULE(_host, m) {
             return std::move(out);
         }, py::arg("firstRow") = 0, py::arg("rowCount") = -1)
         .def_property_readonly("LightmapHandle", &LightingRenderer::Lightmap)
+        .def("TryComputeHistogram", &LightingRenderer::TryComputeHistogram, py::arg("histogram"), py::arg("accuracyFactor") = 3)
         .def_property_readonly("LightmapFormat", &LightingRenderer::LightmapFormat)
         .def("GetDistanceFieldUniformsBytes", [](const LightingRenderer& r) {
             auto u = r.GetDistanceFieldUniforms(r.Configuration.DefaultQuality); return py::bytes((const char*)&u, sizeof(u)); })

@@ -1351,6 +1351,7 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
                                                  gbuffer, Field ? Field->Texture() : 0, lightmap, rowBegin, rowEnd, stats ? &ps : nullptr));
         if (stats) { stats->SdfSamples += ps.SdfSamples; stats->PixelLightPairs += ps.PixelLightPairs; stats->TracedPairs += ps.TracedPairs; }
     }
+    lastInverseScaleFactor = 1.0f / intensityScale;      // new RenderedLighting(this, lightmap.Buffer, 1.0f / intensityScale, ...), :963-966
     if (Probes.Count() > 0)      // :1176-1182
         UpdateLightProbes(intensityScale);
 }
@@ -1424,6 +1425,91 @@ void LightingRenderer::UpdateLightProbes(float intensityScale) {
                     HalfRound(values[(size_t)i].z) * scaleFactor, HalfRound(values[(size_t)i].w) * scaleFactor };
     }
 }
+
+// RenderedLighting.TryComputeHistogram, LightingRenderer.HDR.cs:154-183: LuminanceBuffer is null without EnableBrightnessEstimation (:989)
+bool LightingRenderer::TryComputeHistogram(Histogram& histogram, int accuracyFactor) {
+    if (!Configuration.EnableBrightnessEstimation || lastInverseScaleFactor == 0)
+        return false;
+    histogram.Update(lightmap, Configuration.RenderWidth, Configuration.RenderHeight, accuracyFactor, lastInverseScaleFactor);
+    return true;
+}
+
+}  // namespace Lighting
+
+// ---- Histogram.cs ----------------------------------------------------------------------------------------
+Histogram::Histogram(float maxValue, float power, int bucketCount, bool ignoreZeroes)
+    : BucketCount(bucketCount), MaxInputValue(maxValue), IgnoreZeroes(ignoreZeroes) {
+    if (bucketCount < 2) throw ArgumentException("bucketCount");     // BucketMaxValues[BucketCount - 2], :78
+    bucketMaxValues.resize((size_t)bucketCount);
+    states.resize((size_t)bucketCount);
+    // :69-75 in double; `1 + maxValue` is a float sum, Math.Log(a, b) = log(a) / log(b), the cast binds before the `- 1`
+    const double maxValuePlusOneLog = std::log((double)(1 + maxValue)) / std::log((double)power);
+    for (int i = 0; i < bucketCount; i++) {
+        const double valueLog = (maxValuePlusOneLog / bucketCount) * (i + 1);
+        bucketMaxValues[(size_t)i] = (float)std::pow((double)power, valueLog) - 1;
+    }
+    Clear();
+}
+
+void Histogram::Clear() {
+    sampleCount = 0;
+    min = max = sum = mean = 0;
+    for (IlmHistogramBucket& b : states) b = { 0, 3.402823466e+38f, 0, 0 };
+}
+
+bool Histogram::GetPercentile(float percent, int& bucketIndex, float& value) const {
+    if ((sampleCount < 1) || (percent < 0) || (percent > 100)) {
+        bucketIndex = 0;
+        value = 0;
+        return false;
+    }
+    const int sampleIndex = (int)((float)sampleCount * percent / 100.0f);
+    int bucketFirstSample = 0;
+    for (int i = 0; i < BucketCount; i++) {
+        const int count = states[(size_t)i].Count;
+        const int localIndex = sampleIndex - bucketFirstSample;
+        if ((localIndex >= 0) && (localIndex < count)) {
+            const float minValue = (i > 0) ? bucketMaxValues[(size_t)i - 1] : 0.0f;
+            const float maxValue = bucketMaxValues[(size_t)i];
+            bucketIndex = i;
+            // Arithmetic.Lerp (Squared.Util, outside the tree): a + ((b - a) * x)
+            value = minValue + ((maxValue - minValue) * ((float)localIndex / (float)count));
+            return true;
+        }
+        bucketFirstSample += count;
+    }
+    throw InvalidOperationException("GetPercentile: no bucket holds the sample");     // `throw new Exception()`, :162
+}
+
+std::vector<Histogram::Bucket> Histogram::Buckets() const {
+    std::vector<Bucket> out;
+    for (int i = 0; i < BucketCount; i++) {
+        const IlmHistogramBucket& state = states[(size_t)i];
+        Bucket b;
+        b.BucketStart = (i > 0) ? bucketMaxValues[(size_t)i - 1] : 0.0f;
+        b.BucketEnd = bucketMaxValues[(size_t)i];
+        b.Count = state.Count;
+        b.Min = state.Count > 0 ? state.Min : 0.0f;
+        b.Max = state.Max;
+        b.Mean = state.Count > 0 ? state.Sum / (float)state.Count : 0.0f;
+        out.push_back(b);
+    }
+    return out;
+}
+
+void Histogram::Update(IlmHandle lightmap, int renderWidth, int renderHeight, int accuracyFactor, float scaleFactor, IlmHistogramResult* result) {
+    IlmHistogramParams p;
+    p.RenderWidth = renderWidth; p.RenderHeight = renderHeight; p.AccuracyFactor = accuracyFactor;
+    p.BucketCount = BucketCount; p.IgnoreZeroes = IgnoreZeroes ? 1 : 0; p.ScaleFactor = scaleFactor;
+    IlmHistogramResult r;
+    std::vector<IlmHistogramBucket> fresh((size_t)BucketCount);
+    ThrowIfFailed(ilm_lightmap_histogram(lightmap, &p, bucketMaxValues.data(), fresh.data(), &r));
+    states = fresh;
+    sampleCount = r.SampleCount; min = r.Min; max = r.Max; mean = r.Mean; median = r.Median; sum = r.Sum;
+    if (result) *result = r;
+}
+
+namespace Lighting {
 
 // ---- LightObstruction.cs ---------------------------------------------------------------------------------
 LightObstruction::LightObstruction(LightObstructionType t, Vector3 c, Vector3 radius, float rotation) : type(t), center(c), size(radius) {

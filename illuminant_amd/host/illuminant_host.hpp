@@ -630,6 +630,36 @@ private:
 
 }  // namespace Particles
 
+// Histogram, Illuminant/Histogram.cs:17-246 (no lock: the mirror's read-back is synchronous).  The device fills the bucket states and
+// the totals (ilm_lightmap_histogram = Clear + Add); the table, GetPercentile and Buckets are the reference's host code.
+class Histogram {
+public:
+    struct Bucket { float BucketStart, BucketEnd, Min, Max, Mean; int Count; };     // :26-30
+    const int BucketCount;
+    const float MaxInputValue;
+    bool IgnoreZeroes;
+    Histogram(float maxValue, float power, int bucketCount = 64, bool ignoreZeroes = false);     // :62-85
+    int SampleCount() const { return sampleCount; }
+    float Min() const { return min; }
+    float Max() const { return max; }
+    float Mean() const { return mean; }
+    float Median() const { return median; }
+    void Clear();                                                                    // :98-112
+    bool GetPercentile(float percent, int& bucketIndex, float& value) const;         // :135-163
+    std::vector<Bucket> Buckets() const;                                             // :221-245
+    const std::vector<float>& BucketMaxValues() const { return bucketMaxValues; }
+    const std::vector<IlmHistogramBucket>& States() const { return states; }
+    // HistogramUpdateTask.Execute (LightingRenderer.HDR.cs:30-54) with the level left on the device: Clear + Add over one luminance
+    // level of `lightmap`.  Returns the level's index and size in `result`.
+    void Update(IlmHandle lightmap, int renderWidth, int renderHeight, int accuracyFactor, float scaleFactor, IlmHistogramResult* result = nullptr);
+
+private:
+    std::vector<float> bucketMaxValues;
+    std::vector<IlmHistogramBucket> states;
+    int sampleCount = 0;
+    float min = 0, max = 0, mean = 0, median = 0, sum = 0;
+};
+
 namespace Lighting {
 
 enum class LightSourceRampMode { Linear = 0, Exponential = 1, Constant = 2 };       // LightSource.cs
@@ -797,6 +827,7 @@ struct RendererConfiguration {
     bool RenderGroundPlane = true;
     bool HighQualityGBuffer = true;        // GBuffer format Vector4 (true) or HalfVector4, GBuffer.cs:30-38
     bool FloatLightmap = false;       // extension: fp32 lightmap (parity format)
+    bool EnableBrightnessEstimation = false;   // LightingRenderer.Configuration.cs: RenderLighting keeps what TryComputeHistogram reads
     std::shared_ptr<RampTexture> DefaultRampTexture;   // LightingRenderer.Configuration.cs:78
     RendererConfiguration(int w, int h) : RenderWidth(w), RenderHeight(h) {}
 };
@@ -840,6 +871,11 @@ public:
     void Resolve(IlmHandle destination, const IlmHDRConfiguration* hdr = nullptr, int rowBegin = 0, int rowEnd = -1, IlmHandle albedo = 0) const;
     IlmHandle Lightmap() const { return lightmap; }
     int LightmapFormat() const { return lightmapFormat; }
+    // RenderedLighting.TryComputeHistogram, LightingRenderer.HDR.cs:154-183 (UpdateLuminanceBuffer + HistogramUpdateTask on the device):
+    // false unless Configuration.EnableBrightnessEstimation and a frame has been rendered; the scale is 1 / intensityScale of the last
+    // RenderLighting (LightingRenderer.cs:963-966).  Synchronous, like the probes' read-back (the reference completes a frame later and
+    // reads the PREVIOUS lightmap, :987-1001; here it is the frame just rendered).
+    bool TryComputeHistogram(Histogram& histogram, int accuracyFactor = 3);
 
     // _ParticleLightBatchSetup, :769-790
     static IlmParticleLightParams PackParticleLight(const ParticleLightSource& pls, bool haveDistanceField);
@@ -865,6 +901,7 @@ private:
     std::vector<const RendererQualitySettings*> groupQuality;     // null => Configuration.DefaultQuality
     std::vector<std::vector<IlmLightVertex>> groups;
     const RampTexture* boundRamp = nullptr;
+    float lastInverseScaleFactor = 0;     // RenderedLighting.InverseScaleFactor of the last RenderLighting; 0 = none yet
     void BindRamp(const RampTexture* ramp);
 };
 

@@ -111,6 +111,9 @@ SYMBOLS = {
     "ilm_resolve_lighting": (_I, [_H, _H, _P, _I, _I]),
     "ilm_resolve_lighting_with_albedo": (_I, [_H, _H, _H, _P, _I, _I]),
     "ilm_lightmap_upload": (_I, [_H, _P, _I, _I]),
+    "ilm_lightmap_luminance": (_I, [_H, _I, _I, _I, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "ilm_lightmap_histogram": (_I, [_H, _P, _P, _P, _P]),
+    "ilm_debug_queue_luminance": (_I, [_H, _I, _I, _I]),
     "ilm_group_create": (_I, [_P, _I, C.POINTER(_H)]),
     "ilm_group_unique_id": (_I, [_P]),
     "ilm_group_create_rank": (_I, [_I, _I, _I, _P, C.POINTER(_H)]),
@@ -616,6 +619,25 @@ class Lightmap:
         """ilm_lightmap_clear"""
         c = (C.c_float * 4)(*rgba)
         check(lib().ilm_lightmap_clear(self.handle, c))
+
+    def luminance(self, accuracy_factor=3, render_size=None):
+        """ilm_lightmap_luminance: the luminance level brightness estimation reads, as (level index, float32 array [height, width])."""
+        rw, rh = render_size if render_size is not None else (self.width, self.height)
+        level, w, h = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        check(lib().ilm_lightmap_luminance(self.handle, rw, rh, accuracy_factor, None, 0, C.byref(level), C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value), dtype=np.float32)
+        check(lib().ilm_lightmap_luminance(self.handle, rw, rh, accuracy_factor, _ptr(out), out.size, C.byref(level), C.byref(w), C.byref(h)))
+        return level.value, out
+
+    def histogram(self, bucket_max_values, accuracy_factor=3, scale_factor=1.0, ignore_zeroes=False, render_size=None):
+        """ilm_lightmap_histogram: Histogram.Clear + Histogram.Add over that level; returns (abi.HistogramResult, array of abi.HistogramBucket)."""
+        rw, rh = render_size if render_size is not None else (self.width, self.height)
+        table = np.ascontiguousarray(bucket_max_values, dtype=np.float32)
+        params = abi.HistogramParams(rw, rh, accuracy_factor, int(table.size), 1 if ignore_zeroes else 0, scale_factor)
+        buckets = (abi.HistogramBucket * max(int(table.size), 1))()
+        result = abi.HistogramResult()
+        check(lib().ilm_lightmap_histogram(self.handle, _byref(params), _ptr(table), C.cast(buckets, C.c_void_p), _byref(result)))
+        return result, buckets
 
     def close(self):
         if self.handle.value and self.owned:

@@ -30,13 +30,15 @@
 extern "C" {
 #endif
 
-/* 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
+/* 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
+ * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
+ * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
  * and RenderColor for particle lights across ranks).  Nothing removed or changed in layout.
  * 8 (r05): + ilm_group_lightmap_store_mode, ILM_GATHER_STORE, ilm_debug_last_light_launch, ilm_ctx_create_sibling,
  * ILM_GATHER_ASYNC + ilm_group_lightmap_wait.
  * 7 (r04): + ilm_ctx_set_light_split, ilm_sdf_mark_dirty, ilm_sdf_trace_info / IlmSdfTraceInfo; ilm_group_lightmap_set_strips became a
  * collective with one process per GPU.  Nothing was removed or changed in layout since 6. */
-#define ILM_ABI_VERSION 9
+#define ILM_ABI_VERSION 10
 
 /* ---- return codes ------------------------------------------------------ */
 #define ILM_OK                    0
@@ -937,6 +939,50 @@ int32_t ilm_resolve_lighting(IlmHandle src_lightmap, IlmHandle dst_lightmap, con
  * usual case; upload with ilm_lightmap_upload); albedo == 0 is ilm_resolve_lighting.  Not bound: AlbedoIsSRGB, the LUT-blended technique. */
 int32_t ilm_resolve_lighting_with_albedo(IlmHandle src_lightmap, IlmHandle albedo, IlmHandle dst_lightmap, const IlmHDRConfiguration* hdr,
                                          int32_t row_begin, int32_t row_end);
+
+/* ---- brightness estimation: the inputs of the resolve's AverageLuminance / MaximumLuminance / Exposure / WhitePoint -------
+ *
+ * Configuration.EnableBrightnessEstimation makes RenderLighting draw the lightmap into a half-size Single target with technique
+ * CalculateLuminance (Illuminant/Shaders/Resolve.fx:15,212-227,337-343; Illuminant/Lighting/LightingRenderer.cs:527-537,839-898,989-1001);
+ * RenderedLighting.TryComputeHistogram reads one mip level of it back and feeds it to Histogram.Add
+ * (Illuminant/Lighting/LightingRenderer.HDR.cs:21-55,154-183; Illuminant/Histogram.cs:17-246).  Both run on the device here.
+ *
+ * The level: level 0 is (render_width / 2) x (render_height / 2); its texel (x, y) is the lightmap's texel
+ * (min(rw - 1, ((2x + 1) rw) / (2 w0)), min(rh - 1, ((2y + 1) rh) / (2 h0))) -- the destination pixel centre through the draw of
+ * LightingRenderer.cs:888-893, in integer arithmetic -- turned into (r * 0.299f + g * 0.587f) + b * 0.144f (0.144 is Resolve.fx:15's
+ * constant).  Level k is ((a + b) + (c + d)) * 0.25f over the 2 x 2 texels of level k - 1, an odd last row / column dropped.  The level
+ * used is min(accuracy_factor, LevelCount - 1) with LevelCount = floor(log2(max(W / 2, H / 2))) + 1 of the lightmap's own size
+ * (HDR.cs:164) and holds (w0 >> level) x (h0 >> level) texels (HDR.cs:176-177); a level without texels is ILM_ERR_OUT_OF_RANGE.
+ * Refused with ILM_ERR_INVALID_ARGUMENT, nothing written: a render size below 2 or beyond the lightmap's, a negative accuracy factor,
+ * BucketCount outside [2, 256], a NaN or non-increasing bucket table.
+ *
+ * (The three structs below are untagged typedefs; tests/test_brightness_kat.py holds their layout to the ctypes mirrors.) */
+typedef struct { int32_t Count; float Min, Max, Sum; } IlmHistogramBucket;     /* BucketState, Histogram.cs:32-35 */
+typedef struct {
+    int32_t RenderWidth, RenderHeight;      /* Configuration.GetRenderSize of the frame in the lightmap */
+    int32_t AccuracyFactor;                 /* TryComputeHistogram's accuracyFactor (3 in the reference) */
+    int32_t BucketCount, IgnoreZeroes;
+    float   ScaleFactor;                    /* RenderedLighting.InverseScaleFactor */
+} IlmHistogramParams;
+typedef struct {
+    int32_t SampleCount, LevelIndex, Width, Height;
+    float   Min, Max, Mean, Median, Sum;    /* Histogram.cs:50-54,60 after Clear + Add */
+} IlmHistogramResult;
+/* Texture.GetDataFast(LevelIndex, ...) of HistogramUpdateTask.Execute (HDR.cs:38-41): the level's texels, row-major.
+ * out_values == NULL only reports level and size.  Synchronous. */
+int32_t ilm_lightmap_luminance(IlmHandle lightmap, int32_t render_width, int32_t render_height, int32_t accuracy_factor,
+                               float* out_values, int32_t capacity, int32_t* out_level, int32_t* out_width, int32_t* out_height);
+/* Histogram.Clear + Histogram.Add(buffer, count, ScaleFactor) over that level (HDR.cs:43-49, Histogram.cs:94-112,165-219) with the
+ * caller's BucketMaxValues (Histogram.cs:69-75): out_buckets[BucketCount] are the BucketStates, *out the totals and the median.
+ * Counts, minima, maxima and the median are exact; sums are added in a fixed order (the same call returns the same bits) and differ
+ * from the reference's sequential sum by rounding only.  The median's last-zero search sees exactly the level's values (the reference
+ * searches its whole, possibly longer, scratch array).  Synchronous, like ilm_render_light_probes. */
+int32_t ilm_lightmap_histogram(IlmHandle lightmap, const IlmHistogramParams* params, const float* bucket_max_values,
+                               IlmHistogramBucket* out_buckets, IlmHistogramResult* out);
+
+/* Measurement hook (tools/brightness_time.py): queues the luminance pass of the two calls above on the context's stream and returns --
+ * nothing is read back, nothing synchronises.  Same refusals. */
+int32_t ilm_debug_queue_luminance(IlmHandle lightmap, int32_t render_width, int32_t render_height, int32_t accuracy_factor);
 
 /* ---- multi-device groups (SURVEY 8e / 8b "ilm_ctx_create(device_ids, n)") --------------------------------------------------------
  *

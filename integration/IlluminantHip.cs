@@ -1,6 +1,6 @@
 // IlluminantHip.cs -- P/Invoke layer of libilluminant_hip.so for sq/Illuminant (drop into Illuminant/Native/).
 // GENERATED from include/illuminant_hip.h by tools/gen_csharp_binding.py -- do not edit; the header carries the documentation
-// and the reference file:line each entry point replaces.  ABI version 9.
+// and the reference file:line each entry point replaces.  ABI version 10.
 //
 // Vector4 / Matrix are XNA's; LightVertex is Illuminant/Vertices.cs:10-39; the Uniforms.* structs of the reference
 // (Uniforms.cs:14-24,79-88,197-236; Bezier.cs:433-441,588-599) have the byte layout of the Ilm* mirrors below and can be passed
@@ -16,7 +16,7 @@ namespace Squared.Illuminant.Native {
     }
 
     public static class IlmConstants {
-        public const int ABI_VERSION = 9;
+        public const int ABI_VERSION = 10;
         public const int BLEND_FP16_PER_LIGHT = 1;
         public const int BLEND_FP32_ACCUMULATE = 0;
         public const int ERR_INVALID_ARGUMENT = -1;
@@ -468,6 +468,37 @@ namespace Squared.Illuminant.Native {
         public int AlbedoIsSRGB;
     }
 
+    [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 16)]
+    public struct IlmHistogramBucket {
+        public int Count;
+        public float Min;
+        public float Max;
+        public float Sum;
+    }
+
+    [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 24)]
+    public struct IlmHistogramParams {
+        public int RenderWidth;
+        public int RenderHeight;
+        public int AccuracyFactor;
+        public int BucketCount;
+        public int IgnoreZeroes;
+        public float ScaleFactor;
+    }
+
+    [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 36)]
+    public struct IlmHistogramResult {
+        public int SampleCount;
+        public int LevelIndex;
+        public int Width;
+        public int Height;
+        public float Min;
+        public float Max;
+        public float Mean;
+        public float Median;
+        public float Sum;
+    }
+
     internal static unsafe class IlluminantHip {
         const string Lib = "illuminant_hip";             // libilluminant_hip.so next to the game's assemblies
 
@@ -552,6 +583,9 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_clear (ulong lightmap, float* rgba);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_resolve_lighting (ulong srcLightmap, ulong dstLightmap, IlmHDRConfiguration* hdr, int rowBegin, int rowEnd);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_resolve_lighting_with_albedo (ulong srcLightmap, ulong albedo, ulong dstLightmap, IlmHDRConfiguration* hdr, int rowBegin, int rowEnd);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_luminance (ulong lightmap, int renderWidth, int renderHeight, int accuracyFactor, float* outValues, int capacity, int* outLevel, int* outWidth, int* outHeight);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_histogram (ulong lightmap, IlmHistogramParams* @params, float* bucketMaxValues, IlmHistogramBucket* outBuckets, IlmHistogramResult* @out);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_queue_luminance (ulong lightmap, int renderWidth, int renderHeight, int accuracyFactor);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_group_create (int* deviceIds, int n, ulong* outGroup);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_group_unique_id (void* outId128);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_group_create_rank (int deviceId, int rank, int world, void* id128, ulong* outGroup);

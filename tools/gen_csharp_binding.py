@@ -31,8 +31,9 @@ def strip_comments(text):
 def parse_structs(text):
     """[(name, kind, [(ctype, field, dims)])] in declaration order; kind = 'struct'.  Anonymous unions become a nested entry."""
     structs = []
-    for m in re.finditer(r"typedef struct (Ilm\w+) \{(.*?)\} \1;", text, flags=re.S):
-        name, body = m.group(1), m.group(2)
+    # (tagged `typedef struct IlmX { ... } IlmX;` or untagged `typedef struct { ... } IlmX;`)
+    for m in re.finditer(r"typedef struct (?:(Ilm\w+) \{(.*?)\} \1|\{([^{}]*)\} (Ilm\w+));", text, flags=re.S):
+        name, body = (m.group(1), m.group(2)) if m.group(1) else (m.group(4), m.group(3))
         fields = []
         union = re.search(r"union \{(.*?)\} (\w+);", body, flags=re.S)
         if union:
