@@ -139,6 +139,14 @@ struct Engine {
     std::vector<Slab> slabs;
     std::vector<float*> spare;
     size_t chunk_bytes() const { return sizeof(float) * (size_t)kComponents * (size_t)stride; }
+    // ilm_engine_step_batch: the items' records (StepBatchItem) and the launches' block tables go through a ring of page-locked slots --
+    // a slot is rewritten only after the event behind its copy has passed -- into ONE device table, with one copy per call.  Both grow
+    // on demand; an outgrown device table is kept until the engine goes (freeing it would wait for the device).
+    static constexpr int kBatchRing = 4;
+    void* batch_pinned[kBatchRing] = {}; size_t batch_pinned_bytes[kBatchRing] = {}; hipEvent_t batch_ev[kBatchRing] = {}; int batch_pos = 0;
+    void* d_batch = nullptr; size_t d_batch_bytes = 0;
+    std::vector<void*> d_batch_outgrown;
+    int last_batch_launches = 0, last_batch_rounds = 0, last_batch_fallback = 0;      // ilm_debug_last_step_batch
 };
 
 // A distance field or G-buffer that sibling contexts read (light passes on another context's stream).  Every WRITE to it happens on its
@@ -970,10 +978,15 @@ static bool stream_capturing(hipStream_t stream) {
     return status != hipStreamCaptureStatusNone;
 }
 
-int32_t run_step(System* s, const IlmStepDesc* d) {
+// A step in two halves.  prepare_step validates and fills the StepLaunch with everything the host decides -- and does the bookkeeping
+// that goes with it (System::used, the counting sequence number, feedback sources, the field's slice-0 cells); none of it depends on
+// what the device computes.  The caller launches (*count > 0) and then calls finish_step.  ilm_system_step runs the halves back to back
+// (run_step); ilm_engine_step_batch prepares every item in order first and launches afterwards.
+static int32_t prepare_step(System* s, const IlmStepDesc* d, StepLaunch& a, int* out_first, int* out_count) {
     int first = 0, count = 0;
     int32_t rc = validate_step(s, d, &first, &count);
     if (rc != ILM_OK) return rc;
+    *out_first = first; *out_count = count;
     Engine* e = s->engine;
     Ctx* c = e->ctx;
     HIP_TRY(hipSetDevice(c->device));
@@ -987,7 +1000,6 @@ int32_t run_step(System* s, const IlmStepDesc* d) {
     const bool counting = (d->Flags & ILM_STEP_COUNT_LIVE) != 0;
     const int region = s->count_parity;
 
-    StepLaunch a;
     memcpy(&a.desc, d, sizeof(IlmStepDesc));
     a.chunk_bases = s->d_table;
     a.stride = e->stride;
@@ -1098,6 +1110,31 @@ int32_t run_step(System* s, const IlmStepDesc* d) {
             }
         }
     }
+    return ILM_OK;
+}
+// the bookkeeping that follows a step's launches
+static void finish_step(System* s, const IlmStepDesc* d, int first, int count) {
+    if (d->UpdateMode == ILM_UPDATE_ERASE)
+        for (int ci = first; ci < first + count; ci++) s->used[(size_t)ci] = 0;   // position, velocity and render planes are zero again
+    if (d->Flags & ILM_STEP_COUNT_LIVE) {
+        // the kernel publishes every chunk of its range itself; ilm_system_poll_counts / ilm_system_step_counts read the host table
+        s->counts_n = (int)s->chunks.size();
+        s->counts_first = first; s->counts_span = count;
+        s->counts_pending = true;
+        s->counts_valid = true;
+        s->count_parity ^= 1;
+    }
+}
+
+int32_t run_step(System* s, const IlmStepDesc* d) {
+    int first = 0, count = 0;
+    StepLaunch a;
+    const int32_t rc = prepare_step(s, d, a, &first, &count);
+    if (rc != ILM_OK || count == 0) return rc;
+    Engine* e = s->engine;
+    Ctx* c = e->ctx;
+    const bool counting = (d->Flags & ILM_STEP_COUNT_LIVE) != 0;
+    const int region = s->count_parity;
     // Two streams for a large step.  A launch of this size is a few wave generations long, and back-to-back launches on one stream
     // pay its ramp and its tail (the last waves run alone) plus the dispatch gap every time: ~7.7 us of the ~23 us a cfg2 step takes
     // (tools/two_stream_probe.py: two 8-chunk launches in a row 31.2 us, one 16-chunk launch 23.5 us).  Chunks never interact, so
@@ -1168,16 +1205,155 @@ int32_t run_step(System* s, const IlmStepDesc* d) {
         render_refreshed(first, mid, fresh_a);
         render_refreshed(mid, first + count, fresh_b);
     }
-    if (d->UpdateMode == ILM_UPDATE_ERASE)
-        for (int ci = first; ci < first + count; ci++) s->used[(size_t)ci] = 0;   // position, velocity and render planes are zero again
-    if (d->Flags & ILM_STEP_COUNT_LIVE) {
-        // the kernel publishes every chunk of its range itself; ilm_system_poll_counts / ilm_system_step_counts read the host table
-        s->counts_n = (int)s->chunks.size();
-        s->counts_first = first; s->counts_span = count;
-        s->counts_pending = true;
-        s->counts_valid = true;
-        s->count_parity ^= 1;
+    finish_step(s, d, first, count);
+    return ILM_OK;
+}
+
+// ilm_engine_step_batch.  Every item is validated before anything changes; then every item is prepared in order (prepare_step +
+// finish_step: the host state of item i + 1 sees item i's, as in a loop over ilm_system_step), the launches are planned and the records
+// travel to the device in one copy.  Rounds: an item runs one round after the latest earlier item that touches a system it touches --
+// its own, and the source of each feedback record -- so it reads what earlier items wrote and is read before later items write.  The
+// items of a round are independent: each kernel variant among them is ONE launch of step_batch_kernel on the context stream; an item
+// the batch kernel does not cover (a streaming range, a stream being captured) goes through launch_step in its round.
+static int32_t fail_item(int32_t code, int item) {
+    char text[sizeof(g_last_error)];
+    snprintf(text, sizeof(text), "item %d: %s", item, g_last_error);
+    memcpy(g_last_error, text, sizeof(text));
+    return code;
+}
+int32_t run_step_batch(Engine* e, const IlmHandle* handles, const IlmStepDesc* descs, int32_t count) {
+    Ctx* c = e->ctx;
+    constexpr int kUnitsPerBlock = kStepThreads / 64;      // of the interpreter's blocks (particles.hip)
+    std::vector<System*> sys((size_t)count);
+    size_t block_bound = 0;
+    for (int i = 0; i < count; i++) {
+        System* s = from_handle<System>(handles[i], kMagicSystem);
+        if (!s) return fail(ILM_ERR_INVALID_HANDLE, "item %d: not a system handle", i);
+        if (s->engine != e) return fail(ILM_ERR_INVALID_ARGUMENT, "item %d: the system belongs to another engine", i);
+        int first = 0, n = 0;
+        const int32_t rc = validate_step(s, &descs[i], &first, &n);
+        if (rc != ILM_OK) return fail_item(rc, i);
+        sys[(size_t)i] = s;
+        block_bound += ((size_t)n * (size_t)(e->span / 64) + kUnitsPerBlock - 1) / kUnitsPerBlock;
     }
+    HIP_TRY(hipSetDevice(c->device));
+    const bool capturing = stream_capturing(c->stream_) || stream_capturing(c->aux);
+
+    // the records: in a slot of the page-locked ring, or (no copy can be queued into a capture) in plain host memory
+    const size_t table_bytes = sizeof(StepBatchItem) * (size_t)count, bytes = table_bytes + sizeof(int32_t) * block_bound;
+    StepBatchItem* items = nullptr;
+    int32_t* item_of_block = nullptr;
+    std::vector<StepLaunch> captured;
+    int slot = -1;
+    if (capturing) {
+        captured.resize((size_t)count);
+    } else {
+        slot = e->batch_pos;
+        e->batch_pos = (e->batch_pos + 1) % Engine::kBatchRing;
+        if (e->batch_ev[slot] == nullptr) HIP_TRY(hipEventCreateWithFlags(&e->batch_ev[slot], hipEventDisableTiming));
+        else HIP_TRY(hipEventSynchronize(e->batch_ev[slot]));       // the copy that last read this slot
+        if (e->batch_pinned_bytes[slot] < bytes) {
+            if (e->batch_pinned[slot]) HIP_TRY(hipHostFree(e->batch_pinned[slot]));
+            e->batch_pinned[slot] = nullptr; e->batch_pinned_bytes[slot] = 0;
+            const size_t cap = std::max(bytes + bytes / 2, (size_t)1 << 16);
+            HIP_TRY(hipHostMalloc(&e->batch_pinned[slot], cap, hipHostMallocDefault));
+            e->batch_pinned_bytes[slot] = cap;
+        }
+        if (e->d_batch_bytes < bytes) {
+            const size_t cap = std::max(std::max(bytes, e->d_batch_bytes * 2), (size_t)1 << 16);
+            if (e->d_batch) e->d_batch_outgrown.push_back(e->d_batch);
+            e->d_batch = nullptr; e->d_batch_bytes = 0;
+            HIP_TRY(hipMalloc(&e->d_batch, cap));
+            e->d_batch_bytes = cap;
+        }
+        items = static_cast<StepBatchItem*>(e->batch_pinned[slot]);
+        item_of_block = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(e->batch_pinned[slot]) + table_bytes);
+    }
+    auto record = [&](int i) -> StepLaunch& { return capturing ? captured[(size_t)i] : items[i].a; };
+
+    // prepare in order; plan the rounds
+    struct Planned { int round, variant, blocks; };
+    std::vector<Planned> plan((size_t)count);
+    std::unordered_map<const System*, int> last_round;
+    int rounds = 0, fallback = 0;
+    for (int i = 0; i < count; i++) {
+        System* s = sys[(size_t)i];
+        const IlmStepDesc* d = &descs[i];
+        int first = 0, n = 0;
+        const int32_t rc = prepare_step(s, d, record(i), &first, &n);
+        if (rc != ILM_OK) return fail_item(rc, i);
+        plan[(size_t)i] = Planned{ 0, -1, 0 };
+        if (n == 0) continue;
+        // the render-plane records: a batched item is "another step" (it clears its range and sets nothing)
+        if (d->UpdateMode == ILM_UPDATE_POSITIONS) (void)render_key_generation(s, d);
+        if (capturing) s->render_captured = true;
+        for (int ci = first; ci < first + n; ci++) s->render_gen[(size_t)ci] = 0;
+        finish_step(s, d, first, n);
+
+        Planned& p = plan[(size_t)i];
+        p.variant = step_batch_layout(record(i), &p.blocks);
+        if (capturing) p.variant = -1;
+        if (p.variant < 0) fallback++;
+        int after = last_round[s];
+        for (int k = 0; k < d->SpawnCount; k++)
+            if (d->Spawns[k].Kind == ILM_SPAWN_FEEDBACK) after = std::max(after, last_round[from_handle<System>(d->Spawns[k].Feedback.SourceSystem, kMagicSystem)]);
+        p.round = after + 1;
+        last_round[s] = p.round;
+        for (int k = 0; k < d->SpawnCount; k++)
+            if (d->Spawns[k].Kind == ILM_SPAWN_FEEDBACK) last_round[from_handle<System>(d->Spawns[k].Feedback.SourceSystem, kMagicSystem)] = p.round;
+        rounds = std::max(rounds, p.round);
+    }
+
+    // the launches of each round: one per variant, its items' blocks back to back in the block table
+    struct Launch { int round, variant, first_block, blocks, item; };     // variant < 0: `item` through launch_step
+    std::vector<Launch> launches;
+    size_t blocks_used = 0;
+    for (int r = 1; r <= rounds; r++) {
+        const size_t round_begin = launches.size();
+        for (int i = 0; i < count; i++) {
+            const Planned& p = plan[(size_t)i];
+            if (p.round != r) continue;
+            if (p.variant < 0) continue;
+            size_t at = round_begin;
+            while (at < launches.size() && launches[at].variant != p.variant) at++;
+            if (at == launches.size()) launches.push_back(Launch{ r, p.variant, 0, 0, -1 });
+            launches[at].blocks += p.blocks;
+        }
+        for (size_t l = round_begin; l < launches.size(); l++) {
+            launches[l].first_block = (int)blocks_used;
+            int block = 0;
+            for (int i = 0; i < count; i++) {
+                const Planned& p = plan[(size_t)i];
+                if (p.round != r || p.variant != launches[l].variant) continue;
+                items[i].first_block = block;
+                items[i].block_count = p.blocks;
+                for (int b = 0; b < p.blocks; b++) item_of_block[blocks_used + (size_t)block + (size_t)b] = i;
+                block += p.blocks;
+            }
+            blocks_used += (size_t)launches[l].blocks;
+        }
+        for (int i = 0; i < count; i++)
+            if (plan[(size_t)i].round == r && plan[(size_t)i].variant < 0) launches.push_back(Launch{ r, -1, 0, 0, i });
+    }
+    if (blocks_used > block_bound) return fail(ILM_ERR_STATE, "step batch: %zu blocks planned, %zu reserved", blocks_used, block_bound);
+
+    const hipStream_t stream = c->main();      // (joined with the second stepping stream: no batch item is split over the two)
+    int kernel_launches = 0;
+    if (blocks_used > 0) {
+        HIP_TRY(hipMemcpyAsync(e->d_batch, e->batch_pinned[slot], table_bytes + sizeof(int32_t) * blocks_used, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(e->batch_ev[slot], stream));
+    }
+    const StepBatchItem* d_items = static_cast<const StepBatchItem*>(e->d_batch);
+    const int32_t* d_item_of_block = reinterpret_cast<const int32_t*>(static_cast<const unsigned char*>(e->d_batch) + table_bytes);
+    for (const Launch& l : launches) {
+        if (l.variant >= 0) {
+            HIP_TRY(launch_step_batch(l.variant, d_items, d_item_of_block + l.first_block, l.blocks, stream));
+            kernel_launches++;
+        } else {
+            HIP_TRY(launch_step(record(l.item), stream, 0u, nullptr));
+        }
+    }
+    e->last_batch_launches = kernel_launches; e->last_batch_rounds = rounds; e->last_batch_fallback = fallback;
     return ILM_OK;
 }
 
@@ -1593,6 +1769,12 @@ int32_t ilm_engine_destroy(IlmHandle h) {
     if (e->rnd) (void)hipFree(e->rnd);
     if (e->rnd_lp) (void)hipFree(e->rnd_lp);
     for (const Engine::Slab& slab : e->slabs) (void)hipFree(slab.base);
+    for (int k = 0; k < Engine::kBatchRing; k++) {
+        if (e->batch_pinned[k]) (void)hipHostFree(e->batch_pinned[k]);
+        if (e->batch_ev[k]) (void)hipEventDestroy(e->batch_ev[k]);
+    }
+    if (e->d_batch) (void)hipFree(e->d_batch);
+    for (void* p : e->d_batch_outgrown) (void)hipFree(p);
     retire_handle(e);
     delete e;
     return ILM_OK;
@@ -1818,6 +2000,24 @@ int32_t ilm_system_step(IlmHandle h, const IlmStepDesc* desc) {
     if (!s) return fail(ILM_ERR_INVALID_HANDLE, "not a system handle");
     if (!desc) return fail(ILM_ERR_INVALID_ARGUMENT, "desc is NULL");
     return run_step(s, desc);
+}
+
+int32_t ilm_engine_step_batch(IlmHandle h, const IlmHandle* systems, const IlmStepDesc* descs, int32_t count) {
+    ILM_TRACE_RANGE("ilm_engine_step_batch");
+    if (count < 0) return fail(ILM_ERR_INVALID_ARGUMENT, "count %d is negative", count);
+    if (count > 0 && (!systems || !descs)) return fail(ILM_ERR_INVALID_ARGUMENT, "NULL argument");
+    Engine* e = from_handle<Engine>(h, kMagicEngine);
+    if (!e) return fail(ILM_ERR_INVALID_HANDLE, "not an engine handle");
+    if (count == 0) return ILM_OK;
+    return run_step_batch(e, systems, descs, count);
+}
+int32_t ilm_debug_last_step_batch(IlmHandle h, int32_t* out_launches, int32_t* out_rounds, int32_t* out_fallback_items) {
+    Engine* e = from_handle<Engine>(h, kMagicEngine);
+    if (!e) return fail(ILM_ERR_INVALID_HANDLE, "not an engine handle");
+    if (out_launches) *out_launches = e->last_batch_launches;
+    if (out_rounds) *out_rounds = e->last_batch_rounds;
+    if (out_fallback_items) *out_fallback_items = e->last_batch_fallback;
+    return ILM_OK;
 }
 
 static void init_single_pass(IlmStepDesc* d, int32_t chunk_index, const IlmParticleSystemUniforms* sys) {

@@ -111,6 +111,15 @@ struct StepLaunch {
 
 static_assert(sizeof(StepLaunch) <= 4096, "StepLaunch travels in the kernarg segment (4 KB)");
 
+// One item of ilm_engine_step_batch as it lies in the engine's device table: the item's StepLaunch, then where its blocks start in
+// the grid of its launch (step_batch_kernel).  4 KB each, so a record starts on a line of its own.
+struct alignas(4096) StepBatchItem {
+    StepLaunch a;
+    int32_t first_block;         // of the item in its launch's grid
+    int32_t block_count;
+};
+static_assert(sizeof(StepBatchItem) == 4096 && offsetof(StepBatchItem, a) == 0, "a batch record is its StepLaunch plus the block range, 4 KB");
+
 // per-chunk live counters are kCountStride 64-bit words apart (one 128-byte line each)
 constexpr int kCountStride = 16;     // in 64-bit words
 constexpr int kCountLines = 17;      // per chunk in the step kernels' counter regions: the chunk's line + 16 bucket lines
@@ -123,6 +132,11 @@ constexpr int kCountLines = 17;      // per chunk in the step kernels' counter r
 constexpr uint32_t kElideDerived = 1u;
 constexpr uint32_t kElideColor = 2u;     // (set by build_lean_step) the colour curves cannot produce a NaN factor: renderColor may be elided
 hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide = 0u, bool* refreshed = nullptr);
+// ilm_engine_step_batch: lay a prepared StepLaunch out like launch_step does and return the batch kernel's variant for it (-1: the batch
+// kernel does not cover it -- a streaming range -- and launch_step runs it); *blocks = the blocks it takes in a launch's grid.
+// launch_step_batch: ONE launch over `blocks` blocks of items of one variant; item_of_block[b] indexes `table` (device memory, read-only).
+int step_batch_layout(StepLaunch& a, int* blocks);
+hipError_t launch_step_batch(int variant, const StepBatchItem* table, const int32_t* item_of_block, int blocks, hipStream_t stream);
 hipError_t step_sdf_sample_counter(int enable, unsigned long long* out);   // ilm_debug_step_sdf_samples
 // the slice-0 cells of a UNORM16 field (SdfView::cells0): does this step's collision update use them, and their build
 bool step_wants_slice0_cells(const IlmStepDesc& d, int format);

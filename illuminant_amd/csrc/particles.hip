@@ -8,7 +8,7 @@
 // access is one dword per lane on an SGPR plane base: 256 contiguous bytes per instruction.
 // The hardware dispatcher balances the waves; nothing is persistent or software-pipelined.
 //
-// Three kernels run a step (launch_step chooses; ilm_debug_last_step_kernel reports):
+// Three kernels run a step (launch_step chooses; ilm_debug_last_step_kernel reports), a fourth a batch of steps:
 //   step_kernel            interprets any IlmStepDesc: every transform, spawner kind and update mode.  Runs what
 //                          the lean kernels do not accept, and everything under ILM_STEP_LEAN=0 / ILM_DF_LEAN=0.
 //   step_lean_kernel,      the common shape of a step (power-of-two chunks, UpdatePositions, Gravity / Noise /
@@ -16,7 +16,9 @@
 //                          streaming launch whose curves all have the clamp range.
 //   step_lean_df_kernel    the same shape with UpdateWithDistanceField: K units per wave, the colliding
 //                          lanes parked and finished at full width.
-// The per-slot arithmetic is stated once and shared by all three (gravity_term, apply_noise, apply_fma,
+//   step_batch_kernel      step_kernel's body over the items of ilm_engine_step_batch: many small systems' steps in one
+//                          grid, each block finding its item's StepLaunch in a device table.  The lean kernels are not batched.
+// The per-slot arithmetic is stated once and shared by all of them (gravity_term, apply_noise, apply_fma,
 // spawn_slot, df_long, render_data): the GPU tests hold the kernels to each other bit for bit.
 //
 // HBM-bound integer/float streaming work: no MFMA; LDS only for the parked lanes of the collision kernel.
@@ -1090,10 +1092,11 @@ ILM_DEV bool process_unit(CStepLaunch* ap, const UnitPlanes& up, int chunk, int 
 // the step's sequence number, straight into the host's table.  (Per-wave atomics on one address serialise at ~11 ns each: 1024 of
 // them per chunk made the step 7x slower; one per block on ONE address per chunk still queued 4096 deep on 1024^2 chunks.)  The
 // units of a block always belong to one chunk.
-ILM_DEV void publish_block_count(uint32_t* wave_live, uint32_t n_live, unsigned lane, int wave, bool block_in_range, int chunk, int block_in_chunk,
-                                 int blocks_per_chunk, int buckets, unsigned long long* live_counts, unsigned long long* zero_counts, int zero_n,
-                                 unsigned long long* host_counts, uint32_t seq) {
-    if (blockIdx.x == 0)
+// `zero_block`: this block zeroes the other counter region (one block per launch; per item in step_batch_kernel).
+ILM_DEV void publish_block_count_at(bool zero_block, uint32_t* wave_live, uint32_t n_live, unsigned lane, int wave, bool block_in_range, int chunk, int block_in_chunk,
+                                    int blocks_per_chunk, int buckets, unsigned long long* live_counts, unsigned long long* zero_counts, int zero_n,
+                                    unsigned long long* host_counts, uint32_t seq) {
+    if (zero_block)
         for (int i = (int)threadIdx.x; i < zero_n; i += kStepThreads) zero_counts[i * kCountStride] = 0ull;
     if (lane == 0) wave_live[wave] = n_live;
     __syncthreads();
@@ -1113,6 +1116,13 @@ ILM_DEV void publish_block_count(uint32_t* wave_live, uint32_t n_live, unsigned 
             }
         }
     }
+}
+
+ILM_DEV void publish_block_count(uint32_t* wave_live, uint32_t n_live, unsigned lane, int wave, bool block_in_range, int chunk, int block_in_chunk,
+                                 int blocks_per_chunk, int buckets, unsigned long long* live_counts, unsigned long long* zero_counts, int zero_n,
+                                 unsigned long long* host_counts, uint32_t seq) {
+    publish_block_count_at(blockIdx.x == 0, wave_live, n_live, lane, wave, block_in_range, chunk, block_in_chunk, blocks_per_chunk, buckets, live_counts,
+                           zero_counts, zero_n, host_counts, seq);
 }
 
 // The launch descriptor is written by the host into the kernarg ring just before the launch, so the first wave of every scalar cache
@@ -1195,6 +1205,66 @@ __global__ __launch_bounds__(kStepThreads, MINW) void step_kernel(const StepLaun
         constexpr int kUnitsPerBlock = kStepThreads / 64;
         publish_block_count(wave_live, n_live, lane, wave, v < total, a.first_chunk + chunk_rel, (first_unit - chunk_rel * a.units_per_chunk) / kUnitsPerBlock,
                             a.units_per_chunk / kUnitsPerBlock, a.count_buckets, a.live_counts, a.zero_counts, a.zero_n, a.host_counts, a.count_seq);
+    }
+}
+
+// The interpreter over MANY launches' worth of work in one grid (ilm_engine_step_batch): the StepLaunch records of the items lie in a
+// device table, and a block finds its item with one scalar load of item_of_block[blockIdx.x].  From there it is step_kernel's body with
+// the item's LOCAL block index where step_kernel has blockIdx.x -- the rotation, the range test, the counters' buckets and the zeroing
+// of the item's other counter region all come from the item, none from the grid -- so an item's planes and counts get the bits its own
+// launch of step_kernel would have given them.  The table and the records are read-only here.  No STREAM variant: a range that large
+// is launched on its own.
+typedef const StepBatchItem __attribute__((address_space(4))) CStepBatchItem;
+typedef const int32_t __attribute__((address_space(4))) CInt32;
+ILM_DEV void touch_record_lines_step(CStepLaunch* ap) {     // touch_kernarg_lines_step for a record in the table: its lines are as cold
+    uint32_t sink;
+    asm volatile(ILM_T16(0x0) ILM_T16(0x400) ILM_T16(0x800) ILM_T4(0xc00) ILM_T4(0xd00) ILM_T4(0xe00) ILM_T1(0xf00) ILM_T1(0xf40) ILM_T1(0xf80)
+                 "s_waitcnt lgkmcnt(0)" : "=&s"(sink) : "s"(ap));
+}
+template <int FMT, bool DF, bool SPAWN, int MINW, bool EXT = false>
+__global__ __launch_bounds__(kStepThreads, MINW) void step_batch_kernel(const StepBatchItem* table, const int32_t* item_of_block) {
+    __shared__ uint32_t wave_live[kStepThreads / 64];
+    const int item = ((CInt32*)item_of_block)[blockIdx.x];
+    CStepBatchItem* ip = (CStepBatchItem*)table + item;
+    CStepLaunch* ap = (CStepLaunch*)ip;
+    const StepLaunch& a = *(const StepLaunch*)ap;
+    const int block = (int)blockIdx.x - ip->first_block;     // the block's index in its item
+    if (block < kTouchBlocks) touch_record_lines_step(ap);
+    const unsigned lane = threadIdx.x & 63u;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    int v = block * (kStepThreads / 64) + a.unit_rotate;      // first unit of the block (rotation: see step_kernel)
+    const int total = a.unit_end - a.unit_begin;
+    if (v >= a.total_padded) v -= a.total_padded;
+    const int u = a.unit_begin + v + wave;
+    uint32_t n_live = 0;
+    if (v + wave < total) {
+        const int chunk_rel = (a.upc_shift >= 0) ? (u >> a.upc_shift) : (u / a.units_per_chunk);
+        const int seg = u - chunk_rel * a.units_per_chunk;
+        const int chunk = a.first_chunk + chunk_rel;
+        bool untouched = false;
+        for (int k = 0; k < a.partial_count; k++)
+            untouched = untouched || ((a.partial_chunk[k] == chunk) && (seg >= a.partial_units[k]));
+        if (!untouched) {
+            const UnitPlanes up = unit_planes(((CBase*)a.chunk_bases)[chunk], a.stride, seg * 64);
+            const SlotIn cur = load_slot<true, false>(up, lane * 4u);
+            NoiseDeltas noise;
+            noise.valid = false;
+            if (a.derived.noise.op >= 0) {
+                const int first = seg * 64;
+                const int row = (a.derived.cs_shift >= 0) ? (first >> a.derived.cs_shift) : (first / a.chunk_size);
+                noise = noise_prepare(a.derived.noise, reinterpret_cast<const IlmFloat4*>(&a.desc.Spawns[0]), first - row * a.chunk_size, row);
+            }
+            const bool live_after = process_unit<FMT, DF, SPAWN, EXT, false>(ap, up, chunk, seg * 64 + (int)lane, lane, seg, cur, noise);
+            n_live = (uint32_t)__popcll(__ballot(live_after));
+        }
+    }
+    if (a.desc.Flags & ILM_STEP_COUNT_LIVE) {
+        const int first_unit = a.unit_begin + v;
+        const int chunk_rel = (a.upc_shift >= 0) ? (first_unit >> a.upc_shift) : (first_unit / a.units_per_chunk);
+        constexpr int kUnitsPerBlock = kStepThreads / 64;
+        publish_block_count_at(block == 0, wave_live, n_live, lane, wave, v < total, a.first_chunk + chunk_rel,
+                               (first_unit - chunk_rel * a.units_per_chunk) / kUnitsPerBlock, a.units_per_chunk / kUnitsPerBlock, a.count_buckets,
+                               a.live_counts, a.zero_counts, a.zero_n, a.host_counts, a.count_seq);
     }
 }
 
@@ -2123,8 +2193,8 @@ int set_step_interpreter(int on) {
 
 // One launch per ParticleSystem.Update: the unit range covers every chunk of the step; when spawn records are
 // present the SPAWN variant runs (for every unit) and the grid is rotated to start at the first spawn range.
-hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide, bool* refreshed) {
-    if (refreshed) *refreshed = false;
+// The launch's unit range and block lay-out (the StepLaunch fields "filled by launch_step"); true when spawn records apply to the range.
+static bool layout_step(StepLaunch& a) {
     a.units_per_chunk = a.span / 64;
     a.upc_shift = -1;
     for (int b = 0; b < 31; b++)
@@ -2145,6 +2215,11 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide,
     }
     const BlockLayout l = block_layout(a.unit_end, first_spawn_unit, a.units_per_chunk, kStepThreads / 64);
     a.total_padded = l.total_padded; a.unit_rotate = l.unit_rotate; a.count_buckets = l.count_buckets;
+    return spawning;
+}
+hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide, bool* refreshed) {
+    if (refreshed) *refreshed = false;
+    const bool spawning = layout_step(a);
     if (!step_interpreter_forced() && a.unit_end > a.unit_begin) {
         if (a.desc.UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD) {
             const char* lean_env = getenv("ILM_DF_LEAN");                 // A/B switch, read per launch: 0 = the interpreter
@@ -2168,6 +2243,43 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide,
     }
     g_last_step_kernel = ILM_STEP_KERNEL_INTERPRETER;
     return spawning ? launch_step_variant<true>(a, stream) : launch_step_variant<false>(a, stream);
+}
+
+// The batch kernel's variants are launch_step_variant's without the streaming one.  Key: bits 0-1 = 0 plain, 1 spawning, 2 extended;
+// bits 2.. = 0 without a field, else 1 + the collision kernels' first template argument (format | kFieldSlice0).
+int step_batch_layout(StepLaunch& a, int* blocks) {
+    const bool spawning = layout_step(a);
+    const int units = a.unit_end - a.unit_begin;
+    *blocks = (units + kStepThreads / 64 - 1) / (kStepThreads / 64);
+    if (a.streaming || units <= 0) return -1;
+    int field = 0;
+    if (a.desc.UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD) {
+        if (with_field_format<false>(a, [&](auto fmt) { field = 1 + decltype(fmt)::value; return hipSuccess; }) != hipSuccess) return -1;
+    }
+    return (field << 2) | (needs_extended_variant(a) ? 2 : (spawning ? 1 : 0));
+}
+template <int FMT, bool DF>
+static hipError_t launch_step_batch_variant(int kind, const StepBatchItem* table, const int32_t* item_of_block, const dim3& grid, hipStream_t stream) {
+    const dim3 block(kStepThreads, 1, 1);
+    constexpr int kMinWaves = DF ? kDfMinWaves : 1;
+    if (kind == 2) hipLaunchKernelGGL((step_batch_kernel<FMT, DF, true, 1, true>), grid, block, 0, stream, table, item_of_block);
+    else if (kind == 1) hipLaunchKernelGGL((step_batch_kernel<FMT, DF, true, kMinWaves>), grid, block, 0, stream, table, item_of_block);
+    else hipLaunchKernelGGL((step_batch_kernel<FMT, DF, false, kMinWaves>), grid, block, 0, stream, table, item_of_block);
+    return hipGetLastError();
+}
+hipError_t launch_step_batch(int variant, const StepBatchItem* table, const int32_t* item_of_block, int blocks, hipStream_t stream) {
+    if (blocks <= 0) return hipSuccess;
+    const dim3 grid((unsigned)blocks, 1, 1);
+    const int kind = variant & 3;
+    g_last_step_kernel = ILM_STEP_KERNEL_BATCH;
+    switch (variant >> 2) {
+        case 0: return launch_step_batch_variant<ILM_SDF_UNORM16, false>(kind, table, item_of_block, grid, stream);
+        case 1 + ILM_SDF_UNORM16: return launch_step_batch_variant<ILM_SDF_UNORM16, true>(kind, table, item_of_block, grid, stream);
+        case 1 + ILM_SDF_FP16: return launch_step_batch_variant<ILM_SDF_FP16, true>(kind, table, item_of_block, grid, stream);
+        case 1 + (ILM_SDF_UNORM16 | kFieldSlice0): return launch_step_batch_variant<ILM_SDF_UNORM16 | kFieldSlice0, true>(kind, table, item_of_block, grid, stream);
+        case 1 + (ILM_SDF_FP16 | kFieldSlice0): return launch_step_batch_variant<ILM_SDF_FP16 | kFieldSlice0, true>(kind, table, item_of_block, grid, stream);
+    }
+    return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------

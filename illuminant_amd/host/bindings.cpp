@@ -127,7 +127,8 @@ PYBIND11_MODULE(_host, m) {
                 throw ArgumentException("randomness table must be 653 x 807 x 4 floats");
             return new ParticleEngine(ctx, cfg, rnd.data());
         }), py::keep_alive<1, 2>())
-        .def_readonly("Configuration", &ParticleEngine::Configuration);
+        .def_readonly("Configuration", &ParticleEngine::Configuration)
+        .def("UpdateSystems", &ParticleEngine::UpdateSystems, py::arg("systems"), py::arg("frameIndex"));
 
     py::class_<BezierF>(m, "BezierF").def(py::init<>())
         .def_readwrite("Count", &BezierF::Count).def_readwrite("Mode", &BezierF::Mode)

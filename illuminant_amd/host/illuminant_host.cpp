@@ -205,6 +205,42 @@ ParticleEngine::ParticleEngine(DeviceContext& ctx, const ParticleEngineConfigura
 }
 ParticleEngine::~ParticleEngine() { if (handle) ilm_engine_destroy(handle); }
 
+void ParticleEngine::Flush() {
+    if (queuedSystems.empty()) return;
+    std::vector<IlmHandle> systems;
+    std::vector<IlmStepDesc> steps;
+    systems.swap(queuedSystems);
+    steps.swap(queuedSteps);
+    ThrowIfFailed(ilm_engine_step_batch(handle, systems.data(), steps.data(), (int32_t)systems.size()));
+}
+void ParticleEngine::FlushIfQueued(IlmHandle system) {
+    for (size_t i = 0; i < queuedSystems.size(); i++) {
+        bool touches = queuedSystems[i] == system;
+        const IlmStepDesc& d = queuedSteps[i];
+        for (int k = 0; k < d.SpawnCount && k < ILM_MAX_SPAWNS; k++)
+            touches = touches || (d.Spawns[k].Kind == ILM_SPAWN_FEEDBACK && d.Spawns[k].Feedback.SourceSystem == system);
+        if (touches) { Flush(); return; }
+    }
+}
+std::vector<UpdateResult> ParticleEngine::UpdateSystems(const std::vector<ParticleSystem*>& systems, int frameIndex) {
+    std::vector<UpdateResult> results;
+    results.reserve(systems.size());
+    deferring = true;
+    try {
+        for (ParticleSystem* s : systems) {
+            if (&s->Engine != this) throw InvalidOperationException("UpdateSystems: the system belongs to another engine");
+            results.push_back(s->Update(frameIndex));
+        }
+    } catch (...) {
+        deferring = false;
+        try { Flush(); } catch (...) { queuedSystems.clear(); queuedSteps.clear(); }
+        throw;
+    }
+    deferring = false;
+    Flush();
+    return results;
+}
+
 // ClampedBezier1(BezierF), Bezier.cs:442-460
 IlmClampedBezier1 MakeClampedBezier1(const std::optional<BezierF>& src) {
     IlmClampedBezier1 r;
@@ -640,6 +676,7 @@ void PatternSpawner::FillRecord(IlmSpawnRecord& rec, std::vector<IlmFloat4>& pos
 
 void PatternSpawner::BindResources(ParticleSystem& system, int slot) {
     if (system.PatternBound(slot, this, texVersion)) return;
+    system.BeforeSystemChange();
     ThrowIfFailed(ilm_system_set_spawn_pattern(system.Handle(), slot, texData.data(), texWidth, texHeight, texLevels));
 }
 
@@ -760,6 +797,7 @@ void ParticleSystem::UpdateLiveCountAndReapDeadChunks() {
         for (size_t i = 0; i < chunks.size(); i++)
             if (chunks[i].ID == id) {
                 // Reap, ParticleLiveness.cs:120-129
+                BeforeSystemChange();
                 ThrowIfFailed(ilm_system_remove_chunk(handle, (int32_t)i));
                 chunks.erase(chunks.begin() + (long)i);
                 if (currentSpawnTarget == id) currentSpawnTarget = -1;
@@ -899,6 +937,11 @@ void ParticleSystem::FillSystemUniforms(IlmStepDesc& d, double deltaTimeSeconds)
 
 void ParticleSystem::Launch(const IlmStepDesc& d) {
     lastStep = d;
+    if (Engine.deferring) {
+        Engine.queuedSystems.push_back(handle);
+        Engine.queuedSteps.push_back(d);
+        return;
+    }
     ThrowIfFailed(ilm_system_step(handle, &d));
 }
 
@@ -948,6 +991,7 @@ ParticleSystem::UpdateResult ParticleSystem::Update(int frameIndex) {
         e.ChunkCount = -1;
         e.UpdateMode = ILM_UPDATE_ERASE;
         if (!chunks.empty()) Launch(e);
+        BeforeSystemChange();
         while (!chunks.empty()) {
             ThrowIfFailed(ilm_system_remove_chunk(handle, (int32_t)chunks.size() - 1));
             chunks.pop_back();
@@ -979,8 +1023,10 @@ ParticleSystem::UpdateResult ParticleSystem::Update(int frameIndex) {
     // the PositionBuffer of a position-texture record is bound to the record slot it will occupy in its launch
     auto bindPositions = [&](int slot, size_t recordIndex) {
         const std::vector<IlmFloat4>& pl = recordPositions[recordIndex];
-        if (!pl.empty())
+        if (!pl.empty()) {
+            BeforeSystemChange();
             ThrowIfFailed(ilm_system_set_spawn_positions(handle, slot, pl.data(), (int32_t)pl.size()));
+        }
         recordSpawners[recordIndex]->BindResources(*this, slot);
     };
 
@@ -1007,6 +1053,7 @@ ParticleSystem::UpdateResult ParticleSystem::Update(int frameIndex) {
         // ParticleTransform.cs:144-152: only Uniforms.DistanceField is bound; DistanceFieldPacked1 is never set on the
         // particle effect in the reference and stays zero (the field collapses to its first slice).
         d.DistanceField = Configuration.Collision->Field->GetUniforms();
+        BeforeSystemChange();
         ThrowIfFailed(ilm_system_set_distance_field(handle, Configuration.Collision->Field->Texture()));
     }
 
@@ -1049,6 +1096,7 @@ ParticleSystem::UpdateResult ParticleSystem::Update(int frameIndex) {
 
     if (Configuration.AutoReadback) {     // MaybePerformReadback(timestamp), ParticleSystem.cs:625-628
         ReadbackTimestamp = (float)now;
+        Engine.Flush();
         ReadbackResult = PerformReadback();
     }
     if (computingLiveness) {

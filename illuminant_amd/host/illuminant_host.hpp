@@ -202,6 +202,9 @@ struct ParticleEngineConfiguration {
     explicit ParticleEngineConfiguration(int chunkSize = 256) : ChunkSize(chunkSize) {}
 };
 
+// UpdateResult, ParticleSystem.cs:51-71
+struct UpdateResult { bool PerformedUpdate = false; float Timestamp = 0; };
+
 // ParticleEngine.cs:24-141
 class ParticleEngine {
 public:
@@ -213,7 +216,19 @@ public:
     DeviceContext& Context;
     ParticleEngineConfiguration Configuration;
     IlmHandle Handle() const { return handle; }
+    // A frame's Update loop over the systems of this engine (Scenes/ManySystemsManySpawners.cs:78-81) as ONE ilm_engine_step_batch:
+    // each system's Update runs as usual with its launches queued here instead of issued, and the queue is submitted at the end.
+    // A call that changes what a queued launch of a system reads or what it is read through -- a position-buffer or pattern bind,
+    // the field bind, a chunk removal, a read-back -- submits the queue first (ParticleSystem::BeforeSystemChange).  The deferral
+    // does not outlive the call: an exception out of an Update submits what was queued before it propagates.
+    std::vector<UpdateResult> UpdateSystems(const std::vector<ParticleSystem*>& systems, int frameIndex);
 private:
+    friend class ParticleSystem;
+    bool deferring = false;
+    std::vector<IlmHandle> queuedSystems;
+    std::vector<IlmStepDesc> queuedSteps;
+    void Flush();
+    void FlushIfQueued(IlmHandle system);      // when a queued launch targets `system` or reads it through a feedback record
     IlmHandle handle = 0;
 };
 
@@ -536,8 +551,7 @@ public:
         std::optional<int> Count;
         int DeadFrameCount = 0;
     };
-    // UpdateResult, ParticleSystem.cs:51-71
-    struct UpdateResult { bool PerformedUpdate = false; float Timestamp = 0; };
+    using UpdateResult = Particles::UpdateResult;
 
     ParticleSystem(ParticleEngine& engine, const ParticleSystemConfiguration& configuration);
     ~ParticleSystem();
@@ -590,6 +604,8 @@ public:
     Chunk& ChunkAt(int index) { return chunks.at((size_t)index); }
     // the descriptor of the last launch (tests compare it with the oracle's step)
     const IlmStepDesc& LastStep() const { return lastStep; }
+    // before a native call that changes this system under launches ParticleEngine::UpdateSystems may still hold in its queue
+    void BeforeSystemChange() const { Engine.FlushIfQueued(handle); }
     double LastDeltaTimeSeconds = 0;
     // which pattern texture (owner, version) spawn record slot `slot` currently holds on the device; true = already bound
     bool PatternBound(int slot, const void* owner, uint64_t version) {

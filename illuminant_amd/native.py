@@ -56,6 +56,8 @@ SYMBOLS = {
     "ilm_system_set_distance_field": (_I, [_H, _H]),
     "ilm_system_set_life_ramp": (_I, [_H, _P, _I, _I]),
     "ilm_system_step": (_I, [_H, _P]),
+    "ilm_engine_step_batch": (_I, [_H, _P, _P, _I]),
+    "ilm_debug_last_step_batch": (_I, [_H, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ilm_spawn": (_I, [_H, _I, _P, _P]),
     "ilm_gravity": (_I, [_H, _I, _P, _P]),
     "ilm_noise": (_I, [_H, _I, _P, _P]),
@@ -274,6 +276,25 @@ class Engine:
         self.randomness = rnd
         self.handle = abi.Handle(0)
         check(lib().ilm_engine_create(ctx.handle, chunk_size, _ptr(rnd), rnd.shape[1], rnd.shape[0], C.byref(self.handle)))
+
+    def step_batch(self, systems, descs):
+        """ilm_engine_step_batch: systems[i].step(descs[i]) for every i, in order, with independent items sharing launches.  `descs` is a
+        sequence of abi.StepDesc or a ctypes array of them (abi.StepDesc * n, reusable from call to call)."""
+        n = len(systems)
+        assert len(descs) == n
+        handles = (abi.Handle * max(n, 1))(*[s.handle.value for s in systems])
+        if not isinstance(descs, C.Array):
+            packed = (abi.StepDesc * max(n, 1))()
+            for i, d in enumerate(descs):
+                C.memmove(C.byref(packed, i * C.sizeof(abi.StepDesc)), C.byref(d), C.sizeof(abi.StepDesc))
+            descs = packed
+        check(lib().ilm_engine_step_batch(self.handle, C.cast(handles, C.c_void_p), C.cast(descs, C.c_void_p), n))
+
+    def last_step_batch(self):
+        """ilm_debug_last_step_batch: (launches of the batch kernel, rounds, items launched one by one) of the engine's latest batch."""
+        launches, rounds, fallback = C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().ilm_debug_last_step_batch(self.handle, C.byref(launches), C.byref(rounds), C.byref(fallback)))
+        return int(launches.value), int(rounds.value), int(fallback.value)
 
     def close(self):
         if self.handle.value:

@@ -38,7 +38,7 @@ extern "C" {
  * ILM_GATHER_ASYNC + ilm_group_lightmap_wait.
  * 7 (r04): + ilm_ctx_set_light_split, ilm_sdf_mark_dirty, ilm_sdf_trace_info / IlmSdfTraceInfo; ilm_group_lightmap_set_strips became a
  * collective with one process per GPU.  Nothing was removed or changed in layout since 6. */
-#define ILM_ABI_VERSION 10
+#define ILM_ABI_VERSION 11
 
 /* ---- return codes ------------------------------------------------------ */
 #define ILM_OK                    0
@@ -435,6 +435,22 @@ int32_t ilm_system_set_spawn_pattern(IlmHandle system, int32_t spawn_slot, const
  * draw for every chunk becomes one launch. */
 int32_t ilm_system_step(IlmHandle system, const IlmStepDesc* desc);
 
+/* A frame's worth of steps in one call.  The reference's Update only builds batches inside a BatchGroup (ParticleSystem.cs:33-46,682-687)
+ * that the render coordinator issues later (UpdateHandler._BeforeDraw runs at issue time, ParticleTransform.cs:84-168), and systems do
+ * not interact apart from feedback spawners: the Update loop over the systems of an engine
+ * (Scenes/ManySystemsManySpawners.cs:41-50,78-81: 256 systems, each updated every frame) is independent work.  After the call the
+ * device memory of every system and everything the host can observe are what ilm_system_step(systems[i], &descs[i]) for
+ * i = 0 .. count - 1, in that order, would have left -- the planes bit for bit -- but independent items share launches: one per kernel
+ * variant and round, where an item runs one round after the latest earlier item that touches a system it touches (its own, or the
+ * source of a feedback record).  The same system may appear more than once; count == 0 does nothing.  All items are validated before
+ * anything is queued or changed: a refusal (a handle that is not a system, a system of another engine, or whatever ilm_system_step
+ * refuses, with its code) names the item in ilm_last_error() and leaves every system as it was.  Ranges large enough for the streaming
+ * kernels, and every item while the context's stream is being captured, are launched one by one as ilm_system_step would. */
+int32_t ilm_engine_step_batch(IlmHandle engine, const IlmHandle* systems, const IlmStepDesc* descs, int32_t count);
+/* Diagnostic: the engine's latest ilm_engine_step_batch that had items -- launches of the batch kernel, rounds, and items that were
+ * launched one by one instead.  Any out pointer may be NULL. */
+int32_t ilm_debug_last_step_batch(IlmHandle engine, int32_t* out_launches, int32_t* out_rounds, int32_t* out_fallback_items);
+
 /* Single-pass entry points, one per reference technique (LoadMaterials.cs:387-522);
  * chunk_index < 0 => every chunk.  Thin wrappers over ilm_system_step. */
 int32_t ilm_spawn  (IlmHandle system, int32_t chunk_index, const IlmParticleSystemUniforms* sys, const IlmSpawnParams* p);
@@ -512,6 +528,7 @@ int32_t ilm_debug_step_interpreter(int32_t interpreter);
 #define ILM_STEP_KERNEL_LEAN         2   /* the specialised kernel, general instantiation (cache-resident or streaming) */
 #define ILM_STEP_KERNEL_LEAN_CLAMP   3
 #define ILM_STEP_KERNEL_LEAN_DF      4   /* the specialised collision step */
+#define ILM_STEP_KERNEL_BATCH        5   /* ilm_engine_step_batch: the interpreting kernel over the items of a launch */
 int32_t ilm_debug_last_step_kernel(void);
 /* A step over at least two chunks and half a million slots puts the second half of its chunk range on a second stream of the context
  * (chunks never interact, ParticleSystem.cs:743-745; every other entry point waits for both streams before it touches anything).

@@ -1,6 +1,6 @@
 // IlluminantHip.cs -- P/Invoke layer of libilluminant_hip.so for sq/Illuminant (drop into Illuminant/Native/).
 // GENERATED from include/illuminant_hip.h by tools/gen_csharp_binding.py -- do not edit; the header carries the documentation
-// and the reference file:line each entry point replaces.  ABI version 10.
+// and the reference file:line each entry point replaces.  ABI version 11.
 //
 // Vector4 / Matrix are XNA's; LightVertex is Illuminant/Vertices.cs:10-39; the Uniforms.* structs of the reference
 // (Uniforms.cs:14-24,79-88,197-236; Bezier.cs:433-441,588-599) have the byte layout of the Ilm* mirrors below and can be passed
@@ -16,7 +16,7 @@ namespace Squared.Illuminant.Native {
     }
 
     public static class IlmConstants {
-        public const int ABI_VERSION = 10;
+        public const int ABI_VERSION = 11;
         public const int BLEND_FP16_PER_LIGHT = 1;
         public const int BLEND_FP32_ACCUMULATE = 0;
         public const int ERR_INVALID_ARGUMENT = -1;
@@ -33,6 +33,7 @@ namespace Squared.Illuminant.Native {
         public const int RANDOMNESS_HEIGHT = 653;
         public const int RANDOMNESS_WIDTH = 807;
         public const int STEP_COUNT_LIVE = 1;
+        public const int STEP_KERNEL_BATCH = 5;
         public const int STEP_KERNEL_INTERPRETER = 1;
         public const int STEP_KERNEL_LEAN = 2;
         public const int STEP_KERNEL_LEAN_CLAMP = 3;
@@ -530,6 +531,8 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_set_spawn_positions (ulong system, int spawnSlot, Vector4* positions, int count);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_set_spawn_pattern (ulong system, int spawnSlot, Vector4* texels, int width, int height, int levels);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_step (ulong system, IlmStepDesc* desc);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_engine_step_batch (ulong engine, ulong* systems, IlmStepDesc* descs, int count);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_last_step_batch (ulong engine, int* outLaunches, int* outRounds, int* outFallbackItems);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_spawn (ulong system, int chunkIndex, IlmParticleSystemUniforms* sys, IlmSpawnParams* p);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_gravity (ulong system, int chunkIndex, IlmParticleSystemUniforms* sys, IlmGravityParams* p);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_noise (ulong system, int chunkIndex, IlmParticleSystemUniforms* sys, IlmNoiseParams* p);
