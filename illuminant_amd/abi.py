@@ -327,6 +327,20 @@ class HistogramResult(C.Structure):
                 ("Min", f32), ("Max", f32), ("Mean", f32), ("Median", f32), ("Sum", f32)]
 
 
+VISUALIZE_SURFACES, VISUALIZE_OUTLINES, VISUALIZE_SILHOUETTES = 0, 1, 2    # VisualizationMode, LightingRenderer.cs:2055-2059
+
+
+class VisualizeVertex(C.Structure):
+    """VisualizeDistanceFieldVertex, Illuminant/Vertices.cs:143-148"""
+    _fields_ = [("Position", f32 * 3), ("RayStart", f32 * 3), ("RayVector", f32 * 3), ("Color", f32 * 4)]
+
+
+class VisualizeParams(C.Structure):
+    _fields_ = [("Mode", i32), ("BlendMode", i32), ("OutlineSize", f32), ("_pad0", f32),
+                ("AmbientColor", f32 * 3), ("_pad1", f32), ("LightDirection", f32 * 3), ("_pad2", f32), ("LightColor", f32 * 3), ("_pad3", f32),
+                ("ViewportScale", f32 * 2), ("ViewportPosition", f32 * 2)]
+
+
 # expected sizes (bytes) -- checked against the C header in tests
 EXPECTED_SIZES = {
     "IlmFloat4": (Float4, 16), "IlmMatrix": (Matrix, 64),
@@ -349,4 +363,5 @@ EXPECTED_SIZES = {
     "IlmHeightVolumeVertex": (HeightVolumeVertex, 36), "IlmBillboardVertex": (BillboardVertex, 48),
     "IlmBillboardRun": (BillboardRun, 24), "IlmGBufferMeshDesc": (GBufferMeshDesc, 64),
     "IlmHistogramBucket": (HistogramBucket, 16), "IlmHistogramParams": (HistogramParams, 24), "IlmHistogramResult": (HistogramResult, 36),
+    "IlmVisualizeVertex": (VisualizeVertex, 52), "IlmVisualizeParams": (VisualizeParams, 80),
 }

@@ -3526,6 +3526,112 @@ int32_t ilm_render_particles(IlmHandle hsystem, const int32_t* quad_counts, int3
     return ILM_OK;
 }
 
+namespace {
+// What ilm_visualize_distance_field judges about its vertex and parameter values alone -- no object is needed, so this runs before any
+// handle is looked up -- and the two values the kernel takes from the uniform RayVector: rayLength and rayDirection (traceSurface /
+// traceOutlines, VisualizeCommon.fxh:73-74,108-109), rounded once, here.  traceSurface's max(0.001, length) is the identity on the
+// admitted lengths.
+int32_t check_visualize_arguments(const IlmVisualizeVertex* quad, const IlmVisualizeParams* p, float* ray_length, float ray_direction[3]) {
+    if (!quad || !p) return fail(ILM_ERR_INVALID_ARGUMENT, "quad or params is NULL");
+    static const char* const corner[4] = { "TL", "TR", "BR", "BL" };
+    for (int i = 0; i < 4; i++) {
+        const IlmVisualizeVertex& v = quad[i];
+        const float values[13] = { v.Position[0], v.Position[1], v.Position[2], v.RayStart[0], v.RayStart[1], v.RayStart[2],
+                                   v.RayVector[0], v.RayVector[1], v.RayVector[2], v.Color[0], v.Color[1], v.Color[2], v.Color[3] };
+        for (int k = 0; k < 13; k++)
+            if (!std::isfinite(values[k]))
+                return fail(ILM_ERR_INVALID_ARGUMENT, "vertex %s holds a value that is not finite (%g)", corner[i], (double)values[k]);
+    }
+    const float params[14] = { p->OutlineSize, p->AmbientColor[0], p->AmbientColor[1], p->AmbientColor[2], p->LightDirection[0], p->LightDirection[1],
+                               p->LightDirection[2], p->LightColor[0], p->LightColor[1], p->LightColor[2], p->ViewportScale[0], p->ViewportScale[1],
+                               p->ViewportPosition[0], p->ViewportPosition[1] };
+    for (int k = 0; k < 14; k++)
+        if (!std::isfinite(params[k])) return fail(ILM_ERR_INVALID_ARGUMENT, "a parameter value is not finite (%g)", (double)params[k]);
+    if (p->Mode < ILM_VISUALIZE_SURFACES || p->Mode > ILM_VISUALIZE_SILHOUETTES) return fail(ILM_ERR_INVALID_ARGUMENT, "unknown visualization mode %d", p->Mode);
+    if (p->BlendMode != ILM_BLEND_ALPHA && p->BlendMode != ILM_BLEND_ADDITIVE) return fail(ILM_ERR_INVALID_ARGUMENT, "unknown blend mode %d", p->BlendMode);
+    if (p->Mode != ILM_VISUALIZE_SURFACES && !(p->OutlineSize >= 1.0f))
+        return fail(ILM_ERR_INVALID_ARGUMENT, "OutlineSize %g < 1 (the reference binds Math.Max(outlineSize, 1))", (double)p->OutlineSize);
+    for (int i = 1; i < 4; i++) {
+        for (int k = 0; k < 3; k++)
+            if (quad[i].RayVector[k] != quad[0].RayVector[k]) return fail(ILM_ERR_INVALID_ARGUMENT, "RayVector of vertex %s differs from vertex TL's", corner[i]);
+        for (int k = 0; k < 4; k++)
+            if (quad[i].Color[k] != quad[0].Color[k]) return fail(ILM_ERR_INVALID_ARGUMENT, "Color of vertex %s differs from vertex TL's", corner[i]);
+    }
+    const bool rectangle = quad[0].Position[1] == quad[1].Position[1] && quad[3].Position[1] == quad[2].Position[1] &&
+                           quad[0].Position[0] == quad[3].Position[0] && quad[1].Position[0] == quad[2].Position[0] &&
+                           quad[0].Position[0] <= quad[1].Position[0] && quad[0].Position[1] <= quad[3].Position[1];
+    if (!rectangle) return fail(ILM_ERR_INVALID_ARGUMENT, "the Positions are not an axis-aligned rectangle in TL, TR, BR, BL order");
+    const float* r = quad[0].RayVector;
+    const float length = sqrtf(((r[0] * r[0]) + (r[1] * r[1])) + (r[2] * r[2]));
+    if (!(length >= 1e-3f && length <= 65536.0f))
+        return fail(ILM_ERR_INVALID_ARGUMENT, "|RayVector| = %g outside [1e-3, 65536] (the bound of the trace loop's trip count)", (double)length);
+    *ray_length = length;
+    for (int k = 0; k < 3; k++) ray_direction[k] = r[k] / length;
+    return ILM_OK;
+}
+}  // namespace
+
+int32_t ilm_visualize_distance_field(IlmHandle hctx, IlmHandle hsdf, const IlmDistanceFieldUniforms* df, const IlmVisualizeVertex quad[4],
+                                     const IlmVisualizeParams* params, IlmHandle htarget, uint64_t* out_stats) {
+    ILM_TRACE_RANGE("ilm_visualize_distance_field");
+    VisualizeLaunch a;
+    std::memset(&a, 0, sizeof(a));
+    { const int32_t rc = check_visualize_arguments(quad, params, &a.ray_length, a.ray_direction); if (rc != ILM_OK) return rc; }
+    if (!df) return fail(ILM_ERR_INVALID_ARGUMENT, "df is NULL");
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    if (!hsdf) return fail(ILM_ERR_STATE, "no distance field to visualize (LightingRenderer.cs:1713 returns Failed)");
+    Sdf* f = from_handle<Sdf>(hsdf, kMagicSdf);
+    if (!f) return fail(ILM_ERR_INVALID_HANDLE, "not a distance field handle");
+    Lightmap* m = from_handle<Lightmap>(htarget, kMagicLightmap);
+    if (!m) return fail(ILM_ERR_INVALID_HANDLE, "target is not a lightmap handle");
+    // (the target is written: the context's own; the field is read: the context's or a sibling's, as in ilm_render_sphere_lights)
+    if (m->ctx != c) return fail(ILM_ERR_INVALID_ARGUMENT, "context and target belong to different contexts");
+    if (!siblings(f->ctx, c)) return fail(ILM_ERR_INVALID_ARGUMENT, "resources belong to another context");
+    { char why[256]; if (field_uniforms_mismatch(f, df, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
+    if ((m->width + 15) / 16 > 65535 || (m->height + 15) / 16 > 65535) return fail(ILM_ERR_OUT_OF_RANGE, "target too large");
+    // the quad's rectangle in pixels (the header defines the arithmetic) and the pixels of the target it can cover
+    const IlmVisualizeParams& p = *params;
+    a.px0 = (quad[0].Position[0] - p.ViewportPosition[0]) * p.ViewportScale[0];
+    a.px1 = (quad[1].Position[0] - p.ViewportPosition[0]) * p.ViewportScale[0];
+    a.py0 = (quad[0].Position[1] - p.ViewportPosition[1]) * p.ViewportScale[1];
+    a.py1 = (quad[3].Position[1] - p.ViewportPosition[1]) * p.ViewportScale[1];
+    if (!std::isfinite(a.px0) || !std::isfinite(a.px1) || !std::isfinite(a.py0) || !std::isfinite(a.py1))
+        return fail(ILM_ERR_INVALID_ARGUMENT, "the quad's rectangle in pixels is not finite");
+    a.span_x = a.px1 - a.px0; a.span_y = a.py1 - a.py0;
+    // i + 0.5 >= p0  <=>  i >= ceil(p0 - 0.5);  i + 0.5 < p1  <=>  i < ceil(p1 - 0.5): exact in double for a float p; the kernel decides
+    auto first = [](float p0, int n) { return (int)std::min(std::max(std::floor((double)p0 - 0.5), 0.0), (double)n); };
+    auto end = [](float p1, int n) { return (int)std::min(std::max(std::ceil((double)p1 - 0.5), 0.0), (double)n); };
+    a.x0 = first(a.px0, m->width); a.x1 = end(a.px1, m->width);
+    a.y0 = first(a.py0, m->height); a.y1 = end(a.py1, m->height);
+    if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = 0;
+    if (a.x0 >= a.x1 || a.y0 >= a.y1) return ILM_OK;             // an empty rectangle, or one that misses the target
+    a.sdf = make_sdf_view(f, df);
+    a.df = *df;
+    a.target = m->texels; a.format = m->format; a.width = m->width; a.height = m->height;
+    for (int i = 0; i < 4; i++)
+        for (int k = 0; k < 3; k++) a.ray_start[i][k] = quad[i].RayStart[k];
+    for (int k = 0; k < 4; k++) a.color[k] = quad[0].Color[k];
+    for (int k = 0; k < 3; k++) { a.ambient_color[k] = p.AmbientColor[k]; a.light_direction[k] = p.LightDirection[k]; a.light_color[k] = p.LightColor[k]; }
+    a.outline_size = p.OutlineSize;
+    a.mode = p.Mode; a.blend_mode = p.BlendMode;
+    HIP_TRY(hipSetDevice(c->device));
+    if (f->ctx != c) HIP_TRY(shared_before_read(f->shared, f->ctx, c));      // a sibling's field: behind everything its owner has queued
+    if (out_stats) {
+        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
+        a.stats = c->d_stats;
+    }
+    HIP_TRY(launch_visualize(a, c->main()));
+    HIP_TRY(light_pass_queued(c, f, nullptr));
+    if (out_stats) {
+        unsigned long long host[3] = { 0, 0, 0 };
+        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
+        HIP_TRY(hipStreamSynchronize(c->main()));
+        out_stats[0] = host[0]; out_stats[1] = host[1]; out_stats[2] = host[2];
+    }
+    return ILM_OK;
+}
+
 int32_t ilm_resolve_lighting(IlmHandle hsrc, IlmHandle hdst, const IlmHDRConfiguration* hdr, int32_t row_begin, int32_t row_end) {
     ILM_TRACE_RANGE("ilm_resolve_lighting");
     return ilm_resolve_lighting_with_albedo(hsrc, 0, hdst, hdr, row_begin, row_end);

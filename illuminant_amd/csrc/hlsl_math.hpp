@@ -491,4 +491,52 @@ ILM_DEV float sample_inside_table(f3 position, const InsideConsts& c, const Trac
     return (kDistanceZero - blended) * c.max_distance;      // fma(x, maxDistance, +0): the distance to the volume is +0 inside it
 }
 
+// estimateNormal4, VisualizeCommon.fxh:44-63 (the collision update's bounce normal and the distance-field view's shading normal).  FMT: bit 0
+// the atlas format; bits 1 and 2 select the particle path's slice-0 samplers (particles.hip), 0 elsewhere.
+template <int FMT>
+ILM_DEV f3 estimate_normal4(f3 position, const IlmDistanceFieldUniforms& df, const SdfView& sdf) {
+#pragma clang fp contract(off)
+    const f3 texel = mk3(df.ConeAndMisc.w, df.StepAndMisc2.w, df.Extent.z / fmaxf(df.TextureSliceCount.w, 1.0f));
+    f3 result = mk3(0.0f, 0.0f, 0.0f);
+    const float W[4][3] = { { 1, -1, -1 }, { -1, -1, 1 }, { -1, 1, -1 }, { 1, 1, 1 } };
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const f3 w = mk3(W[i][0], W[i][1], W[i][2]);
+        const float s = sample_distance_field<(FMT & 1), true, (FMT & 2) != 0, (FMT & 4) != 0>(position + (w * texel), df, sdf);
+        result = result + (w * s);
+    }
+    return norm3(result);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Render targets (lightmap objects): one texel in fp32 whatever the storage format -- the particle rasteriser and the
+// distance-field view load, blend and store through these.
+// ---------------------------------------------------------------------------------------------
+template <int FORMAT>
+ILM_DEV float4 load_target(const void* texels, size_t o) {
+    if (FORMAT == ILM_LIGHTMAP_FLOAT4) return reinterpret_cast<const float4*>(texels)[o];
+    if (FORMAT == ILM_LIGHTMAP_HALF4) {
+        const uint2 v = reinterpret_cast<const uint2*>(texels)[o];
+        return mk4(__half2float(__ushort_as_half((unsigned short)(v.x & 0xFFFFu))), __half2float(__ushort_as_half((unsigned short)(v.x >> 16))),
+                   __half2float(__ushort_as_half((unsigned short)(v.y & 0xFFFFu))), __half2float(__ushort_as_half((unsigned short)(v.y >> 16))));
+    }
+    const uint32_t v = reinterpret_cast<const uint32_t*>(texels)[o];
+    return mk4((float)(v & 255u) / 255.0f, (float)((v >> 8) & 255u) / 255.0f, (float)((v >> 16) & 255u) / 255.0f, (float)(v >> 24) / 255.0f);
+}
+template <int FORMAT>
+ILM_DEV void store_target(void* texels, size_t o, float4 c) {
+    if (FORMAT == ILM_LIGHTMAP_FLOAT4) {
+        reinterpret_cast<float4*>(texels)[o] = c;
+    } else if (FORMAT == ILM_LIGHTMAP_HALF4) {
+        uint2 v;
+        v.x = (uint32_t)__half_as_ushort(__float2half_rn(c.x)) | ((uint32_t)__half_as_ushort(__float2half_rn(c.y)) << 16);
+        v.y = (uint32_t)__half_as_ushort(__float2half_rn(c.z)) | ((uint32_t)__half_as_ushort(__float2half_rn(c.w)) << 16);
+        reinterpret_cast<uint2*>(texels)[o] = v;
+    } else {
+        const uint32_t r = (uint32_t)rintf(sat(c.x) * 255.0f), g = (uint32_t)rintf(sat(c.y) * 255.0f);
+        const uint32_t b = (uint32_t)rintf(sat(c.z) * 255.0f), al = (uint32_t)rintf(sat(c.w) * 255.0f);
+        reinterpret_cast<uint32_t*>(texels)[o] = r | (g << 8) | (b << 16) | (al << 24);
+    }
+}
+
 }  // namespace ilm

@@ -431,6 +431,24 @@ hipError_t render_particles(RasterLaunch& a, RasterScratch& s, hipStream_t strea
 void free_raster_scratch(RasterScratch& s);
 hipError_t launch_clear_target(void* texels, int format, size_t n, float4 color, hipStream_t stream);
 
+// ---- distance-field views (visualize.hip) -----------------------------------------------------------------------
+struct VisualizeLaunch {
+    SdfView sdf;
+    IlmDistanceFieldUniforms df;
+    void* target; int32_t format, width, height;
+    int32_t x0, y0, x1, y1;             // pixels [x0, x1) x [y0, y1): a superset of the covered ones, inside the target (coverage is decided per pixel)
+    int32_t tile_x0, tile_y0;           // origin of the grid's first tile (filled by launch_visualize)
+    float px0, py0, px1, py1;           // the quad's rectangle in pixels
+    float span_x, span_y;               // px1 - px0, py1 - py0
+    float ray_start[4][3];              // TL, TR, BR, BL
+    float ray_direction[3], ray_length; // RayVector / |RayVector| and |RayVector|, rounded once on the host (api.hip)
+    float color[4], ambient_color[3], light_direction[3], light_color[3];
+    float outline_size;
+    int32_t mode, blend_mode;           // ILM_VISUALIZE_*, ILM_BLEND_ALPHA / ILM_BLEND_ADDITIVE
+    unsigned long long* stats;          // device, zeroed: [0] covered pixels, [1] pixels drawn, [2] SDF samples; nullptr => the instantiation without counters
+};
+hipError_t launch_visualize(const VisualizeLaunch& a, hipStream_t stream);
+
 // ---- shared with group.hip (the multi-device layer sits on the C ABI of api.hip, inside the same library) -------------------------
 // thread-local error text + return code, as every entry point reports failures
 int32_t api_fail(int32_t code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));

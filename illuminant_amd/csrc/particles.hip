@@ -740,22 +740,6 @@ ILM_DEV void update_positions_select(float4& pos, float4& vel, const IlmParticle
 __device__ unsigned long long g_step_sdf_samples;
 __device__ int g_step_count_sdf_samples;
 
-// estimateNormal4, VisualizeCommon.fxh:44-63
-template <int FMT>
-ILM_DEV f3 estimate_normal4(f3 position, const IlmDistanceFieldUniforms& df, const SdfView& sdf) {
-#pragma clang fp contract(off)
-    const f3 texel = mk3(df.ConeAndMisc.w, df.StepAndMisc2.w, df.Extent.z / fmaxf(df.TextureSliceCount.w, 1.0f));
-    f3 result = mk3(0.0f, 0.0f, 0.0f);
-    const float W[4][3] = { { 1, -1, -1 }, { -1, -1, 1 }, { -1, 1, -1 }, { 1, 1, 1 } };
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const f3 w = mk3(W[i][0], W[i][1], W[i][2]);
-        const float s = sample_distance_field<(FMT & 1), true, (FMT & 2) != 0, (FMT & 4) != 0>(position + (w * texel), df, sdf);
-        result = result + (w * s);
-    }
-    return norm3(result);
-}
-
 // PS_Update, UpdateParticleSystemWithDistanceField.fx:29-147, behind its first lookup: the sweep and the bounce / redirect / escape
 // arithmetic for a live slot whose life does not run out in this step, given initial_distance (the field at the particle) and, when
 // `first_done`, the lookup of the sweep's first iteration (step_distance0) too.  The only statement of them: the interpreter comes

@@ -131,33 +131,6 @@ __global__ __launch_bounds__(256) void raster_emit_kernel(const RasterLaunch a) 
             *out++ = ((unsigned long long)(ty * (uint32_t)a.tiles_x + tx) << 32) | (unsigned long long)(uint32_t)g;
 }
 
-template <int FORMAT>
-ILM_DEV float4 load_target(const void* texels, size_t o) {
-    if (FORMAT == ILM_LIGHTMAP_FLOAT4) return reinterpret_cast<const float4*>(texels)[o];
-    if (FORMAT == ILM_LIGHTMAP_HALF4) {
-        const uint2 v = reinterpret_cast<const uint2*>(texels)[o];
-        return mk4(__half2float(__ushort_as_half((unsigned short)(v.x & 0xFFFFu))), __half2float(__ushort_as_half((unsigned short)(v.x >> 16))),
-                   __half2float(__ushort_as_half((unsigned short)(v.y & 0xFFFFu))), __half2float(__ushort_as_half((unsigned short)(v.y >> 16))));
-    }
-    const uint32_t v = reinterpret_cast<const uint32_t*>(texels)[o];
-    return mk4((float)(v & 255u) / 255.0f, (float)((v >> 8) & 255u) / 255.0f, (float)((v >> 16) & 255u) / 255.0f, (float)(v >> 24) / 255.0f);
-}
-template <int FORMAT>
-ILM_DEV void store_target(void* texels, size_t o, float4 c) {
-    if (FORMAT == ILM_LIGHTMAP_FLOAT4) {
-        reinterpret_cast<float4*>(texels)[o] = c;
-    } else if (FORMAT == ILM_LIGHTMAP_HALF4) {
-        uint2 v;
-        v.x = (uint32_t)__half_as_ushort(__float2half_rn(c.x)) | ((uint32_t)__half_as_ushort(__float2half_rn(c.y)) << 16);
-        v.y = (uint32_t)__half_as_ushort(__float2half_rn(c.z)) | ((uint32_t)__half_as_ushort(__float2half_rn(c.w)) << 16);
-        reinterpret_cast<uint2*>(texels)[o] = v;
-    } else {
-        const uint32_t r = (uint32_t)rintf(sat(c.x) * 255.0f), g = (uint32_t)rintf(sat(c.y) * 255.0f);
-        const uint32_t b = (uint32_t)rintf(sat(c.z) * 255.0f), al = (uint32_t)rintf(sat(c.w) * 255.0f);
-        reinterpret_cast<uint32_t*>(texels)[o] = r | (g << 8) | (b << 16) | (al << 24);
-    }
-}
-
 // tex2D on a bitmap without mips: BitmapPointSampler (POINT, CLAMP) or BitmapSampler (LINEAR, CLAMP), texel centres at + 0.5
 ILM_DEV float4 bitmap_fetch(const float4* __restrict__ tex, int w, int h, float u, float v, int filter) {
     if (filter == ILM_BITMAP_POINT) {

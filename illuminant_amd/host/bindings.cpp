@@ -52,6 +52,7 @@ PYBIND11_MODULE(_host, m) {
         .def(py::init<DeviceContext&, int, int, int>(), py::arg("ctx"), py::arg("width"), py::arg("height"), py::arg("format") = (int)ILM_LIGHTMAP_FLOAT4,
              py::keep_alive<1, 2>())
         .def_readonly("Width", &RenderTarget::Width).def_readonly("Height", &RenderTarget::Height).def_readonly("Format", &RenderTarget::Format)
+        .def_property_readonly("Handle", &RenderTarget::Handle)
         .def("Clear", [](RenderTarget& t, const std::vector<float>& c) { t.Clear(Vector4{ c.at(0), c.at(1), c.at(2), c.at(3) }); })
         // (height, width, 4) float32 for a float4 target; raw bytes reshaped by the caller otherwise
         .def("Download", [](const RenderTarget& t) {
@@ -513,6 +514,10 @@ PYBIND11_MODULE(_host, m) {
             IlmHistogramResult r;
             h.Update(lightmap, renderWidth, renderHeight, accuracyFactor, scaleFactor, &r);
             return py::bytes((const char*)&r, sizeof(r)); });
+    py::class_<VisualizationInfo>(m, "VisualizationInfo")
+        .def_readonly("Failed", &VisualizationInfo::Failed)
+        VEC_PROP(VisualizationInfo, ViewCenter, 3) VEC_PROP(VisualizationInfo, Up, 3) VEC_PROP(VisualizationInfo, Right, 3)
+        VEC_PROP(VisualizationInfo, ViewDirection, 3);
     py::class_<LightingRenderer>(m, "LightingRenderer")
         .def(py::init([](DeviceContext& ctx, const RendererConfiguration& cfg, LightingEnvironment* env, uintptr_t externalLightmap) {
             return new LightingRenderer(ctx, cfg, env, reinterpret_cast<void*>(externalLightmap));
@@ -609,6 +614,38 @@ PYBIND11_MODULE(_host, m) {
         }, py::arg("firstRow") = 0, py::arg("rowCount") = -1)
         .def_property_readonly("LightmapHandle", &LightingRenderer::Lightmap)
         .def("TryComputeHistogram", &LightingRenderer::TryComputeHistogram, py::arg("histogram"), py::arg("accuracyFactor") = 3)
+        // rectangle = (left, top, right, bottom); returns (VisualizationInfo, stats tuple or None)
+        .def("VisualizeDistanceField", [](LightingRenderer& r, IlmHandle target, const std::vector<float>& rectangle, const std::vector<float>& viewDirection,
+                                          int mode, int blendMode, py::object color, py::object ambientColor, py::object lightColor, py::object lightDirection,
+                                          py::object worldBounds, float outlineSize, const std::vector<float>& viewportPosition,
+                                          const std::vector<float>& viewportScale, bool wantStats) {
+            VisualizationOptions o;
+            o.Mode = (VisualizationMode)mode; o.BlendMode = blendMode; o.OutlineSize = outlineSize;
+            if (!color.is_none()) o.Color = v4(color.cast<std::vector<float>>());
+            if (!ambientColor.is_none()) o.AmbientColor = v3(ambientColor.cast<std::vector<float>>());
+            if (!lightColor.is_none()) o.LightColor = v3(lightColor.cast<std::vector<float>>());
+            if (!lightDirection.is_none()) o.LightDirection = v3(lightDirection.cast<std::vector<float>>());
+            if (!worldBounds.is_none()) {
+                const auto b = worldBounds.cast<std::vector<float>>();
+                o.WorldBounds = Bounds3{ Vector3{ b.at(0), b.at(1), b.at(2) }, Vector3{ b.at(3), b.at(4), b.at(5) } };
+            }
+            o.ViewportPosition = v2(viewportPosition); o.ViewportScale = v2(viewportScale);
+            uint64_t stats[3] = { 0, 0, 0 };
+            const VisualizationInfo info = r.VisualizeDistanceField(target, Bounds{ Vector2{ rectangle.at(0), rectangle.at(1) }, Vector2{ rectangle.at(2), rectangle.at(3) } },
+                                                                    v3(viewDirection), o, wantStats ? stats : nullptr);
+            return py::make_tuple(info, (wantStats && !info.Failed) ? py::object(py::make_tuple(stats[0], stats[1], stats[2])) : py::object(py::none())); },
+             py::arg("target"), py::arg("rectangle"), py::arg("viewDirection"), py::arg("mode") = 0, py::arg("blendMode") = (int)ILM_BLEND_ALPHA,
+             py::arg("color") = py::none(), py::arg("ambientColor") = py::none(), py::arg("lightColor") = py::none(), py::arg("lightDirection") = py::none(),
+             py::arg("worldBounds") = py::none(), py::arg("outlineSize") = 1.8f, py::arg("viewportPosition") = std::vector<float>{ 0, 0 },
+             py::arg("viewportScale") = std::vector<float>{ 1, 1 }, py::arg("wantStats") = false)
+        // the quad of VisualizeDistanceField on its own (no device): (VisualizationInfo, the four IlmVisualizeVertex as bytes)
+        .def_static("BuildVisualizationQuad", [](const std::vector<float>& rectangle, const std::vector<float>& viewDirection, const std::vector<float>& worldMin,
+                                                 const std::vector<float>& worldMax, const std::vector<float>& color) {
+            IlmVisualizeVertex vertices[4];
+            std::memset(vertices, 0, sizeof(vertices));
+            const VisualizationInfo info = LightingRenderer::BuildVisualizationQuad(
+                Bounds{ Vector2{ rectangle.at(0), rectangle.at(1) }, Vector2{ rectangle.at(2), rectangle.at(3) } }, v3(viewDirection), v3(worldMin), v3(worldMax), v4(color), vertices);
+            return py::make_tuple(info, py::bytes((const char*)vertices, sizeof(vertices))); })
         .def_property_readonly("LightmapFormat", &LightingRenderer::LightmapFormat)
         .def("GetDistanceFieldUniformsBytes", [](const LightingRenderer& r) {
             auto u = r.GetDistanceFieldUniforms(r.Configuration.DefaultQuality); return py::bytes((const char*)&u, sizeof(u)); })

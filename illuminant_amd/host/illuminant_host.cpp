@@ -1474,6 +1474,134 @@ void LightingRenderer::UpdateLightProbes(float intensityScale) {
     }
 }
 
+// ---- VisualizeDistanceField, LightingRenderer.cs:1647-1892 --------------------------------------------------------------------
+namespace {
+// XNA / FNA's Vector3 and Ray members are outside the reference tree: restated from the functions FNA publishes, in float with one
+// rounding per operation.
+Vector3 Add(Vector3 a, Vector3 b) { return { a.X + b.X, a.Y + b.Y, a.Z + b.Z }; }
+Vector3 Sub(Vector3 a, Vector3 b) { return { a.X - b.X, a.Y - b.Y, a.Z - b.Z }; }
+Vector3 Mul(Vector3 a, Vector3 b) { return { a.X * b.X, a.Y * b.Y, a.Z * b.Z }; }
+Vector3 Scale(Vector3 a, float s) { return { a.X * s, a.Y * s, a.Z * s }; }
+Vector3 Negate(Vector3 a) { return { -a.X, -a.Y, -a.Z }; }
+float Dot(Vector3 a, Vector3 b) { return (a.X * b.X) + (a.Y * b.Y) + (a.Z * b.Z); }
+float Length(Vector3 a) { return std::sqrt((a.X * a.X) + (a.Y * a.Y) + (a.Z * a.Z)); }
+Vector3 Normalized(Vector3 a) { const float factor = 1.0f / Length(a); return Scale(a, factor); }      // Vector3.Normalize: 1 / sqrt, then three products
+Vector3 Cross(Vector3 a, Vector3 b) {
+    return { (a.Y * b.Z) - (b.Y * a.Z), -((a.X * b.Z) - (b.X * a.Z)), (a.X * b.Y) - (b.X * a.Y) };
+}
+float Lerp(float a, float b, float t) { return a + ((b - a) * t); }       // MathHelper.Lerp
+float AbsSign(float v) { return (v > 0 || v < 0) ? 1.0f : 0.0f; }           // Math.Abs(Math.Sign(v)) of a finite v
+
+// Ray.Intersects(Plane) -- a restatement of the function FNA publishes (Plane(normal, d): dot(normal, p) + d = 0):
+// |den| < 1e-5: null; t = (-D - dot(Normal, Position)) / den; t < -1e-5: null; a negative t above that becomes 0.
+std::optional<float> RayIntersectsPlane(Vector3 position, Vector3 direction, Vector3 normal, float d) {
+    const float den = Dot(direction, normal);
+    if (std::fabs(den) < 0.00001f) return std::nullopt;
+    float t = (-d - Dot(normal, position)) / den;
+    if (t < 0.0f) {
+        if (t < -0.00001f) return std::nullopt;
+        t = 0.0f;
+    }
+    return t;
+}
+}  // namespace
+
+std::optional<Vector3> LightingRenderer::FindBoxIntersection(Vector3 rayPosition, Vector3 rayDirection, Vector3 boxMin, Vector3 boxMax) {
+    float minDistance = 999999;
+    std::optional<Vector3> result;
+    for (int i = 0; i < 6; i++) {
+        Vector3 normal; float d;
+        switch (i) {
+            case 0: normal = { 1, 0, 0 }; d = boxMin.X; break;
+            case 1: normal = { 0, 1, 0 }; d = boxMin.X; break;      // (boxMin.X: as written, :1667)
+            case 2: normal = { 0, 0, 1 }; d = boxMin.X; break;      // (boxMin.X: as written, :1670)
+            case 3: normal = { -1, 0, 0 }; d = boxMax.X; break;
+            case 4: normal = { 0, -1, 0 }; d = boxMax.Y; break;
+            default: normal = { 0, 0, -1 }; d = boxMax.Z; break;
+        }
+        const std::optional<float> intersection = RayIntersectsPlane(rayPosition, rayDirection, normal, d);
+        if (!intersection) continue;
+        if (*intersection > minDistance) continue;
+        minDistance = *intersection;
+        result = Add(rayPosition, Scale(rayDirection, *intersection));
+    }
+    return result;
+}
+
+VisualizationInfo LightingRenderer::BuildVisualizationQuad(Bounds rectangle, Vector3 viewDirection, Vector3 worldMin, Vector3 worldMax, Vector4 color,
+                                                           IlmVisualizeVertex vertices[4]) {
+    viewDirection = Normalized(viewDirection);
+    const Vector3 tl{ rectangle.TopLeft.X, rectangle.TopLeft.Y, 0 }, tr{ rectangle.BottomRight.X, rectangle.TopLeft.Y, 0 };
+    const Vector3 bl{ rectangle.TopLeft.X, rectangle.BottomRight.Y, 0 }, br{ rectangle.BottomRight.X, rectangle.BottomRight.Y, 0 };
+    const Vector3 extent = Sub(worldMax, worldMin);
+    Vector3 center = Scale(Add(worldMin, worldMax), 1 / 2.0f);
+    const Vector3 centerMask{ AbsSign(viewDirection.X), AbsSign(viewDirection.Y), AbsSign(viewDirection.Z) };
+    const Vector3 halfDisplaySize{ Lerp(extent.X / 2.0f, 0, centerMask.X), Lerp(extent.Y / 2.0f, 0, centerMask.Y), Lerp(extent.Z / 2.0f, 0, centerMask.Z) };
+    center = { Lerp(center.X, worldMin.X, centerMask.X), Lerp(center.Y, worldMin.Y, centerMask.Y), Lerp(center.Z, worldMin.Z, centerMask.Z) };
+    const Vector2 size{ rectangle.BottomRight.X - rectangle.TopLeft.X, rectangle.BottomRight.Y - rectangle.TopLeft.Y };
+    const Vector3 halfTexel{ -0.5f * (1.0f / size.X), -0.5f * (1.0f / size.Y), 0 };
+    // HACK: Pick an appropriate length that will always travel through the whole field
+    const float rayLength = Length(extent) * 2.0f;
+    const Vector3 rayVector = Scale(viewDirection, rayLength);
+    const Vector3 up = (viewDirection.Z != 0) ? Vector3{ 0, -1, 0 } : Vector3{ 0, 0, 1 };
+    const Vector3 right = (viewDirection.X != 0) ? Vector3{ 0, 1, 0 } : Vector3{ 1, 0, 0 };
+    VisualizationInfo info;
+    // HACK: Place our view plane somewhere reasonable
+    const std::optional<Vector3> planeCenter = FindBoxIntersection(center, Negate(viewDirection), worldMin, worldMax);
+    if (!planeCenter) {
+        info.Failed = true; info.Right = right; info.Up = up; info.ViewDirection = viewDirection;
+        return info;
+    }
+    const Vector3 rayOrigin = Sub(*planeCenter, viewDirection);
+    const Vector3 absViewDirection{ std::fabs(viewDirection.X), std::fabs(viewDirection.Y), std::fabs(viewDirection.Z) };
+    const Vector3 planeRight = Cross(absViewDirection, up), planeUp = Cross(absViewDirection, right);
+    const Vector3 r = Mul(planeRight, halfDisplaySize), u = Mul(planeUp, halfDisplaySize);
+    const Vector3 nr = Mul(Negate(planeRight), halfDisplaySize), nu = Mul(Negate(planeUp), halfDisplaySize);
+    const Vector3 worldTL = Add(Add(rayOrigin, nr), nu), worldTR = Add(Add(rayOrigin, r), nu);
+    const Vector3 worldBL = Add(Add(rayOrigin, nr), u), worldBR = Add(Add(rayOrigin, r), u);
+    const Vector3 positions[4] = { Add(tl, halfTexel), Add(tr, halfTexel), Add(br, halfTexel), Add(bl, halfTexel) };
+    const Vector3 starts[4] = { worldTL, worldTR, worldBR, worldBL };
+    for (int i = 0; i < 4; i++) {
+        IlmVisualizeVertex& v = vertices[i];
+        v.Position[0] = positions[i].X; v.Position[1] = positions[i].Y; v.Position[2] = positions[i].Z;
+        v.RayStart[0] = starts[i].X; v.RayStart[1] = starts[i].Y; v.RayStart[2] = starts[i].Z;
+        v.RayVector[0] = rayVector.X; v.RayVector[1] = rayVector.Y; v.RayVector[2] = rayVector.Z;
+        v.Color[0] = color.X; v.Color[1] = color.Y; v.Color[2] = color.Z; v.Color[3] = color.W;
+    }
+    info.ViewCenter = rayOrigin; info.Up = planeUp; info.Right = planeRight; info.ViewDirection = viewDirection;
+    return info;
+}
+
+VisualizationInfo LightingRenderer::VisualizeDistanceField(IlmHandle target, Bounds rectangle, Vector3 viewDirection, const VisualizationOptions& options,
+                                                           uint64_t* stats) {
+    if (!Field) {
+        VisualizationInfo failed;
+        failed.Failed = true;
+        return failed;
+    }
+    const Vector3 worldMin = options.WorldBounds ? options.WorldBounds->Minimum : Vector3{ 0, 0, 0 };
+    const Vector3 worldMax = options.WorldBounds ? options.WorldBounds->Maximum
+                                                 : Vector3{ (float)Field->VirtualWidth, (float)Field->VirtualHeight, Field->VirtualDepth };
+    IlmVisualizeVertex vertices[4];
+    const VisualizationInfo info = BuildVisualizationQuad(rectangle, viewDirection, worldMin, worldMax, options.Color.value_or(Vector4{ 1, 1, 1, 1 }), vertices);
+    if (info.Failed) return info;
+    IlmVisualizeParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.Mode = (int32_t)options.Mode; p.BlendMode = options.BlendMode;
+    p.OutlineSize = std::max(options.OutlineSize, 1.0f);                                     // :1877
+    const Vector3 ac = options.AmbientColor.value_or(Vector3{ 0.1f, 0.15f, 0.15f });           // :1860
+    const Vector3 ld = Normalized(options.LightDirection.value_or(Vector3{ 0, -0.5f, -1.0f }));   // :1863-1864
+    const Vector3 lc = options.LightColor.value_or(Vector3{ 0.75f, 0.75f, 0.75f });            // :1867
+    p.AmbientColor[0] = ac.X; p.AmbientColor[1] = ac.Y; p.AmbientColor[2] = ac.Z;
+    p.LightDirection[0] = ld.X; p.LightDirection[1] = ld.Y; p.LightDirection[2] = ld.Z;
+    p.LightColor[0] = lc.X; p.LightColor[1] = lc.Y; p.LightColor[2] = lc.Z;
+    p.ViewportScale[0] = options.ViewportScale.X; p.ViewportScale[1] = options.ViewportScale.Y;
+    p.ViewportPosition[0] = options.ViewportPosition.X; p.ViewportPosition[1] = options.ViewportPosition.Y;
+    const IlmDistanceFieldUniforms dfu = GetDistanceFieldUniforms(Configuration.DefaultQuality);      // SetDistanceFieldParameters, :1858
+    ThrowIfFailed(ilm_visualize_distance_field(Context.Handle(), Field->Texture(), &dfu, vertices, &p, target, stats));
+    return info;
+}
+
 // RenderedLighting.TryComputeHistogram, LightingRenderer.HDR.cs:154-183: LuminanceBuffer is null without EnableBrightnessEstimation (:989)
 bool LightingRenderer::TryComputeHistogram(Histogram& histogram, int accuracyFactor) {
     if (!Configuration.EnableBrightnessEstimation || lastInverseScaleFactor == 0)

@@ -848,6 +848,25 @@ struct RendererConfiguration {
     RendererConfiguration(int w, int h) : RenderWidth(w), RenderHeight(h) {}
 };
 
+// VisualizationMode / VisualizationInfo, LightingRenderer.cs:2055-2071; Bounds (Squared.Game: TopLeft, BottomRight) and Bounds3
+enum class VisualizationMode { Surfaces = 0, Outlines = 1, Silhouettes = 2 };
+struct VisualizationInfo {
+    bool Failed = false;
+    Vector3 ViewCenter, Up, Right, ViewDirection;
+};
+struct Bounds { Vector2 TopLeft, BottomRight; };
+struct Bounds3 { Vector3 Minimum, Maximum; };
+// what VisualizeDistanceField leaves to default arguments (:1703-1711) and the view transform of the target
+struct VisualizationOptions {
+    VisualizationMode Mode = VisualizationMode::Surfaces;
+    int BlendMode = ILM_BLEND_ALPHA;                 // blendState ?? BlendState.AlphaBlend
+    std::optional<Vector4> Color;                    // Vector4.One
+    std::optional<Vector3> AmbientColor, LightColor, LightDirection;      // (0.1, 0.15, 0.15), (0.75, 0.75, 0.75), (0, -0.5, -1)
+    std::optional<Bounds3> WorldBounds;              // the field's virtual size
+    float OutlineSize = 1.8f;
+    Vector2 ViewportPosition{0, 0}, ViewportScale{1, 1};
+};
+
 // LightingRenderer.cs (RenderLighting path only)
 class LightingRenderer {
 public:
@@ -892,6 +911,17 @@ public:
     // RenderLighting (LightingRenderer.cs:963-966).  Synchronous, like the probes' read-back (the reference completes a frame later and
     // reads the PREVIOUS lightmap, :987-1001; here it is the frame just rendered).
     bool TryComputeHistogram(Histogram& histogram, int accuracyFactor = 3);
+
+    // VisualizeDistanceField, :1699-1892, without the single-object techniques (ilm_visualize_distance_field says why): the view of
+    // the field along viewDirection, ray-marched per pixel of `rectangle` onto `target` (a lightmap handle of this context).
+    // Failed without a field (:1713) or when the view plane cannot be placed (:1786-1787).  stats: ilm_visualize_distance_field's.
+    VisualizationInfo VisualizeDistanceField(IlmHandle target, Bounds rectangle, Vector3 viewDirection, const VisualizationOptions& options = {},
+                                             uint64_t* stats = nullptr);
+    // :1718-1833 on their own (no device): the view-plane placement and the quad's four vertices, TL, TR, BR, BL
+    static VisualizationInfo BuildVisualizationQuad(Bounds rectangle, Vector3 viewDirection, Vector3 worldMin, Vector3 worldMax, Vector4 color,
+                                                    IlmVisualizeVertex vertices[4]);
+    // FindBoxIntersection, :1656-1697 (its boxMin.X planes as written)
+    static std::optional<Vector3> FindBoxIntersection(Vector3 rayPosition, Vector3 rayDirection, Vector3 boxMin, Vector3 boxMax);
 
     // _ParticleLightBatchSetup, :769-790
     static IlmParticleLightParams PackParticleLight(const ParticleLightSource& pls, bool haveDistanceField);

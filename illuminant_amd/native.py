@@ -116,6 +116,7 @@ SYMBOLS = {
     "ilm_lightmap_luminance": (_I, [_H, _I, _I, _I, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ilm_lightmap_histogram": (_I, [_H, _P, _P, _P, _P]),
     "ilm_debug_queue_luminance": (_I, [_H, _I, _I, _I]),
+    "ilm_visualize_distance_field": (_I, [_H, _H, _P, _P, _P, _H, _P]),
     "ilm_group_create": (_I, [_P, _I, C.POINTER(_H)]),
     "ilm_group_unique_id": (_I, [_P]),
     "ilm_group_create_rank": (_I, [_I, _I, _I, _P, C.POINTER(_H)]),
@@ -834,6 +835,16 @@ def render_particles(system, params, target, quad_counts=None, chunk_count=None,
     stats = (C.c_uint64 * 3)() if want_stats else None
     check(lib().ilm_render_particles(system.handle, _ptr(q) if q is not None else None, chunk_count, _byref(params), target.handle,
                                      C.cast(stats, C.c_void_p) if stats is not None else None))
+    return tuple(int(x) for x in stats) if want_stats else None
+
+
+def visualize_distance_field(ctx, sdf, df, quad, params, target, want_stats=False):
+    """ilm_visualize_distance_field: sphere-traces the field `sdf` per pixel of the quad (ctypes array of four abi.VisualizeVertex:
+    TL, TR, BR, BL) and blends the view onto the lightmap `target`.  Returns (covered pixels, pixels drawn, SDF samples) when want_stats."""
+    stats = (C.c_uint64 * 3)() if want_stats else None
+    check(lib().ilm_visualize_distance_field(ctx.handle, sdf.handle if sdf is not None else abi.Handle(0), _byref(df),
+                                             C.cast(quad, C.c_void_p) if quad is not None else None, _byref(params), target.handle,
+                                             C.cast(stats, C.c_void_p) if stats is not None else None))
     return tuple(int(x) for x in stats) if want_stats else None
 
 

@@ -30,7 +30,9 @@
 extern "C" {
 #endif
 
-/* 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
+/* 11: + ilm_engine_step_batch, ilm_debug_last_step_batch, ILM_STEP_KERNEL_BATCH; later, under the same number (no layout changed, nothing
+ * removed): + ilm_visualize_distance_field / IlmVisualizeVertex, IlmVisualizeParams, ILM_VISUALIZE_* (distance-field views).
+ * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
  * and RenderColor for particle lights across ranks).  Nothing removed or changed in layout.
@@ -1000,6 +1002,61 @@ int32_t ilm_lightmap_histogram(IlmHandle lightmap, const IlmHistogramParams* par
 /* Measurement hook (tools/brightness_time.py): queues the luminance pass of the two calls above on the context's stream and returns --
  * nothing is read back, nothing synchronises.  Same refusals. */
 int32_t ilm_debug_queue_luminance(IlmHandle lightmap, int32_t render_width, int32_t render_height, int32_t accuracy_factor);
+
+/* ---- distance-field views (the reference's debug view of a field) ----------------------------------------------------------
+ *
+ * LightingRenderer.VisualizeDistanceField (Illuminant/Lighting/LightingRenderer.cs:1699-1892) draws one quad and sphere-traces the field
+ * per pixel: techniques ObjectSurfaces / ObjectOutlines (Illuminant/Shaders/VisualizeDistanceField.fx:40-100, traceSurface / traceOutlines /
+ * estimateNormal4 of VisualizeCommon.fxh:47-133).  One launch here, onto a lightmap object used as the render target (any format), blended
+ * like ilm_render_particles; the field is read where it lies -- a host no longer downloads the atlas to look at it.
+ *
+ * The quad: four vertices in the order TL, TR, BR, BL (:1808-1833) whose Positions are an axis-aligned rectangle; RayVector and Color
+ * are the same in all four (the reference gives them the same); Position.z is ignored (VisualizeVertexShader writes z = 0).  What the
+ * reference leaves to the rasteriser is defined here, in fp32 with one rounding per operation in the order written:
+ *     px0 = (quad[0].Position.x - ViewportPosition.x) * ViewportScale.x, px1 the same from quad[1]; py0 from quad[0].Position.y, py1 from
+ *     quad[3].Position.y; pixel (i, j) is covered iff px0 <= i + 0.5 < px1 and py0 <= j + 0.5 < py1 (the top-left rule), pixels outside
+ *     the target are clipped;  u = ((i + 0.5) - px0) / (px1 - px0), v likewise;
+ *     top = TL + (TR - TL) * u, bottom = BL + (BR - BL) * u, rayStart = top + (bottom - top) * v on the RayStart components
+ * (for the reference's parallelogram, :1801-1804, this is barycentric interpolation up to rounding).  An empty rectangle draws nothing.
+ * rayLength = sqrt((x x + y y) + z z) of RayVector and rayDirection = RayVector / rayLength are computed once by the call, on the host.
+ *
+ * The pixel: ILM_VISUALIZE_SURFACES is ObjectSurfacesPixelShader (TRACE_MIN_STEP_SIZE 2, TRACE_FINAL_MIN_STEP_SIZE 12; a hit is
+ * AmbientColor + LightColor * clamp((dot(estimateNormal4, LightDirection) + 0.05) * 1.1, 0, 1) * Color.rgb with alpha 1, a miss is
+ * discarded), ILM_VISUALIZE_OUTLINES is ObjectOutlinesPixelShader with FilledInterior = 0, ILM_VISUALIZE_SILHOUETTES with FilledInterior = 1
+ * (:1878; a ray that never meets distance <= 1 still gets the outline alpha of its closest distance); alpha <= 0 is discarded.  HLSL's
+ * min / max are fminf / fmaxf.  Discarded and uncovered pixels keep their bits; the others are blended, ILM_BLEND_ALPHA (the reference's
+ * default, :1851) dst = src + dst * (1 - src.a) or ILM_BLEND_ADDITIVE dst = src + dst.
+ * The trace loops end: every iteration adds at least 2 to the position along the ray and rayLength is at most 65536 -- at most 32 769
+ * iterations, whatever the field holds (the kernel carries an iteration cap just above that, which can never change a result).
+ *
+ * Refused with ILM_ERR_INVALID_ARGUMENT, nothing queued or written: Positions that are not an axis-aligned rectangle in TL, TR, BR, BL
+ * order; a RayVector or Color that differs between vertices; a vertex or parameter value that is not finite; |RayVector| outside
+ * [1e-3, 65536]; an unknown Mode or BlendMode; OutlineSize below 1 (or NaN) in the outline modes (the reference binds
+ * Math.Max(outlineSize, 1), :1877); distance-field uniforms ilm_render_sphere_lights would refuse.  The vertex and parameter values are
+ * judged before any handle is looked up (they need no object), so a host can learn them without a device.  Then: ctx, sdf != 0 and target
+ * must be live handles (ILM_ERR_INVALID_HANDLE); sdf == 0 is ILM_ERR_STATE (the reference returns Failed without a field, :1713); the
+ * target must belong to ctx (ILM_ERR_INVALID_ARGUMENT, as ilm_render_particles); the field may be ctx's or a sibling context's, ordered
+ * against its owner's writes as ilm_render_sphere_lights orders it.  Asynchronous on ctx's stream unless out_stats is given.
+ * out_stats (may be NULL): [0] covered pixels, [1] pixels drawn (not discarded), [2] sampleDistanceFieldEx calls (the trace's, plus the
+ * normal's four per surface hit).
+ *
+ * Not built: the single-object techniques FunctionSurface / FunctionOutline (VisualizeDistanceFunction.fx).  The reference binds a float
+ * angle (singleObject.Rotation ?? 0, :1874) to FunctionRotation and hands it to evaluateByTypeId, whose rotation parameter is a
+ * quaternion float4 (DistanceFunctionCommon.fxh:167-169): what that computes is not defined by the text.  Refused rather than guessed.
+ *
+ * (The two structs below are untagged typedefs; tests/test_visualize_kat.py holds their layout to the ctypes mirrors.) */
+/* VisualizeDistanceFieldVertex, Vertices.cs:143-148 (Sequential, Pack = 4: 52 bytes) */
+typedef struct { float Position[3], RayStart[3], RayVector[3], Color[4]; } IlmVisualizeVertex;
+enum { ILM_VISUALIZE_SURFACES = 0, ILM_VISUALIZE_OUTLINES = 1, ILM_VISUALIZE_SILHOUETTES = 2 };  /* VisualizationMode, LightingRenderer.cs:2055-2059 */
+typedef struct {
+    int32_t Mode, BlendMode;            /* ILM_VISUALIZE_*, ILM_BLEND_ALPHA (the reference's default) / ILM_BLEND_ADDITIVE */
+    float   OutlineSize, _pad0;         /* Math.Max(outlineSize, 1), LightingRenderer.cs:1877; read in the outline modes only */
+    float   AmbientColor[3], _pad1, LightDirection[3], _pad2, LightColor[3], _pad3;   /* :1860-1868; the host normalises the direction */
+    float   ViewportScale[2], ViewportPosition[2];   /* as IlmRasterizeParams: pixel = (Position.xy - ViewportPosition) * ViewportScale */
+} IlmVisualizeParams;
+int32_t ilm_visualize_distance_field(IlmHandle ctx, IlmHandle sdf, const IlmDistanceFieldUniforms* df,
+                                     const IlmVisualizeVertex quad[4] /* TL, TR, BR, BL */, const IlmVisualizeParams* params,
+                                     IlmHandle target, uint64_t* out_stats /* may be NULL: [0] covered pixels, [1] pixels drawn, [2] SDF samples */);
 
 /* ---- multi-device groups (SURVEY 8e / 8b "ilm_ctx_create(device_ids, n)") --------------------------------------------------------
  *

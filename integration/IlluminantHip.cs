@@ -80,6 +80,9 @@ namespace Squared.Illuminant.Native {
         public const int BITMAP_NONE = 0;
         public const int BITMAP_POINT = 1;
         public const int BITMAP_LINEAR = 2;
+        public const int VISUALIZE_SURFACES = 0;
+        public const int VISUALIZE_OUTLINES = 1;
+        public const int VISUALIZE_SILHOUETTES = 2;
         public const int GATHER_NONE = 0;
         public const int GATHER_PEER = 1;
         public const int GATHER_RCCL = 2;
@@ -500,6 +503,30 @@ namespace Squared.Illuminant.Native {
         public float Sum;
     }
 
+    [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 52)]
+    public unsafe struct IlmVisualizeVertex {
+        public fixed float Position[3];
+        public fixed float RayStart[3];
+        public fixed float RayVector[3];
+        public fixed float Color[4];
+    }
+
+    [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 80)]
+    public unsafe struct IlmVisualizeParams {
+        public int Mode;
+        public int BlendMode;
+        public float OutlineSize;
+        public float _pad0;
+        public fixed float AmbientColor[3];
+        public float _pad1;
+        public fixed float LightDirection[3];
+        public float _pad2;
+        public fixed float LightColor[3];
+        public float _pad3;
+        public fixed float ViewportScale[2];
+        public fixed float ViewportPosition[2];
+    }
+
     internal static unsafe class IlluminantHip {
         const string Lib = "illuminant_hip";             // libilluminant_hip.so next to the game's assemblies
 
@@ -589,6 +616,7 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_luminance (ulong lightmap, int renderWidth, int renderHeight, int accuracyFactor, float* outValues, int capacity, int* outLevel, int* outWidth, int* outHeight);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_histogram (ulong lightmap, IlmHistogramParams* @params, float* bucketMaxValues, IlmHistogramBucket* outBuckets, IlmHistogramResult* @out);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_queue_luminance (ulong lightmap, int renderWidth, int renderHeight, int accuracyFactor);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_visualize_distance_field (ulong ctx, ulong sdf, IlmDistanceFieldUniforms* df, IlmVisualizeVertex* quad, IlmVisualizeParams* @params, ulong target, ulong* outStats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_group_create (int* deviceIds, int n, ulong* outGroup);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_group_unique_id (void* outId128);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_group_create_rank (int deviceId, int rank, int world, void* id128, ulong* outGroup);
