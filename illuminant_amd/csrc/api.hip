@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <array>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -89,33 +90,37 @@ struct Ctx {
     }
     hipEvent_t t0 = nullptr, t1 = nullptr;
     // device staging for AoS <-> SoA conversion
-    void* staging = nullptr; size_t staging_bytes = 0;
+    DeviceScratch staging;
     // pinned ring for small asynchronous parameter uploads (light arrays)
     static constexpr int kRing = 4;
     void* pinned[kRing] = {}; size_t pinned_bytes[kRing] = {}; hipEvent_t pinned_ev[kRing] = {}; int ring_pos = 0;
-    void* d_recs = nullptr; int light_cap = 0;      // prepared light records (kLightRecBytes each) of the last light or probe call
+    DeviceScratch d_recs;                           // prepared light records (kLightRecBytes each) of the last light or probe call
     unsigned long long* d_stats = nullptr;
     // light split (plan_light_split): the tiles' per-part sums and their tickets
     int last_light_blocks = 0, last_light_split = 1, last_light_macro = 0;       // the last tile-kernel launch (ilm_debug_last_light_launch)
-    float4* d_light_partials = nullptr; size_t light_partials_tiles = 0; uint32_t* d_light_tickets = nullptr; size_t light_tickets_cap = 0;
+    DeviceScratch d_light_partials, d_light_tickets;
     int light_split = 0;                  // ilm_ctx_set_light_split: 0 = chosen per launch, else 1 / 2 / 4 / 8
-    uint16_t* d_group_order = nullptr; int group_order_cap = 0; uint64_t group_order_key = 0; int group_order_groups = 0;
+    DeviceScratch d_group_order; uint64_t group_order_key = 0; int group_order_groups = 0;
     // particle lights: records compacted on the device + their count, block counts, per-chunk quad counts
-    void* d_pl_recs = nullptr; int pl_cap = 0; int32_t* d_pl_count = nullptr; int32_t* d_pl_blocks = nullptr; int pl_blocks_cap = 0;
-    int32_t* d_pl_quads = nullptr; int pl_quads_cap = 0;
+    DeviceScratch d_pl_recs, d_pl_count, d_pl_blocks, d_pl_quads;
     float4* d_light_ramp = nullptr; int light_ramp_w = 0, light_ramp_h = 0;    // RampTexture of the light group being rendered
     int lightmap_blend = 0;               // ILM_BLEND_FP32_ACCUMULATE / ILM_BLEND_FP16_PER_LIGHT (ilm_ctx_set_lightmap_blend)
     RasterScratch raster;                                         // particle rasteriser buffers (raster.hip)
-    int32_t* d_raster_quads = nullptr; int raster_quads_cap = 0;
+    DeviceScratch d_raster_quads;
     // particle read-back: draw-call records, total, block counts, per-chunk element counts
-    IlmReadbackDrawCall* d_rb = nullptr; int rb_cap = 0; int32_t* d_rb_count = nullptr; int32_t* d_rb_blocks = nullptr; int rb_blocks_cap = 0;
-    int32_t* d_rb_elems = nullptr; int rb_elems_cap = 0;
+    DeviceScratch d_rb, d_rb_count, d_rb_blocks, d_rb_elems;
     IlmReadbackDrawCall* h_rb = nullptr; size_t h_rb_cap = 0;    // pinned host buffer the read-back records land in
     // light probes
-    float4* d_probe_pairs = nullptr; size_t probe_pairs_cap = 0;   // one contribution per (light, probe)
+    DeviceScratch d_probe_pairs;                                   // one contribution per (light, probe)
     BrightnessScratch brightness;                                  // brightness estimation: the luminance level and the statistics' scratch (brightness.hip)
     // parameter block of the distance-field generation pass (slice list, obstruction records, volumes, polygon vertices)
-    void* d_field_params = nullptr; size_t field_params_bytes = 0;
+    DeviceScratch d_field_params;
+    // every block `reserve` grows: what ilm_ctx_destroy frees
+    std::array<DeviceScratch*, 20> scratch() {
+        return { &staging, &d_recs, &d_light_partials, &d_light_tickets, &d_group_order, &d_pl_recs, &d_pl_count, &d_pl_blocks, &d_pl_quads,
+                 &d_raster_quads, &d_rb, &d_rb_count, &d_rb_blocks, &d_rb_elems, &d_probe_pairs, &brightness.level, &brightness.mip,
+                 &brightness.work, &brightness.partials, &d_field_params };
+    }
 };
 
 struct Engine {
@@ -274,7 +279,7 @@ struct System {
     std::vector<uint8_t> ptr_out;
     RenderKey render_key; uint64_t render_key_gen = 0;
     bool render_captured = false;
-    float** d_table = nullptr; int table_cap = 0; bool table_dirty = true;
+    DeviceScratch d_table; bool table_dirty = true;       // float* per chunk
     // Five counter regions of 64-bit words.  Regions 0-3 belong to the step kernels, kCountLines lines per chunk (internal.hpp),
     // index = parity * 2 + half: a counting launch of half h accumulates into (parity, h) and zeroes (parity ^ 1, h) for the next
     // counting step -- no memset launch, and the two halves of a split step (run_step), which run on different streams, never touch
@@ -287,9 +292,9 @@ struct System {
     int split_at = -1;
     IlmHandle sdf_handle = 0;   // bound distance field: resolved through the handle table at every use (it may have been destroyed)
     float4* ramp = nullptr; int ramp_w = 0, ramp_h = 0;
-    uint32_t* d_slots = nullptr; int slots_cap = 0; uint32_t* d_slot_count = nullptr;
+    DeviceScratch d_slots, d_slot_count;
     // the Spawner's PositionBuffer per spawn record slot (ParticleSpawner.cs:301-353)
-    float4* spawn_positions[ILM_MAX_SPAWNS] = {}; int spawn_position_count[ILM_MAX_SPAWNS] = {}; int spawn_position_cap[ILM_MAX_SPAWNS] = {};
+    DeviceScratch spawn_positions[ILM_MAX_SPAWNS]; int spawn_position_count[ILM_MAX_SPAWNS] = {};
     float4* bitmap = nullptr; int bitmap_w = 0, bitmap_h = 0;     // Appearance.Texture for the textured rasterise techniques
     // the PatternSpawner's texture per spawn record slot, mip levels back to back (SpecialSpawners.cs:19-22)
     float4* spawn_pattern[ILM_MAX_SPAWNS] = {}; int pattern_w[ILM_MAX_SPAWNS] = {}, pattern_h[ILM_MAX_SPAWNS] = {}, pattern_levels[ILM_MAX_SPAWNS] = {};
@@ -507,19 +512,44 @@ size_t lightmap_texel_bytes(int format) {
     return format == ILM_LIGHTMAP_FLOAT4 ? 16 : (format == ILM_LIGHTMAP_HALF4 ? 8 : 4);
 }
 
-int32_t ensure_staging(Ctx* c, size_t bytes) {
-    if (bytes <= c->staging_bytes)
-        return ILM_OK;
-    if (c->staging) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        HIP_TRY(hipFree(c->staging));
-        c->staging = nullptr; c->staging_bytes = 0;
+// Room for `need` bytes in `s`.  Nothing when it fits.  Otherwise an old block is freed once the context's stream has drained (a queued
+// kernel may still read it; a first allocation has no reader to wait for), pointer and size are cleared BEFORE the allocation -- a
+// failure leaves an empty block, never a stale size -- and `want` (>= need: the caller's growth rule) bytes are allocated.
+// try_reserve is for callers that go on without the block: it hands the error back with the runtime's error state cleared.
+hipError_t try_reserve(Ctx* c, DeviceScratch& s, size_t need, size_t want) {
+    if (need <= s.bytes) return hipSuccess;
+    if (s.p) {
+        hipError_t e = hipStreamSynchronize(c->main());
+        if (e == hipSuccess) e = hipFree(s.p);
+        if (e != hipSuccess) return e;
     }
-    size_t cap = bytes < (1u << 20) ? (1u << 20) : bytes;
-    HIP_TRY(hipMalloc(&c->staging, cap));
-    c->staging_bytes = cap;
+    s.p = nullptr; s.bytes = 0;
+    const hipError_t e = hipMalloc(&s.p, want);
+    if (e != hipSuccess) { (void)hipGetLastError(); s.p = nullptr; return e; }
+    s.bytes = want;
+    return hipSuccess;
+}
+int32_t reserve(Ctx* c, DeviceScratch& s, size_t need, size_t want) {
+    const hipError_t e = try_reserve(c, s, need, want);
+    if (e != hipSuccess) return fail((int32_t)e, "device scratch of %zu bytes: %s", want, hipGetErrorString(e));
     return ILM_OK;
 }
+void release(DeviceScratch& s) {
+    if (s.p) (void)hipFree(s.p);
+    s = DeviceScratch();
+}
+inline size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
+
+// the parameter block shared by distance-field generation and the two G-buffer passes: 64 KiB at first, then twice what is asked for
+int32_t reserve_field_params(Ctx* c, size_t total) { return reserve(c, c->d_field_params, total, total < 65536 ? 65536 : total * 2); }
+// every height volume names vertices inside the polygon array (ilm_sdf_render_slices, ilm_gbuffer_render)
+int32_t check_volume_ranges(const IlmHeightVolume* volumes, int32_t volume_count, int32_t polygon_vertex_count) {
+    for (int i = 0; i < volume_count; i++)
+        if (volumes[i].FirstVertex < 0 || volumes[i].VertexCount < 0 || volumes[i].FirstVertex + volumes[i].VertexCount > polygon_vertex_count)
+            return fail(ILM_ERR_OUT_OF_RANGE, "height volume %d vertex range outside the polygon array", i);
+    return ILM_OK;
+}
+int32_t ensure_staging(Ctx* c, size_t bytes) { return reserve(c, c->staging, bytes, std::max<size_t>(bytes, (size_t)1 << 20)); }
 
 // the next slot of the pinned ring, free and at least `bytes` large: the caller fills *host and calls upload_small_commit
 int32_t upload_small_begin(Ctx* c, size_t bytes, void** host, int* slot_out) {
@@ -579,24 +609,13 @@ int32_t upload_small(Ctx* c, void* dst, const void* src, size_t bytes) {
 // kernel that reads it on the context stream and then calls staged_small_done.  One device operation (and one dependent-launch gap)
 // less than upload_small + kernel: the lights of a frame are read once, by the one kernel that digests them.
 int32_t stage_small(Ctx* c, const void* src, size_t bytes, const void** device_visible, int* slot_out) {
-    const int slot = c->ring_pos;
-    c->ring_pos = (c->ring_pos + 1) % Ctx::kRing;
-    if (c->pinned_ev[slot] == nullptr)
-        HIP_TRY(hipEventCreateWithFlags(&c->pinned_ev[slot], hipEventDisableTiming));
-    else
-        HIP_TRY(hipEventSynchronize(c->pinned_ev[slot]));
-    if (c->pinned_bytes[slot] < bytes) {
-        if (c->pinned[slot]) HIP_TRY(hipHostFree(c->pinned[slot]));
-        c->pinned[slot] = nullptr; c->pinned_bytes[slot] = 0;
-        size_t cap = bytes < 65536 ? 65536 : bytes;
-        HIP_TRY(hipHostMalloc(&c->pinned[slot], cap, hipHostMallocDefault));
-        c->pinned_bytes[slot] = cap;
-    }
-    memcpy(c->pinned[slot], src, bytes);
+    void* host = nullptr;
+    const int32_t rc = upload_small_begin(c, bytes, &host, slot_out);
+    if (rc != ILM_OK) return rc;
+    memcpy(host, src, bytes);
     void* dev = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&dev, c->pinned[slot], 0));
+    HIP_TRY(hipHostGetDevicePointer(&dev, host, 0));
     *device_visible = dev;
-    *slot_out = slot;
     return ILM_OK;
 }
 int32_t staged_small_done(Ctx* c, int slot) {
@@ -607,11 +626,9 @@ int32_t staged_small_done(Ctx* c, int slot) {
 int32_t refresh_table(System* s) {
     Ctx* c = s->engine->ctx;
     const int n = (int)s->chunks.size();
-    if (n > s->table_cap) {
-        if (s->d_table) { HIP_TRY(hipStreamSynchronize(c->main())); HIP_TRY(hipFree(s->d_table)); s->d_table = nullptr; }
-        int cap = n < 64 ? 64 : n * 2;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_table), sizeof(float*) * (size_t)cap));
-        s->table_cap = cap;
+    if (sizeof(float*) * (size_t)n > s->d_table.bytes) {
+        const int32_t rc = reserve(c, s->d_table, sizeof(float*) * (size_t)n, sizeof(float*) * (size_t)(n < 64 ? 64 : n * 2));
+        if (rc != ILM_OK) return rc;
         s->table_dirty = true;
     }
     if (n > s->counts_cap) {
@@ -631,7 +648,7 @@ int32_t refresh_table(System* s) {
         s->counts_cap = cap;
     }
     if (s->table_dirty && n > 0) {
-        int32_t rc = upload_small(c, s->d_table, s->chunks.data(), sizeof(float*) * (size_t)n);
+        int32_t rc = upload_small(c, s->d_table.p, s->chunks.data(), sizeof(float*) * (size_t)n);
         if (rc != ILM_OK) return rc;
     }
     s->table_dirty = false;
@@ -1001,7 +1018,7 @@ static int32_t prepare_step(System* s, const IlmStepDesc* d, StepLaunch& a, int*
     const int region = s->count_parity;
 
     memcpy(&a.desc, d, sizeof(IlmStepDesc));
-    a.chunk_bases = s->d_table;
+    a.chunk_bases = s->d_table.as<float*>();
     a.stride = e->stride;
     a.span = e->span;
     a.chunk_size = e->chunk_size;
@@ -1022,7 +1039,7 @@ static int32_t prepare_step(System* s, const IlmStepDesc* d, StepLaunch& a, int*
     a.rnd = e->rnd; a.rw = e->rw; a.rh = e->rh;
     a.rnd_lp = e->rnd_lp;
     for (int k = 0; k < ILM_MAX_SPAWNS; k++) {
-        a.spawn_positions[k] = s->spawn_positions[k];
+        a.spawn_positions[k] = s->spawn_positions[k].as<float4>();
         a.spawn_position_count[k] = s->spawn_position_count[k];
         a.source_base[k] = nullptr;
         a.spawn_pattern[k] = s->spawn_pattern[k];
@@ -1605,33 +1622,14 @@ int32_t ilm_ctx_destroy(IlmHandle h) {
     (void)hipSetDevice(c->device);
     if (c->aux) (void)hipStreamSynchronize(c->aux);
     if (c->stream_) (void)hipStreamSynchronize(c->stream_);
-    if (c->staging) (void)hipFree(c->staging);
+    for (DeviceScratch* s : c->scratch()) release(*s);
     for (int i = 0; i < Ctx::kRing; i++) {
         if (c->pinned[i]) (void)hipHostFree(c->pinned[i]);
         if (c->pinned_ev[i]) (void)hipEventDestroy(c->pinned_ev[i]);
     }
-    if (c->d_recs) (void)hipFree(c->d_recs);
     if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->d_light_partials) (void)hipFree(c->d_light_partials);
-    if (c->d_light_tickets) (void)hipFree(c->d_light_tickets);
-    if (c->d_group_order) (void)hipFree(c->d_group_order);
-    if (c->d_field_params) (void)hipFree(c->d_field_params);
-    if (c->d_pl_recs) (void)hipFree(c->d_pl_recs);
-    if (c->d_pl_count) (void)hipFree(c->d_pl_count);
-    if (c->d_pl_blocks) (void)hipFree(c->d_pl_blocks);
-    if (c->d_pl_quads) (void)hipFree(c->d_pl_quads);
     free_raster_scratch(c->raster);
     if (c->d_light_ramp) (void)hipFree(c->d_light_ramp);
-    if (c->d_raster_quads) (void)hipFree(c->d_raster_quads);
-    if (c->d_probe_pairs) (void)hipFree(c->d_probe_pairs);
-    if (c->brightness.level) (void)hipFree(c->brightness.level);
-    if (c->brightness.mip) (void)hipFree(c->brightness.mip);
-    if (c->brightness.work) (void)hipFree(c->brightness.work);
-    if (c->brightness.partials) (void)hipFree(c->brightness.partials);
-    if (c->d_rb) (void)hipFree(c->d_rb);
-    if (c->d_rb_count) (void)hipFree(c->d_rb_count);
-    if (c->d_rb_blocks) (void)hipFree(c->d_rb_blocks);
-    if (c->d_rb_elems) (void)hipFree(c->d_rb_elems);
     if (c->h_rb) (void)hipHostFree(c->h_rb);
     // (a context whose creation failed half-way has null members here)
     if (c->t0) (void)hipEventDestroy(c->t0);
@@ -1800,13 +1798,10 @@ int32_t ilm_system_destroy(IlmHandle h) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->main());
     for (float* p : s->chunks) release_chunk(s->engine, p);
-    if (s->d_table) (void)hipFree(s->d_table);
+    for (DeviceScratch* b : { &s->d_table, &s->d_slots, &s->d_slot_count }) release(*b);
+    for (DeviceScratch& b : s->spawn_positions) release(b);
     if (s->d_counts) (void)hipFree(s->d_counts);
     if (s->ramp) (void)hipFree(s->ramp);
-    if (s->d_slots) (void)hipFree(s->d_slots);
-    if (s->d_slot_count) (void)hipFree(s->d_slot_count);
-    for (int k = 0; k < ILM_MAX_SPAWNS; k++)
-        if (s->spawn_positions[k]) (void)hipFree(s->spawn_positions[k]);
     for (int k = 0; k < ILM_MAX_SPAWNS; k++)
         if (s->spawn_pattern[k]) (void)hipFree(s->spawn_pattern[k]);
     if (s->bitmap) (void)hipFree(s->bitmap);
@@ -1878,10 +1873,10 @@ int32_t ilm_chunk_upload(IlmHandle h, int32_t chunk, int32_t plane, const IlmFlo
     const size_t bytes = sizeof(float4) * (size_t)count;
     rc = ensure_staging(c, bytes);
     if (rc != ILM_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->staging, src, bytes, hipMemcpyHostToDevice, c->main()));
+    HIP_TRY(hipMemcpyAsync(c->staging.p, src, bytes, hipMemcpyHostToDevice, c->main()));
     s->used[(size_t)chunk] = std::max(s->used[(size_t)chunk], first_slot + count);
     s->render_gen[(size_t)chunk] = 0;
-    HIP_TRY(launch_aos_to_soa(reinterpret_cast<const float4*>(c->staging), s->chunks[(size_t)chunk] + (int64_t)plane * 4 * e->stride,
+    HIP_TRY(launch_aos_to_soa(c->staging.as<const float4>(), s->chunks[(size_t)chunk] + (int64_t)plane * 4 * e->stride,
                               e->stride, first_slot, count, c->main()));
     HIP_TRY(hipStreamSynchronize(c->main()));   // staging is reused by the next call
     return ILM_OK;
@@ -1900,8 +1895,8 @@ int32_t ilm_chunk_download(IlmHandle h, int32_t chunk, int32_t plane, IlmFloat4*
     rc = ensure_staging(c, bytes);
     if (rc != ILM_OK) return rc;
     HIP_TRY(launch_soa_to_aos(s->chunks[(size_t)chunk] + (int64_t)plane * 4 * e->stride, e->stride,
-                              reinterpret_cast<float4*>(c->staging), first_slot, count, c->main()));
-    HIP_TRY(hipMemcpyAsync(dst, c->staging, bytes, hipMemcpyDeviceToHost, c->main()));
+                              c->staging.as<float4>(), first_slot, count, c->main()));
+    HIP_TRY(hipMemcpyAsync(dst, c->staging.p, bytes, hipMemcpyDeviceToHost, c->main()));
     HIP_TRY(hipStreamSynchronize(c->main()));
     return ILM_OK;
 }
@@ -1953,16 +1948,11 @@ int32_t ilm_system_set_spawn_positions(IlmHandle h, int32_t slot, const IlmFloat
     if (count > (1 << 20)) return fail(ILM_ERR_TOO_MANY, "at most %d positions", 1 << 20);
     Ctx* c = s->engine->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    if (count > s->spawn_position_cap[slot]) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (s->spawn_positions[slot]) HIP_TRY(hipFree(s->spawn_positions[slot]));
-        s->spawn_positions[slot] = nullptr; s->spawn_position_cap[slot] = 0;
-        const int cap = (count + 127) / 128 * 128;     // EnsurePositionBufferExists, ParticleSpawner.cs:307
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->spawn_positions[slot]), sizeof(float4) * (size_t)cap));
-        s->spawn_position_cap[slot] = cap;
-    }
+    // (rounded up to 128: EnsurePositionBufferExists, ParticleSpawner.cs:307)
+    int32_t rc = reserve(c, s->spawn_positions[slot], sizeof(float4) * (size_t)count, sizeof(float4) * (size_t)((count + 127) / 128 * 128));
+    if (rc != ILM_OK) return rc;
     if (count > 0) {
-        int32_t rc = upload_small(c, s->spawn_positions[slot], positions, sizeof(float4) * (size_t)count);
+        rc = upload_small(c, s->spawn_positions[slot].p, positions, sizeof(float4) * (size_t)count);
         if (rc != ILM_OK) return rc;
     }
     s->spawn_position_count[slot] = count;
@@ -2140,7 +2130,7 @@ int32_t ilm_system_live_counts(IlmHandle h, uint32_t* out_counts, int32_t capaci
     const int n = (int)s->chunks.size();
     if (n > 0) {
         HIP_TRY(hipMemsetAsync(s->counts_region(4), 0, sizeof(uint32_t) * (size_t)n * kCountStride, c->main()));
-        HIP_TRY(launch_count_live(s->d_table, s->engine->stride, s->engine->span, s->engine->slots, n, reinterpret_cast<uint32_t*>(s->counts_region(4)), c->main()));
+        HIP_TRY(launch_count_live(s->d_table.as<float*>(), s->engine->stride, s->engine->span, s->engine->slots, n, reinterpret_cast<uint32_t*>(s->counts_region(4)), c->main()));
     }
     return copy_counts(s, s->counts_region(4), out_counts, capacity, saturate16);
 }
@@ -2194,8 +2184,10 @@ int32_t ilm_chunk_live_slots(IlmHandle h, int32_t chunk, uint32_t* out_slots, in
     if (!out_count || capacity < 0 || (capacity > 0 && !out_slots)) return fail(ILM_ERR_INVALID_ARGUMENT, "bad output arguments");
     Engine* e = s->engine; Ctx* c = e->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    if (!s->d_slot_count)      // [0]: the list's length (the copying path); [1 ...]: live slots per block of 1024
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_slot_count), sizeof(uint32_t) * (size_t)(1 + (e->slots + 1023) / 1024)));
+    // [0]: the list's length (the copying path); [1 ...]: live slots per block of 1024
+    const size_t count_bytes = sizeof(uint32_t) * (size_t)(1 + (e->slots + 1023) / 1024);
+    { const int32_t rc = reserve(c, s->d_slot_count, count_bytes, count_bytes); if (rc != ILM_OK) return rc; }
+    uint32_t* const d_slot_count = s->d_slot_count.as<uint32_t>();
     if ((size_t)e->slots * sizeof(uint32_t) <= ((size_t)8 << 20)) {
         // the list and its length are written by the kernel straight into a pinned ring slot: one synchronisation, no copy commands
         const size_t list_bytes = sizeof(uint32_t) * (size_t)e->slots;
@@ -2207,7 +2199,7 @@ int32_t ilm_chunk_live_slots(IlmHandle h, int32_t chunk, uint32_t* out_slots, in
         HIP_TRY(hipHostGetDevicePointer(&dv, block, 0));
         uint32_t* p_count = static_cast<uint32_t*>(dv);
         uint32_t* p_slots = reinterpret_cast<uint32_t*>(static_cast<char*>(dv) + 64);
-        HIP_TRY(launch_live_slots(s->chunks[(size_t)chunk] + 3 * e->stride, e->slots, p_slots, (uint32_t)e->slots, p_count, s->d_slot_count + 1, c->main()));
+        HIP_TRY(launch_live_slots(s->chunks[(size_t)chunk] + 3 * e->stride, e->slots, p_slots, (uint32_t)e->slots, p_count, d_slot_count + 1, c->main()));
         const int32_t rc2 = staged_small_done(c, slot);
         if (rc2 != ILM_OK) return rc2;
         HIP_TRY(hipStreamSynchronize(c->main()));
@@ -2217,19 +2209,15 @@ int32_t ilm_chunk_live_slots(IlmHandle h, int32_t chunk, uint32_t* out_slots, in
         if (m > 0) memcpy(out_slots, block + 64, sizeof(uint32_t) * (size_t)m);
         return ILM_OK;
     }
-    if (s->slots_cap < e->slots) {
-        if (s->d_slots) { HIP_TRY(hipStreamSynchronize(c->main())); HIP_TRY(hipFree(s->d_slots)); s->d_slots = nullptr; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_slots), sizeof(uint32_t) * (size_t)e->slots));
-        s->slots_cap = e->slots;
-    }
-    HIP_TRY(launch_live_slots(s->chunks[(size_t)chunk] + 3 * e->stride, e->slots, s->d_slots, (uint32_t)e->slots, s->d_slot_count, s->d_slot_count + 1, c->main()));
+    { const int32_t rc = reserve(c, s->d_slots, sizeof(uint32_t) * (size_t)e->slots, sizeof(uint32_t) * (size_t)e->slots); if (rc != ILM_OK) return rc; }
+    HIP_TRY(launch_live_slots(s->chunks[(size_t)chunk] + 3 * e->stride, e->slots, s->d_slots.as<uint32_t>(), (uint32_t)e->slots, d_slot_count, d_slot_count + 1, c->main()));
     uint32_t n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, s->d_slot_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->main()));
+    HIP_TRY(hipMemcpyAsync(&n, d_slot_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->main()));
     HIP_TRY(hipStreamSynchronize(c->main()));
     *out_count = (int32_t)n;
     const uint32_t m = n < (uint32_t)capacity ? n : (uint32_t)capacity;
     if (m > 0) {
-        HIP_TRY(hipMemcpyAsync(out_slots, s->d_slots, sizeof(uint32_t) * (size_t)m, hipMemcpyDeviceToHost, c->main()));
+        HIP_TRY(hipMemcpyAsync(out_slots, s->d_slots.p, sizeof(uint32_t) * (size_t)m, hipMemcpyDeviceToHost, c->main()));
         HIP_TRY(hipStreamSynchronize(c->main()));
     }
     return ILM_OK;
@@ -2299,7 +2287,7 @@ int32_t ilm_sdf_sample(IlmHandle h, const IlmDistanceFieldUniforms* df, const fl
     }
     int32_t rc = ensure_staging(c, in_bytes + out_bytes);
     if (rc != ILM_OK) return rc;
-    float* d_in = static_cast<float*>(c->staging);
+    float* d_in = c->staging.as<float>();
     float* d_out = d_in + 3 * (size_t)count;
     HIP_TRY(hipMemcpyAsync(d_in, positions, in_bytes, hipMemcpyHostToDevice, c->main()));
     HIP_TRY(launch_sdf_sample(make_sdf_view(f, df), *df, d_in, count, d_out, c->main()));
@@ -2320,7 +2308,7 @@ int32_t ilm_debug_sdf_sample_inside(IlmHandle h, const IlmDistanceFieldUniforms*
     const size_t in_bytes = sizeof(float) * 3 * (size_t)count, out_bytes = sizeof(float) * (size_t)count;
     int32_t rc = ensure_staging(c, in_bytes + 2 * out_bytes);
     if (rc != ILM_OK) return rc;
-    float* d_in = static_cast<float*>(c->staging);
+    float* d_in = c->staging.as<float>();
     float* d_out = d_in + 3 * (size_t)count;
     int32_t* d_used = reinterpret_cast<int32_t*>(d_out + (size_t)count);
     HIP_TRY(hipMemcpyAsync(d_in, positions, in_bytes, hipMemcpyHostToDevice, c->main()));
@@ -2386,7 +2374,7 @@ int32_t ilm_debug_divide(IlmHandle hctx, const float* numerators, const float* d
     const size_t bytes = sizeof(float) * (size_t)count;
     int32_t rc = ensure_staging(c, 4 * bytes);
     if (rc != ILM_OK) return rc;
-    float* d_n = static_cast<float*>(c->staging);
+    float* d_n = c->staging.as<float>();
     float* d_d = d_n + count; float* d_f = d_d + count; float* d_i = d_f + count;
     HIP_TRY(hipMemcpyAsync(d_n, numerators, bytes, hipMemcpyHostToDevice, c->main()));
     HIP_TRY(hipMemcpyAsync(d_d, denominators, bytes, hipMemcpyHostToDevice, c->main()));
@@ -2488,9 +2476,7 @@ int32_t ilm_sdf_render_slices(IlmHandle h, IlmHandle hclear, const IlmDistanceFi
     for (int i = 0; i < obstruction_count; i++)
         if (obstructions[i].Type < ILM_OBSTRUCTION_ELLIPSOID || obstructions[i].Type > ILM_OBSTRUCTION_OCTAGON)
             return fail(ILM_ERR_INVALID_ARGUMENT, "obstruction %d has unknown type %d", i, obstructions[i].Type);
-    for (int i = 0; i < volume_count; i++)
-        if (volumes[i].FirstVertex < 0 || volumes[i].VertexCount < 0 || volumes[i].FirstVertex + volumes[i].VertexCount > polygon_vertex_count)
-            return fail(ILM_ERR_OUT_OF_RANGE, "height volume %d vertex range outside the polygon array", i);
+    { const int32_t rc = check_volume_ranges(volumes, volume_count, polygon_vertex_count); if (rc != ILM_OK) return rc; }
     if (triplet_count == 0) return ILM_OK;
     Ctx* c = f->ctx;
     HIP_TRY(hipSetDevice(c->device));
@@ -2558,20 +2544,12 @@ int32_t ilm_sdf_render_slices(IlmHandle h, IlmHandle hclear, const IlmDistanceFi
     }
 
     // one parameter block: [slices | obstruction records | volumes | polygon vertices], 64-byte aligned sections
-    auto align64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
     const size_t off_slices = 0;
     const size_t off_recs = align64(off_slices + sizeof(int32_t) * (size_t)triplet_count);
     const size_t off_vols = align64(off_recs + sizeof(FieldObstruction) * recs.size());
     const size_t off_poly = align64(off_vols + sizeof(FieldVolume) * vols.size());
     const size_t total = align64(off_poly + sizeof(float) * 2 * (size_t)(vols.empty() ? 0 : polygon_vertex_count));
-    if (total > c->field_params_bytes) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_field_params) HIP_TRY(hipFree(c->d_field_params));
-        c->d_field_params = nullptr; c->field_params_bytes = 0;
-        const size_t cap = total < 65536 ? 65536 : total * 2;
-        HIP_TRY(hipMalloc(&c->d_field_params, cap));
-        c->field_params_bytes = cap;
-    }
+    { const int32_t rc = reserve_field_params(c, total); if (rc != ILM_OK) return rc; }
     std::vector<unsigned char> block(total, 0);
     memcpy(block.data() + off_slices, first_virtual_slices, sizeof(int32_t) * (size_t)triplet_count);
     if (!recs.empty()) memcpy(block.data() + off_recs, recs.data(), sizeof(FieldObstruction) * recs.size());
@@ -2579,11 +2557,11 @@ int32_t ilm_sdf_render_slices(IlmHandle h, IlmHandle hclear, const IlmDistanceFi
         memcpy(block.data() + off_vols, vols.data(), sizeof(FieldVolume) * vols.size());
         memcpy(block.data() + off_poly, polygon_xy, sizeof(float) * 2 * (size_t)polygon_vertex_count);
     }
-    int32_t rc = upload_small(c, c->d_field_params, block.data(), total);
+    int32_t rc = upload_small(c, c->d_field_params.p, block.data(), total);
     if (rc != ILM_OK) return rc;
 
     FieldLaunch a;
-    char* base = static_cast<char*>(c->d_field_params);
+    char* base = c->d_field_params.as<char>();
     a.atlas = f->texels; a.clear_source = clr ? clr->texels : nullptr; a.atlas_w = f->width;
     a.first_slices = reinterpret_cast<const int32_t*>(base + off_slices); a.triplet_count = triplet_count;
     a.obstructions = reinterpret_cast<const FieldObstruction*>(base + off_recs); a.obstruction_count = (int32_t)recs.size();
@@ -2652,9 +2630,7 @@ int32_t ilm_gbuffer_render(IlmHandle h, const IlmGBufferRenderDesc* d, const Ilm
     if (volume_count < 0 || polygon_vertex_count < 0 || (volume_count > 0 && (!volumes || !polygon_xy)))
         return fail(ILM_ERR_INVALID_ARGUMENT, "bad array argument");
     if (!(d->ViewportScale[0] > 0.0f) || !(d->ViewportScale[1] > 0.0f)) return fail(ILM_ERR_INVALID_ARGUMENT, "ViewportScale must be positive");
-    for (int i = 0; i < volume_count; i++)
-        if (volumes[i].FirstVertex < 0 || volumes[i].VertexCount < 0 || volumes[i].FirstVertex + volumes[i].VertexCount > polygon_vertex_count)
-            return fail(ILM_ERR_OUT_OF_RANGE, "height volume %d vertex range outside the polygon array", i);
+    { const int32_t rc = check_volume_ranges(volumes, volume_count, polygon_vertex_count); if (rc != ILM_OK) return rc; }
     Ctx* c = g->ctx;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(shared_before_write(g->shared, c));
@@ -2678,29 +2654,21 @@ int32_t ilm_gbuffer_render(IlmHandle h, const IlmGBufferRenderDesc* d, const Ilm
         }
         vols.push_back(v);
     }
-    auto align64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
     const size_t off_poly = align64(sizeof(GBufferVolume) * vols.size());
     const size_t total = align64(off_poly + sizeof(float) * 2 * (size_t)(vols.empty() ? 0 : polygon_vertex_count)) + 64;
-    if (total > c->field_params_bytes) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_field_params) HIP_TRY(hipFree(c->d_field_params));
-        c->d_field_params = nullptr; c->field_params_bytes = 0;
-        const size_t cap = total < 65536 ? 65536 : total * 2;
-        HIP_TRY(hipMalloc(&c->d_field_params, cap));
-        c->field_params_bytes = cap;
-    }
+    { const int32_t rc = reserve_field_params(c, total); if (rc != ILM_OK) return rc; }
     if (!vols.empty()) {
         std::vector<unsigned char> block(total, 0);
         memcpy(block.data(), vols.data(), sizeof(GBufferVolume) * vols.size());
         memcpy(block.data() + off_poly, polygon_xy, sizeof(float) * 2 * (size_t)polygon_vertex_count);
-        int32_t rc = upload_small(c, c->d_field_params, block.data(), total);
+        int32_t rc = upload_small(c, c->d_field_params.p, block.data(), total);
         if (rc != ILM_OK) return rc;
     }
     GBufferLaunch a;
     a.texels = g->texels; a.width = g->width; a.height = g->height; a.format = g->format;
     a.desc = *d;
-    a.volumes = reinterpret_cast<const GBufferVolume*>(c->d_field_params); a.volume_count = (int32_t)vols.size();
-    a.polygon_xy = reinterpret_cast<const float2*>(static_cast<char*>(c->d_field_params) + off_poly);
+    a.volumes = c->d_field_params.as<const GBufferVolume>(); a.volume_count = (int32_t)vols.size();
+    a.polygon_xy = reinterpret_cast<const float2*>(c->d_field_params.as<char>() + off_poly);
     HIP_TRY(launch_render_gbuffer(a, c->main()));
     return ILM_OK;
 }
@@ -2753,7 +2721,6 @@ int32_t ilm_gbuffer_render_meshes(IlmHandle h, const IlmGBufferMeshDesc* d,
     if (prim_count > (1 << 24)) return fail(ILM_ERR_TOO_MANY, "%lld triangles in one G-buffer frame", (long long)prim_count);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(shared_before_write(g->shared, c));
-    auto align64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
     const size_t off_front = align64(sizeof(IlmHeightVolumeVertex) * (size_t)top_vertex_count);
     const size_t off_bb = align64(off_front + sizeof(IlmHeightVolumeVertex) * (size_t)front_vertex_count);
     const size_t off_quads = align64(off_bb + sizeof(IlmBillboardVertex) * (size_t)billboard_vertex_count);
@@ -2772,14 +2739,7 @@ int32_t ilm_gbuffer_render_meshes(IlmHandle h, const IlmGBufferMeshDesc* d,
     const size_t off_block_count = align64(off_verts + 2 * sizeof(int4) * (size_t)prim_count);
     const size_t off_block_list = align64(off_block_count + sizeof(int32_t) * block_count);
     const size_t total = off_block_list + sizeof(int32_t) * block_count * (size_t)prim_count;
-    if (total > c->field_params_bytes) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_field_params) HIP_TRY(hipFree(c->d_field_params));
-        c->d_field_params = nullptr; c->field_params_bytes = 0;
-        const size_t cap = total < 65536 ? 65536 : total * 2;
-        HIP_TRY(hipMalloc(&c->d_field_params, cap));
-        c->field_params_bytes = cap;
-    }
+    { const int32_t rc = reserve_field_params(c, total); if (rc != ILM_OK) return rc; }
     // the frame's inputs are gathered straight into a pinned slot of the ring (one host copy) and read by the setup kernel where they lie
     // (one device operation and one dependent-launch gap less than a copy: the vertices are read once, by the one kernel that digests them)
     unsigned char* block = nullptr;
@@ -2791,7 +2751,7 @@ int32_t ilm_gbuffer_render_meshes(IlmHandle h, const IlmGBufferMeshDesc* d,
     if (billboard_vertex_count) memcpy(block + off_bb, billboard_vertices, sizeof(IlmBillboardVertex) * (size_t)billboard_vertex_count);
     if (!quads.empty()) memcpy(block + off_quads, quads.data(), sizeof(int4) * quads.size());
     if (!textures.empty()) memcpy(block + off_tex, textures.data(), sizeof(GBufferTex) * textures.size());
-    char* base = static_cast<char*>(c->d_field_params);
+    char* base = c->d_field_params.as<char>();
     void* dv = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dv, block, 0));
     const char* in = static_cast<const char*>(dv);
@@ -2984,28 +2944,22 @@ int32_t plan_light_split(Ctx* c, LightLaunch* a) {
     // per tile (a forced split on a 4K frame asked for 1 GB).  When the device cannot give it the launch is not split: the
     // frame is the same bits either way.
     const size_t split_slots = (size_t)(slots - t[0]) * 8u;
-    if (split_slots > c->light_partials_tiles) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_light_partials) HIP_TRY(hipFree(c->d_light_partials));
-        c->d_light_partials = nullptr; c->light_partials_tiles = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&c->d_light_partials), split_slots * (size_t)kLightParts * (size_t)kLightTileThreads * sizeof(float4)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->d_light_partials = nullptr;
-            a->split = 1; a->taper[0] = a->taper[1] = a->taper[2] = slots;
-            return ILM_OK;
+    const size_t partial_bytes = split_slots * (size_t)kLightParts * (size_t)kLightTileThreads * sizeof(float4);
+    if (try_reserve(c, c->d_light_partials, partial_bytes, partial_bytes) != hipSuccess) {
+        a->split = 1; a->taper[0] = a->taper[1] = a->taper[2] = slots;
+        return ILM_OK;
+    }
+    // (one ticket per tile and wave: the quadrants of a tile are delivered independently)
+    const size_t ticket_bytes = (size_t)tiles * (kLightTileThreads / 64) * sizeof(uint32_t);
+    if (ticket_bytes > c->d_light_tickets.bytes) {
+        const int32_t rc = reserve(c, c->d_light_tickets, ticket_bytes, ticket_bytes);
+        if (rc != ILM_OK) return rc;
+        if (const hipError_t e = hipMemsetAsync(c->d_light_tickets.p, 0, ticket_bytes, c->main())) {
+            release(c->d_light_tickets);        // (never a block that is not known to be zero)
+            return fail((int32_t)e, "clearing the light tickets failed: %s", hipGetErrorString(e));
         }
-        c->light_partials_tiles = split_slots;
     }
-    if ((size_t)tiles > c->light_tickets_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_light_tickets) HIP_TRY(hipFree(c->d_light_tickets));
-        c->d_light_tickets = nullptr; c->light_tickets_cap = 0;
-        // (one ticket per tile and wave: the quadrants of a tile are delivered independently)
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_light_tickets), (size_t)tiles * (kLightTileThreads / 64) * sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(c->d_light_tickets, 0, (size_t)tiles * (kLightTileThreads / 64) * sizeof(uint32_t), c->main()));
-        c->light_tickets_cap = (size_t)tiles;
-    }
-    a->partials = c->d_light_partials; a->tickets = c->d_light_tickets;
+    a->partials = c->d_light_partials.as<float4>(); a->tickets = c->d_light_tickets.as<uint32_t>();
     return ILM_OK;
 }
 
@@ -3031,7 +2985,7 @@ int32_t plan_group_order(Ctx* c, LightLaunch* a, const IlmLightVertex* lights, i
         mix(&a->env, sizeof(a->env));
         const int32_t geom[5] = { a->width, a->row_begin, a->row_end, group_edge_px, light_count };
         mix(geom, sizeof(geom));
-        if (c->d_group_order && c->group_order_key == key && c->group_order_groups == groups) { a->group_order = c->d_group_order; return ILM_OK; }
+        if (c->d_group_order.p && c->group_order_key == key && c->group_order_groups == groups) { a->group_order = c->d_group_order.as<uint16_t>(); return ILM_OK; }
         pending_key = key;       // committed below, once the table IS on the device (a failed upload left the key of a table that was not there)
         c->group_order_groups = 0;
     }
@@ -3068,30 +3022,18 @@ int32_t plan_group_order(Ctx* c, LightLaunch* a, const IlmLightVertex* lights, i
     }
     // (the last, partial round of a snake may name a group twice and skip another: repair by a plain copy of that round)
     { const int tail = (groups / 8) * 8; for (int p = tail; p < groups; p++) dealt[(size_t)p] = order[(size_t)p]; }
-    if (groups > c->group_order_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_group_order) HIP_TRY(hipFree(c->d_group_order));
-        c->d_group_order = nullptr; c->group_order_cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_group_order), sizeof(uint16_t) * (size_t)groups * 2));
-        c->group_order_cap = groups * 2;
-    }
-    const int32_t rc = upload_small(c, c->d_group_order, dealt.data(), sizeof(uint16_t) * (size_t)groups);
+    int32_t rc = reserve(c, c->d_group_order, sizeof(uint16_t) * (size_t)groups, sizeof(uint16_t) * (size_t)groups * 2);
+    if (rc != ILM_OK) return rc;
+    rc = upload_small(c, c->d_group_order.p, dealt.data(), sizeof(uint16_t) * (size_t)groups);
     if (rc != ILM_OK) return rc;
     c->group_order_key = pending_key; c->group_order_groups = groups;
-    a->group_order = c->d_group_order;
+    a->group_order = c->d_group_order.as<uint16_t>();
     return ILM_OK;
 }
 
 // room for light_count prepared light records in c->d_recs (sphere lights and probes)
 int32_t reserve_light_recs(Ctx* c, int light_count) {
-    if (light_count <= c->light_cap) return ILM_OK;
-    HIP_TRY(hipStreamSynchronize(c->main()));
-    if (c->d_recs) HIP_TRY(hipFree(c->d_recs));
-    c->d_recs = nullptr; c->light_cap = 0;
-    const int cap = light_count < 256 ? 256 : light_count * 2;
-    HIP_TRY(hipMalloc(&c->d_recs, kLightRecBytes * (size_t)cap));
-    c->light_cap = cap;
-    return ILM_OK;
+    return reserve(c, c->d_recs, kLightRecBytes * (size_t)light_count, kLightRecBytes * (size_t)(light_count < 256 ? 256 : light_count * 2));
 }
 
 // shared by the three light passes: resource checks + the launch descriptor
@@ -3163,50 +3105,32 @@ int32_t ilm_render_particle_lights(IlmHandle hctx, IlmHandle hsystem, const int3
     if (total == 0) return ILM_OK;
     const int blocks_per_chunk = (e->slots + 1023) / 1024;
     const int blocks = chunk_count * blocks_per_chunk;
-    if ((int)total > c->pl_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_pl_recs) HIP_TRY(hipFree(c->d_pl_recs));
-        c->d_pl_recs = nullptr; c->pl_cap = 0;
-        const int cap = (int)total < 4096 ? 4096 : (int)total;
-        HIP_TRY(hipMalloc(&c->d_pl_recs, kLightRecBytes * (size_t)cap));
-        c->pl_cap = cap;
-    }
-    if (!c->d_pl_count) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_pl_count), sizeof(int32_t)));
-    if (blocks > c->pl_blocks_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_pl_blocks) HIP_TRY(hipFree(c->d_pl_blocks));
-        c->d_pl_blocks = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_pl_blocks), sizeof(int32_t) * (size_t)blocks * 2));
-        c->pl_blocks_cap = blocks * 2;
-    }
-    if (chunk_count > c->pl_quads_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_pl_quads) HIP_TRY(hipFree(c->d_pl_quads));
-        c->d_pl_quads = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_pl_quads), sizeof(int32_t) * (size_t)chunk_count * 2));
-        c->pl_quads_cap = chunk_count * 2;
-    }
+    rc = reserve(c, c->d_pl_recs, kLightRecBytes * (size_t)total, kLightRecBytes * (size_t)std::max<int64_t>(total, 4096));
+    if (rc == ILM_OK) rc = reserve(c, c->d_pl_count, sizeof(int32_t), sizeof(int32_t));
+    if (rc == ILM_OK) rc = reserve(c, c->d_pl_blocks, sizeof(int32_t) * (size_t)blocks, sizeof(int32_t) * (size_t)blocks * 2);
+    if (rc == ILM_OK) rc = reserve(c, c->d_pl_quads, sizeof(int32_t) * (size_t)chunk_count, sizeof(int32_t) * (size_t)chunk_count * 2);
+    if (rc != ILM_OK) return rc;
     if (quad_counts) {
-        rc = upload_small(c, c->d_pl_quads, quad_counts, sizeof(int32_t) * (size_t)chunk_count);
+        rc = upload_small(c, c->d_pl_quads.p, quad_counts, sizeof(int32_t) * (size_t)chunk_count);
         if (rc != ILM_OK) return rc;
     }
     ParticleLightLaunch pl;
-    pl.chunk_bases = s->d_table; pl.stride = e->stride; pl.chunk_count = chunk_count; pl.slots = e->slots;
-    pl.quad_counts = quad_counts ? c->d_pl_quads : nullptr;
+    pl.chunk_bases = s->d_table.as<float*>(); pl.stride = e->stride; pl.chunk_count = chunk_count; pl.slots = e->slots;
+    pl.quad_counts = quad_counts ? c->d_pl_quads.as<int32_t>() : nullptr;
     pl.params = *params; pl.env = *env; pl.max_cone_radius = df->ConeAndMisc.x;
     pl.gate = make_trace_gate(*df, a.sdf);
-    pl.block_counts = c->d_pl_blocks; pl.recs = c->d_pl_recs; pl.capacity = c->pl_cap; pl.out_count = c->d_pl_count;
+    pl.block_counts = c->d_pl_blocks.as<int32_t>(); pl.recs = c->d_pl_recs.p; pl.capacity = (int32_t)(c->d_pl_recs.bytes / kLightRecBytes); pl.out_count = c->d_pl_count.as<int32_t>();
     HIP_TRY(launch_prepare_particle_lights(pl, c->main()));
 
     a.light_count = 0;
-    a.light_count_ptr = c->d_pl_count;
+    a.light_count_ptr = c->d_pl_count.as<int32_t>();
     a.accumulate = 1;
     if (stats) {
         HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
         a.stats = c->d_stats;
     }
     c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
-    HIP_TRY(launch_sphere_lights_prepared(a, c->d_pl_recs, c->main()));
+    HIP_TRY(launch_sphere_lights_prepared(a, c->d_pl_recs.p, c->main()));
     HIP_TRY(light_pass_queued(c, hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr, hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr));
     if (stats) {
         unsigned long long host[3] = { 0, 0, 0 };
@@ -3235,7 +3159,6 @@ int32_t ilm_render_light_probes(IlmHandle hctx, const IlmLightVertex* lights, in
     { const int32_t rc = reserve_light_recs(c, light_count); if (rc != ILM_OK) return rc; }
     // One pinned block [lights | positions | normals | values]: the kernels read their inputs where it lies (each word once) and the
     // last one writes the values into it -- no copy command on either side of the two kernels (r04; three uploads and a read-back before)
-    auto align64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
     const size_t off_pos = align64(sizeof(IlmLightVertex) * (size_t)light_count);
     const size_t off_nrm = off_pos + align64(sizeof(float4) * (size_t)probe_count);
     const size_t off_val = off_nrm + align64(sizeof(float4) * (size_t)probe_count);
@@ -3251,7 +3174,7 @@ int32_t ilm_render_light_probes(IlmHandle hctx, const IlmLightVertex* lights, in
     HIP_TRY(hipHostGetDevicePointer(&dv, block, 0));
     const char* in = static_cast<const char*>(dv);
     if (light_count > 0)
-        HIP_TRY(launch_prepare_lights(reinterpret_cast<const IlmLightVertex*>(in), light_count, *env, *df, make_sdf_view(f, df), c->d_recs, c->main()));
+        HIP_TRY(launch_prepare_lights(reinterpret_cast<const IlmLightVertex*>(in), light_count, *env, *df, make_sdf_view(f, df), c->d_recs.p, c->main()));
     const float4* d_pos = reinterpret_cast<const float4*>(in + off_pos);
     const float4* d_nrm = reinterpret_cast<const float4*>(in + off_nrm);
     float4* d_val = reinterpret_cast<float4*>(const_cast<char*>(in) + off_val);
@@ -3259,17 +3182,11 @@ int32_t ilm_render_light_probes(IlmHandle hctx, const IlmLightVertex* lights, in
     float4* d_pairs = nullptr;
     const size_t pair_count = (size_t)probe_count * (size_t)(light_count > 0 ? light_count : 0);
     if (light_count > 1 && pair_count * sizeof(float4) <= ((size_t)256 << 20)) {
-        if (pair_count > c->probe_pairs_cap) {
-            HIP_TRY(hipStreamSynchronize(c->main()));
-            if (c->d_probe_pairs) HIP_TRY(hipFree(c->d_probe_pairs));
-            c->d_probe_pairs = nullptr; c->probe_pairs_cap = 0;
-            const size_t cap = pair_count < 65536 ? 65536 : pair_count + pair_count / 2;
-            if (hipMalloc(reinterpret_cast<void**>(&c->d_probe_pairs), sizeof(float4) * cap) == hipSuccess) c->probe_pairs_cap = cap;
-            else { (void)hipGetLastError(); c->d_probe_pairs = nullptr; }      // (the one-kernel form needs no scratch)
-        }
-        d_pairs = c->d_probe_pairs;
+        // (without the block the one-kernel form runs: it needs no scratch)
+        if (try_reserve(c, c->d_probe_pairs, sizeof(float4) * pair_count, sizeof(float4) * (pair_count < 65536 ? 65536 : pair_count + pair_count / 2)) == hipSuccess)
+            d_pairs = c->d_probe_pairs.as<float4>();
     }
-    HIP_TRY(launch_light_probes(c->d_recs, light_count, d_pos, d_nrm, probe_count, *env, *df, make_sdf_view(f, df),
+    HIP_TRY(launch_light_probes(c->d_recs.p, light_count, d_pos, d_nrm, probe_count, *env, *df, make_sdf_view(f, df),
                                 RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h }, d_val, d_pairs, c->main()));
     rc = staged_small_done(c, slot);
     if (rc != ILM_OK) return rc;
@@ -3291,35 +3208,19 @@ static int32_t readback_to_pinned(System* s, const int32_t* element_counts, int3
     int32_t rc = refresh_table(s);
     if (rc != ILM_OK) return rc;
     const int blocks = chunk_count * ((e->slots + 1023) / 1024);
-    if (capacity > c->rb_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_rb) HIP_TRY(hipFree(c->d_rb));
-        c->d_rb = nullptr; c->rb_cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_rb), sizeof(IlmReadbackDrawCall) * (size_t)capacity));
-        c->rb_cap = capacity;
-    }
-    if (!c->d_rb_count) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_rb_count), sizeof(int32_t)));
-    if (blocks > c->rb_blocks_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_rb_blocks) HIP_TRY(hipFree(c->d_rb_blocks));
-        c->d_rb_blocks = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_rb_blocks), sizeof(int32_t) * (size_t)blocks * 2));
-        c->rb_blocks_cap = blocks * 2;
-    }
-    if (chunk_count > c->rb_elems_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (c->d_rb_elems) HIP_TRY(hipFree(c->d_rb_elems));
-        c->d_rb_elems = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_rb_elems), sizeof(int32_t) * (size_t)chunk_count * 2));
-        c->rb_elems_cap = chunk_count * 2;
-    }
+    const size_t rb_bytes = sizeof(IlmReadbackDrawCall) * (size_t)capacity;
+    rc = reserve(c, c->d_rb, rb_bytes, rb_bytes);
+    if (rc == ILM_OK) rc = reserve(c, c->d_rb_count, sizeof(int32_t), sizeof(int32_t));
+    if (rc == ILM_OK) rc = reserve(c, c->d_rb_blocks, sizeof(int32_t) * (size_t)blocks, sizeof(int32_t) * (size_t)blocks * 2);
+    if (rc == ILM_OK) rc = reserve(c, c->d_rb_elems, sizeof(int32_t) * (size_t)chunk_count, sizeof(int32_t) * (size_t)chunk_count * 2);
+    if (rc != ILM_OK) return rc;
     if (element_counts) {
-        rc = upload_small(c, c->d_rb_elems, element_counts, sizeof(int32_t) * (size_t)chunk_count);
+        rc = upload_small(c, c->d_rb_elems.p, element_counts, sizeof(int32_t) * (size_t)chunk_count);
         if (rc != ILM_OK) return rc;
     }
     ReadbackLaunch a;
-    a.chunk_bases = s->d_table; a.stride = e->stride; a.chunk_count = chunk_count; a.slots = e->slots;
-    a.element_counts = element_counts ? c->d_rb_elems : nullptr;
+    a.chunk_bases = s->d_table.as<float*>(); a.stride = e->stride; a.chunk_count = chunk_count; a.slots = e->slots;
+    a.element_counts = element_counts ? c->d_rb_elems.as<int32_t>() : nullptr;
     a.params = *params;
     // ParticleReadback.cs:100-112
     a.region_w = params->TextureRegion[2] - params->TextureRegion[0];
@@ -3328,10 +3229,10 @@ static int32_t readback_to_pinned(System* s, const int32_t* element_counts, int3
     a.frame_count_y = std::max((int)(1.0f / a.region_h), 1);
     a.max_angle_x = (2 * 3.14159265358979323846) / a.frame_count_x;
     a.max_angle_y = (2 * 3.14159265358979323846) / a.frame_count_y;
-    a.block_counts = c->d_rb_blocks; a.out = c->d_rb; a.capacity = capacity; a.out_count = c->d_rb_count;
+    a.block_counts = c->d_rb_blocks.as<int32_t>(); a.out = c->d_rb.as<IlmReadbackDrawCall>(); a.capacity = capacity; a.out_count = c->d_rb_count.as<int32_t>();
     HIP_TRY(launch_readback(a, c->main()));
     int32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, c->d_rb_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->main()));
+    HIP_TRY(hipMemcpyAsync(&total, c->d_rb_count.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->main()));
     HIP_TRY(hipStreamSynchronize(c->main()));
     *out_total = total;
     const int n_copy = total < capacity ? total : capacity;
@@ -3345,7 +3246,7 @@ static int32_t readback_to_pinned(System* s, const int32_t* element_counts, int3
             HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_rb), sizeof(IlmReadbackDrawCall) * cap, hipHostMallocDefault));
             c->h_rb_cap = cap;
         }
-        HIP_TRY(hipMemcpyAsync(c->h_rb, c->d_rb, sizeof(IlmReadbackDrawCall) * (size_t)n_copy, hipMemcpyDeviceToHost, c->main()));
+        HIP_TRY(hipMemcpyAsync(c->h_rb, c->d_rb.p, sizeof(IlmReadbackDrawCall) * (size_t)n_copy, hipMemcpyDeviceToHost, c->main()));
         HIP_TRY(hipStreamSynchronize(c->main()));
     }
     return ILM_OK;
@@ -3498,21 +3399,16 @@ int32_t ilm_render_particles(IlmHandle hsystem, const int32_t* quad_counts, int3
     int32_t rc = refresh_table(s);
     if (rc != ILM_OK) return rc;
     if (quad_counts) {
-        if (chunk_count > c->raster_quads_cap) {
-            HIP_TRY(hipStreamSynchronize(c->main()));
-            if (c->d_raster_quads) HIP_TRY(hipFree(c->d_raster_quads));
-            c->d_raster_quads = nullptr; c->raster_quads_cap = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_raster_quads), sizeof(int32_t) * (size_t)chunk_count * 2));
-            c->raster_quads_cap = chunk_count * 2;
-        }
-        rc = upload_small(c, c->d_raster_quads, quad_counts, sizeof(int32_t) * (size_t)chunk_count);
+        rc = reserve(c, c->d_raster_quads, sizeof(int32_t) * (size_t)chunk_count, sizeof(int32_t) * (size_t)chunk_count * 2);
+        if (rc != ILM_OK) return rc;
+        rc = upload_small(c, c->d_raster_quads.p, quad_counts, sizeof(int32_t) * (size_t)chunk_count);
         if (rc != ILM_OK) return rc;
     }
     RasterLaunch a;
     std::memset(&a, 0, sizeof(a));
-    a.chunk_bases = s->d_table; a.stride = e->stride; a.chunk_count = chunk_count; a.slots = e->slots;
+    a.chunk_bases = s->d_table.as<float*>(); a.stride = e->stride; a.chunk_count = chunk_count; a.slots = e->slots;
     a.total_slots = chunk_count * e->slots;
-    a.quad_counts = quad_counts ? c->d_raster_quads : nullptr;
+    a.quad_counts = quad_counts ? c->d_raster_quads.as<int32_t>() : nullptr;
     a.params = *params;
     a.target = m->texels; a.format = m->format; a.width = m->width; a.height = m->height;
     a.tiles_x = (m->width + 15) / 16; a.tiles_y = (m->height + 15) / 16;
@@ -3715,26 +3611,15 @@ int32_t queue_luminance_level(Lightmap* m, int32_t rw, int32_t rh, int32_t level
     Ctx* c = m->ctx;
     BrightnessScratch& b = c->brightness;
     const size_t n = (size_t)w * (size_t)h;
-    if (n > b.level_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (b.level) HIP_TRY(hipFree(b.level));
-        b.level = nullptr; b.level_cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.level), sizeof(float) * n));
-        b.level_cap = n;
-    }
+    int32_t rc = reserve(c, b.level, sizeof(float) * n, sizeof(float) * n);
     const size_t level3 = (size_t)((rw / 2) >> 3) * (size_t)((rh / 2) >> 3);
-    if (level > 3 && 2 * level3 > b.mip_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (b.mip) HIP_TRY(hipFree(b.mip));
-        b.mip = nullptr; b.mip_cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.mip), sizeof(float) * 2 * level3));
-        b.mip_cap = 2 * level3;
-    }
+    if (rc == ILM_OK && level > 3) rc = reserve(c, b.mip, sizeof(float) * 2 * level3, sizeof(float) * 2 * level3);
+    if (rc != ILM_OK) return rc;
     LuminanceLaunch a;
     a.texels = m->texels; a.format = m->format; a.pitch = m->width;
     a.rw = rw; a.rh = rh; a.w0 = rw / 2; a.h0 = rh / 2; a.level = level;
-    a.out = b.level;
-    a.mip[0] = b.mip; a.mip[1] = b.mip ? b.mip + b.mip_cap / 2 : nullptr;
+    a.out = b.level.as<float>();
+    a.mip[0] = b.mip.as<float>(); a.mip[1] = b.mip.p ? b.mip.as<float>() + b.mip.bytes / sizeof(float) / 2 : nullptr;
     HIP_TRY(launch_luminance_level(a, c->main()));
     return ILM_OK;
 }
@@ -3752,7 +3637,7 @@ int32_t ilm_lightmap_luminance(IlmHandle h, int32_t render_width, int32_t render
     if (out_values) {
         HIP_TRY(hipSetDevice(m->ctx->device));
         { const int32_t rc = queue_luminance_level(m, render_width, render_height, level, w, ht); if (rc != ILM_OK) return rc; }
-        HIP_TRY(hipMemcpyAsync(out_values, m->ctx->brightness.level, sizeof(float) * (size_t)w * (size_t)ht, hipMemcpyDeviceToHost, m->ctx->main()));
+        HIP_TRY(hipMemcpyAsync(out_values, m->ctx->brightness.level.p, sizeof(float) * (size_t)w * (size_t)ht, hipMemcpyDeviceToHost, m->ctx->main()));
         HIP_TRY(hipStreamSynchronize(m->ctx->main()));
     }
     if (out_level) *out_level = level;
@@ -3792,27 +3677,23 @@ int32_t ilm_lightmap_histogram(IlmHandle h, const IlmHistogramParams* params, co
     { const int32_t rc = queue_luminance_level(m, params->RenderWidth, params->RenderHeight, level, w, ht); if (rc != ILM_OK) return rc; }
     BrightnessScratch& b = c->brightness;
     const int n = w * ht, blocks = histogram_blocks(n), buckets = params->BucketCount;
-    if (!b.work) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.work), histogram_work_bytes()));
-    if ((size_t)blocks * 256 > b.partials_cap) {
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        if (b.partials) HIP_TRY(hipFree(b.partials));
-        b.partials = nullptr; b.partials_cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.partials), sizeof(double) * 256 + sizeof(float) * (size_t)blocks * 256));
-        b.partials_cap = (size_t)blocks * 256;
-    }
+    const size_t partial_bytes = sizeof(double) * 256 + sizeof(float) * (size_t)blocks * 256;
+    int32_t rc = reserve(c, b.work, histogram_work_bytes(), histogram_work_bytes());
+    if (rc == ILM_OK) rc = reserve(c, b.partials, partial_bytes, partial_bytes);
+    if (rc != ILM_OK) return rc;
     // the results leave through one pinned block the last kernel writes: [bucket states | totals], read after the call's one synchronisation
     const size_t off_totals = sizeof(IlmHistogramBucket) * (size_t)buckets;
     unsigned char* block = nullptr;
     int slot = -1;
-    int32_t rc = upload_small_begin(c, off_totals + 8 * sizeof(float), reinterpret_cast<void**>(&block), &slot);
+    rc = upload_small_begin(c, off_totals + 8 * sizeof(float), reinterpret_cast<void**>(&block), &slot);
     if (rc != ILM_OK) return rc;
     void* dv = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dv, block, 0));
     HistogramLaunch a;
-    a.values = b.level; a.n = n;
+    a.values = b.level.as<float>(); a.n = n;
     a.bucket_count = buckets; a.ignore_zeroes = params->IgnoreZeroes != 0 ? 1 : 0; a.scale = params->ScaleFactor;
     for (int i = 0; i < 256; i++) a.table[i] = i < buckets ? bucket_max_values[i] : 0.0f;
-    a.work = b.work; a.sums = reinterpret_cast<double*>(b.partials); a.partials = b.partials + 512; a.blocks = blocks;
+    a.work = b.work.as<uint32_t>(); a.sums = b.partials.as<double>(); a.partials = b.partials.as<float>() + 512; a.blocks = blocks;
     a.out_buckets = static_cast<IlmHistogramBucket*>(dv);
     a.out_totals = reinterpret_cast<float*>(static_cast<unsigned char*>(dv) + off_totals);
     HIP_TRY(launch_histogram(a, c->main()));
@@ -3858,7 +3739,7 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
         const void* staged = nullptr; int slot = 0;
         int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
         if (rc != ILM_OK) return rc;
-        HIP_TRY(launch_prepare_lights(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, trace_view, c->d_recs, c->main()));
+        HIP_TRY(launch_prepare_lights(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, trace_view, c->d_recs.p, c->main()));
         rc = staged_small_done(c, slot);
         if (rc != ILM_OK) return rc;
     }
@@ -3887,7 +3768,7 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     { const int32_t rc = plan_light_split(c, &a); if (rc != ILM_OK) return rc; }
     { const int32_t rc = plan_group_order(c, &a, lights, light_count, 16 * a.tile_macro); if (rc != ILM_OK) return rc; }
     c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
-    HIP_TRY(launch_sphere_lights_prepared(a, c->d_recs, c->main()));
+    HIP_TRY(launch_sphere_lights_prepared(a, c->d_recs.p, c->main()));
     HIP_TRY(light_pass_queued(c, f, g));
     if (stats) {
         unsigned long long host[3] = { 0, 0, 0 };

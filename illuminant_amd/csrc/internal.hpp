@@ -394,11 +394,17 @@ struct HistogramLaunch {
 int histogram_blocks(int n);
 size_t histogram_work_bytes();
 hipError_t launch_histogram(const HistogramLaunch& a, hipStream_t stream);
+// One block of grow-on-demand device scratch: grown by api.hip's `reserve`, freed by the destroy entry point of its owner (no destructor:
+// those may run while the process is torn down).  `bytes` is what was allocated; a capacity in elements is bytes / sizeof(T).
+struct DeviceScratch {
+    void* p = nullptr; size_t bytes = 0;
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
 struct BrightnessScratch {
-    float* level = nullptr; size_t level_cap = 0;    // floats
-    float* mip = nullptr; size_t mip_cap = 0;        // floats, both halves
-    uint32_t* work = nullptr;
-    float* partials = nullptr; size_t partials_cap = 0;      // floats; 256 doubles (the buckets' sums) lie in front of them
+    DeviceScratch level;         // floats
+    DeviceScratch mip;           // floats, both halves
+    DeviceScratch work;          // histogram_work_bytes()
+    DeviceScratch partials;      // 256 doubles (the buckets' sums), then 256 floats per workgroup
 };
 
 // ---- particle rasterisation (raster.hip) ------------------------------------------------------------------------
