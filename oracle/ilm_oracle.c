@@ -743,13 +743,13 @@ float orc_sample_distance_field(const float pos[3], const IlmDistanceFieldUnifor
 }
 
 /* estimateNormal4, VisualizeCommon.fxh:44-63 with VISUALIZE_TEXEL (:8-15) */
-static f3 estimate_normal4(f3 position, const IlmDistanceFieldUniforms* df, const OrcTexture* sdf) {
+static f3 estimate_normal4(f3 position, const IlmDistanceFieldUniforms* df, const OrcTexture* sdf, SdfCounter* ctr) {
     f3 texel = v3(df->ConeAndMisc.w, df->StepAndMisc2.w, df->Extent.z / fmaxf(df->TextureSliceCount.w, 1.0f));
     static const float W[4][3] = { { 1, -1, -1 }, { -1, -1, 1 }, { -1, 1, -1 }, { 1, 1, 1 } };
     f3 result = v3(0, 0, 0);
     for (int i = 0; i < 4; i++) {
         f3 w = v3(W[i][0], W[i][1], W[i][2]);
-        float s = sample_distance_field_ex(v3add(position, v3mul(w, texel)), df, sdf, NULL);
+        float s = sample_distance_field_ex(v3add(position, v3mul(w, texel)), df, sdf, ctr);
         result = v3add(result, v3scale(w, s));
     }
     return v3norm(result);
@@ -856,10 +856,20 @@ static void update_slot(f4* pos, f4* vel, const f4* attr, f4* rc, f4* rd, float 
 
 /* PS_Update, UpdateParticleSystemWithDistanceField.fx:29-147 */
 
+/* orc_update_sdf_samples: the sampleDistanceFieldEx calls of the collision updates since the count was last fetched (the device keeps
+ * the same count, ilm_debug_step_sdf_samples) */
+static uint64_t g_update_sdf_samples;
+
+uint64_t orc_update_sdf_samples(void) {
+    uint64_t n = g_update_sdf_samples;
+    g_update_sdf_samples = 0;
+    return n;
+}
+
 static void update_df_slot(f4* pos, f4* vel, const f4* attr, f4* rc, f4* rd, float x, float y,
                            const IlmParticleSystemUniforms* sys, const IlmUpdateParams* p,
                            const f4* ramp, int ramp_w, int ramp_h,
-                           const IlmDistanceFieldUniforms* df, const OrcTexture* sdf) {
+                           const IlmDistanceFieldUniforms* df, const OrcTexture* sdf, SdfCounter* ctr) {
     f4 old_position = *pos, old_velocity = *vel;
     const f4 zero = v4(0, 0, 0, 0);
     if (old_position.w <= 0.0f) {
@@ -884,7 +894,7 @@ static void update_df_slot(f4* pos, f4* vel, const f4* attr, f4* rc, f4* rd, flo
     f3 old_xyz = xyz(old_position);
     f3 collision_position = v3(0, 0, 0), new_position = old_xyz;
 
-    float initial_distance = sample_distance_field_ex(old_xyz, df, sdf, NULL);
+    float initial_distance = sample_distance_field_ex(old_xyz, df, sdf, ctr);
     int was_colliding = initial_distance < collision_distance;
     float travel_distance = fmaxf(0.0f, fminf(initial_distance, v3len(scaled_velocity)));
     int step_count = DF_MAX_STEP_COUNT;
@@ -895,7 +905,7 @@ static void update_df_slot(f4* pos, f4* vel, const f4* attr, f4* rc, f4* rd, flo
 
     for (int i = 0; i < step_count; i++) {
         f3 test_position = v3add(old_xyz, v3scale(unit_vector, travel_distance));
-        float step_distance = sample_distance_field_ex(test_position, df, sdf, NULL);
+        float step_distance = sample_distance_field_ex(test_position, df, sdf, ctr);
         if (step_distance < collision_distance) {
             collided = 1;
             collision_position = test_position;
@@ -919,7 +929,7 @@ static void update_df_slot(f4* pos, f4* vel, const f4* attr, f4* rc, f4* rd, flo
 
         f3 normal = v3(0, 0, 0);
         if (bounce || redirect)
-            normal = estimate_normal4(collision_position, df, sdf);
+            normal = estimate_normal4(collision_position, df, sdf, ctr);
 
         float escape_speed = fminf(sys_max_velocity(sys), sys->CollisionSettings.x);
 
@@ -973,16 +983,21 @@ static void update_rows(IlmFloat4* pos, IlmFloat4* vel, const IlmFloat4* attr,
                         const IlmParticleSystemUniforms* sys, const IlmUpdateParams* p,
                         const IlmFloat4* life_ramp, int32_t ramp_w, int32_t ramp_h,
                         const IlmDistanceFieldUniforms* df, const OrcTexture* sdf) {
+    SdfCounter ctr = { 0 };
     for (int y = y0; y < y1; y++)
         for (int x = 0; x < chunk_size; x++) {
             int i = y * chunk_size + x;
             if (df && sdf)
                 update_df_slot(&pos[i], &vel[i], &attr[i], &render_color[i], &render_data[i], (float)x, (float)y,
-                               sys, p, life_ramp, ramp_w, ramp_h, df, sdf);
+                               sys, p, life_ramp, ramp_w, ramp_h, df, sdf, &ctr);
             else
                 update_slot(&pos[i], &vel[i], &attr[i], &render_color[i], &render_data[i], (float)x, (float)y,
                             sys, p, life_ramp, ramp_w, ramp_h);
         }
+    if (ctr.samples) {
+        #pragma omp atomic
+        g_update_sdf_samples += ctr.samples;
+    }
 }
 
 void orc_update(IlmFloat4* pos, IlmFloat4* vel, const IlmFloat4* attr,

@@ -60,6 +60,8 @@ void orc_update(IlmFloat4* pos, IlmFloat4* vel, const IlmFloat4* attr,
                 const IlmDistanceFieldUniforms* df, const OrcTexture* sdf /* both NULL => UpdatePositions */);
 void orc_erase(IlmFloat4* pos, IlmFloat4* vel, IlmFloat4* render_color, IlmFloat4* render_data, int32_t chunk_size);
 uint32_t orc_count_live(const IlmFloat4* pos, int32_t slots, int32_t saturate16);
+/* fetch and clear: the sampleDistanceFieldEx calls of the collision updates (orc_update, orc_step) since the last fetch */
+uint64_t orc_update_sdf_samples(void);
 
 /* one ParticleSystem.Update over a table of chunks; planes[c][0..4] = pos, vel, attr, rc, rd */
 void orc_step(IlmFloat4** planes, int32_t chunk_count, int32_t chunk_size,

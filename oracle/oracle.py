@@ -74,6 +74,7 @@ def lib():
         _lib.orc_decode_distance.argtypes = [C.c_float, C.c_float]
         _lib.orc_evaluate_area.restype = C.c_float
         _lib.orc_count_live.restype = C.c_uint32
+        _lib.orc_update_sdf_samples.restype = C.c_uint64
         _lib.orc_spawner_begin_tick.restype = C.c_int32
         _lib.orc_spawner_begin_tick.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_double, C.c_int32]
         _lib.orc_distance_field_layout.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_double, C.c_int32, C.c_void_p]
@@ -174,6 +175,12 @@ def reference_constants():
 
 def count_live(pos, saturate16=False):
     return int(lib().orc_count_live(_f4(pos), pos.shape[0], 1 if saturate16 else 0))
+
+
+def update_sdf_samples():
+    """Fetch and clear the sampleDistanceFieldEx calls of the collision updates (update, step) since the last fetch -- what
+    ilm_debug_step_sdf_samples counts on the device."""
+    return int(lib().orc_update_sdf_samples())
 
 
 def step(chunks, chunk_size, rnd, desc, life_ramp=None, sdf=None, want_counts=False, spawn_positions=None, feedback_sources=None,

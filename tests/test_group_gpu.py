@@ -499,15 +499,16 @@ def test_asynchronous_rccl_exchange_at_world_one(ctx):
     sdf.close(); g.close()
 
 
-@pytest.mark.parametrize("members,gather", [(2, native.GATHER_PEER), (3, native.GATHER_PEER), (1, native.GATHER_RCCL)])
-def test_gather_chunks_lights_every_strip_with_every_ranks_particles(ctx, members, gather):
+@pytest.mark.parametrize("members,gather,cs", [(2, native.GATHER_PEER, 16), (3, native.GATHER_PEER, 16), (1, native.GATHER_RCCL, 16), (2, native.GATHER_PEER, 48)],
+                         ids=["2-1", "3-1", "1-2", "2-1-48"])          # 48: a stride with padding (2 304 slots in 3 072)
+def test_gather_chunks_lights_every_strip_with_every_ranks_particles(ctx, members, gather, cs):
     """cfg5 joins P and L and chunk c lives on rank c % world: a member's strip sees only its own chunks' particles as
     lights until the table is made whole.  ilm_group_gather_chunks moves Pos+Life and RenderColor of every chunk into every member's
     gathered system (chunk order = table order), ilm_render_particle_lights over that system lights the member's strip, the strips are
     exchanged: every member's frame equals the single-context particle-light frame BIT FOR BIT (same records in the same order)."""
     from tests import lights_common as lc
     from tests.test_lights_ext_gpu import particle_scene, small_field
-    w, h, cs, n_chunks = 160, 112, 16, 5
+    w, h, n_chunks = 160, 112, 5
     atlas, dfu = small_field()
     env = scenes.environment()
     chunks = particle_scene(cs, n_chunks, w, h)

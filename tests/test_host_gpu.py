@@ -81,10 +81,11 @@ def test_spawner_slot_allocation_matches_the_fixture(H, hctx):
         assert total == case["trace"][-1]["total_spawned_after"]
 
 
-def test_update_loop_matches_the_oracle_step_by_step(H, hctx, oracle):
+@pytest.mark.parametrize("cs", [64, 48])
+def test_update_loop_matches_the_oracle_step_by_step(H, hctx, oracle, cs):
     """SimpleParticles-like system (Spawner + Gravity + Noise, Scenes/SimpleParticles.cs) for 12 Updates; the oracle
-    replays the very descriptors the host mirror launched, pass by pass."""
-    cs = 64
+    replays the very descriptors the host mirror launched, pass by pass.  48: a chunk size that is no power of two (the spawner fills
+    more, smaller chunks)."""
     n = cs * cs
     engine, tp, rnd = make_engine(H, hctx, cs)
     cfg = H.ParticleSystemConfiguration()

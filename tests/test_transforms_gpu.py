@@ -60,9 +60,7 @@ def compare(got, want, got_counts, want_counts, planes=(0, 1, 2, 3, 4)):
             assert_close(got[c][k], want[c][k], "chunk %d plane %d" % (c, k))
 
 
-@pytest.mark.parametrize("area_type", [0, 1, 2, 3, 4, 5])
-def test_matrix_multiply_matches_oracle(ctx, oracle, area_type):
-    cs = 64
+def check_matrix_multiply(ctx, oracle, area_type, cs=64, n_chunks=2):
     d = abi.StepDesc()
     d.FirstChunk, d.ChunkCount = 0, -1
     d.System = scenes.system_uniforms(cs, friction=0.05, max_velocity=500.0, life_decay=1.0)
@@ -74,13 +72,16 @@ def test_matrix_multiply_matches_oracle(ctx, oracle, area_type):
                                                                                 strength=0.9, category_filter=(0.0, 2.0))
     d.Ops[0].u.MatrixMultiply = scenes.matrix_multiply_params(ar, random_matrix(5, perspective=(area_type % 2 == 1)), random_matrix(6),
                                                               None if area_type == 3 else 10.0)
-    got, want, gc, wc = run_both(ctx, oracle, cs, 2, d)
+    got, want, gc, wc = run_both(ctx, oracle, cs, n_chunks, d)
     compare(got, want, gc, wc)
 
 
-@pytest.mark.parametrize("replace", [True, False])
-def test_spatial_noise_matches_oracle(ctx, oracle, replace):
-    cs = 64
+@pytest.mark.parametrize("area_type", [0, 1, 2, 3, 4, 5])
+def test_matrix_multiply_matches_oracle(ctx, oracle, area_type):
+    check_matrix_multiply(ctx, oracle, area_type)
+
+
+def check_spatial_noise(ctx, oracle, replace, cs=64, n_chunks=2):
     d = abi.StepDesc()
     d.FirstChunk, d.ChunkCount = 0, -1
     d.System = scenes.system_uniforms(cs, friction=0.05, max_velocity=500.0, life_decay=1.0)
@@ -92,8 +93,13 @@ def test_spatial_noise_matches_oracle(ctx, oracle, replace):
                                 (0.12 * 253, 0.55 * 127), 0.35, 10.0, replace, position=((-0.5,) * 4, (0,) * 4, (3.0, 2.0, 1.0, 0.0)),
                                 velocity=((-0.5,) * 3, (0,) * 3, (40.0, 30.0, 5.0)), speed=(-0.5, 0.0, 6.0))
     d.Ops[0].u.SpatialNoise = scenes.spatial_noise_params(noise, (13.0, 7.0))
-    got, want, gc, wc = run_both(ctx, oracle, cs, 2, d)
+    got, want, gc, wc = run_both(ctx, oracle, cs, n_chunks, d)
     compare(got, want, gc, wc)
+
+
+@pytest.mark.parametrize("replace", [True, False])
+def test_spatial_noise_matches_oracle(ctx, oracle, replace):
+    check_spatial_noise(ctx, oracle, replace)
 
 
 def test_spatial_noise_that_changes_life_and_single_pass_entry(ctx, oracle):
@@ -149,10 +155,9 @@ def test_all_five_transform_types_fused(ctx, oracle):
     compare(got, want, gc, wc)
 
 
-def test_position_buffer_spawner_matches_oracle(ctx, oracle):
-    cs = 64
+def check_position_buffer_spawner(ctx, oracle, cases, cs=64, n_chunks=2):
     positions = [(40.0 + 30.0 * i, 20.0 + 11.0 * i, float(i)) for i in range(9)]
-    for (rate, loop) in ((None, True), (3.0, True), (2.5, False)):
+    for (rate, loop) in cases:
         p, buf = scenes.position_buffer_spawn_params(cs, 700, 1500, 4321, (0.42 * 253, 0.77 * 127), positions, life_constant=3.3,
                                                      position=((0, 0, 0), (9, 5, 2), (0, 0, 0), scenes.FORMULA_SPHERICAL),
                                                      velocity=((1, 2, 3), (60, 60, 60), (0, 0, 0), scenes.FORMULA_SPHERICAL),
@@ -166,8 +171,12 @@ def test_position_buffer_spawner_matches_oracle(ctx, oracle):
         d.Spawns[0].ChunkIndex = 1
         d.Spawns[0].Kind = abi.SPAWN_POSITION_BUFFER
         d.Spawns[0].Params = p
-        got, want, gc, wc = run_both(ctx, oracle, cs, 2, d, dead_fraction=0.6, spawn_positions=buf)
+        got, want, gc, wc = run_both(ctx, oracle, cs, n_chunks, d, dead_fraction=0.6, spawn_positions=buf)
         compare(got, want, gc, wc)
+
+
+def test_position_buffer_spawner_matches_oracle(ctx, oracle):
+    check_position_buffer_spawner(ctx, oracle, ((None, True), (3.0, True), (2.5, False)))
 
 
 @pytest.mark.parametrize("divisor,top_left,size_px,multiply", [(1, None, None, True), (2, None, None, False), (3, (5, 3), (30, 18), True),
@@ -175,7 +184,10 @@ def test_position_buffer_spawner_matches_oracle(ctx, oracle):
 def test_pattern_spawner_matches_oracle(ctx, oracle, divisor, top_left, size_px, multiply):
     """PatternSpawner.fx:21-97 on a 37 x 23 texture with a full mip chain: whole-instance and single-row spawns, every Divisor's mip
     level, a sub-rectangle, spherical position / velocity formulas, the alpha discard."""
-    cs = 64
+    check_pattern_spawner(ctx, oracle, divisor, top_left, size_px, multiply)
+
+
+def check_pattern_spawner(ctx, oracle, divisor, top_left, size_px, multiply, cs=64, n_chunks=2):
     tw, th = 37, 23
     texels = scenes.uniform(900, (th, tw, 4), 0.0, 1.0)
     texels[::5, ::7, 3] = 0.0          # some transparent pixels: rejected by the attribute discard threshold
@@ -198,7 +210,8 @@ def test_pattern_spawner_matches_oracle(ctx, oracle, divisor, top_left, size_px,
         d.Spawns[0].Kind = abi.SPAWN_PATTERN
         d.Spawns[0].Params = p
         d.Spawns[0].Pattern = scenes.pattern_params(tw, th, divisor, current_row, top_left, size_px, multiply_color_constant=multiply)
-        got, want, gc, wc = run_both(ctx, oracle, cs, 2, d, dead_fraction=1.0, spawn_pattern=levels)
+        assert first + count <= cs * cs
+        got, want, gc, wc = run_both(ctx, oracle, cs, n_chunks, d, dead_fraction=1.0, spawn_pattern=levels)
         compare(got, want, gc, wc)
         assert 0 < wc[1] <= count      # something spawned; transparent / out-of-texture particles did not
 
