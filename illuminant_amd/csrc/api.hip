@@ -3036,9 +3036,10 @@ int32_t reserve_light_recs(Ctx* c, int light_count) {
     return reserve(c, c->d_recs, kLightRecBytes * (size_t)light_count, kLightRecBytes * (size_t)(light_count < 256 ? 256 : light_count * 2));
 }
 
-// shared by the three light passes: resource checks + the launch descriptor
+// shared by the light passes: resource checks + the launch descriptor.  with_cells = false: the field as the plain view of the general
+// sampler, no cell array (the directional pass has no in-volume loop)
 int32_t fill_light_launch(Ctx* c, const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf,
-                          IlmHandle hlightmap, int32_t row_begin, int32_t row_end, LightLaunch* a) {
+                          IlmHandle hlightmap, int32_t row_begin, int32_t row_end, LightLaunch* a, bool with_cells = true) {
     Lightmap* m = from_handle<Lightmap>(hlightmap, kMagicLightmap);
     if (!m) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
     GBuffer* g = nullptr; Sdf* f = nullptr;
@@ -3055,7 +3056,14 @@ int32_t fill_light_launch(Ctx* c, const IlmEnvironment* env, const IlmDistanceFi
     a->gbuffer.texels = g ? g->texels : nullptr;
     a->gbuffer.width = g ? g->width : 0; a->gbuffer.height = g ? g->height : 0; a->gbuffer.format = g ? g->format : 0;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(borrowed_trace_view(c, f, g, df, &a->sdf));
+    if (with_cells) {
+        HIP_TRY(borrowed_trace_view(c, f, g, df, &a->sdf));
+    } else {
+        static_cast<SdfView&>(a->sdf) = make_sdf_view(f, df);
+        a->sdf.cells = nullptr; a->sdf.cells_bytes = 0; a->sdf.slice_w = 0; a->sdf.slice_h = 0;
+        if (f && f->ctx != c) HIP_TRY(shared_before_read(f->shared, f->ctx, c));      // a sibling's resources: behind everything their owner has queued
+        if (g && g->ctx != c) HIP_TRY(shared_before_read(g->shared, g->ctx, c));
+    }
     for (int i = 0; i < 4; i++) a->ambient[i] = 0.0f;
     a->lightmap = m->texels; a->width = m->width; a->height = m->height; a->format = m->format;
     a->row_begin = row_begin; a->row_end = row_end;
@@ -3769,6 +3777,59 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     { const int32_t rc = plan_group_order(c, &a, lights, light_count, 16 * a.tile_macro); if (rc != ILM_OK) return rc; }
     c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
     HIP_TRY(launch_sphere_lights_prepared(a, c->d_recs.p, c->main()));
+    HIP_TRY(light_pass_queued(c, f, g));
+    if (stats) {
+        unsigned long long host[3] = { 0, 0, 0 };
+        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
+        HIP_TRY(hipStreamSynchronize(c->main()));
+        stats->SdfSamples = host[0]; stats->PixelLightPairs = host[1]; stats->TracedPairs = host[2];
+    }
+    return ILM_OK;
+}
+
+int32_t ilm_render_directional_lights(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,
+                                      const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf, const float ambient[4],
+                                      IlmHandle hlightmap, int32_t row_begin, int32_t row_end, IlmRenderStats* stats) {
+    ILM_TRACE_RANGE("ilm_render_directional_lights");
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    if (light_count < 0 || (light_count > 0 && !lights)) return fail(ILM_ERR_INVALID_ARGUMENT, "bad light array");
+    // the footprint is the rectangle LightPosition1.xy .. LightPosition2.xy: a NaN corner or an inverted axis names none
+    for (int i = 0; i < light_count; i++) {
+        const IlmFloat4& p1 = lights[i].LightPosition1; const IlmFloat4& p2 = lights[i].LightPosition2;
+        if (p1.x != p1.x || p1.y != p1.y || p2.x != p2.x || p2.y != p2.y)
+            return fail(ILM_ERR_INVALID_ARGUMENT, "directional light %d: its bounds are NaN", i);
+        if (p1.x > p2.x || p1.y > p2.y)
+            return fail(ILM_ERR_INVALID_ARGUMENT, "directional light %d: bounds inverted, LightPosition1 (%g, %g) exceeds LightPosition2 (%g, %g)", i,
+                        (double)p1.x, (double)p1.y, (double)p2.x, (double)p2.y);
+    }
+    LightLaunch a = {};
+    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, false); if (rc != ILM_OK) return rc; }
+    Sdf* f = hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr;
+    GBuffer* g = hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr;
+    if (stats) stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0;
+
+    { const int32_t rc = reserve_light_recs(c, light_count); if (rc != ILM_OK) return rc; }
+    if (light_count > 0) {
+        const void* staged = nullptr; int slot = 0;
+        int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
+        if (rc != ILM_OK) return rc;
+        HIP_TRY(launch_prepare_directional_lights(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, c->d_recs.p, c->main()));
+        rc = staged_small_done(c, slot);
+        if (rc != ILM_OK) return rc;
+    }
+    a.light_count = light_count;
+    for (int i = 0; i < 4; i++) a.ambient[i] = ambient ? ambient[i] : 0.0f;
+    a.accumulate = ambient ? 0 : 1;
+    a.ramp = RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h };
+    if (stats) {
+        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
+        a.stats = c->d_stats;
+    }
+    // (ilm_debug_last_light_launch: one workgroup per 16 x 16 tile of the rows, no split, no tile map)
+    c->last_light_blocks = ((a.width + kLightTile - 1) / kLightTile) * ((row_end - row_begin + kLightTile - 1) / kLightTile);
+    c->last_light_split = 1; c->last_light_macro = 0;
+    HIP_TRY(launch_directional_lights_prepared(a, c->d_recs.p, c->main()));
     HIP_TRY(light_pass_queued(c, f, g));
     if (stats) {
         unsigned long long host[3] = { 0, 0, 0 };

@@ -233,6 +233,12 @@ TraceGate make_trace_gate(const IlmDistanceFieldUniforms& df, const SdfView& sdf
 hipError_t launch_prepare_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
                                  const SdfView& sdf, void* recs, hipStream_t stream);
 hipError_t launch_sphere_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream);
+// Directional lights (DirectionalLight.fx): the records (count * kLightRecBytes) and the full-frame pass over a's rows.  Of the launch
+// descriptor the pass reads the frame, the resources, ambient / accumulate / blend_fp16, the ramp, stats and the mirrors; the sphere
+// pass's tile map and light split do not apply (a footprint is a rectangle: four compares per pixel and light).
+hipError_t launch_prepare_directional_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
+                                             void* recs, hipStream_t stream);
+hipError_t launch_directional_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream);
 int light_launch_blocks(const LightLaunch& a);    // workgroups of the tile kernel's launch for a (split / taper included)
 int light_block_slots(const LightLaunch& a);      // block slots per XCD of the tile kernel's launch over a's rows
 

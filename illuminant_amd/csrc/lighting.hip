@@ -1245,6 +1245,246 @@ hipError_t launch_sphere_lights_prepared(const LightLaunch& launch, const void* 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Directional lights -- techniques DirectionalLight / DirectionalLightWithRamp, DirectionalLight.fx:19-161, drawn by
+// RenderDirectionalLightSource (LightingRenderer.cs:1256-1307) as one full-frame (or Bounds-sized) quad per light.
+// A footprint is a rectangle: no tile lists, no light split -- one thread per pixel, one wave per 8 x 8 pixels, the light loop is
+// wave-uniform over the prepared records (uniform index: scalar loads), the G-buffer texel is decoded once, the sum lives in
+// registers, the lightmap texel is read at most once (accumulate mode) and stored once.  The trace is the general loop
+// (cone_trace_loop<.., false>): the in-volume loop is not built for this pass (docs/experiments.md 7.21 has what it costs: about
+// twice the vector instructions per sample).
+// ---------------------------------------------------------------------------------------------
+constexpr float kDirectionalDotOffset = 0.35f;          // LightCommon.fxh:7 DIRECTIONAL_DOT_OFFSET
+constexpr float kDirectionalDotRampRange = 0.35f;       // LightCommon.fxh:8 DIRECTIONAL_DOT_RAMP_RANGE
+constexpr float kDirectionalSelfOcclusionHack = 1.5f;   // DirectionalLight.fx:13 SELF_OCCLUSION_HACK
+constexpr float kDirectionalTraceThreshold = 1.0f / 256.0f;      // DirectionalLight.fx:73 (lightOpacity >= 1 / 256.0)
+constexpr float kDirectionalMinimumW = 0.1f;            // DirectionalLight.fx:73, LightCommon.fxh:227 (lightDirection.w < 0.1: no direction)
+
+struct DirectionalRec {
+    float x0, y0, x1, y1;                                       // footprint in screen pixels: centre in [x0, x1) x [y0, y1)
+    float dir_x, dir_y, dir_z, dir_w;                           // Color2
+    float casts_shadows, trace_length, softness, shadow_filter; // LightProperties.xyz, EvenMoreLightProperties.x
+    float ao_radius, ao_opacity, cfg_x, cfg_y;                  // MoreLightProperties.xw; createTraceConfig: maxRadius, radiusGrowthPerPixel
+    float col_r, col_g, col_b, _pad0;                           // Color1.rgb * Color1.a
+    float _pad[12];
+};
+static_assert(sizeof(DirectionalRec) == kLightRecBytes, "a directional record fills the slot of a LightRec (reserve_light_recs)");
+
+// DirectionalLightVertexShader (DirectionalLight.fx:32-34) at the quad's two extreme corners + createTraceConfig (ConeTrace.fxh:122-139)
+// with lightRamp = (ShadowSoftness, shadowDistanceFalloff) and cone growth = ShadowRampRate (DirectionalLight.fx:77-80)
+__global__ __launch_bounds__(64) void prepare_directional_lights_kernel(const IlmLightVertex* __restrict__ lights, int count, IlmEnvironment env,
+                                                                         float max_cone_radius, DirectionalRec* __restrict__ out) {
+    const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (i >= count) return;
+    const IlmLightVertex L = lights[i];
+    DirectionalRec r = {};
+    const float sx = env.GBufferTexelSizeAndMisc.z * env.ZAndScale.z, sy = env.GBufferTexelSizeAndMisc.w * env.ZAndScale.w;
+    r.x0 = (L.LightPosition1.x - env.ViewportPosition[0]) * sx; r.y0 = (L.LightPosition1.y - env.ViewportPosition[1]) * sy;
+    r.x1 = (L.LightPosition2.x - env.ViewportPosition[0]) * sx; r.y1 = (L.LightPosition2.y - env.ViewportPosition[1]) * sy;
+    r.dir_x = L.Color2.x; r.dir_y = L.Color2.y; r.dir_z = L.Color2.z; r.dir_w = L.Color2.w;
+    r.casts_shadows = L.LightProperties.x; r.trace_length = L.LightProperties.y; r.softness = L.LightProperties.z;
+    r.shadow_filter = L.EvenMoreLightProperties.x;
+    r.ao_radius = L.MoreLightProperties.x; r.ao_opacity = L.MoreLightProperties.w;
+    const float max_radius = clampf(L.LightProperties.z, ref::kMinConeRadius, max_cone_radius);
+    r.cfg_x = max_radius;
+    r.cfg_y = max_radius / fmaxf(L.MoreLightProperties.y, 16.0f) * L.LightProperties.w;
+    r.col_r = L.Color1.x * L.Color1.w; r.col_g = L.Color1.y * L.Color1.w; r.col_b = L.Color1.z * L.Color1.w;
+    out[i] = r;
+}
+
+// SampleFromRamp (RampCommon.fxh:15-17): channel r at (x, v = 0) through RampTextureSampler -- the sphere pass's lookup (shade_light:
+// tex2Dlod level 0, LINEAR, U CLAMP, V WRAP) with its v fixed at 0.  A COPY of shade_light's tap and weight arithmetic, to be kept in
+// step with it: one helper for both was built in two forms (taps returned in a struct; columns, rows and weights through references) and
+// each changed the instruction streams of sphere_lights_kernel and light_probes_kernel (tools/isa_compare.py: 10 of 21 kernels `diff`,
+// same instruction counts, another schedule), which the existing passes are held not to do.  tests/test_directional_gpu.py holds this
+// copy to the oracle's lookup, tests/test_lighting_gpu.py the other.
+ILM_DEV float sample_from_ramp(const RampView& ramp, float u) {
+    const int w = ramp.width, h = ramp.height;
+    const float sx = u * (float)w - 0.5f, sy = 0.0f * (float)h - 0.5f;
+    float x0f = floorf(sx);
+    const float y0f = floorf(sy);
+    const float fx = sx - x0f, fy = sy - y0f;
+    float x1f = x0f + 1.0f;
+    x0f = (x0f >= 0.0f) ? x0f : 0.0f; x0f = fminf(x0f, (float)(w - 1));
+    x1f = (x1f >= 0.0f) ? x1f : 0.0f; x1f = fminf(x1f, (float)(w - 1));
+    const int x0 = (int)x0f, x1 = (int)x1f;
+    const int y0 = wrap_index(y0f, h), y1 = (y0 + 1 == h) ? 0 : y0 + 1;
+    return lerp(lerp(ramp.texels[y0 * w + x0].x, ramp.texels[y0 * w + x1].x, fx), lerp(ramp.texels[y1 * w + x0].x, ramp.texels[y1 * w + x1].x, fx), fy);
+}
+
+// One directional light on one shaded point: DirectionalLightPixelShader / ...WithRamp (DirectionalLight.fx:95-161) over
+// DirectionalLightPixelCore (:52-93), after the footprint test.  Returns false when the shader discards (fullbright, the shadow
+// filter, clip(!visible)); otherwise the opacity that multiplies color.rgb * color.a.  Unlike the sphere light's shader this one has no
+// opacity discard: a visible pixel with opacity 0 is blended (alpha + 1).
+template <int FMT, bool STATS>
+ILM_DEV bool shade_directional(const Pixel& P, const DirectionalRec& L, const TraceField& F, bool have_sdf, const RampView& ramp, LightStats& st,
+                               float& opacity) {
+    const bool filtered = (L.shadow_filter < 0.0f) ? false : ((L.shadow_filter > 0.5f) != P.enable_shadows);      // checkShadowFilter, LightCommon.fxh:146-152
+    if (P.fullbright || filtered)
+        return false;
+    const bool visible = P.shaded.x > -9999.0f;
+    if (!visible)      // clip(visible ? 1 : -1), :91 -- nothing the core computes for such a pixel is seen
+        return false;
+    const float casts = L.casts_shadows * (P.enable_shadows ? 1.0f : 0.0f);
+    const bool directed = L.dir_w >= kDirectionalMinimumW;
+    // computeDirectionalLightOpacity -> computeNormalFactorEx, LightCommon.fxh:154-165,224-231
+    float light_opacity = 1.0f;
+    if (directed && ((P.normal.x != 0.0f) || (P.normal.y != 0.0f) || (P.normal.z != 0.0f))) {
+        const float d = dot3(mk3(L.dir_x, L.dir_y, L.dir_z) * -1.0f, P.normal);
+        light_opacity = pow_pos(sat((d + kDirectionalDotOffset) / kDirectionalDotRampRange), ref::kDotExponent);
+    }
+    // computeAO, AOCommon.fxh:1-19 (aoRadius scaled by max(0, normal.z), :68)
+    const float ao_radius = L.ao_radius * fmaxf(0.0f, P.normal.z);
+    if ((ao_radius >= 0.5f) && have_sdf) {
+        const float distance = sample_distance_field<FMT>(mk3(P.shaded.x, P.shaded.y, P.shaded.z + P.normal.z * ao_radius), F.df, F.sdf);
+        if (STATS) st.samples++;
+        float r = 1.0f - sat(clampf(distance, 0.0f, ao_radius) / ao_radius);
+        r *= r;
+        r = 1.0f - r;
+        light_opacity *= (1.0f - L.ao_opacity) + (r * L.ao_opacity);
+    }
+    // coneTrace towards the fake light centre, :73-83 + ConeTrace.fxh:141-191
+    const bool trace = (casts != 0.0f) && (light_opacity >= kDirectionalTraceThreshold) && directed;
+    if (trace) {
+        if (STATS && have_sdf) st.traced++;
+        f3 start = P.shaded + (P.normal * kDirectionalSelfOcclusionHack);
+        const f3 centre = P.shaded - (mk3(L.dir_x, L.dir_y, L.dir_z) * L.trace_length);
+        const f3 tv = centre - start;
+        const float trace_length = len3(tv);
+        const float data_y = fmaxf(trace_length - L.softness, 1.0f);
+        float data_x = ref::kTraceInitialOffsetPx;
+        float data_z = 1.0f;
+        const float cfg_z = fmaxf(1.0f, F.df.Packed1.w);
+        float steps_remaining = F.df.StepAndMisc2.x;
+        // (two VGPRs keep the cone configuration resident across the loop, as in shade_light)
+        float cone_max_radius = L.cfg_x, cone_growth = L.cfg_y;
+        asm volatile("" : "+v"(cone_max_radius), "+v"(cone_growth));
+        f3 dir = mk3(tv.x / trace_length, tv.y / trace_length, tv.z / trace_length);
+        // (the sampler treats a NaN coordinate as 0: hoisted as in shade_light's general path)
+        if ((start.x != start.x) || (dir.x != dir.x)) { start.x = 0.0f; dir.x = 0.0f; }
+        if ((start.y != start.y) || (dir.y != dir.y)) { start.y = 0.0f; dir.y = 0.0f; }
+        if ((start.z != start.z) || (dir.z != dir.z)) { start.z = 0.0f; dir.z = 0.0f; }
+        cone_trace_loop<FMT, STATS, false>(start, dir, data_y, cfg_z, cone_growth, cone_max_radius, F, data_x, data_z, steps_remaining, have_sdf, st);
+        const float visibility = fminf(data_z, steps_remaining / ref::kMaxStepRampWindow);
+        light_opacity *= pow_pos(sat(div_with_rcp(sat(visibility - ref::kFullyShadowedThreshold), kVisibilityRange, kVisibilityRangeRcp)), F.df.ConeAndMisc.z);
+    }
+    if (ramp.texels != nullptr)
+        light_opacity = sample_from_ramp(ramp, light_opacity);
+    opacity = light_opacity;
+    return true;
+}
+
+template <int FMT, bool STATS>
+__global__ __launch_bounds__(kLightThreads) void directional_lights_kernel(const LightLaunch a, const DirectionalRec* __restrict__ recs, int tiles_x) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int tile_x = (int)blockIdx.x % tiles_x, tile_y = (int)blockIdx.x / tiles_x;
+    const int px = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
+    const int py = a.row_begin + tile_y * kTile + (wave >> 1) * 8 + (lane >> 3);
+    const bool in_image = (px < a.width) && (py < a.row_end);
+    if (__builtin_amdgcn_ballot_w64(in_image) == 0ull)
+        return;
+    Pixel P = sample_gbuffer((float)px, (float)py, a.env, a.gbuffer);
+    P.origin_x = 0; P.origin_y = 0; P.start_inside = false;
+    const float cxp = (float)px + 0.5f, cyp = (float)py + 0.5f;
+    const bool have_sdf = (a.sdf.texels != nullptr) && (a.df.Extent.x > 0.0f);
+    const InsideConsts no_table = {};
+    const TraceField field = { a.df, a.sdf, no_table, nullptr };
+    const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
+    auto through_half = [](float v) { return __half2float(__float2half_rn(v)); };
+    // what the lights are added to: the clear colour, or the lightmap's contents; in the fp16-per-light model it passes through fp16
+    // and starts the chain of roundings, otherwise the call's sum (from zero, in list order) is added to it at the end
+    auto base_value = [&]() -> float4 {
+        float4 v = mk4(a.ambient[0], a.ambient[1], a.ambient[2], a.ambient[3]);
+        if (a.accumulate != 0 && in_image) {
+            if (a.format == ILM_LIGHTMAP_FLOAT4) v = load_target<ILM_LIGHTMAP_FLOAT4>(a.lightmap, o);
+            else if (a.format == ILM_LIGHTMAP_HALF4) v = load_target<ILM_LIGHTMAP_HALF4>(a.lightmap, o);
+            else v = load_target<ILM_LIGHTMAP_RGBA8>(a.lightmap, o);
+        }
+        if (a.blend_fp16 != 0) v = mk4(through_half(v.x), through_half(v.y), through_half(v.z), through_half(v.w));
+        return v;
+    };
+    const bool blend_fp16 = a.blend_fp16 != 0;
+    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if (blend_fp16) { const float4 v = base_value(); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
+    LightStats st;
+    const int light_count = a.light_count;
+    for (int k = 0; k < light_count; k++) {
+        const DirectionalRec& L = recs[k];
+        const float x0 = L.x0, y0 = L.y0, x1 = L.x1, y1 = L.y1;
+        const bool covered = in_image & (cxp >= x0) & (cxp < x1) & (cyp >= y0) & (cyp < y1);
+        // a wave none of whose lanes the light covers leaves on a scalar branch (r06's finding for particle lights)
+        if (__builtin_amdgcn_ballot_w64(covered) == 0ull)
+            continue;
+        if (!covered)
+            continue;
+        if (STATS) st.pairs++;
+        float opacity;
+        if (!shade_directional<FMT, STATS>(P, L, field, have_sdf, a.ramp, st, opacity))
+            continue;
+        const float cr = L.col_r * opacity, cg = L.col_g * opacity, cb = L.col_b * opacity;
+        if (blend_fp16) {
+            acc_r = through_half(acc_r + through_half(cr));
+            acc_g = through_half(acc_g + through_half(cg));
+            acc_b = through_half(acc_b + through_half(cb));
+            acc_a = through_half(acc_a + 1.0f);
+        } else {
+            acc_r += cr; acc_g += cg; acc_b += cb; acc_a += 1.0f;
+        }
+    }
+    if (!blend_fp16) {
+        const float4 v = base_value();
+        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+    }
+    if (in_image) {
+        const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
+        auto store_texel = [&](void* base) {
+            if (a.format == ILM_LIGHTMAP_FLOAT4) store_target<ILM_LIGHTMAP_FLOAT4>(base, o, v);
+            else if (a.format == ILM_LIGHTMAP_HALF4) store_target<ILM_LIGHTMAP_HALF4>(base, o, v);
+            else store_target<ILM_LIGHTMAP_RGBA8>(base, o, v);
+        };
+        store_texel(a.lightmap);
+        for (int m = 0; m < a.mirror_count; m++) store_texel(a.mirrors[m]);      // store-mode exchange of a group lightmap, as the sphere pass
+    }
+    if (STATS) {
+        for (int off = 32; off > 0; off >>= 1) {
+            st.samples += __shfl_down(st.samples, off);
+            st.pairs += __shfl_down(st.pairs, off);
+            st.traced += __shfl_down(st.traced, off);
+        }
+        if (lane == 0) {
+            atomicAdd(&a.stats[0], st.samples);
+            atomicAdd(&a.stats[1], st.pairs);
+            atomicAdd(&a.stats[2], st.traced);
+        }
+    }
+}
+
+hipError_t launch_prepare_directional_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
+                                             void* recs, hipStream_t stream) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(prepare_directional_lights_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, lights, count, env, df.ConeAndMisc.x,
+                       reinterpret_cast<DirectionalRec*>(recs));
+    return hipGetLastError();
+}
+
+hipError_t launch_directional_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
+    const int rows = a.row_end - a.row_begin;
+    if (rows <= 0 || a.width <= 0) return hipSuccess;
+    if (a.light_count == 0 && a.accumulate != 0) return hipSuccess;      // nothing to add: no texel (and no mirror) would change
+    const int tiles_x = (a.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
+    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y), block(kLightThreads);
+    const DirectionalRec* r = reinterpret_cast<const DirectionalRec*>(recs);
+    const bool stats = a.stats != nullptr;
+    if (a.sdf.format == ILM_SDF_FP16) {
+        if (stats) hipLaunchKernelGGL((directional_lights_kernel<ILM_SDF_FP16, true>), grid, block, 0, stream, a, r, tiles_x);
+        else hipLaunchKernelGGL((directional_lights_kernel<ILM_SDF_FP16, false>), grid, block, 0, stream, a, r, tiles_x);
+    } else {
+        if (stats) hipLaunchKernelGGL((directional_lights_kernel<ILM_SDF_UNORM16, true>), grid, block, 0, stream, a, r, tiles_x);
+        else hipLaunchKernelGGL((directional_lights_kernel<ILM_SDF_UNORM16, false>), grid, block, 0, stream, a, r, tiles_x);
+    }
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void divide_probe_kernel(const float* __restrict__ n, const float* __restrict__ d, int count,
                                                             float* __restrict__ out_fast, float* __restrict__ out_ieee) {
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;

@@ -410,6 +410,30 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("TextureRef", &SphereLightSource::TextureRef)
         .def_readwrite("Quality", &SphereLightSource::Quality)
         .def_readwrite("RampOffset", &SphereLightSource::RampOffset).def_readwrite("RampRate", &SphereLightSource::RampRate);
+    // Direction: None or three floats, normalised when set; Bounds: None or (left, top, right, bottom)
+    py::class_<DirectionalLightSource>(m, "DirectionalLightSource").def(py::init<>())
+        .def_readwrite("SortKey", &DirectionalLightSource::SortKey).def_readwrite("Enabled", &DirectionalLightSource::Enabled)
+        .def_property("Direction", [](const DirectionalLightSource& l) -> py::object { return l.Direction() ? py::cast(l3(*l.Direction())) : py::none(); },
+                      [](DirectionalLightSource& l, py::object v) { if (v.is_none()) l.SetDirection(std::nullopt); else l.SetDirection(v3(v.cast<std::vector<float>>())); })
+        .def_property("Bounds", [](const DirectionalLightSource& l) -> py::object {
+                          if (!l.Bounds) return py::none();
+                          return py::cast(std::vector<float>{ l.Bounds->TopLeft.X, l.Bounds->TopLeft.Y, l.Bounds->BottomRight.X, l.Bounds->BottomRight.Y }); },
+                      [](DirectionalLightSource& l, py::object v) {
+                          if (v.is_none()) { l.Bounds.reset(); return; }
+                          const auto b = v.cast<std::vector<float>>();
+                          l.Bounds = Bounds{ Vector2{ b.at(0), b.at(1) }, Vector2{ b.at(2), b.at(3) } }; })
+        .def_readwrite("ShadowTraceLength", &DirectionalLightSource::ShadowTraceLength)
+        .def_readwrite("ShadowSoftness", &DirectionalLightSource::ShadowSoftness)
+        .def_readwrite("ShadowRampRate", &DirectionalLightSource::ShadowRampRate)
+        VEC_PROP(DirectionalLightSource, Color, 4)
+        .def_readwrite("Opacity", &DirectionalLightSource::Opacity)
+        .def_readwrite("CastsShadows", &DirectionalLightSource::CastsShadows)
+        .def_readwrite("AmbientOcclusionRadius", &DirectionalLightSource::AmbientOcclusionRadius)
+        .def_readwrite("AmbientOcclusionOpacity", &DirectionalLightSource::AmbientOcclusionOpacity)
+        .def_readwrite("ShadowDistanceFalloff", &DirectionalLightSource::ShadowDistanceFalloff)
+        .def_readwrite("ShadowFilter", &DirectionalLightSource::ShadowFilter)
+        .def_readwrite("TextureRef", &DirectionalLightSource::TextureRef)
+        .def_readwrite("Quality", &DirectionalLightSource::Quality);
     py::class_<ReplicatedLight>(m, "ReplicatedLight").def(py::init<>())
         VEC_PROP(ReplicatedLight, Position, 3)
         .def_readwrite("Radius", &ReplicatedLight::Radius).def_readwrite("RampLength", &ReplicatedLight::RampLength)
@@ -466,6 +490,7 @@ PYBIND11_MODULE(_host, m) {
     py::class_<LightingEnvironment>(m, "LightingEnvironment").def(py::init<>())
         .def_readwrite("Lights", &LightingEnvironment::Lights)
         .def_readwrite("Replicators", &LightingEnvironment::Replicators)
+        .def_readwrite("DirectionalLights", &LightingEnvironment::DirectionalLights)
         .def_readwrite("ParticleLights", &LightingEnvironment::ParticleLights)
         .def_property_readonly("Obstructions", [](LightingEnvironment& e) -> LightObstructionCollection& { return e.Obstructions; }, py::return_value_policy::reference_internal)
         .def_readwrite("HeightVolumes", &LightingEnvironment::HeightVolumes)
@@ -656,6 +681,11 @@ PYBIND11_MODULE(_host, m) {
         .def_static("PackSphereLightBytes", [](const SphereLightSource& l, float intensityScale, bool haveDF) -> py::object {
             IlmLightVertex v;
             if (!LightingRenderer::PackSphereLight(l, intensityScale, haveDF, v)) return py::none();
+            return py::bytes((const char*)&v, sizeof(v));
+        })
+        .def_static("PackDirectionalLightBytes", [](const DirectionalLightSource& l, float intensityScale) -> py::object {
+            IlmLightVertex v;
+            if (!LightingRenderer::PackDirectionalLight(l, intensityScale, v)) return py::none();
             return py::bytes((const char*)&v, sizeof(v));
         });
 }

@@ -1267,6 +1267,38 @@ bool LightingRenderer::PackSphereLight(const SphereLightSource& l, float intensi
     return true;
 }
 
+// DirectionalLightSource.Direction's setter, LightSource.cs:117-130: Vector3.Normalize (1 / sqrt, then three products)
+void DirectionalLightSource::SetDirection(std::optional<Vector3> value) {
+    if (!value) { direction.reset(); return; }
+    const Vector3 d = *value;
+    const float factor = 1.0f / std::sqrt((d.X * d.X) + (d.Y * d.Y) + (d.Z * d.Z));
+    direction = Vector3{ d.X * factor, d.Y * factor, d.Z * factor };
+}
+
+// RenderDirectionalLightSource, LightingRenderer.cs:1256-1293
+bool LightingRenderer::PackDirectionalLight(const DirectionalLightSource& l, float intensityScale, IlmLightVertex& v) {
+    if (l.Opacity <= 0.0f)
+        return false;
+    std::memset(&v, 0, sizeof(v));
+    if (l.Bounds) {
+        v.LightPosition1 = { l.Bounds->TopLeft.X, l.Bounds->TopLeft.Y, 0, 0 };
+        v.LightPosition2 = { l.Bounds->BottomRight.X, l.Bounds->BottomRight.Y, 0, 0 };
+    } else {
+        v.LightPosition1 = { -99999, -99999, 0, 0 };
+        v.LightPosition2 = { 99999, 99999, 0, 0 };
+    }
+    v.LightPosition3 = { 0, 0, 0, 0 };
+    v.Color1 = { l.Color.X, l.Color.Y, l.Color.Z, l.Color.W * (l.Opacity * intensityScale) };
+    if (l.Direction()) v.Color2 = { l.Direction()->X, l.Direction()->Y, l.Direction()->Z, 1.0f };
+    else v.Color2 = { 0, 0, 0, 0 };
+    v.LightProperties = { l.CastsShadows ? 1.0f : 0.0f, l.ShadowTraceLength, l.ShadowSoftness, l.ShadowRampRate };
+    v.MoreLightProperties = { l.AmbientOcclusionRadius, l.ShadowDistanceFalloff.value_or(-99999.0f), 0, l.AmbientOcclusionOpacity };
+    // RampOffsetForGPU / RampRateForGPU of a light whose RampOffsetAndRate is the default (0, 1), LightSource.cs:97-98 (the directional
+    // techniques do not read them)
+    v.EvenMoreLightProperties = { (float)l.ShadowFilter, 0, (float)-3.14159265358979323846, (float)(1.0 / (3.14159265358979323846 * 2)) };
+    return true;
+}
+
 // SetDistanceFieldParameters, LightingRenderer.cs:1894-1940
 IlmDistanceFieldUniforms LightingRenderer::GetDistanceFieldUniforms(const RendererQualitySettings& q) const {
     IlmDistanceFieldUniforms dfu;
@@ -1304,19 +1336,26 @@ IlmEnvironment LightingRenderer::GetEnvironmentUniforms() const {
     return e;
 }
 
-// RenderLighting, LightingRenderer.cs:917-1191 (sphere lights only)
+// RenderLighting, LightingRenderer.cs:917-1191 (sphere, directional and particle lights)
 void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int rowEnd, IlmRenderStats* stats) {
     if (rowEnd < 0) rowEnd = Configuration.RenderHeight;
+    // the probe techniques of directional lights (DirectionalLightProbe*) are not built: refuse rather than leave them out of the probes
+    if (Probes.Count() > 0)
+        for (const DirectionalLightSource& d : Environment->DirectionalLights)
+            if (d.Enabled) throw InvalidOperationException("RenderLighting: directional lights do not reach light probes yet");
     vertices.clear();
     // LightSorter (:2066-2096): SortKey first; blend mode, ramp texture and type are the same for every light of this pass.  The
     // reference's sort is not stable for equal keys; a stable one keeps list order, which is one of its possible outcomes
     // (Lights before Replicators here, since the mirror holds them in two lists).
-    struct Entry { int sortKey; const SphereLightSource* sphere; const LightSourceReplicator* replicator; };
+    // Directional lights sort after spheres of equal key (TypeID 2 after 1, :2094): listed last, the stable sort keeps them there.
+    struct Entry { int sortKey; const SphereLightSource* sphere; const LightSourceReplicator* replicator; const DirectionalLightSource* directional; };
     std::vector<Entry> sorted;
     for (const SphereLightSource& l : Environment->Lights)
-        if (l.Enabled) sorted.push_back({ l.SortKey, &l, nullptr });
+        if (l.Enabled) sorted.push_back({ l.SortKey, &l, nullptr, nullptr });
     for (const LightSourceReplicator& r : Environment->Replicators)
-        if (r.Enabled) sorted.push_back({ r.SortKey, nullptr, &r });
+        if (r.Enabled) sorted.push_back({ r.SortKey, nullptr, &r, nullptr });
+    for (const DirectionalLightSource& d : Environment->DirectionalLights)
+        if (d.Enabled) sorted.push_back({ d.SortKey, nullptr, nullptr, &d });
     std::stable_sort(sorted.begin(), sorted.end(), [](const Entry& x, const Entry& y) { return x.sortKey < y.sortKey; });
     // GetLightRenderState (:799-845): lights that share a ramp texture and quality settings form one render state (BlendState is
     // additive for every light here); the states are drawn one after the other onto the same target, in the order their keys first appear.
@@ -1324,18 +1363,31 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     groupKeys.clear();
     groupQuality.clear();
     groups.clear();
-    auto groupFor = [&](const SphereLightSource& l) -> size_t {
-        const RampTexture* ramp = l.TextureRef ? l.TextureRef.get() : Configuration.DefaultRampTexture.get();
+    // the render state of a (ramp texture, quality) key among `keys` / `quality` / `lists`, appended when the key is new
+    auto stateFor = [&](const std::shared_ptr<RampTexture>& texture, const RendererQualitySettings* quality, std::vector<const RampTexture*>& keys,
+                        std::vector<const RendererQualitySettings*>& qualities, std::vector<std::vector<IlmLightVertex>>& lists) -> size_t {
+        const RampTexture* ramp = texture ? texture.get() : Configuration.DefaultRampTexture.get();
         if (ramp && ((ramp->Width == 1 && ramp->Height == 1) || ramp->Width <= 0))
             ramp = nullptr;                                   // a 1 x 1 ramp is no ramp (:822-827)
-        const RendererQualitySettings* quality = l.Quality.get();
         size_t g = 0;
-        while (g < groupKeys.size() && !(groupKeys[g] == ramp && groupQuality[g] == quality)) g++;
-        if (g == groupKeys.size()) { groupKeys.push_back(ramp); groupQuality.push_back(quality); groups.emplace_back(); }
+        while (g < keys.size() && !(keys[g] == ramp && qualities[g] == quality)) g++;
+        if (g == keys.size()) { keys.push_back(ramp); qualities.push_back(quality); lists.emplace_back(); }
         return g;
     };
+    auto groupFor = [&](const SphereLightSource& l) -> size_t { return stateFor(l.TextureRef, l.Quality.get(), groupKeys, groupQuality, groups); };
+    // directional lights form render states of their own (LightTypeRenderStateKey.Type): grouped by the same key, in first-appearance order
+    directionalKeys.clear();
+    directionalQuality.clear();
+    directionalGroups.clear();
     for (const Entry& e : sorted) {
         IlmLightVertex v;
+        if (e.directional) {
+            if (!PackDirectionalLight(*e.directional, intensityScale, v))
+                continue;
+            directionalGroups[stateFor(e.directional->TextureRef, e.directional->Quality.get(), directionalKeys, directionalQuality, directionalGroups)].push_back(v);
+            vertices.push_back(v);
+            continue;
+        }
         if (e.sphere) {
             if (!PackSphereLight(*e.sphere, intensityScale, Field != nullptr, v))
                 continue;
@@ -1371,7 +1423,8 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     // clear colour: Ambient * intensityScale (:1013-1024)
     const float ambient[4] = { Environment->Ambient.X * intensityScale, Environment->Ambient.Y * intensityScale,
                                Environment->Ambient.Z * intensityScale, Environment->Ambient.W * intensityScale };
-    if (groups.empty()) { groupKeys.push_back(nullptr); groupQuality.push_back(nullptr); groups.emplace_back(); }     // no lights: the clear still happens
+    // no lights: the clear still happens (with directional lights alone, their first launch carries it)
+    if (groups.empty() && directionalGroups.empty()) { groupKeys.push_back(nullptr); groupQuality.push_back(nullptr); groups.emplace_back(); }
     if (stats) { stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0; }
     for (size_t g = 0; g < groups.size(); g++) {
         BindRamp(groupKeys[g]);
@@ -1380,6 +1433,16 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
         ThrowIfFailed(ilm_render_sphere_lights(Context.Handle(), groups[g].empty() ? nullptr : groups[g].data(), (int32_t)groups[g].size(),
                                                &env, &gdfu, gbuffer, Field ? Field->Texture() : 0, (g == 0) ? ambient : nullptr, lightmap, rowBegin, rowEnd,
                                                stats ? &gs : nullptr));
+        if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
+    }
+    // the directional render states, onto the same target after the sphere ones
+    for (size_t g = 0; g < directionalGroups.size(); g++) {
+        BindRamp(directionalKeys[g]);
+        IlmRenderStats gs{};
+        const IlmDistanceFieldUniforms gdfu = directionalQuality[g] ? GetDistanceFieldUniforms(*directionalQuality[g]) : dfu;
+        ThrowIfFailed(ilm_render_directional_lights(Context.Handle(), directionalGroups[g].data(), (int32_t)directionalGroups[g].size(), &env, &gdfu, gbuffer,
+                                                    Field ? Field->Texture() : 0, (groups.empty() && g == 0) ? ambient : nullptr, lightmap, rowBegin, rowEnd,
+                                                    stats ? &gs : nullptr));
         if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
     }
     BindRamp(nullptr);         // particle lights have no ramp technique (:176-178)

@@ -711,6 +711,31 @@ struct SphereLightSource {
     float RampOffset = 0, RampRate = 1;           // RampOffsetAndRate, LightSource.cs:90
 };
 
+// Bounds (Squared.Game: TopLeft, BottomRight)
+struct Bounds { Vector2 TopLeft, BottomRight; };
+
+// DirectionalLightSource, LightSource.cs:105-180 (+ the LightSource / LightSourceBase members RenderDirectionalLightSource reads,
+// LightingRenderer.cs:1256-1293)
+struct DirectionalLightSource {
+    int SortKey = 0;
+    bool Enabled = true;
+    std::optional<Lighting::Bounds> Bounds;       // restricts the light to a rectangle of the world; with a null Direction: ambient light in an area
+    // the direction light travels, normalised when set (:117-130); null: a non-directional light
+    const std::optional<Vector3>& Direction() const { return direction; }
+    void SetDirection(std::optional<Vector3> value);
+    float ShadowTraceLength = 256, ShadowSoftness = 12, ShadowRampRate = 0.5f;
+    Vector4 Color{1, 1, 1, 1};
+    float Opacity = 1;
+    bool CastsShadows = true;
+    float AmbientOcclusionRadius = 0, AmbientOcclusionOpacity = 1;
+    std::optional<float> ShadowDistanceFalloff;
+    int ShadowFilter = -1;
+    std::shared_ptr<RampTexture> TextureRef;      // RampTexture (:182-190); null => Configuration.DefaultRampTexture
+    std::shared_ptr<RendererQualitySettings> Quality;
+private:
+    std::optional<Vector3> direction;
+};
+
 // ReplicatedLight / LightSourceReplicator, LightSource.cs:601-620: one template, many placements.  Each placement may override the
 // per-light values; everything else (ramp mode, shadows, AO, falloff, ramp texture, quality) comes from the template.
 struct ReplicatedLight {
@@ -814,6 +839,7 @@ struct HeightVolume {
 struct LightingEnvironment {
     std::vector<SphereLightSource> Lights;
     std::vector<LightSourceReplicator> Replicators;    // LightSourceReplicator entries of Lights in the reference
+    std::vector<DirectionalLightSource> DirectionalLights;   // DirectionalLightSource entries of Lights in the reference
     std::vector<ParticleLightSource> ParticleLights;   // ParticleLightSource entries of Lights in the reference (one render state each)
     LightObstructionCollection Obstructions;
     std::vector<HeightVolume> HeightVolumes;
@@ -848,13 +874,12 @@ struct RendererConfiguration {
     RendererConfiguration(int w, int h) : RenderWidth(w), RenderHeight(h) {}
 };
 
-// VisualizationMode / VisualizationInfo, LightingRenderer.cs:2055-2071; Bounds (Squared.Game: TopLeft, BottomRight) and Bounds3
+// VisualizationMode / VisualizationInfo, LightingRenderer.cs:2055-2071; Bounds3
 enum class VisualizationMode { Surfaces = 0, Outlines = 1, Silhouettes = 2 };
 struct VisualizationInfo {
     bool Failed = false;
     Vector3 ViewCenter, Up, Right, ViewDirection;
 };
-struct Bounds { Vector2 TopLeft, BottomRight; };
 struct Bounds3 { Vector3 Minimum, Maximum; };
 // what VisualizeDistanceField leaves to default arguments (:1703-1711) and the view transform of the target
 struct VisualizationOptions {
@@ -895,7 +920,8 @@ public:
     void RenderGBuffer(Vector2 viewportPosition = {0, 0}, Vector2 viewportScale = {1, 1});
     IlmHandle GBuffer() const { return gbuffer; }
 
-    // RenderLighting, :917-1191: clears to Ambient * intensityScale and adds every sphere light.
+    // RenderLighting, :917-1191: clears to Ambient * intensityScale and adds every sphere light, then every directional light, then
+    // the particle lights.  Directional lights do not reach light probes yet: with probes and an enabled directional light it throws.
     // [rowBegin, rowEnd) restricts the pass to a screen strip (multi-GPU split); rowEnd < 0 => whole frame.
     void RenderLighting(float intensityScale = 1.0f, int rowBegin = 0, int rowEnd = -1, IlmRenderStats* stats = nullptr);
     void ReadLightmap(void* dst, int firstRow, int rowCount) const;
@@ -927,6 +953,8 @@ public:
     static IlmParticleLightParams PackParticleLight(const ParticleLightSource& pls, bool haveDistanceField);
     // RenderSphereLightSource, :1193-1219
     static bool PackSphereLight(const SphereLightSource& l, float intensityScale, bool haveDistanceField, IlmLightVertex& v);
+    // RenderDirectionalLightSource, :1256-1293: false for Opacity <= 0 (:1258); CastsShadows is packed without the field test (:1279)
+    static bool PackDirectionalLight(const DirectionalLightSource& l, float intensityScale, IlmLightVertex& v);
     // SetDistanceFieldParameters, :1894-1940
     IlmDistanceFieldUniforms GetDistanceFieldUniforms(const RendererQualitySettings& q) const;
     // ComputeUniforms :691-701 + SetGBufferParameters LightingRenderer.GBuffer.cs:520-534
@@ -946,6 +974,10 @@ private:
     std::vector<const RampTexture*> groupKeys;
     std::vector<const RendererQualitySettings*> groupQuality;     // null => Configuration.DefaultQuality
     std::vector<std::vector<IlmLightVertex>> groups;
+    // the directional groups of the last RenderLighting, drawn after the sphere groups (same keys: ramp texture, quality)
+    std::vector<const RampTexture*> directionalKeys;
+    std::vector<const RendererQualitySettings*> directionalQuality;
+    std::vector<std::vector<IlmLightVertex>> directionalGroups;
     const RampTexture* boundRamp = nullptr;
     float lastInverseScaleFactor = 0;     // RenderedLighting.InverseScaleFactor of the last RenderLighting; 0 = none yet
     void BindRamp(const RampTexture* ramp);

@@ -776,6 +776,35 @@ def sphere_light(position, radius, ramp_length, color=(1, 1, 1, 1), opacity=1.0,
     return v
 
 
+def directional_light(direction=None, bounds=None, color=(1, 1, 1, 1), opacity=1.0, intensity_scale=1.0, casts_shadows=True,
+                      shadow_trace_length=256.0, shadow_softness=12.0, shadow_ramp_rate=0.5, ao_radius=0.0, ao_opacity=1.0,
+                      shadow_distance_falloff=None, shadow_filter=-1, normalise=True):
+    """RenderDirectionalLightSource, LightingRenderer.cs:1256-1293, from the DirectionalLightSource's members (Direction is normalised
+    by its setter, LightSource.cs:117-130: Vector3.Normalize = 1 / sqrt, then three products)."""
+    v = abi.LightVertex()
+    if bounds is not None:
+        v.LightPosition1 = abi.f4(bounds[0], bounds[1], 0, 0)
+        v.LightPosition2 = abi.f4(bounds[2], bounds[3], 0, 0)
+    else:
+        v.LightPosition1 = abi.f4(-99999, -99999, 0, 0)
+        v.LightPosition2 = abi.f4(99999, 99999, 0, 0)
+    v.LightPosition3 = abi.f4(0, 0, 0, 0)
+    v.Color1 = abi.f4(color[0], color[1], color[2], np.float32(color[3]) * (np.float32(opacity) * np.float32(intensity_scale)))
+    if direction is not None:
+        d = np.asarray(direction, np.float32)
+        if normalise:
+            f = np.float32
+            factor = f(f(1) / f(np.sqrt(f(f(f(d[0] * d[0]) + f(d[1] * d[1])) + f(d[2] * d[2])))))
+            d = (d * factor).astype(np.float32)
+        v.Color2 = abi.f4(d[0], d[1], d[2], 1.0)
+    else:
+        v.Color2 = abi.f4(0, 0, 0, 0)
+    v.LightProperties = abi.f4(1.0 if casts_shadows else 0.0, shadow_trace_length, shadow_softness, shadow_ramp_rate)
+    v.MoreLightProperties = abi.f4(ao_radius, -99999.0 if shadow_distance_falloff is None else shadow_distance_falloff, 0, ao_opacity)
+    v.EvenMoreLightProperties = abi.f4(float(shadow_filter), 0, np.float32(-np.pi), np.float32(1.0 / (np.pi * 2)))
+    return v
+
+
 def random_lights(seed, n, width, height, z=(8.0, 64.0), radius=24.0, ramp=(200.0, 550.0), **kw):
     xs = uniform(seed + 1, (n,), 0, width)
     ys = uniform(seed + 2, (n,), 0, height)

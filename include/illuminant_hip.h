@@ -31,7 +31,8 @@ extern "C" {
 #endif
 
 /* 11: + ilm_engine_step_batch, ilm_debug_last_step_batch, ILM_STEP_KERNEL_BATCH; later, under the same number (no layout changed, nothing
- * removed): + ilm_visualize_distance_field / IlmVisualizeVertex, IlmVisualizeParams, ILM_VISUALIZE_* (distance-field views).
+ * removed): + ilm_visualize_distance_field / IlmVisualizeVertex, IlmVisualizeParams, ILM_VISUALIZE_* (distance-field views);
+ * + ilm_render_directional_lights (directional lights; no new struct: the reference packs them into a LightVertex).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -770,7 +771,45 @@ int32_t ilm_render_sphere_lights(IlmHandle ctx,
                                  IlmHandle lightmap, int32_t row_begin, int32_t row_end,
                                  IlmRenderStats* stats);
 
-/* LightSource.TextureRef / Configuration.DefaultRampTexture of the light group rendered by the FOLLOWING ilm_render_sphere_lights and
+/* The directional-light pass of LightingRenderer.RenderLighting: techniques DirectionalLight / DirectionalLightWithRamp
+ * (Illuminant/Shaders/DirectionalLight.fx:19-161), one quad per light, added onto the lightmap like every other light type.  The
+ * arguments mean what they mean for ilm_render_sphere_lights: gbuffer == 0 => ground plane, sdf == 0 => no distance field, ambient ==
+ * NULL => the lights are ADDED to what rows [row_begin, row_end) hold, ambient != NULL => every pixel of the rows is cleared to it first
+ * (whatever light_count is, 0 included), stats != NULL => the counting variant runs and the call synchronises.  Any light_count >= 0.
+ * ilm_ctx_set_lightmap_blend applies (fp32 registers over this call's lights in list order, the sum added to the base value and rounded
+ * once at the store; or the fp16-per-light model), and so does ilm_ctx_set_light_ramp: while a ramp is bound the technique is
+ * DirectionalLightWithRamp, opacity = SampleFromRamp(opacity) (RampCommon.fxh:15-17: channel r at v = 0).
+ * Vertex layout, as RenderDirectionalLightSource fills it (Illuminant/Lighting/LightingRenderer.cs:1256-1307, LightVertex
+ * Illuminant/Lighting/Vertices.cs:22-30):
+ *   LightPosition1.xy / LightPosition2.xy   Bounds.TopLeft / BottomRight, or -99999 / +99999 without bounds
+ *   Color1                                  Color.rgb, Color.a * Opacity * intensityScale
+ *   Color2                                  (Direction, 1), or all 0 for a null direction (an ambient light in an area)
+ *   LightProperties                         CastsShadows ? 1 : 0, ShadowTraceLength, ShadowSoftness, ShadowRampRate
+ *   MoreLightProperties                     AmbientOcclusionRadius, ShadowDistanceFalloff or -99999, 0, AmbientOcclusionOpacity
+ *   EvenMoreLightProperties.x               ShadowFilter
+ * (LightPosition3 and the other members are not read.)
+ * Coverage -- the reference leaves it to the rasteriser; here: pixel (x, y) lies in a light's footprint iff its centre (x + 0.5,
+ * y + 0.5) lies in [x0, x1) x [y0, y1), with x0 = (LightPosition1.x - ViewportPosition.x) * (ViewportScale.x * RenderScale.x), x1 the same
+ * from LightPosition2.x, y0 / y1 likewise: fp32, one rounding per operation, the scales multiplied first as
+ * DirectionalLightVertexShader writes it (DirectionalLight.fx:32-34; ViewportScale = GBufferTexelSizeAndMisc.zw, RenderScale =
+ * ZAndScale.zw).  A light with LightPosition1 > LightPosition2 on an axis, or a NaN in either, is refused: ILM_ERR_INVALID_ARGUMENT.
+ * Discards: a pixel outside the footprint, a fullbright pixel, one the shadow filter rejects and one that is not visible (G-buffer x <=
+ * -9999, clip(), :91) get nothing from the light -- no rgb and no + 1 on alpha.  There is no opacity discard (unlike SphereLight.fx): a
+ * visible pixel whose opacity is 0 still adds alpha 1.
+ * Statistics: PixelLightPairs = pairs inside a footprint; TracedPairs = pairs with traceShadows (:73) and a bound field (sdf != 0,
+ * Extent.x > 0); SdfSamples = ambient-occlusion + cone-trace samples.
+ * Not built: the light-probe techniques (DirectionalLightProbe*), the group entry point. */
+int32_t ilm_render_directional_lights(IlmHandle ctx,
+                                      const IlmLightVertex* lights, int32_t light_count,
+                                      const IlmEnvironment* env,
+                                      const IlmDistanceFieldUniforms* df,
+                                      IlmHandle gbuffer, IlmHandle sdf,
+                                      const float ambient[4],
+                                      IlmHandle lightmap, int32_t row_begin, int32_t row_end,
+                                      IlmRenderStats* stats);
+
+/* LightSource.TextureRef / Configuration.DefaultRampTexture of the light group rendered by the FOLLOWING ilm_render_sphere_lights,
+ * ilm_render_directional_lights (SampleFromRamp(opacity), channel r at v = 0: DirectionalLightWithRamp) and
  * ilm_render_light_probes calls (bound per group by _LightBatchSetup, Illuminant/Lighting/LightingRenderer.cs:764-766; sampler
  * RampTextureSampler, Illuminant/Shaders/RampCommon.fxh:4-21: tex2Dlod level 0, LINEAR, U CLAMP, V WRAP): width * height float4 texels.
  * width == 0 -- or a 1 x 1 texture, which the reference treats as none (:822-827) -- selects the techniques without a ramp. */
