@@ -104,6 +104,8 @@ struct Ctx {
     // particle lights: records compacted on the device + their count, block counts, per-chunk quad counts
     DeviceScratch d_pl_recs, d_pl_count, d_pl_blocks, d_pl_quads;
     float4* d_light_ramp = nullptr; int light_ramp_w = 0, light_ramp_h = 0;    // RampTexture of the light group being rendered
+    // ProjectorLightSource.TextureRef of the projector group being rendered (ilm_ctx_set_projector_texture): a binding of its own
+    DeviceScratch d_projector_texture; int projector_texture_w = 0, projector_texture_h = 0;
     int lightmap_blend = 0;               // ILM_BLEND_FP32_ACCUMULATE / ILM_BLEND_FP16_PER_LIGHT (ilm_ctx_set_lightmap_blend)
     RasterScratch raster;                                         // particle rasteriser buffers (raster.hip)
     DeviceScratch d_raster_quads;
@@ -116,10 +118,10 @@ struct Ctx {
     // parameter block of the distance-field generation pass (slice list, obstruction records, volumes, polygon vertices)
     DeviceScratch d_field_params;
     // every block `reserve` grows: what ilm_ctx_destroy frees
-    std::array<DeviceScratch*, 20> scratch() {
+    std::array<DeviceScratch*, 21> scratch() {
         return { &staging, &d_recs, &d_light_partials, &d_light_tickets, &d_group_order, &d_pl_recs, &d_pl_count, &d_pl_blocks, &d_pl_quads,
                  &d_raster_quads, &d_rb, &d_rb_count, &d_rb_blocks, &d_rb_elems, &d_probe_pairs, &brightness.level, &brightness.mip,
-                 &brightness.work, &brightness.partials, &d_field_params };
+                 &brightness.work, &brightness.partials, &d_field_params, &d_projector_texture };
     }
 };
 
@@ -3359,6 +3361,22 @@ int32_t ilm_ctx_set_light_ramp(IlmHandle hctx, const IlmFloat4* texels, int32_t 
     return ILM_OK;
 }
 
+int32_t ilm_ctx_set_projector_texture(IlmHandle hctx, const IlmFloat4* texels, int32_t width, int32_t height) {
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    if (width < 0 || height < 0 || width > 16384 || height > 16384 || ((width > 0) != (height > 0)) || (width > 0 && !texels))
+        return fail(ILM_ERR_INVALID_ARGUMENT, "bad projector texture (%d x %d)", width, height);
+    if (width == 0) { c->projector_texture_w = c->projector_texture_h = 0; return ILM_OK; }      // unbound; the block stays for the next texture
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->main()));     // an earlier pass may still read the texels about to be replaced
+    c->projector_texture_w = c->projector_texture_h = 0;
+    const size_t bytes = sizeof(float4) * (size_t)width * (size_t)height;
+    { const int32_t rc = reserve(c, c->d_projector_texture, bytes, bytes); if (rc != ILM_OK) return rc; }
+    HIP_TRY(hipMemcpy(c->d_projector_texture.p, texels, bytes, hipMemcpyHostToDevice));
+    c->projector_texture_w = width; c->projector_texture_h = height;
+    return ILM_OK;
+}
+
 int32_t ilm_lightmap_clear(IlmHandle h, const float rgba[4]) {
     ILM_TRACE_RANGE("ilm_lightmap_clear");
     Lightmap* m = from_handle<Lightmap>(h, kMagicLightmap);
@@ -3830,6 +3848,58 @@ int32_t ilm_render_directional_lights(IlmHandle hctx, const IlmLightVertex* ligh
     c->last_light_blocks = ((a.width + kLightTile - 1) / kLightTile) * ((row_end - row_begin + kLightTile - 1) / kLightTile);
     c->last_light_split = 1; c->last_light_macro = 0;
     HIP_TRY(launch_directional_lights_prepared(a, c->d_recs.p, c->main()));
+    HIP_TRY(light_pass_queued(c, f, g));
+    if (stats) {
+        unsigned long long host[3] = { 0, 0, 0 };
+        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
+        HIP_TRY(hipStreamSynchronize(c->main()));
+        stats->SdfSamples = host[0]; stats->PixelLightPairs = host[1]; stats->TracedPairs = host[2];
+    }
+    return ILM_OK;
+}
+
+int32_t ilm_render_projector_lights(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,
+                                    const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf, const float ambient[4],
+                                    IlmHandle hlightmap, int32_t row_begin, int32_t row_end, IlmRenderStats* stats) {
+    ILM_TRACE_RANGE("ilm_render_projector_lights");
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    if (light_count < 0 || (light_count > 0 && !lights)) return fail(ILM_ERR_INVALID_ARGUMENT, "bad light array");
+    // the reference skips a light whose texture is null before packing (LightingRenderer.cs:1389-1391): lights without one are a caller's error
+    if (light_count > 0 && c->projector_texture_w == 0)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "projector lights without a texture: ilm_ctx_set_projector_texture binds the group's");
+    LightLaunch a = {};
+    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, false); if (rc != ILM_OK) return rc; }
+    Sdf* f = hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr;
+    GBuffer* g = hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr;
+    if (stats) stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0;
+
+    // (a projector record is one and a half slots of the other passes' records)
+    static_assert(kProjectorRecBytes * 2 == kLightRecBytes * 3, "a projector record is one and a half light-record slots");
+    if (light_count > kMaxProjectorLights)      // (keeps the slot count and reserve_light_recs's doubling inside an int)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "%d projector lights in one call: at most %d", light_count, kMaxProjectorLights);
+    { const int32_t rc = reserve_light_recs(c, light_count + (light_count + 1) / 2); if (rc != ILM_OK) return rc; }
+    if (light_count > 0) {
+        const void* staged = nullptr; int slot = 0;
+        int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
+        if (rc != ILM_OK) return rc;
+        HIP_TRY(launch_prepare_projector_lights(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, c->d_recs.p, c->main()));
+        rc = staged_small_done(c, slot);
+        if (rc != ILM_OK) return rc;
+    }
+    a.light_count = light_count;
+    for (int i = 0; i < 4; i++) a.ambient[i] = ambient ? ambient[i] : 0.0f;
+    a.accumulate = ambient ? 0 : 1;
+    // the group's texture rides in the descriptor's ramp member; the ramp binding (ilm_ctx_set_light_ramp) is neither read nor touched
+    a.ramp = RampView{ light_count > 0 ? static_cast<const float4*>(c->d_projector_texture.p) : nullptr, c->projector_texture_w, c->projector_texture_h };
+    if (stats) {
+        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
+        a.stats = c->d_stats;
+    }
+    // (ilm_debug_last_light_launch: one workgroup per 16 x 16 tile of the rows, no split, no tile map)
+    c->last_light_blocks = ((a.width + kLightTile - 1) / kLightTile) * ((row_end - row_begin + kLightTile - 1) / kLightTile);
+    c->last_light_split = 1; c->last_light_macro = 0;
+    HIP_TRY(launch_projector_lights_prepared(a, c->d_recs.p, c->main()));
     HIP_TRY(light_pass_queued(c, f, g));
     if (stats) {
         unsigned long long host[3] = { 0, 0, 0 };

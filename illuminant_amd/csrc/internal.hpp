@@ -239,6 +239,14 @@ hipError_t launch_sphere_lights_prepared(const LightLaunch& a, const void* recs,
 hipError_t launch_prepare_directional_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
                                              void* recs, hipStream_t stream);
 hipError_t launch_directional_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream);
+// Projector lights (ProjectorLight.fx): the records (count * kProjectorRecBytes: one and a half slots of reserve_light_recs each) and the
+// pass over a's rows, in the directional pass's frame.  a.ramp is the group's projector texture (ilm_ctx_set_projector_texture), not the
+// ramp binding; a launch with lights needs one.
+constexpr size_t kProjectorRecBytes = 192;
+constexpr int32_t kMaxProjectorLights = 1 << 24;      // per call: 3 GiB of records; the slot arithmetic stays far inside an int
+hipError_t launch_prepare_projector_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
+                                           void* recs, hipStream_t stream);
+hipError_t launch_projector_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream);
 int light_launch_blocks(const LightLaunch& a);    // workgroups of the tile kernel's launch for a (split / taper included)
 int light_block_slots(const LightLaunch& a);      // block slots per XCD of the tile kernel's launch over a's rows
 

@@ -1485,6 +1485,321 @@ hipError_t launch_directional_lights_prepared(const LightLaunch& a, const void* 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Projector lights -- technique ProjectorLight, ProjectorLight.fx:14-56 over ProjectorLightCore.fxh:20-151,290-302, drawn by
+// RenderProjectorLightSource (LightingRenderer.cs:1386-1446) as one quad per light: the whole frame for a wrapping light, the bounding
+// box of the projector's volume for a clamped one (ProjectorLightVertexShader, ProjectorLightCore.fxh:251-278).  The frame of the
+// directional pass: one thread per pixel, one wave per 8 x 8 pixels, a wave-uniform loop over the prepared records (scalar loads: the
+// 16 matrix entries of a light cost no vector registers), the G-buffer texel decoded once, the sum in registers, one store.  The
+// shadow is the sphere light's trace towards one point in its general form (cone_trace_loop<.., false>); the group's texture (one
+// level, LINEAR, WRAP on both axes) travels in the launch descriptor's `ramp` member, which this pass reads as nothing else.
+// ---------------------------------------------------------------------------------------------
+constexpr float kProjectorSelfOcclusionHack = 1.5f;              // ProjectorLightCore.fxh:7 SELF_OCCLUSION_HACK
+constexpr float kProjectorTraceThreshold = 0.75f / 255.0f;       // ProjectorLightCore.fxh:8 SHADOW_OPACITY_THRESHOLD
+constexpr float kProjectorEdgeThreshold = 0.001f;                // ProjectorLightCore.fxh:62
+constexpr float kProjectorEdgeScale = 1.0f / 0.001f;             // (1 / threshold), :63 -- the fp32 quotient
+
+struct ProjectorRec {
+    float x0, y0, x1, y1;                                       // footprint in screen pixels: centre in [x0, x1) x [y0, y1)
+    float m[16];                                                // rows 1-4 of the inverse matrix, m[15] = 1 (the mip bias is not read: one level)
+    float origin_x, origin_y, origin_z, origin_w;               // LightPosition3
+    float region_x0, region_y0, region_x1, region_y1;           // EvenMoreLightProperties
+    float clamp, opacity, ao_radius, ao_opacity;                // MoreLightProperties.z, .y, .x, .w
+    float shadows, radius, cfg_x, cfg_y;                        // LightProperties.w, .x; createTraceConfig: maxRadius, radiusGrowthPerPixel
+    float _pad[12];
+};
+static_assert(sizeof(ProjectorRec) == kProjectorRecBytes, "a projector record is 192 bytes (internal.hpp: one and a half slots of reserve_light_recs)");
+
+// invertMatrix (ProjectorLightCore.fxh:155-192) as a table: entry [i][j] of the result is the sum of six signed triple products,
+// added in the order the shader writes them, times 1 / det.  A term +-abcdef names the factors n_ab * n_cd * n_ef with the shader's
+// n_rc = m[c - 1][r - 1]; entries [i][0] are its t11 .. t14, and det = n11 t11 + n21 t12 + n31 t13 + n41 t14.
+__constant__ const int kInverseTerms[16][6] = {
+    { 233442, -243342, 243243, -223443, -233244, 223344 }, { 243341, -233441, -243143, 213443, 233144, -213344 },
+    { 223441, -243241, 243142, -213442, -223144, 213244 }, { 233241, -223341, -233142, 213342, 223143, -213243 },
+    { 143342, -133442, -143243, 123443, 133244, -123344 }, { 133441, -143341, 143143, -113443, -133144, 113344 },
+    { 143241, -123441, -143142, 113442, 123144, -113244 }, { 123341, -133241, 133142, -113342, -123143, 113243 },
+    { 132442, -142342, 142243, -122443, -132244, 122344 }, { 142341, -132441, -142143, 112443, 132144, -112344 },
+    { 122441, -142241, 142142, -112442, -122144, 112244 }, { 132241, -122341, -132142, 112342, 122143, -112243 },
+    { 142332, -132432, -142233, 122433, 132234, -122334 }, { 132431, -142331, 142133, -112433, -132134, 112334 },
+    { 142231, -122431, -142132, 112432, 122134, -112234 }, { 122331, -132231, 132132, -112332, -122133, 112233 },
+};
+ILM_DEV void invert_matrix(const float (&m)[16], float (&out)[16]) {
+    auto n = [&](int rc) { return m[(rc % 10 - 1) * 4 + (rc / 10 - 1)]; };
+    float sums[16];
+    for (int e = 0; e < 16; e++) {
+        float acc = 0.0f;
+        for (int t = 0; t < 6; t++) {
+            const int code = kInverseTerms[e][t], a = code < 0 ? -code : code;
+            const float product = (n(a / 10000) * n((a / 100) % 100)) * n(a % 100);
+            acc = (t == 0) ? product : ((code < 0) ? (acc - product) : (acc + product));
+        }
+        sums[e] = acc;
+    }
+    const float det = ((n(11) * sums[0] + n(21) * sums[4]) + n(31) * sums[8]) + n(41) * sums[12];
+    const float idet = 1.0f / det;
+    for (int e = 0; e < 16; e++) out[e] = sums[e] * idet;
+}
+
+// component c of mul(float4(x, y, z, 1), M), M's rows in m[0..3], [4..7], [8..11], [12..15]
+ILM_DEV float row_times_matrix(const float (&m)[16], int c, float x, float y, float z) {
+    return ((x * m[c] + y * m[4 + c]) + z * m[8 + c]) + 1.0f * m[12 + c];
+}
+
+// ProjectorLightVertexShader (ProjectorLightCore.fxh:244-287) at the quad's two extreme corners + createTraceConfig
+// (ConeTrace.fxh:122-139) with lightRamp = (Radius, RampLength) and cone growth getConeGrowthFactor() == 1
+__global__ __launch_bounds__(64) void prepare_projector_lights_kernel(const IlmLightVertex* __restrict__ lights, int count, IlmEnvironment env,
+                                                                       float max_cone_radius, ProjectorRec* __restrict__ out) {
+    const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (i >= count) return;
+    const IlmLightVertex L = lights[i];
+    ProjectorRec r = {};
+    const IlmFloat4 rows[4] = { L.LightPosition1, L.LightPosition2, L.Color1, L.Color2 };
+    for (int k = 0; k < 4; k++) { r.m[k * 4] = rows[k].x; r.m[k * 4 + 1] = rows[k].y; r.m[k * 4 + 2] = rows[k].z; r.m[k * 4 + 3] = rows[k].w; }
+    r.m[15] = 1.0f;                                   // mat4.w carries the mip bias; the matrix's m44 is 1 (:244-245)
+    r.origin_x = L.LightPosition3.x; r.origin_y = L.LightPosition3.y; r.origin_z = L.LightPosition3.z; r.origin_w = L.LightPosition3.w;
+    r.region_x0 = L.EvenMoreLightProperties.x; r.region_y0 = L.EvenMoreLightProperties.y;
+    r.region_x1 = L.EvenMoreLightProperties.z; r.region_y1 = L.EvenMoreLightProperties.w;
+    r.clamp = L.MoreLightProperties.z; r.opacity = L.MoreLightProperties.y;
+    r.ao_radius = L.MoreLightProperties.x; r.ao_opacity = L.MoreLightProperties.w;
+    r.shadows = L.LightProperties.w; r.radius = L.LightProperties.x;
+    const float max_radius = clampf(L.LightProperties.x, ref::kMinConeRadius, max_cone_radius);
+    r.cfg_x = max_radius;
+    r.cfg_y = max_radius / fmaxf(L.LightProperties.y, 16.0f) * 1.0f;
+
+    float wx0, wy0, wx1, wy1;                         // the quad's world rectangle
+    if (r.clamp > 0.5f) {
+        float world[16];
+        invert_matrix(r.m, world);
+        const float sx = r.region_x1 - r.region_x0, sy = r.region_y1 - r.region_y0;
+        float tlx = 999999.0f, tly = 999999.0f, brx = -999999.0f, bry = -999999.0f;
+        for (int k = 0; k < 4; k++) {
+            const float cx = (k == 1 || k == 2) ? 1.0f : 0.0f, cy = (k >= 2) ? 1.0f : 0.0f;      // LightCorners, LightCommon.fxh:12-17
+            const float ix = lerp(0.0f, sx, cx), iy = lerp(0.0f, sy, cy);
+            // projectBoundingBoxEdge (:194-221): the corner at z = 0 and z = 1, each divided by its w
+            const float w1 = row_times_matrix(world, 3, ix, iy, 0.0f), w2 = row_times_matrix(world, 3, ix, iy, 1.0f);
+            const float ax = row_times_matrix(world, 0, ix, iy, 0.0f) / w1, ay = row_times_matrix(world, 1, ix, iy, 0.0f) / w1;
+            const float bx = row_times_matrix(world, 0, ix, iy, 1.0f) / w2, by = row_times_matrix(world, 1, ix, iy, 1.0f) / w2;
+            const float px = lerp(fminf(ax, bx), fmaxf(ax, bx), cx), py = lerp(fminf(ay, by), fmaxf(ay, by), cy);
+            tlx = fminf(tlx, px); tly = fminf(tly, py); brx = fmaxf(brx, px); bry = fmaxf(bry, py);
+        }
+        const float z_offset = env.ZAndScale.y * env.ZToY.x;
+        wx0 = lerp(tlx, brx, 0.0f); wx1 = lerp(tlx, brx, 1.0f);
+        wy0 = lerp(tly, bry, 0.0f) + (z_offset * ((0.0f * 2.0f) - 1.0f));
+        wy1 = lerp(tly, bry, 1.0f) + (z_offset * ((1.0f * 2.0f) - 1.0f));
+    } else {
+        wx0 = lerp(-9999.0f, 9999.0f, 0.0f); wx1 = lerp(-9999.0f, 9999.0f, 1.0f);
+        wy0 = wx0; wy1 = wx1;
+    }
+    const float scale_x = env.GBufferTexelSizeAndMisc.z * env.ZAndScale.z, scale_y = env.GBufferTexelSizeAndMisc.w * env.ZAndScale.w;
+    r.x0 = (wx0 - env.ViewportPosition[0]) * scale_x; r.y0 = (wy0 - env.ViewportPosition[1]) * scale_y;
+    r.x1 = (wx1 - env.ViewportPosition[0]) * scale_x; r.y1 = (wy1 - env.ViewportPosition[1]) * scale_y;
+    out[i] = r;
+}
+
+// tex2Dlod(ProjectorTextureSampler, (u, v, 0, mip)) on a one-level texture: LINEAR, WRAP on both axes.  The tap and weight arithmetic
+// of the ramp lookup's V axis (shade_light) on both axes: the second tap is the integer first tap + 1 wrapped, wrap_index is exact for
+// every finite float and names tap 0 for a non-finite one -- every index lies inside the texture by integer arithmetic.
+ILM_DEV float4 sample_projector_texture(const RampView& tex, float u, float v) {
+    const int w = tex.width, h = tex.height;
+    const float sx = u * (float)w - 0.5f, sy = v * (float)h - 0.5f;
+    const float x0f = floorf(sx), y0f = floorf(sy);
+    const float fx = sx - x0f, fy = sy - y0f;
+    const int x0 = wrap_index(x0f, w), x1 = (x0 + 1 == w) ? 0 : x0 + 1;
+    const int y0 = wrap_index(y0f, h), y1 = (y0 + 1 == h) ? 0 : y0 + 1;
+    const float4 t00 = tex.texels[y0 * w + x0], t10 = tex.texels[y0 * w + x1], t01 = tex.texels[y1 * w + x0], t11 = tex.texels[y1 * w + x1];
+    return lerp4(lerp4(t00, t10, fx), lerp4(t01, t11, fx), fy);
+}
+
+// One projector light on one shaded point: ProjectorLightPixelShader (ProjectorLight.fx:14-56) after the footprint test.  Returns false
+// when the shader discards (fullbright, !visible); otherwise the rgb it adds.  No shadow filter and no opacity discard: a visible
+// pixel whose opacity is 0 is blended (alpha + 1).
+template <int FMT, bool STATS>
+ILM_DEV bool shade_projector(const Pixel& P, const ProjectorRec& L, const TraceField& F, bool have_sdf, const RampView& tex, LightStats& st,
+                             float& out_r, float& out_g, float& out_b) {
+    if (P.fullbright)
+        return false;
+    // ProjectorLightPixelCoreNoDF, ProjectorLightCore.fxh:20-85
+    const f3 p = P.shaded;
+    const float tw = ((p.x * L.m[3] + p.y * L.m[7]) + p.z * L.m[11]) + 1.0f * L.m[15];
+    float tx = (((p.x * L.m[0] + p.y * L.m[4]) + p.z * L.m[8]) + 1.0f * L.m[12]) / tw;
+    float ty = (((p.x * L.m[1] + p.y * L.m[5]) + p.z * L.m[9]) + 1.0f * L.m[13]) / tw;
+    float tz = (((p.x * L.m[2] + p.y * L.m[6]) + p.z * L.m[10]) + 1.0f * L.m[14]) / tw;
+    tx += L.region_x0; ty += L.region_y0;
+    tz = fmaxf(0.0f, tz);
+    const f3 clamped = mk3(clampf(tx, L.region_x0, L.region_x1), clampf(ty, L.region_y0, L.region_y1), clampf(tz, 0.0f, 1.0f));
+    const float distance_to_volume = fminf(len3(clamped - mk3(tx, ty, tz)), kProjectorEdgeThreshold) * kProjectorEdgeScale;
+    float distance_opacity = 1.0f;
+    if (L.clamp > 0.5f)
+        distance_opacity = fmaxf(1.0f - distance_to_volume, 0.0f);
+    const bool visible = (distance_opacity > 0.0f) && (p.x > -9999.0f) && (L.opacity > 0.0f);
+    if (!visible)
+        return false;
+    tx = lerp(tx, clamped.x, L.clamp); ty = lerp(ty, clamped.y, L.clamp);
+    // lerp(1, computeNormalFactor(normalize(shaded - origin), normal), origin.w); at origin.w == 0 the factor is not evaluated (the
+    // header's defined deviation: the lerp's value for every finite factor, and no NaN at shaded == origin == 0)
+    float normal_opacity = 1.0f;
+    if (L.origin_w != 0.0f) {
+        float factor = 1.0f;
+        if ((P.normal.x != 0.0f) || (P.normal.y != 0.0f) || (P.normal.z != 0.0f)) {
+            const f3 ln = norm3(p - mk3(L.origin_x, L.origin_y, L.origin_z));
+            const float d = dot3(ln * -1.0f, P.normal);
+            factor = pow_pos(sat((d + ref::kDotOffset) / ref::kDotRampRange), ref::kDotExponent);
+        }
+        normal_opacity = lerp(1.0f, factor, L.origin_w);
+    }
+    // computeAO, AOCommon.fxh:1-19 (aoRadius scaled by max(0, normal.z), ProjectorLightCore.fxh:127)
+    float ao_opacity = 1.0f;
+    const float ao_radius = L.ao_radius * fmaxf(0.0f, P.normal.z);
+    if ((ao_radius >= 0.5f) && have_sdf) {
+        const float distance = sample_distance_field<FMT>(mk3(p.x, p.y, p.z + P.normal.z * ao_radius), F.df, F.sdf);
+        if (STATS) st.samples++;
+        float r = 1.0f - sat(clampf(distance, 0.0f, ao_radius) / ao_radius);
+        r *= r;
+        r = 1.0f - r;
+        ao_opacity = (1.0f - L.ao_opacity) + (r * L.ao_opacity);
+    }
+    float opacity = ((distance_opacity * normal_opacity) * L.opacity) * ao_opacity;
+    // coneTrace towards the origin, :133-139 + ConeTrace.fxh:141-191: shade_light's general path
+    const float casts = L.shadows * (P.enable_shadows ? 1.0f : 0.0f);
+    if ((casts != 0.0f) && (opacity >= kProjectorTraceThreshold)) {
+        if (STATS && have_sdf) st.traced++;
+        f3 start = p + (P.normal * kProjectorSelfOcclusionHack);
+        const f3 tv = mk3(L.origin_x, L.origin_y, L.origin_z) - start;
+        const float trace_length = len3(tv);
+        const float data_y = fmaxf(trace_length - L.radius, 1.0f);
+        float data_x = ref::kTraceInitialOffsetPx;
+        float data_z = 1.0f;
+        const float cfg_z = fmaxf(1.0f, F.df.Packed1.w);
+        float steps_remaining = F.df.StepAndMisc2.x;
+        // (two VGPRs keep the cone configuration resident across the loop, as in shade_light)
+        float cone_max_radius = L.cfg_x, cone_growth = L.cfg_y;
+        asm volatile("" : "+v"(cone_max_radius), "+v"(cone_growth));
+        f3 dir = mk3(tv.x / trace_length, tv.y / trace_length, tv.z / trace_length);
+        // (the sampler treats a NaN coordinate as 0: hoisted as in shade_light's general path)
+        if ((start.x != start.x) || (dir.x != dir.x)) { start.x = 0.0f; dir.x = 0.0f; }
+        if ((start.y != start.y) || (dir.y != dir.y)) { start.y = 0.0f; dir.y = 0.0f; }
+        if ((start.z != start.z) || (dir.z != dir.z)) { start.z = 0.0f; dir.z = 0.0f; }
+        cone_trace_loop<FMT, STATS, false>(start, dir, data_y, cfg_z, cone_growth, cone_max_radius, F, data_x, data_z, steps_remaining, have_sdf, st);
+        const float visibility = fminf(data_z, steps_remaining / ref::kMaxStepRampWindow);
+        opacity *= pow_pos(sat(div_with_rcp(sat(visibility - ref::kFullyShadowedThreshold), kVisibilityRange, kVisibilityRangeRcp)), F.df.ConeAndMisc.z);
+    }
+    // ProjectorLightColorCore, :290-302
+    const float4 t = sample_projector_texture(tex, tx, ty);
+    out_r = (t.x * t.w) * opacity; out_g = (t.y * t.w) * opacity; out_b = (t.z * t.w) * opacity;
+    return true;
+}
+
+// The frame of directional_lights_kernel with its base value / blend / store / mirror / statistics tail as a COPY, to be kept in step
+// with it.  The shared form was built -- the base value and the store with its mirrors as two device functions both kernels call --
+// and compared (tools/isa_compare.py against the parent's listing): the four instantiations of directional_lights_kernel came out
+// `diff` (8 vector instructions fewer, one scalar instruction more, another schedule), and the existing passes are held not to move.
+template <int FMT, bool STATS>
+__global__ __launch_bounds__(kLightThreads) void projector_lights_kernel(const LightLaunch a, const ProjectorRec* __restrict__ recs, int tiles_x) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int tile_x = (int)blockIdx.x % tiles_x, tile_y = (int)blockIdx.x / tiles_x;
+    const int px = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
+    const int py = a.row_begin + tile_y * kTile + (wave >> 1) * 8 + (lane >> 3);
+    const bool in_image = (px < a.width) && (py < a.row_end);
+    if (__builtin_amdgcn_ballot_w64(in_image) == 0ull)
+        return;
+    Pixel P = sample_gbuffer((float)px, (float)py, a.env, a.gbuffer);
+    P.origin_x = 0; P.origin_y = 0; P.start_inside = false;
+    const float cxp = (float)px + 0.5f, cyp = (float)py + 0.5f;
+    const bool have_sdf = (a.sdf.texels != nullptr) && (a.df.Extent.x > 0.0f);
+    const InsideConsts no_table = {};
+    const TraceField field = { a.df, a.sdf, no_table, nullptr };
+    const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
+    auto through_half = [](float v) { return __half2float(__float2half_rn(v)); };
+    auto base_value = [&]() -> float4 {
+        float4 v = mk4(a.ambient[0], a.ambient[1], a.ambient[2], a.ambient[3]);
+        if (a.accumulate != 0 && in_image) {
+            if (a.format == ILM_LIGHTMAP_FLOAT4) v = load_target<ILM_LIGHTMAP_FLOAT4>(a.lightmap, o);
+            else if (a.format == ILM_LIGHTMAP_HALF4) v = load_target<ILM_LIGHTMAP_HALF4>(a.lightmap, o);
+            else v = load_target<ILM_LIGHTMAP_RGBA8>(a.lightmap, o);
+        }
+        if (a.blend_fp16 != 0) v = mk4(through_half(v.x), through_half(v.y), through_half(v.z), through_half(v.w));
+        return v;
+    };
+    const bool blend_fp16 = a.blend_fp16 != 0;
+    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if (blend_fp16) { const float4 v = base_value(); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
+    LightStats st;
+    const int light_count = a.light_count;
+    for (int k = 0; k < light_count; k++) {
+        const ProjectorRec& L = recs[k];
+        const float x0 = L.x0, y0 = L.y0, x1 = L.x1, y1 = L.y1;
+        const bool covered = in_image & (cxp >= x0) & (cxp < x1) & (cyp >= y0) & (cyp < y1);
+        if (__builtin_amdgcn_ballot_w64(covered) == 0ull)
+            continue;
+        if (!covered)
+            continue;
+        if (STATS) st.pairs++;
+        float cr, cg, cb;
+        if (!shade_projector<FMT, STATS>(P, L, field, have_sdf, a.ramp, st, cr, cg, cb))
+            continue;
+        if (blend_fp16) {
+            acc_r = through_half(acc_r + through_half(cr));
+            acc_g = through_half(acc_g + through_half(cg));
+            acc_b = through_half(acc_b + through_half(cb));
+            acc_a = through_half(acc_a + 1.0f);
+        } else {
+            acc_r += cr; acc_g += cg; acc_b += cb; acc_a += 1.0f;
+        }
+    }
+    if (!blend_fp16) {
+        const float4 v = base_value();
+        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+    }
+    if (in_image) {
+        const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
+        auto store_texel = [&](void* base) {
+            if (a.format == ILM_LIGHTMAP_FLOAT4) store_target<ILM_LIGHTMAP_FLOAT4>(base, o, v);
+            else if (a.format == ILM_LIGHTMAP_HALF4) store_target<ILM_LIGHTMAP_HALF4>(base, o, v);
+            else store_target<ILM_LIGHTMAP_RGBA8>(base, o, v);
+        };
+        store_texel(a.lightmap);
+        for (int m = 0; m < a.mirror_count; m++) store_texel(a.mirrors[m]);      // store-mode exchange of a group lightmap, as the sphere pass
+    }
+    if (STATS) {
+        for (int off = 32; off > 0; off >>= 1) {
+            st.samples += __shfl_down(st.samples, off);
+            st.pairs += __shfl_down(st.pairs, off);
+            st.traced += __shfl_down(st.traced, off);
+        }
+        if (lane == 0) {
+            atomicAdd(&a.stats[0], st.samples);
+            atomicAdd(&a.stats[1], st.pairs);
+            atomicAdd(&a.stats[2], st.traced);
+        }
+    }
+}
+
+hipError_t launch_prepare_projector_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
+                                           void* recs, hipStream_t stream) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(prepare_projector_lights_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, lights, count, env, df.ConeAndMisc.x,
+                       reinterpret_cast<ProjectorRec*>(recs));
+    return hipGetLastError();
+}
+
+hipError_t launch_projector_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
+    const int rows = a.row_end - a.row_begin;
+    if (rows <= 0 || a.width <= 0) return hipSuccess;
+    if (a.light_count == 0 && a.accumulate != 0) return hipSuccess;      // nothing to add: no texel (and no mirror) would change
+    const int tiles_x = (a.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
+    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y), block(kLightThreads);
+    const ProjectorRec* r = reinterpret_cast<const ProjectorRec*>(recs);
+    const bool stats = a.stats != nullptr;
+    if (a.sdf.format == ILM_SDF_FP16) {
+        if (stats) hipLaunchKernelGGL((projector_lights_kernel<ILM_SDF_FP16, true>), grid, block, 0, stream, a, r, tiles_x);
+        else hipLaunchKernelGGL((projector_lights_kernel<ILM_SDF_FP16, false>), grid, block, 0, stream, a, r, tiles_x);
+    } else {
+        if (stats) hipLaunchKernelGGL((projector_lights_kernel<ILM_SDF_UNORM16, true>), grid, block, 0, stream, a, r, tiles_x);
+        else hipLaunchKernelGGL((projector_lights_kernel<ILM_SDF_UNORM16, false>), grid, block, 0, stream, a, r, tiles_x);
+    }
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void divide_probe_kernel(const float* __restrict__ n, const float* __restrict__ d, int count,
                                                             float* __restrict__ out_fast, float* __restrict__ out_ieee) {
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;

@@ -434,6 +434,30 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("ShadowFilter", &DirectionalLightSource::ShadowFilter)
         .def_readwrite("TextureRef", &DirectionalLightSource::TextureRef)
         .def_readwrite("Quality", &DirectionalLightSource::Quality);
+    // Transform: 16 floats, row-major (M11 .. M44); Rotation: (X, Y, Z, W); Origin / Depth: None or a value; TextureRegion: (x1, y1, x2, y2)
+    py::class_<ProjectorLightSource>(m, "ProjectorLightSource").def(py::init<>())
+        .def_readwrite("SortKey", &ProjectorLightSource::SortKey).def_readwrite("Enabled", &ProjectorLightSource::Enabled)
+        .def_property("Transform", [](const ProjectorLightSource& l) { return std::vector<float>(&l.Transform.M[0][0], &l.Transform.M[0][0] + 16); },
+                      [](ProjectorLightSource& l, const std::vector<float>& v) { for (int i = 0; i < 16; i++) l.Transform.M[i / 4][i % 4] = v.at(i); })
+        VEC_PROP(ProjectorLightSource, Rotation, 4)
+        VEC_PROP(ProjectorLightSource, Scale, 2)
+        VEC_PROP(ProjectorLightSource, Position, 3)
+        .def_property("Origin", [](const ProjectorLightSource& l) -> py::object { return l.Origin ? py::cast(l3(*l.Origin)) : py::none(); },
+                      [](ProjectorLightSource& l, py::object v) { if (v.is_none()) l.Origin.reset(); else l.Origin = v3(v.cast<std::vector<float>>()); })
+        .def_readwrite("Depth", &ProjectorLightSource::Depth)
+        .def_property("TextureRegion", [](const ProjectorLightSource& l) {
+                          return std::vector<float>{ l.TextureRegion.TopLeft.X, l.TextureRegion.TopLeft.Y, l.TextureRegion.BottomRight.X, l.TextureRegion.BottomRight.Y }; },
+                      [](ProjectorLightSource& l, const std::vector<float>& b) {
+                          l.TextureRegion = Bounds{ Vector2{ b.at(0), b.at(1) }, Vector2{ b.at(2), b.at(3) } }; })
+        .def_readwrite("Wrap", &ProjectorLightSource::Wrap)
+        .def_readwrite("Radius", &ProjectorLightSource::Radius).def_readwrite("RampLength", &ProjectorLightSource::RampLength)
+        .def_property("RampMode", [](const ProjectorLightSource& l) { return (int)l.RampMode; }, [](ProjectorLightSource& l, int v) { l.RampMode = (LightSourceRampMode)v; })
+        .def_readwrite("CastsShadows", &ProjectorLightSource::CastsShadows)
+        .def_readwrite("AmbientOcclusionRadius", &ProjectorLightSource::AmbientOcclusionRadius)
+        .def_readwrite("AmbientOcclusionOpacity", &ProjectorLightSource::AmbientOcclusionOpacity)
+        .def_readwrite("Opacity", &ProjectorLightSource::Opacity)
+        .def_readwrite("TextureRef", &ProjectorLightSource::TextureRef)
+        .def_readwrite("Quality", &ProjectorLightSource::Quality);
     py::class_<ReplicatedLight>(m, "ReplicatedLight").def(py::init<>())
         VEC_PROP(ReplicatedLight, Position, 3)
         .def_readwrite("Radius", &ReplicatedLight::Radius).def_readwrite("RampLength", &ReplicatedLight::RampLength)
@@ -491,6 +515,7 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("Lights", &LightingEnvironment::Lights)
         .def_readwrite("Replicators", &LightingEnvironment::Replicators)
         .def_readwrite("DirectionalLights", &LightingEnvironment::DirectionalLights)
+        .def_readwrite("ProjectorLights", &LightingEnvironment::ProjectorLights)
         .def_readwrite("ParticleLights", &LightingEnvironment::ParticleLights)
         .def_property_readonly("Obstructions", [](LightingEnvironment& e) -> LightObstructionCollection& { return e.Obstructions; }, py::return_value_policy::reference_internal)
         .def_readwrite("HeightVolumes", &LightingEnvironment::HeightVolumes)
@@ -687,5 +712,13 @@ PYBIND11_MODULE(_host, m) {
             IlmLightVertex v;
             if (!LightingRenderer::PackDirectionalLight(l, intensityScale, v)) return py::none();
             return py::bytes((const char*)&v, sizeof(v));
-        });
+        })
+        .def_static("PackProjectorLightBytes", [](const ProjectorLightSource& l, float intensityScale, bool haveDF, float maximumZ, std::vector<float> renderScale,
+                                                  float mipBias) -> py::object {
+            IlmLightVertex v;
+            if (!LightingRenderer::PackProjectorLight(l, intensityScale, haveDF, maximumZ, Vector2{ renderScale.at(0), renderScale.at(1) }, mipBias, v))
+                return py::none();
+            return py::bytes((const char*)&v, sizeof(v));
+        }, py::arg("light"), py::arg("intensityScale") = 1.0f, py::arg("haveDistanceField") = true, py::arg("maximumZ") = 128.0f,
+           py::arg("renderScale") = std::vector<float>{ 1.0f, 1.0f }, py::arg("mipBias") = -0.33f);
 }

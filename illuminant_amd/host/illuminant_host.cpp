@@ -1299,6 +1299,82 @@ bool LightingRenderer::PackDirectionalLight(const DirectionalLightSource& l, flo
     return true;
 }
 
+Matrix Matrix::CreateScale(float x, float y, float z) { Matrix m; m.M[0][0] = x; m.M[1][1] = y; m.M[2][2] = z; return m; }
+Matrix Matrix::CreateTranslation(Vector3 t) { Matrix m; m.M[3][0] = t.X; m.M[3][1] = t.Y; m.M[3][2] = t.Z; return m; }
+Matrix Matrix::CreateFromQuaternion(Vector4 q) {
+    const float xx = q.X * q.X, yy = q.Y * q.Y, zz = q.Z * q.Z, xy = q.X * q.Y, zw = q.Z * q.W, zx = q.Z * q.X, yw = q.Y * q.W, yz = q.Y * q.Z, xw = q.X * q.W;
+    Matrix m;
+    m.M[0][0] = 1.0f - (2.0f * (yy + zz)); m.M[0][1] = 2.0f * (xy + zw); m.M[0][2] = 2.0f * (zx - yw);
+    m.M[1][0] = 2.0f * (xy - zw); m.M[1][1] = 1.0f - (2.0f * (zz + xx)); m.M[1][2] = 2.0f * (yz + xw);
+    m.M[2][0] = 2.0f * (zx + yw); m.M[2][1] = 2.0f * (yz - xw); m.M[2][2] = 1.0f - (2.0f * (yy + xx));
+    return m;
+}
+Matrix Matrix::Multiply(const Matrix& a, const Matrix& b) {
+    Matrix r;
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++)
+            r.M[i][j] = (((a.M[i][0] * b.M[0][j]) + (a.M[i][1] * b.M[1][j])) + (a.M[i][2] * b.M[2][j])) + (a.M[i][3] * b.M[3][j]);
+    return r;
+}
+// the cofactor expansion over 2 x 2 minors of the lower rows (what XNA's Matrix.Invert evaluates); a singular matrix gives infinities or
+// NaN, as there
+Matrix Matrix::Invert(const Matrix& m) {
+    const float (&a)[4][4] = m.M;
+    auto minor2 = [&](int r0, int r1, int c0, int c1) { return (a[r0][c0] * a[r1][c1]) - (a[r0][c1] * a[r1][c0]); };
+    // cofactor of row `skip` column j: the 3 x 3 determinant of the other rows (in order) without column j, expanded along its first row
+    auto cofactor = [&](int skip, int j) {
+        int rows[3], cols[3], n = 0, k = 0;
+        for (int i = 0; i < 4; i++) if (i != skip) rows[n++] = i;
+        for (int i = 0; i < 4; i++) if (i != j) cols[k++] = i;
+        const float d = ((a[rows[0]][cols[0]] * minor2(rows[1], rows[2], cols[1], cols[2])) - (a[rows[0]][cols[1]] * minor2(rows[1], rows[2], cols[0], cols[2]))) +
+                        (a[rows[0]][cols[2]] * minor2(rows[1], rows[2], cols[0], cols[1]));
+        return ((skip + j) & 1) ? -d : d;
+    };
+    float c[4][4];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) c[i][j] = cofactor(i, j);
+    const float det = (((a[0][0] * c[0][0]) + (a[0][1] * c[0][1])) + (a[0][2] * c[0][2])) + (a[0][3] * c[0][3]);
+    const float inv = 1.0f / det;
+    Matrix r;
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) r.M[i][j] = c[j][i] * inv;      // the adjugate is the cofactors' transpose
+    return r;
+}
+
+// RenderProjectorLightSource, LightingRenderer.cs:1386-1446
+bool LightingRenderer::PackProjectorLight(const ProjectorLightSource& l, float intensityScale, bool haveDistanceField, float maximumZ, Vector2 renderScale,
+                                          float mipBiasSetting, IlmLightVertex& v) {
+    const RampTexture* tex = l.TextureRef.get();
+    if (!tex || tex->Width <= 0 || tex->Height <= 0)
+        return false;
+    std::memset(&v, 0, sizeof(v));
+    const float texW = (float)tex->Width, texH = (float)tex->Height;
+    Matrix m = l.Transform;
+    m = Matrix::Multiply(m, Matrix::CreateScale(texW * l.Scale.X, texH * l.Scale.Y, l.Depth.value_or(maximumZ)));
+    m = Matrix::Multiply(m, Matrix::CreateTranslation(l.Position));
+    Matrix inv = Matrix::Invert(m);
+    if (!(l.Rotation.X == 0 && l.Rotation.Y == 0 && l.Rotation.Z == 0 && l.Rotation.W == 1)) {
+        // in texture space, about the centre of the region (:1400-1415)
+        const float sx = l.TextureRegion.BottomRight.X - l.TextureRegion.TopLeft.X, sy = l.TextureRegion.BottomRight.Y - l.TextureRegion.TopLeft.Y;
+        inv = Matrix::Multiply(inv, Matrix::CreateTranslation(Vector3{ -sx * 0.5f, -sy * 0.5f, 0 }));
+        inv = Matrix::Multiply(inv, Matrix::CreateFromQuaternion(l.Rotation));
+        inv = Matrix::Multiply(inv, Matrix::CreateTranslation(Vector3{ sx * 0.5f, sy * 0.5f, 0 }));
+    }
+    const double approximateScale = ((l.Scale.X * renderScale.X) + (l.Scale.Y * renderScale.Y)) / 2.0;
+    const double invApproximateScale = 1.0 / approximateScale;
+    const float mipBias = (float)std::max(0.0, (std::log(invApproximateScale) / std::log(2.0)) + mipBiasSetting);
+    v.LightPosition1 = { inv.M[0][0], inv.M[0][1], inv.M[0][2], inv.M[0][3] };
+    v.LightPosition2 = { inv.M[1][0], inv.M[1][1], inv.M[1][2], inv.M[1][3] };
+    if (l.Origin) v.LightPosition3 = { l.Origin->X, l.Origin->Y, l.Origin->Z, 1 };
+    else v.LightPosition3 = { 0, 0, 0, 0 };
+    v.Color1 = { inv.M[2][0], inv.M[2][1], inv.M[2][2], inv.M[2][3] };
+    v.Color2 = { inv.M[3][0], inv.M[3][1], inv.M[3][2], mipBias };
+    v.LightProperties = { l.Radius, l.RampLength, (float)(int)l.RampMode, (l.CastsShadows && haveDistanceField && l.Origin) ? 1.0f : 0.0f };
+    v.MoreLightProperties = { l.AmbientOcclusionRadius, l.Opacity * intensityScale, l.Wrap ? 0.0f : 1.0f, l.AmbientOcclusionOpacity };
+    v.EvenMoreLightProperties = { l.TextureRegion.TopLeft.X, l.TextureRegion.TopLeft.Y, l.TextureRegion.BottomRight.X, l.TextureRegion.BottomRight.Y };
+    return true;
+}
+
 // SetDistanceFieldParameters, LightingRenderer.cs:1894-1940
 IlmDistanceFieldUniforms LightingRenderer::GetDistanceFieldUniforms(const RendererQualitySettings& q) const {
     IlmDistanceFieldUniforms dfu;
@@ -1336,26 +1412,34 @@ IlmEnvironment LightingRenderer::GetEnvironmentUniforms() const {
     return e;
 }
 
-// RenderLighting, LightingRenderer.cs:917-1191 (sphere, directional and particle lights)
+// RenderLighting, LightingRenderer.cs:917-1191 (sphere, directional, projector and particle lights)
 void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int rowEnd, IlmRenderStats* stats) {
     if (rowEnd < 0) rowEnd = Configuration.RenderHeight;
     // the probe techniques of directional lights (DirectionalLightProbe*) are not built: refuse rather than leave them out of the probes
     if (Probes.Count() > 0)
         for (const DirectionalLightSource& d : Environment->DirectionalLights)
             if (d.Enabled) throw InvalidOperationException("RenderLighting: directional lights do not reach light probes yet");
+    // nor is the projector lights' (ProjectorLightProbe.fx)
+    if (Probes.Count() > 0)
+        for (const ProjectorLightSource& pl : Environment->ProjectorLights)
+            if (pl.Enabled) throw InvalidOperationException("RenderLighting: projector lights do not reach light probes yet");
     vertices.clear();
     // LightSorter (:2066-2096): SortKey first; blend mode, ramp texture and type are the same for every light of this pass.  The
     // reference's sort is not stable for equal keys; a stable one keeps list order, which is one of its possible outcomes
     // (Lights before Replicators here, since the mirror holds them in two lists).
     // Directional lights sort after spheres of equal key (TypeID 2 after 1, :2094): listed last, the stable sort keeps them there.
-    struct Entry { int sortKey; const SphereLightSource* sphere; const LightSourceReplicator* replicator; const DirectionalLightSource* directional; };
+    // Projector lights likewise, after the directional ones.
+    struct Entry { int sortKey; const SphereLightSource* sphere; const LightSourceReplicator* replicator; const DirectionalLightSource* directional;
+                   const ProjectorLightSource* projector; };
     std::vector<Entry> sorted;
     for (const SphereLightSource& l : Environment->Lights)
-        if (l.Enabled) sorted.push_back({ l.SortKey, &l, nullptr, nullptr });
+        if (l.Enabled) sorted.push_back({ l.SortKey, &l, nullptr, nullptr, nullptr });
     for (const LightSourceReplicator& r : Environment->Replicators)
-        if (r.Enabled) sorted.push_back({ r.SortKey, nullptr, &r, nullptr });
+        if (r.Enabled) sorted.push_back({ r.SortKey, nullptr, &r, nullptr, nullptr });
     for (const DirectionalLightSource& d : Environment->DirectionalLights)
-        if (d.Enabled) sorted.push_back({ d.SortKey, nullptr, nullptr, &d });
+        if (d.Enabled) sorted.push_back({ d.SortKey, nullptr, nullptr, &d, nullptr });
+    for (const ProjectorLightSource& pl : Environment->ProjectorLights)
+        if (pl.Enabled) sorted.push_back({ pl.SortKey, nullptr, nullptr, nullptr, &pl });
     std::stable_sort(sorted.begin(), sorted.end(), [](const Entry& x, const Entry& y) { return x.sortKey < y.sortKey; });
     // GetLightRenderState (:799-845): lights that share a ramp texture and quality settings form one render state (BlendState is
     // additive for every light here); the states are drawn one after the other onto the same target, in the order their keys first appear.
@@ -1379,8 +1463,25 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     directionalKeys.clear();
     directionalQuality.clear();
     directionalGroups.clear();
+    // projector lights: one render state per texture (and quality) -- the key's RampTexture member is the projected texture (:1389)
+    projectorKeys.clear();
+    projectorQuality.clear();
+    projectorGroups.clear();
     for (const Entry& e : sorted) {
         IlmLightVertex v;
+        if (e.projector) {
+            if (!PackProjectorLight(*e.projector, intensityScale, Field != nullptr, Environment->MaximumZ, Configuration.RenderScale,
+                                    Configuration.ProjectorMipBias, v))
+                continue;
+            const RampTexture* texture = e.projector->TextureRef.get();
+            const RendererQualitySettings* quality = e.projector->Quality.get();
+            size_t g = 0;
+            while (g < projectorKeys.size() && !(projectorKeys[g] == texture && projectorQuality[g] == quality)) g++;
+            if (g == projectorKeys.size()) { projectorKeys.push_back(texture); projectorQuality.push_back(quality); projectorGroups.emplace_back(); }
+            projectorGroups[g].push_back(v);
+            vertices.push_back(v);
+            continue;
+        }
         if (e.directional) {
             if (!PackDirectionalLight(*e.directional, intensityScale, v))
                 continue;
@@ -1423,7 +1524,7 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     // clear colour: Ambient * intensityScale (:1013-1024)
     const float ambient[4] = { Environment->Ambient.X * intensityScale, Environment->Ambient.Y * intensityScale,
                                Environment->Ambient.Z * intensityScale, Environment->Ambient.W * intensityScale };
-    // no lights: the clear still happens (with directional lights alone, their first launch carries it)
+    // no lights: the clear still happens (with directional lights alone, their first launch carries it; projector groups always add)
     if (groups.empty() && directionalGroups.empty()) { groupKeys.push_back(nullptr); groupQuality.push_back(nullptr); groups.emplace_back(); }
     if (stats) { stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0; }
     for (size_t g = 0; g < groups.size(); g++) {
@@ -1445,6 +1546,16 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
                                                     stats ? &gs : nullptr));
         if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
     }
+    // the projector render states: the group's texture, then one call; the ramp binding is not theirs
+    for (size_t g = 0; g < projectorGroups.size(); g++) {
+        ThrowIfFailed(ilm_ctx_set_projector_texture(Context.Handle(), projectorKeys[g]->Texels.data(), projectorKeys[g]->Width, projectorKeys[g]->Height));
+        IlmRenderStats gs{};
+        const IlmDistanceFieldUniforms gdfu = projectorQuality[g] ? GetDistanceFieldUniforms(*projectorQuality[g]) : dfu;
+        ThrowIfFailed(ilm_render_projector_lights(Context.Handle(), projectorGroups[g].data(), (int32_t)projectorGroups[g].size(), &env, &gdfu, gbuffer,
+                                                  Field ? Field->Texture() : 0, nullptr, lightmap, rowBegin, rowEnd, stats ? &gs : nullptr));
+        if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
+    }
+    if (!projectorGroups.empty()) ThrowIfFailed(ilm_ctx_set_projector_texture(Context.Handle(), nullptr, 0, 0));
     BindRamp(nullptr);         // particle lights have no ramp technique (:176-178)
     // particle light sources: one more light-type render state each, blended on top (:1126-1141)
     for (const ParticleLightSource& pls : Environment->ParticleLights) {

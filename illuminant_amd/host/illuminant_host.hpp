@@ -736,6 +736,38 @@ private:
     std::optional<Vector3> direction;
 };
 
+// Matrix / Quaternion (XNA: row vectors, M[r][c] = M(r+1)(c+1)) with the operations RenderProjectorLightSource uses, each in fp32 with
+// one rounding per operation in the order the XNA / MonoGame sources write them
+struct Matrix {
+    float M[4][4] = { { 1, 0, 0, 0 }, { 0, 1, 0, 0 }, { 0, 0, 1, 0 }, { 0, 0, 0, 1 } };
+    static Matrix CreateScale(float x, float y, float z);
+    static Matrix CreateTranslation(Vector3 t);
+    static Matrix CreateFromQuaternion(Vector4 q);      // q = (X, Y, Z, W)
+    static Matrix Multiply(const Matrix& a, const Matrix& b);
+    static Matrix Invert(const Matrix& m);
+};
+
+// ProjectorLightSource, LightSource.cs:507-599 (+ the LightSource members RenderProjectorLightSource reads, LightingRenderer.cs:1386-1446)
+struct ProjectorLightSource {
+    int SortKey = 0;
+    bool Enabled = true;
+    Matrix Transform;
+    Vector4 Rotation{0, 0, 0, 1};                 // Quaternion (X, Y, Z, W); identity: no rotation about the region's centre
+    Vector2 Scale{1, 1};
+    Vector3 Position;
+    std::optional<Vector3> Origin;                // set: projected from there, shadowed and shaded by surface normals
+    std::optional<float> Depth;                   // height of the projection; unset => Environment.MaximumZ
+    Lighting::Bounds TextureRegion{ {0, 0}, {1, 1} };    // Bounds.Unit
+    bool Wrap = true;
+    float Radius = 0, RampLength = 1;
+    LightSourceRampMode RampMode = LightSourceRampMode::Linear;
+    bool CastsShadows = true;
+    float AmbientOcclusionRadius = 0, AmbientOcclusionOpacity = 1;
+    float Opacity = 1;
+    std::shared_ptr<RampTexture> TextureRef;      // the projected texture (its id is the pointer, its size Width x Height); null: the light is skipped (:1389-1391)
+    std::shared_ptr<RendererQualitySettings> Quality;
+};
+
 // ReplicatedLight / LightSourceReplicator, LightSource.cs:601-620: one template, many placements.  Each placement may override the
 // per-light values; everything else (ramp mode, shadows, AO, falloff, ramp texture, quality) comes from the template.
 struct ReplicatedLight {
@@ -840,6 +872,7 @@ struct LightingEnvironment {
     std::vector<SphereLightSource> Lights;
     std::vector<LightSourceReplicator> Replicators;    // LightSourceReplicator entries of Lights in the reference
     std::vector<DirectionalLightSource> DirectionalLights;   // DirectionalLightSource entries of Lights in the reference
+    std::vector<ProjectorLightSource> ProjectorLights;       // ProjectorLightSource entries of Lights in the reference
     std::vector<ParticleLightSource> ParticleLights;   // ParticleLightSource entries of Lights in the reference (one render state each)
     LightObstructionCollection Obstructions;
     std::vector<HeightVolume> HeightVolumes;
@@ -871,6 +904,7 @@ struct RendererConfiguration {
     bool FloatLightmap = false;       // extension: fp32 lightmap (parity format)
     bool EnableBrightnessEstimation = false;   // LightingRenderer.Configuration.cs: RenderLighting keeps what TryComputeHistogram reads
     std::shared_ptr<RampTexture> DefaultRampTexture;   // LightingRenderer.Configuration.cs:78
+    float ProjectorMipBias = -0.33f;       // LightingRenderer.Configuration.cs:164
     RendererConfiguration(int w, int h) : RenderWidth(w), RenderHeight(h) {}
 };
 
@@ -921,7 +955,8 @@ public:
     IlmHandle GBuffer() const { return gbuffer; }
 
     // RenderLighting, :917-1191: clears to Ambient * intensityScale and adds every sphere light, then every directional light, then
-    // the particle lights.  Directional lights do not reach light probes yet: with probes and an enabled directional light it throws.
+    // every projector light (grouped by texture), then the particle lights.  Directional and projector lights do not reach light
+    // probes yet: with probes and an enabled light of either type it throws.
     // [rowBegin, rowEnd) restricts the pass to a screen strip (multi-GPU split); rowEnd < 0 => whole frame.
     void RenderLighting(float intensityScale = 1.0f, int rowBegin = 0, int rowEnd = -1, IlmRenderStats* stats = nullptr);
     void ReadLightmap(void* dst, int firstRow, int rowCount) const;
@@ -955,6 +990,10 @@ public:
     static bool PackSphereLight(const SphereLightSource& l, float intensityScale, bool haveDistanceField, IlmLightVertex& v);
     // RenderDirectionalLightSource, :1256-1293: false for Opacity <= 0 (:1258); CastsShadows is packed without the field test (:1279)
     static bool PackDirectionalLight(const DirectionalLightSource& l, float intensityScale, IlmLightVertex& v);
+    // RenderProjectorLightSource, :1386-1446: false for a light without a texture (:1389-1391).  maximumZ: Environment.MaximumZ, the
+    // depth of a light that sets none; renderScale / mipBias: Configuration.RenderScale / ProjectorMipBias
+    static bool PackProjectorLight(const ProjectorLightSource& l, float intensityScale, bool haveDistanceField, float maximumZ, Vector2 renderScale,
+                                   float mipBias, IlmLightVertex& v);
     // SetDistanceFieldParameters, :1894-1940
     IlmDistanceFieldUniforms GetDistanceFieldUniforms(const RendererQualitySettings& q) const;
     // ComputeUniforms :691-701 + SetGBufferParameters LightingRenderer.GBuffer.cs:520-534
@@ -978,6 +1017,10 @@ private:
     std::vector<const RampTexture*> directionalKeys;
     std::vector<const RendererQualitySettings*> directionalQuality;
     std::vector<std::vector<IlmLightVertex>> directionalGroups;
+    // the projector groups, drawn after the directional ones: one per (texture, quality), the texture bound per group
+    std::vector<const RampTexture*> projectorKeys;
+    std::vector<const RendererQualitySettings*> projectorQuality;
+    std::vector<std::vector<IlmLightVertex>> projectorGroups;
     const RampTexture* boundRamp = nullptr;
     float lastInverseScaleFactor = 0;     // RenderedLighting.InverseScaleFactor of the last RenderLighting; 0 = none yet
     void BindRamp(const RampTexture* ramp);

@@ -101,6 +101,7 @@ SYMBOLS = {
     "ilm_lightmap_destroy": (_I, [_H]),
     "ilm_render_sphere_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
     "ilm_render_directional_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
+    "ilm_render_projector_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
     "ilm_render_particle_lights": (_I, [_H, _H, _P, _I, _P, _P, _P, _H, _H, _H, _I, _I, _P]),
     "ilm_render_light_probes": (_I, [_H, _P, _I, _P, _P, _I, _P, _P, _H, _P]),
     "ilm_system_readback": (_I, [_H, _P, _I, _P, _P, _I, C.POINTER(_I)]),
@@ -108,6 +109,7 @@ SYMBOLS = {
     "ilm_render_particles": (_I, [_H, _P, _I, _P, _H, _P]),
     "ilm_lightmap_clear": (_I, [_H, _P]),
     "ilm_ctx_set_light_ramp": (_I, [_H, _P, _I, _I]),
+    "ilm_ctx_set_projector_texture": (_I, [_H, _P, _I, _I]),
     "ilm_ctx_set_lightmap_blend": (_I, [_H, _I]),
     "ilm_ctx_set_light_split": (_I, [_H, _I]),
     "ilm_system_set_bitmap": (_I, [_H, _P, _I, _I]),
@@ -222,6 +224,10 @@ class Context:
             return
         a = np.ascontiguousarray(texels, dtype=np.float32)
         check(lib().ilm_ctx_set_light_ramp(self.handle, _ptr(a), a.shape[1], a.shape[0]))
+
+    def set_projector_texture(self, texels):
+        """ilm_ctx_set_projector_texture: (h, w, 4) float32 texture of the projector group rendered next (one level); None unbinds."""
+        set_projector_texture(self, texels)
 
     def set_lightmap_blend(self, fp16_per_light):
         """ilm_ctx_set_lightmap_blend: True = the reference's HalfVector4 render target (rounded through fp16 after every light)."""
@@ -874,6 +880,34 @@ def render_directional_lights(ctx, lights, env, df, gbuffer, sdf, ambient, light
     amb = (C.c_float * 4)(*[float(x) for x in ambient]) if ambient is not None else None
     stats = abi.RenderStats() if want_stats else None
     check(lib().ilm_render_directional_lights(
+        ctx.handle, C.cast(lights, C.c_void_p) if n else None, n, _byref(env), _byref(df),
+        gbuffer.handle if gbuffer is not None else abi.Handle(0),
+        sdf.handle if sdf is not None else abi.Handle(0),
+        C.cast(amb, C.c_void_p) if amb is not None else None, lightmap.handle, row_begin, row_end, _byref(stats)))
+    return stats
+
+
+def set_projector_texture(ctx, texels):
+    """ilm_ctx_set_projector_texture: (h, w, 4) float32 texels of the projector-light group rendered next; None unbinds.  The ramp
+    binding (Context.set_light_ramp) is a separate one."""
+    if texels is None:
+        check(lib().ilm_ctx_set_projector_texture(ctx.handle, None, 0, 0))
+        return
+    a = np.ascontiguousarray(texels, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("a projector texture is (height, width, 4) float32")
+    check(lib().ilm_ctx_set_projector_texture(ctx.handle, _ptr(a), a.shape[1], a.shape[0]))
+
+
+def render_projector_lights(ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin=0, row_end=None, want_stats=False):
+    """ilm_render_projector_lights.  lights: ctypes array of abi.LightVertex packed as RenderProjectorLightSource packs them (or None
+    for zero lights), lit through the texture set_projector_texture bound; ambient None = add this group to what the lightmap holds."""
+    if row_end is None:
+        row_end = lightmap.height
+    n = len(lights) if lights is not None else 0
+    amb = (C.c_float * 4)(*[float(x) for x in ambient]) if ambient is not None else None
+    stats = abi.RenderStats() if want_stats else None
+    check(lib().ilm_render_projector_lights(
         ctx.handle, C.cast(lights, C.c_void_p) if n else None, n, _byref(env), _byref(df),
         gbuffer.handle if gbuffer is not None else abi.Handle(0),
         sdf.handle if sdf is not None else abi.Handle(0),

@@ -805,6 +805,24 @@ def directional_light(direction=None, bounds=None, color=(1, 1, 1, 1), opacity=1
     return v
 
 
+def projector_light(forward, region=(0.0, 0.0, 1.0, 1.0), origin=None, radius=4.0, ramp_length=32.0, ramp_mode=0, casts_shadows=True,
+                    have_distance_field=True, ao_radius=0.0, ao_opacity=1.0, opacity=1.0, intensity_scale=1.0, wrap=False, mip_bias=0.0):
+    """RenderProjectorLightSource's vertex, LightingRenderer.cs:1422-1442, from the FORWARD matrix (texture space -> world, row vectors:
+    what the reference builds from Transform, the scale and the translation): its inverse goes into LightPosition1, LightPosition2,
+    Color1, Color2, inverted here in float64 and rounded once (PackProjectorLight of the host mirror restates Matrix.Invert in fp32)."""
+    inv = np.linalg.inv(np.asarray(forward, np.float64).reshape(4, 4)).astype(np.float32)
+    v = abi.LightVertex()
+    v.LightPosition1 = abi.f4(*inv[0])
+    v.LightPosition2 = abi.f4(*inv[1])
+    v.LightPosition3 = abi.f4(origin[0], origin[1], origin[2], 1.0) if origin is not None else abi.f4(0, 0, 0, 0)
+    v.Color1 = abi.f4(*inv[2])
+    v.Color2 = abi.f4(inv[3][0], inv[3][1], inv[3][2], mip_bias)
+    v.LightProperties = abi.f4(radius, ramp_length, float(ramp_mode), 1.0 if (casts_shadows and have_distance_field and origin is not None) else 0.0)
+    v.MoreLightProperties = abi.f4(ao_radius, np.float32(opacity) * np.float32(intensity_scale), 0.0 if wrap else 1.0, ao_opacity)
+    v.EvenMoreLightProperties = abi.f4(*region)
+    return v
+
+
 def random_lights(seed, n, width, height, z=(8.0, 64.0), radius=24.0, ramp=(200.0, 550.0), **kw):
     xs = uniform(seed + 1, (n,), 0, width)
     ys = uniform(seed + 2, (n,), 0, height)

@@ -32,7 +32,8 @@ extern "C" {
 
 /* 11: + ilm_engine_step_batch, ilm_debug_last_step_batch, ILM_STEP_KERNEL_BATCH; later, under the same number (no layout changed, nothing
  * removed): + ilm_visualize_distance_field / IlmVisualizeVertex, IlmVisualizeParams, ILM_VISUALIZE_* (distance-field views);
- * + ilm_render_directional_lights (directional lights; no new struct: the reference packs them into a LightVertex).
+ * + ilm_render_directional_lights (directional lights; no new struct: the reference packs them into a LightVertex);
+ * + ilm_ctx_set_projector_texture, ilm_render_projector_lights (projector lights; a LightVertex again).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -807,6 +808,72 @@ int32_t ilm_render_directional_lights(IlmHandle ctx,
                                       const float ambient[4],
                                       IlmHandle lightmap, int32_t row_begin, int32_t row_end,
                                       IlmRenderStats* stats);
+
+/* ProjectorLightSource.TextureRef of the light group rendered by the FOLLOWING ilm_render_projector_lights calls (the reference groups
+ * projector lights by texture, one LightTypeRenderStateKey each, and binds it as the group's RampTexture; sampler
+ * ProjectorTextureSampler, Illuminant/Shaders/ProjectorLightCore.fxh:11-18: LINEAR, WRAP on both axes): width * height float4 texels,
+ * row-major, ONE level.  Any size from 1 x 1 up is a texture; width == 0 unbinds.  A binding of its own: ilm_ctx_set_light_ramp's (U
+ * CLAMP, a 1 x 1 ramp is none) is neither read nor changed by it, nor by ilm_render_projector_lights.  The texels are copied: the call
+ * waits for the context's queued work (an earlier pass may still read the texels it replaces) and copies synchronously, so a host keeps a
+ * texture bound over as many calls and frames as it serves and binds only when the group's texture changes. */
+int32_t ilm_ctx_set_projector_texture(IlmHandle ctx, const IlmFloat4* texels, int32_t width, int32_t height);
+
+/* The projector-light pass of LightingRenderer.RenderLighting: technique ProjectorLight (Illuminant/Shaders/ProjectorLight.fx:14-56 over
+ * ProjectorLightCore.fxh), one quad per light, added onto the lightmap like every other light type.  The arguments mean what they mean
+ * for ilm_render_directional_lights: gbuffer == 0 => ground plane, sdf == 0 => no distance field (which is the technique
+ * ProjectorLightWithoutDistanceField), ambient == NULL => the lights are ADDED to what rows [row_begin, row_end) hold, ambient != NULL =>
+ * every pixel of the rows is cleared to it first (whatever light_count is, 0 included), stats != NULL => the counting variant runs and
+ * the call synchronises.  Any light_count from 0 to 2^24 (more are refused); light_count > 0 with no projector texture bound is refused (ILM_ERR_INVALID_ARGUMENT:
+ * the reference skips a light whose texture is null before it packs it).  ilm_ctx_set_lightmap_blend applies (fp32 registers over this
+ * call's lights in list order, the sum added to the base value and rounded once at the store; or the fp16-per-light model).
+ * Vertex layout, as RenderProjectorLightSource fills it (Illuminant/Lighting/LightingRenderer.cs:1386-1446):
+ *   LightPosition1, LightPosition2, Color1, Color2   rows 1-4 of the inverse matrix M (world -> texture space); Color2.w carries the mip
+ *                                           bias and the matrix's m44 is 1, as the vertex shader restores it (ProjectorLightCore.fxh:244-245)
+ *   LightPosition3                          (Origin, 1), or all 0 without an origin
+ *   LightProperties                         Radius, RampLength, RampMode (not read), shadows ? 1 : 0
+ *   MoreLightProperties                     AmbientOcclusionRadius, Opacity * intensityScale, clamp (1 = not Wrap), AmbientOcclusionOpacity
+ *   EvenMoreLightProperties                 the texture region x1, y1, x2, y2
+ * Per pixel, fp32 with one rounding per + - * / sqrt, p = the shaded point, region = EvenMoreLightProperties:
+ *   t_c = ((p.x * m1c + p.y * m2c) + p.z * m3c) + 1 * m4c for c = x, y, z, w; t.xyz /= t.w (IEEE divisions); t.xy += region.xy;
+ *   t.z = max(0, t.z); clamped = clamp(t.xyz, (region.xy, 0), (region.zw, 1));
+ *   distanceToVolume = min(length(clamped - t), 0.001f) * (1.0f / 0.001f);
+ *   distanceOpacity = clamp > 0.5 ? max(1 - distanceToVolume, 0) : 1;
+ *   visible = distanceOpacity > 0 && p.x > -9999 && MoreLightProperties.y > 0;
+ *   t.xy = t.xy + (clamped.xy - t.xy) * clamp;
+ *   normalOpacity = 1 + (computeNormalFactor(normalize(p - origin.xyz), normal) - 1) * origin.w -- the sphere pass's DOT_OFFSET,
+ *   DOT_RAMP_RANGE, DOT_EXPONENT and its rule for a zero normal (factor 1), IEEE divisions.  DEFINED DEVIATION: when origin.w == 0
+ *   exactly the factor is not evaluated and normalOpacity is 1 -- the lerp's value for every finite factor; it removes the reference's
+ *   NaN at a shaded point equal to a zero origin.
+ *   AO as for directional lights: radius * max(0, normal.z), sampled only when >= 0.5 and a field is bound;
+ *   opacity = ((distanceOpacity * normalOpacity) * MoreLightProperties.y) * aoOpacity, times the cone opacity when the pair traces:
+ *   LightProperties.w * enableShadows != 0 and that opacity >= 0.75 / 255 -- the sphere light's coneTrace from p + 1.5 * normal towards
+ *   origin.xyz with lightRamp = (Radius, RampLength) and cone growth 1;
+ *   rgb added = (tex.rgb * tex.a) * opacity, alpha + 1, with tex = the texture at (t.x, t.y).
+ * Texture fetch: tex2Dlod(ProjectorTextureSampler, (u, v, 0, mipBias)) on the bound one-level texture -- every LOD reads level 0, as a
+ * sampler does for a texture without a mip chain (mip chains are not built: the bias is carried and not read).  LINEAR: s = u * width -
+ * 0.5, first tap floor(s), weight s - floor(s), second tap = the integer first tap + 1; WRAP: both taps modulo the size in exact
+ * integer arithmetic for every finite coordinate, tap 0 for a non-finite one; the same on v.  Every index lies inside the texture.
+ * Discards: a pixel outside the footprint, a fullbright pixel and one that is not `visible` get nothing from the light -- no rgb and
+ * no + 1 on alpha.  No shadow filter (the shader never calls it) and no opacity discard: a visible pixel whose opacity is 0 adds alpha 1.
+ * Coverage -- the reference leaves it to the rasteriser; here, as for directional lights: pixel (x, y) is covered iff its centre lies
+ * in the half-open screen rectangle [x0, x1) x [y0, y1) of the light's world rectangle, mapped by (world - ViewportPosition) *
+ * (ViewportScale * RenderScale), the scales multiplied first.  With clamp <= 0.5 the world rectangle is (-9999, -9999) .. (9999, 9999).
+ * With clamp > 0.5 it is the vertex shader's bounding box (ProjectorLightCore.fxh:251-278), fp32 in the order the shader writes it,
+ * once per light: invertMatrix of the four rows; the four corners lerp(0, region.zw - region.xy, corner) projected at z = 0 and z = 1,
+ * each divided by its w; min / max (minNum / maxNum) over the eight points from 999999 / -999999; the quad's corners lerp(tl, br, 0 / 1);
+ * y padded by -/+ MaximumZ * ZToYMultiplier.  A light whose rectangle comes out NaN or inverted on an axis covers nothing.
+ * Statistics: PixelLightPairs = pairs inside a footprint and the image; TracedPairs = pairs that trace with a bound field (sdf != 0,
+ * Extent.x > 0); SdfSamples = ambient-occlusion + cone-trace samples.
+ * Not built: the light-probe technique (ProjectorLightProbe.fx), ProjectorLightWithoutDistanceField as a technique of its own (sdf == 0
+ * is it), mip chains, the group entry point. */
+int32_t ilm_render_projector_lights(IlmHandle ctx,
+                                    const IlmLightVertex* lights, int32_t light_count,
+                                    const IlmEnvironment* env,
+                                    const IlmDistanceFieldUniforms* df,
+                                    IlmHandle gbuffer, IlmHandle sdf,
+                                    const float ambient[4],
+                                    IlmHandle lightmap, int32_t row_begin, int32_t row_end,
+                                    IlmRenderStats* stats);
 
 /* LightSource.TextureRef / Configuration.DefaultRampTexture of the light group rendered by the FOLLOWING ilm_render_sphere_lights,
  * ilm_render_directional_lights (SampleFromRamp(opacity), channel r at v = 0: DirectionalLightWithRamp) and
