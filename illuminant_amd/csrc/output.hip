@@ -3,7 +3,7 @@
 //     compaction of the live particles into draw-call records (the reference copies three float4 planes per chunk to the host
 //     and filters there: 48 B/slot over PCIe; here 48 B per LIVE particle);
 //   * lightmap resolve: the LightingResolve[WithAlbedo] techniques of Illuminant/Shaders/Resolve.fx:25-233 + HDR.fxh, a pure stream
-//     (8 B read + 4..16 B written per pixel): HBM-bound, no LDS, no MFMA.
+//     (8 B read + 4..16 B written per pixel): no LDS, no MFMA; at 0.6 of HBM's rate it is as close to the VALU's issue limit.
 #include "internal.hpp"
 
 namespace ilm {
@@ -166,14 +166,32 @@ ILM_DEV float4 resolve_texel(const ResolveLaunch& a, float4 color, float4 albedo
         r *= rescale; g *= rescale; b *= rescale;
     } else if (a.mode == ILM_HDR_TONE_MAP) {
         // ToneMappedLightingResolve[WithAlbedo]PixelShader, Resolve.fx:113-139,209-233; Uncharted2Tonemap, HDR.fxh:38-44
-        const float kA = 0.15f, kB = 0.50f, kC = 0.10f, kD = 0.20f, kE = 0.02f, kF = 0.30f;
+        const float kA = 0.15f, kB = 0.50f, kC = 0.10f, kD = 0.20f, kE = 0.02f, kF = 0.30f, kExactBelow = 0.03125f;
         const float e = a.exposure_minus_one + 1.0f, gm = a.gamma_minus_one + 1.0f;
         float v[3] = { fmaxf(0.0f, r + a.offset) * e, fmaxf(0.0f, g + a.offset) * e, fmaxf(0.0f, b + a.offset) * e };
+        // num / den - kE / kF cancels as v goes to 0: at a black pixel the quotient is ONE ulp (2^-27) above kE / kF and the difference is
+        // all rounding, so a dim pixel needs the IEEE quotient: t then equals the shader's bit for bit.  (With num * fast_rcp(den) an ulp
+        // was lost at every seventh dim texel or so: 0.4 % off after pow with Gamma 0.1, 2 - 5 % with 0.45 and 0.8; two ulps low at v = 0
+        // would be pow of a negative number.)  From kExactBelow = 1 / 32 on, t >= 0.0086, and the 1.5 ulp of the fast quotient (1.8e-7 q,
+        // q = 0.0754 there and q / t falling) are at most 1.6e-6 of t, 6.3e-6 after Gamma <= 4.  Which quotient a channel gets depends on
+        // its own value alone (a strip resolves to the bits of the whole frame), but a WAVE without a dim pixel branches round the
+        // division (left to the compiler the select computes both everywhere): a lit frame over an ambient term pays nothing for it.
+        // The kernel is as close to the VALU's limit as to HBM's: eleven more instructions per channel in every wave cost 20 % of its time.
+        float num[3], den[3], q[3];
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const float t = ((v[k] * (kA * v[k] + kC * kB) + kD * kE) * fast_rcp(v[k] * (kA * v[k] + kB) + kD * kF)) - kE / kF;
-            v[k] = pow_pos(t * a.inv_white, gm);
+            num[k] = v[k] * (kA * v[k] + kC * kB) + kD * kE;
+            den[k] = v[k] * (kA * v[k] + kB) + kD * kF;
         }
+#pragma unroll
+        for (int k = 0; k < 3; k++) q[k] = num[k] * fast_rcp(den[k]);
+        if (__any(fminf(fminf(v[0], v[1]), v[2]) < kExactBelow)) {
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+                if (v[k] < kExactBelow) q[k] = num[k] / den[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) v[k] = pow_pos((q[k] - kE / kF) * a.inv_white, gm);
         r = v[0]; g = v[1]; b = v[2];
     } else {
         // LightingResolve[WithAlbedo]PixelShader, Resolve.fx:62-83,141-158

@@ -1054,7 +1054,12 @@ typedef struct IlmHDRConfiguration {
  * ToneMappedLightingResolve, Illuminant/Shaders/Resolve.fx:25-139 + HDR.fxh): dst[row_begin..row_end) = tone-mapped src, alpha 1.
  * src and dst are lightmap handles of the same width (any formats; dst RGBA8 is the back-buffer case).  Heights may differ -- a group
  * member's lightmap (ilm_group_lightmap_member) carries padding rows below the frame, a back buffer does not -- as long as the rows
- * resolved exist in every texture involved. */
+ * resolved exist in every texture involved.
+ * Non-finite results (defined behaviour, both entry points): the shader's arithmetic is kept, so a black pixel is NaN (0 / 0) in the
+ * GammaCompress mode, and inf or NaN texels give what IEEE arithmetic gives.  What the destination then holds: a FLOAT4 destination
+ * the value itself; a HALF4 destination NaN for NaN and infinity for whatever lies beyond the largest half; an RGBA8 destination
+ * byte 0 for NaN (saturate(NaN) = 0, as Direct3D's), 0 for -inf and 255 for +inf.  A finite texel whose square stays finite never resolves
+ * to NaN in the plain and ToneMap modes. */
 int32_t ilm_resolve_lighting(IlmHandle src_lightmap, IlmHandle dst_lightmap, const IlmHDRConfiguration* hdr,
                              int32_t row_begin, int32_t row_end);
 /* RenderedLighting.Resolve WITH albedo (LightingRenderer.ResolveLighting with `albedo != null`, Illuminant/Lighting/LightingRenderer.cs:1537-1580;

@@ -73,8 +73,7 @@ class GpuBackend:
         native = self.native
         h, w = lightmap.shape[:2]
         src = native.Lightmap(self.ctx, w, h, abi.LIGHTMAP_FLOAT4)
-        # seed: a zero-light pass clears to `ambient`; the fixture lightmaps are constant
-        native.render_sphere_lights(self.ctx, None, self.scenes.environment(), abi.DistanceFieldUniforms(), None, None, tuple(lightmap[0, 0]), src)
+        src.upload(lightmap)
         dst = native.Lightmap(self.ctx, w, h, abi.LIGHTMAP_FLOAT4)
         tex = None
         if albedo is not None:
@@ -122,3 +121,290 @@ def check_case(case, backend):
         assert_close(out[2, 5], case["expected"], "resolved texel", rtol=2e-5)
     else:
         raise AssertionError(case["kind"])
+
+
+# ---------------------------------------------------------------------------------------------
+# The resolve at black, dim and non-finite texels, over every format pair and on ragged strips
+# ---------------------------------------------------------------------------------------------
+F = np.float32
+W, H = 37, 29                        # 1073 texels = 537 pairs: three blocks of the kernel, the last one ragged; rows start on both parities
+STRIPS = ((1, 8), (2, 29))           # odd start (1 * 37) and odd count (259): every pair falls back; even start, odd count (999): a single-texel tail
+FORMATS = (abi.LIGHTMAP_FLOAT4, abi.LIGHTMAP_HALF4, abi.LIGHTMAP_RGBA8)
+MODES = (abi.HDR_NONE, abi.HDR_GAMMA_COMPRESS, abi.HDR_TONE_MAP)
+FORMAT_NAME = {abi.LIGHTMAP_FLOAT4: "float4", abi.LIGHTMAP_HALF4: "half4", abi.LIGHTMAP_RGBA8: "rgba8", None: "none"}
+MODE_NAME = {abi.HDR_NONE: "none", abi.HDR_GAMMA_COMPRESS: "gamma_compress", abi.HDR_TONE_MAP: "tone_map"}
+EDGE_GAMMAS = (0.1, 0.45, 0.8, 1.0, 2.2, 4.0)
+EDGE_OFFSETS = (0.0, -0.01)
+_DTYPE = {abi.LIGHTMAP_FLOAT4: np.float32, abi.LIGHTMAP_HALF4: np.float16, abi.LIGHTMAP_RGBA8: np.uint8}
+
+
+def decode(texels, fmt):
+    """What the resolve reads from a texture of format `fmt`, as float32: half -> float is exact, a Color byte is byte / 255 (one
+    float32 division)."""
+    if fmt == abi.LIGHTMAP_RGBA8:
+        return texels.astype(np.float32) / F(255.0)
+    return texels.astype(np.float32)
+
+
+def _max0(x):
+    # HLSL max(0, x) returns the operand that is not NaN (Direct3D's max; fmaxf does the same)
+    return np.fmax(x, F(0.0))
+
+
+def _saturate(x):
+    return np.fmin(np.fmax(x, F(0.0)), F(1.0))
+
+
+def _clamp(v, lo, hi):
+    return min(max(F(v), F(lo)), F(hi))              # MathHelper.Clamp on floats
+
+
+def _pow(x, y):
+    with np.errstate(all="ignore"):
+        return np.power(x.astype(np.float64), np.float64(y)).astype(np.float32)
+
+
+def _uncharted2(v):
+    """Uncharted2Tonemap / Uncharted2Tonemap1, HDR.fxh:24-45, every operation rounded to float32."""
+    kA, kB, kC, kD, kE, kF = F(0.15), F(0.50), F(0.10), F(0.20), F(0.02), F(0.30)
+    return ((v * (kA * v + kC * kB) + kD * kE) / (v * (kA * v + kB) + kD * kF)) - kE / kF
+
+
+def resolve_reference(lightmap, hdr, albedo=None):
+    """A second reading of the resolve in numpy float32, from Resolve.fx (ResolveCommon :28-41, ResolveWithAlbedoCommon :43-63, the six pixel
+    shaders :65-210), HDR.fxh (GammaCompress :11-18, Uncharted2Tonemap :24-45), the clamps of SetGammaCompressionParameters /
+    SetToneMappingParameters (IlluminantMaterials.cs:81-137) and `InverseScaleFactor == 0 -> 1` of the header (include/illuminant_hip.h).
+    One float32 rounding per operation, left to right as the shader writes them; pow goes through float64."""
+    with np.errstate(all="ignore"):
+        light = np.ascontiguousarray(lightmap, np.float32)
+        min_v, max_v = F(1.0) / F(256.0), F(99999.0)
+        inverse_scale = F(hdr.InverseScaleFactor) if hdr.InverseScaleFactor != 0.0 else F(1.0)
+        offset = F(hdr.Offset)
+        exposure = (_clamp(hdr.Exposure, min_v, max_v) - F(1.0)) + F(1.0)            # the uniform is ExposureMinusOne; the shader adds the 1 back
+        gamma = (_clamp(hdr.Gamma, 0.1, 4.0) - F(1.0)) + F(1.0)
+        out = np.empty_like(light)
+        if albedo is None:
+            rgb = light[..., :3] * inverse_scale
+            out[..., 3] = F(1.0)
+        else:
+            a = np.ascontiguousarray(albedo, np.float32)
+            scaled = light * (inverse_scale * F(2.0))
+            t = _saturate(scaled[..., 3:4])
+            rgb = a[..., :3] + (a[..., :3] * scaled[..., :3] - a[..., :3]) * t       # lerp(x, y, s) = x + s * (y - x)
+            out[..., 3] = a[..., 3]
+        if hdr.Mode == abi.HDR_GAMMA_COMPRESS:
+            middle_gray = _clamp(hdr.MiddleGray, 0.0, max_v)
+            average = _clamp(hdr.AverageLuminance, min_v, max_v)
+            maximum = _clamp(hdr.MaximumLuminance, min_v, max_v)
+            maximum_squared = maximum * maximum
+            rgb = _max0(rgb + offset)
+            luminance = (rgb[..., 0:1] * F(0.299) + rgb[..., 1:2] * F(0.587)) + rgb[..., 2:3] * F(0.114)
+            s = (luminance * middle_gray) / average
+            compressed = (s * (F(1.0) + (s / maximum_squared))) / (F(1.0) + s)
+            out[..., :3] = rgb * (compressed / luminance)
+        elif hdr.Mode == abi.HDR_TONE_MAP:
+            white = _uncharted2(_clamp(hdr.WhitePoint, min_v, max_v))
+            out[..., :3] = _pow(_uncharted2(_max0(rgb + offset) * exposure) / white, gamma)
+        else:
+            out[..., :3] = _pow(_max0(rgb + offset) * exposure, gamma)
+        return out
+
+
+def assert_same_where_not_finite(got, want, what):
+    """NaN exactly where `want` has NaN, the same infinity where it has one; returns both with those elements zeroed, ready for
+    assert_close (whose |inf - inf| is NaN)."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), "%s: NaN at %s, the reference has it at %s" % (
+        what, np.argwhere(np.isnan(got))[:6].tolist(), np.argwhere(np.isnan(want))[:6].tolist())
+    inf = np.isinf(want)
+    assert np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], want[inf]), "%s: infinities differ" % what
+    odd = ~np.isfinite(want)
+    return np.where(odd, 0.0, got), np.where(odd, 0.0, want)
+
+
+# ---- contents -----------------------------------------------------------------------------------
+def _rng(seed):
+    return np.random.default_rng(seed)
+
+
+def random_source(fmt):
+    """Independent light values in [0, 3) per texel and channel, in the format's own element type (a Color texture holds [0, 1])."""
+    if fmt == abi.LIGHTMAP_RGBA8:
+        return _rng(11).integers(0, 256, (H, W, 4), dtype=np.uint8)
+    return _rng(12 + fmt).uniform(0.0, 3.0, (H, W, 4)).astype(_DTYPE[fmt])
+
+
+def random_albedo(fmt, height=H):
+    """[0, 1.5) where the format allows; a Color texture holds bytes."""
+    if fmt is None:
+        return None
+    if fmt == abi.LIGHTMAP_RGBA8:
+        return _rng(21).integers(0, 256, (height, W, 4), dtype=np.uint8)
+    return _rng(22 + fmt).uniform(0.0, 1.5, (height, W, 4)).astype(_DTYPE[fmt])
+
+
+def edge_values(fmt, offset=-0.01):
+    """The special light values of one source format: zeros, 25 dim values (log-spaced 1e-7 .. 1e-2: through the subnormal range of a
+    half), the floats next to -offset on both sides, negatives (float only), the neighbours of 1 / 32 (where the kernel's tone curve changes
+    from the IEEE quotient to the fast one), 1, the largest half, +inf, NaN.  A Color texture holds none of the non-finite ones: its
+    dim values are the bytes around offset * 255 and around 255 / 32."""
+    if fmt == abi.LIGHTMAP_RGBA8:
+        return np.array([0, 1, 2, 3, 4, 7, 8, 26, 128, 255], np.uint8)
+    dt = _DTYPE[fmt]
+    edge = dt(-offset)
+    v = [dt(0.0), dt(-0.0)] + list(np.logspace(-7.0, -2.0, 25).astype(dt))
+    v += [np.nextafter(edge, dt(1.0)), edge, np.nextafter(edge, dt(0.0))]
+    if fmt == abi.LIGHTMAP_FLOAT4:
+        v += [dt(-1e-3), dt(-1.0), dt(-65504.0), dt(-np.inf)]
+    v += [np.nextafter(dt(0.03125), dt(0.0)), dt(0.03125), dt(0.05)]        # both sides of the kernel's switch to the fast quotient
+    v += [dt(1.0), dt(65504.0), dt(np.inf), dt(np.nan)]
+    return np.array(v, dt)
+
+
+def edge_source(fmt):
+    """37 x 29 texels cycling through edge_values: even rows carry one value in r, g and b (so black texels are black in every channel,
+    which is what GammaCompress's 0 / 0 needs), odd rows three different ones; alpha (the lerp weight of the with-albedo techniques)
+    cycles with a period of its own."""
+    v = edge_values(fmt)
+    n = len(v)
+    i = np.arange(H * W).reshape(H, W)
+    same = (np.arange(H) % 2 == 0)[:, None]
+    out = np.empty((H, W, 4), v.dtype)
+    out[..., 0] = v[i % n]
+    out[..., 1] = v[np.where(same, i, i + 11) % n]
+    out[..., 2] = v[np.where(same, i, i + 23) % n]
+    if fmt == abi.LIGHTMAP_RGBA8:
+        alpha = np.array([0, 26, 77, 128, 255], np.uint8)
+    else:
+        alpha = np.array([0.0, 0.1, 0.3, 0.5, 1.0, 7.0, np.inf, np.nan], v.dtype)
+    out[..., 3] = alpha[(i // 3) % len(alpha)]
+    return out
+
+
+def edge_albedo(fmt):
+    """A random albedo with every seventh texel black and every eleventh white."""
+    a = random_albedo(fmt).copy()
+    i = np.arange(H * W).reshape(H, W)
+    one = 255 if fmt == abi.LIGHTMAP_RGBA8 else 1.0
+    a[i % 7 == 0, :3] = 0
+    a[i % 11 == 0, :3] = one
+    return a
+
+
+def edge_albedo_format(src_fmt):
+    # the packed path takes a Color albedo; the other sources get a float one (values above 1)
+    return abi.LIGHTMAP_RGBA8 if src_fmt == abi.LIGHTMAP_HALF4 else abi.LIGHTMAP_FLOAT4
+
+
+def matrix_hdr(mode):
+    return hdr_configuration(mode, 0.75, 0.02, 1.3, 0.9, 0.5, 0.8, 3.0, 2.5)
+
+
+def edge_hdr(mode, gamma, offset):
+    return hdr_configuration(mode, 1.0, offset, 1.0, gamma, 0.6, 0.4, 2.0, 4.0)
+
+
+# ---- criteria -----------------------------------------------------------------------------------
+SENTINEL = {abi.LIGHTMAP_FLOAT4: np.float32(7.25), abi.LIGHTMAP_HALF4: np.float16(7.25), abi.LIGHTMAP_RGBA8: np.uint8(0x5A)}
+
+
+def byte_band(want):
+    """The RGBA8 destination's two sets.  `nearest` = rint(saturate(want) * 255) with the reference's NaN read as 0 (the defined
+    behaviour: include/illuminant_hip.h); `exact`: where the whole band want +- (1e-4 |want| + 1e-7) rounds to that one byte, i.e. does
+    not touch a (k + 0.5) / 255 boundary -- there the byte must be equal, elsewhere within 1."""
+    w = np.where(np.isnan(want), 0.0, np.asarray(want, np.float64))
+    tol = np.where(np.isfinite(w), 1e-4 * np.abs(w) + 1e-7, 0.0)
+    lo, hi = np.clip(w - tol, 0.0, 1.0) * 255.0, np.clip(w + tol, 0.0, 1.0) * 255.0
+    nearest = np.rint(np.clip(w, 0.0, 1.0) * 255.0).astype(np.int32)
+    exact = (np.floor(lo + 0.5) == np.floor(hi + 0.5)) & (np.ceil(lo - 0.5) == np.ceil(hi - 0.5))
+    return nearest, exact
+
+
+def check_destination(got, want, dst_fmt, what, exact_share=None):
+    """The criterion of one destination format, `want` being the oracle's float32 frame (rows as in `got`).
+    float4: assert_close defaults, NaN and infinities exactly where the oracle has them.
+    half4: |float(got) - want| <= 1e-4 |want| + half an fp16 ulp (2^-11 |want|, 2^-25 in the subnormal range); NaN stays NaN; a value
+        that rounds past the largest half may be that or infinity.
+    rgba8: within 1 of the nearest byte everywhere, equal on the `exact` set of byte_band; exact_share: the least share of that set."""
+    if dst_fmt == abi.LIGHTMAP_FLOAT4:
+        g, w = assert_same_where_not_finite(got, want, what)
+        assert_close(g, w, what)
+    elif dst_fmt == abi.LIGHTMAP_HALF4:
+        g, w = got.astype(np.float64), np.asarray(want, np.float64)
+        assert np.array_equal(np.isnan(g), np.isnan(w)), "%s: NaN texels differ" % what
+        with np.errstate(invalid="ignore"):
+            tol = 1e-4 * np.abs(w) + np.maximum(2.0 ** -11 * np.abs(w), 2.0 ** -25)
+            over = np.abs(w) + tol >= 65520.0             # the float at and beyond which round-to-nearest-even gives infinity
+            ok = np.isnan(w) | (np.abs(g - w) <= tol) | (over & (np.sign(g) == np.sign(w)) & (np.abs(g) >= 65504.0))
+        assert ok.all(), "%s: %d half texels off, first at %s: got %r want %r" % (
+            what, int((~ok).sum()), np.argwhere(~ok)[0].tolist(), g[tuple(np.argwhere(~ok)[0])], w[tuple(np.argwhere(~ok)[0])])
+    else:
+        nearest, exact = byte_band(want)
+        g = got.astype(np.int32)
+        assert np.abs(g - nearest).max() <= 1, "%s: a byte is more than 1 off at %s" % (what, np.argwhere(np.abs(g - nearest) > 1)[:4].tolist())
+        bad = exact & (g != nearest)
+        assert not bad.any(), "%s: %d bytes differ where the band holds one byte, first at %s: got %d want %d" % (
+            what, int(bad.sum()), np.argwhere(bad)[0].tolist(), g[tuple(np.argwhere(bad)[0])], nearest[tuple(np.argwhere(bad)[0])])
+        if exact_share is not None:
+            assert exact[..., :3].mean() >= exact_share, (what, exact[..., :3].mean())
+
+
+def check_alpha(got, dst_fmt, albedo_texels, albedo_fmt, what):
+    """Alpha is exactly 1 without albedo; a Color albedo's alpha byte reaches a Color destination bit for bit."""
+    if albedo_texels is None:
+        one = 255 if dst_fmt == abi.LIGHTMAP_RGBA8 else 1.0
+        assert (got[..., 3] == one).all(), what + ": alpha is not 1"
+    elif albedo_fmt == abi.LIGHTMAP_RGBA8 and dst_fmt == abi.LIGHTMAP_RGBA8:
+        assert np.array_equal(got[..., 3], albedo_texels[..., 3]), what + ": the albedo's alpha byte did not pass through"
+
+
+# ---- closed forms at the edges of the parameter space (hand-evaluated in double; no backend is asked what it thinks) ------------------
+def _u2(v):
+    return (v * (0.15 * v + 0.10 * 0.50) + 0.20 * 0.02) / (v * (0.15 * v + 0.50) + 0.20 * 0.30) - 0.02 / 0.30
+
+
+# Uncharted2Tonemap(0) in float32: fl(0.2f * 0.02f) / fl(0.2f * 0.3f) is the float above fl(0.02f / 0.3f) = 0x3d888889, whose ulp is 2^-27
+_T_BLACK = 2.0 ** -27
+_NAN = float("nan")
+
+
+def _gc(rgb, mg=0.6, avg=0.4, mx=2.0):
+    lum = 0.299 * rgb[0] + 0.587 * rgb[1] + 0.114 * rgb[2]
+    s = lum * mg / avg
+    k = (s * (1 + s / (mx * mx)) / (1 + s)) / lum
+    return [rgb[0] * k, rgb[1] * k, rgb[2] * k, 1.0]
+
+
+EDGE_CASES = [
+    # a black texel in each mode
+    {"name": "black, none", "texel": [0, 0, 0, 7], "hdr": {"mode": 0, "gamma": 0.45}, "expected": [0.0, 0.0, 0.0, 1.0]},
+    {"name": "black, gamma compress", "texel": [0, 0, 0, 7], "hdr": {"mode": 1, "middle_gray": 0.6, "average_luminance": 0.4, "maximum_luminance": 2.0},
+     "expected": [_NAN, _NAN, _NAN, 1.0]},
+    {"name": "black, tone map", "texel": [0, 0, 0, 7], "hdr": {"mode": 2, "gamma": 0.45, "white_point": 4.0},
+     "expected": [(_T_BLACK / _u2(4.0)) ** 0.45] * 3 + [1.0]},
+    {"name": "black, tone map, gamma floor", "texel": [0, 0, 0, 7], "hdr": {"mode": 2, "gamma": 0.1, "white_point": 4.0},
+     "expected": [(_T_BLACK / _u2(4.0)) ** 0.1] * 3 + [1.0]},
+    # Offset below -texel: the channel is black, the others are not
+    {"name": "offset below -texel, none", "texel": [0.5, 0.25, 1.0, 7], "hdr": {"mode": 0, "offset": -0.625}, "expected": [0.0, 0.0, 0.375, 1.0]},
+    {"name": "offset below -texel, gamma compress", "texel": [0.5, 0.25, 1.0, 7],
+     "hdr": {"mode": 1, "offset": -0.625, "middle_gray": 0.6, "average_luminance": 0.4, "maximum_luminance": 2.0}, "expected": _gc([0.0, 0.0, 0.375])},
+    {"name": "offset below -texel, tone map", "texel": [0.5, 0.25, 1.0, 7], "hdr": {"mode": 2, "offset": -0.625, "gamma": 0.45, "white_point": 4.0},
+     "expected": [(_T_BLACK / _u2(4.0)) ** 0.45] * 2 + [(_u2(0.375) / _u2(4.0)) ** 0.45, 1.0]},
+    # Gamma is clamped to [0.1, 4]
+    {"name": "gamma 0.05 -> 0.1", "texel": [0.5, 0.25, 1.0, 7], "hdr": {"mode": 0, "gamma": 0.05}, "expected": [0.5 ** 0.1, 0.25 ** 0.1, 1.0, 1.0]},
+    {"name": "gamma 9 -> 4", "texel": [0.5, 0.25, 1.0, 7], "hdr": {"mode": 0, "gamma": 9.0}, "expected": [0.5 ** 4, 0.25 ** 4, 1.0, 1.0]},
+    {"name": "gamma 0.05 -> 0.1, tone map", "texel": [0.5, 0.25, 1.0, 7], "hdr": {"mode": 2, "gamma": 0.05, "white_point": 4.0},
+     "expected": [(_u2(v) / _u2(4.0)) ** 0.1 for v in (0.5, 0.25, 1.0)] + [1.0]},
+    {"name": "gamma 9 -> 4, tone map", "texel": [0.5, 0.25, 1.0, 7], "hdr": {"mode": 2, "gamma": 9.0, "white_point": 4.0},
+     "expected": [(_u2(v) / _u2(4.0)) ** 4 for v in (0.5, 0.25, 1.0)] + [1.0]},
+    # Exposure 0 -> 1 / 256, InverseScaleFactor 0 -> 1
+    {"name": "exposure 0 -> 1/256", "texel": [0.5, 0.25, 1.0, 7], "hdr": {"mode": 0, "exposure": 0.0}, "expected": [0.5 / 256, 0.25 / 256, 1.0 / 256, 1.0]},
+    {"name": "inverse scale 0 -> 1", "texel": [0.5, 0.25, 1.0, 7], "hdr": {"mode": 0, "inverse_scale": 0.0}, "expected": [0.5, 0.25, 1.0, 1.0]},
+    {"name": "inverse scale 0 -> 1, with albedo", "texel": [0.5, 0.25, 1.0, 0.25], "albedo": [0.8, 0.4, 0.2, 0.5], "hdr": {"mode": 0, "inverse_scale": 0.0},
+     "expected": [0.8 + (0.8 * 1.0 - 0.8) * 0.5, 0.4 + (0.4 * 0.5 - 0.4) * 0.5, 0.2 + (0.2 * 2.0 - 0.2) * 0.5, 0.5]},
+]
+
+
+def check_edge_case(case, backend):
+    c = dict(case, kind="resolve")
+    check_case(c, backend)

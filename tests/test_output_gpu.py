@@ -1,4 +1,8 @@
-"""Parity of the output-side kernels (ordered read-back compaction, lightmap resolve -- SURVEY 8f-4) against the CPU oracle."""
+"""Parity of the output-side kernels (ordered read-back compaction, lightmap resolve -- SURVEY 8f-4) against the CPU oracle.
+
+The resolve: two lit-frame tests, then (contents and criteria in tests/output_common.py) every source / destination / albedo format and
+mode on a frame of independent random texels, a frame of black, dim, negative and non-finite texels at six gammas, and strips whose
+first texel or texel count is odd -- all on 37 x 29 texels uploaded as they are."""
 import numpy as np
 import pytest
 
@@ -144,3 +148,151 @@ def test_fracture_only_options_are_refused(ctx):
     with pytest.raises(native.IlluminantError):
         native.resolve_lighting(a, b, oc.hdr_configuration(), albedo=small)
     a.close(); b.close(); t.close(); small.close()
+
+
+# ---- the resolve on uploaded 37 x 29 frames: formats, edge texels, ragged strips ------------------------------------------------------
+_ids = lambda names: (lambda v: names[v])
+_WANT = {}
+
+
+def _want(oracle, key, light, hdr, albedo):
+    """The oracle's frame, computed once per content and configuration and shared by the destinations."""
+    if key not in _WANT:
+        _WANT[key] = oracle.resolve_lighting(np.ascontiguousarray(light), hdr, albedo=albedo)
+        _WANT[key].setflags(write=False)
+    return _WANT[key]
+
+
+def _texture(ctx, texels, fmt):
+    t = native.Lightmap(ctx, texels.shape[1], texels.shape[0], fmt)
+    t.upload(texels)
+    return t
+
+
+def _sentinel(fmt, height=oc.H):
+    return np.full((height, oc.W, 4), oc.SENTINEL[fmt])
+
+
+def _resolve_into(dst, src, hdr, tex, row_begin=0, row_end=None):
+    """Resolve rows [row_begin, row_end) into a destination filled with the sentinel; the rows outside must still hold it."""
+    fill = _sentinel(dst.format, dst.height)
+    dst.upload(fill)
+    native.resolve_lighting(src, dst, hdr, row_begin, row_end, albedo=tex)
+    out = dst.download()
+    end = dst.height if row_end is None else row_end
+    assert np.array_equal(out[:row_begin], fill[:row_begin]) and np.array_equal(out[end:], fill[end:]), "rows outside the strip were written"
+    return out
+
+
+@pytest.mark.parametrize("index", range(len(oc.EDGE_CASES)), ids=[c["name"] for c in oc.EDGE_CASES])
+def test_edge_closed_form_case(ctx, index):
+    oc.check_edge_case(oc.EDGE_CASES[index], oc.GpuBackend(ctx))
+
+
+@pytest.mark.parametrize("mode", oc.MODES, ids=_ids(oc.MODE_NAME))
+@pytest.mark.parametrize("albedo_fmt", (None,) + oc.FORMATS, ids=lambda f: "albedo_" + oc.FORMAT_NAME[f])
+@pytest.mark.parametrize("dst_fmt", oc.FORMATS, ids=lambda f: "to_" + oc.FORMAT_NAME[f])
+@pytest.mark.parametrize("src_fmt", oc.FORMATS, ids=_ids(oc.FORMAT_NAME))
+def test_resolve_format_matrix(ctx, oracle, src_fmt, dst_fmt, albedo_fmt, mode):
+    """Every source x destination x albedo format x mode on independent random texels (light in [0, 3), albedo in [0, 1.5) or bytes):
+    the whole frame and the two ragged strips against the oracle on the decoded textures.  Every texel is identifiable, and an RGBA8
+    destination must hold the exact byte on at least 90 % of the colour bytes: swapped pairs or an albedo word off by one cannot pass."""
+    src_t, alb_t = oc.random_source(src_fmt), oc.random_albedo(albedo_fmt)
+    hdr = oc.matrix_hdr(mode)
+    want = _want(oracle, ("matrix", src_fmt, albedo_fmt, mode), oc.decode(src_t, src_fmt), hdr,
+                 oc.decode(alb_t, albedo_fmt) if alb_t is not None else None)
+    what = "%s -> %s, albedo %s, %s" % (oc.FORMAT_NAME[src_fmt], oc.FORMAT_NAME[dst_fmt], oc.FORMAT_NAME[albedo_fmt], oc.MODE_NAME[mode])
+    src, dst = _texture(ctx, src_t, src_fmt), native.Lightmap(ctx, oc.W, oc.H, dst_fmt)
+    tex = _texture(ctx, alb_t, albedo_fmt) if alb_t is not None else None
+    whole = _resolve_into(dst, src, hdr, tex)
+    oc.check_destination(whole, want, dst_fmt, what, exact_share=0.9)
+    oc.check_alpha(whole, dst_fmt, alb_t, albedo_fmt, what)
+    for b, e in oc.STRIPS:
+        part = _resolve_into(dst, src, hdr, tex, b, e)
+        oc.check_destination(part[b:e], want[b:e], dst_fmt, what + " rows [%d, %d)" % (b, e))
+        oc.check_alpha(part[b:e], dst_fmt, alb_t[b:e] if alb_t is not None else None, albedo_fmt, what)
+    for x in (src, dst, tex):
+        if x is not None:
+            x.close()
+
+
+_EDGE_PARAMS = [(m, g) for m in oc.MODES for g in (oc.EDGE_GAMMAS if m != abi.HDR_GAMMA_COMPRESS else (1.0,))]
+
+
+@pytest.mark.parametrize("mode,gamma", _EDGE_PARAMS, ids=["%s-gamma_%g" % (oc.MODE_NAME[m], g) for m, g in _EDGE_PARAMS])
+@pytest.mark.parametrize("src_fmt", oc.FORMATS, ids=_ids(oc.FORMAT_NAME))
+def test_resolve_black_dim_and_non_finite_texels(ctx, oracle, src_fmt, mode, gamma):
+    """Texels cycling through 0, -0, 25 dim values (1e-7 .. 1e-2), the neighbours of -Offset, negatives, 1, 65504, inf and NaN, at Offset 0
+    and -0.01, with and without albedo, into every destination format (GammaCompress does not read Gamma: one case).
+    A tone-mapped black pixel is ((q - kE / kF) / white) ^ gamma with q = num / den one ulp (2^-27) above kE / kF: a quotient one ulp low
+    makes it 0 -- at gamma 0.1 the oracle's 0.164 against 0, and outside the criterion for every v below about 1e-4 at gamma < 1 --, two
+    ulps low NaN.  So the quotient has to be the correctly rounded one; the criterion is the default one and not wider.
+    The float destination is held to it twice: over the frame, whose component scale the 65504 texels set, and over the texels the
+    oracle resolves to at most 2, where the floor is 1e-7 of a scale near 1."""
+    src_t = oc.edge_source(src_fmt)
+    light = oc.decode(src_t, src_fmt)
+    albedo_fmt = oc.edge_albedo_format(src_fmt)
+    alb_t = oc.edge_albedo(albedo_fmt)
+    albedo = oc.decode(alb_t, albedo_fmt)
+    src, tex = _texture(ctx, src_t, src_fmt), _texture(ctx, alb_t, albedo_fmt)
+    dsts = [native.Lightmap(ctx, oc.W, oc.H, f) for f in oc.FORMATS]
+    for offset in oc.EDGE_OFFSETS:
+        hdr = oc.edge_hdr(mode, gamma, offset)
+        for with_albedo in (False, True):
+            want = _want(oracle, ("edge", src_fmt, mode, gamma, offset, with_albedo), light, hdr, albedo if with_albedo else None)
+            finite = np.isfinite(light).all(axis=-1) & (np.isfinite(albedo).all(axis=-1) | (not with_albedo))
+            for dst in dsts:
+                what = "edge texels %s -> %s, %s, gamma %g, offset %g, %s" % (oc.FORMAT_NAME[src_fmt], oc.FORMAT_NAME[dst.format], oc.MODE_NAME[mode],
+                                                                         gamma, offset, "albedo" if with_albedo else "plain")
+                got = _resolve_into(dst, src, hdr, tex if with_albedo else None)
+                if dst.format != abi.LIGHTMAP_RGBA8 and mode != abi.HDR_GAMMA_COMPRESS:
+                    assert not np.isnan(got[finite].astype(np.float32)).any(), what + ": a finite texel resolved to NaN"
+                oc.check_destination(got, want, dst.format, what)
+                if dst.format == abi.LIGHTMAP_FLOAT4:
+                    low = (np.isfinite(want) & (np.abs(want) <= 2.0)).all(axis=-1)
+                    assert low.sum() > 100
+                    assert_close(got[low], want[low], what + " (texels resolving to at most 2)")
+                oc.check_alpha(got, dst.format, alb_t if with_albedo else None, albedo_fmt, what)
+    for x in dsts + [src, tex]:
+        x.close()
+
+
+_STRIP_PARAMS = [(abi.LIGHTMAP_HALF4, abi.LIGHTMAP_RGBA8, abi.LIGHTMAP_RGBA8), (abi.LIGHTMAP_FLOAT4, abi.LIGHTMAP_FLOAT4, abi.LIGHTMAP_FLOAT4)]
+_STRIP_IDS = ["packed_half4_to_rgba8", "float4_to_float4"]
+
+
+@pytest.mark.parametrize("mode", oc.MODES, ids=_ids(oc.MODE_NAME))
+@pytest.mark.parametrize("src_fmt,dst_fmt,albedo_fmt", _STRIP_PARAMS, ids=_STRIP_IDS)
+def test_resolve_ragged_strips_equal_the_whole_frame_bit_for_bit(ctx, src_fmt, dst_fmt, albedo_fmt, mode):
+    """Rows [1, 8): 1 * 37 is odd, so no pair of the strip is aligned and the two-texel path falls back throughout (259 texels, odd).
+    Rows [2, 29): aligned, 999 texels, so the strip ends in a pair with one texel.  Both do the arithmetic of the whole-frame resolve."""
+    src_t, alb_t = oc.random_source(src_fmt), oc.random_albedo(albedo_fmt)
+    src, tex, dst = _texture(ctx, src_t, src_fmt), _texture(ctx, alb_t, albedo_fmt), native.Lightmap(ctx, oc.W, oc.H, dst_fmt)
+    hdr = oc.matrix_hdr(mode)
+    whole = _resolve_into(dst, src, hdr, tex)
+    assert not np.array_equal(whole, _sentinel(dst_fmt))
+    for b, e in oc.STRIPS:
+        part = _resolve_into(dst, src, hdr, tex, b, e)
+        assert part[b:e].tobytes() == whole[b:e].tobytes(), "rows [%d, %d) differ from the whole-frame resolve" % (b, e)
+    for x in (src, tex, dst):
+        x.close()
+
+
+@pytest.mark.parametrize("src_fmt,dst_fmt,albedo_fmt", _STRIP_PARAMS, ids=_STRIP_IDS)
+def test_resolve_textures_of_different_heights(ctx, oracle, src_fmt, dst_fmt, albedo_fmt):
+    """Source 37 x 12, destination 37 x 9, albedo 37 x 10: rows [0, 9) exist in all three and resolve; row_end = 10 is refused and
+    writes nothing."""
+    src_t, alb_t = oc.random_source(src_fmt)[:12], oc.random_albedo(albedo_fmt)[:10]
+    src, tex, dst = _texture(ctx, src_t, src_fmt), _texture(ctx, alb_t, albedo_fmt), native.Lightmap(ctx, oc.W, 9, dst_fmt)
+    hdr = oc.matrix_hdr(abi.HDR_TONE_MAP)
+    got = _resolve_into(dst, src, hdr, tex)
+    want = oracle.resolve_lighting(oc.decode(src_t[:9], src_fmt), hdr, albedo=oc.decode(alb_t[:9], albedo_fmt))
+    oc.check_destination(got, want, dst_fmt, "rows [0, 9) of textures 12 / 9 / 10 rows high", exact_share=0.9)
+    oc.check_alpha(got, dst_fmt, alb_t[:9], albedo_fmt, "rows [0, 9)")
+    dst.upload(_sentinel(dst_fmt, 9))
+    with pytest.raises(native.IlluminantError) as e:
+        native.resolve_lighting(src, dst, hdr, 0, 10, albedo=tex)
+    assert e.value.code == abi.ERR_OUT_OF_RANGE
+    assert np.array_equal(dst.download(), _sentinel(dst_fmt, 9))
+    for x in (src, tex, dst):
+        x.close()
