@@ -3858,6 +3858,51 @@ int32_t ilm_render_directional_lights(IlmHandle hctx, const IlmLightVertex* ligh
     return ILM_OK;
 }
 
+int32_t ilm_render_line_lights(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,
+                               const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf, const float ambient[4],
+                               IlmHandle hlightmap, int32_t row_begin, int32_t row_end, IlmRenderStats* stats) {
+    ILM_TRACE_RANGE("ilm_render_line_lights");
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    if (light_count < 0 || (light_count > 0 && !lights)) return fail(ILM_ERR_INVALID_ARGUMENT, "bad light array");
+    // (no light is refused: degenerate geometry -- radius 0, start == end, a NaN position -- is defined by the arithmetic: opacity 0)
+    LightLaunch a = {};
+    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, false); if (rc != ILM_OK) return rc; }
+    Sdf* f = hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr;
+    GBuffer* g = hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr;
+    if (stats) stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0;
+
+    { const int32_t rc = reserve_light_recs(c, light_count); if (rc != ILM_OK) return rc; }
+    if (light_count > 0) {
+        const void* staged = nullptr; int slot = 0;
+        int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
+        if (rc != ILM_OK) return rc;
+        HIP_TRY(launch_prepare_line_lights(static_cast<const IlmLightVertex*>(staged), light_count, *df, c->d_recs.p, c->main()));
+        rc = staged_small_done(c, slot);
+        if (rc != ILM_OK) return rc;
+    }
+    a.light_count = light_count;
+    for (int i = 0; i < 4; i++) a.ambient[i] = ambient ? ambient[i] : 0.0f;
+    a.accumulate = ambient ? 0 : 1;
+    // (a.ramp stays empty: the reference has no LineLightWithRamp; the ramp binding is neither read nor touched)
+    if (stats) {
+        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
+        a.stats = c->d_stats;
+    }
+    // (ilm_debug_last_light_launch: one workgroup per 16 x 16 tile of the rows, no split, no tile map)
+    c->last_light_blocks = ((a.width + kLightTile - 1) / kLightTile) * ((row_end - row_begin + kLightTile - 1) / kLightTile);
+    c->last_light_split = 1; c->last_light_macro = 0;
+    HIP_TRY(launch_line_lights_prepared(a, c->d_recs.p, c->main()));
+    HIP_TRY(light_pass_queued(c, f, g));
+    if (stats) {
+        unsigned long long host[3] = { 0, 0, 0 };
+        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
+        HIP_TRY(hipStreamSynchronize(c->main()));
+        stats->SdfSamples = host[0]; stats->PixelLightPairs = host[1]; stats->TracedPairs = host[2];
+    }
+    return ILM_OK;
+}
+
 int32_t ilm_render_projector_lights(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,
                                     const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf, const float ambient[4],
                                     IlmHandle hlightmap, int32_t row_begin, int32_t row_end, IlmRenderStats* stats) {

@@ -81,6 +81,26 @@ ILM_DEV int wrap_index_fast(float t, int size) {
 // tolerance -- at 3 instructions instead of OCML powf's ~160.  pow(0, y > 0) = exp2(-inf) = 0 as powf gives; pow(x, 0) = 1.
 ILM_DEV float pow_pos(float x, float y) { return (y == 0.0f) ? 1.0f : __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x)); }
 
+// acos(x) as a DEFINED function: a fixed sequence of fp32 operations, one rounding each (no fma), that the tests restate operation for
+// operation -- Abramowitz & Stegun 4.4.46 on |x|, sqrt(1 - |x|) * P7(|x|) with P7 in Horner form from the highest coefficient down, and
+// pi - r for x < 0.  The line light's solid angle is four of these minus 2 pi (FBPBR.fxh:46-50): it cancels, so a library acos that differs
+// from the host's by an ulp moves the decisions that feed the exact statistics (docs/experiments.md, "Line lights").  Within 2^-21
+// absolute of the real acos on [-1, 1] (tools/acos_defined_error.py: 4.12e-7); |x| > 1 and NaN give NaN through the square root.
+ILM_DEV float acos_defined(float x) {
+#pragma clang fp contract(off)
+    const float a = fabsf(x);
+    float p = -0.0012624911f;
+    p = p * a + 0.0066700901f;
+    p = p * a + -0.0170881256f;
+    p = p * a + 0.0308918810f;
+    p = p * a + -0.0501743046f;
+    p = p * a + 0.0889789874f;
+    p = p * a + -0.2145988016f;
+    p = p * a + 1.5707963050f;
+    const float r = sqrtf(1.0f - a) * p;
+    return (x < 0.0f) ? kPi - r : r;
+}
+
 // sign(d) * m for m >= 0 (HLSL sign() is 0 at 0)
 ILM_DEV float sign_times(float d, float m) { return (d == 0.0f) ? 0.0f * m : copysignf(m, d); }
 

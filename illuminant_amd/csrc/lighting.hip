@@ -1800,6 +1800,308 @@ hipError_t launch_projector_lights_prepared(const LightLaunch& a, const void* re
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Line lights -- technique LineLight, LineLight.fx:7-42 over LineLightCore.fxh:17-120, drawn by RenderLineLightSource
+// (LightingRenderer.cs:1309-1337) as one quad per light whose vertex shader pads the segment's bounds by 9999 (LineLightCore.fxh:142-152):
+// every pixel of the rows is covered, so there is no footprint test.  The frame of the directional pass: one thread per pixel, one wave
+// per 8 x 8 pixels, a wave-uniform loop over the prepared records (scalar loads), the G-buffer texel decoded once, the sum in registers,
+// one store.  New here: the closed-form area-light term (computeLineLightOpacity, FBPBR.fxh:53-101) in the exact forms of hlsl_math.hpp with
+// acos_defined, and a cone trace of three rays in lock-step (lineConeTrace over coneTraceAdvanceEx, ConeTrace.fxh:84-96): three
+// independent sample chains per lane.  No ramp technique, no texture.
+// ---------------------------------------------------------------------------------------------
+constexpr float kLineSelfOcclusionHack = 1.5f;              // LineLightCore.fxh:10 SELF_OCCLUSION_HACK
+constexpr float kLineTraceThreshold = 0.75f / 255.0f;       // LineLightCore.fxh:11 SHADOW_OPACITY_THRESHOLD
+constexpr float kLineMinimumOffset = 0.03f;                 // LineLightCore.fxh:30
+constexpr float kLineIlluminanceWeight = 0.2f;              // FBPBR.fxh:76
+
+struct LineRec {
+    float ax, ay, az, radius;                   // LightPosition1.xyz (start); LightProperties.x
+    float bx, by, bz, radius_sq;                // LightPosition2.xyz (end); radius * radius
+    float dx, dy, dz, ab_dot;                   // delta = end - start; dot(delta, delta), the divisor of closestPointOnLineSegment3
+    float lx, ly, lz, offset;                   // lightLeft = normalize(delta); max(saturate((radius + 1) / |delta|), 0.03)
+    float mx, my, mz, casts;                    // lightCenter = lerp(start, end, 0.5); LightProperties.w
+    float cfg_x, cfg_y, ao_radius, ao_opacity;  // createTraceConfig: maxRadius, radiusGrowthPerPixel; MoreLightProperties.xw
+    float c1[4], c2[4];                         // Color1, Color2
+};
+static_assert(sizeof(LineRec) == kLightRecBytes, "a line record fills the slot of a LightRec (reserve_light_recs)");
+
+// What of computeLineLightOpacity (FBPBR.fxh:60-63), lineConeTrace (LineLightCore.fxh:28-30) and createTraceConfig (ConeTrace.fxh:122-139,
+// lightRamp = LightProperties.xy, cone growth 1) depends on the light alone, with the roundings the per-pixel code would make
+__global__ __launch_bounds__(64) void prepare_line_lights_kernel(const IlmLightVertex* __restrict__ lights, int count, float max_cone_radius,
+                                                                  LineRec* __restrict__ out) {
+    const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (i >= count) return;
+    const IlmLightVertex L = lights[i];
+    LineRec r;
+    const f3 a = mk3(L.LightPosition1.x, L.LightPosition1.y, L.LightPosition1.z), b = mk3(L.LightPosition2.x, L.LightPosition2.y, L.LightPosition2.z);
+    const f3 delta = b - a;
+    const f3 left = norm3(delta);
+    const f3 centre = a + ((b - a) * 0.5f);
+    r.ax = a.x; r.ay = a.y; r.az = a.z; r.bx = b.x; r.by = b.y; r.bz = b.z;
+    r.dx = delta.x; r.dy = delta.y; r.dz = delta.z; r.ab_dot = dot3(delta, delta);
+    r.lx = left.x; r.ly = left.y; r.lz = left.z;
+    r.mx = centre.x; r.my = centre.y; r.mz = centre.z;
+    r.radius = L.LightProperties.x; r.radius_sq = L.LightProperties.x * L.LightProperties.x;
+    r.offset = fmaxf(sat((L.LightProperties.x + 1.0f) / len3(delta)), kLineMinimumOffset);
+    r.casts = L.LightProperties.w;
+    const float max_radius = clampf(L.LightProperties.x, ref::kMinConeRadius, max_cone_radius);
+    r.cfg_x = max_radius;
+    r.cfg_y = max_radius / fmaxf(L.LightProperties.y, 16.0f) * 1.0f;  // getConeGrowthFactor() == 1 (DistanceFieldCommon.fxh:233-236)
+    r.ao_radius = L.MoreLightProperties.x; r.ao_opacity = L.MoreLightProperties.w;
+    r.c1[0] = L.Color1.x; r.c1[1] = L.Color1.y; r.c1[2] = L.Color1.z; r.c1[3] = L.Color1.w;
+    r.c2[0] = L.Color2.x; r.c2[1] = L.Color2.y; r.c2[2] = L.Color2.z; r.c2[3] = L.Color2.w;
+    out[i] = r;
+}
+
+// lineConeTrace's loop (LineLightCore.fxh:41-50): every iteration advances ALL three rays with coneTraceAdvanceEx (ConeTrace.fxh:84-96) --
+// a ray that has reached its end (x = y) keeps sampling there and keeps lowering its own visibility while another ray lives -- then
+// takes one step off the shared budget.  Three independent chains of sample -> step per lane.
+// liveness = stepsRemaining * (la + lb + lc) > 0 with l = saturate(visibility - FULLY_SHADOWED) * saturate((length - position) * 100) is
+// stepsRemaining > 0 && any ray has visibility > FULLY_SHADOWED && length > position: the factors are never negative, the smallest
+// positive ones (ulp(0.075) = 2^-27; ulp(0.5) * 100, since 0.5 <= position < length; a budget's fraction >= ulp(1) once it has run) cannot
+// underflow their product, a sum of non-negative terms is positive iff a term is, and a NaN factor saturates to 0 and fails its compare
+// alike (as in cone_trace_loop).
+// The division is skipped as in cone_trace_loop's general form, for all three rays at once: when for every lane and ray
+// n >= fl(fl(v (1 + 2^-20)) r) with v > FULLY_SHADOWED and r >= 2^-60, n / r > v, so RN(n / r) >= v and min() keeps v -- exactly.  A ray
+// whose visibility has fallen to the threshold or below (it may still be advanced here, unlike there) always divides.
+template <int FMT, bool STATS, bool CHECK_NAN>
+ILM_DEV void line_trace_loop(const f3& start, const f3 (&dir)[3], const float (&data_y)[3], float cfg_z, float cone_growth, float cone_max_radius,
+                             const TraceField& F, float (&data_x)[3], float (&data_z)[3], float& steps_remaining, bool alive, LightStats& st) {
+    const float long_step = F.df.StepAndMisc2.z;
+    while (alive) {
+        float s[3], n[3], local_radius[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const f3 sp = mk3(__builtin_fmaf(dir[i].x, data_x[i], start.x), __builtin_fmaf(dir[i].y, data_x[i], start.y), __builtin_fmaf(dir[i].z, data_x[i], start.z));
+            s[i] = sample_distance_field<FMT, CHECK_NAN>(sp, F.df, F.sdf);
+        }
+        if (STATS) st.samples += 3;
+        bool keeps = true;
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            local_radius[i] = __builtin_elementwise_minimum(__builtin_fmaf(cone_growth, data_x[i], ref::kMinConeRadius), cone_max_radius);
+            n[i] = s[i] + ref::kHackDistanceOffset;
+            keeps = keeps & (n[i] >= (data_z[i] * 1.00000095367431640625f) * local_radius[i]) & (local_radius[i] >= 0x1p-60f) &
+                    (data_z[i] > ref::kFullyShadowedThreshold);
+        }
+        if (__builtin_amdgcn_ballot_w64(!keeps) != 0ull) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const float local_visibility = n[i] / local_radius[i];
+                asm("v_min_f32 %0, %0, %1" : "+v"(data_z[i]) : "v"(local_visibility));      // (minNum without the canonicalising v_max, as cone_trace_loop)
+            }
+        }
+        bool any = false;
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            float step = fabsf(s[i]) * long_step;
+            asm("v_max_f32 %0, %0, %1" : "+v"(step) : "v"(cfg_z));
+            data_x[i] = fminf(data_x[i] + step, data_y[i]);
+            any = any | ((data_z[i] > ref::kFullyShadowedThreshold) & (data_y[i] > data_x[i]));
+        }
+        steps_remaining -= 1.0f;
+        alive = (steps_remaining > 0.0f) & any;
+    }
+}
+
+// One line light on one shaded point: LineLightPixelShader (LineLight.fx:7-42) over LineLightPixelCore (LineLightCore.fxh:70-120).
+// Returns false when the shader discards (fullbright; clip(!visible): distance opacity not > 0, or shaded x <= -9999); otherwise the
+// rgb it adds.  Every operation of the opacity term is an exact form, in the order the HLSL writes it: degenerate geometry (radius 0, a
+// pixel on the segment's axis, start == end, a NaN position) makes norm3(0) = NaN, the NaN reaches the final saturate, sat(NaN) = 0
+// and the pair is discarded before anything is sampled.
+template <int FMT, bool STATS>
+ILM_DEV bool shade_line(const Pixel& P, const LineRec& L, const TraceField& F, bool have_sdf, LightStats& st, float& out_r, float& out_g, float& out_b) {
+    const f3 pos = P.shaded, a = mk3(L.ax, L.ay, L.az), b = mk3(L.bx, L.by, L.bz), ab = mk3(L.dx, L.dy, L.dz);
+    // closestPointOnLineSegment3, DistanceFieldCommon.fxh:151-155
+    const float u = sat(dot3(pos - a, ab) / L.ab_dot);
+    const f3 sphere = a + (ab * u);
+    // computeLineLightOpacity, FBPBR.fxh:53-101
+    const f3 to_sphere = sphere - pos;
+    const f3 forward = norm3(to_sphere);
+    const f3 up = cross3(mk3(L.lx, L.ly, L.lz), forward);
+    const f3 ru = up * L.radius;
+    const f3 v0 = (a + ru) - pos, v1 = (a - ru) - pos, v2 = (b - ru) - pos, v3 = (b + ru) - pos;
+    // rectangleSolidAngle, FBPBR.fxh:33-51
+    const f3 n0 = norm3(cross3(v0, v1)), n1 = norm3(cross3(v1, v2)), n2 = norm3(cross3(v2, v3)), n3 = norm3(cross3(v3, v0));
+    const float g0 = acos_defined(dot3(n0 * -1.0f, n1)), g1 = acos_defined(dot3(n1 * -1.0f, n2));
+    const float g2 = acos_defined(dot3(n2 * -1.0f, n3)), g3 = acos_defined(dot3(n3 * -1.0f, n0));
+    const float solid_angle = (((g0 + g1) + g2) + g3) - (2.0f * kPi);
+    const float facing = (((sat(dot3(norm3(v0), P.normal)) + sat(dot3(norm3(v1), P.normal))) + sat(dot3(norm3(v2), P.normal))) +
+                          sat(dot3(norm3(v3), P.normal))) + sat(dot3(norm3(mk3(L.mx, L.my, L.mz) - pos), P.normal));
+    const float illuminance = (solid_angle * kLineIlluminanceWeight) * facing;
+    // (sphereL = normalize(spherePosition - worldPos) is `forward`: the same operations on the same values)
+    const float illuminance_sphere = (kPi * sat(dot3(forward, P.normal))) * (L.radius_sq / dot3(to_sphere, to_sphere));
+    const float distance_opacity = sat(illuminance + illuminance_sphere);
+    const bool visible = (distance_opacity > 0.0f) && (pos.x > -9999.0f);
+    if (!visible)
+        return false;
+
+    // computeAO, AOCommon.fxh:1-19 (aoRadius scaled by max(0, normal.z), LineLightCore.fxh:98)
+    float ao_opacity = 1.0f;
+    const float ao_radius = L.ao_radius * fmaxf(0.0f, P.normal.z);
+    if ((ao_radius >= 0.5f) && have_sdf) {
+        const float distance = sample_distance_field<FMT>(mk3(pos.x, pos.y, pos.z + P.normal.z * ao_radius), F.df, F.sdf);
+        if (STATS) st.samples++;
+        float r = 1.0f - sat(clampf(distance, 0.0f, ao_radius) / ao_radius);
+        r *= r;
+        r = 1.0f - r;
+        ao_opacity = (1.0f - L.ao_opacity) + (r * L.ao_opacity);
+    }
+    const float pre_trace = distance_opacity * ao_opacity;
+
+    // lineConeTrace, LineLightCore.fxh:17-68
+    float cone_opacity = 1.0f;
+    const float casts = L.casts * (P.enable_shadows ? 1.0f : 0.0f);
+    if ((casts != 0.0f) && (pre_trace >= kLineTraceThreshold)) {
+        if (STATS && have_sdf) st.traced++;
+        const f3 start = pos + (P.normal * kLineSelfOcclusionHack);
+        const float along[3] = { sat(u - L.offset), u, sat(u + L.offset) };
+        f3 dir[3];
+        float data_x[3], data_y[3], data_z[3];
+        bool any_nan = (start.x != start.x) | (start.y != start.y) | (start.z != start.z);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            // coneTraceInitialize, ConeTrace.fxh:37-49
+            const f3 tv = (a + (ab * along[i])) - start;
+            const float trace_length = len3(tv);
+            dir[i] = mk3(tv.x / trace_length, tv.y / trace_length, tv.z / trace_length);
+            data_y[i] = fmaxf(trace_length - L.radius, 1.0f);
+            data_x[i] = ref::kTraceInitialOffsetPx;
+            data_z[i] = 1.0f;
+            any_nan = any_nan | (dir[i].x != dir[i].x) | (dir[i].y != dir[i].y) | (dir[i].z != dir[i].z);
+        }
+        const float cfg_z = fmaxf(1.0f, F.df.Packed1.w);
+        float steps_remaining = F.df.StepAndMisc2.x;
+        // (two VGPRs keep the cone configuration resident across the loop, as in shade_light)
+        float cone_max_radius = L.cfg_x, cone_growth = L.cfg_y;
+        asm volatile("" : "+v"(cone_max_radius), "+v"(cone_growth));
+        // The sampler treats a NaN coordinate as 0, and start + dir * x is NaN for every x exactly when start or dir is.  The three rays
+        // share their start, so the hoist of shade_light (start = dir = 0 on such an axis) would need a start per ray: instead a wave with
+        // such a lane (a target equal to the start: length 0) takes the loop whose sampler tests its coordinates.
+        if (__builtin_amdgcn_ballot_w64(any_nan) != 0ull)
+            line_trace_loop<FMT, STATS, true>(start, dir, data_y, cfg_z, cone_growth, cone_max_radius, F, data_x, data_z, steps_remaining, have_sdf, st);
+        else
+            line_trace_loop<FMT, STATS, false>(start, dir, data_y, cfg_z, cone_growth, cone_max_radius, F, data_x, data_z, steps_remaining, have_sdf, st);
+        // (no stepsRemaining == 0 fix-up here, unlike coneTrace)
+        const float visibility = fminf(((data_z[0] + data_z[1]) + data_z[2]) / 3.0f, steps_remaining / ref::kMaxStepRampWindow);
+        cone_opacity = pow_pos(sat(div_with_rcp(sat(visibility - ref::kFullyShadowedThreshold), kVisibilityRange, kVisibilityRangeRcp)), F.df.ConeAndMisc.z);
+    }
+    const float opacity = pre_trace * cone_opacity;
+    // color = lerp(startColor, endColor, u); result = (color.rgb * color.a * opacity, 1), LineLight.fx:40-41
+    const float ca = lerp(L.c1[3], L.c2[3], u);
+    out_r = (lerp(L.c1[0], L.c2[0], u) * ca) * opacity;
+    out_g = (lerp(L.c1[1], L.c2[1], u) * ca) * opacity;
+    out_b = (lerp(L.c1[2], L.c2[2], u) * ca) * opacity;
+    return true;
+}
+
+// The frame of directional_lights_kernel with its base value / blend / store / mirror / statistics tail as a COPY, to be kept in step
+// with it (and with projector_lights_kernel's): the shared form was built twice and moved the existing kernels' instruction streams
+// (see the comments at sample_from_ramp and projector_lights_kernel), and the existing passes are held not to move.  No footprint: the
+// vertex shader's quad, min(P) - 9999 .. max(P) + 9999, is defined here as every pixel of the rows.
+template <int FMT, bool STATS>
+__global__ __launch_bounds__(kLightThreads) void line_lights_kernel(const LightLaunch a, const LineRec* __restrict__ recs, int tiles_x) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int tile_x = (int)blockIdx.x % tiles_x, tile_y = (int)blockIdx.x / tiles_x;
+    const int px = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
+    const int py = a.row_begin + tile_y * kTile + (wave >> 1) * 8 + (lane >> 3);
+    const bool in_image = (px < a.width) && (py < a.row_end);
+    if (__builtin_amdgcn_ballot_w64(in_image) == 0ull)
+        return;
+    Pixel P = sample_gbuffer((float)px, (float)py, a.env, a.gbuffer);
+    P.origin_x = 0; P.origin_y = 0; P.start_inside = false;
+    const bool have_sdf = (a.sdf.texels != nullptr) && (a.df.Extent.x > 0.0f);
+    const InsideConsts no_table = {};
+    const TraceField field = { a.df, a.sdf, no_table, nullptr };
+    const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
+    auto through_half = [](float v) { return __half2float(__float2half_rn(v)); };
+    auto base_value = [&]() -> float4 {
+        float4 v = mk4(a.ambient[0], a.ambient[1], a.ambient[2], a.ambient[3]);
+        if (a.accumulate != 0 && in_image) {
+            if (a.format == ILM_LIGHTMAP_FLOAT4) v = load_target<ILM_LIGHTMAP_FLOAT4>(a.lightmap, o);
+            else if (a.format == ILM_LIGHTMAP_HALF4) v = load_target<ILM_LIGHTMAP_HALF4>(a.lightmap, o);
+            else v = load_target<ILM_LIGHTMAP_RGBA8>(a.lightmap, o);
+        }
+        if (a.blend_fp16 != 0) v = mk4(through_half(v.x), through_half(v.y), through_half(v.z), through_half(v.w));
+        return v;
+    };
+    const bool blend_fp16 = a.blend_fp16 != 0;
+    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if (blend_fp16) { const float4 v = base_value(); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
+    LightStats st;
+    const int light_count = a.light_count;
+    // (a fullbright pixel is discarded before anything of a light is read, LineLight.fx:25-29: it forms no pair)
+    const bool shades = in_image && !P.fullbright;
+    for (int k = 0; k < light_count; k++) {
+        const LineRec& L = recs[k];
+        if (!shades)
+            continue;
+        if (STATS) st.pairs++;
+        float cr, cg, cb;
+        if (!shade_line<FMT, STATS>(P, L, field, have_sdf, st, cr, cg, cb))
+            continue;
+        if (blend_fp16) {
+            acc_r = through_half(acc_r + through_half(cr));
+            acc_g = through_half(acc_g + through_half(cg));
+            acc_b = through_half(acc_b + through_half(cb));
+            acc_a = through_half(acc_a + 1.0f);
+        } else {
+            acc_r += cr; acc_g += cg; acc_b += cb; acc_a += 1.0f;
+        }
+    }
+    if (!blend_fp16) {
+        const float4 v = base_value();
+        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+    }
+    if (in_image) {
+        const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
+        auto store_texel = [&](void* base) {
+            if (a.format == ILM_LIGHTMAP_FLOAT4) store_target<ILM_LIGHTMAP_FLOAT4>(base, o, v);
+            else if (a.format == ILM_LIGHTMAP_HALF4) store_target<ILM_LIGHTMAP_HALF4>(base, o, v);
+            else store_target<ILM_LIGHTMAP_RGBA8>(base, o, v);
+        };
+        store_texel(a.lightmap);
+        for (int m = 0; m < a.mirror_count; m++) store_texel(a.mirrors[m]);      // store-mode exchange of a group lightmap, as the sphere pass
+    }
+    if (STATS) {
+        for (int off = 32; off > 0; off >>= 1) {
+            st.samples += __shfl_down(st.samples, off);
+            st.pairs += __shfl_down(st.pairs, off);
+            st.traced += __shfl_down(st.traced, off);
+        }
+        if (lane == 0) {
+            atomicAdd(&a.stats[0], st.samples);
+            atomicAdd(&a.stats[1], st.pairs);
+            atomicAdd(&a.stats[2], st.traced);
+        }
+    }
+}
+
+hipError_t launch_prepare_line_lights(const IlmLightVertex* lights, int count, const IlmDistanceFieldUniforms& df, void* recs, hipStream_t stream) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(prepare_line_lights_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, lights, count, df.ConeAndMisc.x,
+                       reinterpret_cast<LineRec*>(recs));
+    return hipGetLastError();
+}
+
+hipError_t launch_line_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
+    const int rows = a.row_end - a.row_begin;
+    if (rows <= 0 || a.width <= 0) return hipSuccess;
+    if (a.light_count == 0 && a.accumulate != 0) return hipSuccess;      // nothing to add: no texel (and no mirror) would change
+    const int tiles_x = (a.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
+    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y), block(kLightThreads);
+    const LineRec* r = reinterpret_cast<const LineRec*>(recs);
+    const bool stats = a.stats != nullptr;
+    if (a.sdf.format == ILM_SDF_FP16) {
+        if (stats) hipLaunchKernelGGL((line_lights_kernel<ILM_SDF_FP16, true>), grid, block, 0, stream, a, r, tiles_x);
+        else hipLaunchKernelGGL((line_lights_kernel<ILM_SDF_FP16, false>), grid, block, 0, stream, a, r, tiles_x);
+    } else {
+        if (stats) hipLaunchKernelGGL((line_lights_kernel<ILM_SDF_UNORM16, true>), grid, block, 0, stream, a, r, tiles_x);
+        else hipLaunchKernelGGL((line_lights_kernel<ILM_SDF_UNORM16, false>), grid, block, 0, stream, a, r, tiles_x);
+    }
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void divide_probe_kernel(const float* __restrict__ n, const float* __restrict__ d, int count,
                                                             float* __restrict__ out_fast, float* __restrict__ out_ieee) {
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;

@@ -435,6 +435,24 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("TextureRef", &DirectionalLightSource::TextureRef)
         .def_readwrite("Quality", &DirectionalLightSource::Quality);
     // Transform: 16 floats, row-major (M11 .. M44); Rotation: (X, Y, Z, W); Origin / Depth: None or a value; TextureRegion: (x1, y1, x2, y2)
+    py::class_<LineLightSource>(m, "LineLightSource").def(py::init<>())
+        .def_readwrite("SortKey", &LineLightSource::SortKey).def_readwrite("Enabled", &LineLightSource::Enabled)
+        VEC_PROP(LineLightSource, StartPosition, 3)
+        VEC_PROP(LineLightSource, EndPosition, 3)
+        .def_readwrite("Radius", &LineLightSource::Radius)
+        .def_property("RampMode", [](const LineLightSource& l) { return (int)l.RampMode; }, [](LineLightSource& l, int v) { l.RampMode = (LightSourceRampMode)v; })
+        VEC_PROP(LineLightSource, StartColor, 4)
+        VEC_PROP(LineLightSource, EndColor, 4)
+        .def("SetColor", [](LineLightSource& l, const std::vector<float>& v) { l.SetColor(v4(v)); })
+        .def_readwrite("Opacity", &LineLightSource::Opacity)
+        .def_readwrite("CastsShadows", &LineLightSource::CastsShadows)
+        .def_readwrite("AmbientOcclusionRadius", &LineLightSource::AmbientOcclusionRadius)
+        .def_readwrite("AmbientOcclusionOpacity", &LineLightSource::AmbientOcclusionOpacity)
+        .def_readwrite("ShadowDistanceFalloff", &LineLightSource::ShadowDistanceFalloff)
+        .def_readwrite("FalloffYFactor", &LineLightSource::FalloffYFactor)
+        .def_readwrite("TextureRef", &LineLightSource::TextureRef)
+        .def_readwrite("Quality", &LineLightSource::Quality)
+        .def_readwrite("RampOffset", &LineLightSource::RampOffset).def_readwrite("RampRate", &LineLightSource::RampRate);
     py::class_<ProjectorLightSource>(m, "ProjectorLightSource").def(py::init<>())
         .def_readwrite("SortKey", &ProjectorLightSource::SortKey).def_readwrite("Enabled", &ProjectorLightSource::Enabled)
         .def_property("Transform", [](const ProjectorLightSource& l) { return std::vector<float>(&l.Transform.M[0][0], &l.Transform.M[0][0] + 16); },
@@ -516,6 +534,7 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("Replicators", &LightingEnvironment::Replicators)
         .def_readwrite("DirectionalLights", &LightingEnvironment::DirectionalLights)
         .def_readwrite("ProjectorLights", &LightingEnvironment::ProjectorLights)
+        .def_readwrite("LineLights", &LightingEnvironment::LineLights)
         .def_readwrite("ParticleLights", &LightingEnvironment::ParticleLights)
         .def_property_readonly("Obstructions", [](LightingEnvironment& e) -> LightObstructionCollection& { return e.Obstructions; }, py::return_value_policy::reference_internal)
         .def_readwrite("HeightVolumes", &LightingEnvironment::HeightVolumes)
@@ -711,6 +730,11 @@ PYBIND11_MODULE(_host, m) {
         .def_static("PackDirectionalLightBytes", [](const DirectionalLightSource& l, float intensityScale) -> py::object {
             IlmLightVertex v;
             if (!LightingRenderer::PackDirectionalLight(l, intensityScale, v)) return py::none();
+            return py::bytes((const char*)&v, sizeof(v));
+        })
+        .def_static("PackLineLightBytes", [](const LineLightSource& l, float intensityScale, bool haveDF) -> py::object {
+            IlmLightVertex v;
+            if (!LightingRenderer::PackLineLight(l, intensityScale, haveDF, v)) return py::none();
             return py::bytes((const char*)&v, sizeof(v));
         })
         .def_static("PackProjectorLightBytes", [](const ProjectorLightSource& l, float intensityScale, bool haveDF, float maximumZ, std::vector<float> renderScale,

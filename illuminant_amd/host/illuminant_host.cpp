@@ -1299,6 +1299,22 @@ bool LightingRenderer::PackDirectionalLight(const DirectionalLightSource& l, flo
     return true;
 }
 
+// RenderLineLightSource, LightingRenderer.cs:1309-1337
+bool LightingRenderer::PackLineLight(const LineLightSource& l, float intensityScale, bool haveDistanceField, IlmLightVertex& v) {
+    if (l.Opacity <= 0.0f)
+        return false;
+    std::memset(&v, 0, sizeof(v));
+    v.LightPosition1 = { l.StartPosition.X, l.StartPosition.Y, l.StartPosition.Z, 0 };
+    v.LightPosition2 = { l.EndPosition.X, l.EndPosition.Y, l.EndPosition.Z, 0 };
+    v.LightPosition3 = { 0, 0, 0, 0 };
+    v.Color1 = { l.StartColor.X, l.StartColor.Y, l.StartColor.Z, l.StartColor.W * (l.Opacity * intensityScale) };
+    v.Color2 = { l.EndColor.X, l.EndColor.Y, l.EndColor.Z, l.EndColor.W * (l.Opacity * intensityScale) };
+    v.LightProperties = { l.Radius, 0, (float)(int)l.RampMode, (l.CastsShadows && haveDistanceField) ? 1.0f : 0.0f };
+    v.MoreLightProperties = { l.AmbientOcclusionRadius, l.ShadowDistanceFalloff.value_or(-99999.0f), l.FalloffYFactor, l.AmbientOcclusionOpacity };
+    v.EvenMoreLightProperties = { 0, 0, (float)-3.14159265358979323846 + l.RampOffset, (float)(1.0 / (3.14159265358979323846 * 2) * l.RampRate) };
+    return true;
+}
+
 Matrix Matrix::CreateScale(float x, float y, float z) { Matrix m; m.M[0][0] = x; m.M[1][1] = y; m.M[2][2] = z; return m; }
 Matrix Matrix::CreateTranslation(Vector3 t) { Matrix m; m.M[3][0] = t.X; m.M[3][1] = t.Y; m.M[3][2] = t.Z; return m; }
 Matrix Matrix::CreateFromQuaternion(Vector4 q) {
@@ -1412,7 +1428,7 @@ IlmEnvironment LightingRenderer::GetEnvironmentUniforms() const {
     return e;
 }
 
-// RenderLighting, LightingRenderer.cs:917-1191 (sphere, directional, projector and particle lights)
+// RenderLighting, LightingRenderer.cs:917-1191 (sphere, directional, line, projector and particle lights)
 void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int rowEnd, IlmRenderStats* stats) {
     if (rowEnd < 0) rowEnd = Configuration.RenderHeight;
     // the probe techniques of directional lights (DirectionalLightProbe*) are not built: refuse rather than leave them out of the probes
@@ -1423,23 +1439,29 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     if (Probes.Count() > 0)
         for (const ProjectorLightSource& pl : Environment->ProjectorLights)
             if (pl.Enabled) throw InvalidOperationException("RenderLighting: projector lights do not reach light probes yet");
+    // nor is the line lights' (LineLightProbe.fx)
+    if (Probes.Count() > 0)
+        for (const LineLightSource& ll : Environment->LineLights)
+            if (ll.Enabled) throw InvalidOperationException("RenderLighting: line lights do not reach light probes yet");
     vertices.clear();
     // LightSorter (:2066-2096): SortKey first; blend mode, ramp texture and type are the same for every light of this pass.  The
     // reference's sort is not stable for equal keys; a stable one keeps list order, which is one of its possible outcomes
     // (Lights before Replicators here, since the mirror holds them in two lists).
     // Directional lights sort after spheres of equal key (TypeID 2 after 1, :2094): listed last, the stable sort keeps them there.
-    // Projector lights likewise, after the directional ones.
+    // Line lights (TypeID 4) likewise, after the directional ones, and projector lights (TypeID 5) after those.
     struct Entry { int sortKey; const SphereLightSource* sphere; const LightSourceReplicator* replicator; const DirectionalLightSource* directional;
-                   const ProjectorLightSource* projector; };
+                   const ProjectorLightSource* projector; const LineLightSource* line; };
     std::vector<Entry> sorted;
     for (const SphereLightSource& l : Environment->Lights)
-        if (l.Enabled) sorted.push_back({ l.SortKey, &l, nullptr, nullptr, nullptr });
+        if (l.Enabled) sorted.push_back({ l.SortKey, &l, nullptr, nullptr, nullptr, nullptr });
     for (const LightSourceReplicator& r : Environment->Replicators)
-        if (r.Enabled) sorted.push_back({ r.SortKey, nullptr, &r, nullptr, nullptr });
+        if (r.Enabled) sorted.push_back({ r.SortKey, nullptr, &r, nullptr, nullptr, nullptr });
     for (const DirectionalLightSource& d : Environment->DirectionalLights)
-        if (d.Enabled) sorted.push_back({ d.SortKey, nullptr, nullptr, &d, nullptr });
+        if (d.Enabled) sorted.push_back({ d.SortKey, nullptr, nullptr, &d, nullptr, nullptr });
+    for (const LineLightSource& ll : Environment->LineLights)
+        if (ll.Enabled) sorted.push_back({ ll.SortKey, nullptr, nullptr, nullptr, nullptr, &ll });
     for (const ProjectorLightSource& pl : Environment->ProjectorLights)
-        if (pl.Enabled) sorted.push_back({ pl.SortKey, nullptr, nullptr, nullptr, &pl });
+        if (pl.Enabled) sorted.push_back({ pl.SortKey, nullptr, nullptr, nullptr, &pl, nullptr });
     std::stable_sort(sorted.begin(), sorted.end(), [](const Entry& x, const Entry& y) { return x.sortKey < y.sortKey; });
     // GetLightRenderState (:799-845): lights that share a ramp texture and quality settings form one render state (BlendState is
     // additive for every light here); the states are drawn one after the other onto the same target, in the order their keys first appear.
@@ -1463,6 +1485,10 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     directionalKeys.clear();
     directionalQuality.clear();
     directionalGroups.clear();
+    // line lights: render states of their own under the same key (the technique reads no ramp)
+    lineKeys.clear();
+    lineQuality.clear();
+    lineGroups.clear();
     // projector lights: one render state per texture (and quality) -- the key's RampTexture member is the projected texture (:1389)
     projectorKeys.clear();
     projectorQuality.clear();
@@ -1479,6 +1505,13 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
             while (g < projectorKeys.size() && !(projectorKeys[g] == texture && projectorQuality[g] == quality)) g++;
             if (g == projectorKeys.size()) { projectorKeys.push_back(texture); projectorQuality.push_back(quality); projectorGroups.emplace_back(); }
             projectorGroups[g].push_back(v);
+            vertices.push_back(v);
+            continue;
+        }
+        if (e.line) {
+            if (!PackLineLight(*e.line, intensityScale, Field != nullptr, v))
+                continue;
+            lineGroups[stateFor(e.line->TextureRef, e.line->Quality.get(), lineKeys, lineQuality, lineGroups)].push_back(v);
             vertices.push_back(v);
             continue;
         }
@@ -1524,7 +1557,7 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     // clear colour: Ambient * intensityScale (:1013-1024)
     const float ambient[4] = { Environment->Ambient.X * intensityScale, Environment->Ambient.Y * intensityScale,
                                Environment->Ambient.Z * intensityScale, Environment->Ambient.W * intensityScale };
-    // no lights: the clear still happens (with directional lights alone, their first launch carries it; projector groups always add)
+    // no lights: the clear still happens (with directional lights alone, their first launch carries it; line and projector groups always add)
     if (groups.empty() && directionalGroups.empty()) { groupKeys.push_back(nullptr); groupQuality.push_back(nullptr); groups.emplace_back(); }
     if (stats) { stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0; }
     for (size_t g = 0; g < groups.size(); g++) {
@@ -1544,6 +1577,14 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
         ThrowIfFailed(ilm_render_directional_lights(Context.Handle(), directionalGroups[g].data(), (int32_t)directionalGroups[g].size(), &env, &gdfu, gbuffer,
                                                     Field ? Field->Texture() : 0, (groups.empty() && g == 0) ? ambient : nullptr, lightmap, rowBegin, rowEnd,
                                                     stats ? &gs : nullptr));
+        if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
+    }
+    // the line render states: no ramp technique, the ramp binding is neither read nor changed
+    for (size_t g = 0; g < lineGroups.size(); g++) {
+        IlmRenderStats gs{};
+        const IlmDistanceFieldUniforms gdfu = lineQuality[g] ? GetDistanceFieldUniforms(*lineQuality[g]) : dfu;
+        ThrowIfFailed(ilm_render_line_lights(Context.Handle(), lineGroups[g].data(), (int32_t)lineGroups[g].size(), &env, &gdfu, gbuffer,
+                                             Field ? Field->Texture() : 0, nullptr, lightmap, rowBegin, rowEnd, stats ? &gs : nullptr));
         if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
     }
     // the projector render states: the group's texture, then one call; the ramp binding is not theirs

@@ -736,6 +736,26 @@ private:
     std::optional<Vector3> direction;
 };
 
+// LineLightSource, LightSource.cs:313-370 (+ the LightSource / LightSourceBase members RenderLineLightSource reads,
+// LightingRenderer.cs:1309-1337)
+struct LineLightSource {
+    int SortKey = 0;
+    bool Enabled = true;
+    Vector3 StartPosition, EndPosition;
+    float Radius = 0;                             // the reference's default (:325): such a light lights nothing (ilm_render_line_lights)
+    LightSourceRampMode RampMode = LightSourceRampMode::Linear;
+    Vector4 StartColor{1, 1, 1, 1}, EndColor{1, 1, 1, 1};
+    void SetColor(Vector4 value) { StartColor = EndColor = value; }      // the Color setter, :338-342
+    float Opacity = 1;
+    bool CastsShadows = true;
+    float AmbientOcclusionRadius = 0, AmbientOcclusionOpacity = 1;
+    std::optional<float> ShadowDistanceFalloff;
+    float FalloffYFactor = 1;
+    std::shared_ptr<RampTexture> TextureRef;      // part of the render state's key; the technique has no ramp
+    std::shared_ptr<RendererQualitySettings> Quality;
+    float RampOffset = 0, RampRate = 1;           // RampOffsetAndRate, LightSource.cs:90 (packed, not read by the shader)
+};
+
 // Matrix / Quaternion (XNA: row vectors, M[r][c] = M(r+1)(c+1)) with the operations RenderProjectorLightSource uses, each in fp32 with
 // one rounding per operation in the order the XNA / MonoGame sources write them
 struct Matrix {
@@ -873,6 +893,7 @@ struct LightingEnvironment {
     std::vector<LightSourceReplicator> Replicators;    // LightSourceReplicator entries of Lights in the reference
     std::vector<DirectionalLightSource> DirectionalLights;   // DirectionalLightSource entries of Lights in the reference
     std::vector<ProjectorLightSource> ProjectorLights;       // ProjectorLightSource entries of Lights in the reference
+    std::vector<LineLightSource> LineLights;                 // LineLightSource entries of Lights in the reference
     std::vector<ParticleLightSource> ParticleLights;   // ParticleLightSource entries of Lights in the reference (one render state each)
     LightObstructionCollection Obstructions;
     std::vector<HeightVolume> HeightVolumes;
@@ -955,8 +976,8 @@ public:
     IlmHandle GBuffer() const { return gbuffer; }
 
     // RenderLighting, :917-1191: clears to Ambient * intensityScale and adds every sphere light, then every directional light, then
-    // every projector light (grouped by texture), then the particle lights.  Directional and projector lights do not reach light
-    // probes yet: with probes and an enabled light of either type it throws.
+    // every line light, then every projector light (grouped by texture), then the particle lights.  Directional, line and projector
+    // lights do not reach light probes yet: with probes and an enabled light of any of these types it throws.
     // [rowBegin, rowEnd) restricts the pass to a screen strip (multi-GPU split); rowEnd < 0 => whole frame.
     void RenderLighting(float intensityScale = 1.0f, int rowBegin = 0, int rowEnd = -1, IlmRenderStats* stats = nullptr);
     void ReadLightmap(void* dst, int firstRow, int rowCount) const;
@@ -990,6 +1011,8 @@ public:
     static bool PackSphereLight(const SphereLightSource& l, float intensityScale, bool haveDistanceField, IlmLightVertex& v);
     // RenderDirectionalLightSource, :1256-1293: false for Opacity <= 0 (:1258); CastsShadows is packed without the field test (:1279)
     static bool PackDirectionalLight(const DirectionalLightSource& l, float intensityScale, IlmLightVertex& v);
+    // RenderLineLightSource, :1309-1337: false for Opacity <= 0 (:1311)
+    static bool PackLineLight(const LineLightSource& l, float intensityScale, bool haveDistanceField, IlmLightVertex& v);
     // RenderProjectorLightSource, :1386-1446: false for a light without a texture (:1389-1391).  maximumZ: Environment.MaximumZ, the
     // depth of a light that sets none; renderScale / mipBias: Configuration.RenderScale / ProjectorMipBias
     static bool PackProjectorLight(const ProjectorLightSource& l, float intensityScale, bool haveDistanceField, float maximumZ, Vector2 renderScale,
@@ -1017,7 +1040,11 @@ private:
     std::vector<const RampTexture*> directionalKeys;
     std::vector<const RendererQualitySettings*> directionalQuality;
     std::vector<std::vector<IlmLightVertex>> directionalGroups;
-    // the projector groups, drawn after the directional ones: one per (texture, quality), the texture bound per group
+    // the line groups, drawn after the directional ones (LightSourceTypeID.Line = 4 sorts between Directional = 2 and Projector = 5)
+    std::vector<const RampTexture*> lineKeys;
+    std::vector<const RendererQualitySettings*> lineQuality;
+    std::vector<std::vector<IlmLightVertex>> lineGroups;
+    // the projector groups, drawn after the line ones: one per (texture, quality), the texture bound per group
     std::vector<const RampTexture*> projectorKeys;
     std::vector<const RendererQualitySettings*> projectorQuality;
     std::vector<std::vector<IlmLightVertex>> projectorGroups;

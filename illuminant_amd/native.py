@@ -101,6 +101,7 @@ SYMBOLS = {
     "ilm_lightmap_destroy": (_I, [_H]),
     "ilm_render_sphere_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
     "ilm_render_directional_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
+    "ilm_render_line_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
     "ilm_render_projector_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
     "ilm_render_particle_lights": (_I, [_H, _H, _P, _I, _P, _P, _P, _H, _H, _H, _I, _I, _P]),
     "ilm_render_light_probes": (_I, [_H, _P, _I, _P, _P, _I, _P, _P, _H, _P]),
@@ -880,6 +881,22 @@ def render_directional_lights(ctx, lights, env, df, gbuffer, sdf, ambient, light
     amb = (C.c_float * 4)(*[float(x) for x in ambient]) if ambient is not None else None
     stats = abi.RenderStats() if want_stats else None
     check(lib().ilm_render_directional_lights(
+        ctx.handle, C.cast(lights, C.c_void_p) if n else None, n, _byref(env), _byref(df),
+        gbuffer.handle if gbuffer is not None else abi.Handle(0),
+        sdf.handle if sdf is not None else abi.Handle(0),
+        C.cast(amb, C.c_void_p) if amb is not None else None, lightmap.handle, row_begin, row_end, _byref(stats)))
+    return stats
+
+
+def render_line_lights(ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin=0, row_end=None, want_stats=False):
+    """ilm_render_line_lights.  lights: ctypes array of abi.LightVertex packed as RenderLineLightSource packs them (or None for zero
+    lights); ambient None = add this light group to what the lightmap already holds."""
+    if row_end is None:
+        row_end = lightmap.height
+    n = len(lights) if lights is not None else 0
+    amb = (C.c_float * 4)(*[float(x) for x in ambient]) if ambient is not None else None
+    stats = abi.RenderStats() if want_stats else None
+    check(lib().ilm_render_line_lights(
         ctx.handle, C.cast(lights, C.c_void_p) if n else None, n, _byref(env), _byref(df),
         gbuffer.handle if gbuffer is not None else abi.Handle(0),
         sdf.handle if sdf is not None else abi.Handle(0),

@@ -805,6 +805,25 @@ def directional_light(direction=None, bounds=None, color=(1, 1, 1, 1), opacity=1
     return v
 
 
+def line_light(start, end, radius, start_color=(1, 1, 1, 1), end_color=None, opacity=1.0, intensity_scale=1.0, ramp_mode=0,
+               casts_shadows=True, have_distance_field=True, ao_radius=0.0, ao_opacity=1.0, falloff_y=1.0, shadow_distance_falloff=None,
+               ramp_length=0.0):
+    """RenderLineLightSource, LightingRenderer.cs:1309-1337, from the LineLightSource's members.  ramp_length is what the host writes
+    into LightProperties.y -- 0 in the reference (:1324); the shader reads it."""
+    end_color = start_color if end_color is None else end_color
+    scale = np.float32(opacity) * np.float32(intensity_scale)
+    v = abi.LightVertex()
+    v.LightPosition1 = abi.f4(start[0], start[1], start[2], 0)
+    v.LightPosition2 = abi.f4(end[0], end[1], end[2], 0)
+    v.LightPosition3 = abi.f4(0, 0, 0, 0)
+    v.Color1 = abi.f4(start_color[0], start_color[1], start_color[2], np.float32(start_color[3]) * scale)
+    v.Color2 = abi.f4(end_color[0], end_color[1], end_color[2], np.float32(end_color[3]) * scale)
+    v.LightProperties = abi.f4(radius, ramp_length, float(ramp_mode), 1.0 if (casts_shadows and have_distance_field) else 0.0)
+    v.MoreLightProperties = abi.f4(ao_radius, -99999.0 if shadow_distance_falloff is None else shadow_distance_falloff, falloff_y, ao_opacity)
+    v.EvenMoreLightProperties = abi.f4(0, 0, np.float32(-np.pi), np.float32(1.0 / (np.pi * 2)))
+    return v
+
+
 def projector_light(forward, region=(0.0, 0.0, 1.0, 1.0), origin=None, radius=4.0, ramp_length=32.0, ramp_mode=0, casts_shadows=True,
                     have_distance_field=True, ao_radius=0.0, ao_opacity=1.0, opacity=1.0, intensity_scale=1.0, wrap=False, mip_bias=0.0):
     """RenderProjectorLightSource's vertex, LightingRenderer.cs:1422-1442, from the FORWARD matrix (texture space -> world, row vectors:

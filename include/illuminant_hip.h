@@ -33,7 +33,8 @@ extern "C" {
 /* 11: + ilm_engine_step_batch, ilm_debug_last_step_batch, ILM_STEP_KERNEL_BATCH; later, under the same number (no layout changed, nothing
  * removed): + ilm_visualize_distance_field / IlmVisualizeVertex, IlmVisualizeParams, ILM_VISUALIZE_* (distance-field views);
  * + ilm_render_directional_lights (directional lights; no new struct: the reference packs them into a LightVertex);
- * + ilm_ctx_set_projector_texture, ilm_render_projector_lights (projector lights; a LightVertex again).
+ * + ilm_ctx_set_projector_texture, ilm_render_projector_lights (projector lights; a LightVertex again);
+ * + ilm_render_line_lights (line lights; a LightVertex again).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -808,6 +809,63 @@ int32_t ilm_render_directional_lights(IlmHandle ctx,
                                       const float ambient[4],
                                       IlmHandle lightmap, int32_t row_begin, int32_t row_end,
                                       IlmRenderStats* stats);
+
+/* The line-light pass of LightingRenderer.RenderLighting: technique LineLight (Illuminant/Shaders/LineLight.fx:7-42 over
+ * LineLightCore.fxh:17-120), one quad per light, added onto the lightmap like every other light type.  The arguments mean what they mean
+ * for ilm_render_directional_lights: gbuffer == 0 => ground plane, sdf == 0 => no distance field, ambient == NULL => the lights are ADDED
+ * to what rows [row_begin, row_end) hold, ambient != NULL => every pixel of the rows is cleared to it first (whatever light_count is, 0
+ * included), stats != NULL => the counting variant runs and the call synchronises.  Any light_count >= 0.  ilm_ctx_set_lightmap_blend
+ * applies (fp32 registers over this call's lights in list order, the sum added to the base value and rounded once at the store; or the
+ * fp16-per-light model).  A bound light ramp (ilm_ctx_set_light_ramp) is neither read nor changed: the reference has no LineLightWithRamp.
+ * Vertex layout, as RenderLineLightSource fills it (Illuminant/Lighting/LightingRenderer.cs:1309-1337):
+ *   LightPosition1.xyz / LightPosition2.xyz StartPosition / EndPosition
+ *   Color1 / Color2                         StartColor / EndColor, alpha already multiplied by Opacity * intensityScale
+ *   LightProperties                         Radius, ramp length, RampMode, casts ? 1 : 0.  The host writes 0 for the ramp length (:1324);
+ *                                           the shader reads it (createTraceConfig), so what is given is honoured.  RampMode is not read.
+ *   MoreLightProperties                     AmbientOcclusionRadius, ShadowDistanceFalloff or -99999, FalloffYFactor,
+ *                                           AmbientOcclusionOpacity; .y and .z are not read by the pixel shader.
+ * (EvenMoreLightProperties and LightPosition3 are not read.)
+ * Coverage: every pixel of the rows.  The vertex shader's quad is min(P) - 9999 .. max(P) + 9999 (LineLightCore.fxh:142-152: "how the
+ * hell do we compute bounds for this"); that it covers the frame is the definition here -- there is no footprint test.
+ * Per pixel (LineLight.fx:7-42, LineLightCore.fxh:70-120), p = the shaded point, n = its normal:
+ *   a fullbright pixel is discarded (:25-29); casts *= enableShadows (:31);
+ *   distanceOpacity = computeLineLightOpacity (FBPBR.fxh:53-101), which also yields u = saturate(dot(p - start, delta) / dot(delta,
+ *   delta)) and the closest point start + u * delta (closestPointOnLineSegment3, DistanceFieldCommon.fxh:151-155);
+ *   the pixel is discarded unless distanceOpacity > 0 && p.x > -9999 (clip(), :90-93);
+ *   AO as for directional lights: radius * max(0, n.z), sampled only when >= 0.5 and a field is bound;
+ *   preTraceOpacity = distanceOpacity * aoOpacity; the pair traces iff casts != 0 && preTraceOpacity >= 0.75 / 255 (:104);
+ *   color = lerp(Color1, Color2, u) on all four components; rgb added = (color.rgb * color.a) * (preTraceOpacity * coneOpacity), alpha + 1.
+ * Unlike the directional pass, a pixel whose distance opacity is 0 IS discarded: it gets no rgb and no + 1 on alpha.
+ * The opacity term is a DEFINED function, fp32 with one rounding per + - * / sqrt in the order the HLSL writes it (dot = (x + y) + z,
+ * normalize = three IEEE divisions by the length, cross as written), and acos = acos_defined: sqrt(1 - |x|) * P7(|x|) with Abramowitz &
+ * Stegun 4.4.46's coefficients rounded to fp32, Horner form without fma, pi - r for x < 0 -- within 2^-21 of the real acos on [-1, 1],
+ * NaN outside it.  The solid angle g0 + g1 + g2 + g3 - 2 pi (FBPBR.fxh:46-50) cancels, so a library acos that differs by an ulp between
+ * host and device would move the decisions above, which feed exact statistics; parity with fxc's own acos expansion stays unpinned.
+ * Degenerate geometry is defined by that arithmetic and not special-cased: normalize(0) is 0 / 0 = NaN, the NaN reaches the final
+ * saturate, and saturate(NaN) = min(max(NaN, 0), 1) = 0.  So each of these gives distance opacity 0 and a discard, with no trace and no
+ * sample: Radius == 0 (the reference's default, LightSource.cs:325), a pixel on the segment's axis (up = cross(left, forward) = 0),
+ * start == end, a NaN position.  No memory access depends on any of them.
+ * The trace (lineConeTrace, LineLightCore.fxh:17-68): three TraceStates share the origin p + 1.5 * n and aim at start + saturate(u - o) *
+ * delta, start + u * delta and start + saturate(u + o) * delta, o = max(saturate((Radius + 1) / |delta|), 0.03); each is initialised
+ * with lightRadius = Radius (length = max(|target - origin| - Radius, 1), position 0.5, visibility 1); config = createTraceConfig((Radius,
+ * ramp length), (1, falloff)): maxRadius = clamp(Radius, 0.33, MaxConeRadius), growth = maxRadius / max(ramp length, 16).  Every
+ * iteration advances ALL three rays with coneTraceAdvanceEx (ConeTrace.fxh:84-96: position = min(position + step, length), liveness
+ * factor saturate(visibility - 0.075) * saturate((length - position) * 100)), then stepsRemaining-- and liveness = stepsRemaining * (the
+ * sum of the three).  A ray that has reached its end keeps sampling at its end point and keeps lowering its own visibility while
+ * another ray lives: that is the reference's arithmetic.  visibility = min((va + vb + vc) / 3, stepsRemaining / 2), then the sphere
+ * light's threshold and pow; unlike coneTrace there is no stepsRemaining == 0 fix-up.  The sample position origin + direction * position
+ * and the cone radius growth * position + 0.33 are fused multiply-adds, as in the other passes.
+ * Statistics: PixelLightPairs = pairs that reach the opacity term (every pair of a pixel of the rows that is not fullbright);
+ * TracedPairs = pairs that trace with a bound field (sdf != 0, Extent.x > 0); SdfSamples = the AO sample + 3 per loop iteration.
+ * Not built: LineLightProbe, the group entry point, an in-volume fast loop. */
+int32_t ilm_render_line_lights(IlmHandle ctx,
+                               const IlmLightVertex* lights, int32_t light_count,
+                               const IlmEnvironment* env,
+                               const IlmDistanceFieldUniforms* df,
+                               IlmHandle gbuffer, IlmHandle sdf,
+                               const float ambient[4],
+                               IlmHandle lightmap, int32_t row_begin, int32_t row_end,
+                               IlmRenderStats* stats);
 
 /* ProjectorLightSource.TextureRef of the light group rendered by the FOLLOWING ilm_render_projector_lights calls (the reference groups
  * projector lights by texture, one LightTypeRenderStateKey each, and binds it as the group's RampTexture; sampler
