@@ -3805,6 +3805,55 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     return ILM_OK;
 }
 
+// What ilm_render_directional_lights, ilm_render_line_lights and ilm_render_projector_lights share once each has made its own refusals:
+// the resource checks and the launch descriptor, rec_slots record slots, the staged vertices prepared into them, then one full-frame
+// launch (no split, no tile map) and the statistics.  `ramp` is what the pass reads through the descriptor's ramp member; light_limit
+// (0: none) is the projector pass's, refused where its slot count is about to be used.
+typedef hipError_t (*PrepareFullFrameLights)(const IlmLightVertex*, int, const IlmEnvironment&, const IlmDistanceFieldUniforms&, void*, hipStream_t);
+typedef hipError_t (*LaunchFullFrameLights)(const LightLaunch&, const void*, hipStream_t);
+static int32_t render_full_frame_lights(Ctx* c, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,
+                                        const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf, const float ambient[4],
+                                        IlmHandle hlightmap, int32_t row_begin, int32_t row_end, IlmRenderStats* stats, int rec_slots,
+                                        int light_limit, const RampView& ramp, PrepareFullFrameLights prepare, LaunchFullFrameLights launch) {
+    LightLaunch a = {};
+    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, false); if (rc != ILM_OK) return rc; }
+    Sdf* f = hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr;
+    GBuffer* g = hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr;
+    if (stats) stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0;
+
+    if (light_limit > 0 && light_count > light_limit)      // (keeps the slot count and reserve_light_recs's doubling inside an int)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "%d projector lights in one call: at most %d", light_count, light_limit);
+    { const int32_t rc = reserve_light_recs(c, rec_slots); if (rc != ILM_OK) return rc; }
+    if (light_count > 0) {
+        const void* staged = nullptr; int slot = 0;
+        int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
+        if (rc != ILM_OK) return rc;
+        HIP_TRY(prepare(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, c->d_recs.p, c->main()));
+        rc = staged_small_done(c, slot);
+        if (rc != ILM_OK) return rc;
+    }
+    a.light_count = light_count;
+    for (int i = 0; i < 4; i++) a.ambient[i] = ambient ? ambient[i] : 0.0f;
+    a.accumulate = ambient ? 0 : 1;
+    a.ramp = ramp;
+    if (stats) {
+        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
+        a.stats = c->d_stats;
+    }
+    // (ilm_debug_last_light_launch: one workgroup per 16 x 16 tile of the rows, no split, no tile map)
+    c->last_light_blocks = ((a.width + kLightTile - 1) / kLightTile) * ((row_end - row_begin + kLightTile - 1) / kLightTile);
+    c->last_light_split = 1; c->last_light_macro = 0;
+    HIP_TRY(launch(a, c->d_recs.p, c->main()));
+    HIP_TRY(light_pass_queued(c, f, g));
+    if (stats) {
+        unsigned long long host[3] = { 0, 0, 0 };
+        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
+        HIP_TRY(hipStreamSynchronize(c->main()));
+        stats->SdfSamples = host[0]; stats->PixelLightPairs = host[1]; stats->TracedPairs = host[2];
+    }
+    return ILM_OK;
+}
+
 int32_t ilm_render_directional_lights(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,
                                       const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf, const float ambient[4],
                                       IlmHandle hlightmap, int32_t row_begin, int32_t row_end, IlmRenderStats* stats) {
@@ -3821,41 +3870,9 @@ int32_t ilm_render_directional_lights(IlmHandle hctx, const IlmLightVertex* ligh
             return fail(ILM_ERR_INVALID_ARGUMENT, "directional light %d: bounds inverted, LightPosition1 (%g, %g) exceeds LightPosition2 (%g, %g)", i,
                         (double)p1.x, (double)p1.y, (double)p2.x, (double)p2.y);
     }
-    LightLaunch a = {};
-    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, false); if (rc != ILM_OK) return rc; }
-    Sdf* f = hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr;
-    GBuffer* g = hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr;
-    if (stats) stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0;
-
-    { const int32_t rc = reserve_light_recs(c, light_count); if (rc != ILM_OK) return rc; }
-    if (light_count > 0) {
-        const void* staged = nullptr; int slot = 0;
-        int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
-        if (rc != ILM_OK) return rc;
-        HIP_TRY(launch_prepare_directional_lights(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, c->d_recs.p, c->main()));
-        rc = staged_small_done(c, slot);
-        if (rc != ILM_OK) return rc;
-    }
-    a.light_count = light_count;
-    for (int i = 0; i < 4; i++) a.ambient[i] = ambient ? ambient[i] : 0.0f;
-    a.accumulate = ambient ? 0 : 1;
-    a.ramp = RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h };
-    if (stats) {
-        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
-        a.stats = c->d_stats;
-    }
-    // (ilm_debug_last_light_launch: one workgroup per 16 x 16 tile of the rows, no split, no tile map)
-    c->last_light_blocks = ((a.width + kLightTile - 1) / kLightTile) * ((row_end - row_begin + kLightTile - 1) / kLightTile);
-    c->last_light_split = 1; c->last_light_macro = 0;
-    HIP_TRY(launch_directional_lights_prepared(a, c->d_recs.p, c->main()));
-    HIP_TRY(light_pass_queued(c, f, g));
-    if (stats) {
-        unsigned long long host[3] = { 0, 0, 0 };
-        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        stats->SdfSamples = host[0]; stats->PixelLightPairs = host[1]; stats->TracedPairs = host[2];
-    }
-    return ILM_OK;
+    return render_full_frame_lights(c, lights, light_count, env, df, hgbuffer, hsdf, ambient, hlightmap, row_begin, row_end, stats, light_count, 0,
+                                    RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h }, launch_prepare_directional_lights,
+                                    launch_directional_lights_prepared);
 }
 
 int32_t ilm_render_line_lights(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,
@@ -3866,41 +3883,12 @@ int32_t ilm_render_line_lights(IlmHandle hctx, const IlmLightVertex* lights, int
     if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
     if (light_count < 0 || (light_count > 0 && !lights)) return fail(ILM_ERR_INVALID_ARGUMENT, "bad light array");
     // (no light is refused: degenerate geometry -- radius 0, start == end, a NaN position -- is defined by the arithmetic: opacity 0)
-    LightLaunch a = {};
-    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, false); if (rc != ILM_OK) return rc; }
-    Sdf* f = hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr;
-    GBuffer* g = hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr;
-    if (stats) stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0;
-
-    { const int32_t rc = reserve_light_recs(c, light_count); if (rc != ILM_OK) return rc; }
-    if (light_count > 0) {
-        const void* staged = nullptr; int slot = 0;
-        int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
-        if (rc != ILM_OK) return rc;
-        HIP_TRY(launch_prepare_line_lights(static_cast<const IlmLightVertex*>(staged), light_count, *df, c->d_recs.p, c->main()));
-        rc = staged_small_done(c, slot);
-        if (rc != ILM_OK) return rc;
-    }
-    a.light_count = light_count;
-    for (int i = 0; i < 4; i++) a.ambient[i] = ambient ? ambient[i] : 0.0f;
-    a.accumulate = ambient ? 0 : 1;
-    // (a.ramp stays empty: the reference has no LineLightWithRamp; the ramp binding is neither read nor touched)
-    if (stats) {
-        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
-        a.stats = c->d_stats;
-    }
-    // (ilm_debug_last_light_launch: one workgroup per 16 x 16 tile of the rows, no split, no tile map)
-    c->last_light_blocks = ((a.width + kLightTile - 1) / kLightTile) * ((row_end - row_begin + kLightTile - 1) / kLightTile);
-    c->last_light_split = 1; c->last_light_macro = 0;
-    HIP_TRY(launch_line_lights_prepared(a, c->d_recs.p, c->main()));
-    HIP_TRY(light_pass_queued(c, f, g));
-    if (stats) {
-        unsigned long long host[3] = { 0, 0, 0 };
-        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        stats->SdfSamples = host[0]; stats->PixelLightPairs = host[1]; stats->TracedPairs = host[2];
-    }
-    return ILM_OK;
+    // (the ramp stays empty: the reference has no LineLightWithRamp; the ramp binding is neither read nor touched)
+    return render_full_frame_lights(c, lights, light_count, env, df, hgbuffer, hsdf, ambient, hlightmap, row_begin, row_end, stats, light_count, 0,
+                                    RampView{ nullptr, 0, 0 },
+                                    [](const IlmLightVertex* staged, int count, const IlmEnvironment&, const IlmDistanceFieldUniforms& dfu, void* recs,
+                                       hipStream_t stream) { return launch_prepare_line_lights(staged, count, dfu, recs, stream); },
+                                    launch_line_lights_prepared);
 }
 
 int32_t ilm_render_projector_lights(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,
@@ -3913,46 +3901,15 @@ int32_t ilm_render_projector_lights(IlmHandle hctx, const IlmLightVertex* lights
     // the reference skips a light whose texture is null before packing (LightingRenderer.cs:1389-1391): lights without one are a caller's error
     if (light_count > 0 && c->projector_texture_w == 0)
         return fail(ILM_ERR_INVALID_ARGUMENT, "projector lights without a texture: ilm_ctx_set_projector_texture binds the group's");
-    LightLaunch a = {};
-    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, false); if (rc != ILM_OK) return rc; }
-    Sdf* f = hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr;
-    GBuffer* g = hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr;
-    if (stats) stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0;
-
     // (a projector record is one and a half slots of the other passes' records)
     static_assert(kProjectorRecBytes * 2 == kLightRecBytes * 3, "a projector record is one and a half light-record slots");
-    if (light_count > kMaxProjectorLights)      // (keeps the slot count and reserve_light_recs's doubling inside an int)
-        return fail(ILM_ERR_INVALID_ARGUMENT, "%d projector lights in one call: at most %d", light_count, kMaxProjectorLights);
-    { const int32_t rc = reserve_light_recs(c, light_count + (light_count + 1) / 2); if (rc != ILM_OK) return rc; }
-    if (light_count > 0) {
-        const void* staged = nullptr; int slot = 0;
-        int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
-        if (rc != ILM_OK) return rc;
-        HIP_TRY(launch_prepare_projector_lights(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, c->d_recs.p, c->main()));
-        rc = staged_small_done(c, slot);
-        if (rc != ILM_OK) return rc;
-    }
-    a.light_count = light_count;
-    for (int i = 0; i < 4; i++) a.ambient[i] = ambient ? ambient[i] : 0.0f;
-    a.accumulate = ambient ? 0 : 1;
+    // (more than kMaxProjectorLights are refused behind the shared checks, before the slots are reserved)
     // the group's texture rides in the descriptor's ramp member; the ramp binding (ilm_ctx_set_light_ramp) is neither read nor touched
-    a.ramp = RampView{ light_count > 0 ? static_cast<const float4*>(c->d_projector_texture.p) : nullptr, c->projector_texture_w, c->projector_texture_h };
-    if (stats) {
-        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
-        a.stats = c->d_stats;
-    }
-    // (ilm_debug_last_light_launch: one workgroup per 16 x 16 tile of the rows, no split, no tile map)
-    c->last_light_blocks = ((a.width + kLightTile - 1) / kLightTile) * ((row_end - row_begin + kLightTile - 1) / kLightTile);
-    c->last_light_split = 1; c->last_light_macro = 0;
-    HIP_TRY(launch_projector_lights_prepared(a, c->d_recs.p, c->main()));
-    HIP_TRY(light_pass_queued(c, f, g));
-    if (stats) {
-        unsigned long long host[3] = { 0, 0, 0 };
-        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        stats->SdfSamples = host[0]; stats->PixelLightPairs = host[1]; stats->TracedPairs = host[2];
-    }
-    return ILM_OK;
+    return render_full_frame_lights(c, lights, light_count, env, df, hgbuffer, hsdf, ambient, hlightmap, row_begin, row_end, stats,
+                                    light_count > kMaxProjectorLights ? 0 : light_count + (light_count + 1) / 2, kMaxProjectorLights,
+                                    RampView{ light_count > 0 ? static_cast<const float4*>(c->d_projector_texture.p) : nullptr, c->projector_texture_w,
+                                              c->projector_texture_h },
+                                    launch_prepare_projector_lights, launch_projector_lights_prepared);
 }
 
 }  // extern "C"

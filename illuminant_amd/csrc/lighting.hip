@@ -1246,6 +1246,55 @@ hipError_t launch_sphere_lights_prepared(const LightLaunch& launch, const void* 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The full-frame light passes (directional, projector, line) -- one thread per pixel, one wave per 8 x 8 pixels, a wave-uniform loop
+// over the prepared records (uniform index: scalar loads), the G-buffer texel decoded once, the sum in registers, the lightmap texel
+// read at most once (accumulate mode) and stored once.  Shared by the three kernels: the store with its mirrors, the statistics and
+// the launcher.  Each kernel states its own pixel mapping, base value, blend chains and light loop: as device functions these change
+// the instruction streams of all three kernels, and the passes then run up to 3 % slower (docs/experiments.md 7.24).  A change to
+// one of those parts is made in directional_lights_kernel, projector_lights_kernel and line_lights_kernel alike.
+// ---------------------------------------------------------------------------------------------
+// the texel into the lightmap and into every mirror (store-mode exchange of a group lightmap, as the sphere pass)
+ILM_DEV void store_light_texel(const LightLaunch& a, size_t o, const float4& v) {
+    auto store_texel = [&](void* base) {
+        if (a.format == ILM_LIGHTMAP_FLOAT4) store_target<ILM_LIGHTMAP_FLOAT4>(base, o, v);
+        else if (a.format == ILM_LIGHTMAP_HALF4) store_target<ILM_LIGHTMAP_HALF4>(base, o, v);
+        else store_target<ILM_LIGHTMAP_RGBA8>(base, o, v);
+    };
+    store_texel(a.lightmap);
+    for (int m = 0; m < a.mirror_count; m++) store_texel(a.mirrors[m]);
+}
+
+// the wave's statistics: three sums over the lanes, three atomics
+ILM_DEV void add_light_stats(LightStats st, unsigned long long* stats, int lane) {
+    for (int off = 32; off > 0; off >>= 1) {
+        st.samples += __shfl_down(st.samples, off);
+        st.pairs += __shfl_down(st.pairs, off);
+        st.traced += __shfl_down(st.traced, off);
+    }
+    if (lane == 0) {
+        atomicAdd(&stats[0], st.samples);
+        atomicAdd(&stats[1], st.pairs);
+        atomicAdd(&stats[2], st.traced);
+    }
+}
+
+// one workgroup per 16 x 16 tile of the rows; the pass's kernel by field format and by whether the call counts
+template <class Rec>
+using FullFrameKernel = void (*)(LightLaunch, const Rec*, int);
+template <class Rec>
+hipError_t launch_full_frame_lights(const LightLaunch& a, const void* recs, hipStream_t stream, FullFrameKernel<Rec> fp16, FullFrameKernel<Rec> fp16_stats,
+                                    FullFrameKernel<Rec> unorm16, FullFrameKernel<Rec> unorm16_stats) {
+    const int rows = a.row_end - a.row_begin;
+    if (rows <= 0 || a.width <= 0) return hipSuccess;
+    if (a.light_count == 0 && a.accumulate != 0) return hipSuccess;      // nothing to add: no texel (and no mirror) would change
+    const int tiles_x = (a.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
+    const bool stats = a.stats != nullptr;
+    const FullFrameKernel<Rec> kernel = (a.sdf.format == ILM_SDF_FP16) ? (stats ? fp16_stats : fp16) : (stats ? unorm16_stats : unorm16);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles_x * (unsigned)tiles_y), dim3(kLightThreads), 0, stream, a, reinterpret_cast<const Rec*>(recs), tiles_x);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Directional lights -- techniques DirectionalLight / DirectionalLightWithRamp, DirectionalLight.fx:19-161, drawn by
 // RenderDirectionalLightSource (LightingRenderer.cs:1256-1307) as one full-frame (or Bounds-sized) quad per light.
 // A footprint is a rectangle: no tile lists, no light split -- one thread per pixel, one wave per 8 x 8 pixels, the light loop is
@@ -1437,26 +1486,9 @@ __global__ __launch_bounds__(kLightThreads) void directional_lights_kernel(const
     }
     if (in_image) {
         const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
-        auto store_texel = [&](void* base) {
-            if (a.format == ILM_LIGHTMAP_FLOAT4) store_target<ILM_LIGHTMAP_FLOAT4>(base, o, v);
-            else if (a.format == ILM_LIGHTMAP_HALF4) store_target<ILM_LIGHTMAP_HALF4>(base, o, v);
-            else store_target<ILM_LIGHTMAP_RGBA8>(base, o, v);
-        };
-        store_texel(a.lightmap);
-        for (int m = 0; m < a.mirror_count; m++) store_texel(a.mirrors[m]);      // store-mode exchange of a group lightmap, as the sphere pass
+        store_light_texel(a, o, v);
     }
-    if (STATS) {
-        for (int off = 32; off > 0; off >>= 1) {
-            st.samples += __shfl_down(st.samples, off);
-            st.pairs += __shfl_down(st.pairs, off);
-            st.traced += __shfl_down(st.traced, off);
-        }
-        if (lane == 0) {
-            atomicAdd(&a.stats[0], st.samples);
-            atomicAdd(&a.stats[1], st.pairs);
-            atomicAdd(&a.stats[2], st.traced);
-        }
-    }
+    if (STATS) add_light_stats(st, a.stats, lane);
 }
 
 hipError_t launch_prepare_directional_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
@@ -1468,21 +1500,8 @@ hipError_t launch_prepare_directional_lights(const IlmLightVertex* lights, int c
 }
 
 hipError_t launch_directional_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
-    const int rows = a.row_end - a.row_begin;
-    if (rows <= 0 || a.width <= 0) return hipSuccess;
-    if (a.light_count == 0 && a.accumulate != 0) return hipSuccess;      // nothing to add: no texel (and no mirror) would change
-    const int tiles_x = (a.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
-    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y), block(kLightThreads);
-    const DirectionalRec* r = reinterpret_cast<const DirectionalRec*>(recs);
-    const bool stats = a.stats != nullptr;
-    if (a.sdf.format == ILM_SDF_FP16) {
-        if (stats) hipLaunchKernelGGL((directional_lights_kernel<ILM_SDF_FP16, true>), grid, block, 0, stream, a, r, tiles_x);
-        else hipLaunchKernelGGL((directional_lights_kernel<ILM_SDF_FP16, false>), grid, block, 0, stream, a, r, tiles_x);
-    } else {
-        if (stats) hipLaunchKernelGGL((directional_lights_kernel<ILM_SDF_UNORM16, true>), grid, block, 0, stream, a, r, tiles_x);
-        else hipLaunchKernelGGL((directional_lights_kernel<ILM_SDF_UNORM16, false>), grid, block, 0, stream, a, r, tiles_x);
-    }
-    return hipGetLastError();
+    return launch_full_frame_lights<DirectionalRec>(a, recs, stream, directional_lights_kernel<ILM_SDF_FP16, false>, directional_lights_kernel<ILM_SDF_FP16, true>,
+                                           directional_lights_kernel<ILM_SDF_UNORM16, false>, directional_lights_kernel<ILM_SDF_UNORM16, true>);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1689,10 +1708,7 @@ ILM_DEV bool shade_projector(const Pixel& P, const ProjectorRec& L, const TraceF
     return true;
 }
 
-// The frame of directional_lights_kernel with its base value / blend / store / mirror / statistics tail as a COPY, to be kept in step
-// with it.  The shared form was built -- the base value and the store with its mirrors as two device functions both kernels call --
-// and compared (tools/isa_compare.py against the parent's listing): the four instantiations of directional_lights_kernel came out
-// `diff` (8 vector instructions fewer, one scalar instruction more, another schedule), and the existing passes are held not to move.
+// (pixel mapping, base value and blend chains as in directional_lights_kernel: see the note at the head of the full-frame passes)
 template <int FMT, bool STATS>
 __global__ __launch_bounds__(kLightThreads) void projector_lights_kernel(const LightLaunch a, const ProjectorRec* __restrict__ recs, int tiles_x) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
@@ -1752,26 +1768,9 @@ __global__ __launch_bounds__(kLightThreads) void projector_lights_kernel(const L
     }
     if (in_image) {
         const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
-        auto store_texel = [&](void* base) {
-            if (a.format == ILM_LIGHTMAP_FLOAT4) store_target<ILM_LIGHTMAP_FLOAT4>(base, o, v);
-            else if (a.format == ILM_LIGHTMAP_HALF4) store_target<ILM_LIGHTMAP_HALF4>(base, o, v);
-            else store_target<ILM_LIGHTMAP_RGBA8>(base, o, v);
-        };
-        store_texel(a.lightmap);
-        for (int m = 0; m < a.mirror_count; m++) store_texel(a.mirrors[m]);      // store-mode exchange of a group lightmap, as the sphere pass
+        store_light_texel(a, o, v);
     }
-    if (STATS) {
-        for (int off = 32; off > 0; off >>= 1) {
-            st.samples += __shfl_down(st.samples, off);
-            st.pairs += __shfl_down(st.pairs, off);
-            st.traced += __shfl_down(st.traced, off);
-        }
-        if (lane == 0) {
-            atomicAdd(&a.stats[0], st.samples);
-            atomicAdd(&a.stats[1], st.pairs);
-            atomicAdd(&a.stats[2], st.traced);
-        }
-    }
+    if (STATS) add_light_stats(st, a.stats, lane);
 }
 
 hipError_t launch_prepare_projector_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
@@ -1783,27 +1782,14 @@ hipError_t launch_prepare_projector_lights(const IlmLightVertex* lights, int cou
 }
 
 hipError_t launch_projector_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
-    const int rows = a.row_end - a.row_begin;
-    if (rows <= 0 || a.width <= 0) return hipSuccess;
-    if (a.light_count == 0 && a.accumulate != 0) return hipSuccess;      // nothing to add: no texel (and no mirror) would change
-    const int tiles_x = (a.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
-    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y), block(kLightThreads);
-    const ProjectorRec* r = reinterpret_cast<const ProjectorRec*>(recs);
-    const bool stats = a.stats != nullptr;
-    if (a.sdf.format == ILM_SDF_FP16) {
-        if (stats) hipLaunchKernelGGL((projector_lights_kernel<ILM_SDF_FP16, true>), grid, block, 0, stream, a, r, tiles_x);
-        else hipLaunchKernelGGL((projector_lights_kernel<ILM_SDF_FP16, false>), grid, block, 0, stream, a, r, tiles_x);
-    } else {
-        if (stats) hipLaunchKernelGGL((projector_lights_kernel<ILM_SDF_UNORM16, true>), grid, block, 0, stream, a, r, tiles_x);
-        else hipLaunchKernelGGL((projector_lights_kernel<ILM_SDF_UNORM16, false>), grid, block, 0, stream, a, r, tiles_x);
-    }
-    return hipGetLastError();
+    return launch_full_frame_lights<ProjectorRec>(a, recs, stream, projector_lights_kernel<ILM_SDF_FP16, false>, projector_lights_kernel<ILM_SDF_FP16, true>,
+                                           projector_lights_kernel<ILM_SDF_UNORM16, false>, projector_lights_kernel<ILM_SDF_UNORM16, true>);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Line lights -- technique LineLight, LineLight.fx:7-42 over LineLightCore.fxh:17-120, drawn by RenderLineLightSource
 // (LightingRenderer.cs:1309-1337) as one quad per light whose vertex shader pads the segment's bounds by 9999 (LineLightCore.fxh:142-152):
-// every pixel of the rows is covered, so there is no footprint test.  The frame of the directional pass: one thread per pixel, one wave
+// every pixel of the rows is covered, so there is no footprint test.  The full-frame passes' frame: one thread per pixel, one wave
 // per 8 x 8 pixels, a wave-uniform loop over the prepared records (scalar loads), the G-buffer texel decoded once, the sum in registers,
 // one store.  New here: the closed-form area-light term (computeLineLightOpacity, FBPBR.fxh:53-101) in the exact forms of hlsl_math.hpp with
 // acos_defined, and a cone trace of three rays in lock-step (lineConeTrace over coneTraceAdvanceEx, ConeTrace.fxh:84-96): three
@@ -1995,10 +1981,8 @@ ILM_DEV bool shade_line(const Pixel& P, const LineRec& L, const TraceField& F, b
     return true;
 }
 
-// The frame of directional_lights_kernel with its base value / blend / store / mirror / statistics tail as a COPY, to be kept in step
-// with it (and with projector_lights_kernel's): the shared form was built twice and moved the existing kernels' instruction streams
-// (see the comments at sample_from_ramp and projector_lights_kernel), and the existing passes are held not to move.  No footprint: the
-// vertex shader's quad, min(P) - 9999 .. max(P) + 9999, is defined here as every pixel of the rows.
+// (pixel mapping, base value and blend chains as in directional_lights_kernel: see the note at the head of the full-frame passes.)
+// No footprint: the vertex shader's quad, min(P) - 9999 .. max(P) + 9999, is defined here as every pixel of the rows.
 template <int FMT, bool STATS>
 __global__ __launch_bounds__(kLightThreads) void line_lights_kernel(const LightLaunch a, const LineRec* __restrict__ recs, int tiles_x) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
@@ -2055,26 +2039,9 @@ __global__ __launch_bounds__(kLightThreads) void line_lights_kernel(const LightL
     }
     if (in_image) {
         const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
-        auto store_texel = [&](void* base) {
-            if (a.format == ILM_LIGHTMAP_FLOAT4) store_target<ILM_LIGHTMAP_FLOAT4>(base, o, v);
-            else if (a.format == ILM_LIGHTMAP_HALF4) store_target<ILM_LIGHTMAP_HALF4>(base, o, v);
-            else store_target<ILM_LIGHTMAP_RGBA8>(base, o, v);
-        };
-        store_texel(a.lightmap);
-        for (int m = 0; m < a.mirror_count; m++) store_texel(a.mirrors[m]);      // store-mode exchange of a group lightmap, as the sphere pass
+        store_light_texel(a, o, v);
     }
-    if (STATS) {
-        for (int off = 32; off > 0; off >>= 1) {
-            st.samples += __shfl_down(st.samples, off);
-            st.pairs += __shfl_down(st.pairs, off);
-            st.traced += __shfl_down(st.traced, off);
-        }
-        if (lane == 0) {
-            atomicAdd(&a.stats[0], st.samples);
-            atomicAdd(&a.stats[1], st.pairs);
-            atomicAdd(&a.stats[2], st.traced);
-        }
-    }
+    if (STATS) add_light_stats(st, a.stats, lane);
 }
 
 hipError_t launch_prepare_line_lights(const IlmLightVertex* lights, int count, const IlmDistanceFieldUniforms& df, void* recs, hipStream_t stream) {
@@ -2085,21 +2052,8 @@ hipError_t launch_prepare_line_lights(const IlmLightVertex* lights, int count, c
 }
 
 hipError_t launch_line_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
-    const int rows = a.row_end - a.row_begin;
-    if (rows <= 0 || a.width <= 0) return hipSuccess;
-    if (a.light_count == 0 && a.accumulate != 0) return hipSuccess;      // nothing to add: no texel (and no mirror) would change
-    const int tiles_x = (a.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
-    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y), block(kLightThreads);
-    const LineRec* r = reinterpret_cast<const LineRec*>(recs);
-    const bool stats = a.stats != nullptr;
-    if (a.sdf.format == ILM_SDF_FP16) {
-        if (stats) hipLaunchKernelGGL((line_lights_kernel<ILM_SDF_FP16, true>), grid, block, 0, stream, a, r, tiles_x);
-        else hipLaunchKernelGGL((line_lights_kernel<ILM_SDF_FP16, false>), grid, block, 0, stream, a, r, tiles_x);
-    } else {
-        if (stats) hipLaunchKernelGGL((line_lights_kernel<ILM_SDF_UNORM16, true>), grid, block, 0, stream, a, r, tiles_x);
-        else hipLaunchKernelGGL((line_lights_kernel<ILM_SDF_UNORM16, false>), grid, block, 0, stream, a, r, tiles_x);
-    }
-    return hipGetLastError();
+    return launch_full_frame_lights<LineRec>(a, recs, stream, line_lights_kernel<ILM_SDF_FP16, false>, line_lights_kernel<ILM_SDF_FP16, true>,
+                                           line_lights_kernel<ILM_SDF_UNORM16, false>, line_lights_kernel<ILM_SDF_UNORM16, true>);
 }
 
 __global__ __launch_bounds__(256) void divide_probe_kernel(const float* __restrict__ n, const float* __restrict__ d, int count,

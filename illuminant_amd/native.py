@@ -856,52 +856,37 @@ def visualize_distance_field(ctx, sdf, df, quad, params, target, want_stats=Fals
     return tuple(int(x) for x in stats) if want_stats else None
 
 
-def render_sphere_lights(ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin=0, row_end=None, want_stats=False):
-    """ilm_render_sphere_lights.  lights: ctypes array of abi.LightVertex (or None for zero lights); ambient None = add this light
-    group to what the lightmap already holds."""
+def _render_lights(fn, ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin, row_end, want_stats):
+    """one of the ilm_render_*_lights entry points that take a light array: they share one argument list"""
     if row_end is None:
         row_end = lightmap.height
     n = len(lights) if lights is not None else 0
     amb = (C.c_float * 4)(*[float(x) for x in ambient]) if ambient is not None else None
     stats = abi.RenderStats() if want_stats else None
-    check(lib().ilm_render_sphere_lights(
+    check(fn(
         ctx.handle, C.cast(lights, C.c_void_p) if n else None, n, _byref(env), _byref(df),
         gbuffer.handle if gbuffer is not None else abi.Handle(0),
         sdf.handle if sdf is not None else abi.Handle(0),
         C.cast(amb, C.c_void_p) if amb is not None else None, lightmap.handle, row_begin, row_end, _byref(stats)))
     return stats
+
+
+def render_sphere_lights(ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin=0, row_end=None, want_stats=False):
+    """ilm_render_sphere_lights.  lights: ctypes array of abi.LightVertex (or None for zero lights); ambient None = add this light
+    group to what the lightmap already holds."""
+    return _render_lights(lib().ilm_render_sphere_lights, ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin, row_end, want_stats)
 
 
 def render_directional_lights(ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin=0, row_end=None, want_stats=False):
     """ilm_render_directional_lights.  lights: ctypes array of abi.LightVertex packed as RenderDirectionalLightSource packs them (or
     None for zero lights); ambient None = add this light group to what the lightmap already holds."""
-    if row_end is None:
-        row_end = lightmap.height
-    n = len(lights) if lights is not None else 0
-    amb = (C.c_float * 4)(*[float(x) for x in ambient]) if ambient is not None else None
-    stats = abi.RenderStats() if want_stats else None
-    check(lib().ilm_render_directional_lights(
-        ctx.handle, C.cast(lights, C.c_void_p) if n else None, n, _byref(env), _byref(df),
-        gbuffer.handle if gbuffer is not None else abi.Handle(0),
-        sdf.handle if sdf is not None else abi.Handle(0),
-        C.cast(amb, C.c_void_p) if amb is not None else None, lightmap.handle, row_begin, row_end, _byref(stats)))
-    return stats
+    return _render_lights(lib().ilm_render_directional_lights, ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin, row_end, want_stats)
 
 
 def render_line_lights(ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin=0, row_end=None, want_stats=False):
     """ilm_render_line_lights.  lights: ctypes array of abi.LightVertex packed as RenderLineLightSource packs them (or None for zero
     lights); ambient None = add this light group to what the lightmap already holds."""
-    if row_end is None:
-        row_end = lightmap.height
-    n = len(lights) if lights is not None else 0
-    amb = (C.c_float * 4)(*[float(x) for x in ambient]) if ambient is not None else None
-    stats = abi.RenderStats() if want_stats else None
-    check(lib().ilm_render_line_lights(
-        ctx.handle, C.cast(lights, C.c_void_p) if n else None, n, _byref(env), _byref(df),
-        gbuffer.handle if gbuffer is not None else abi.Handle(0),
-        sdf.handle if sdf is not None else abi.Handle(0),
-        C.cast(amb, C.c_void_p) if amb is not None else None, lightmap.handle, row_begin, row_end, _byref(stats)))
-    return stats
+    return _render_lights(lib().ilm_render_line_lights, ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin, row_end, want_stats)
 
 
 def set_projector_texture(ctx, texels):
@@ -919,17 +904,7 @@ def set_projector_texture(ctx, texels):
 def render_projector_lights(ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin=0, row_end=None, want_stats=False):
     """ilm_render_projector_lights.  lights: ctypes array of abi.LightVertex packed as RenderProjectorLightSource packs them (or None
     for zero lights), lit through the texture set_projector_texture bound; ambient None = add this group to what the lightmap holds."""
-    if row_end is None:
-        row_end = lightmap.height
-    n = len(lights) if lights is not None else 0
-    amb = (C.c_float * 4)(*[float(x) for x in ambient]) if ambient is not None else None
-    stats = abi.RenderStats() if want_stats else None
-    check(lib().ilm_render_projector_lights(
-        ctx.handle, C.cast(lights, C.c_void_p) if n else None, n, _byref(env), _byref(df),
-        gbuffer.handle if gbuffer is not None else abi.Handle(0),
-        sdf.handle if sdf is not None else abi.Handle(0),
-        C.cast(amb, C.c_void_p) if amb is not None else None, lightmap.handle, row_begin, row_end, _byref(stats)))
-    return stats
+    return _render_lights(lib().ilm_render_projector_lights, ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin, row_end, want_stats)
 
 
 def render_particle_lights(ctx, system, params, env, df, gbuffer, sdf, lightmap, quad_counts=None, chunk_count=None, row_begin=0, row_end=None,

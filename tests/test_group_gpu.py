@@ -417,6 +417,83 @@ def test_store_mode_composites_the_frame_without_a_gather(ctx, members, fmt, bal
         g.close()
 
 
+def full_frame_pass(which):
+    """(render call, extra environment arguments, projector texture or None, first light group, second light group) of one of the three
+    full-frame passes, in the 44 x 27 scene of tests/directional_common.py, from the pass's own test helpers"""
+    # (the light helpers are module-level functions of the passes' own test files -- oblique, from_below, area_ambient, straight_down;
+    # three_lights, wrapping, clamped; overhead, low, buried, SPECIAL -- imported by name: whoever renames one there renames it here)
+    if which == "directional":
+        from tests import test_directional_gpu as t
+        return (native.render_directional_lights, {}, None, [t.oblique(), t.from_below(), t.area_ambient()],
+                [t.straight_down(), t.area_ambient(bounds=(0.0, 10.5, 44.0, 18.5))])
+    if which == "projector":
+        from tests import projector_common as pc, test_projector_gpu as t
+        return (native.render_projector_lights, dict(maximum_z=32.0), pc.texture(5, 3), t.three_lights(), [t.wrapping(), t.clamped(rotation_z=0.3)])
+    from tests import test_line_gpu as t
+    return native.render_line_lights, {}, None, [t.overhead(), t.low()], [t.overhead(**t.SPECIAL["vertical"]), t.buried()]
+
+
+@pytest.mark.parametrize("fmt,blend_fp16", [(abi.LIGHTMAP_HALF4, True), (abi.LIGHTMAP_RGBA8, False)])
+@pytest.mark.parametrize("which", ["directional", "projector", "line"])
+def test_store_mode_mirrors_the_full_frame_passes(ctx, which, fmt, blend_fp16):
+    """The directional, projector and line passes into an armed group lightmap: their store writes every member's copy of the frame, as the
+    sphere pass's does.  Two members on one device render rows 0 .. 13 and 13 .. 27 of the 44 x 27 frame -- a cut inside a wave tile, so a
+    wave of each member has lanes on both sides of its row_end (ilm_group_lightmap_set_strips takes whole tile bands only; the store-mode
+    table belongs to the buffers, not to the strip table, and the host-driven form names its rows itself).  A first group with an
+    ambient colour, then a smaller one accumulated on top, which reads the member's own texel and writes both copies.  Both members must
+    hold, byte for byte, the frame one plain context renders with the same two calls over the whole height.  Member 0 runs the counting
+    instantiation of the kernel, member 1 the other."""
+    from tests import directional_common as dc
+    render, env_kw, texture, first, second = full_frame_pass(which)
+    w, h = dc.WIDTH, dc.HEIGHT
+    env = scenes.environment(gbuffer_size=(w, h), **env_kw)
+    dfu = dc.field_uniforms(step_limit=dc.MAX_STEP_COUNT)
+    atlas, texels = dc.field_atlas(abi.SDF_UNORM16), dc.gbuffer_texels()
+    groups = [(dc.light_array(first), AMBIENT), (dc.light_array(second), None)]
+    g = native.Group([0, 0])
+    contexts = list(g.contexts) + [ctx]
+    sdfs = [native.DistanceFieldTexture(c, atlas, abi.SDF_UNORM16) for c in contexts]
+    gbs = [native.GBufferTexture(c, texels, abi.GBUFFER_FLOAT4) for c in contexts]
+    glm = native.GroupLightmap(g, w, h, fmt)
+    lm = native.Lightmap(ctx, w, h, fmt)
+    try:
+        for c in contexts:
+            c.set_lightmap_blend(blend_fp16)
+            if texture is not None:
+                native.set_projector_texture(c, texture)
+        # the plain context's frames: cleared, the ambient colour alone, after the first group, after the second
+        lm.clear()
+        cleared = lm.download()
+        render(ctx, None, env, dfu, gbs[2], sdfs[2], AMBIENT, lm)
+        ambient_only = lm.download()
+        stats = render(ctx, groups[0][0], env, dfu, gbs[2], sdfs[2], AMBIENT, lm, want_stats=True)
+        want1 = lm.download()
+        render(ctx, groups[1][0], env, dfu, gbs[2], sdfs[2], None, lm)
+        want2 = lm.download()
+        assert stats.TracedPairs > 0, "no light of the first group traces"
+        assert not np.array_equal(want1, cleared) and not np.array_equal(want1, ambient_only), "the first group lit nothing"
+        assert not np.array_equal(want2, want1), "the second group changed nothing"
+        glm.store_mode(True)
+        strips = ((0, 13), (13, h))
+        for lights, ambient in groups:
+            glm.gather(native.GATHER_STORE)                      # (readers of the previous pass are done before anybody overwrites)
+            for i, (b, e) in enumerate(strips):
+                render(g.contexts[i], lights, env, dfu, gbs[i], sdfs[i], ambient, glm.members[i], b, e, want_stats=(i == 0))
+        glm.gather(native.GATHER_STORE)
+        g.sync()
+        for i in range(2):
+            assert np.array_equal(glm.download(i).view(np.uint8), want2.view(np.uint8)), "%s pass in store mode: member %d's frame differs" % (which, i)
+        glm.store_mode(False)
+    finally:
+        ctx.set_lightmap_blend(False)
+        if texture is not None:
+            native.set_projector_texture(ctx, None)
+        lm.close(); glm.close()
+        for x in sdfs + gbs:
+            x.close()
+        g.close()
+
+
 def test_store_mode_of_a_rank_group_at_world_one(ctx):
     """A group that spans processes arms the store mode through IPC handles of the ranks' buffers (a collective; world sizes 2, 3 and 8 on this
     GPU: tests/test_two_ranks_one_gpu.py); with one rank there is nobody to map and the frame is simply the rank's own."""
