@@ -3805,7 +3805,7 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     return ILM_OK;
 }
 
-// What ilm_render_directional_lights, ilm_render_line_lights and ilm_render_projector_lights share once each has made its own refusals:
+// What ilm_render_directional_lights, _line_lights, _projector_lights and _volumetric_lights share once each has made its own refusals:
 // the resource checks and the launch descriptor, rec_slots record slots, the staged vertices prepared into them, then one full-frame
 // launch (no split, no tile map) and the statistics.  `ramp` is what the pass reads through the descriptor's ramp member; light_limit
 // (0: none) is the projector pass's, refused where its slot count is about to be used.
@@ -3910,6 +3910,27 @@ int32_t ilm_render_projector_lights(IlmHandle hctx, const IlmLightVertex* lights
                                     RampView{ light_count > 0 ? static_cast<const float4*>(c->d_projector_texture.p) : nullptr, c->projector_texture_w,
                                               c->projector_texture_h },
                                     launch_prepare_projector_lights, launch_projector_lights_prepared);
+}
+
+int32_t ilm_render_volumetric_lights(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,
+                                     const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf, const float ambient[4],
+                                     IlmHandle hlightmap, int32_t row_begin, int32_t row_end, IlmRenderStats* stats) {
+    ILM_TRACE_RANGE("ilm_render_volumetric_lights");
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    if (light_count < 0 || (light_count > 0 && !lights)) return fail(ILM_ERR_INVALID_ARGUMENT, "bad light array");
+    // the shader's three tests of the shape (<=, (float) ==, (int) ==) agree only at 0, 1 and 2
+    for (int i = 0; i < light_count; i++) {
+        const float shape = lights[i].EvenMoreLightProperties.w;
+        if (!(shape == 0.0f || shape == 1.0f || shape == 2.0f))
+            return fail(ILM_ERR_INVALID_ARGUMENT, "volumetric light %d: shape %g is none of 0 (ellipsoid), 1 (cone), 2 (box)", i, (double)shape);
+    }
+    // MaxStepCount divides the column and bounds both loops (a null df is refused behind the shared checks)
+    if (df && !(df->StepAndMisc2.x >= 1.0f && df->StepAndMisc2.x <= 4096.0f))
+        return fail(ILM_ERR_INVALID_ARGUMENT, "volumetric lights: MaxStepCount %g is not in [1, 4096]", (double)df->StepAndMisc2.x);
+    // (the ramp stays empty: the ramp and projector-texture bindings are neither read nor touched)
+    return render_full_frame_lights(c, lights, light_count, env, df, hgbuffer, hsdf, ambient, hlightmap, row_begin, row_end, stats, light_count, 0,
+                                    RampView{ nullptr, 0, 0 }, launch_prepare_volumetric_lights, launch_volumetric_lights_prepared);
 }
 
 }  // extern "C"

@@ -251,6 +251,11 @@ hipError_t launch_projector_lights_prepared(const LightLaunch& a, const void* re
 // The ramp is not read (the reference has no LineLightWithRamp).
 hipError_t launch_prepare_line_lights(const IlmLightVertex* lights, int count, const IlmDistanceFieldUniforms& df, void* recs, hipStream_t stream);
 hipError_t launch_line_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream);
+// Volumetric lights (VolumetricLight.fx, ShadowedVolumetricLight.fx): the records (count * kLightRecBytes) and the pass over a's rows, in the
+// directional pass's frame with its footprint test.  Neither the ramp nor the field uniforms are read by the preparation.
+hipError_t launch_prepare_volumetric_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
+                                            void* recs, hipStream_t stream);
+hipError_t launch_volumetric_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream);
 int light_launch_blocks(const LightLaunch& a);    // workgroups of the tile kernel's launch for a (split / taper included)
 int light_block_slots(const LightLaunch& a);      // block slots per XCD of the tile kernel's launch over a's rows
 

@@ -1246,12 +1246,12 @@ hipError_t launch_sphere_lights_prepared(const LightLaunch& launch, const void* 
 }
 
 // ---------------------------------------------------------------------------------------------
-// The full-frame light passes (directional, projector, line) -- one thread per pixel, one wave per 8 x 8 pixels, a wave-uniform loop
-// over the prepared records (uniform index: scalar loads), the G-buffer texel decoded once, the sum in registers, the lightmap texel
-// read at most once (accumulate mode) and stored once.  Shared by the three kernels: the store with its mirrors, the statistics and
+// The full-frame light passes (directional, projector, line, volumetric) -- one thread per pixel, one wave per 8 x 8 pixels, a wave-uniform
+// loop over the prepared records (uniform index: scalar loads), the G-buffer texel decoded once, the sum in registers, the lightmap texel
+// read at most once (accumulate mode) and stored once.  Shared by the four kernels: the store with its mirrors, the statistics and
 // the launcher.  Each kernel states its own pixel mapping, base value, blend chains and light loop: as device functions these change
-// the instruction streams of all three kernels, and the passes then run up to 3 % slower (docs/experiments.md 7.24).  A change to
-// one of those parts is made in directional_lights_kernel, projector_lights_kernel and line_lights_kernel alike.
+// the instruction streams of the kernels, and the passes then run up to 3 % slower (docs/experiments.md 7.24).  A change to one of
+// those parts is made in directional_lights_kernel, projector_lights_kernel, line_lights_kernel and volumetric_lights_kernel alike.
 // ---------------------------------------------------------------------------------------------
 // the texel into the lightmap and into every mirror (store-mode exchange of a group lightmap, as the sphere pass)
 ILM_DEV void store_light_texel(const LightLaunch& a, size_t o, const float4& v) {
@@ -2054,6 +2054,346 @@ hipError_t launch_prepare_line_lights(const IlmLightVertex* lights, int count, c
 hipError_t launch_line_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
     return launch_full_frame_lights<LineRec>(a, recs, stream, line_lights_kernel<ILM_SDF_FP16, false>, line_lights_kernel<ILM_SDF_FP16, true>,
                                            line_lights_kernel<ILM_SDF_UNORM16, false>, line_lights_kernel<ILM_SDF_UNORM16, true>);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Volumetric lights -- techniques VolumetricLight / ShadowedVolumetricLight (VolumetricLight.fx:7-51, ShadowedVolumetricLight.fx:7-52) over
+// VolumetricLightCore.fxh:25-88,281-298,315-549, drawn by RenderVolumetricLightSource (LightingRenderer.cs:1339-1384) as one quad per light
+// over the bounding rectangle of its shape.  The full-frame passes' frame with the directional pass's footprint test.  New here: per pair a
+// column of up to MaxStepCount + 1 points through the shape (volumetricTrace), each of which evaluates the shape's distance function and --
+// for a light that casts shadows -- marches the field towards the light with up to MaxStepCount samples; then a contact term at the shaded
+// point.  The shape is uniform per light (a scalar branch around three copies of the column loop, never a test per sample); the column's trip
+// count is nearly uniform over a wave, the march's is not and stays a plain per-lane loop.  `intersect` (:300-313) returns true on its
+// second line, so the early-out never fires: the five ray / shape intersections, sdCappedCone and sdCapsule are dead code and not built.
+// ---------------------------------------------------------------------------------------------
+constexpr float kVolumetricDitherScale = 0.66f;             // VolumetricLightCore.fxh:361
+constexpr float kVolumetricStepScale = 0.99f;               // :361
+constexpr float kVolumetricHit = -0.1f;                     // :388
+constexpr float kVolumetricProjectThreshold = 0.01f;        // :327
+constexpr float kVolumetricConeDot = 0.33f;                 // :469,476
+constexpr float kVolumetricBoxFloor = 0.0001f;              // :87
+constexpr int kVolumetricLoopGuard = 4;                     // the column loop runs at most (int)MaxStepCount + 4 times (illuminant_hip.h)
+constexpr int kVolumetricShapeMask = 3, kVolumetricProject = 4, kVolumetricCasts = 8, kVolumetricCastsUnshadowed = 16;
+
+// 32 floats: what the record cannot hold is made per pair from what it does hold, with the roundings of the definition -- the cone's
+// rr = r1 - r2, the dot constants (one value: DOT_OFFSET == DOT_RAMP_RANGE) and the march direction trace / md (three divisions, "traceAlong /=
+// md" as written).  fullLength is md: the same operations on the same values (:339,343 and :465-467).
+struct VolumetricRec {
+    float x0, y0, x1, y1;                                       // footprint in screen pixels: centre in [x0, x1) x [y0, y1)
+    float sx, sy, sz; int flags;                                // LightPosition1.xyz; shape | project from the origin | casts (w * 1 != 0, w * 0 != 0)
+    float z_hi, z_lo, md, full_att;                             // the shape's z extent (:335-344); defaultTraceDistance; fullLength * DistanceAttenuation
+    float tx, ty, tz, volumetricity;                            // traceAlong = rayNormal * defaultTraceDistance (:372); LightProperties.x
+    float ramp_length, ramp_power, blowout, ao_radius;          // LightProperties.y, EvenMoreLightProperties.yx, MoreLightProperties.x
+    float ao_opacity, col_r, col_g, col_b;                      // MoreLightProperties.w; Color1.rgb * Color1.a
+    float u[8];                                                 // cone: ba, l2, a2, il2, r1, r2; ellipsoid: r, r * r; box: b
+};
+static_assert(sizeof(VolumetricRec) == kLightRecBytes, "a volumetric record fills the slot of a LightRec (reserve_light_recs)");
+
+// VolumetricLightVertexShader (VolumetricLightCore.fxh:510-549) at the quad's two extreme corners, and what volumetricTrace, eval and the
+// contact term compute from the light alone.  Shape is 0, 1 or 2 (ilm_render_volumetric_lights refuses every other value).
+__global__ __launch_bounds__(64) void prepare_volumetric_lights_kernel(const IlmLightVertex* __restrict__ lights, int count, IlmEnvironment env,
+                                                                        VolumetricRec* __restrict__ out) {
+    const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (i >= count) return;
+    const IlmLightVertex L = lights[i];
+    VolumetricRec r = {};
+    const int shape = (int)L.EvenMoreLightProperties.w;
+    const f3 s = mk3(L.LightPosition1.x, L.LightPosition1.y, L.LightPosition1.z), e = mk3(L.LightPosition2.x, L.LightPosition2.y, L.LightPosition2.z);
+    const float r1 = L.LightPosition1.w, r2 = L.LightPosition2.w;
+    float p1x, p1y, p2x, p2y;
+    if (shape == 1) {
+        const float m = fmaxf(r1, r2);
+        p1x = fminf(s.x, e.x) - m; p1y = fminf(s.y, e.y) - m;
+        p2x = fmaxf(s.x, e.x) + m; p2y = fmaxf(s.y, e.y) + m;
+        r.z_hi = fmaxf(s.z, e.z) + m; r.z_lo = fminf(s.z, e.z) - m;
+        r.md = len3(e - s);
+        const f3 ba = e - s;
+        const float l2 = dot3(ba, ba), rr = r1 - r2;
+        r.u[0] = ba.x; r.u[1] = ba.y; r.u[2] = ba.z; r.u[3] = l2; r.u[4] = l2 - rr * rr; r.u[5] = 1.0f / l2; r.u[6] = r1; r.u[7] = r2;
+    } else {
+        p1x = s.x - e.x; p1y = s.y - e.y;
+        p2x = s.x + e.x; p2y = s.y + e.y;
+        r.z_hi = s.z + e.z; r.z_lo = s.z - e.z;
+        r.md = len3(e);
+        r.u[0] = e.x; r.u[1] = e.y; r.u[2] = e.z;
+        if (shape == 0) { r.u[3] = e.x * e.x; r.u[4] = e.y * e.y; r.u[5] = e.z * e.z; }
+    }
+    const float scale_x = env.GBufferTexelSizeAndMisc.z * env.ZAndScale.z, scale_y = env.GBufferTexelSizeAndMisc.w * env.ZAndScale.w;
+    r.x0 = (fminf(p1x, p2x) - env.ViewportPosition[0]) * scale_x; r.y0 = (fminf(p1y, p2y) - env.ViewportPosition[1]) * scale_y;
+    r.x1 = (fmaxf(p1x, p2x) - env.ViewportPosition[0]) * scale_x; r.y1 = (fmaxf(p1y, p2y) - env.ViewportPosition[1]) * scale_y;
+    // (fminf / fmaxf return the operand that is not a NaN: a rectangle keeps a NaN only where both candidates of a bound are NaN)
+    r.sx = s.x; r.sy = s.y; r.sz = s.z;
+    const f3 ray = mk3(L.LightPosition3.x, L.LightPosition3.y, L.LightPosition3.z);
+    const float w = L.LightProperties.w;
+    r.flags = shape | ((len3(ray) < kVolumetricProjectThreshold) ? kVolumetricProject : 0) | ((w * 1.0f != 0.0f) ? kVolumetricCasts : 0) |
+              ((w * 0.0f != 0.0f) ? kVolumetricCastsUnshadowed : 0);
+    r.full_att = r.md * L.EvenMoreLightProperties.z;
+    r.tx = ray.x * r.md; r.ty = ray.y * r.md; r.tz = ray.z * r.md;
+    r.volumetricity = L.LightProperties.x; r.ramp_length = L.LightProperties.y;
+    r.ramp_power = L.EvenMoreLightProperties.y; r.blowout = L.EvenMoreLightProperties.x;
+    r.ao_radius = L.MoreLightProperties.x; r.ao_opacity = L.MoreLightProperties.w;
+    r.col_r = L.Color1.x * L.Color1.w; r.col_g = L.Color1.y * L.Color1.w; r.col_b = L.Color1.z * L.Color1.w;
+    out[i] = r;
+}
+
+// Dither17 (Fracture's DitherCommon.fxh, outside the reference tree; Jimenez: frac(dot(float3(pos, frame), float3(2, 7, 23) / 17))) as a
+// DEFINED function at frame value 0.5 (FrameIndex stays at its default 0): k = 2 x + 7 y + 11.5 is exact, k mod 17 = ((2 x + 7 y + 11) mod 17)
+// + 0.5 is exact, and the result is that value / 17 -- one IEEE division.
+ILM_DEV float dither17(int px, int py) {
+    return ((float)((2 * px + 7 * py + 11) % 17) + 0.5f) / 17.0f;
+}
+
+// eval (VolumetricLightCore.fxh:281-298) along one pixel's column: x and y of the position are the shaded point's for every point of
+// volumetricTrace and for the contact term, so what depends on them alone is made once per pair -- the leading terms of the sums stay the
+// leading terms (dot = (x + y) + z), no rounding changes.
+struct EllipsoidColumn {        // sdEllipsoid, :25-29
+    float k0xy, k1xy, cz, rz, rrz;
+    ILM_DEV EllipsoidColumn(const f3& p, const VolumetricRec& L) {
+        const float ax = (p.x - L.sx) / L.u[0], ay = (p.y - L.sy) / L.u[1], bx = (p.x - L.sx) / L.u[3], by = (p.y - L.sy) / L.u[4];
+        k0xy = ax * ax + ay * ay; k1xy = bx * bx + by * by; cz = L.sz; rz = L.u[2]; rrz = L.u[5];
+    }
+    ILM_DEV float operator()(float z) const {
+        const float az = (z - cz) / rz, bz = (z - cz) / rrz;
+        const float k0 = sqrtf(k0xy + az * az), k1 = sqrtf(k1xy + bz * bz);
+        return k0 * (k0 - 1.0f) / k1;
+    }
+};
+struct ConeColumn {             // sdRoundCone, :31-54
+    float pax, pay, yxy, az, bax, bay, baz, l2, rr, a2, il2, r1, r2;
+    ILM_DEV ConeColumn(const f3& p, const VolumetricRec& L) {
+        pax = p.x - L.sx; pay = p.y - L.sy; az = L.sz; bax = L.u[0]; bay = L.u[1]; baz = L.u[2]; l2 = L.u[3]; a2 = L.u[4]; il2 = L.u[5];
+        r1 = L.u[6]; r2 = L.u[7]; rr = r1 - r2;
+        yxy = pax * bax + pay * bay;
+    }
+    ILM_DEV float operator()(float pz) const {
+        const float paz = pz - az;
+        const float y = yxy + paz * baz;
+        const float z = y - l2;
+        const float vx = pax * l2 - bax * y, vy = pay * l2 - bay * y, vz = paz * l2 - baz * y;
+        const float x2 = (vx * vx + vy * vy) + vz * vz;
+        const float y2 = y * y * l2, z2 = z * z * l2;
+        const float k = sgn(rr) * rr * rr * x2;
+        if (sgn(z) * a2 * z2 > k) return sqrtf(x2 + z2) * il2 - r2;
+        if (sgn(y) * a2 * y2 < k) return sqrtf(x2 + y2) * il2 - r1;
+        return (sqrtf(x2 * a2 * il2) + y * rr) * il2 - r1;
+    }
+};
+struct BoxColumn {              // sdBox, :85-88
+    float lxy, mxy, cz, bz;
+    ILM_DEV BoxColumn(const f3& p, const VolumetricRec& L) {
+        const float dx = fabsf(p.x - L.sx) - L.u[0], dy = fabsf(p.y - L.sy) - L.u[1];
+        const float ex = fmaxf(dx, kVolumetricBoxFloor), ey = fmaxf(dy, kVolumetricBoxFloor);
+        lxy = ex * ex + ey * ey; mxy = fmaxf(dx, dy); cz = L.sz; bz = L.u[2];
+    }
+    ILM_DEV float operator()(float z) const {
+        const float dz = fabsf(z - cz) - bz, ez = fmaxf(dz, kVolumetricBoxFloor);
+        return sqrtf(lxy + ez * ez) + fminf(fmaxf(mxy, dz), kVolumetricBoxFloor);
+    }
+};
+
+// volumetricTrace (VolumetricLightCore.fxh:315-409) for one pair.  `march`: traceShadows with a bound field (without one occlusion = 1 and
+// nothing is sampled).  The body always runs once; z -= step stops making progress once step falls below an ulp of z, so the loop is also
+// bounded by an integer: (int)steps + 4 bodies (with a valid MaxStepCount the arithmetic ends it after at most steps + 1).  A NaN z ends it:
+// the comparison is false.
+template <int FMT, bool STATS, class Column>
+ILM_DEV float volumetric_trace(const Column& eval, const Pixel& P, const VolumetricRec& L, const TraceField& F, bool march, float dither, float ground_z,
+                               float maximum_z, LightStats& st) {
+    const float steps = F.df.StepAndMisc2.x, min_step = F.df.Packed1.w;
+    float z2 = fmaxf(P.shaded.z, ground_z), z1 = fmaxf(maximum_z, z2);
+    z1 = fminf(z1, L.z_hi);
+    z2 = fmaxf(z2, L.z_lo);
+    const float step = fmaxf(fabsf(z2 - z1), 1.0f) / steps;
+    float z = z1 + (dither * step);
+    float hits = 0.0f;
+    const int trace_steps = (int)steps;
+    int guard = trace_steps + kVolumetricLoopGuard;
+    const bool project = (L.flags & kVolumetricProject) != 0;
+    const f3 origin = mk3(L.sx, L.sy, L.sz), trace = mk3(L.tx, L.ty, L.tz);
+    f3 fixed_along = mk3(0.0f, 0.0f, 0.0f);
+    if (march && !project)
+        fixed_along = mk3(trace.x / L.md, trace.y / L.md, trace.z / L.md);
+    do {
+        const float sd = eval(z);
+        float occlusion = 1.0f;
+        if (march) {
+            const f3 pos = mk3(P.shaded.x, P.shaded.y, z);
+            f3 from, along;
+            float md;
+            if (project) {
+                along = pos - origin;
+                from = origin;
+                md = len3(along);
+                along = mk3(along.x / md, along.y / md, along.z / md);
+            } else {
+                from = pos - trace;
+                along = fixed_along;
+                md = L.md;
+            }
+            // (the sampler treats a NaN coordinate as 0: hoisted as in shade_directional)
+            if ((from.x != from.x) || (along.x != along.x)) { from.x = 0.0f; along.x = 0.0f; }
+            if ((from.y != from.y) || (along.y != along.y)) { from.y = 0.0f; along.y = 0.0f; }
+            if ((from.z != from.z) || (along.z != along.z)) { from.z = 0.0f; along.z = 0.0f; }
+            float d = dither * kVolumetricDitherScale;
+            int remaining = trace_steps;
+            while (remaining > 0) {
+                const f3 sp = mk3(__builtin_fmaf(along.x, d, from.x), __builtin_fmaf(along.y, d, from.y), __builtin_fmaf(along.z, d, from.z));
+                const float s = sample_distance_field<FMT, false>(sp, F.df, F.sdf);
+                if (STATS) st.samples++;
+                occlusion = sat(s * 0.5f);
+                if (s <= kVolumetricHit) { remaining = 0; occlusion = 0.0f; }
+                d += fmaxf(fabsf(s) * kVolumetricStepScale, min_step);
+                if (d >= md) remaining = 0; else remaining--;
+            }
+        }
+        const float ramp = pow_pos(sat(-sd / L.ramp_length), L.ramp_power);
+        hits += ramp * occlusion;
+        z -= step;
+    } while ((z >= z2) && (--guard > 0));
+    return sat(hits / steps / L.volumetricity);
+}
+
+// One volumetric light on one shaded point inside its footprint: the two pixel shaders over VolumetricLightPixelCore (:411-508).  Returns
+// false when the shader discards (fullbright; not visible: the core returns 0; opacity <= 0); otherwise the opacity that multiplies
+// color.rgb * color.a.  The RampMode >= 1 squaring of distanceOpacity (:495-498) follows the last read of it and is not computed.
+template <int FMT, bool STATS>
+ILM_DEV bool shade_volumetric(const Pixel& P, int px, int py, const VolumetricRec& L, const TraceField& F, bool have_sdf, float ground_z, float maximum_z,
+                              LightStats& st, float& opacity) {
+    if (P.fullbright)
+        return false;
+    if (!(P.shaded.x > -9999.0f))
+        return false;
+    // computeAO, AOCommon.fxh:1-19 (aoRadius scaled by max(0, normal.z), :448)
+    float ao_opacity = 1.0f;
+    const float ao_radius = L.ao_radius * fmaxf(0.0f, P.normal.z);
+    if ((ao_radius >= 0.5f) && have_sdf) {
+        const float distance = sample_distance_field<FMT>(mk3(P.shaded.x, P.shaded.y, P.shaded.z + P.normal.z * ao_radius), F.df, F.sdf);
+        if (STATS) st.samples++;
+        float r = 1.0f - sat(clampf(distance, 0.0f, ao_radius) / ao_radius);
+        r *= r;
+        r = 1.0f - r;
+        ao_opacity = (1.0f - L.ao_opacity) + (r * L.ao_opacity);
+    }
+    // traceShadows = (lightProperties.w * enableShadows != 0) && Extent.z > 0 (:451; VolumetricLight.fx passes w = 0)
+    const bool casts = (L.flags & (P.enable_shadows ? kVolumetricCasts : kVolumetricCastsUnshadowed)) != 0;
+    const bool march = casts && (F.df.Extent.z > 0.0f) && have_sdf;
+    if (STATS && march) st.traced++;
+    const float dither = dither17(px, py);
+    const int shape = L.flags & kVolumetricShapeMask;
+    float volumetric_opacity, contact_distance, cone_dot = 0.0f;
+    if (shape == 0) {
+        const EllipsoidColumn eval(P.shaded, L);
+        volumetric_opacity = volumetric_trace<FMT, STATS>(eval, P, L, F, march, dither, ground_z, maximum_z, st);
+        contact_distance = eval(P.shaded.z);
+    } else if (shape == 1) {
+        const ConeColumn eval(P.shaded, L);
+        volumetric_opacity = volumetric_trace<FMT, STATS>(eval, P, L, F, march, dither, ground_z, maximum_z, st);
+        contact_distance = eval(P.shaded.z);
+        cone_dot = fmaxf(L.u[6], L.u[7]) / 64.0f;
+    } else {
+        const BoxColumn eval(P.shaded, L);
+        volumetric_opacity = volumetric_trace<FMT, STATS>(eval, P, L, F, march, dither, ground_z, maximum_z, st);
+        contact_distance = eval(P.shaded.z);
+    }
+    const float pre_trace = ao_opacity * volumetric_opacity;
+    // the contact term, :464-507
+    const float dot_range = lerp(ref::kDotRampRange, kVolumetricConeDot, cone_dot), dot_offset = lerp(ref::kDotOffset, kVolumetricConeDot, cone_dot);
+    const f3 to_point = P.shaded - mk3(L.sx, L.sy, L.sz);
+    const float distance = len3(to_point);
+    float normal_opacity = 1.0f;
+    if ((P.normal.x != 0.0f) || (P.normal.y != 0.0f) || (P.normal.z != 0.0f)) {
+        const f3 light_normal = mk3(to_point.x / distance, to_point.y / distance, to_point.z / distance);
+        const float d = dot3(light_normal * -1.0f, P.normal);
+        normal_opacity = pow_pos(sat((d + dot_offset) / dot_range), ref::kDotExponent);
+    }
+    normal_opacity = lerp(normal_opacity, normal_opacity * 2.0f - 1.0f, L.blowout);
+    const float shape_opacity = (contact_distance < 0.0f) ? pow_pos(sat(-contact_distance / L.ramp_length), L.ramp_power) : 0.0f;
+    const float distance_opacity = 1.0f - sat(distance / L.full_att);
+    const float diffuse = normal_opacity * shape_opacity * distance_opacity;
+    opacity = (diffuse < 0.0f) ? (pre_trace + diffuse) : fmaxf(pre_trace, diffuse);
+    return !(opacity <= 0.0f);
+}
+
+// (pixel mapping, base value, blend chains and footprint test as in directional_lights_kernel: see the note at the head of the full-frame
+// passes.)
+template <int FMT, bool STATS>
+__global__ __launch_bounds__(kLightThreads) void volumetric_lights_kernel(const LightLaunch a, const VolumetricRec* __restrict__ recs, int tiles_x) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int tile_x = (int)blockIdx.x % tiles_x, tile_y = (int)blockIdx.x / tiles_x;
+    const int px = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
+    const int py = a.row_begin + tile_y * kTile + (wave >> 1) * 8 + (lane >> 3);
+    const bool in_image = (px < a.width) && (py < a.row_end);
+    if (__builtin_amdgcn_ballot_w64(in_image) == 0ull)
+        return;
+    Pixel P = sample_gbuffer((float)px, (float)py, a.env, a.gbuffer);
+    P.origin_x = 0; P.origin_y = 0; P.start_inside = false;
+    const float cxp = (float)px + 0.5f, cyp = (float)py + 0.5f;
+    const bool have_sdf = (a.sdf.texels != nullptr) && (a.df.Extent.x > 0.0f);
+    const InsideConsts no_table = {};
+    const TraceField field = { a.df, a.sdf, no_table, nullptr };
+    const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
+    auto through_half = [](float v) { return __half2float(__float2half_rn(v)); };
+    auto base_value = [&]() -> float4 {
+        float4 v = mk4(a.ambient[0], a.ambient[1], a.ambient[2], a.ambient[3]);
+        if (a.accumulate != 0 && in_image) {
+            if (a.format == ILM_LIGHTMAP_FLOAT4) v = load_target<ILM_LIGHTMAP_FLOAT4>(a.lightmap, o);
+            else if (a.format == ILM_LIGHTMAP_HALF4) v = load_target<ILM_LIGHTMAP_HALF4>(a.lightmap, o);
+            else v = load_target<ILM_LIGHTMAP_RGBA8>(a.lightmap, o);
+        }
+        if (a.blend_fp16 != 0) v = mk4(through_half(v.x), through_half(v.y), through_half(v.z), through_half(v.w));
+        return v;
+    };
+    const bool blend_fp16 = a.blend_fp16 != 0;
+    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if (blend_fp16) { const float4 v = base_value(); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
+    LightStats st;
+    const int light_count = a.light_count;
+    const float ground_z = a.env.ZAndScale.x, maximum_z = a.env.ZAndScale.y;
+    for (int k = 0; k < light_count; k++) {
+        const VolumetricRec& L = recs[k];
+        const float x0 = L.x0, y0 = L.y0, x1 = L.x1, y1 = L.y1;
+        const bool covered = in_image & (cxp >= x0) & (cxp < x1) & (cyp >= y0) & (cyp < y1);
+        if (__builtin_amdgcn_ballot_w64(covered) == 0ull)
+            continue;
+        if (!covered)
+            continue;
+        if (STATS) st.pairs++;
+        float opacity;
+        if (!shade_volumetric<FMT, STATS>(P, px, py, L, field, have_sdf, ground_z, maximum_z, st, opacity))
+            continue;
+        const float cr = L.col_r * opacity, cg = L.col_g * opacity, cb = L.col_b * opacity;
+        if (blend_fp16) {
+            acc_r = through_half(acc_r + through_half(cr));
+            acc_g = through_half(acc_g + through_half(cg));
+            acc_b = through_half(acc_b + through_half(cb));
+            acc_a = through_half(acc_a + 1.0f);
+        } else {
+            acc_r += cr; acc_g += cg; acc_b += cb; acc_a += 1.0f;
+        }
+    }
+    if (!blend_fp16) {
+        const float4 v = base_value();
+        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+    }
+    if (in_image) {
+        const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
+        store_light_texel(a, o, v);
+    }
+    if (STATS) add_light_stats(st, a.stats, lane);
+}
+
+hipError_t launch_prepare_volumetric_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
+                                            void* recs, hipStream_t stream) {
+    if (count <= 0) return hipSuccess;
+    (void)df;
+    hipLaunchKernelGGL(prepare_volumetric_lights_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, lights, count, env,
+                       reinterpret_cast<VolumetricRec*>(recs));
+    return hipGetLastError();
+}
+
+hipError_t launch_volumetric_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
+    return launch_full_frame_lights<VolumetricRec>(a, recs, stream, volumetric_lights_kernel<ILM_SDF_FP16, false>,
+                                                   volumetric_lights_kernel<ILM_SDF_FP16, true>, volumetric_lights_kernel<ILM_SDF_UNORM16, false>,
+                                                   volumetric_lights_kernel<ILM_SDF_UNORM16, true>);
 }
 
 __global__ __launch_bounds__(256) void divide_probe_kernel(const float* __restrict__ n, const float* __restrict__ d, int count,

@@ -453,6 +453,29 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("TextureRef", &LineLightSource::TextureRef)
         .def_readwrite("Quality", &LineLightSource::Quality)
         .def_readwrite("RampOffset", &LineLightSource::RampOffset).def_readwrite("RampRate", &LineLightSource::RampRate);
+    // Shape: 0 ellipsoid, 1 cone, 2 box (any other int is an unknown shape: not packed); LightDirection: None or (x, y, z)
+    py::class_<VolumetricLightSource>(m, "VolumetricLightSource").def(py::init<>())
+        .def_readwrite("SortKey", &VolumetricLightSource::SortKey).def_readwrite("Enabled", &VolumetricLightSource::Enabled)
+        .def_property("Shape", [](const VolumetricLightSource& l) { return (int)l.Shape; }, [](VolumetricLightSource& l, int v) { l.Shape = (VolumetricLightShape)v; })
+        VEC_PROP(VolumetricLightSource, StartPosition, 3)
+        VEC_PROP(VolumetricLightSource, EndPosition, 3)
+        .def_property("LightDirection", [](const VolumetricLightSource& l) -> py::object { return l.LightDirection ? py::cast(l3(*l.LightDirection)) : py::none(); },
+                      [](VolumetricLightSource& l, py::object v) { if (v.is_none()) l.LightDirection.reset(); else l.LightDirection = v3(v.cast<std::vector<float>>()); })
+        .def_readwrite("StartRadius", &VolumetricLightSource::StartRadius).def_readwrite("EndRadius", &VolumetricLightSource::EndRadius)
+        .def_readwrite("Volumetricity", &VolumetricLightSource::Volumetricity)
+        .def_readwrite("DistanceAttenuation", &VolumetricLightSource::DistanceAttenuation)
+        .def_readwrite("RampLength", &VolumetricLightSource::RampLength).def_readwrite("RampPower", &VolumetricLightSource::RampPower)
+        .def_readwrite("BlowoutFactor", &VolumetricLightSource::BlowoutFactor)
+        .def_property("RampMode", [](const VolumetricLightSource& l) { return (int)l.RampMode; }, [](VolumetricLightSource& l, int v) { l.RampMode = (LightSourceRampMode)v; })
+        VEC_PROP(VolumetricLightSource, Color, 4)
+        .def_readwrite("Opacity", &VolumetricLightSource::Opacity)
+        .def_readwrite("CastsShadows", &VolumetricLightSource::CastsShadows)
+        .def_readwrite("AmbientOcclusionRadius", &VolumetricLightSource::AmbientOcclusionRadius)
+        .def_readwrite("AmbientOcclusionOpacity", &VolumetricLightSource::AmbientOcclusionOpacity)
+        .def_readwrite("ShadowDistanceFalloff", &VolumetricLightSource::ShadowDistanceFalloff)
+        .def_readwrite("FalloffYFactor", &VolumetricLightSource::FalloffYFactor)
+        .def_readwrite("TextureRef", &VolumetricLightSource::TextureRef)
+        .def_readwrite("Quality", &VolumetricLightSource::Quality);
     py::class_<ProjectorLightSource>(m, "ProjectorLightSource").def(py::init<>())
         .def_readwrite("SortKey", &ProjectorLightSource::SortKey).def_readwrite("Enabled", &ProjectorLightSource::Enabled)
         .def_property("Transform", [](const ProjectorLightSource& l) { return std::vector<float>(&l.Transform.M[0][0], &l.Transform.M[0][0] + 16); },
@@ -535,6 +558,7 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("DirectionalLights", &LightingEnvironment::DirectionalLights)
         .def_readwrite("ProjectorLights", &LightingEnvironment::ProjectorLights)
         .def_readwrite("LineLights", &LightingEnvironment::LineLights)
+        .def_readwrite("VolumetricLights", &LightingEnvironment::VolumetricLights)
         .def_readwrite("ParticleLights", &LightingEnvironment::ParticleLights)
         .def_property_readonly("Obstructions", [](LightingEnvironment& e) -> LightObstructionCollection& { return e.Obstructions; }, py::return_value_policy::reference_internal)
         .def_readwrite("HeightVolumes", &LightingEnvironment::HeightVolumes)
@@ -735,6 +759,11 @@ PYBIND11_MODULE(_host, m) {
         .def_static("PackLineLightBytes", [](const LineLightSource& l, float intensityScale, bool haveDF) -> py::object {
             IlmLightVertex v;
             if (!LightingRenderer::PackLineLight(l, intensityScale, haveDF, v)) return py::none();
+            return py::bytes((const char*)&v, sizeof(v));
+        })
+        .def_static("PackVolumetricLightBytes", [](const VolumetricLightSource& l, float intensityScale, bool haveDF) -> py::object {
+            IlmLightVertex v;
+            if (!LightingRenderer::PackVolumetricLight(l, intensityScale, haveDF, v)) return py::none();
             return py::bytes((const char*)&v, sizeof(v));
         })
         .def_static("PackProjectorLightBytes", [](const ProjectorLightSource& l, float intensityScale, bool haveDF, float maximumZ, std::vector<float> renderScale,

@@ -1315,6 +1315,38 @@ bool LightingRenderer::PackLineLight(const LineLightSource& l, float intensitySc
     return true;
 }
 
+// RenderVolumetricLightSource, LightingRenderer.cs:1339-1384
+bool LightingRenderer::PackVolumetricLight(const VolumetricLightSource& l, float intensityScale, bool haveDistanceField, IlmLightVertex& v) {
+    if (l.Opacity <= 0.0f)
+        return false;
+    Vector3 start = l.StartPosition, end = l.EndPosition;
+    switch (l.Shape) {
+        case VolumetricLightShape::Ellipsoid:
+        case VolumetricLightShape::Box:
+            // [tl, br] -> [origin, radius]: (end - start).Abs() * 0.5f and (start + end) * 0.5f, :1353-1354
+            end = { std::fabs(l.EndPosition.X - l.StartPosition.X) * 0.5f, std::fabs(l.EndPosition.Y - l.StartPosition.Y) * 0.5f,
+                    std::fabs(l.EndPosition.Z - l.StartPosition.Z) * 0.5f };
+            start = { (l.StartPosition.X + l.EndPosition.X) * 0.5f, (l.StartPosition.Y + l.EndPosition.Y) * 0.5f,
+                      (l.StartPosition.Z + l.EndPosition.Z) * 0.5f };
+            break;
+        case VolumetricLightShape::Cone:
+            break;
+        default:
+            return false;
+    }
+    std::memset(&v, 0, sizeof(v));
+    v.LightPosition1 = { start.X, start.Y, start.Z, l.StartRadius };
+    v.LightPosition2 = { end.X, end.Y, end.Z, l.EndRadius };
+    const Vector3 direction = l.LightDirection.value_or(Vector3{});
+    v.LightPosition3 = { direction.X, direction.Y, direction.Z, 0 };
+    v.Color1 = { l.Color.X, l.Color.Y, l.Color.Z, l.Color.W * (l.Opacity * intensityScale) };
+    v.Color2 = v.Color1;
+    v.LightProperties = { l.Volumetricity, l.RampLength, (float)(int)l.RampMode, (l.CastsShadows && haveDistanceField) ? 1.0f : 0.0f };
+    v.MoreLightProperties = { l.AmbientOcclusionRadius, l.ShadowDistanceFalloff.value_or(-99999.0f), l.FalloffYFactor, l.AmbientOcclusionOpacity };
+    v.EvenMoreLightProperties = { l.BlowoutFactor, l.RampPower, l.DistanceAttenuation, (float)(int)l.Shape };
+    return true;
+}
+
 Matrix Matrix::CreateScale(float x, float y, float z) { Matrix m; m.M[0][0] = x; m.M[1][1] = y; m.M[2][2] = z; return m; }
 Matrix Matrix::CreateTranslation(Vector3 t) { Matrix m; m.M[3][0] = t.X; m.M[3][1] = t.Y; m.M[3][2] = t.Z; return m; }
 Matrix Matrix::CreateFromQuaternion(Vector4 q) {
@@ -1428,7 +1460,7 @@ IlmEnvironment LightingRenderer::GetEnvironmentUniforms() const {
     return e;
 }
 
-// RenderLighting, LightingRenderer.cs:917-1191 (sphere, directional, line, projector and particle lights)
+// RenderLighting, LightingRenderer.cs:917-1191 (sphere, directional, line, projector, volumetric and particle lights)
 void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int rowEnd, IlmRenderStats* stats) {
     if (rowEnd < 0) rowEnd = Configuration.RenderHeight;
     // the probe techniques of directional lights (DirectionalLightProbe*) are not built: refuse rather than leave them out of the probes
@@ -1443,14 +1475,18 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     if (Probes.Count() > 0)
         for (const LineLightSource& ll : Environment->LineLights)
             if (ll.Enabled) throw InvalidOperationException("RenderLighting: line lights do not reach light probes yet");
+    // nor is the volumetric lights' (VolumetricLightProbe.fx)
+    if (Probes.Count() > 0)
+        for (const VolumetricLightSource& vl : Environment->VolumetricLights)
+            if (vl.Enabled) throw InvalidOperationException("RenderLighting: volumetric lights do not reach light probes yet");
     vertices.clear();
     // LightSorter (:2066-2096): SortKey first; blend mode, ramp texture and type are the same for every light of this pass.  The
     // reference's sort is not stable for equal keys; a stable one keeps list order, which is one of its possible outcomes
     // (Lights before Replicators here, since the mirror holds them in two lists).
     // Directional lights sort after spheres of equal key (TypeID 2 after 1, :2094): listed last, the stable sort keeps them there.
-    // Line lights (TypeID 4) likewise, after the directional ones, and projector lights (TypeID 5) after those.
+    // Line lights (TypeID 4) likewise, after the directional ones, projector lights (TypeID 5) after those, volumetric lights (TypeID 6) last.
     struct Entry { int sortKey; const SphereLightSource* sphere; const LightSourceReplicator* replicator; const DirectionalLightSource* directional;
-                   const ProjectorLightSource* projector; const LineLightSource* line; };
+                   const ProjectorLightSource* projector; const LineLightSource* line; const VolumetricLightSource* volumetric = nullptr; };
     std::vector<Entry> sorted;
     for (const SphereLightSource& l : Environment->Lights)
         if (l.Enabled) sorted.push_back({ l.SortKey, &l, nullptr, nullptr, nullptr, nullptr });
@@ -1462,6 +1498,8 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
         if (ll.Enabled) sorted.push_back({ ll.SortKey, nullptr, nullptr, nullptr, nullptr, &ll });
     for (const ProjectorLightSource& pl : Environment->ProjectorLights)
         if (pl.Enabled) sorted.push_back({ pl.SortKey, nullptr, nullptr, nullptr, &pl, nullptr });
+    for (const VolumetricLightSource& vl : Environment->VolumetricLights)
+        if (vl.Enabled) sorted.push_back({ vl.SortKey, nullptr, nullptr, nullptr, nullptr, nullptr, &vl });
     std::stable_sort(sorted.begin(), sorted.end(), [](const Entry& x, const Entry& y) { return x.sortKey < y.sortKey; });
     // GetLightRenderState (:799-845): lights that share a ramp texture and quality settings form one render state (BlendState is
     // additive for every light here); the states are drawn one after the other onto the same target, in the order their keys first appear.
@@ -1493,8 +1531,23 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     projectorKeys.clear();
     projectorQuality.clear();
     projectorGroups.clear();
+    // Volumetric lights: the reference draws two render states per (texture, quality) key, ShadowedVolumetricLight and VolumetricLight,
+    // selected by CastsShadows (:190-193).  The two techniques differ only in LightProperties.w, which the vertex carries, so ONE call
+    // serves the shadowed and the unshadowed lights of a key in list order: what a light adds to a pixel depends on no other light, the
+    // lights of each state keep their order within the call, and the blend is an addition -- the states' sums are the same terms.  (In the
+    // fp32 model the sum of a call is rounded in list order, where two calls would round state by state: sums of the same terms.)
+    volumetricKeys.clear();
+    volumetricQuality.clear();
+    volumetricGroups.clear();
     for (const Entry& e : sorted) {
         IlmLightVertex v;
+        if (e.volumetric) {
+            if (!PackVolumetricLight(*e.volumetric, intensityScale, Field != nullptr, v))
+                continue;
+            volumetricGroups[stateFor(e.volumetric->TextureRef, e.volumetric->Quality.get(), volumetricKeys, volumetricQuality, volumetricGroups)].push_back(v);
+            vertices.push_back(v);
+            continue;
+        }
         if (e.projector) {
             if (!PackProjectorLight(*e.projector, intensityScale, Field != nullptr, Environment->MaximumZ, Configuration.RenderScale,
                                     Configuration.ProjectorMipBias, v))
@@ -1557,7 +1610,7 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     // clear colour: Ambient * intensityScale (:1013-1024)
     const float ambient[4] = { Environment->Ambient.X * intensityScale, Environment->Ambient.Y * intensityScale,
                                Environment->Ambient.Z * intensityScale, Environment->Ambient.W * intensityScale };
-    // no lights: the clear still happens (with directional lights alone, their first launch carries it; line and projector groups always add)
+    // no lights: the clear still happens (with directional lights alone, their first launch carries it; line, projector and volumetric groups always add)
     if (groups.empty() && directionalGroups.empty()) { groupKeys.push_back(nullptr); groupQuality.push_back(nullptr); groups.emplace_back(); }
     if (stats) { stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0; }
     for (size_t g = 0; g < groups.size(); g++) {
@@ -1597,6 +1650,14 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
         if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
     }
     if (!projectorGroups.empty()) ThrowIfFailed(ilm_ctx_set_projector_texture(Context.Handle(), nullptr, 0, 0));
+    // the volumetric render states, last: no ramp technique, neither binding is read
+    for (size_t g = 0; g < volumetricGroups.size(); g++) {
+        IlmRenderStats gs{};
+        const IlmDistanceFieldUniforms gdfu = volumetricQuality[g] ? GetDistanceFieldUniforms(*volumetricQuality[g]) : dfu;
+        ThrowIfFailed(ilm_render_volumetric_lights(Context.Handle(), volumetricGroups[g].data(), (int32_t)volumetricGroups[g].size(), &env, &gdfu, gbuffer,
+                                                   Field ? Field->Texture() : 0, nullptr, lightmap, rowBegin, rowEnd, stats ? &gs : nullptr));
+        if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
+    }
     BindRamp(nullptr);         // particle lights have no ramp technique (:176-178)
     // particle light sources: one more light-type render state each, blended on top (:1126-1141)
     for (const ParticleLightSource& pls : Environment->ParticleLights) {

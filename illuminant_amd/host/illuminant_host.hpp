@@ -756,6 +756,28 @@ struct LineLightSource {
     float RampOffset = 0, RampRate = 1;           // RampOffsetAndRate, LightSource.cs:90 (packed, not read by the shader)
 };
 
+// VolumetricLightShape and VolumetricLightSource, LightSource.cs:372-455 with its defaults (+ the LightSource members
+// RenderVolumetricLightSource reads, LightingRenderer.cs:1339-1384)
+enum class VolumetricLightShape { Ellipsoid = 0, Cone = 1, Box = 2 };
+struct VolumetricLightSource {
+    int SortKey = 0;
+    bool Enabled = true;
+    VolumetricLightShape Shape = VolumetricLightShape::Cone;
+    Vector3 StartPosition, EndPosition;           // cone: its two ends; ellipsoid and box: two corners of the bounds
+    std::optional<Vector3> LightDirection;        // unset: the light travels from StartPosition towards the point being lit
+    float StartRadius = 0, EndRadius = 0;
+    float Volumetricity = 1, DistanceAttenuation = 1, RampLength = 1, RampPower = 1, BlowoutFactor = 0;
+    LightSourceRampMode RampMode = LightSourceRampMode::Linear;
+    Vector4 Color{1, 1, 1, 1};
+    float Opacity = 1;
+    bool CastsShadows = true;
+    float AmbientOcclusionRadius = 0, AmbientOcclusionOpacity = 1;
+    std::optional<float> ShadowDistanceFalloff;
+    float FalloffYFactor = 1;
+    std::shared_ptr<RampTexture> TextureRef;      // part of the render state's key; the techniques have no ramp
+    std::shared_ptr<RendererQualitySettings> Quality;
+};
+
 // Matrix / Quaternion (XNA: row vectors, M[r][c] = M(r+1)(c+1)) with the operations RenderProjectorLightSource uses, each in fp32 with
 // one rounding per operation in the order the XNA / MonoGame sources write them
 struct Matrix {
@@ -894,6 +916,7 @@ struct LightingEnvironment {
     std::vector<DirectionalLightSource> DirectionalLights;   // DirectionalLightSource entries of Lights in the reference
     std::vector<ProjectorLightSource> ProjectorLights;       // ProjectorLightSource entries of Lights in the reference
     std::vector<LineLightSource> LineLights;                 // LineLightSource entries of Lights in the reference
+    std::vector<VolumetricLightSource> VolumetricLights;     // VolumetricLightSource entries of Lights in the reference
     std::vector<ParticleLightSource> ParticleLights;   // ParticleLightSource entries of Lights in the reference (one render state each)
     LightObstructionCollection Obstructions;
     std::vector<HeightVolume> HeightVolumes;
@@ -1013,6 +1036,8 @@ public:
     static bool PackDirectionalLight(const DirectionalLightSource& l, float intensityScale, IlmLightVertex& v);
     // RenderLineLightSource, :1309-1337: false for Opacity <= 0 (:1311)
     static bool PackLineLight(const LineLightSource& l, float intensityScale, bool haveDistanceField, IlmLightVertex& v);
+    // RenderVolumetricLightSource, :1339-1384: false for Opacity <= 0 (:1341) and for an unknown shape (:1361-1362)
+    static bool PackVolumetricLight(const VolumetricLightSource& l, float intensityScale, bool haveDistanceField, IlmLightVertex& v);
     // RenderProjectorLightSource, :1386-1446: false for a light without a texture (:1389-1391).  maximumZ: Environment.MaximumZ, the
     // depth of a light that sets none; renderScale / mipBias: Configuration.RenderScale / ProjectorMipBias
     static bool PackProjectorLight(const ProjectorLightSource& l, float intensityScale, bool haveDistanceField, float maximumZ, Vector2 renderScale,
@@ -1048,6 +1073,10 @@ private:
     std::vector<const RampTexture*> projectorKeys;
     std::vector<const RendererQualitySettings*> projectorQuality;
     std::vector<std::vector<IlmLightVertex>> projectorGroups;
+    // the volumetric groups, drawn last (LightSourceTypeID.Volumetric = 6 sorts after Projector = 5): one per (ramp texture, quality)
+    std::vector<const RampTexture*> volumetricKeys;
+    std::vector<const RendererQualitySettings*> volumetricQuality;
+    std::vector<std::vector<IlmLightVertex>> volumetricGroups;
     const RampTexture* boundRamp = nullptr;
     float lastInverseScaleFactor = 0;     // RenderedLighting.InverseScaleFactor of the last RenderLighting; 0 = none yet
     void BindRamp(const RampTexture* ramp);

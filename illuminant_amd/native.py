@@ -102,6 +102,7 @@ SYMBOLS = {
     "ilm_render_sphere_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
     "ilm_render_directional_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
     "ilm_render_line_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
+    "ilm_render_volumetric_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
     "ilm_render_projector_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
     "ilm_render_particle_lights": (_I, [_H, _H, _P, _I, _P, _P, _P, _H, _H, _H, _I, _I, _P]),
     "ilm_render_light_probes": (_I, [_H, _P, _I, _P, _P, _I, _P, _P, _H, _P]),
@@ -887,6 +888,12 @@ def render_line_lights(ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, ro
     """ilm_render_line_lights.  lights: ctypes array of abi.LightVertex packed as RenderLineLightSource packs them (or None for zero
     lights); ambient None = add this light group to what the lightmap already holds."""
     return _render_lights(lib().ilm_render_line_lights, ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin, row_end, want_stats)
+
+
+def render_volumetric_lights(ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin=0, row_end=None, want_stats=False):
+    """ilm_render_volumetric_lights.  lights: ctypes array of abi.LightVertex packed as RenderVolumetricLightSource packs them (or None
+    for zero lights), shadowed and unshadowed ones alike; ambient None = add this light group to what the lightmap already holds."""
+    return _render_lights(lib().ilm_render_volumetric_lights, ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin, row_end, want_stats)
 
 
 def set_projector_texture(ctx, texels):

@@ -824,6 +824,37 @@ def line_light(start, end, radius, start_color=(1, 1, 1, 1), end_color=None, opa
     return v
 
 
+VOLUMETRIC_ELLIPSOID, VOLUMETRIC_CONE, VOLUMETRIC_BOX = 0, 1, 2      # VolumetricLightShape, LightSource.cs
+
+
+def volumetric_light(shape=VOLUMETRIC_CONE, start=(0.0, 0.0, 0.0), end=(0.0, 0.0, 0.0), start_radius=0.0, end_radius=0.0, direction=None,
+                     color=(1, 1, 1, 1), opacity=1.0, volumetricity=1.0, ramp_length=1.0, ramp_power=1.0, blowout=0.0,
+                     distance_attenuation=1.0, ramp_mode=0, casts_shadows=True, ao_radius=0.0, ao_opacity=1.0, shadow_distance_falloff=None,
+                     falloff_y=1.0, intensity_scale=1, have_field=True):
+    """RenderVolumetricLightSource, LightingRenderer.cs:1339-1384, from the VolumetricLightSource's members: None for Opacity <= 0
+    (:1341) and for an unknown shape (:1361-1362); for the ellipsoid and the box [start, end] becomes [centre, half-extent] in fp32,
+    (end - start).Abs() * 0.5 and (start + end) * 0.5 (:1353-1354)."""
+    if opacity <= 0:
+        return None
+    f = np.float32
+    s, e = np.asarray(start, np.float32), np.asarray(end, np.float32)
+    if shape in (VOLUMETRIC_ELLIPSOID, VOLUMETRIC_BOX):
+        s, e = ((s + e).astype(f) * f(0.5)).astype(f), (np.abs((e - s).astype(f)) * f(0.5)).astype(f)
+    elif shape != VOLUMETRIC_CONE:
+        return None
+    v = abi.LightVertex()
+    v.LightPosition1 = abi.f4(s[0], s[1], s[2], start_radius)
+    v.LightPosition2 = abi.f4(e[0], e[1], e[2], end_radius)
+    v.LightPosition3 = abi.f4(direction[0], direction[1], direction[2], 0) if direction is not None else abi.f4(0, 0, 0, 0)
+    c = abi.f4(color[0], color[1], color[2], f(color[3]) * (f(opacity) * f(intensity_scale)))
+    v.Color1 = c
+    v.Color2 = c
+    v.LightProperties = abi.f4(volumetricity, ramp_length, float(int(ramp_mode)), 1.0 if (casts_shadows and have_field) else 0.0)
+    v.MoreLightProperties = abi.f4(ao_radius, -99999.0 if shadow_distance_falloff is None else shadow_distance_falloff, falloff_y, ao_opacity)
+    v.EvenMoreLightProperties = abi.f4(blowout, ramp_power, distance_attenuation, float(int(shape)))
+    return v
+
+
 def projector_light(forward, region=(0.0, 0.0, 1.0, 1.0), origin=None, radius=4.0, ramp_length=32.0, ramp_mode=0, casts_shadows=True,
                     have_distance_field=True, ao_radius=0.0, ao_opacity=1.0, opacity=1.0, intensity_scale=1.0, wrap=False, mip_bias=0.0):
     """RenderProjectorLightSource's vertex, LightingRenderer.cs:1422-1442, from the FORWARD matrix (texture space -> world, row vectors:

@@ -34,7 +34,7 @@ extern "C" {
  * removed): + ilm_visualize_distance_field / IlmVisualizeVertex, IlmVisualizeParams, ILM_VISUALIZE_* (distance-field views);
  * + ilm_render_directional_lights (directional lights; no new struct: the reference packs them into a LightVertex);
  * + ilm_ctx_set_projector_texture, ilm_render_projector_lights (projector lights; a LightVertex again);
- * + ilm_render_line_lights (line lights; a LightVertex again).
+ * + ilm_render_line_lights (line lights; a LightVertex again); + ilm_render_volumetric_lights (volumetric lights; likewise).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -932,6 +932,90 @@ int32_t ilm_render_projector_lights(IlmHandle ctx,
                                     const float ambient[4],
                                     IlmHandle lightmap, int32_t row_begin, int32_t row_end,
                                     IlmRenderStats* stats);
+
+/* The volumetric-light pass of LightingRenderer.RenderLighting: techniques VolumetricLight and ShadowedVolumetricLight
+ * (Illuminant/Shaders/VolumetricLight.fx:7-51, ShadowedVolumetricLight.fx:7-52 over VolumetricLightCore.fxh), one quad per light, added
+ * onto the lightmap like every other light type.  The arguments mean what they mean for ilm_render_directional_lights: gbuffer == 0 =>
+ * ground plane, sdf == 0 => no distance field, ambient == NULL => the lights are ADDED to what rows [row_begin, row_end) hold, ambient !=
+ * NULL => every pixel of the rows is cleared to it first (whatever light_count is, 0 included), stats != NULL => the counting variant runs
+ * and the call synchronises.  Any light_count >= 0.  ilm_ctx_set_lightmap_blend applies (both models).  A bound light ramp or projector
+ * texture is neither read nor changed.  One entry point serves both techniques: they differ in LightProperties.w alone (VolumetricLight
+ * sets it to 0, the render-state key selects by CastsShadows, LightingRenderer.cs:190-193), and the vertex's w already carries that.
+ * Vertex layout, as RenderVolumetricLightSource fills it (Illuminant/Lighting/LightingRenderer.cs:1339-1384):
+ *   LightPosition1 / LightPosition2         (start, StartRadius) / (end, EndRadius); for Shape 0 and 2 the host has already turned
+ *                                           [start, end] into [centre, half-extent]
+ *   LightPosition3.xyz                      LightDirection, or 0
+ *   Color1                                  Color, alpha already multiplied by Opacity * intensityScale (Color2 is the same; not read)
+ *   LightProperties                         Volumetricity, RampLength, RampMode, casts && field ? 1 : 0
+ *   MoreLightProperties                     AmbientOcclusionRadius, ShadowDistanceFalloff or -99999, FalloffYFactor,
+ *                                           AmbientOcclusionOpacity; .y and .z are not read
+ *   EvenMoreLightProperties                 BlowoutFactor, RampPower, DistanceAttenuation, Shape (0 ellipsoid, 1 cone, 2 box)
+ * Shape must be exactly 0, 1 or 2 -- the shader's `<=`, `(float) ==` and `(int) ==` tests agree only there; anything else, a NaN included,
+ * is ILM_ERR_INVALID_ARGUMENT (the host never packs another value, :1361-1362).  MaxStepCount (StepAndMisc2.x) that is NaN, < 1 or > 4096
+ * is ILM_ERR_INVALID_ARGUMENT for this entry point: it divides the column and bounds both loops.
+ * Coverage (VolumetricLightVertexShader, VolumetricLightCore.fxh:510-549), once per light, fp32 in the order written: cone p1 = min(start,
+ * end) - max(r1, r2), p2 = max(start, end) + max(r1, r2); otherwise p1 = start - end, p2 = start + end; tl = min(p1, p2), br = max(p1, p2)
+ * (min / max return the operand that is not a NaN).  Only x and y matter; z is not padded into y ("FIXME: zToY").  The world rectangle is
+ * mapped by (world - ViewportPosition) * (ViewportScale * RenderScale), the scales multiplied first, and a pixel is covered iff its centre
+ * lies in the half-open rectangle [x0, x1) x [y0, y1): the directional pass's rule.  A rectangle with a NaN bound covers nothing.
+ * Per pixel (VolumetricLightPixelCore and volumetricTrace, :315-508), p = the shaded point, n = its normal.  Arithmetic is fp32 with one
+ * rounding per + - * / sqrt in the order the HLSL writes it; every division is IEEE (1.0 / l2; hits / steps / Volumetricity as two; p / r per
+ * component); dot = (x + y) + z, length = sqrt of that dot, normalize = three divisions by the length, lerp(a, b, t) = a + (b - a) * t
+ * unsaturated, saturate(NaN) = 0, sign(0) = sign(NaN) = 0, max / min return the operand that is not a NaN, pow(x, y) = y == 0 ? 1 : exp2(y *
+ * log2(x)).  FUSED are only the march's sample position from + along * d (one fma per component) and what the shared sampler fuses.
+ *   a fullbright pixel is discarded; a pixel with p.x <= -9999 is not visible, the core returns 0 and it is discarded;
+ *   `intersect` (:300-313) returns true on its second line: the early-out never fires, and ellipsoidIntersect, roundConeIntersect,
+ *   boxIntersect, coneIntersect, capsuleIntersect, sdCappedCone and sdCapsule are dead code -- not built;
+ *   AO as for directional lights: radius * max(0, n.z), sampled only when >= 0.5 and a field is bound (sdf != 0, Extent.x > 0);
+ *   traceShadows = (LightProperties.w * enableShadows != 0) && Extent.z > 0 -- .z, the only pass that tests it; samples are taken only with
+ *   a bound field: without one occlusion = 1 and nothing is sampled;
+ *   the column: steps = MaxStepCount, z2 = max(p.z, GroundZ), z1 = max(MaximumZ, z2); cone: z1 = min(z1, max(start.z, end.z) + max(r1, r2)),
+ *   z2 = max(z2, min(start.z, end.z) - max(r1, r2)), md0 = |end - start|; otherwise z1 = min(z1, start.z + end.z), z2 = max(z2, start.z -
+ *   end.z), md0 = |end|; step = max(|z2 - z1|, 1) / steps; z = z1 + dither * step; do { body; z -= step; } while (z >= z2).  The body always
+ *   runs once, even when the narrowed z1 < z2;
+ *   body at pos = (p.x, p.y, z): sd = eval(pos): sdEllipsoid(pos - start, end) = k0 * (k0 - 1) / k1 with k0 = |q / r|, k1 = |q / (r * r)|;
+ *   sdRoundCone(pos, start, end, r1, r2) (:31-54) as written, products left to right; sdBox(pos - start, end) = |max(d, 0.0001)| + min(max(
+ *   max(d.x, d.y), d.z), 0.0001), d = |q| - b.  occlusion = 1, or the march's; hits += pow(saturate(-sd / RampLength), RampPower) * occlusion;
+ *   the march (:359-399), only when traceShadows: d = dither * 0.66; when |LightPosition3.xyz| < 0.01 it runs from start.xyz along pos -
+ *   start with md = |pos - start|, otherwise from pos - t along t with t = LightPosition3.xyz * md0 and md = md0; along /= md as written
+ *   (t / md0 is not simplified); at most (int)MaxStepCount samples: s = the field at from + along * d; occlusion = saturate(s * 0.5); s <= -0.1
+ *   ends the march with occlusion = 0; d += max(|s| * 0.99, MinStepSize); d >= md ends it; occlusion is what the last sample left;
+ *   volumetricOpacity = saturate(hits / steps / Volumetricity); preTraceOpacity = aoOpacity * volumetricOpacity;
+ *   the contact term: fullLength = md0; c = cone ? max(r1, r2) / 64 : 0; dotRange = lerp(0.15, 0.33, c), dotOffset likewise;
+ *   normalOpacity = computeNormalFactorEx(normalize(p - start), n, dotOffset, dotRange) (1 for a zero normal), then lerp(x, x * 2 - 1,
+ *   BlowoutFactor); shapeOpacity = eval(p) < 0 ? pow(saturate(-eval(p) / RampLength), RampPower) : 0; distanceOpacity = 1 - saturate(|p -
+ *   start| / (fullLength * DistanceAttenuation)); diffuse = (normalOpacity * shapeOpacity) * distanceOpacity.  The RampMode >= 1 squaring
+ *   (:495-498) follows the last read of what it changes: it is not computed, RampMode is not read;
+ *   opacity = diffuse < 0 ? preTraceOpacity + diffuse : max(preTraceOpacity, diffuse).
+ * Discards: a fullbright pixel, an uncovered one, one that is not visible and one with opacity <= 0 get nothing -- no rgb, no + 1 on
+ * alpha.  Otherwise rgb += (Color1.rgb * Color1.a) * opacity and alpha += 1.
+ * dither = Dither17(vpos, (FrameIndex % 4) + 0.5), a function of Fracture's DitherCommon.fxh outside the reference tree, restated from the
+ * one its author published (Jimenez, "Next Generation Post Processing in Call of Duty: Advanced Warfare": frac(dot(float3(pos, frame),
+ * float3(2, 7, 23) / 17))) as a DEFINED function, since 1 / 17 is no binary fraction and the order of operations would matter: k = 2 x + 7 y
+ * + 23 f with the integer pixel (x, y), exact in fp32; k mod 17 exactly; dither = (k mod 17) / 17, one IEEE division.  FrameIndex is an
+ * effect parameter nothing in Illuminant/Lighting sets for the light materials (the only assignment, LightingRenderer.cs:1495, is the
+ * resolve pass's): it holds its default 0, f = 0.5, and the entry point takes no frame argument.
+ * Termination: z -= step stops making progress once step is below an ulp of z (a huge MaximumZ), so the column loop is also bounded by an
+ * integer: at most (int)MaxStepCount + 4 bodies (the arithmetic ends it after at most MaxStepCount + 1 where it makes progress).  A NaN z
+ * ends the loop: the comparison is false.  The march is bounded by its counter.
+ * Degenerate geometry is defined by that arithmetic and not special-cased; no memory access depends on any of it.  A zero radius component
+ * of an ellipsoid: q / 0 is +-inf or NaN, sd = inf * inf / inf = NaN or inf, saturate gives 0 -- no hits; sdEllipsoid at the centre: 0 * -1 /
+ * 0 = NaN, no hit from that point; a zero-length cone: l2 = 0, il2 = inf, every product with it NaN or inf, no hits and shapeOpacity 0; md =
+ * 0 (the column point at start): along = 0 / 0 = NaN, the NaN sample coordinates are treated as 0 (the test is hoisted out of the march),
+ * d >= 0 ends the march after one sample; RampLength = 0: -sd / 0 = +inf inside the shape (ramp 1), -inf outside (0), NaN on the surface
+ * (0); Volumetricity = 0: hits / steps / 0 = +inf (1) or NaN (0); NaN positions: a NaN footprint covers nothing, a NaN sd adds no hit, a
+ * NaN diffuse compares false and max(preTraceOpacity, NaN) = preTraceOpacity.
+ * Statistics: PixelLightPairs = pairs inside a footprint and the image; TracedPairs = pairs with traceShadows and a bound field;
+ * SdfSamples = the AO sample + every sample of every march.
+ * Not built: VolumetricLightProbe, the group entry point, the dead intersection code. */
+int32_t ilm_render_volumetric_lights(IlmHandle ctx,
+                                     const IlmLightVertex* lights, int32_t light_count,
+                                     const IlmEnvironment* env,
+                                     const IlmDistanceFieldUniforms* df,
+                                     IlmHandle gbuffer, IlmHandle sdf,
+                                     const float ambient[4],
+                                     IlmHandle lightmap, int32_t row_begin, int32_t row_end,
+                                     IlmRenderStats* stats);
 
 /* LightSource.TextureRef / Configuration.DefaultRampTexture of the light group rendered by the FOLLOWING ilm_render_sphere_lights,
  * ilm_render_directional_lights (SampleFromRamp(opacity), channel r at v = 0: DirectionalLightWithRamp) and
