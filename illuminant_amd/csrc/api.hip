@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <functional>
 #include <array>
 #include <cstring>
 #include <mutex>
@@ -106,6 +107,7 @@ struct Ctx {
     float4* d_light_ramp = nullptr; int light_ramp_w = 0, light_ramp_h = 0;    // RampTexture of the light group being rendered
     // ProjectorLightSource.TextureRef of the projector group being rendered (ilm_ctx_set_projector_texture): a binding of its own
     DeviceScratch d_projector_texture; int projector_texture_w = 0, projector_texture_h = 0;
+    ProjectorMips projector_mips = {};    // the bound chain's levels (ilm_ctx_set_projector_texture_mips); levels <= 1: the one-level pass
     int lightmap_blend = 0;               // ILM_BLEND_FP32_ACCUMULATE / ILM_BLEND_FP16_PER_LIGHT (ilm_ctx_set_lightmap_blend)
     RasterScratch raster;                                         // particle rasteriser buffers (raster.hip)
     DeviceScratch d_raster_quads;
@@ -3366,14 +3368,41 @@ int32_t ilm_ctx_set_projector_texture(IlmHandle hctx, const IlmFloat4* texels, i
     if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
     if (width < 0 || height < 0 || width > 16384 || height > 16384 || ((width > 0) != (height > 0)) || (width > 0 && !texels))
         return fail(ILM_ERR_INVALID_ARGUMENT, "bad projector texture (%d x %d)", width, height);
-    if (width == 0) { c->projector_texture_w = c->projector_texture_h = 0; return ILM_OK; }      // unbound; the block stays for the next texture
+    if (width == 0) { c->projector_texture_w = c->projector_texture_h = 0; c->projector_mips.levels = 0; return ILM_OK; }      // unbound; the block stays for the next texture
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->main()));     // an earlier pass may still read the texels about to be replaced
-    c->projector_texture_w = c->projector_texture_h = 0;
+    c->projector_texture_w = c->projector_texture_h = 0; c->projector_mips.levels = 0;
     const size_t bytes = sizeof(float4) * (size_t)width * (size_t)height;
     { const int32_t rc = reserve(c, c->d_projector_texture, bytes, bytes); if (rc != ILM_OK) return rc; }
     HIP_TRY(hipMemcpy(c->d_projector_texture.p, texels, bytes, hipMemcpyHostToDevice));
-    c->projector_texture_w = width; c->projector_texture_h = height;
+    c->projector_texture_w = width; c->projector_texture_h = height; c->projector_mips.levels = 1;
+    return ILM_OK;
+}
+
+int32_t ilm_ctx_set_projector_texture_mips(IlmHandle hctx, const IlmFloat4* texels, int32_t width, int32_t height, int32_t levels) {
+    if (levels == 1) return ilm_ctx_set_projector_texture(hctx, texels, width, height);          // the one-level binding, bit for bit
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    if (levels < 0 || levels > kMaxProjectorLevels) return fail(ILM_ERR_OUT_OF_RANGE, "%d mip levels outside [0, %d]", levels, kMaxProjectorLevels);
+    if (levels == 0 || (width == 0 && height == 0)) return ilm_ctx_set_projector_texture(hctx, nullptr, 0, 0);      // unbinds
+    if (!texels || width < 1 || height < 1 || width > 16384 || height > 16384)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "bad projector texture (%d x %d)", width, height);
+    // the table of the levels: level l is max(1, width >> l) x max(1, height >> l), back to back (at most 4 / 3 * 2^28 texels: an int)
+    ProjectorMips mips = {};
+    size_t total = 0;
+    for (int l = 0, lw = width, lh = height; l < levels; l++) {
+        mips.offset[l] = (int32_t)total; mips.width[l] = lw; mips.height[l] = lh;
+        total += (size_t)lw * (size_t)lh;
+        lw = std::max(1, lw >> 1); lh = std::max(1, lh >> 1);
+    }
+    mips.levels = levels;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->main()));     // an earlier pass may still read the texels about to be replaced
+    c->projector_texture_w = c->projector_texture_h = 0; c->projector_mips.levels = 0;
+    const size_t bytes = sizeof(float4) * total;
+    { const int32_t rc = reserve(c, c->d_projector_texture, bytes, bytes); if (rc != ILM_OK) return rc; }
+    HIP_TRY(hipMemcpy(c->d_projector_texture.p, texels, bytes, hipMemcpyHostToDevice));
+    c->projector_texture_w = width; c->projector_texture_h = height; c->projector_mips = mips;
     return ILM_OK;
 }
 
@@ -3809,12 +3838,13 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
 // the resource checks and the launch descriptor, rec_slots record slots, the staged vertices prepared into them, then one full-frame
 // launch (no split, no tile map) and the statistics.  `ramp` is what the pass reads through the descriptor's ramp member; light_limit
 // (0: none) is the projector pass's, refused where its slot count is about to be used.
-typedef hipError_t (*PrepareFullFrameLights)(const IlmLightVertex*, int, const IlmEnvironment&, const IlmDistanceFieldUniforms&, void*, hipStream_t);
+// The two launchers are callables, so that a pass can bind what else it hands them (the projector pass's mip table).
+typedef std::function<hipError_t(const IlmLightVertex*, int, const IlmEnvironment&, const IlmDistanceFieldUniforms&, void*, hipStream_t)> PrepareFullFrameLights;
 typedef hipError_t (*LaunchFullFrameLights)(const LightLaunch&, const void*, hipStream_t);
 static int32_t render_full_frame_lights(Ctx* c, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,
                                         const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf, const float ambient[4],
                                         IlmHandle hlightmap, int32_t row_begin, int32_t row_end, IlmRenderStats* stats, int rec_slots,
-                                        int light_limit, const RampView& ramp, PrepareFullFrameLights prepare, LaunchFullFrameLights launch) {
+                                        int light_limit, const RampView& ramp, const PrepareFullFrameLights& prepare, LaunchFullFrameLights launch) {
     LightLaunch a = {};
     { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, false); if (rc != ILM_OK) return rc; }
     Sdf* f = hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr;
@@ -3901,15 +3931,26 @@ int32_t ilm_render_projector_lights(IlmHandle hctx, const IlmLightVertex* lights
     // the reference skips a light whose texture is null before packing (LightingRenderer.cs:1389-1391): lights without one are a caller's error
     if (light_count > 0 && c->projector_texture_w == 0)
         return fail(ILM_ERR_INVALID_ARGUMENT, "projector lights without a texture: ilm_ctx_set_projector_texture binds the group's");
+    // a chain of more than one level: the preparation resolves each light's LOD against the levels' table, the MIPS kernels fetch
+    const RampView texture{ light_count > 0 ? static_cast<const float4*>(c->d_projector_texture.p) : nullptr, c->projector_texture_w,
+                            c->projector_texture_h };
+    const int rec_slots = light_count > kMaxProjectorLights ? 0 : light_count + (light_count + 1) / 2;
+    if (c->projector_mips.levels > 1) {
+        const ProjectorMips mips = c->projector_mips;
+        return render_full_frame_lights(c, lights, light_count, env, df, hgbuffer, hsdf, ambient, hlightmap, row_begin, row_end, stats, rec_slots,
+                                        kMaxProjectorLights, texture,
+                                        [mips](const IlmLightVertex* staged, int count, const IlmEnvironment& e, const IlmDistanceFieldUniforms& dfu,
+                                               void* recs, hipStream_t stream) {
+                                            return launch_prepare_projector_mip_lights(staged, count, e, dfu, mips, recs, stream);
+                                        },
+                                        launch_projector_mip_lights_prepared);
+    }
     // (a projector record is one and a half slots of the other passes' records)
     static_assert(kProjectorRecBytes * 2 == kLightRecBytes * 3, "a projector record is one and a half light-record slots");
     // (more than kMaxProjectorLights are refused behind the shared checks, before the slots are reserved)
     // the group's texture rides in the descriptor's ramp member; the ramp binding (ilm_ctx_set_light_ramp) is neither read nor touched
-    return render_full_frame_lights(c, lights, light_count, env, df, hgbuffer, hsdf, ambient, hlightmap, row_begin, row_end, stats,
-                                    light_count > kMaxProjectorLights ? 0 : light_count + (light_count + 1) / 2, kMaxProjectorLights,
-                                    RampView{ light_count > 0 ? static_cast<const float4*>(c->d_projector_texture.p) : nullptr, c->projector_texture_w,
-                                              c->projector_texture_h },
-                                    launch_prepare_projector_lights, launch_projector_lights_prepared);
+    return render_full_frame_lights(c, lights, light_count, env, df, hgbuffer, hsdf, ambient, hlightmap, row_begin, row_end, stats, rec_slots,
+                                    kMaxProjectorLights, texture, launch_prepare_projector_lights, launch_projector_lights_prepared);
 }
 
 int32_t ilm_render_volumetric_lights(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count, const IlmEnvironment* env,

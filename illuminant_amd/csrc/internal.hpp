@@ -247,6 +247,15 @@ constexpr int32_t kMaxProjectorLights = 1 << 24;      // per call: 3 GiB of reco
 hipError_t launch_prepare_projector_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
                                            void* recs, hipStream_t stream);
 hipError_t launch_projector_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream);
+// ... with a mip chain bound (ilm_ctx_set_projector_texture_mips, levels > 1): the table of the chain's levels, made on the host when the
+// texture is bound -- level l is width[l] x height[l] texels from texel offset[l] of a.ramp.texels -- goes to the preparation by value
+// (kernel arguments: scalar registers), which resolves each light's LOD against it into the record; the pass then reads records only.
+// Records of the one preparation are not for the other pass.
+constexpr int kMaxProjectorLevels = 16;
+struct ProjectorMips { int32_t levels; int32_t offset[kMaxProjectorLevels], width[kMaxProjectorLevels], height[kMaxProjectorLevels]; };
+hipError_t launch_prepare_projector_mip_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
+                                               const ProjectorMips& mips, void* recs, hipStream_t stream);
+hipError_t launch_projector_mip_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream);
 // Line lights (LineLight.fx): the records (count * kLightRecBytes) and the full-frame pass over a's rows, in the directional pass's frame.
 // The ramp is not read (the reference has no LineLightWithRamp).
 hipError_t launch_prepare_line_lights(const IlmLightVertex* lights, int count, const IlmDistanceFieldUniforms& df, void* recs, hipStream_t stream);

@@ -1248,10 +1248,11 @@ hipError_t launch_sphere_lights_prepared(const LightLaunch& launch, const void* 
 // ---------------------------------------------------------------------------------------------
 // The full-frame light passes (directional, projector, line, volumetric) -- one thread per pixel, one wave per 8 x 8 pixels, a wave-uniform
 // loop over the prepared records (uniform index: scalar loads), the G-buffer texel decoded once, the sum in registers, the lightmap texel
-// read at most once (accumulate mode) and stored once.  Shared by the four kernels: the store with its mirrors, the statistics and
+// read at most once (accumulate mode) and stored once.  Shared by the five kernels: the store with its mirrors, the statistics and
 // the launcher.  Each kernel states its own pixel mapping, base value, blend chains and light loop: as device functions these change
 // the instruction streams of the kernels, and the passes then run up to 3 % slower (docs/experiments.md 7.24).  A change to one of
-// those parts is made in directional_lights_kernel, projector_lights_kernel, line_lights_kernel and volumetric_lights_kernel alike.
+// those parts is made in directional_lights_kernel, projector_lights_kernel, projector_mip_lights_kernel, line_lights_kernel and
+// volumetric_lights_kernel alike.
 // ---------------------------------------------------------------------------------------------
 // the texel into the lightmap and into every mirror (store-mode exchange of a group lightmap, as the sphere pass)
 ILM_DEV void store_light_texel(const LightLaunch& a, size_t o, const float4& v) {
@@ -1510,8 +1511,10 @@ hipError_t launch_directional_lights_prepared(const LightLaunch& a, const void* 
 // box of the projector's volume for a clamped one (ProjectorLightVertexShader, ProjectorLightCore.fxh:251-278).  The frame of the
 // directional pass: one thread per pixel, one wave per 8 x 8 pixels, a wave-uniform loop over the prepared records (scalar loads: the
 // 16 matrix entries of a light cost no vector registers), the G-buffer texel decoded once, the sum in registers, one store.  The
-// shadow is the sphere light's trace towards one point in its general form (cone_trace_loop<.., false>); the group's texture (one
-// level, LINEAR, WRAP on both axes) travels in the launch descriptor's `ramp` member, which this pass reads as nothing else.
+// shadow is the sphere light's trace towards one point in its general form (cone_trace_loop<.., false>); the group's texture (LINEAR,
+// WRAP on both axes) travels in the launch descriptor's `ramp` member, which this pass reads as nothing else.  A texture bound with
+// more than one level (ilm_ctx_set_projector_texture_mips) runs the MIPS instantiations: the record then names the light's two levels
+// and the weight between them (prepare_projector_mips_kernel), all wave-uniform -- scalar loads, a scalar branch at weight 0.
 // ---------------------------------------------------------------------------------------------
 constexpr float kProjectorSelfOcclusionHack = 1.5f;              // ProjectorLightCore.fxh:7 SELF_OCCLUSION_HACK
 constexpr float kProjectorTraceThreshold = 0.75f / 255.0f;       // ProjectorLightCore.fxh:8 SHADOW_OPACITY_THRESHOLD
@@ -1520,12 +1523,16 @@ constexpr float kProjectorEdgeScale = 1.0f / 0.001f;             // (1 / thresho
 
 struct ProjectorRec {
     float x0, y0, x1, y1;                                       // footprint in screen pixels: centre in [x0, x1) x [y0, y1)
-    float m[16];                                                // rows 1-4 of the inverse matrix, m[15] = 1 (the mip bias is not read: one level)
+    float m[16];                                                // rows 1-4 of the inverse matrix, m[15] = 1 (the mip bias: lod_* below)
     float origin_x, origin_y, origin_z, origin_w;               // LightPosition3
     float region_x0, region_y0, region_x1, region_y1;           // EvenMoreLightProperties
     float clamp, opacity, ao_radius, ao_opacity;                // MoreLightProperties.z, .y, .x, .w
     float shadows, radius, cfg_x, cfg_y;                        // LightProperties.w, .x; createTraceConfig: maxRadius, radiusGrowthPerPixel
-    float _pad[12];
+    // the explicit LOD (Color2.w) over the bound chain, written by prepare_projector_mips_kernel alone (one level: all zero, not
+    // read): levels l0 and l1 = min(l0 + 1, L - 1), the weight of l1, and each level's first texel, width and height from the host's table
+    int32_t lod_l0, lod_l1; float lod_f;
+    int32_t l0_offset, l0_width, l0_height, l1_offset, l1_width, l1_height;
+    float _pad[3];
 };
 static_assert(sizeof(ProjectorRec) == kProjectorRecBytes, "a projector record is 192 bytes (internal.hpp: one and a half slots of reserve_light_recs)");
 
@@ -1615,6 +1622,26 @@ __global__ __launch_bounds__(64) void prepare_projector_lights_kernel(const IlmL
     out[i] = r;
 }
 
+// ... and, for a texture of mips.levels > 1 levels, a second kernel behind it on the stream fills in the record's lod_* members: the
+// light's LOD = Color2.w (RenderProjectorLightSource, LightingRenderer.cs:1417-1428) resolved against the chain -- c = min(max(lod, 0),
+// L - 1), where a NaN becomes 0 through fmaxf and an infinity clamps; l0 = floor(c), f = c - floor(c), l1 = min(l0 + 1, L - 1) -- and
+// both levels' rows of the host's table.  The table arrives by value (kernel arguments: scalar registers) and is walked with compares,
+// not indexed, so it stays there.  A kernel of its own: prepare_projector_lights_kernel keeps the instruction stream it had.
+__global__ __launch_bounds__(64) void prepare_projector_mips_kernel(const IlmLightVertex* __restrict__ lights, int count, const ProjectorMips mips,
+                                                                     ProjectorRec* __restrict__ out) {
+    const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (i >= count) return;
+    const float c = fminf(fmaxf(lights[i].Color2.w, 0.0f), (float)(mips.levels - 1));
+    const float whole = floorf(c);
+    const int l0 = (int)whole, l1 = (l0 + 1 < mips.levels) ? l0 + 1 : mips.levels - 1;
+    ProjectorRec& r = out[i];
+    r.lod_l0 = l0; r.lod_l1 = l1; r.lod_f = c - whole;
+    for (int l = 0; l < kMaxProjectorLevels; l++) {
+        if (l == l0) { r.l0_offset = mips.offset[l]; r.l0_width = mips.width[l]; r.l0_height = mips.height[l]; }
+        if (l == l1) { r.l1_offset = mips.offset[l]; r.l1_width = mips.width[l]; r.l1_height = mips.height[l]; }
+    }
+}
+
 // tex2Dlod(ProjectorTextureSampler, (u, v, 0, mip)) on a one-level texture: LINEAR, WRAP on both axes.  The tap and weight arithmetic
 // of the ramp lookup's V axis (shade_light) on both axes: the second tap is the integer first tap + 1 wrapped, wrap_index is exact for
 // every finite float and names tap 0 for a non-finite one -- every index lies inside the texture by integer arithmetic.
@@ -1629,10 +1656,38 @@ ILM_DEV float4 sample_projector_texture(const RampView& tex, float u, float v) {
     return lerp4(lerp4(t00, t10, fx), lerp4(t01, t11, fx), fy);
 }
 
+// The same fetch with the explicit LOD over a chain (MipFilter LINEAR): sample_projector_texture's taps and weights on level l0 with
+// that level's own size and, unless the weight f is 0, on level l1; the texel is c0 + (c1 - c0) * f.  At f == 0 -- one level read: an
+// integral or a clamped LOD -- level l1 is not touched, so nothing of it (a NaN texel) can show.  l0, l1 and f are the light's, hence
+// wave-uniform: the branch is a scalar one.  With two levels all eight taps are issued before the first lerp, to be in flight together.
+struct ProjectorTaps { int i00, i10, i01, i11; float fx, fy; };
+ILM_DEV ProjectorTaps projector_taps(int w, int h, float u, float v) {
+    const float sx = u * (float)w - 0.5f, sy = v * (float)h - 0.5f;
+    const float x0f = floorf(sx), y0f = floorf(sy);
+    const int x0 = wrap_index(x0f, w), x1 = (x0 + 1 == w) ? 0 : x0 + 1;
+    const int y0 = wrap_index(y0f, h), y1 = (y0 + 1 == h) ? 0 : y0 + 1;
+    return { y0 * w + x0, y0 * w + x1, y1 * w + x0, y1 * w + x1, sx - x0f, sy - y0f };
+}
+ILM_DEV float4 sample_projector_mips(const RampView& tex, const ProjectorRec& L, float u, float v) {
+    const float4* level0 = tex.texels + L.l0_offset;
+    const ProjectorTaps a = projector_taps(L.l0_width, L.l0_height, u, v);
+    if (L.lod_f == 0.0f) {
+        const float4 t00 = level0[a.i00], t10 = level0[a.i10], t01 = level0[a.i01], t11 = level0[a.i11];
+        return lerp4(lerp4(t00, t10, a.fx), lerp4(t01, t11, a.fx), a.fy);
+    }
+    const float4* level1 = tex.texels + L.l1_offset;
+    const ProjectorTaps b = projector_taps(L.l1_width, L.l1_height, u, v);
+    const float4 a00 = level0[a.i00], a10 = level0[a.i10], a01 = level0[a.i01], a11 = level0[a.i11];
+    const float4 b00 = level1[b.i00], b10 = level1[b.i10], b01 = level1[b.i01], b11 = level1[b.i11];
+    const float4 c0 = lerp4(lerp4(a00, a10, a.fx), lerp4(a01, a11, a.fx), a.fy);
+    const float4 c1 = lerp4(lerp4(b00, b10, b.fx), lerp4(b01, b11, b.fx), b.fy);
+    return lerp4(c0, c1, L.lod_f);
+}
+
 // One projector light on one shaded point: ProjectorLightPixelShader (ProjectorLight.fx:14-56) after the footprint test.  Returns false
 // when the shader discards (fullbright, !visible); otherwise the rgb it adds.  No shadow filter and no opacity discard: a visible
 // pixel whose opacity is 0 is blended (alpha + 1).
-template <int FMT, bool STATS>
+template <int FMT, bool STATS, bool MIPS>
 ILM_DEV bool shade_projector(const Pixel& P, const ProjectorRec& L, const TraceField& F, bool have_sdf, const RampView& tex, LightStats& st,
                              float& out_r, float& out_g, float& out_b) {
     if (P.fullbright)
@@ -1703,7 +1758,7 @@ ILM_DEV bool shade_projector(const Pixel& P, const ProjectorRec& L, const TraceF
         opacity *= pow_pos(sat(div_with_rcp(sat(visibility - ref::kFullyShadowedThreshold), kVisibilityRange, kVisibilityRangeRcp)), F.df.ConeAndMisc.z);
     }
     // ProjectorLightColorCore, :290-302
-    const float4 t = sample_projector_texture(tex, tx, ty);
+    const float4 t = MIPS ? sample_projector_mips(tex, L, tx, ty) : sample_projector_texture(tex, tx, ty);
     out_r = (t.x * t.w) * opacity; out_g = (t.y * t.w) * opacity; out_b = (t.z * t.w) * opacity;
     return true;
 }
@@ -1751,7 +1806,74 @@ __global__ __launch_bounds__(kLightThreads) void projector_lights_kernel(const L
             continue;
         if (STATS) st.pairs++;
         float cr, cg, cb;
-        if (!shade_projector<FMT, STATS>(P, L, field, have_sdf, a.ramp, st, cr, cg, cb))
+        if (!shade_projector<FMT, STATS, false>(P, L, field, have_sdf, a.ramp, st, cr, cg, cb))
+            continue;
+        if (blend_fp16) {
+            acc_r = through_half(acc_r + through_half(cr));
+            acc_g = through_half(acc_g + through_half(cg));
+            acc_b = through_half(acc_b + through_half(cb));
+            acc_a = through_half(acc_a + 1.0f);
+        } else {
+            acc_r += cr; acc_g += cg; acc_b += cb; acc_a += 1.0f;
+        }
+    }
+    if (!blend_fp16) {
+        const float4 v = base_value();
+        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+    }
+    if (in_image) {
+        const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
+        store_light_texel(a, o, v);
+    }
+    if (STATS) add_light_stats(st, a.stats, lane);
+}
+
+// The same kernel over a mip chain: the records are prepare_projector_mips_kernel's, the fetch sample_projector_mips.  A copy of the frame,
+// as each full-frame pass has its own (the note at their head): as a device function shared with projector_lights_kernel the frame changed
+// that kernel's schedule (tools/isa_compare.py: four of four `diff`, same counts), which the one-level pass is held not to do.
+template <int FMT, bool STATS>
+__global__ __launch_bounds__(kLightThreads) void projector_mip_lights_kernel(const LightLaunch a, const ProjectorRec* __restrict__ recs, int tiles_x) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int tile_x = (int)blockIdx.x % tiles_x, tile_y = (int)blockIdx.x / tiles_x;
+    const int px = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
+    const int py = a.row_begin + tile_y * kTile + (wave >> 1) * 8 + (lane >> 3);
+    const bool in_image = (px < a.width) && (py < a.row_end);
+    if (__builtin_amdgcn_ballot_w64(in_image) == 0ull)
+        return;
+    Pixel P = sample_gbuffer((float)px, (float)py, a.env, a.gbuffer);
+    P.origin_x = 0; P.origin_y = 0; P.start_inside = false;
+    const float cxp = (float)px + 0.5f, cyp = (float)py + 0.5f;
+    const bool have_sdf = (a.sdf.texels != nullptr) && (a.df.Extent.x > 0.0f);
+    const InsideConsts no_table = {};
+    const TraceField field = { a.df, a.sdf, no_table, nullptr };
+    const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
+    auto through_half = [](float v) { return __half2float(__float2half_rn(v)); };
+    auto base_value = [&]() -> float4 {
+        float4 v = mk4(a.ambient[0], a.ambient[1], a.ambient[2], a.ambient[3]);
+        if (a.accumulate != 0 && in_image) {
+            if (a.format == ILM_LIGHTMAP_FLOAT4) v = load_target<ILM_LIGHTMAP_FLOAT4>(a.lightmap, o);
+            else if (a.format == ILM_LIGHTMAP_HALF4) v = load_target<ILM_LIGHTMAP_HALF4>(a.lightmap, o);
+            else v = load_target<ILM_LIGHTMAP_RGBA8>(a.lightmap, o);
+        }
+        if (a.blend_fp16 != 0) v = mk4(through_half(v.x), through_half(v.y), through_half(v.z), through_half(v.w));
+        return v;
+    };
+    const bool blend_fp16 = a.blend_fp16 != 0;
+    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if (blend_fp16) { const float4 v = base_value(); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
+    LightStats st;
+    const int light_count = a.light_count;
+    for (int k = 0; k < light_count; k++) {
+        const ProjectorRec& L = recs[k];
+        const float x0 = L.x0, y0 = L.y0, x1 = L.x1, y1 = L.y1;
+        const bool covered = in_image & (cxp >= x0) & (cxp < x1) & (cyp >= y0) & (cyp < y1);
+        if (__builtin_amdgcn_ballot_w64(covered) == 0ull)
+            continue;
+        if (!covered)
+            continue;
+        if (STATS) st.pairs++;
+        float cr, cg, cb;
+        if (!shade_projector<FMT, STATS, true>(P, L, field, have_sdf, a.ramp, st, cr, cg, cb))
             continue;
         if (blend_fp16) {
             acc_r = through_half(acc_r + through_half(cr));
@@ -1784,6 +1906,21 @@ hipError_t launch_prepare_projector_lights(const IlmLightVertex* lights, int cou
 hipError_t launch_projector_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
     return launch_full_frame_lights<ProjectorRec>(a, recs, stream, projector_lights_kernel<ILM_SDF_FP16, false>, projector_lights_kernel<ILM_SDF_FP16, true>,
                                            projector_lights_kernel<ILM_SDF_UNORM16, false>, projector_lights_kernel<ILM_SDF_UNORM16, true>);
+}
+
+hipError_t launch_prepare_projector_mip_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
+                                               const ProjectorMips& mips, void* recs, hipStream_t stream) {
+    if (count <= 0) return hipSuccess;
+    const hipError_t e = launch_prepare_projector_lights(lights, count, env, df, recs, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(prepare_projector_mips_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, lights, count, mips, reinterpret_cast<ProjectorRec*>(recs));
+    return hipGetLastError();
+}
+
+hipError_t launch_projector_mip_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
+    return launch_full_frame_lights<ProjectorRec>(a, recs, stream, projector_mip_lights_kernel<ILM_SDF_FP16, false>,
+                                           projector_mip_lights_kernel<ILM_SDF_FP16, true>, projector_mip_lights_kernel<ILM_SDF_UNORM16, false>,
+                                           projector_mip_lights_kernel<ILM_SDF_UNORM16, true>);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -7,6 +7,8 @@
 
 #include <algorithm>
 #include <cstring>
+#include <optional>
+#include <string>
 
 #include "illuminant_host.hpp"
 
@@ -382,16 +384,30 @@ PYBIND11_MODULE(_host, m) {
         .def("LastStepBytes", [](const ParticleSystem& s) { return py::bytes((const char*)&s.LastStep(), sizeof(IlmStepDesc)); });
 
     // ---- lighting ------------------------------------------------------------------------------------------------
-    // RampTexture((h, w, 4) float32)
+    // RampTexture((h, w, 4) float32[, mips = [level 1 (max(1, h >> 1), max(1, w >> 1), 4), level 2, ...]]): the further levels of a projector's texture
     py::class_<RampTexture, std::shared_ptr<RampTexture>>(m, "RampTexture")
-        .def(py::init([](py::array_t<float, py::array::c_style | py::array::forcecast> a) {
+        .def(py::init([](py::array_t<float, py::array::c_style | py::array::forcecast> a,
+                         std::optional<std::vector<py::array_t<float, py::array::c_style | py::array::forcecast>>> mips) {
             if (a.ndim() != 3 || a.shape(2) != 4) throw std::invalid_argument("ramp texture must be (h, w, 4) float32");
             auto t = std::make_shared<RampTexture>();
             t->Width = (int)a.shape(1); t->Height = (int)a.shape(0);
             const IlmFloat4* p = reinterpret_cast<const IlmFloat4*>(a.data());
             t->Texels.assign(p, p + a.shape(0) * a.shape(1));
-            return t; }))
-        .def_readonly("Width", &RampTexture::Width).def_readonly("Height", &RampTexture::Height);
+            if (mips) {
+                if (mips->size() > 15) throw std::invalid_argument("a texture has at most 16 mip levels");
+                for (size_t l = 1; l <= mips->size(); l++) {
+                    const auto& level = (*mips)[l - 1];
+                    const py::ssize_t w = std::max(1, t->Width >> l), h = std::max(1, t->Height >> l);
+                    if (level.ndim() != 3 || level.shape(0) != h || level.shape(1) != w || level.shape(2) != 4)
+                        throw std::invalid_argument("mip level " + std::to_string(l) + " must be (" + std::to_string(h) + ", " + std::to_string(w) + ", 4) float32");
+                    const IlmFloat4* q = reinterpret_cast<const IlmFloat4*>(level.data());
+                    t->Texels.insert(t->Texels.end(), q, q + h * w);
+                }
+                t->LevelCount = 1 + (int)mips->size();
+            }
+            return t; }), py::arg("texels"), py::arg("mips") = py::none())
+        .def_readonly("Width", &RampTexture::Width).def_readonly("Height", &RampTexture::Height)
+        .def_readonly("LevelCount", &RampTexture::LevelCount);
     py::class_<SphereLightSource>(m, "SphereLightSource").def(py::init<>())
         .def_readwrite("SortKey", &SphereLightSource::SortKey).def_readwrite("Enabled", &SphereLightSource::Enabled)
         VEC_PROP(SphereLightSource, Position, 3)

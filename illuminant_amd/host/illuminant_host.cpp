@@ -1642,7 +1642,12 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     }
     // the projector render states: the group's texture, then one call; the ramp binding is not theirs
     for (size_t g = 0; g < projectorGroups.size(); g++) {
-        ThrowIfFailed(ilm_ctx_set_projector_texture(Context.Handle(), projectorKeys[g]->Texels.data(), projectorKeys[g]->Width, projectorKeys[g]->Height));
+        // (a texture with a mip chain goes through the call that takes the levels; a one-level texture makes the call it always made)
+        const RampTexture& texture = *projectorKeys[g];
+        if (texture.LevelCount > 1)
+            ThrowIfFailed(ilm_ctx_set_projector_texture_mips(Context.Handle(), texture.Texels.data(), texture.Width, texture.Height, texture.LevelCount));
+        else
+            ThrowIfFailed(ilm_ctx_set_projector_texture(Context.Handle(), texture.Texels.data(), texture.Width, texture.Height));
         IlmRenderStats gs{};
         const IlmDistanceFieldUniforms gdfu = projectorQuality[g] ? GetDistanceFieldUniforms(*projectorQuality[g]) : dfu;
         ThrowIfFailed(ilm_render_projector_lights(Context.Handle(), projectorGroups[g].data(), (int32_t)projectorGroups[g].size(), &env, &gdfu, gbuffer,

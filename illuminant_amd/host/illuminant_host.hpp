@@ -684,8 +684,12 @@ enum class LightShadowFilter { None = -1, ShadowsOnly = 1, NoShadowsOnly = 0 }; 
 // LightSource.cs:37-280 (SphereLightSource)
 // A light ramp texture (LightSource.TextureRef / RendererConfiguration.DefaultRampTexture): width x height float4 texels.  Lights are
 // grouped by the texture they share (LightTypeRenderStateKey.RampTexture, LightingRenderer.cs:50-83); a 1 x 1 ramp is no ramp (:822-827).
+// As a projector's texture (ProjectorLightSource.TextureRef) it may carry a mip chain (Texture2D.LevelCount > 1): Texels then holds
+// LevelCount levels back to back, level l being max(1, Width >> l) x max(1, Height >> l) texels -- ilm_ctx_set_projector_texture_mips's
+// layout.  Every other reader takes level 0, the first Width x Height texels.
 struct RampTexture {
     int Width = 0, Height = 0;
+    int LevelCount = 1;
     std::vector<IlmFloat4> Texels;
 };
 

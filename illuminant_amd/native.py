@@ -112,6 +112,7 @@ SYMBOLS = {
     "ilm_lightmap_clear": (_I, [_H, _P]),
     "ilm_ctx_set_light_ramp": (_I, [_H, _P, _I, _I]),
     "ilm_ctx_set_projector_texture": (_I, [_H, _P, _I, _I]),
+    "ilm_ctx_set_projector_texture_mips": (_I, [_H, _P, _I, _I, _I]),
     "ilm_ctx_set_lightmap_blend": (_I, [_H, _I]),
     "ilm_ctx_set_light_split": (_I, [_H, _I]),
     "ilm_system_set_bitmap": (_I, [_H, _P, _I, _I]),
@@ -227,9 +228,10 @@ class Context:
         a = np.ascontiguousarray(texels, dtype=np.float32)
         check(lib().ilm_ctx_set_light_ramp(self.handle, _ptr(a), a.shape[1], a.shape[0]))
 
-    def set_projector_texture(self, texels):
-        """ilm_ctx_set_projector_texture: (h, w, 4) float32 texture of the projector group rendered next (one level); None unbinds."""
-        set_projector_texture(self, texels)
+    def set_projector_texture(self, texels, mips=None):
+        """ilm_ctx_set_projector_texture / _mips: the (h, w, 4) float32 texture of the projector group rendered next, or the list of its
+        mip levels (or level 0 with the further levels in `mips`); None unbinds."""
+        set_projector_texture(self, texels, mips)
 
     def set_lightmap_blend(self, fp16_per_light):
         """ilm_ctx_set_lightmap_blend: True = the reference's HalfVector4 render target (rounded through fp16 after every light)."""
@@ -896,11 +898,25 @@ def render_volumetric_lights(ctx, lights, env, df, gbuffer, sdf, ambient, lightm
     return _render_lights(lib().ilm_render_volumetric_lights, ctx, lights, env, df, gbuffer, sdf, ambient, lightmap, row_begin, row_end, want_stats)
 
 
-def set_projector_texture(ctx, texels):
+def set_projector_texture(ctx, texels, mips=None):
     """ilm_ctx_set_projector_texture: (h, w, 4) float32 texels of the projector-light group rendered next; None unbinds.  The ramp
-    binding (Context.set_light_ramp) is a separate one."""
+    binding (Context.set_light_ramp) is a separate one.  A mip chain -- `texels` a list or tuple of levels [level 0 (h, w, 4), level 1
+    (max(1, h >> 1), max(1, w >> 1), 4), ...], or level 0 with the further levels listed in `mips` -- goes through
+    ilm_ctx_set_projector_texture_mips, a single array through the one-level call."""
     if texels is None:
         check(lib().ilm_ctx_set_projector_texture(ctx.handle, None, 0, 0))
+        return
+    if mips is not None or isinstance(texels, (list, tuple)):
+        levels = (list(texels) if isinstance(texels, (list, tuple)) else [texels]) + list(mips or [])
+        levels = [np.asarray(a, dtype=np.float32) for a in levels]
+        if not levels or levels[0].ndim != 3:
+            raise ValueError("a projector texture is (height, width, 4) float32")
+        h, w = levels[0].shape[0], levels[0].shape[1]
+        for l, a in enumerate(levels):
+            if a.shape != (max(1, h >> l), max(1, w >> l), 4):
+                raise ValueError("mip level %d is %s, expected %s" % (l, a.shape, (max(1, h >> l), max(1, w >> l), 4)))
+        flat = np.ascontiguousarray(np.concatenate([a.reshape(-1, 4) for a in levels]))
+        check(lib().ilm_ctx_set_projector_texture_mips(ctx.handle, _ptr(flat), w, h, len(levels)))
         return
     a = np.ascontiguousarray(texels, dtype=np.float32)
     if a.ndim != 3 or a.shape[2] != 4:

@@ -287,6 +287,10 @@ def pattern_mip_chain(texels, levels=None):
     return out
 
 
+# the same chain for a projector's texture (native.set_projector_texture takes the list; ilm_ctx_set_projector_texture_mips has the layout)
+projector_mip_chain = pattern_mip_chain
+
+
 FORMULA_LINEAR, FORMULA_SPHERICAL, FORMULA_TOWARDS, FORMULA_RECTANGULAR = 0, 1, 2, 3
 
 

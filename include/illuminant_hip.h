@@ -34,7 +34,8 @@ extern "C" {
  * removed): + ilm_visualize_distance_field / IlmVisualizeVertex, IlmVisualizeParams, ILM_VISUALIZE_* (distance-field views);
  * + ilm_render_directional_lights (directional lights; no new struct: the reference packs them into a LightVertex);
  * + ilm_ctx_set_projector_texture, ilm_render_projector_lights (projector lights; a LightVertex again);
- * + ilm_render_line_lights (line lights; a LightVertex again); + ilm_render_volumetric_lights (volumetric lights; likewise).
+ * + ilm_render_line_lights (line lights; a LightVertex again); + ilm_render_volumetric_lights (volumetric lights; likewise);
+ * + ilm_ctx_set_projector_texture_mips (a projector texture's mip chain, fetched trilinearly at the light's mip bias).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -876,6 +877,16 @@ int32_t ilm_render_line_lights(IlmHandle ctx,
  * texture bound over as many calls and frames as it serves and binds only when the group's texture changes. */
 int32_t ilm_ctx_set_projector_texture(IlmHandle ctx, const IlmFloat4* texels, int32_t width, int32_t height);
 
+/* The same binding with a mip chain (a Texture2D with LevelCount > 1; the reference's texture loader, which builds the chain, is outside
+ * the tree: the levels are an input, as for ilm_system_set_spawn_pattern, whose layout and limits these are).  `texels` holds `levels`
+ * levels back to back, level l being max(1, width >> l) x max(1, height >> l) float4 texels, row-major; levels in [0, 16] (else
+ * ILM_ERR_OUT_OF_RANGE), sides in [1, 16384] and texels != NULL when levels > 0 (else ILM_ERR_INVALID_ARGUMENT).  levels == 0 or
+ * width == 0 (with height == 0) unbinds; levels == 1 IS ilm_ctx_set_projector_texture(ctx, texels, width, height).  There is one projector
+ * binding: either setter replaces what the other bound.  Copy and ordering as above (waits for the context's queued work, copies
+ * synchronously); a refused call leaves the binding as it was; the ramp binding is neither read nor changed.  How the levels are read:
+ * "Texture fetch" under ilm_render_projector_lights. */
+int32_t ilm_ctx_set_projector_texture_mips(IlmHandle ctx, const IlmFloat4* texels, int32_t width, int32_t height, int32_t levels);
+
 /* The projector-light pass of LightingRenderer.RenderLighting: technique ProjectorLight (Illuminant/Shaders/ProjectorLight.fx:14-56 over
  * ProjectorLightCore.fxh), one quad per light, added onto the lightmap like every other light type.  The arguments mean what they mean
  * for ilm_render_directional_lights: gbuffer == 0 => ground plane, sdf == 0 => no distance field (which is the technique
@@ -907,10 +918,19 @@ int32_t ilm_ctx_set_projector_texture(IlmHandle ctx, const IlmFloat4* texels, in
  *   LightProperties.w * enableShadows != 0 and that opacity >= 0.75 / 255 -- the sphere light's coneTrace from p + 1.5 * normal towards
  *   origin.xyz with lightRamp = (Radius, RampLength) and cone growth 1;
  *   rgb added = (tex.rgb * tex.a) * opacity, alpha + 1, with tex = the texture at (t.x, t.y).
- * Texture fetch: tex2Dlod(ProjectorTextureSampler, (u, v, 0, mipBias)) on the bound one-level texture -- every LOD reads level 0, as a
- * sampler does for a texture without a mip chain (mip chains are not built: the bias is carried and not read).  LINEAR: s = u * width -
+ * Texture fetch: tex2Dlod(ProjectorTextureSampler, (u, v, 0, lod)) with lod = Color2.w (the mip bias RenderProjectorLightSource packs,
+ * LightingRenderer.cs:1417-1428) and MipFilter, MinFilter, MagFilter all LINEAR (ProjectorLightCore.fxh:9-18), over the L levels bound
+ * (L = 1 after ilm_ctx_set_projector_texture; mip chains come from ilm_ctx_set_projector_texture_mips).  fp32, one rounding per operation:
+ *   c = fminf(fmaxf(lod, 0), L - 1) -- a NaN lod becomes 0 through fmaxf, an infinite one clamps;
+ *   l0 = (int)floorf(c); f = c - floorf(c); l1 = min(l0 + 1, L - 1);
+ *   c0 = the bilinear fetch below on level l0, with that level's own width and height;
+ *   f == 0: tex = c0 and level l1 is NOT read (one level, an integral lod and a clamped lod are exact; no texel of l1 can show);
+ *   otherwise c1 = the same fetch on level l1 and tex = c0 + (c1 - c0) * f per component.
+ * With L = 1 every lod reads level 0, as a sampler does for a texture without a chain.  DEFINED DEVIATION: a hardware sampler's
+ * trilinear (and bilinear) weights are fixed-point; these are the fp32 values above, and parity with a D3D9 sampler's rounding is not
+ * pinned.  The bilinear fetch on a level of width x height texels -- LINEAR: s = u * width -
  * 0.5, first tap floor(s), weight s - floor(s), second tap = the integer first tap + 1; WRAP: both taps modulo the size in exact
- * integer arithmetic for every finite coordinate, tap 0 for a non-finite one; the same on v.  Every index lies inside the texture.
+ * integer arithmetic for every finite coordinate, tap 0 for a non-finite one; the same on v.  Every index lies inside the level.
  * Discards: a pixel outside the footprint, a fullbright pixel and one that is not `visible` get nothing from the light -- no rgb and
  * no + 1 on alpha.  No shadow filter (the shader never calls it) and no opacity discard: a visible pixel whose opacity is 0 adds alpha 1.
  * Coverage -- the reference leaves it to the rasteriser; here, as for directional lights: pixel (x, y) is covered iff its centre lies
@@ -921,9 +941,9 @@ int32_t ilm_ctx_set_projector_texture(IlmHandle ctx, const IlmFloat4* texels, in
  * each divided by its w; min / max (minNum / maxNum) over the eight points from 999999 / -999999; the quad's corners lerp(tl, br, 0 / 1);
  * y padded by -/+ MaximumZ * ZToYMultiplier.  A light whose rectangle comes out NaN or inverted on an axis covers nothing.
  * Statistics: PixelLightPairs = pairs inside a footprint and the image; TracedPairs = pairs that trace with a bound field (sdf != 0,
- * Extent.x > 0); SdfSamples = ambient-occlusion + cone-trace samples.
+ * Extent.x > 0); SdfSamples = ambient-occlusion + cone-trace samples.  Texture taps are not counted, with one level or many.
  * Not built: the light-probe technique (ProjectorLightProbe.fx), ProjectorLightWithoutDistanceField as a technique of its own (sdf == 0
- * is it), mip chains, the group entry point. */
+ * is it), the group entry point. */
 int32_t ilm_render_projector_lights(IlmHandle ctx,
                                     const IlmLightVertex* lights, int32_t light_count,
                                     const IlmEnvironment* env,

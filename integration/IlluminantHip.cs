@@ -604,6 +604,7 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_directional_lights (ulong ctx, LightVertex* lights, int lightCount, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong gbuffer, ulong sdf, float* ambient, ulong lightmap, int rowBegin, int rowEnd, IlmRenderStats* stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_line_lights (ulong ctx, LightVertex* lights, int lightCount, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong gbuffer, ulong sdf, float* ambient, ulong lightmap, int rowBegin, int rowEnd, IlmRenderStats* stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_ctx_set_projector_texture (ulong ctx, Vector4* texels, int width, int height);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_ctx_set_projector_texture_mips (ulong ctx, Vector4* texels, int width, int height, int levels);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_projector_lights (ulong ctx, LightVertex* lights, int lightCount, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong gbuffer, ulong sdf, float* ambient, ulong lightmap, int rowBegin, int rowEnd, IlmRenderStats* stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_volumetric_lights (ulong ctx, LightVertex* lights, int lightCount, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong gbuffer, ulong sdf, float* ambient, ulong lightmap, int rowBegin, int rowEnd, IlmRenderStats* stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_ctx_set_light_ramp (ulong ctx, Vector4* texels, int width, int height);
