@@ -32,6 +32,8 @@ STEP_COUNT_LIVE = 1
 SDF_UNORM16, SDF_FP16 = 0, 1
 GBUFFER_FLOAT4, GBUFFER_HALF4 = 0, 1
 LIGHTMAP_FLOAT4, LIGHTMAP_HALF4, LIGHTMAP_RGBA8 = 0, 1, 2
+# ILM_LIGHT_BLEND_*: a light group's blend function (ilm_ctx_set_light_blend_function), for rgb and for alpha
+LIGHT_BLEND_ADD, LIGHT_BLEND_REVERSE_SUBTRACT, LIGHT_BLEND_MAX, LIGHT_BLEND_MIN = 0, 1, 2, 3
 PLANE_POSITION, PLANE_VELOCITY, PLANE_ATTRIBUTES, PLANE_RENDER_COLOR, PLANE_RENDER_DATA = 0, 1, 2, 3, 4
 
 Handle = C.c_uint64

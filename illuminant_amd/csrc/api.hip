@@ -109,6 +109,7 @@ struct Ctx {
     DeviceScratch d_projector_texture; int projector_texture_w = 0, projector_texture_h = 0;
     ProjectorMips projector_mips = {};    // the bound chain's levels (ilm_ctx_set_projector_texture_mips); levels <= 1: the one-level pass
     int lightmap_blend = 0;               // ILM_BLEND_FP32_ACCUMULATE / ILM_BLEND_FP16_PER_LIGHT (ilm_ctx_set_lightmap_blend)
+    int light_blend_color = ILM_LIGHT_BLEND_ADD, light_blend_alpha = ILM_LIGHT_BLEND_ADD;      // ilm_ctx_set_light_blend_function: rgb | a of the calls that follow
     RasterScratch raster;                                         // particle rasteriser buffers (raster.hip)
     DeviceScratch d_raster_quads;
     // particle read-back: draw-call records, total, block counts, per-chunk element counts
@@ -2923,8 +2924,9 @@ int32_t plan_light_split(Ctx* c, LightLaunch* a) {
     const int slots = light_block_slots(*a);
     a->taper[0] = a->taper[1] = a->taper[2] = slots; a->taper_slots = slots;
     const int64_t tiles = (int64_t)((a->width + kLightTile - 1) / kLightTile) * (int64_t)((rows + kLightTile - 1) / kLightTile);
-    // one list per tile (<= 1 024 lights; device-side counts are particle lights: thousands), and no per-light fp16 rounding chain
-    if (a->blend_fp16 || a->light_count_ptr != nullptr || a->light_count > 1024 || a->light_count < 16) return ILM_OK;
+    // one list per tile (<= 1 024 lights; device-side counts are particle lights: thousands), and no per-light fp16 rounding chain;
+    // a launch with a non-additive blend function is served by one workgroup per tile (the partial hand-off carries sums)
+    if (a->blend_fp16 || a->blend_color != ILM_LIGHT_BLEND_ADD || a->blend_alpha != ILM_LIGHT_BLEND_ADD || a->light_count_ptr != nullptr || a->light_count > 1024 || a->light_count < 16) return ILM_OK;
     // f[i]: the fraction of an XCD's tiles from which on a tile is served by 2, 4 and 8 workgroups (1 = never)
     const int k = c->light_split;
     double f[3];
@@ -3074,6 +3076,7 @@ int32_t fill_light_launch(Ctx* c, const IlmEnvironment* env, const IlmDistanceFi
     a->stats = nullptr; a->light_count_ptr = nullptr; a->accumulate = 0;
     a->ramp = RampView{ nullptr, 0, 0 };      // particle lights have no ramp technique (LightingRenderer.cs:176-178)
     a->blend_fp16 = (c->lightmap_blend == ILM_BLEND_FP16_PER_LIGHT) ? 1 : 0;
+    a->blend_color = (int16_t)c->light_blend_color; a->blend_alpha = (int16_t)c->light_blend_alpha;
     a->tile_macro = light_tile_macro_for(m->width, row_end - row_begin);
     a->split = 1; a->partials = nullptr; a->tickets = nullptr; a->group_order = nullptr;
     { const int32_t rc = set_launch_mirrors(m, a); if (rc != ILM_OK) return rc; }
@@ -3331,6 +3334,16 @@ int32_t ilm_ctx_set_lightmap_blend(IlmHandle hctx, int32_t mode) {
     if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
     if (mode != ILM_BLEND_FP32_ACCUMULATE && mode != ILM_BLEND_FP16_PER_LIGHT) return fail(ILM_ERR_INVALID_ARGUMENT, "unknown lightmap blend mode %d", mode);
     c->lightmap_blend = mode;
+    return ILM_OK;
+}
+
+int32_t ilm_ctx_set_light_blend_function(IlmHandle hctx, int32_t color_function, int32_t alpha_function) {
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    auto known = [](int32_t f) { return f == ILM_LIGHT_BLEND_ADD || f == ILM_LIGHT_BLEND_REVERSE_SUBTRACT || f == ILM_LIGHT_BLEND_MAX || f == ILM_LIGHT_BLEND_MIN; };
+    if (!known(color_function) || !known(alpha_function))
+        return fail(ILM_ERR_INVALID_ARGUMENT, "unknown light blend function (colour %d, alpha %d)", color_function, alpha_function);
+    c->light_blend_color = color_function; c->light_blend_alpha = alpha_function;
     return ILM_OK;
 }
 
@@ -3813,6 +3826,7 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     a.accumulate = ambient ? 0 : 1;          // a further light group of the frame: added to what the lightmap holds
     a.ramp = RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h };
     a.blend_fp16 = (c->lightmap_blend == ILM_BLEND_FP16_PER_LIGHT) ? 1 : 0;
+    a.blend_color = (int16_t)c->light_blend_color; a.blend_alpha = (int16_t)c->light_blend_alpha;
     a.tile_macro = light_tile_macro_for(m->width, row_end - row_begin);
     if (stats) {
         HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));

@@ -211,7 +211,12 @@ struct LightLaunch {
     // `mirror_count` other buffers -- the other members' copies of the frame, peer-mapped over xGMI -- so the strips need no gather phase.
     void* const* mirrors;           // device array of mirror_count base pointers (nullptr / 0: an ordinary lightmap)
     int32_t mirror_count;
+    // ILM_LIGHT_BLEND_* of the call's rgb and of its alpha (ilm_ctx_set_light_blend_function).  Anything but ADD / ADD runs the BLEND
+    // instantiations of the pass's kernel; the additive ones never read the pair.  (Two halves of the word that padded the descriptor
+    // to its alignment: no member and no kernel argument moved.)
+    int16_t blend_color, blend_alpha;
 };
+static_assert(sizeof(LightLaunch) == 456, "the blend functions fill the descriptor's tail padding: the kernels' argument offsets stay where they were");
 // A tile's light list is summed in kLightParts consecutive parts (entries [p n / 8, (p + 1) n / 8) of a list of n), each part from zero in
 // light order, the parts added onto the clear colour in part order: the sum's bits depend on the tile and its list only, not on how
 // many workgroups computed the parts.

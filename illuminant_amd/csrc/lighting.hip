@@ -468,6 +468,52 @@ constexpr int kTile = kLightTile;                   // internal.hpp
 constexpr int kLightThreads = kLightTileThreads;
 constexpr int kListCapacity = 1024;
 
+// ---------------------------------------------------------------------------------------------
+// Light blend functions (ilm_ctx_set_light_blend_function; the header has the contract) -- one channel of the BLEND instantiations of
+// the light kernels, f the channel's ILM_LIGHT_BLEND_* (wave-uniform: a scalar compare and branch per use).  The additive
+// instantiations (BLEND = false) do not call these: their instruction streams are what they were.
+// MAX / MIN are comparisons and selects, not fmaxf / fminf: a NaN source is never selected, a NaN base is kept.
+// ---------------------------------------------------------------------------------------------
+// A BLEND instantiation is named by its field format + kBlendVariant in the kernel's first template argument: the additive
+// instantiations keep the names they had (<FMT, STATS[, WIDE_BIN]>: what profiles and tools look kernels up by).
+constexpr int kBlendVariant = 2;
+static_assert((ILM_SDF_UNORM16 & kBlendVariant) == 0 && (ILM_SDF_FP16 & kBlendVariant) == 0, "the field formats leave the variant bit free");
+// what a channel's running value starts from in the fp32 model (a part, a call)
+ILM_DEV float blend_identity(int f) {
+    return (f == ILM_LIGHT_BLEND_MAX) ? -__builtin_inff() : (f == ILM_LIGHT_BLEND_MIN) ? __builtin_inff() : 0.0f;
+}
+// a contributing pair's value c -- or a later part's running value -- into the running value (fp32 model); REVERSE_SUBTRACT gathers
+// the sum ADD forms
+ILM_DEV float blend_gather(int f, float running, float c) {
+    if (f == ILM_LIGHT_BLEND_MAX) return (c > running) ? c : running;
+    if (f == ILM_LIGHT_BLEND_MIN) return (c < running) ? c : running;
+    return running + c;
+}
+// the call's running value onto the base value (fp32 model): one operation, one rounding
+ILM_DEV float blend_onto_base(int f, float base, float running) {
+    if (f == ILM_LIGHT_BLEND_MAX) return (running > base) ? running : base;
+    if (f == ILM_LIGHT_BLEND_MIN) return (running < base) ? running : base;
+    if (f == ILM_LIGHT_BLEND_REVERSE_SUBTRACT) return base - running;
+    return base + running;
+}
+// one pair in the fp16-per-light model: dst (an fp16 value) and s = half(c)
+ILM_DEV float blend_half_step(int f, float dst, float c) {
+    const float s = __half2float(__float2half_rn(c));
+    if (f == ILM_LIGHT_BLEND_MAX) return (s > dst) ? s : dst;
+    if (f == ILM_LIGHT_BLEND_MIN) return (s < dst) ? s : dst;
+    return __half2float(__float2half_rn((f == ILM_LIGHT_BLEND_REVERSE_SUBTRACT) ? dst - s : dst + s));
+}
+// the pair (cr, cg, cb, 1) into the four running values of a BLEND instantiation, in the call's model
+ILM_DEV void blend_pair(int fc, int fa, bool blend_fp16, float cr, float cg, float cb, float& acc_r, float& acc_g, float& acc_b, float& acc_a) {
+    if (blend_fp16) {
+        acc_r = blend_half_step(fc, acc_r, cr); acc_g = blend_half_step(fc, acc_g, cg); acc_b = blend_half_step(fc, acc_b, cb);
+        acc_a = blend_half_step(fa, acc_a, 1.0f);
+    } else {
+        acc_r = blend_gather(fc, acc_r, cr); acc_g = blend_gather(fc, acc_g, cg); acc_b = blend_gather(fc, acc_b, cb);
+        acc_a = blend_gather(fa, acc_a, 1.0f);
+    }
+}
+
 // Eight waves per SIMD (64 VGPRs; the fp16 kernel without scratch, the unorm16 one with 8 bytes outside the loop).  History, tools/ab_lib.sh:
 // r02, table-driven sampler: five waves (81 VGPRs, the allocator's own need) cfg5 11.93 ms, six 11.26, seven 10.89, eight (48 bytes of
 // scratch) 10.93.  r03, cell array + exact skips + tile groups: six 9.29, seven 8.82, eight 8.67 on cfg5 but 0.61 -> 0.66 on cfg3 (spills
@@ -476,8 +522,14 @@ constexpr int kListCapacity = 1024;
 // WIDE_BIN: the tile list is built by all the workgroup's waves, 256 lights per round (frames of particle lights: thousands per tile);
 // otherwise by wave 0 alone, 64 per round, while the others wait -- a frame of a few hundred lights bins in 1-4 rounds either way, and
 // the wide form's extra code costs the sphere-light frames 1-2 % through register allocation, so it is its own instantiation.
-template <int FMT, bool STATS, bool WIDE_BIN>
+// BLEND (VARIANT = the field format + kBlendVariant): the launch's blend functions are not ADD / ADD (blend_pair and its neighbours
+// above; the functions are read from the launch descriptor where they are used).  An instantiation of its own for the same reason:
+// with BLEND = false every line it adds is compiled out.  Such a launch comes with one workgroup per tile (api.hip plan_light_split),
+// so the partial hand-off only ever carries sums.
+template <int VARIANT, bool STATS, bool WIDE_BIN>
 __global__ __launch_bounds__(kLightThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void sphere_lights_kernel(const LightLaunch a, const LightRec* __restrict__ recs, int tiles_x, int tiles_y, int tile_count) {
+    constexpr int FMT = VARIANT & ~kBlendVariant;
+    constexpr bool BLEND = (VARIANT & kBlendVariant) != 0;
     __shared__ uint16_t list[kListCapacity];
     __shared__ int list_count;
     __shared__ int bin_count[2][kLightThreads / 64];
@@ -622,6 +674,7 @@ __global__ __launch_bounds__(kLightThreads) __attribute__((amdgpu_waves_per_eu(8
     const bool blend_fp16 = a.blend_fp16 != 0;
     // the running sum of the current part of the light list (the whole chain in the fp16-per-light model)
     float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if constexpr (BLEND) { acc_r = acc_g = acc_b = blend_identity(a.blend_color); acc_a = blend_identity(a.blend_alpha); }
     if (blend_fp16) { const float4 v = base_value(a); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
     // wave-uniform: every pixel of this wave has a flat normal (no G-buffer, or ground / top-face texels): the normal factor needs one
     // component of the light direction instead of three (sphere_light_opacity<.., FLAT>)
@@ -653,13 +706,20 @@ __global__ __launch_bounds__(kLightThreads) __attribute__((amdgpu_waves_per_eu(8
         int r = part - part_first, level = 0;
         while (r & 1) {
             const float4 left = tree[level][threadIdx.x];
-            acc_r = left.x + acc_r; acc_g = left.y + acc_g; acc_b = left.z + acc_b; acc_a = left.w + acc_a;
+            if constexpr (BLEND) {
+                const int fc = kernargs().blend_color, fa = kernargs().blend_alpha;
+                acc_r = blend_gather(fc, left.x, acc_r); acc_g = blend_gather(fc, left.y, acc_g); acc_b = blend_gather(fc, left.z, acc_b);
+                acc_a = blend_gather(fa, left.w, acc_a);
+            } else {
+                acc_r = left.x + acc_r; acc_g = left.y + acc_g; acc_b = left.z + acc_b; acc_a = left.w + acc_a;
+            }
             level++; r >>= 1;
         }
         part++;
         if (part < part_end) {
             tree[level][threadIdx.x] = mk4(acc_r, acc_g, acc_b, acc_a);
             acc_r = 0.0f; acc_g = 0.0f; acc_b = 0.0f; acc_a = 0.0f;
+            if constexpr (BLEND) { acc_r = acc_g = acc_b = blend_identity(kernargs().blend_color); acc_a = blend_identity(kernargs().blend_alpha); }
         }       // else: the member's subtree is summed, its root stays in the registers
     };
     int part_bound = blend_fp16 ? 0x7FFFFFFF : (int)(((long long)light_count * (part + 1)) / kLightParts);   // first light of the next part
@@ -792,7 +852,9 @@ __global__ __launch_bounds__(kLightThreads) __attribute__((amdgpu_waves_per_eu(8
             float cr, cg, cb;
             if (!shade_light<FMT, STATS>(P, L, env_k, field, have_sdf, ramp_k, st, cr, cg, cb, flat_normals))
                 continue;
-            if (blend_fp16) {      // dst = half(float(dst) + float(half(src))): the shader's output is converted to the target format, then blended
+            if constexpr (BLEND) {
+                blend_pair(A.blend_color, A.blend_alpha, blend_fp16, cr, cg, cb, acc_r, acc_g, acc_b, acc_a);
+            } else if (blend_fp16) {      // dst = half(float(dst) + float(half(src))): the shader's output is converted to the target format, then blended
                 acc_r = through_half(acc_r + through_half(cr));
                 acc_g = through_half(acc_g + through_half(cg));
                 acc_b = through_half(acc_b + through_half(cb));
@@ -836,7 +898,13 @@ __global__ __launch_bounds__(kLightThreads) __attribute__((amdgpu_waves_per_eu(8
     }
     if (!blend_fp16) {
         const float4 v = base_value(kernargs());
-        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        if constexpr (BLEND) {
+            const int fc = kernargs().blend_color, fa = kernargs().blend_alpha;
+            acc_r = blend_onto_base(fc, v.x, acc_r); acc_g = blend_onto_base(fc, v.y, acc_g); acc_b = blend_onto_base(fc, v.z, acc_b);
+            acc_a = blend_onto_base(fa, v.w, acc_a);
+        } else {
+            acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        }
     }
 
     if (in_image) {
@@ -1220,6 +1288,7 @@ hipError_t launch_sphere_lights_prepared(const LightLaunch& launch, const void* 
     const int tile_count = tiles_x * tiles_y;
     const int slots = light_block_slots(a);
     if (a.split <= 1) { a.split = 1; a.taper[0] = a.taper[1] = a.taper[2] = slots; a.taper_slots = slots; }     // one workgroup per tile throughout
+    if (a.split > 1 && (a.blend_color != ILM_LIGHT_BLEND_ADD || a.blend_alpha != ILM_LIGHT_BLEND_ADD)) return hipErrorInvalidValue;      // (planned so: the hand-off adds)
     const int t0 = a.taper[0], t1 = a.taper[1], t2 = a.taper[2];
     if (a.taper_slots != slots || t0 < 0 || t0 > t1 || t1 > t2 || t2 > slots) return hipErrorInvalidValue;
     const int per_xcd_blocks = t0 + 2 * (t1 - t0) + 4 * (t2 - t1) + 8 * (slots - t2);
@@ -1227,7 +1296,11 @@ hipError_t launch_sphere_lights_prepared(const LightLaunch& launch, const void* 
     const bool stats = a.stats != nullptr;
     const bool fp16 = a.sdf.format == ILM_SDF_FP16;
     const dim3 grid(per_xcd_blocks * 8), block(kLightThreads);
-#define ILM_LAUNCH_LIGHTS(F, S, W) hipLaunchKernelGGL((sphere_lights_kernel<F, S, W>), grid, block, 0, stream, a, r, tiles_x, tiles_y, tile_count)
+    // anything but ADD / ADD: the BLEND instantiation of the same variant
+    const bool blend = a.blend_color != ILM_LIGHT_BLEND_ADD || a.blend_alpha != ILM_LIGHT_BLEND_ADD;
+#define ILM_LAUNCH_LIGHTS(F, S, W) do { \
+        if (blend) hipLaunchKernelGGL((sphere_lights_kernel<F + kBlendVariant, S, W>), grid, block, 0, stream, a, r, tiles_x, tiles_y, tile_count); \
+        else hipLaunchKernelGGL((sphere_lights_kernel<F, S, W>), grid, block, 0, stream, a, r, tiles_x, tiles_y, tile_count); } while (0)
     // device-side counts are particle lights: thousands
     const bool wide = (a.light_count_ptr != nullptr) || (a.light_count > 512);
     const int variant = (wide ? 4 : 0) | (fp16 ? 2 : 0) | (stats ? 1 : 0);
@@ -1252,7 +1325,9 @@ hipError_t launch_sphere_lights_prepared(const LightLaunch& launch, const void* 
 // the launcher.  Each kernel states its own pixel mapping, base value, blend chains and light loop: as device functions these change
 // the instruction streams of the kernels, and the passes then run up to 3 % slower (docs/experiments.md 7.24).  A change to one of
 // those parts is made in directional_lights_kernel, projector_lights_kernel, projector_mip_lights_kernel, line_lights_kernel and
-// volumetric_lights_kernel alike.
+// volumetric_lights_kernel alike.  The BLEND instantiations (a launch whose blend functions are not ADD / ADD) are such a change:
+// the same three lines in each of the five -- the identities, blend_pair, blend_onto_base -- compiled out where BLEND is false
+// (VARIANT = the field format, + kBlendVariant for BLEND).
 // ---------------------------------------------------------------------------------------------
 // the texel into the lightmap and into every mirror (store-mode exchange of a group lightmap, as the sphere pass)
 ILM_DEV void store_light_texel(const LightLaunch& a, size_t o, const float4& v) {
@@ -1284,13 +1359,16 @@ template <class Rec>
 using FullFrameKernel = void (*)(LightLaunch, const Rec*, int);
 template <class Rec>
 hipError_t launch_full_frame_lights(const LightLaunch& a, const void* recs, hipStream_t stream, FullFrameKernel<Rec> fp16, FullFrameKernel<Rec> fp16_stats,
-                                    FullFrameKernel<Rec> unorm16, FullFrameKernel<Rec> unorm16_stats) {
+                                    FullFrameKernel<Rec> unorm16, FullFrameKernel<Rec> unorm16_stats, const FullFrameKernel<Rec> (&blend)[4]) {
     const int rows = a.row_end - a.row_begin;
     if (rows <= 0 || a.width <= 0) return hipSuccess;
     if (a.light_count == 0 && a.accumulate != 0) return hipSuccess;      // nothing to add: no texel (and no mirror) would change
     const int tiles_x = (a.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
     const bool stats = a.stats != nullptr;
-    const FullFrameKernel<Rec> kernel = (a.sdf.format == ILM_SDF_FP16) ? (stats ? fp16_stats : fp16) : (stats ? unorm16_stats : unorm16);
+    FullFrameKernel<Rec> kernel = (a.sdf.format == ILM_SDF_FP16) ? (stats ? fp16_stats : fp16) : (stats ? unorm16_stats : unorm16);
+    // anything but ADD / ADD: the BLEND instantiation of the same variant (in the order of the four above)
+    if (a.blend_color != ILM_LIGHT_BLEND_ADD || a.blend_alpha != ILM_LIGHT_BLEND_ADD)
+        kernel = blend[((a.sdf.format == ILM_SDF_FP16) ? 0 : 2) + (stats ? 1 : 0)];
     hipLaunchKernelGGL(kernel, dim3((unsigned)tiles_x * (unsigned)tiles_y), dim3(kLightThreads), 0, stream, a, reinterpret_cast<const Rec*>(recs), tiles_x);
     return hipGetLastError();
 }
@@ -1424,8 +1502,10 @@ ILM_DEV bool shade_directional(const Pixel& P, const DirectionalRec& L, const Tr
     return true;
 }
 
-template <int FMT, bool STATS>
+template <int VARIANT, bool STATS>
 __global__ __launch_bounds__(kLightThreads) void directional_lights_kernel(const LightLaunch a, const DirectionalRec* __restrict__ recs, int tiles_x) {
+    constexpr int FMT = VARIANT & ~kBlendVariant;
+    constexpr bool BLEND = (VARIANT & kBlendVariant) != 0;
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int tile_x = (int)blockIdx.x % tiles_x, tile_y = (int)blockIdx.x / tiles_x;
     const int px = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
@@ -1455,6 +1535,7 @@ __global__ __launch_bounds__(kLightThreads) void directional_lights_kernel(const
     };
     const bool blend_fp16 = a.blend_fp16 != 0;
     float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if constexpr (BLEND) { acc_r = acc_g = acc_b = blend_identity(a.blend_color); acc_a = blend_identity(a.blend_alpha); }
     if (blend_fp16) { const float4 v = base_value(); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
     LightStats st;
     const int light_count = a.light_count;
@@ -1472,7 +1553,9 @@ __global__ __launch_bounds__(kLightThreads) void directional_lights_kernel(const
         if (!shade_directional<FMT, STATS>(P, L, field, have_sdf, a.ramp, st, opacity))
             continue;
         const float cr = L.col_r * opacity, cg = L.col_g * opacity, cb = L.col_b * opacity;
-        if (blend_fp16) {
+        if constexpr (BLEND) {
+            blend_pair(a.blend_color, a.blend_alpha, blend_fp16, cr, cg, cb, acc_r, acc_g, acc_b, acc_a);
+        } else if (blend_fp16) {
             acc_r = through_half(acc_r + through_half(cr));
             acc_g = through_half(acc_g + through_half(cg));
             acc_b = through_half(acc_b + through_half(cb));
@@ -1483,7 +1566,12 @@ __global__ __launch_bounds__(kLightThreads) void directional_lights_kernel(const
     }
     if (!blend_fp16) {
         const float4 v = base_value();
-        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        if constexpr (BLEND) {
+            acc_r = blend_onto_base(a.blend_color, v.x, acc_r); acc_g = blend_onto_base(a.blend_color, v.y, acc_g);
+            acc_b = blend_onto_base(a.blend_color, v.z, acc_b); acc_a = blend_onto_base(a.blend_alpha, v.w, acc_a);
+        } else {
+            acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        }
     }
     if (in_image) {
         const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
@@ -1501,8 +1589,10 @@ hipError_t launch_prepare_directional_lights(const IlmLightVertex* lights, int c
 }
 
 hipError_t launch_directional_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
+    static const FullFrameKernel<DirectionalRec> blend[4] = { directional_lights_kernel<ILM_SDF_FP16 + kBlendVariant, false>, directional_lights_kernel<ILM_SDF_FP16 + kBlendVariant, true>,
+                                                  directional_lights_kernel<ILM_SDF_UNORM16 + kBlendVariant, false>, directional_lights_kernel<ILM_SDF_UNORM16 + kBlendVariant, true> };
     return launch_full_frame_lights<DirectionalRec>(a, recs, stream, directional_lights_kernel<ILM_SDF_FP16, false>, directional_lights_kernel<ILM_SDF_FP16, true>,
-                                           directional_lights_kernel<ILM_SDF_UNORM16, false>, directional_lights_kernel<ILM_SDF_UNORM16, true>);
+                                           directional_lights_kernel<ILM_SDF_UNORM16, false>, directional_lights_kernel<ILM_SDF_UNORM16, true>, blend);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1764,8 +1854,10 @@ ILM_DEV bool shade_projector(const Pixel& P, const ProjectorRec& L, const TraceF
 }
 
 // (pixel mapping, base value and blend chains as in directional_lights_kernel: see the note at the head of the full-frame passes)
-template <int FMT, bool STATS>
+template <int VARIANT, bool STATS>
 __global__ __launch_bounds__(kLightThreads) void projector_lights_kernel(const LightLaunch a, const ProjectorRec* __restrict__ recs, int tiles_x) {
+    constexpr int FMT = VARIANT & ~kBlendVariant;
+    constexpr bool BLEND = (VARIANT & kBlendVariant) != 0;
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int tile_x = (int)blockIdx.x % tiles_x, tile_y = (int)blockIdx.x / tiles_x;
     const int px = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
@@ -1793,6 +1885,7 @@ __global__ __launch_bounds__(kLightThreads) void projector_lights_kernel(const L
     };
     const bool blend_fp16 = a.blend_fp16 != 0;
     float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if constexpr (BLEND) { acc_r = acc_g = acc_b = blend_identity(a.blend_color); acc_a = blend_identity(a.blend_alpha); }
     if (blend_fp16) { const float4 v = base_value(); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
     LightStats st;
     const int light_count = a.light_count;
@@ -1808,7 +1901,9 @@ __global__ __launch_bounds__(kLightThreads) void projector_lights_kernel(const L
         float cr, cg, cb;
         if (!shade_projector<FMT, STATS, false>(P, L, field, have_sdf, a.ramp, st, cr, cg, cb))
             continue;
-        if (blend_fp16) {
+        if constexpr (BLEND) {
+            blend_pair(a.blend_color, a.blend_alpha, blend_fp16, cr, cg, cb, acc_r, acc_g, acc_b, acc_a);
+        } else if (blend_fp16) {
             acc_r = through_half(acc_r + through_half(cr));
             acc_g = through_half(acc_g + through_half(cg));
             acc_b = through_half(acc_b + through_half(cb));
@@ -1819,7 +1914,12 @@ __global__ __launch_bounds__(kLightThreads) void projector_lights_kernel(const L
     }
     if (!blend_fp16) {
         const float4 v = base_value();
-        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        if constexpr (BLEND) {
+            acc_r = blend_onto_base(a.blend_color, v.x, acc_r); acc_g = blend_onto_base(a.blend_color, v.y, acc_g);
+            acc_b = blend_onto_base(a.blend_color, v.z, acc_b); acc_a = blend_onto_base(a.blend_alpha, v.w, acc_a);
+        } else {
+            acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        }
     }
     if (in_image) {
         const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
@@ -1831,8 +1931,10 @@ __global__ __launch_bounds__(kLightThreads) void projector_lights_kernel(const L
 // The same kernel over a mip chain: the records are prepare_projector_mips_kernel's, the fetch sample_projector_mips.  A copy of the frame,
 // as each full-frame pass has its own (the note at their head): as a device function shared with projector_lights_kernel the frame changed
 // that kernel's schedule (tools/isa_compare.py: four of four `diff`, same counts), which the one-level pass is held not to do.
-template <int FMT, bool STATS>
+template <int VARIANT, bool STATS>
 __global__ __launch_bounds__(kLightThreads) void projector_mip_lights_kernel(const LightLaunch a, const ProjectorRec* __restrict__ recs, int tiles_x) {
+    constexpr int FMT = VARIANT & ~kBlendVariant;
+    constexpr bool BLEND = (VARIANT & kBlendVariant) != 0;
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int tile_x = (int)blockIdx.x % tiles_x, tile_y = (int)blockIdx.x / tiles_x;
     const int px = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
@@ -1860,6 +1962,7 @@ __global__ __launch_bounds__(kLightThreads) void projector_mip_lights_kernel(con
     };
     const bool blend_fp16 = a.blend_fp16 != 0;
     float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if constexpr (BLEND) { acc_r = acc_g = acc_b = blend_identity(a.blend_color); acc_a = blend_identity(a.blend_alpha); }
     if (blend_fp16) { const float4 v = base_value(); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
     LightStats st;
     const int light_count = a.light_count;
@@ -1875,7 +1978,9 @@ __global__ __launch_bounds__(kLightThreads) void projector_mip_lights_kernel(con
         float cr, cg, cb;
         if (!shade_projector<FMT, STATS, true>(P, L, field, have_sdf, a.ramp, st, cr, cg, cb))
             continue;
-        if (blend_fp16) {
+        if constexpr (BLEND) {
+            blend_pair(a.blend_color, a.blend_alpha, blend_fp16, cr, cg, cb, acc_r, acc_g, acc_b, acc_a);
+        } else if (blend_fp16) {
             acc_r = through_half(acc_r + through_half(cr));
             acc_g = through_half(acc_g + through_half(cg));
             acc_b = through_half(acc_b + through_half(cb));
@@ -1886,7 +1991,12 @@ __global__ __launch_bounds__(kLightThreads) void projector_mip_lights_kernel(con
     }
     if (!blend_fp16) {
         const float4 v = base_value();
-        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        if constexpr (BLEND) {
+            acc_r = blend_onto_base(a.blend_color, v.x, acc_r); acc_g = blend_onto_base(a.blend_color, v.y, acc_g);
+            acc_b = blend_onto_base(a.blend_color, v.z, acc_b); acc_a = blend_onto_base(a.blend_alpha, v.w, acc_a);
+        } else {
+            acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        }
     }
     if (in_image) {
         const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
@@ -1904,8 +2014,10 @@ hipError_t launch_prepare_projector_lights(const IlmLightVertex* lights, int cou
 }
 
 hipError_t launch_projector_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
+    static const FullFrameKernel<ProjectorRec> blend[4] = { projector_lights_kernel<ILM_SDF_FP16 + kBlendVariant, false>, projector_lights_kernel<ILM_SDF_FP16 + kBlendVariant, true>,
+                                                  projector_lights_kernel<ILM_SDF_UNORM16 + kBlendVariant, false>, projector_lights_kernel<ILM_SDF_UNORM16 + kBlendVariant, true> };
     return launch_full_frame_lights<ProjectorRec>(a, recs, stream, projector_lights_kernel<ILM_SDF_FP16, false>, projector_lights_kernel<ILM_SDF_FP16, true>,
-                                           projector_lights_kernel<ILM_SDF_UNORM16, false>, projector_lights_kernel<ILM_SDF_UNORM16, true>);
+                                           projector_lights_kernel<ILM_SDF_UNORM16, false>, projector_lights_kernel<ILM_SDF_UNORM16, true>, blend);
 }
 
 hipError_t launch_prepare_projector_mip_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
@@ -1918,9 +2030,11 @@ hipError_t launch_prepare_projector_mip_lights(const IlmLightVertex* lights, int
 }
 
 hipError_t launch_projector_mip_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
+    static const FullFrameKernel<ProjectorRec> blend[4] = { projector_mip_lights_kernel<ILM_SDF_FP16 + kBlendVariant, false>, projector_mip_lights_kernel<ILM_SDF_FP16 + kBlendVariant, true>,
+                                                  projector_mip_lights_kernel<ILM_SDF_UNORM16 + kBlendVariant, false>, projector_mip_lights_kernel<ILM_SDF_UNORM16 + kBlendVariant, true> };
     return launch_full_frame_lights<ProjectorRec>(a, recs, stream, projector_mip_lights_kernel<ILM_SDF_FP16, false>,
                                            projector_mip_lights_kernel<ILM_SDF_FP16, true>, projector_mip_lights_kernel<ILM_SDF_UNORM16, false>,
-                                           projector_mip_lights_kernel<ILM_SDF_UNORM16, true>);
+                                           projector_mip_lights_kernel<ILM_SDF_UNORM16, true>, blend);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2120,8 +2234,10 @@ ILM_DEV bool shade_line(const Pixel& P, const LineRec& L, const TraceField& F, b
 
 // (pixel mapping, base value and blend chains as in directional_lights_kernel: see the note at the head of the full-frame passes.)
 // No footprint: the vertex shader's quad, min(P) - 9999 .. max(P) + 9999, is defined here as every pixel of the rows.
-template <int FMT, bool STATS>
+template <int VARIANT, bool STATS>
 __global__ __launch_bounds__(kLightThreads) void line_lights_kernel(const LightLaunch a, const LineRec* __restrict__ recs, int tiles_x) {
+    constexpr int FMT = VARIANT & ~kBlendVariant;
+    constexpr bool BLEND = (VARIANT & kBlendVariant) != 0;
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int tile_x = (int)blockIdx.x % tiles_x, tile_y = (int)blockIdx.x / tiles_x;
     const int px = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
@@ -2148,6 +2264,7 @@ __global__ __launch_bounds__(kLightThreads) void line_lights_kernel(const LightL
     };
     const bool blend_fp16 = a.blend_fp16 != 0;
     float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if constexpr (BLEND) { acc_r = acc_g = acc_b = blend_identity(a.blend_color); acc_a = blend_identity(a.blend_alpha); }
     if (blend_fp16) { const float4 v = base_value(); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
     LightStats st;
     const int light_count = a.light_count;
@@ -2161,7 +2278,9 @@ __global__ __launch_bounds__(kLightThreads) void line_lights_kernel(const LightL
         float cr, cg, cb;
         if (!shade_line<FMT, STATS>(P, L, field, have_sdf, st, cr, cg, cb))
             continue;
-        if (blend_fp16) {
+        if constexpr (BLEND) {
+            blend_pair(a.blend_color, a.blend_alpha, blend_fp16, cr, cg, cb, acc_r, acc_g, acc_b, acc_a);
+        } else if (blend_fp16) {
             acc_r = through_half(acc_r + through_half(cr));
             acc_g = through_half(acc_g + through_half(cg));
             acc_b = through_half(acc_b + through_half(cb));
@@ -2172,7 +2291,12 @@ __global__ __launch_bounds__(kLightThreads) void line_lights_kernel(const LightL
     }
     if (!blend_fp16) {
         const float4 v = base_value();
-        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        if constexpr (BLEND) {
+            acc_r = blend_onto_base(a.blend_color, v.x, acc_r); acc_g = blend_onto_base(a.blend_color, v.y, acc_g);
+            acc_b = blend_onto_base(a.blend_color, v.z, acc_b); acc_a = blend_onto_base(a.blend_alpha, v.w, acc_a);
+        } else {
+            acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        }
     }
     if (in_image) {
         const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
@@ -2189,8 +2313,10 @@ hipError_t launch_prepare_line_lights(const IlmLightVertex* lights, int count, c
 }
 
 hipError_t launch_line_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
+    static const FullFrameKernel<LineRec> blend[4] = { line_lights_kernel<ILM_SDF_FP16 + kBlendVariant, false>, line_lights_kernel<ILM_SDF_FP16 + kBlendVariant, true>,
+                                                  line_lights_kernel<ILM_SDF_UNORM16 + kBlendVariant, false>, line_lights_kernel<ILM_SDF_UNORM16 + kBlendVariant, true> };
     return launch_full_frame_lights<LineRec>(a, recs, stream, line_lights_kernel<ILM_SDF_FP16, false>, line_lights_kernel<ILM_SDF_FP16, true>,
-                                           line_lights_kernel<ILM_SDF_UNORM16, false>, line_lights_kernel<ILM_SDF_UNORM16, true>);
+                                           line_lights_kernel<ILM_SDF_UNORM16, false>, line_lights_kernel<ILM_SDF_UNORM16, true>, blend);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2452,8 +2578,10 @@ ILM_DEV bool shade_volumetric(const Pixel& P, int px, int py, const VolumetricRe
 
 // (pixel mapping, base value, blend chains and footprint test as in directional_lights_kernel: see the note at the head of the full-frame
 // passes.)
-template <int FMT, bool STATS>
+template <int VARIANT, bool STATS>
 __global__ __launch_bounds__(kLightThreads) void volumetric_lights_kernel(const LightLaunch a, const VolumetricRec* __restrict__ recs, int tiles_x) {
+    constexpr int FMT = VARIANT & ~kBlendVariant;
+    constexpr bool BLEND = (VARIANT & kBlendVariant) != 0;
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int tile_x = (int)blockIdx.x % tiles_x, tile_y = (int)blockIdx.x / tiles_x;
     const int px = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
@@ -2481,6 +2609,7 @@ __global__ __launch_bounds__(kLightThreads) void volumetric_lights_kernel(const 
     };
     const bool blend_fp16 = a.blend_fp16 != 0;
     float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    if constexpr (BLEND) { acc_r = acc_g = acc_b = blend_identity(a.blend_color); acc_a = blend_identity(a.blend_alpha); }
     if (blend_fp16) { const float4 v = base_value(); acc_r = v.x; acc_g = v.y; acc_b = v.z; acc_a = v.w; }
     LightStats st;
     const int light_count = a.light_count;
@@ -2498,7 +2627,9 @@ __global__ __launch_bounds__(kLightThreads) void volumetric_lights_kernel(const 
         if (!shade_volumetric<FMT, STATS>(P, px, py, L, field, have_sdf, ground_z, maximum_z, st, opacity))
             continue;
         const float cr = L.col_r * opacity, cg = L.col_g * opacity, cb = L.col_b * opacity;
-        if (blend_fp16) {
+        if constexpr (BLEND) {
+            blend_pair(a.blend_color, a.blend_alpha, blend_fp16, cr, cg, cb, acc_r, acc_g, acc_b, acc_a);
+        } else if (blend_fp16) {
             acc_r = through_half(acc_r + through_half(cr));
             acc_g = through_half(acc_g + through_half(cg));
             acc_b = through_half(acc_b + through_half(cb));
@@ -2509,7 +2640,12 @@ __global__ __launch_bounds__(kLightThreads) void volumetric_lights_kernel(const 
     }
     if (!blend_fp16) {
         const float4 v = base_value();
-        acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        if constexpr (BLEND) {
+            acc_r = blend_onto_base(a.blend_color, v.x, acc_r); acc_g = blend_onto_base(a.blend_color, v.y, acc_g);
+            acc_b = blend_onto_base(a.blend_color, v.z, acc_b); acc_a = blend_onto_base(a.blend_alpha, v.w, acc_a);
+        } else {
+            acc_r = v.x + acc_r; acc_g = v.y + acc_g; acc_b = v.z + acc_b; acc_a = v.w + acc_a;
+        }
     }
     if (in_image) {
         const float4 v = mk4(acc_r, acc_g, acc_b, acc_a);
@@ -2528,9 +2664,11 @@ hipError_t launch_prepare_volumetric_lights(const IlmLightVertex* lights, int co
 }
 
 hipError_t launch_volumetric_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream) {
+    static const FullFrameKernel<VolumetricRec> blend[4] = { volumetric_lights_kernel<ILM_SDF_FP16 + kBlendVariant, false>, volumetric_lights_kernel<ILM_SDF_FP16 + kBlendVariant, true>,
+                                                  volumetric_lights_kernel<ILM_SDF_UNORM16 + kBlendVariant, false>, volumetric_lights_kernel<ILM_SDF_UNORM16 + kBlendVariant, true> };
     return launch_full_frame_lights<VolumetricRec>(a, recs, stream, volumetric_lights_kernel<ILM_SDF_FP16, false>,
                                                    volumetric_lights_kernel<ILM_SDF_FP16, true>, volumetric_lights_kernel<ILM_SDF_UNORM16, false>,
-                                                   volumetric_lights_kernel<ILM_SDF_UNORM16, true>);
+                                                   volumetric_lights_kernel<ILM_SDF_UNORM16, true>, blend);
 }
 
 __global__ __launch_bounds__(256) void divide_probe_kernel(const float* __restrict__ n, const float* __restrict__ d, int count,

@@ -410,6 +410,7 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("LevelCount", &RampTexture::LevelCount);
     py::class_<SphereLightSource>(m, "SphereLightSource").def(py::init<>())
         .def_readwrite("SortKey", &SphereLightSource::SortKey).def_readwrite("Enabled", &SphereLightSource::Enabled)
+        .def_readwrite("BlendColorFunction", &SphereLightSource::BlendColorFunction).def_readwrite("BlendAlphaFunction", &SphereLightSource::BlendAlphaFunction)
         VEC_PROP(SphereLightSource, Position, 3)
         .def_readwrite("Radius", &SphereLightSource::Radius).def_readwrite("RampLength", &SphereLightSource::RampLength)
         VEC_PROP(SphereLightSource, Color, 4)
@@ -429,6 +430,7 @@ PYBIND11_MODULE(_host, m) {
     // Direction: None or three floats, normalised when set; Bounds: None or (left, top, right, bottom)
     py::class_<DirectionalLightSource>(m, "DirectionalLightSource").def(py::init<>())
         .def_readwrite("SortKey", &DirectionalLightSource::SortKey).def_readwrite("Enabled", &DirectionalLightSource::Enabled)
+        .def_readwrite("BlendColorFunction", &DirectionalLightSource::BlendColorFunction).def_readwrite("BlendAlphaFunction", &DirectionalLightSource::BlendAlphaFunction)
         .def_property("Direction", [](const DirectionalLightSource& l) -> py::object { return l.Direction() ? py::cast(l3(*l.Direction())) : py::none(); },
                       [](DirectionalLightSource& l, py::object v) { if (v.is_none()) l.SetDirection(std::nullopt); else l.SetDirection(v3(v.cast<std::vector<float>>())); })
         .def_property("Bounds", [](const DirectionalLightSource& l) -> py::object {
@@ -453,6 +455,7 @@ PYBIND11_MODULE(_host, m) {
     // Transform: 16 floats, row-major (M11 .. M44); Rotation: (X, Y, Z, W); Origin / Depth: None or a value; TextureRegion: (x1, y1, x2, y2)
     py::class_<LineLightSource>(m, "LineLightSource").def(py::init<>())
         .def_readwrite("SortKey", &LineLightSource::SortKey).def_readwrite("Enabled", &LineLightSource::Enabled)
+        .def_readwrite("BlendColorFunction", &LineLightSource::BlendColorFunction).def_readwrite("BlendAlphaFunction", &LineLightSource::BlendAlphaFunction)
         VEC_PROP(LineLightSource, StartPosition, 3)
         VEC_PROP(LineLightSource, EndPosition, 3)
         .def_readwrite("Radius", &LineLightSource::Radius)
@@ -472,6 +475,7 @@ PYBIND11_MODULE(_host, m) {
     // Shape: 0 ellipsoid, 1 cone, 2 box (any other int is an unknown shape: not packed); LightDirection: None or (x, y, z)
     py::class_<VolumetricLightSource>(m, "VolumetricLightSource").def(py::init<>())
         .def_readwrite("SortKey", &VolumetricLightSource::SortKey).def_readwrite("Enabled", &VolumetricLightSource::Enabled)
+        .def_readwrite("BlendColorFunction", &VolumetricLightSource::BlendColorFunction).def_readwrite("BlendAlphaFunction", &VolumetricLightSource::BlendAlphaFunction)
         .def_property("Shape", [](const VolumetricLightSource& l) { return (int)l.Shape; }, [](VolumetricLightSource& l, int v) { l.Shape = (VolumetricLightShape)v; })
         VEC_PROP(VolumetricLightSource, StartPosition, 3)
         VEC_PROP(VolumetricLightSource, EndPosition, 3)
@@ -494,6 +498,7 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("Quality", &VolumetricLightSource::Quality);
     py::class_<ProjectorLightSource>(m, "ProjectorLightSource").def(py::init<>())
         .def_readwrite("SortKey", &ProjectorLightSource::SortKey).def_readwrite("Enabled", &ProjectorLightSource::Enabled)
+        .def_readwrite("BlendColorFunction", &ProjectorLightSource::BlendColorFunction).def_readwrite("BlendAlphaFunction", &ProjectorLightSource::BlendAlphaFunction)
         .def_property("Transform", [](const ProjectorLightSource& l) { return std::vector<float>(&l.Transform.M[0][0], &l.Transform.M[0][0] + 16); },
                       [](ProjectorLightSource& l, const std::vector<float>& v) { for (int i = 0; i < 16; i++) l.Transform.M[i / 4][i % 4] = v.at(i); })
         VEC_PROP(ProjectorLightSource, Rotation, 4)

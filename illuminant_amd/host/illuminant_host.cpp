@@ -1501,35 +1501,47 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     for (const VolumetricLightSource& vl : Environment->VolumetricLights)
         if (vl.Enabled) sorted.push_back({ vl.SortKey, nullptr, nullptr, nullptr, nullptr, nullptr, &vl });
     std::stable_sort(sorted.begin(), sorted.end(), [](const Entry& x, const Entry& y) { return x.sortKey < y.sortKey; });
-    // GetLightRenderState (:799-845): lights that share a ramp texture and quality settings form one render state (BlendState is
-    // additive for every light here); the states are drawn one after the other onto the same target, in the order their keys first appear.
+    // GetLightRenderState (:799-845): lights that share a ramp texture, quality settings and blend state (Key.BlendState ??
+    // BlendState.Additive, :806: here the light's two blend functions) form one render state; the states of a type are drawn one after
+    // the other onto the same target, in the order their keys first appear, and the types in the fixed order below -- sphere,
+    // directional, line, projector, volumetric, particle.  (The reference draws its states in the enumeration order of a dictionary
+    // keyed by type, texture, quality and blend state, which its text does not define: with alternate blend modes the order ACROSS
+    // states matters, and a host that depends on it says so through SortKey within a type only.)
     // A replicator takes its state from its Template (:802).
     groupKeys.clear();
     groupQuality.clear();
+    groupBlend.clear();
     groups.clear();
-    // the render state of a (ramp texture, quality) key among `keys` / `quality` / `lists`, appended when the key is new
-    auto stateFor = [&](const std::shared_ptr<RampTexture>& texture, const RendererQualitySettings* quality, std::vector<const RampTexture*>& keys,
-                        std::vector<const RendererQualitySettings*>& qualities, std::vector<std::vector<IlmLightVertex>>& lists) -> size_t {
+    // the render state of a (ramp texture, quality, blend functions) key among `keys` / `qualities` / `blends` / `lists`, appended when the key is new
+    auto stateFor = [&](const std::shared_ptr<RampTexture>& texture, const RendererQualitySettings* quality, std::pair<int, int> blend,
+                        std::vector<const RampTexture*>& keys, std::vector<const RendererQualitySettings*>& qualities,
+                        std::vector<std::pair<int, int>>& blends, std::vector<std::vector<IlmLightVertex>>& lists) -> size_t {
         const RampTexture* ramp = texture ? texture.get() : Configuration.DefaultRampTexture.get();
         if (ramp && ((ramp->Width == 1 && ramp->Height == 1) || ramp->Width <= 0))
             ramp = nullptr;                                   // a 1 x 1 ramp is no ramp (:822-827)
         size_t g = 0;
-        while (g < keys.size() && !(keys[g] == ramp && qualities[g] == quality)) g++;
-        if (g == keys.size()) { keys.push_back(ramp); qualities.push_back(quality); lists.emplace_back(); }
+        while (g < keys.size() && !(keys[g] == ramp && qualities[g] == quality && blends[g] == blend)) g++;
+        if (g == keys.size()) { keys.push_back(ramp); qualities.push_back(quality); blends.push_back(blend); lists.emplace_back(); }
         return g;
     };
-    auto groupFor = [&](const SphereLightSource& l) -> size_t { return stateFor(l.TextureRef, l.Quality.get(), groupKeys, groupQuality, groups); };
+    auto blendOf = [](const auto& l) { return std::pair<int, int>(l.BlendColorFunction, l.BlendAlphaFunction); };
+    auto groupFor = [&](const SphereLightSource& l) -> size_t {
+        return stateFor(l.TextureRef, l.Quality.get(), blendOf(l), groupKeys, groupQuality, groupBlend, groups);
+    };
     // directional lights form render states of their own (LightTypeRenderStateKey.Type): grouped by the same key, in first-appearance order
     directionalKeys.clear();
     directionalQuality.clear();
+    directionalBlend.clear();
     directionalGroups.clear();
     // line lights: render states of their own under the same key (the technique reads no ramp)
     lineKeys.clear();
     lineQuality.clear();
+    lineBlend.clear();
     lineGroups.clear();
     // projector lights: one render state per texture (and quality) -- the key's RampTexture member is the projected texture (:1389)
     projectorKeys.clear();
     projectorQuality.clear();
+    projectorBlend.clear();
     projectorGroups.clear();
     // Volumetric lights: the reference draws two render states per (texture, quality) key, ShadowedVolumetricLight and VolumetricLight,
     // selected by CastsShadows (:190-193).  The two techniques differ only in LightProperties.w, which the vertex carries, so ONE call
@@ -1538,13 +1550,15 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     // fp32 model the sum of a call is rounded in list order, where two calls would round state by state: sums of the same terms.)
     volumetricKeys.clear();
     volumetricQuality.clear();
+    volumetricBlend.clear();
     volumetricGroups.clear();
     for (const Entry& e : sorted) {
         IlmLightVertex v;
         if (e.volumetric) {
             if (!PackVolumetricLight(*e.volumetric, intensityScale, Field != nullptr, v))
                 continue;
-            volumetricGroups[stateFor(e.volumetric->TextureRef, e.volumetric->Quality.get(), volumetricKeys, volumetricQuality, volumetricGroups)].push_back(v);
+            volumetricGroups[stateFor(e.volumetric->TextureRef, e.volumetric->Quality.get(), blendOf(*e.volumetric), volumetricKeys, volumetricQuality, volumetricBlend,
+                                      volumetricGroups)].push_back(v);
             vertices.push_back(v);
             continue;
         }
@@ -1555,8 +1569,10 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
             const RampTexture* texture = e.projector->TextureRef.get();
             const RendererQualitySettings* quality = e.projector->Quality.get();
             size_t g = 0;
-            while (g < projectorKeys.size() && !(projectorKeys[g] == texture && projectorQuality[g] == quality)) g++;
-            if (g == projectorKeys.size()) { projectorKeys.push_back(texture); projectorQuality.push_back(quality); projectorGroups.emplace_back(); }
+            while (g < projectorKeys.size() && !(projectorKeys[g] == texture && projectorQuality[g] == quality && projectorBlend[g] == blendOf(*e.projector))) g++;
+            if (g == projectorKeys.size()) {
+                projectorKeys.push_back(texture); projectorQuality.push_back(quality); projectorBlend.push_back(blendOf(*e.projector)); projectorGroups.emplace_back();
+            }
             projectorGroups[g].push_back(v);
             vertices.push_back(v);
             continue;
@@ -1564,14 +1580,15 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
         if (e.line) {
             if (!PackLineLight(*e.line, intensityScale, Field != nullptr, v))
                 continue;
-            lineGroups[stateFor(e.line->TextureRef, e.line->Quality.get(), lineKeys, lineQuality, lineGroups)].push_back(v);
+            lineGroups[stateFor(e.line->TextureRef, e.line->Quality.get(), blendOf(*e.line), lineKeys, lineQuality, lineBlend, lineGroups)].push_back(v);
             vertices.push_back(v);
             continue;
         }
         if (e.directional) {
             if (!PackDirectionalLight(*e.directional, intensityScale, v))
                 continue;
-            directionalGroups[stateFor(e.directional->TextureRef, e.directional->Quality.get(), directionalKeys, directionalQuality, directionalGroups)].push_back(v);
+            directionalGroups[stateFor(e.directional->TextureRef, e.directional->Quality.get(), blendOf(*e.directional), directionalKeys, directionalQuality,
+                                       directionalBlend, directionalGroups)].push_back(v);
             vertices.push_back(v);
             continue;
         }
@@ -1611,10 +1628,23 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     const float ambient[4] = { Environment->Ambient.X * intensityScale, Environment->Ambient.Y * intensityScale,
                                Environment->Ambient.Z * intensityScale, Environment->Ambient.W * intensityScale };
     // no lights: the clear still happens (with directional lights alone, their first launch carries it; line, projector and volumetric groups always add)
-    if (groups.empty() && directionalGroups.empty()) { groupKeys.push_back(nullptr); groupQuality.push_back(nullptr); groups.emplace_back(); }
+    if (groups.empty() && directionalGroups.empty()) {
+        groupKeys.push_back(nullptr); groupQuality.push_back(nullptr); groupBlend.push_back({ ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD }); groups.emplace_back();
+    }
     if (stats) { stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0; }
+    // every group sets its blend functions before its call (no native call while they are what the context holds: a frame of default
+    // lights makes the calls it always made); the context is left at ADD / ADD however this function is left
+    struct BlendReset {
+        LightingRenderer& r;
+        ~BlendReset() {
+            if (r.boundBlend != std::pair<int, int>(ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD))
+                (void)ilm_ctx_set_light_blend_function(r.Context.Handle(), ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD);
+            r.boundBlend = { ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD };
+        }
+    } blendReset{ *this };
     for (size_t g = 0; g < groups.size(); g++) {
         BindRamp(groupKeys[g]);
+        BindBlend(groupBlend[g]);
         IlmRenderStats gs{};
         const IlmDistanceFieldUniforms gdfu = groupQuality[g] ? GetDistanceFieldUniforms(*groupQuality[g]) : dfu;     // SetDistanceFieldParameters(material, true, ltrs.Key.Quality), :792
         ThrowIfFailed(ilm_render_sphere_lights(Context.Handle(), groups[g].empty() ? nullptr : groups[g].data(), (int32_t)groups[g].size(),
@@ -1625,6 +1655,7 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     // the directional render states, onto the same target after the sphere ones
     for (size_t g = 0; g < directionalGroups.size(); g++) {
         BindRamp(directionalKeys[g]);
+        BindBlend(directionalBlend[g]);
         IlmRenderStats gs{};
         const IlmDistanceFieldUniforms gdfu = directionalQuality[g] ? GetDistanceFieldUniforms(*directionalQuality[g]) : dfu;
         ThrowIfFailed(ilm_render_directional_lights(Context.Handle(), directionalGroups[g].data(), (int32_t)directionalGroups[g].size(), &env, &gdfu, gbuffer,
@@ -1634,6 +1665,7 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     }
     // the line render states: no ramp technique, the ramp binding is neither read nor changed
     for (size_t g = 0; g < lineGroups.size(); g++) {
+        BindBlend(lineBlend[g]);
         IlmRenderStats gs{};
         const IlmDistanceFieldUniforms gdfu = lineQuality[g] ? GetDistanceFieldUniforms(*lineQuality[g]) : dfu;
         ThrowIfFailed(ilm_render_line_lights(Context.Handle(), lineGroups[g].data(), (int32_t)lineGroups[g].size(), &env, &gdfu, gbuffer,
@@ -1644,6 +1676,7 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     for (size_t g = 0; g < projectorGroups.size(); g++) {
         // (a texture with a mip chain goes through the call that takes the levels; a one-level texture makes the call it always made)
         const RampTexture& texture = *projectorKeys[g];
+        BindBlend(projectorBlend[g]);
         if (texture.LevelCount > 1)
             ThrowIfFailed(ilm_ctx_set_projector_texture_mips(Context.Handle(), texture.Texels.data(), texture.Width, texture.Height, texture.LevelCount));
         else
@@ -1657,6 +1690,7 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     if (!projectorGroups.empty()) ThrowIfFailed(ilm_ctx_set_projector_texture(Context.Handle(), nullptr, 0, 0));
     // the volumetric render states, last: no ramp technique, neither binding is read
     for (size_t g = 0; g < volumetricGroups.size(); g++) {
+        BindBlend(volumetricBlend[g]);
         IlmRenderStats gs{};
         const IlmDistanceFieldUniforms gdfu = volumetricQuality[g] ? GetDistanceFieldUniforms(*volumetricQuality[g]) : dfu;
         ThrowIfFailed(ilm_render_volumetric_lights(Context.Handle(), volumetricGroups[g].data(), (int32_t)volumetricGroups[g].size(), &env, &gdfu, gbuffer,
@@ -1675,13 +1709,15 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
             quads.push_back(std::min(pls.System->ChunkMaximumCount(), c.TotalSpawned + 1));
         if (quads.empty())
             continue;
+        BindBlend(blendOf(pls.Template));      // a particle light source's template carries its blend functions
         IlmRenderStats ps{};
         ThrowIfFailed(ilm_render_particle_lights(Context.Handle(), pls.System->Handle(), quads.data(), (int32_t)quads.size(), &p, &env, &dfu,
                                                  gbuffer, Field ? Field->Texture() : 0, lightmap, rowBegin, rowEnd, stats ? &ps : nullptr));
         if (stats) { stats->SdfSamples += ps.SdfSamples; stats->PixelLightPairs += ps.PixelLightPairs; stats->TracedPairs += ps.TracedPairs; }
     }
     lastInverseScaleFactor = 1.0f / intensityScale;      // new RenderedLighting(this, lightmap.Buffer, 1.0f / intensityScale, ...), :963-966
-    if (Probes.Count() > 0)      // :1176-1182
+    BindBlend({ ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD });
+    if (Probes.Count() > 0)      // :1176-1182 (the probe target is always blended additively, LightingRenderer.LightProbes.cs:27)
         UpdateLightProbes(intensityScale);
 }
 
@@ -1690,6 +1726,13 @@ void LightingRenderer::BindRamp(const RampTexture* ramp) {
     if (ramp == boundRamp) return;
     ThrowIfFailed(ilm_ctx_set_light_ramp(Context.Handle(), ramp ? ramp->Texels.data() : nullptr, ramp ? ramp->Width : 0, ramp ? ramp->Height : 0));
     boundRamp = ramp;
+}
+
+// the group's blend functions (Key.BlendState, :806); the native layer keeps one pair per context
+void LightingRenderer::BindBlend(std::pair<int, int> functions) {
+    if (functions == boundBlend) return;
+    ThrowIfFailed(ilm_ctx_set_light_blend_function(Context.Handle(), functions.first, functions.second));
+    boundBlend = functions;
 }
 
 IlmParticleLightParams LightingRenderer::PackParticleLight(const ParticleLightSource& pls, bool haveDistanceField) {

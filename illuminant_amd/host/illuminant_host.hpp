@@ -698,6 +698,7 @@ struct RendererQualitySettings;
 struct SphereLightSource {
     int SortKey = 0;          // LightSourceBase.SortKey: RenderLighting sorts by it first (LightSorter, LightingRenderer.cs:2066-2096)
     bool Enabled = true;      // LightSourceBase.Enabled (LightSource.cs:42): disabled lights are skipped (LightingRenderer.cs:1062)
+    int BlendColorFunction = ILM_LIGHT_BLEND_ADD, BlendAlphaFunction = ILM_LIGHT_BLEND_ADD;     // LightSource.BlendMode (LightSource.cs:59-65): ILM_LIGHT_BLEND_* of rgb | a, part of the render state's key
     Vector3 Position;
     float Radius = 0, RampLength = 1;
     Vector4 Color{1, 1, 1, 1};
@@ -723,6 +724,7 @@ struct Bounds { Vector2 TopLeft, BottomRight; };
 struct DirectionalLightSource {
     int SortKey = 0;
     bool Enabled = true;
+    int BlendColorFunction = ILM_LIGHT_BLEND_ADD, BlendAlphaFunction = ILM_LIGHT_BLEND_ADD;     // LightSource.BlendMode (LightSource.cs:59-65): ILM_LIGHT_BLEND_* of rgb | a, part of the render state's key
     std::optional<Lighting::Bounds> Bounds;       // restricts the light to a rectangle of the world; with a null Direction: ambient light in an area
     // the direction light travels, normalised when set (:117-130); null: a non-directional light
     const std::optional<Vector3>& Direction() const { return direction; }
@@ -745,6 +747,7 @@ private:
 struct LineLightSource {
     int SortKey = 0;
     bool Enabled = true;
+    int BlendColorFunction = ILM_LIGHT_BLEND_ADD, BlendAlphaFunction = ILM_LIGHT_BLEND_ADD;     // LightSource.BlendMode (LightSource.cs:59-65): ILM_LIGHT_BLEND_* of rgb | a, part of the render state's key
     Vector3 StartPosition, EndPosition;
     float Radius = 0;                             // the reference's default (:325): such a light lights nothing (ilm_render_line_lights)
     LightSourceRampMode RampMode = LightSourceRampMode::Linear;
@@ -766,6 +769,7 @@ enum class VolumetricLightShape { Ellipsoid = 0, Cone = 1, Box = 2 };
 struct VolumetricLightSource {
     int SortKey = 0;
     bool Enabled = true;
+    int BlendColorFunction = ILM_LIGHT_BLEND_ADD, BlendAlphaFunction = ILM_LIGHT_BLEND_ADD;     // LightSource.BlendMode (LightSource.cs:59-65): ILM_LIGHT_BLEND_* of rgb | a, part of the render state's key
     VolumetricLightShape Shape = VolumetricLightShape::Cone;
     Vector3 StartPosition, EndPosition;           // cone: its two ends; ellipsoid and box: two corners of the bounds
     std::optional<Vector3> LightDirection;        // unset: the light travels from StartPosition towards the point being lit
@@ -797,6 +801,7 @@ struct Matrix {
 struct ProjectorLightSource {
     int SortKey = 0;
     bool Enabled = true;
+    int BlendColorFunction = ILM_LIGHT_BLEND_ADD, BlendAlphaFunction = ILM_LIGHT_BLEND_ADD;     // LightSource.BlendMode (LightSource.cs:59-65): ILM_LIGHT_BLEND_* of rgb | a, part of the render state's key
     Matrix Transform;
     Vector4 Rotation{0, 0, 0, 1};                 // Quaternion (X, Y, Z, W); identity: no rotation about the region's centre
     Vector2 Scale{1, 1};
@@ -1064,24 +1069,31 @@ private:
     // the light groups of the last RenderLighting (one per ramp texture) and the ramp currently bound on the context
     std::vector<const RampTexture*> groupKeys;
     std::vector<const RendererQualitySettings*> groupQuality;     // null => Configuration.DefaultQuality
+    std::vector<std::pair<int, int>> groupBlend;        // (BlendColorFunction, BlendAlphaFunction) of the group: the third member of its key
     std::vector<std::vector<IlmLightVertex>> groups;
     // the directional groups of the last RenderLighting, drawn after the sphere groups (same keys: ramp texture, quality)
     std::vector<const RampTexture*> directionalKeys;
     std::vector<const RendererQualitySettings*> directionalQuality;
+    std::vector<std::pair<int, int>> directionalBlend;
     std::vector<std::vector<IlmLightVertex>> directionalGroups;
     // the line groups, drawn after the directional ones (LightSourceTypeID.Line = 4 sorts between Directional = 2 and Projector = 5)
     std::vector<const RampTexture*> lineKeys;
     std::vector<const RendererQualitySettings*> lineQuality;
+    std::vector<std::pair<int, int>> lineBlend;
     std::vector<std::vector<IlmLightVertex>> lineGroups;
     // the projector groups, drawn after the line ones: one per (texture, quality), the texture bound per group
     std::vector<const RampTexture*> projectorKeys;
     std::vector<const RendererQualitySettings*> projectorQuality;
+    std::vector<std::pair<int, int>> projectorBlend;
     std::vector<std::vector<IlmLightVertex>> projectorGroups;
     // the volumetric groups, drawn last (LightSourceTypeID.Volumetric = 6 sorts after Projector = 5): one per (ramp texture, quality)
     std::vector<const RampTexture*> volumetricKeys;
     std::vector<const RendererQualitySettings*> volumetricQuality;
+    std::vector<std::pair<int, int>> volumetricBlend;
     std::vector<std::vector<IlmLightVertex>> volumetricGroups;
     const RampTexture* boundRamp = nullptr;
+    std::pair<int, int> boundBlend{ ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD };      // what the context's light blend functions are set to
+    void BindBlend(std::pair<int, int> functions);
     float lastInverseScaleFactor = 0;     // RenderedLighting.InverseScaleFactor of the last RenderLighting; 0 = none yet
     void BindRamp(const RampTexture* ramp);
 };

@@ -114,6 +114,7 @@ SYMBOLS = {
     "ilm_ctx_set_projector_texture": (_I, [_H, _P, _I, _I]),
     "ilm_ctx_set_projector_texture_mips": (_I, [_H, _P, _I, _I, _I]),
     "ilm_ctx_set_lightmap_blend": (_I, [_H, _I]),
+    "ilm_ctx_set_light_blend_function": (_I, [_H, _I, _I]),
     "ilm_ctx_set_light_split": (_I, [_H, _I]),
     "ilm_system_set_bitmap": (_I, [_H, _P, _I, _I]),
     "ilm_resolve_lighting": (_I, [_H, _H, _P, _I, _I]),
@@ -236,6 +237,10 @@ class Context:
     def set_lightmap_blend(self, fp16_per_light):
         """ilm_ctx_set_lightmap_blend: True = the reference's HalfVector4 render target (rounded through fp16 after every light)."""
         check(lib().ilm_ctx_set_lightmap_blend(self.handle, 1 if fp16_per_light else 0))
+
+    def set_light_blend_function(self, color_function=abi.LIGHT_BLEND_ADD, alpha_function=abi.LIGHT_BLEND_ADD):
+        """ilm_ctx_set_light_blend_function: abi.LIGHT_BLEND_* of rgb and of alpha for the light passes that follow (LightSource.BlendMode)."""
+        check(lib().ilm_ctx_set_light_blend_function(self.handle, int(color_function), int(alpha_function)))
 
     def set_light_split(self, workgroups):
         """ilm_ctx_set_light_split: workgroups per tile of the sphere-light launches (0 = chosen per launch, 1 / 2 / 4 / 8)."""

@@ -35,7 +35,8 @@ extern "C" {
  * + ilm_render_directional_lights (directional lights; no new struct: the reference packs them into a LightVertex);
  * + ilm_ctx_set_projector_texture, ilm_render_projector_lights (projector lights; a LightVertex again);
  * + ilm_render_line_lights (line lights; a LightVertex again); + ilm_render_volumetric_lights (volumetric lights; likewise);
- * + ilm_ctx_set_projector_texture_mips (a projector texture's mip chain, fetched trilinearly at the light's mip bias).
+ * + ilm_ctx_set_projector_texture_mips (a projector texture's mip chain, fetched trilinearly at the light's mip bias);
+ * + ilm_ctx_set_light_blend_function, ILM_LIGHT_BLEND_* (subtractive, max and min light groups: LightSource.BlendMode).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -1055,6 +1056,40 @@ int32_t ilm_ctx_set_light_ramp(IlmHandle ctx, const IlmFloat4* texels, int32_t w
 #define ILM_BLEND_FP32_ACCUMULATE 0
 #define ILM_BLEND_FP16_PER_LIGHT 1
 int32_t ilm_ctx_set_lightmap_blend(IlmHandle ctx, int32_t mode);
+
+/* Light blend functions: LightSource.BlendMode (Illuminant/Lighting/LightSource.cs:59-65, "Overrides how light is blended into the
+ * lightmap"), the BlendState member of LightTypeRenderStateKey (LightingRenderer.cs:51,84,206,806: Key.BlendState ?? BlendState.Additive).
+ * Per context, like ilm_ctx_set_lightmap_blend; applies to the FOLLOWING ilm_render_sphere_lights, ilm_render_particle_lights,
+ * ilm_render_directional_lights, ilm_render_line_lights, ilm_render_projector_lights and ilm_render_volumetric_lights calls, and to
+ * ilm_group_render_sphere_lights through each member context's own setting (the host sets every member alike).  ilm_render_light_probes
+ * ignores it: the reference forces RenderStates.AdditiveBlend on the probe target (LightingRenderer.LightProbes.cs:27).
+ * color_function acts on r, g and b, alpha_function on a (XNA's ColorBlendFunction / AlphaBlendFunction); both default to ADD.  The
+ * factors are One / One -- BlendState.Additive's too: a light shader's output alpha is always 1, so SourceAlpha is One for every technique.
+ * Any other value: ILM_ERR_INVALID_ARGUMENT, the state stays as it was (the handle is looked up first: ILM_ERR_INVALID_HANDLE).
+ *
+ * A (pixel, light) pair contributes exactly when it does under ADD: every discard, footprint test and trace decision is unchanged, and
+ * so is IlmRenderStats.  A contributing pair's source value is c = (its rgb contribution, 1).  `base` is the clear colour when
+ * ambient != NULL, else the texel, read and converted as under ADD.  Per channel, with f that channel's function:
+ *   ILM_BLEND_FP32_ACCUMULATE
+ *     ADD:               out = base + S, as ever.
+ *     REVERSE_SUBTRACT:  out = base - S, S the very sum ADD forms (sphere and particle lights: the same parts, the same balanced tree;
+ *                        the full-frame passes: list order from zero): one subtraction, one rounding.
+ *     MAX:               M = -inf; every contributing pair: M = (c > M) ? c : M; out = (M > base) ? M : base.
+ *     MIN:               M = +inf; every contributing pair: M = (c < M) ? c : M; out = (M < base) ? M : base.
+ *     Comparisons and selects, not fmaxf / fminf: a NaN source is never selected, a NaN base is kept, a pixel without a contributing
+ *     pair keeps base bit for bit.  The result of MAX / MIN does not depend on the order of the lights, on parts or on the light split.
+ *   ILM_BLEND_FP16_PER_LIGHT: dst = half(base); every contributing pair in list order, s = half(c):
+ *     ADD: dst = half(dst + s).  REVERSE_SUBTRACT: dst = half(dst - s).  MAX: dst = (s > dst) ? s : dst.  MIN: dst = (s < dst) ? s : dst.
+ * Both models: the store conversion follows the combine and is unchanged -- HALF4 rounds once, RGBA8 saturates (a subtraction ends at
+ * byte 0, as on a UNORM target); ambient != NULL with light_count == 0 still clears; store-mode mirrors receive the same texel; the
+ * particle lights of a call are one light list (S is the sum ADD forms over it, list batches included).  A sphere-light launch whose functions are not
+ * ADD / ADD is served by one workgroup per tile (ilm_ctx_set_light_split does not apply; the bits do not depend on it anyway).
+ * Not built: BlendFunction.Subtract (src - dst); destination-colour factors (multiplicative lights); blend factors and write masks. */
+#define ILM_LIGHT_BLEND_ADD              0   /* BlendFunction.Add (default) */
+#define ILM_LIGHT_BLEND_REVERSE_SUBTRACT 1   /* BlendFunction.ReverseSubtract: dst - src */
+#define ILM_LIGHT_BLEND_MAX              2   /* BlendFunction.Max */
+#define ILM_LIGHT_BLEND_MIN              3   /* BlendFunction.Min */
+int32_t ilm_ctx_set_light_blend_function(IlmHandle ctx, int32_t color_function, int32_t alpha_function);
 
 /* How many workgroups serve one 16 x 16 tile of this context's sphere-light launches ("light split").  The reference cuts a frame's
  * light list into draws of 128 instances and the ROP adds them (Illuminant/Lighting/LightingRenderer.cs:1149-1166,

@@ -25,6 +25,10 @@ namespace Squared.Illuminant.Native {
         public const int ERR_OUT_OF_RANGE = -3;
         public const int ERR_STATE = -6;
         public const int ERR_TOO_MANY = -4;
+        public const int LIGHT_BLEND_ADD = 0;
+        public const int LIGHT_BLEND_MAX = 2;
+        public const int LIGHT_BLEND_MIN = 3;
+        public const int LIGHT_BLEND_REVERSE_SUBTRACT = 1;
         public const int MAX_ATTRACTORS = 16;
         public const int MAX_INLINE_POSITION_CONSTANTS = 4;
         public const int MAX_OPS = 4;
@@ -609,6 +613,7 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_volumetric_lights (ulong ctx, LightVertex* lights, int lightCount, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong gbuffer, ulong sdf, float* ambient, ulong lightmap, int rowBegin, int rowEnd, IlmRenderStats* stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_ctx_set_light_ramp (ulong ctx, Vector4* texels, int width, int height);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_ctx_set_lightmap_blend (ulong ctx, int mode);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_ctx_set_light_blend_function (ulong ctx, int colorFunction, int alphaFunction);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_ctx_set_light_split (ulong ctx, int workgroups);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_particle_lights (ulong ctx, ulong system, int* quadCounts, int chunkCount, IlmParticleLightParams* @params, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong gbuffer, ulong sdf, ulong lightmap, int rowBegin, int rowEnd, IlmRenderStats* stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_light_probes (ulong ctx, LightVertex* lights, int lightCount, Vector4* probePositions, Vector4* probeNormals, int probeCount, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong sdf, Vector4* outValues);
