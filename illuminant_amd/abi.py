@@ -34,6 +34,8 @@ GBUFFER_FLOAT4, GBUFFER_HALF4 = 0, 1
 LIGHTMAP_FLOAT4, LIGHTMAP_HALF4, LIGHTMAP_RGBA8 = 0, 1, 2
 # ILM_LIGHT_BLEND_*: a light group's blend function (ilm_ctx_set_light_blend_function), for rgb and for alpha
 LIGHT_BLEND_ADD, LIGHT_BLEND_REVERSE_SUBTRACT, LIGHT_BLEND_MAX, LIGHT_BLEND_MIN = 0, 1, 2, 3
+# ILM_FILTER_*: the sampler of ilm_resolve_lighting_scaled (SamplerState.PointClamp / LinearClamp)
+FILTER_POINT, FILTER_LINEAR = 0, 1
 PLANE_POSITION, PLANE_VELOCITY, PLANE_ATTRIBUTES, PLANE_RENDER_COLOR, PLANE_RENDER_DATA = 0, 1, 2, 3, 4
 
 Handle = C.c_uint64

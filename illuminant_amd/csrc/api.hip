@@ -3596,6 +3596,30 @@ int32_t ilm_visualize_distance_field(IlmHandle hctx, IlmHandle hsdf, const IlmDi
     return ILM_OK;
 }
 
+namespace {
+// The uniforms of the resolve's pixel shaders as LightingResolveHandler._Before binds them (LightingRenderer.cs:1463-1520), with the
+// clamps of SetGammaCompressionParameters / SetToneMappingParameters, IlluminantMaterials.cs:81-137
+void resolve_uniforms(ResolveLaunch& a, const IlmHDRConfiguration* hdr) {
+    const float min_v = 1.0f / 256.0f, max_v = 99999.0f;
+    auto clamp = [](float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); };
+    a.mode = hdr->Mode;
+    a.inverse_scale = (hdr->InverseScaleFactor != 0.0f) ? hdr->InverseScaleFactor : 1.0f;     // LightingRenderer.cs:1468-1472
+    a.offset = hdr->Offset;
+    a.exposure_minus_one = clamp(hdr->Exposure, min_v, max_v) - 1.0f;
+    a.gamma_minus_one = clamp(hdr->Gamma, 0.1f, 4.0f) - 1.0f;
+    const float white_point = clamp(hdr->Mode == ILM_HDR_TONE_MAP ? hdr->WhitePoint : 1.0f, min_v, max_v);
+    {   // Uncharted2Tonemap1(WhitePoint), HDR.fxh:30-36
+        const float kA = 0.15f, kB = 0.50f, kC = 0.10f, kD = 0.20f, kE = 0.02f, kF = 0.30f;
+        const float w = ((white_point * (kA * white_point + kC * kB) + kD * kE) / (white_point * (kA * white_point + kB) + kD * kF)) - kE / kF;
+        a.inv_white = 1.0f / w;
+    }
+    a.middle_gray = clamp(hdr->MiddleGray, 0.0f, max_v);
+    a.inv_average_luminance = 1.0f / clamp(hdr->AverageLuminance, min_v, max_v);
+    const float maximum_luminance = clamp(hdr->MaximumLuminance, min_v, max_v);
+    a.inv_maximum_luminance_squared = 1.0f / (maximum_luminance * maximum_luminance);
+}
+}  // namespace
+
 int32_t ilm_resolve_lighting(IlmHandle hsrc, IlmHandle hdst, const IlmHDRConfiguration* hdr, int32_t row_begin, int32_t row_end) {
     ILM_TRACE_RANGE("ilm_resolve_lighting");
     return ilm_resolve_lighting_with_albedo(hsrc, 0, hdst, hdr, row_begin, row_end);
@@ -3631,28 +3655,84 @@ int32_t ilm_resolve_lighting_with_albedo(IlmHandle hsrc, IlmHandle halbedo, IlmH
         return fail(ILM_ERR_OUT_OF_RANGE, "rows [%d, %d) outside [0, %d] (the smallest of the textures' heights)", row_begin, row_end, common_height);
     Ctx* c = src->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    // clamps of SetGammaCompressionParameters / SetToneMappingParameters, IlluminantMaterials.cs:81-137
-    const float min_v = 1.0f / 256.0f, max_v = 99999.0f;
-    auto clamp = [](float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); };
     ResolveLaunch a;
     a.src = src->texels; a.src_format = src->format; a.dst = dst->texels; a.dst_format = dst->format;
     a.albedo = albedo ? albedo->texels : nullptr; a.albedo_format = albedo ? albedo->format : 0;
-    a.width = src->width; a.row_begin = row_begin; a.row_end = row_end; a.mode = hdr->Mode;
-    a.inverse_scale = (hdr->InverseScaleFactor != 0.0f) ? hdr->InverseScaleFactor : 1.0f;     // LightingRenderer.cs:1468-1472
-    a.offset = hdr->Offset;
-    a.exposure_minus_one = clamp(hdr->Exposure, min_v, max_v) - 1.0f;
-    a.gamma_minus_one = clamp(hdr->Gamma, 0.1f, 4.0f) - 1.0f;
-    const float white_point = clamp(hdr->Mode == ILM_HDR_TONE_MAP ? hdr->WhitePoint : 1.0f, min_v, max_v);
-    {   // Uncharted2Tonemap1(WhitePoint), HDR.fxh:30-36
-        const float kA = 0.15f, kB = 0.50f, kC = 0.10f, kD = 0.20f, kE = 0.02f, kF = 0.30f;
-        const float w = ((white_point * (kA * white_point + kC * kB) + kD * kE) / (white_point * (kA * white_point + kB) + kD * kF)) - kE / kF;
-        a.inv_white = 1.0f / w;
-    }
-    a.middle_gray = clamp(hdr->MiddleGray, 0.0f, max_v);
-    a.inv_average_luminance = 1.0f / clamp(hdr->AverageLuminance, min_v, max_v);
-    const float maximum_luminance = clamp(hdr->MaximumLuminance, min_v, max_v);
-    a.inv_maximum_luminance_squared = 1.0f / (maximum_luminance * maximum_luminance);
+    a.width = src->width; a.row_begin = row_begin; a.row_end = row_end;
+    resolve_uniforms(a, hdr);
     HIP_TRY(launch_resolve(a, c->main()));
+    return ILM_OK;
+}
+
+int32_t ilm_resolve_lighting_scaled(IlmHandle hsrc, IlmHandle halbedo, IlmHandle hdst, const IlmHDRConfiguration* hdr, const float quad[4],
+                                    const float lightmap_region[4], const float albedo_region[4], const float uv_offset[2],
+                                    int32_t lightmap_filter, int32_t albedo_filter, int32_t row_begin, int32_t row_end) {
+    ILM_TRACE_RANGE("ilm_resolve_lighting_scaled");
+    Lightmap* src = from_handle<Lightmap>(hsrc, kMagicLightmap);
+    Lightmap* dst = from_handle<Lightmap>(hdst, kMagicLightmap);
+    if (!src || !dst) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
+    Lightmap* albedo = nullptr;
+    if (halbedo) {
+        albedo = from_handle<Lightmap>(halbedo, kMagicLightmap);
+        if (!albedo) return fail(ILM_ERR_INVALID_HANDLE, "albedo is not a texture (lightmap) handle");
+        if (albedo->ctx != src->ctx) return fail(ILM_ERR_INVALID_ARGUMENT, "the albedo texture must share its context with the lightmap");
+        if (hdr && hdr->AlbedoIsSRGB != 0)
+            return fail(ILM_ERR_INVALID_ARGUMENT, "AlbedoIsSRGB needs Fracture's pSRGBToPLinear (sRGBCommon.fxh), which is outside the reference tree");
+    }
+    if (src->ctx != dst->ctx) return fail(ILM_ERR_INVALID_ARGUMENT, "source and destination must share their context");
+    if (!hdr) return fail(ILM_ERR_INVALID_ARGUMENT, "hdr is NULL");
+    if (!quad) return fail(ILM_ERR_INVALID_ARGUMENT, "quad is NULL");
+    if (!lightmap_region) return fail(ILM_ERR_INVALID_ARGUMENT, "lightmap_region is NULL");
+    if (albedo && !albedo_region) return fail(ILM_ERR_INVALID_ARGUMENT, "albedo_region is NULL with an albedo texture");
+    for (int k = 0; k < 4; k++)
+        if (!std::isfinite(quad[k])) return fail(ILM_ERR_INVALID_ARGUMENT, "the quad is not finite");
+    if (!(quad[2] >= 0.0f && quad[3] >= 0.0f)) return fail(ILM_ERR_INVALID_ARGUMENT, "quad size %g x %g is negative", (double)quad[2], (double)quad[3]);
+    auto region_ok = [](const float* r, const Lightmap* m) {
+        for (int k = 0; k < 4; k++)
+            if (!std::isfinite(r[k])) return false;
+        return 0.0f <= r[0] && r[0] <= r[2] && r[2] <= (float)m->width && 0.0f <= r[1] && r[1] <= r[3] && r[3] <= (float)m->height;
+    };
+    if (!region_ok(lightmap_region, src))
+        return fail(ILM_ERR_INVALID_ARGUMENT, "lightmap_region (%g, %g, %g, %g) is not an ordered rectangle inside the %d x %d lightmap",
+                    (double)lightmap_region[0], (double)lightmap_region[1], (double)lightmap_region[2], (double)lightmap_region[3], src->width, src->height);
+    if (albedo && !region_ok(albedo_region, albedo))
+        return fail(ILM_ERR_INVALID_ARGUMENT, "albedo_region (%g, %g, %g, %g) is not an ordered rectangle inside the %d x %d albedo texture",
+                    (double)albedo_region[0], (double)albedo_region[1], (double)albedo_region[2], (double)albedo_region[3], albedo->width, albedo->height);
+    if (lightmap_filter != ILM_FILTER_POINT && lightmap_filter != ILM_FILTER_LINEAR)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "unknown lightmap filter %d", lightmap_filter);
+    if (albedo_filter != ILM_FILTER_POINT && albedo_filter != ILM_FILTER_LINEAR)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "unknown albedo filter %d", albedo_filter);
+    if (hdr->Mode < ILM_HDR_NONE || hdr->Mode > ILM_HDR_TONE_MAP) return fail(ILM_ERR_INVALID_ARGUMENT, "unknown HDR mode %d", hdr->Mode);
+    if (hdr->ResolveToSRGB != 0)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "ResolveToSRGB needs Fracture's pLinearToPSRGB (sRGBCommon.fxh), which is outside the reference tree");
+    if (hdr->DitheringStrength != 0)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "dithering needs Fracture's ApplyDither (DitherCommon.fxh), which is outside the reference tree");
+    if (row_begin < 0 || row_end > dst->height || row_begin > row_end)
+        return fail(ILM_ERR_OUT_OF_RANGE, "rows [%d, %d) outside [0, %d] (the destination's height)", row_begin, row_end, dst->height);
+    // the pixels whose centre the quad contains: i + 0.5 >= p  <=>  i >= ceil(p - 0.5), i + 0.5 < q  <=>  i < ceil(q - 0.5), exact in
+    // double for float arguments; clamped to the target (and the rows) BEFORE the conversion to int
+    auto edge = [](double p, int lo, int hi) { return (int)std::min(std::max(std::ceil(p - 0.5), (double)lo), (double)hi); };
+    ResolveScaledLaunch a;
+    a.x0 = edge((double)quad[0], 0, dst->width);         a.x1 = edge((double)quad[0] + (double)quad[2], 0, dst->width);
+    a.y0 = edge((double)quad[1], row_begin, row_end);    a.y1 = edge((double)quad[1] + (double)quad[3], row_begin, row_end);
+    if (a.x0 >= a.x1 || a.y0 >= a.y1) return ILM_OK;             // an empty quad, or one that misses the target or the rows
+    if (a.y1 - a.y0 > 65535) return fail(ILM_ERR_OUT_OF_RANGE, "more than 65535 destination rows in one call");
+    a.r.src = src->texels; a.r.src_format = src->format; a.r.dst = dst->texels; a.r.dst_format = dst->format;
+    a.r.albedo = albedo ? albedo->texels : nullptr; a.r.albedo_format = albedo ? albedo->format : 0;
+    a.r.width = dst->width; a.r.row_begin = a.y0; a.r.row_end = a.y1;
+    resolve_uniforms(a.r, hdr);
+    a.src_w = src->width; a.src_h = src->height;
+    a.albedo_w = albedo ? albedo->width : 0; a.albedo_h = albedo ? albedo->height : 0;
+    for (int k = 0; k < 4; k++) {
+        a.quad[k] = quad[k];
+        a.lightmap_region[k] = lightmap_region[k];
+        a.albedo_region[k] = albedo ? albedo_region[k] : 0.0f;
+    }
+    a.uv_offset[0] = uv_offset ? uv_offset[0] : 0.0f; a.uv_offset[1] = uv_offset ? uv_offset[1] : 0.0f;
+    a.lightmap_filter = lightmap_filter; a.albedo_filter = albedo_filter;
+    Ctx* c = src->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_resolve_scaled(a, c->main()));
     return ILM_OK;
 }
 

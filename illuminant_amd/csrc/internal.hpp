@@ -410,6 +410,17 @@ struct ResolveLaunch {
 };
 hipError_t launch_resolve(const ResolveLaunch& a, hipStream_t stream);
 
+// ilm_resolve_lighting_scaled: the per-pixel arithmetic is ResolveLaunch's (r.width is the DESTINATION's pitch in texels; r.row_begin and
+// r.row_end are not read), the fetch is the header's: destination pixels [x0, x1) x [y0, y1), already clamped to the target and the rows.
+struct ResolveScaledLaunch {
+    ResolveLaunch r;
+    int32_t src_w, src_h, albedo_w, albedo_h;
+    int32_t x0, x1, y0, y1;
+    float quad[4], lightmap_region[4], albedo_region[4], uv_offset[2];
+    int32_t lightmap_filter, albedo_filter;
+};
+hipError_t launch_resolve_scaled(const ResolveScaledLaunch& a, hipStream_t stream);
+
 // ---- brightness estimation (brightness.hip) ---------------------------------------------------------------------
 struct LuminanceLaunch {
     const void* texels; int32_t format, pitch;      // the lightmap, pitch in texels

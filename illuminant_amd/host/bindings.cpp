@@ -21,6 +21,29 @@ using namespace Squared::Illuminant::Lighting;
 using farray = py::array_t<float, py::array::c_style | py::array::forcecast>;
 
 static Vector2 v2(const std::vector<float>& v) { return Vector2{ v.at(0), v.at(1) }; }
+// the optional arguments of ResolveTo / ResolveAt as Python passes them; `hdr` is where the configuration's bytes are kept
+static ResolveOptions resolve_options(py::object albedo, py::object albedoTextureRegion, int albedoSamplerState, int lightmapSamplerState,
+                                      const std::vector<float>& uvOffset, py::object hdrBytes, int rowBegin, int rowEnd, IlmHDRConfiguration& hdr) {
+    ResolveOptions o;
+    if (!albedo.is_none()) {
+        const auto a = albedo.cast<std::tuple<IlmHandle, int, int>>();
+        o.Albedo = ResolveTexture{ std::get<0>(a), std::get<1>(a), std::get<2>(a) };
+    }
+    if (!albedoTextureRegion.is_none()) {
+        const auto b = albedoTextureRegion.cast<std::vector<float>>();
+        o.AlbedoTextureRegion = Bounds{ Vector2{ b.at(0), b.at(1) }, Vector2{ b.at(2), b.at(3) } };
+    }
+    o.AlbedoSamplerState = albedoSamplerState; o.LightmapSamplerState = lightmapSamplerState;
+    o.UVOffset = v2(uvOffset);
+    if (!hdrBytes.is_none()) {
+        const std::string b = hdrBytes.cast<std::string>();
+        if (b.size() != sizeof(IlmHDRConfiguration)) throw ArgumentException("hdr must be an IlmHDRConfiguration");
+        std::memcpy(&hdr, b.data(), sizeof(hdr));
+        o.HDR = &hdr;
+    }
+    o.RowBegin = rowBegin; o.RowEnd = rowEnd;
+    return o;
+}
 static Vector3 v3(const std::vector<float>& v) { return Vector3{ v.at(0), v.at(1), v.at(2) }; }
 static Vector4 v4(const std::vector<float>& v) { return Vector4{ v.at(0), v.at(1), v.at(2), v.at(3) }; }
 static std::vector<float> l2(const Vector2& v) { return { v.X, v.Y }; }
@@ -697,6 +720,26 @@ PYBIND11_MODULE(_host, m) {
             IlmHDRConfiguration h; std::memcpy(&h, b.data(), sizeof(h));
             r.Resolve(destination, &h, rowBegin, rowEnd);
         }, py::arg("destination"), py::arg("hdr") = py::none(), py::arg("rowBegin") = 0, py::arg("rowEnd") = -1)
+        // destination and albedo: (handle, width, height); albedoTextureRegion: (u0, v0, u1, v1); uvOffset in UV, as the reference's
+        .def("ResolveTo", [](const LightingRenderer& r, const std::tuple<IlmHandle, int, int>& destination, float width, float height, py::object albedo,
+                             py::object albedoTextureRegion, int albedoSamplerState, int lightmapSamplerState, const std::vector<float>& uvOffset,
+                             py::object hdrBytes, int rowBegin, int rowEnd) {
+            IlmHDRConfiguration h;
+            const ResolveOptions o = resolve_options(albedo, albedoTextureRegion, albedoSamplerState, lightmapSamplerState, uvOffset, hdrBytes, rowBegin, rowEnd, h);
+            r.ResolveTo(ResolveTexture{ std::get<0>(destination), std::get<1>(destination), std::get<2>(destination) }, width, height, o);
+        }, py::arg("destination"), py::arg("width"), py::arg("height"), py::arg("albedo") = py::none(), py::arg("albedoTextureRegion") = py::none(),
+           py::arg("albedoSamplerState") = (int)ILM_FILTER_LINEAR, py::arg("lightmapSamplerState") = (int)ILM_FILTER_LINEAR,
+           py::arg("uvOffset") = std::vector<float>{0, 0}, py::arg("hdr") = py::none(), py::arg("rowBegin") = 0, py::arg("rowEnd") = -1)
+        .def("ResolveAt", [](const LightingRenderer& r, const std::tuple<IlmHandle, int, int>& destination, const std::vector<float>& position,
+                             const std::vector<float>& scale, py::object albedo, py::object albedoTextureRegion, int albedoSamplerState,
+                             int lightmapSamplerState, const std::vector<float>& uvOffset, py::object hdrBytes, int rowBegin, int rowEnd) {
+            IlmHDRConfiguration h;
+            const ResolveOptions o = resolve_options(albedo, albedoTextureRegion, albedoSamplerState, lightmapSamplerState, uvOffset, hdrBytes, rowBegin, rowEnd, h);
+            r.ResolveAt(ResolveTexture{ std::get<0>(destination), std::get<1>(destination), std::get<2>(destination) }, v2(position), v2(scale), o);
+        }, py::arg("destination"), py::arg("position"), py::arg("scale") = std::vector<float>{1, 1}, py::arg("albedo") = py::none(),
+           py::arg("albedoTextureRegion") = py::none(), py::arg("albedoSamplerState") = (int)ILM_FILTER_LINEAR,
+           py::arg("lightmapSamplerState") = (int)ILM_FILTER_LINEAR, py::arg("uvOffset") = std::vector<float>{0, 0}, py::arg("hdr") = py::none(),
+           py::arg("rowBegin") = 0, py::arg("rowEnd") = -1)
         .def_property_readonly("Probes", [](LightingRenderer& r) -> LightProbeCollection& { return r.Probes; }, py::return_value_policy::reference_internal)
         .def_static("PackParticleLightBytes", [](const ParticleLightSource& pls, bool haveDF) {
             auto p = LightingRenderer::PackParticleLight(pls, haveDF); return py::bytes((const char*)&p, sizeof(p)); })

@@ -2182,6 +2182,59 @@ void LightingRenderer::Resolve(IlmHandle destination, const IlmHDRConfiguration*
     ThrowIfFailed(ilm_resolve_lighting_with_albedo(lightmap, albedo, destination, hdr, rowBegin, rowEnd));
 }
 
+// RenderedLighting.Resolve(container, layer, width, height, ...), LightingRenderer.HDR.cs:99-126
+void LightingRenderer::ResolveTo(const ResolveTexture& destination, float width, float height, const ResolveOptions& options) const {
+    const bool haveAlbedo = options.Albedo.Handle != 0;
+    const int rw = haveAlbedo ? options.Albedo.Width : Configuration.RenderWidth;
+    const int rh = haveAlbedo ? options.Albedo.Height : Configuration.RenderHeight;
+    ResolveLighting(destination, Vector2{0, 0}, Vector2{width / (float)rw, height / (float)rh}, options);
+}
+
+// RenderedLighting.Resolve(container, layer, position, scale, ...), LightingRenderer.HDR.cs:128-151
+void LightingRenderer::ResolveAt(const ResolveTexture& destination, Vector2 position, Vector2 scale, const ResolveOptions& options) const {
+    ResolveLighting(destination, position, scale, options);
+}
+
+void LightingRenderer::ResolveQuad(Vector2 position, Vector2 scale, const ResolveOptions& options, float quad[4]) const {
+    quad[0] = position.X; quad[1] = position.Y;
+    if (options.Albedo.Handle != 0) {
+        // new BitmapDrawCall(albedo, position, albedoBounds) { Scale = scale }, LightingRenderer.cs:1627-1633
+        const Bounds region = options.AlbedoTextureRegion.value_or(Bounds{Vector2{0, 0}, Vector2{1, 1}});
+        quad[2] = (region.BottomRight.X * (float)options.Albedo.Width - region.TopLeft.X * (float)options.Albedo.Width) * scale.X;
+        quad[3] = (region.BottomRight.Y * (float)options.Albedo.Height - region.TopLeft.Y * (float)options.Albedo.Height) * scale.Y;
+    } else {
+        // new BitmapDrawCall(lightmap, position, lightmapBounds) { Scale = scale / Configuration.RenderScale }, :1635-1639
+        quad[2] = (float)Configuration.RenderWidth * (scale.X / Configuration.RenderScale.X);
+        quad[3] = (float)Configuration.RenderHeight * (scale.Y / Configuration.RenderScale.Y);
+    }
+}
+
+// ResolveLighting, LightingRenderer.cs:1537-1645 (screen space, no LUT, the material's own blend state)
+void LightingRenderer::ResolveLighting(const ResolveTexture& destination, Vector2 position, Vector2 scale, const ResolveOptions& options) const {
+    IlmHDRConfiguration plain;
+    const IlmHDRConfiguration* hdr = options.HDR;
+    if (!hdr) {      // hdr == null: as Resolve above
+        std::memset(&plain, 0, sizeof(plain));
+        plain.Mode = ILM_HDR_NONE; plain.InverseScaleFactor = 1; plain.Exposure = 1; plain.Gamma = 1; plain.WhitePoint = 1;
+        hdr = &plain;
+    }
+    // the mirror's lightmap is exactly GetRenderSize: lightmapBounds (:1598-1600) is the whole texture
+    const float w = (float)Configuration.RenderWidth, h = (float)Configuration.RenderHeight;
+    const float lightmapRegion[4] = { 0.0f, 0.0f, w, h };
+    float albedoRegion[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    if (options.Albedo.Handle != 0) {
+        const Bounds region = options.AlbedoTextureRegion.value_or(Bounds{Vector2{0, 0}, Vector2{1, 1}});
+        albedoRegion[0] = region.TopLeft.X * (float)options.Albedo.Width;      albedoRegion[1] = region.TopLeft.Y * (float)options.Albedo.Height;
+        albedoRegion[2] = region.BottomRight.X * (float)options.Albedo.Width;  albedoRegion[3] = region.BottomRight.Y * (float)options.Albedo.Height;
+    }
+    float quad[4];
+    ResolveQuad(position, scale, options, quad);
+    const float uvOffset[2] = { options.UVOffset.X * w, options.UVOffset.Y * h };       // the reference's is in UV: texels here
+    const int rowEnd = options.RowEnd < 0 ? destination.Height : options.RowEnd;
+    ThrowIfFailed(ilm_resolve_lighting_scaled(lightmap, options.Albedo.Handle, destination.Handle, hdr, quad, lightmapRegion, albedoRegion, uvOffset,
+                                              options.LightmapSamplerState, options.AlbedoSamplerState, options.RowBegin, rowEnd));
+}
+
 void LightingRenderer::ReadLightmap(void* dst, int firstRow, int rowCount) const {
     ThrowIfFailed(ilm_lightmap_download(lightmap, dst, firstRow, rowCount));
 }

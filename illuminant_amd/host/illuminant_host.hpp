@@ -979,6 +979,23 @@ struct VisualizationOptions {
     Vector2 ViewportPosition{0, 0}, ViewportScale{1, 1};
 };
 
+// A texture or render target as the resolve sees one (XNA's Texture2D: the surface and its size); the surface is a lightmap object
+struct ResolveTexture {
+    IlmHandle Handle = 0;
+    int Width = 0, Height = 0;
+};
+// The optional arguments of RenderedLighting.Resolve, LightingRenderer.HDR.cs:101-105, with the reference's defaults.  Not carried:
+// lutBlending, blendState and worldSpace (ilm_resolve_lighting_scaled says why).
+struct ResolveOptions {
+    ResolveTexture Albedo;                              // albedo = null
+    std::optional<Bounds> AlbedoTextureRegion;          // in UV; albedoRegion.GetValueOrDefault(Bounds.Unit), LightingRenderer.cs:1601
+    int AlbedoSamplerState = ILM_FILTER_LINEAR;         // albedoSamplerState ?? SamplerState.LinearClamp, :1621
+    int LightmapSamplerState = ILM_FILTER_LINEAR;       // lightmapSamplerState ?? SamplerState.LinearClamp, :1622
+    Vector2 UVOffset{0, 0};                             // in UV of the lightmap, as the reference's
+    const IlmHDRConfiguration* HDR = nullptr;           // null: the plain LightingResolve with exposure / gamma 1
+    int RowBegin = 0, RowEnd = -1;                      // destination rows (a group member's strip); RowEnd < 0 => the destination's height
+};
+
 // LightingRenderer.cs (RenderLighting path only)
 class LightingRenderer {
 public:
@@ -1018,6 +1035,16 @@ public:
     // plain LightingResolve with exposure / gamma 1.
     // `albedo` != 0: the ...WithAlbedo techniques over a texture of the lightmap's size (ResolveLighting with albedo != null, :1549-1580).
     void Resolve(IlmHandle destination, const IlmHDRConfiguration* hdr = nullptr, int rowBegin = 0, int rowEnd = -1, IlmHandle albedo = 0) const;
+    // The two RenderedLighting.Resolve overloads at any destination size (LightingRenderer.HDR.cs:99-126 and :128-151), both ending in
+    // ResolveLighting (LightingRenderer.cs:1537-1645) over ilm_resolve_lighting_scaled -- the call a frame lit at RenderScale != 1 needs.
+    // ResolveTo: scale = (width / rw, height / rh), rw x rh the albedo's size when there is one, else the lightmap's (:115-117).
+    // ResolveAt: the quad's top left corner in destination pixels and the scale itself (default Vector2.One).
+    void ResolveTo(const ResolveTexture& destination, float width, float height, const ResolveOptions& options = {}) const;
+    void ResolveAt(const ResolveTexture& destination, Vector2 position, Vector2 scale = {1, 1}, const ResolveOptions& options = {}) const;
+    // ResolveLighting's draw call (:1595-1640) as the quad of ilm_resolve_lighting_scaled, x, y, width, height in destination pixels: without
+    // albedo the lightmap region's texel size x (scale / Configuration.RenderScale), with albedo the albedo region's texel size x scale.
+    void ResolveQuad(Vector2 position, Vector2 scale, const ResolveOptions& options, float quad[4]) const;
+    void ResolveLighting(const ResolveTexture& destination, Vector2 position, Vector2 scale, const ResolveOptions& options) const;
     IlmHandle Lightmap() const { return lightmap; }
     int LightmapFormat() const { return lightmapFormat; }
     // RenderedLighting.TryComputeHistogram, LightingRenderer.HDR.cs:154-183 (UpdateLuminanceBuffer + HistogramUpdateTask on the device):

@@ -119,6 +119,7 @@ SYMBOLS = {
     "ilm_system_set_bitmap": (_I, [_H, _P, _I, _I]),
     "ilm_resolve_lighting": (_I, [_H, _H, _P, _I, _I]),
     "ilm_resolve_lighting_with_albedo": (_I, [_H, _H, _H, _P, _I, _I]),
+    "ilm_resolve_lighting_scaled": (_I, [_H, _H, _H, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "ilm_lightmap_upload": (_I, [_H, _P, _I, _I]),
     "ilm_lightmap_luminance": (_I, [_H, _I, _I, _I, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ilm_lightmap_histogram": (_I, [_H, _P, _P, _P, _P]),
@@ -971,3 +972,24 @@ def resolve_lighting(src, dst, hdr, row_begin=0, row_end=None, albedo=None):
         check(lib().ilm_resolve_lighting(src.handle, dst.handle, _byref(hdr), row_begin, row_end))
     else:
         check(lib().ilm_resolve_lighting_with_albedo(src.handle, albedo.handle, dst.handle, _byref(hdr), row_begin, row_end))
+
+
+def resolve_lighting_scaled(src, dst, hdr, quad, lightmap_region=None, albedo=None, albedo_region=None, uv_offset=None,
+                            lightmap_filter=abi.FILTER_LINEAR, albedo_filter=abi.FILTER_LINEAR, row_begin=0, row_end=None):
+    """ilm_resolve_lighting_scaled: tone-map lightmap `src` onto the quad (x, y, width, height in pixels of `dst`), sampled with the
+    filters over the regions (x0, y0, x1, y1 in texels; None = the whole texture); uv_offset in texels of `src`; textures of any sizes."""
+    def floats(values, n):
+        a = (C.c_float * n)(*[float(v) for v in values])
+        return a, C.cast(a, C.c_void_p)
+    if row_end is None:
+        row_end = dst.height
+    if lightmap_region is None:
+        lightmap_region = (0.0, 0.0, src.width, src.height)
+    if albedo is not None and albedo_region is None:
+        albedo_region = (0.0, 0.0, albedo.width, albedo.height)
+    q, qp = floats(quad, 4)
+    lr, lrp = floats(lightmap_region, 4)
+    ar, arp = floats(albedo_region, 4) if albedo_region is not None else (None, None)
+    uv, uvp = floats(uv_offset, 2) if uv_offset is not None else (None, None)
+    check(lib().ilm_resolve_lighting_scaled(src.handle, albedo.handle if albedo is not None else abi.Handle(0), dst.handle, _byref(hdr),
+                                            qp, lrp, arp, uvp, lightmap_filter, albedo_filter, row_begin, row_end))

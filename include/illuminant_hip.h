@@ -36,7 +36,8 @@ extern "C" {
  * + ilm_ctx_set_projector_texture, ilm_render_projector_lights (projector lights; a LightVertex again);
  * + ilm_render_line_lights (line lights; a LightVertex again); + ilm_render_volumetric_lights (volumetric lights; likewise);
  * + ilm_ctx_set_projector_texture_mips (a projector texture's mip chain, fetched trilinearly at the light's mip bias);
- * + ilm_ctx_set_light_blend_function, ILM_LIGHT_BLEND_* (subtractive, max and min light groups: LightSource.BlendMode).
+ * + ilm_ctx_set_light_blend_function, ILM_LIGHT_BLEND_* (subtractive, max and min light groups: LightSource.BlendMode);
+ * + ilm_resolve_lighting_scaled, ILM_FILTER_* (the resolve onto a target of another size: RenderScale != 1).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -1266,6 +1267,55 @@ int32_t ilm_resolve_lighting(IlmHandle src_lightmap, IlmHandle dst_lightmap, con
  * usual case; upload with ilm_lightmap_upload); albedo == 0 is ilm_resolve_lighting.  Not bound: AlbedoIsSRGB, the LUT-blended technique. */
 int32_t ilm_resolve_lighting_with_albedo(IlmHandle src_lightmap, IlmHandle albedo, IlmHandle dst_lightmap, const IlmHDRConfiguration* hdr,
                                          int32_t row_begin, int32_t row_end);
+
+/* The scaled, filtered resolve: RenderedLighting.Resolve(container, layer, width, height, ...) and Resolve(container, layer, position,
+ * scale, ...) (Illuminant/Lighting/LightingRenderer.HDR.cs:99-151) through LightingRenderer.ResolveLighting
+ * (Illuminant/Lighting/LightingRenderer.cs:1537-1645) -- the lightmap, rendered at Configuration.RenderScale
+ * (LightingRenderer.Configuration.cs:58-60,203-214), drawn as a quad of any size (Scale = scale / Configuration.RenderScale, :1638) through
+ * `lightmapSamplerState ?? SamplerState.LinearClamp` (:1621-1622), over an albedo texture when there is one (TextureRegion2 =
+ * lightmapBounds, :1626-1633).  The two entry points above are the case source size == destination size and stay as they are.
+ *
+ * DEFINED DEVIATION.  The reference leaves the quad to Fracture's BitmapDrawCall, its vertex shader and BitmapCommon.fxh, and the fetch
+ * to the hardware sampler; none of these is in the tree.  What replaces them is stated here in full, as the rasteriser's view
+ * transform is:
+ *   Coverage.  Destination pixel (px, py) is written when its centre (px + 0.5, py + 0.5) lies in [x, x + width) x [y, y + height)
+ *     (quad = x, y, width, height in DESTINATION pixels), row_begin <= py < row_end, and it is inside `dst`.  The pixel ranges are
+ *     computed in double from the float arguments and clamped to the target before any conversion to int.  Every other texel of `dst`
+ *     keeps its bits; a quad that misses the target, or has width or height 0, succeeds and writes nothing.
+ *   Coordinate.  Per axis, in TEXELS of the texture read (not UV: at scale 1 the coordinate is exactly px + 0.5), in fp32 with every
+ *     operation rounded, in this order -- r0, r1 the region's bounds on the axis, a multiply, then an IEEE divide:
+ *         u = r0 + (((float)px + 0.5f) - x) * (r1 - r0) / width
+ *     the lightmap only:  u += uv_offset        (LightmapUVOffset, in SOURCE texels; NULL = (0, 0))
+ *         u = fminf(fmaxf(u, r0), r1)           (clamp2(texCoord + LightmapUVOffset, texRgn.xy, texRgn.zw), Resolve.fx:34,49-50)
+ *     so a NaN coordinate becomes r0 and an infinite one a bound of the region: any uv_offset is valid input.
+ *   ILM_FILTER_LINEAR (CLAMP addressing).  s = u - 0.5f, f = s - floorf(s); taps clamp((int)floorf(s), 0, size - 1) and
+ *     clamp((int)floorf(s) + 1, 0, size - 1); the value is lerp4(lerp4(t00, t10, fx), lerp4(t01, t11, fx), fy), lerp(a, b, t) =
+ *     a + (b - a) * t: the taps and weights of the projector texture's fetch with clamped instead of wrapped indices.  Every index is
+ *     inside the texture by integer arithmetic, whatever the floats are.  The region clamps the COORDINATE, not the taps: a region
+ *     smaller than its texture (the reference's lightmap is MaximumRenderSize, its region GetRenderSize) bleeds the neighbouring column
+ *     or row at its far edge when magnified, as the hardware fetch does.
+ *   ILM_FILTER_POINT.  The texel clamp((int)floorf(u), 0, size - 1).
+ *   The light texel sampled so over lightmap_region with lightmap_filter, and the albedo texel sampled the same way over albedo_region
+ *     with albedo_filter (no offset), go through the arithmetic of ilm_resolve_lighting[_with_albedo] unchanged: every HDR mode, every
+ *     source / albedo / destination format and the non-finite behaviour documented there carry over.
+ * Regions are x0, y0, x1, y1 in texels of their texture; albedo_region is ignored (may be NULL) when albedo == 0.  The three textures
+ * may have any sizes and formats.
+ * Refused, leaving `dst` untouched: a bad handle (ILM_ERR_INVALID_HANDLE, before anything else); textures of different contexts; hdr,
+ * quad or a needed region NULL; a quad that is not finite or has a negative size; a region that is not finite or not
+ * 0 <= x0 <= x1 <= the texture's width (likewise in y); a filter other than the two; rows outside [0, dst height] (ILM_ERR_OUT_OF_RANGE);
+ * ResolveToSRGB, dithering and AlbedoIsSRGB as above.  Asynchronous on the context's main stream, like the 1:1 resolve.
+ * Not built: the world-space techniques (they need the view transform), the `blendState` override, LUT blending, and mip filtering
+ * of the albedo. */
+#define ILM_FILTER_POINT  0   /* SamplerState.PointClamp */
+#define ILM_FILTER_LINEAR 1   /* SamplerState.LinearClamp: the default of ResolveLighting, LightingRenderer.cs:1621-1622 */
+int32_t ilm_resolve_lighting_scaled(IlmHandle src_lightmap, IlmHandle albedo /* 0 = none */, IlmHandle dst,
+                                    const IlmHDRConfiguration* hdr,
+                                    const float quad[4],             /* x, y, width, height in DESTINATION pixels */
+                                    const float lightmap_region[4],  /* x0, y0, x1, y1 in SOURCE texels */
+                                    const float albedo_region[4],    /* x0, y0, x1, y1 in ALBEDO texels; ignored (may be NULL) when albedo == 0 */
+                                    const float uv_offset[2],        /* LightmapUVOffset in SOURCE texels; NULL = (0, 0) */
+                                    int32_t lightmap_filter, int32_t albedo_filter,
+                                    int32_t row_begin, int32_t row_end);   /* destination rows; the strip of a group member */
 
 /* ---- brightness estimation: the inputs of the resolve's AverageLuminance / MaximumLuminance / Exposure / WhitePoint -------
  *

@@ -25,6 +25,8 @@ namespace Squared.Illuminant.Native {
         public const int ERR_OUT_OF_RANGE = -3;
         public const int ERR_STATE = -6;
         public const int ERR_TOO_MANY = -4;
+        public const int FILTER_LINEAR = 1;
+        public const int FILTER_POINT = 0;
         public const int LIGHT_BLEND_ADD = 0;
         public const int LIGHT_BLEND_MAX = 2;
         public const int LIGHT_BLEND_MIN = 3;
@@ -624,6 +626,7 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_clear (ulong lightmap, float* rgba);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_resolve_lighting (ulong srcLightmap, ulong dstLightmap, IlmHDRConfiguration* hdr, int rowBegin, int rowEnd);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_resolve_lighting_with_albedo (ulong srcLightmap, ulong albedo, ulong dstLightmap, IlmHDRConfiguration* hdr, int rowBegin, int rowEnd);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_resolve_lighting_scaled (ulong srcLightmap, ulong albedo, ulong dst, IlmHDRConfiguration* hdr, float* quad, float* lightmapRegion, float* albedoRegion, float* uvOffset, int lightmapFilter, int albedoFilter, int rowBegin, int rowEnd);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_luminance (ulong lightmap, int renderWidth, int renderHeight, int accuracyFactor, float* outValues, int capacity, int* outLevel, int* outWidth, int* outHeight);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_histogram (ulong lightmap, IlmHistogramParams* @params, float* bucketMaxValues, IlmHistogramBucket* outBuckets, IlmHistogramResult* @out);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_queue_luminance (ulong lightmap, int renderWidth, int renderHeight, int accuracyFactor);
