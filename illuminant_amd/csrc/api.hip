@@ -480,6 +480,30 @@ hipError_t light_pass_queued(Ctx* c, Sdf* f, GBuffer* g) {
     return hipSuccess;
 }
 
+// The three counters of a counting launch (the light passes' IlmRenderStats, the visualize pass's three) live in c->d_stats.  When the
+// caller wants them: launch_stats_begin() zeroes them on the context's stream and points the launch at them, ahead of the launch;
+// launch_stats_end() copies them back and synchronises, behind it.  Otherwise both do nothing and the launch keeps its null pointer.
+hipError_t launch_stats_begin(Ctx* c, bool wanted, unsigned long long** launch_stats) {
+    if (!wanted) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main());
+    if (e == hipSuccess) *launch_stats = c->d_stats;
+    return e;
+}
+hipError_t launch_stats_end(Ctx* c, uint64_t* out) {
+    if (!out) return hipSuccess;
+    unsigned long long host[3] = { 0, 0, 0 };
+    hipError_t e = hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->main());
+    if (e == hipSuccess) { out[0] = host[0]; out[1] = host[1]; out[2] = host[2]; }
+    return e;
+}
+hipError_t launch_stats_end(Ctx* c, IlmRenderStats* out) {
+    uint64_t host[3];
+    const hipError_t e = launch_stats_end(c, out ? host : nullptr);
+    if (e == hipSuccess && out) { out->SdfSamples = host[0]; out->PixelLightPairs = host[1]; out->TracedPairs = host[2]; }
+    return e;
+}
+
 // Handles are the object addresses, but an address is only trusted after it has been found in this table: a stale, foreign or
 // garbage handle is answered with ILM_ERR_INVALID_HANDLE instead of being dereferenced (the C# side owns handle lifetimes and can
 // hand in anything).  One mutex-protected lookup per entry point: ~50 ns against microseconds of launch cost.
@@ -3043,9 +3067,11 @@ int32_t reserve_light_recs(Ctx* c, int light_count) {
 }
 
 // shared by the light passes: resource checks + the launch descriptor.  with_cells = false: the field as the plain view of the general
-// sampler, no cell array (the directional pass has no in-volume loop)
+// sampler, no cell array (the directional pass has no in-volume loop).  *out_field / *out_gbuffer: the objects behind hsdf / hgbuffer
+// (null for handle 0), for light_pass_queued() once the pass has been queued.
 int32_t fill_light_launch(Ctx* c, const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf,
-                          IlmHandle hlightmap, int32_t row_begin, int32_t row_end, LightLaunch* a, bool with_cells = true) {
+                          IlmHandle hlightmap, int32_t row_begin, int32_t row_end, LightLaunch* a, Sdf** out_field, GBuffer** out_gbuffer,
+                          bool with_cells = true) {
     Lightmap* m = from_handle<Lightmap>(hlightmap, kMagicLightmap);
     if (!m) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
     GBuffer* g = nullptr; Sdf* f = nullptr;
@@ -3079,7 +3105,8 @@ int32_t fill_light_launch(Ctx* c, const IlmEnvironment* env, const IlmDistanceFi
     a->blend_color = (int16_t)c->light_blend_color; a->blend_alpha = (int16_t)c->light_blend_alpha;
     a->tile_macro = light_tile_macro_for(m->width, row_end - row_begin);
     a->split = 1; a->partials = nullptr; a->tickets = nullptr; a->group_order = nullptr;
-    { const int32_t rc = set_launch_mirrors(m, a); if (rc != ILM_OK) return rc; }
+    { const int32_t rc = set_launch_mirrors(m, a); if (rc != ILM_OK) return rc; }      // store-mode exchange of a group lightmap
+    *out_field = f; *out_gbuffer = g;
     return ILM_OK;
 }
 }  // namespace
@@ -3102,7 +3129,8 @@ int32_t ilm_render_particle_lights(IlmHandle hctx, IlmHandle hsystem, const int3
     const int n = (int)s->chunks.size();
     if (chunk_count < 0 || chunk_count > n) return fail(ILM_ERR_OUT_OF_RANGE, "chunk_count %d outside [0, %d]", chunk_count, n);
     LightLaunch a = {};
-    int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a);
+    Sdf* f = nullptr; GBuffer* g = nullptr;
+    int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, &f, &g);
     if (rc != ILM_OK) return rc;
     if (chunk_count == 0) return ILM_OK;
     Engine* e = s->engine;
@@ -3140,19 +3168,11 @@ int32_t ilm_render_particle_lights(IlmHandle hctx, IlmHandle hsystem, const int3
     a.light_count = 0;
     a.light_count_ptr = c->d_pl_count.as<int32_t>();
     a.accumulate = 1;
-    if (stats) {
-        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
-        a.stats = c->d_stats;
-    }
+    HIP_TRY(launch_stats_begin(c, stats != nullptr, &a.stats));
     c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
     HIP_TRY(launch_sphere_lights_prepared(a, c->d_pl_recs.p, c->main()));
-    HIP_TRY(light_pass_queued(c, hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr, hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr));
-    if (stats) {
-        unsigned long long host[3] = { 0, 0, 0 };
-        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        stats->SdfSamples = host[0]; stats->PixelLightPairs = host[1]; stats->TracedPairs = host[2];
-    }
+    HIP_TRY(light_pass_queued(c, f, g));
+    HIP_TRY(launch_stats_end(c, stats));
     return ILM_OK;
 }
 
@@ -3581,18 +3601,10 @@ int32_t ilm_visualize_distance_field(IlmHandle hctx, IlmHandle hsdf, const IlmDi
     a.mode = p.Mode; a.blend_mode = p.BlendMode;
     HIP_TRY(hipSetDevice(c->device));
     if (f->ctx != c) HIP_TRY(shared_before_read(f->shared, f->ctx, c));      // a sibling's field: behind everything its owner has queued
-    if (out_stats) {
-        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
-        a.stats = c->d_stats;
-    }
+    HIP_TRY(launch_stats_begin(c, out_stats != nullptr, &a.stats));
     HIP_TRY(launch_visualize(a, c->main()));
     HIP_TRY(light_pass_queued(c, f, nullptr));
-    if (out_stats) {
-        unsigned long long host[3] = { 0, 0, 0 };
-        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        out_stats[0] = host[0]; out_stats[1] = host[1]; out_stats[2] = host[2];
-    }
+    HIP_TRY(launch_stats_end(c, out_stats));
     return ILM_OK;
 }
 
@@ -3864,22 +3876,11 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     ILM_TRACE_RANGE("ilm_render_sphere_lights");
     Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
     if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
-    Lightmap* m = from_handle<Lightmap>(hlightmap, kMagicLightmap);
-    if (!m) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
-    GBuffer* g = nullptr; Sdf* f = nullptr;
-    if (hgbuffer) { g = from_handle<GBuffer>(hgbuffer, kMagicGBuffer); if (!g) return fail(ILM_ERR_INVALID_HANDLE, "not a G-buffer handle"); }
-    if (hsdf) { f = from_handle<Sdf>(hsdf, kMagicSdf); if (!f) return fail(ILM_ERR_INVALID_HANDLE, "not a distance field handle"); }
-    if (!env || !df) return fail(ILM_ERR_INVALID_ARGUMENT, "NULL argument");
     if (light_count < 0 || (light_count > 0 && !lights)) return fail(ILM_ERR_INVALID_ARGUMENT, "bad light array");
     if (light_count > 65535) return fail(ILM_ERR_TOO_MANY, "at most 65535 lights per call");
-    // (the lightmap is written: the context's own; the field and the G-buffer are read: the context's or a sibling's, ilm_ctx_create_sibling)
-    if (m->ctx != c || (g && !siblings(g->ctx, c)) || (f && !siblings(f->ctx, c))) return fail(ILM_ERR_INVALID_ARGUMENT, "resources belong to another context");
-    { char why[256]; if (field_uniforms_mismatch(f, df, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
-    if (row_begin < 0 || row_end > m->height || row_begin > row_end)
-        return fail(ILM_ERR_OUT_OF_RANGE, "rows [%d, %d) outside [0, %d]", row_begin, row_end, m->height);
-    HIP_TRY(hipSetDevice(c->device));
-    TraceSdfView trace_view;
-    HIP_TRY(borrowed_trace_view(c, f, g, df, &trace_view));
+    LightLaunch a = {};
+    Sdf* f = nullptr; GBuffer* g = nullptr;
+    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, &f, &g); if (rc != ILM_OK) return rc; }
 
     { const int32_t rc = reserve_light_recs(c, light_count); if (rc != ILM_OK) return rc; }
     if (light_count > 0) {
@@ -3887,44 +3888,22 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
         const void* staged = nullptr; int slot = 0;
         int32_t rc = stage_small(c, lights, sizeof(IlmLightVertex) * (size_t)light_count, &staged, &slot);
         if (rc != ILM_OK) return rc;
-        HIP_TRY(launch_prepare_lights(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, trace_view, c->d_recs.p, c->main()));
+        HIP_TRY(launch_prepare_lights(static_cast<const IlmLightVertex*>(staged), light_count, *env, *df, a.sdf, c->d_recs.p, c->main()));
         rc = staged_small_done(c, slot);
         if (rc != ILM_OK) return rc;
     }
 
-    LightLaunch a = {};
     a.light_count = light_count;
-    a.env = *env;
-    a.df = *df;
-    a.gbuffer.texels = g ? g->texels : nullptr;
-    a.gbuffer.width = g ? g->width : 0; a.gbuffer.height = g ? g->height : 0; a.gbuffer.format = g ? g->format : 0;
-    a.sdf = trace_view;
     for (int i = 0; i < 4; i++) a.ambient[i] = ambient ? ambient[i] : 0.0f;
-    a.lightmap = m->texels; a.width = m->width; a.height = m->height; a.format = m->format;
-    a.row_begin = row_begin; a.row_end = row_end;
-    a.stats = nullptr; a.light_count_ptr = nullptr;
     a.accumulate = ambient ? 0 : 1;          // a further light group of the frame: added to what the lightmap holds
     a.ramp = RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h };
-    a.blend_fp16 = (c->lightmap_blend == ILM_BLEND_FP16_PER_LIGHT) ? 1 : 0;
-    a.blend_color = (int16_t)c->light_blend_color; a.blend_alpha = (int16_t)c->light_blend_alpha;
-    a.tile_macro = light_tile_macro_for(m->width, row_end - row_begin);
-    if (stats) {
-        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
-        a.stats = c->d_stats;
-    }
-    a.split = 1; a.partials = nullptr; a.tickets = nullptr; a.group_order = nullptr;
-    { const int32_t rc = set_launch_mirrors(m, &a); if (rc != ILM_OK) return rc; }      // store-mode exchange of a group lightmap
+    HIP_TRY(launch_stats_begin(c, stats != nullptr, &a.stats));
     { const int32_t rc = plan_light_split(c, &a); if (rc != ILM_OK) return rc; }
     { const int32_t rc = plan_group_order(c, &a, lights, light_count, 16 * a.tile_macro); if (rc != ILM_OK) return rc; }
     c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
     HIP_TRY(launch_sphere_lights_prepared(a, c->d_recs.p, c->main()));
     HIP_TRY(light_pass_queued(c, f, g));
-    if (stats) {
-        unsigned long long host[3] = { 0, 0, 0 };
-        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        stats->SdfSamples = host[0]; stats->PixelLightPairs = host[1]; stats->TracedPairs = host[2];
-    }
+    HIP_TRY(launch_stats_end(c, stats));
     return ILM_OK;
 }
 
@@ -3940,9 +3919,8 @@ static int32_t render_full_frame_lights(Ctx* c, const IlmLightVertex* lights, in
                                         IlmHandle hlightmap, int32_t row_begin, int32_t row_end, IlmRenderStats* stats, int rec_slots,
                                         int light_limit, const RampView& ramp, const PrepareFullFrameLights& prepare, LaunchFullFrameLights launch) {
     LightLaunch a = {};
-    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, false); if (rc != ILM_OK) return rc; }
-    Sdf* f = hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr;
-    GBuffer* g = hgbuffer ? from_handle<GBuffer>(hgbuffer, kMagicGBuffer) : nullptr;
+    Sdf* f = nullptr; GBuffer* g = nullptr;
+    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, &f, &g, false); if (rc != ILM_OK) return rc; }
     if (stats) stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0;
 
     if (light_limit > 0 && light_count > light_limit)      // (keeps the slot count and reserve_light_recs's doubling inside an int)
@@ -3960,21 +3938,13 @@ static int32_t render_full_frame_lights(Ctx* c, const IlmLightVertex* lights, in
     for (int i = 0; i < 4; i++) a.ambient[i] = ambient ? ambient[i] : 0.0f;
     a.accumulate = ambient ? 0 : 1;
     a.ramp = ramp;
-    if (stats) {
-        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 3 * sizeof(unsigned long long), c->main()));
-        a.stats = c->d_stats;
-    }
+    HIP_TRY(launch_stats_begin(c, stats != nullptr, &a.stats));
     // (ilm_debug_last_light_launch: one workgroup per 16 x 16 tile of the rows, no split, no tile map)
     c->last_light_blocks = ((a.width + kLightTile - 1) / kLightTile) * ((row_end - row_begin + kLightTile - 1) / kLightTile);
     c->last_light_split = 1; c->last_light_macro = 0;
     HIP_TRY(launch(a, c->d_recs.p, c->main()));
     HIP_TRY(light_pass_queued(c, f, g));
-    if (stats) {
-        unsigned long long host[3] = { 0, 0, 0 };
-        HIP_TRY(hipMemcpyAsync(host, c->d_stats, sizeof(host), hipMemcpyDeviceToHost, c->main()));
-        HIP_TRY(hipStreamSynchronize(c->main()));
-        stats->SdfSamples = host[0]; stats->PixelLightPairs = host[1]; stats->TracedPairs = host[2];
-    }
+    HIP_TRY(launch_stats_end(c, stats));
     return ILM_OK;
 }
 

@@ -1460,179 +1460,173 @@ IlmEnvironment LightingRenderer::GetEnvironmentUniforms() const {
     return e;
 }
 
+namespace {
+// What RenderLighting knows about a light kind beyond its packing: the five ilm_render_*_lights entries share one signature
+typedef int32_t (*RenderLightsEntry)(IlmHandle, const IlmLightVertex*, int32_t, const IlmEnvironment*, const IlmDistanceFieldUniforms*, IlmHandle, IlmHandle,
+                                     const float*, IlmHandle, int32_t, int32_t, IlmRenderStats*);
+struct LightKindInfo {
+    const char* name;
+    RenderLightsEntry render;
+    bool bindsRamp;            // the state's texture is the ramp of its technique; false: the ramp binding is neither read nor changed
+    bool uploadsTexture;       // the state's texture is bound through ilm_ctx_set_projector_texture[_mips] before its call
+};
+const LightKindInfo kLightKinds[(size_t)LightKind::Count] = {
+    { "sphere", ilm_render_sphere_lights, true, false },
+    { "directional", ilm_render_directional_lights, true, false },
+    { "line", ilm_render_line_lights, false, false },                   // no LineLightWithRamp technique
+    { "projector", ilm_render_projector_lights, false, true },
+    { "volumetric", ilm_render_volumetric_lights, false, false },       // no ramp technique either
+};
+
+void AddStats(IlmRenderStats* total, const IlmRenderStats& part) {
+    if (!total) return;
+    total->SdfSamples += part.SdfSamples; total->PixelLightPairs += part.PixelLightPairs; total->TracedPairs += part.TracedPairs;
+}
+}  // namespace
+
 // RenderLighting, LightingRenderer.cs:917-1191 (sphere, directional, line, projector, volumetric and particle lights)
 void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int rowEnd, IlmRenderStats* stats) {
     if (rowEnd < 0) rowEnd = Configuration.RenderHeight;
-    // the probe techniques of directional lights (DirectionalLightProbe*) are not built: refuse rather than leave them out of the probes
-    if (Probes.Count() > 0)
-        for (const DirectionalLightSource& d : Environment->DirectionalLights)
-            if (d.Enabled) throw InvalidOperationException("RenderLighting: directional lights do not reach light probes yet");
-    // nor is the projector lights' (ProjectorLightProbe.fx)
-    if (Probes.Count() > 0)
-        for (const ProjectorLightSource& pl : Environment->ProjectorLights)
-            if (pl.Enabled) throw InvalidOperationException("RenderLighting: projector lights do not reach light probes yet");
-    // nor is the line lights' (LineLightProbe.fx)
-    if (Probes.Count() > 0)
-        for (const LineLightSource& ll : Environment->LineLights)
-            if (ll.Enabled) throw InvalidOperationException("RenderLighting: line lights do not reach light probes yet");
-    // nor is the volumetric lights' (VolumetricLightProbe.fx)
-    if (Probes.Count() > 0)
-        for (const VolumetricLightSource& vl : Environment->VolumetricLights)
-            if (vl.Enabled) throw InvalidOperationException("RenderLighting: volumetric lights do not reach light probes yet");
-    vertices.clear();
+    // the probe techniques of these kinds (DirectionalLightProbe*, ProjectorLightProbe.fx, LineLightProbe.fx, VolumetricLightProbe.fx) are
+    // not built: refuse rather than leave the lights out of the probes
+    auto refuseWithProbes = [&](const auto& lights, LightKind kind) {
+        for (const auto& l : lights)
+            if (l.Enabled)
+                throw InvalidOperationException(std::string("RenderLighting: ") + kLightKinds[(size_t)kind].name + " lights do not reach light probes yet");
+    };
+    if (Probes.Count() > 0) {
+        refuseWithProbes(Environment->DirectionalLights, LightKind::Directional);
+        refuseWithProbes(Environment->ProjectorLights, LightKind::Projector);
+        refuseWithProbes(Environment->LineLights, LightKind::Line);
+        refuseWithProbes(Environment->VolumetricLights, LightKind::Volumetric);
+    }
+
+    // ---- sort --------------------------------------------------------------------------------------------------------------------------
     // LightSorter (:2066-2096): SortKey first; blend mode, ramp texture and type are the same for every light of this pass.  The
     // reference's sort is not stable for equal keys; a stable one keeps list order, which is one of its possible outcomes
     // (Lights before Replicators here, since the mirror holds them in two lists).
     // Directional lights sort after spheres of equal key (TypeID 2 after 1, :2094): listed last, the stable sort keeps them there.
     // Line lights (TypeID 4) likewise, after the directional ones, projector lights (TypeID 5) after those, volumetric lights (TypeID 6) last.
-    struct Entry { int sortKey; const SphereLightSource* sphere; const LightSourceReplicator* replicator; const DirectionalLightSource* directional;
-                   const ProjectorLightSource* projector; const LineLightSource* line; const VolumetricLightSource* volumetric = nullptr; };
+    enum class Source { Sphere, Replicator, Directional, Line, Projector, Volumetric };
+    struct Entry { int sortKey; Source source; const void* light; };      // light: the source's struct in the environment
     std::vector<Entry> sorted;
-    for (const SphereLightSource& l : Environment->Lights)
-        if (l.Enabled) sorted.push_back({ l.SortKey, &l, nullptr, nullptr, nullptr, nullptr });
-    for (const LightSourceReplicator& r : Environment->Replicators)
-        if (r.Enabled) sorted.push_back({ r.SortKey, nullptr, &r, nullptr, nullptr, nullptr });
-    for (const DirectionalLightSource& d : Environment->DirectionalLights)
-        if (d.Enabled) sorted.push_back({ d.SortKey, nullptr, nullptr, &d, nullptr, nullptr });
-    for (const LineLightSource& ll : Environment->LineLights)
-        if (ll.Enabled) sorted.push_back({ ll.SortKey, nullptr, nullptr, nullptr, nullptr, &ll });
-    for (const ProjectorLightSource& pl : Environment->ProjectorLights)
-        if (pl.Enabled) sorted.push_back({ pl.SortKey, nullptr, nullptr, nullptr, &pl, nullptr });
-    for (const VolumetricLightSource& vl : Environment->VolumetricLights)
-        if (vl.Enabled) sorted.push_back({ vl.SortKey, nullptr, nullptr, nullptr, nullptr, nullptr, &vl });
+    auto candidates = [&](Source source, const auto& lights) {
+        for (const auto& l : lights)
+            if (l.Enabled) sorted.push_back({ l.SortKey, source, &l });
+    };
+    candidates(Source::Sphere, Environment->Lights);
+    candidates(Source::Replicator, Environment->Replicators);
+    candidates(Source::Directional, Environment->DirectionalLights);
+    candidates(Source::Line, Environment->LineLights);
+    candidates(Source::Projector, Environment->ProjectorLights);
+    candidates(Source::Volumetric, Environment->VolumetricLights);
     std::stable_sort(sorted.begin(), sorted.end(), [](const Entry& x, const Entry& y) { return x.sortKey < y.sortKey; });
+
+    // ---- pack and group ----------------------------------------------------------------------------------------------------------------
     // GetLightRenderState (:799-845): lights that share a ramp texture, quality settings and blend state (Key.BlendState ??
     // BlendState.Additive, :806: here the light's two blend functions) form one render state; the states of a type are drawn one after
-    // the other onto the same target, in the order their keys first appear, and the types in the fixed order below -- sphere,
-    // directional, line, projector, volumetric, particle.  (The reference draws its states in the enumeration order of a dictionary
+    // the other onto the same target, in the order their keys first appear, and the types in the fixed order of LightKind -- sphere,
+    // directional, line, projector, volumetric -- then particle.  (The reference draws its states in the enumeration order of a dictionary
     // keyed by type, texture, quality and blend state, which its text does not define: with alternate blend modes the order ACROSS
     // states matters, and a host that depends on it says so through SortKey within a type only.)
-    // A replicator takes its state from its Template (:802).
-    groupKeys.clear();
-    groupQuality.clear();
-    groupBlend.clear();
-    groups.clear();
-    // the render state of a (ramp texture, quality, blend functions) key among `keys` / `qualities` / `blends` / `lists`, appended when the key is new
-    auto stateFor = [&](const std::shared_ptr<RampTexture>& texture, const RendererQualitySettings* quality, std::pair<int, int> blend,
-                        std::vector<const RampTexture*>& keys, std::vector<const RendererQualitySettings*>& qualities,
-                        std::vector<std::pair<int, int>>& blends, std::vector<std::vector<IlmLightVertex>>& lists) -> size_t {
-        const RampTexture* ramp = texture ? texture.get() : Configuration.DefaultRampTexture.get();
-        if (ramp && ((ramp->Width == 1 && ramp->Height == 1) || ramp->Width <= 0))
-            ramp = nullptr;                                   // a 1 x 1 ramp is no ramp (:822-827)
-        size_t g = 0;
-        while (g < keys.size() && !(keys[g] == ramp && qualities[g] == quality && blends[g] == blend)) g++;
-        if (g == keys.size()) { keys.push_back(ramp); qualities.push_back(quality); blends.push_back(blend); lists.emplace_back(); }
-        return g;
+    vertices.clear();
+    for (std::vector<LightRenderState>& kind : renderStates) kind.clear();
+    // the render state of `l`'s key among those of `kind`, appended when the key is new
+    auto stateFor = [&](LightKind kind, const auto& l) -> LightRenderState& {
+        const RampTexture* texture = l.TextureRef.get();
+        // a projector state's key is the projected texture itself (:1389); everywhere else the member is a ramp: null is the
+        // configuration's default, and a 1 x 1 ramp is no ramp (:822-827)
+        if (kind != LightKind::Projector) {
+            if (!texture) texture = Configuration.DefaultRampTexture.get();
+            if (texture && ((texture->Width == 1 && texture->Height == 1) || texture->Width <= 0)) texture = nullptr;
+        }
+        const RendererQualitySettings* quality = l.Quality.get();
+        const std::pair<int, int> blend(l.BlendColorFunction, l.BlendAlphaFunction);
+        std::vector<LightRenderState>& list = renderStates[(size_t)kind];
+        for (LightRenderState& s : list)
+            if (s.texture == texture && s.quality == quality && s.blend == blend) return s;
+        list.push_back({ texture, quality, blend, {} });
+        return list.back();
     };
-    auto blendOf = [](const auto& l) { return std::pair<int, int>(l.BlendColorFunction, l.BlendAlphaFunction); };
-    auto groupFor = [&](const SphereLightSource& l) -> size_t {
-        return stateFor(l.TextureRef, l.Quality.get(), blendOf(l), groupKeys, groupQuality, groupBlend, groups);
-    };
-    // directional lights form render states of their own (LightTypeRenderStateKey.Type): grouped by the same key, in first-appearance order
-    directionalKeys.clear();
-    directionalQuality.clear();
-    directionalBlend.clear();
-    directionalGroups.clear();
-    // line lights: render states of their own under the same key (the technique reads no ramp)
-    lineKeys.clear();
-    lineQuality.clear();
-    lineBlend.clear();
-    lineGroups.clear();
-    // projector lights: one render state per texture (and quality) -- the key's RampTexture member is the projected texture (:1389)
-    projectorKeys.clear();
-    projectorQuality.clear();
-    projectorBlend.clear();
-    projectorGroups.clear();
-    // Volumetric lights: the reference draws two render states per (texture, quality) key, ShadowedVolumetricLight and VolumetricLight,
-    // selected by CastsShadows (:190-193).  The two techniques differ only in LightProperties.w, which the vertex carries, so ONE call
-    // serves the shadowed and the unshadowed lights of a key in list order: what a light adds to a pixel depends on no other light, the
-    // lights of each state keep their order within the call, and the blend is an addition -- the states' sums are the same terms.  (In the
-    // fp32 model the sum of a call is rounded in list order, where two calls would round state by state: sums of the same terms.)
-    volumetricKeys.clear();
-    volumetricQuality.clear();
-    volumetricBlend.clear();
-    volumetricGroups.clear();
+    auto add = [&](LightRenderState& state, const IlmLightVertex& v) { state.vertices.push_back(v); vertices.push_back(v); };
+    const bool haveField = Field != nullptr;
     for (const Entry& e : sorted) {
         IlmLightVertex v;
-        if (e.volumetric) {
-            if (!PackVolumetricLight(*e.volumetric, intensityScale, Field != nullptr, v))
-                continue;
-            volumetricGroups[stateFor(e.volumetric->TextureRef, e.volumetric->Quality.get(), blendOf(*e.volumetric), volumetricKeys, volumetricQuality, volumetricBlend,
-                                      volumetricGroups)].push_back(v);
-            vertices.push_back(v);
-            continue;
+        switch (e.source) {
+        case Source::Sphere: {
+            const SphereLightSource& l = *static_cast<const SphereLightSource*>(e.light);
+            if (PackSphereLight(l, intensityScale, haveField, v)) add(stateFor(LightKind::Sphere, l), v);
+            break;
         }
-        if (e.projector) {
-            if (!PackProjectorLight(*e.projector, intensityScale, Field != nullptr, Environment->MaximumZ, Configuration.RenderScale,
-                                    Configuration.ProjectorMipBias, v))
-                continue;
-            const RampTexture* texture = e.projector->TextureRef.get();
-            const RendererQualitySettings* quality = e.projector->Quality.get();
-            size_t g = 0;
-            while (g < projectorKeys.size() && !(projectorKeys[g] == texture && projectorQuality[g] == quality && projectorBlend[g] == blendOf(*e.projector))) g++;
-            if (g == projectorKeys.size()) {
-                projectorKeys.push_back(texture); projectorQuality.push_back(quality); projectorBlend.push_back(blendOf(*e.projector)); projectorGroups.emplace_back();
+        case Source::Replicator: {
+            // RenderReplicatorLightSource (:1221-1255): the template's packed vertex with position / colour / radius / ramp length /
+            // specular replaced per placement; a placement whose final alpha is <= 0 is dropped.  A replicator takes its state from its
+            // Template (:802).
+            const LightSourceReplicator& r = *static_cast<const LightSourceReplicator*>(e.light);
+            const SphereLightSource& t = r.Template;
+            SphereLightSource visible = t;
+            visible.Opacity = 1;                              // the template's own Opacity only matters through the per-placement product
+            PackSphereLight(visible, intensityScale, haveField, v);
+            LightRenderState& state = stateFor(LightKind::Sphere, t);
+            for (const ReplicatedLight& rl : r.Lights) {
+                const Vector4 color = rl.Color.value_or(t.Color);
+                const float alpha = color.W * (rl.Opacity.value_or(t.Opacity) * intensityScale);
+                if (alpha <= 0)
+                    continue;
+                const Vector3 spec = rl.SpecularColor.value_or(t.SpecularColor);
+                const IlmFloat4 pos = { rl.Position.X, rl.Position.Y, rl.Position.Z, 0 };
+                v.LightPosition1 = v.LightPosition2 = v.LightPosition3 = pos;
+                v.Color1 = { color.X, color.Y, color.Z, alpha };
+                v.Color2 = { spec.X, spec.Y, spec.Z, rl.SpecularPower.value_or(t.SpecularPower) };
+                v.LightProperties.x = rl.Radius.value_or(t.Radius);
+                v.LightProperties.y = rl.RampLength.value_or(t.RampLength);
+                add(state, v);
             }
-            projectorGroups[g].push_back(v);
-            vertices.push_back(v);
-            continue;
+            break;
         }
-        if (e.line) {
-            if (!PackLineLight(*e.line, intensityScale, Field != nullptr, v))
-                continue;
-            lineGroups[stateFor(e.line->TextureRef, e.line->Quality.get(), blendOf(*e.line), lineKeys, lineQuality, lineBlend, lineGroups)].push_back(v);
-            vertices.push_back(v);
-            continue;
+        case Source::Directional: {
+            const DirectionalLightSource& l = *static_cast<const DirectionalLightSource*>(e.light);
+            if (PackDirectionalLight(l, intensityScale, v)) add(stateFor(LightKind::Directional, l), v);
+            break;
         }
-        if (e.directional) {
-            if (!PackDirectionalLight(*e.directional, intensityScale, v))
-                continue;
-            directionalGroups[stateFor(e.directional->TextureRef, e.directional->Quality.get(), blendOf(*e.directional), directionalKeys, directionalQuality,
-                                       directionalBlend, directionalGroups)].push_back(v);
-            vertices.push_back(v);
-            continue;
+        case Source::Line: {
+            const LineLightSource& l = *static_cast<const LineLightSource*>(e.light);
+            if (PackLineLight(l, intensityScale, haveField, v)) add(stateFor(LightKind::Line, l), v);
+            break;
         }
-        if (e.sphere) {
-            if (!PackSphereLight(*e.sphere, intensityScale, Field != nullptr, v))
-                continue;
-            groups[groupFor(*e.sphere)].push_back(v);
-            vertices.push_back(v);
-            continue;
+        case Source::Projector: {
+            const ProjectorLightSource& l = *static_cast<const ProjectorLightSource*>(e.light);
+            if (PackProjectorLight(l, intensityScale, haveField, Environment->MaximumZ, Configuration.RenderScale, Configuration.ProjectorMipBias, v))
+                add(stateFor(LightKind::Projector, l), v);
+            break;
         }
-        // RenderReplicatorLightSource (:1221-1255): the template's packed vertex with position / colour / radius / ramp length /
-        // specular replaced per placement; a placement whose final alpha is <= 0 is dropped
-        const SphereLightSource& t = e.replicator->Template;
-        SphereLightSource visible = t;
-        visible.Opacity = 1;                                  // the template's own Opacity only matters through the per-placement product
-        PackSphereLight(visible, intensityScale, Field != nullptr, v);
-        const size_t g = groupFor(t);
-        for (const ReplicatedLight& rl : e.replicator->Lights) {
-            const Vector4 color = rl.Color.value_or(t.Color);
-            const float alpha = color.W * (rl.Opacity.value_or(t.Opacity) * intensityScale);
-            if (alpha <= 0)
-                continue;
-            const Vector3 spec = rl.SpecularColor.value_or(t.SpecularColor);
-            const IlmFloat4 pos = { rl.Position.X, rl.Position.Y, rl.Position.Z, 0 };
-            v.LightPosition1 = v.LightPosition2 = v.LightPosition3 = pos;
-            v.Color1 = { color.X, color.Y, color.Z, alpha };
-            v.Color2 = { spec.X, spec.Y, spec.Z, rl.SpecularPower.value_or(t.SpecularPower) };
-            v.LightProperties.x = rl.Radius.value_or(t.Radius);
-            v.LightProperties.y = rl.RampLength.value_or(t.RampLength);
-            groups[g].push_back(v);
-            vertices.push_back(v);
+        case Source::Volumetric: {
+            // The reference draws two render states per (texture, quality) key, ShadowedVolumetricLight and VolumetricLight, selected by
+            // CastsShadows (:190-193).  The two techniques differ only in LightProperties.w, which the vertex carries, so ONE call serves
+            // the shadowed and the unshadowed lights of a key in list order: what a light adds to a pixel depends on no other light, the
+            // lights of each state keep their order within the call, and the blend is an addition -- the states' sums are the same terms.
+            // (In the fp32 model the sum of a call is rounded in list order, where two calls would round state by state: sums of the same
+            // terms.)
+            const VolumetricLightSource& l = *static_cast<const VolumetricLightSource*>(e.light);
+            if (PackVolumetricLight(l, intensityScale, haveField, v)) add(stateFor(LightKind::Volumetric, l), v);
+            break;
+        }
         }
     }
+    // no lights: the clear still happens (with directional lights alone, their first call carries it; line, projector and volumetric
+    // states always add)
+    if (renderStates[(size_t)LightKind::Sphere].empty() && renderStates[(size_t)LightKind::Directional].empty())
+        renderStates[(size_t)LightKind::Sphere].push_back({ nullptr, nullptr, { ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD }, {} });
+
+    // ---- draw --------------------------------------------------------------------------------------------------------------------------
     const IlmEnvironment env = GetEnvironmentUniforms();
     const IlmDistanceFieldUniforms dfu = GetDistanceFieldUniforms(Configuration.DefaultQuality);
+    const IlmHandle field = Field ? Field->Texture() : 0;
     // clear colour: Ambient * intensityScale (:1013-1024)
     const float ambient[4] = { Environment->Ambient.X * intensityScale, Environment->Ambient.Y * intensityScale,
                                Environment->Ambient.Z * intensityScale, Environment->Ambient.W * intensityScale };
-    // no lights: the clear still happens (with directional lights alone, their first launch carries it; line, projector and volumetric groups always add)
-    if (groups.empty() && directionalGroups.empty()) {
-        groupKeys.push_back(nullptr); groupQuality.push_back(nullptr); groupBlend.push_back({ ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD }); groups.emplace_back();
-    }
-    if (stats) { stats->SdfSamples = stats->PixelLightPairs = stats->TracedPairs = 0; }
-    // every group sets its blend functions before its call (no native call while they are what the context holds: a frame of default
+    if (stats) *stats = IlmRenderStats{};
+    // every state sets its blend functions before its call (no native call while they are what the context holds: a frame of default
     // lights makes the calls it always made); the context is left at ADD / ADD however this function is left
     struct BlendReset {
         LightingRenderer& r;
@@ -1642,81 +1636,52 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
             r.boundBlend = { ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD };
         }
     } blendReset{ *this };
-    for (size_t g = 0; g < groups.size(); g++) {
-        BindRamp(groupKeys[g]);
-        BindBlend(groupBlend[g]);
-        IlmRenderStats gs{};
-        const IlmDistanceFieldUniforms gdfu = groupQuality[g] ? GetDistanceFieldUniforms(*groupQuality[g]) : dfu;     // SetDistanceFieldParameters(material, true, ltrs.Key.Quality), :792
-        ThrowIfFailed(ilm_render_sphere_lights(Context.Handle(), groups[g].empty() ? nullptr : groups[g].data(), (int32_t)groups[g].size(),
-                                               &env, &gdfu, gbuffer, Field ? Field->Texture() : 0, (g == 0) ? ambient : nullptr, lightmap, rowBegin, rowEnd,
-                                               stats ? &gs : nullptr));
-        if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
+    // the frame's first call carries the clear colour: the first sphere state's or, without sphere states, the first directional one's
+    const float* clear = ambient;
+    for (size_t kind = 0; kind < renderStates.size(); kind++) {
+        const LightKindInfo& info = kLightKinds[kind];
+        for (const LightRenderState& state : renderStates[kind]) {
+            if (info.bindsRamp) BindRamp(state.texture);
+            BindBlend(state.blend);
+            // (a texture with a mip chain goes through the call that takes the levels; a one-level texture makes the call it always made)
+            if (info.uploadsTexture && state.texture->LevelCount > 1)
+                ThrowIfFailed(ilm_ctx_set_projector_texture_mips(Context.Handle(), state.texture->Texels.data(), state.texture->Width, state.texture->Height,
+                                                                 state.texture->LevelCount));
+            else if (info.uploadsTexture)
+                ThrowIfFailed(ilm_ctx_set_projector_texture(Context.Handle(), state.texture->Texels.data(), state.texture->Width, state.texture->Height));
+            IlmRenderStats part{};
+            const IlmDistanceFieldUniforms stateDfu = state.quality ? GetDistanceFieldUniforms(*state.quality) : dfu;     // SetDistanceFieldParameters(material, true, ltrs.Key.Quality), :792
+            ThrowIfFailed(info.render(Context.Handle(), state.vertices.empty() ? nullptr : state.vertices.data(), (int32_t)state.vertices.size(), &env, &stateDfu,
+                                      gbuffer, field, clear, lightmap, rowBegin, rowEnd, stats ? &part : nullptr));
+            AddStats(stats, part);
+            clear = nullptr;
+        }
+        if (info.uploadsTexture && !renderStates[kind].empty()) ThrowIfFailed(ilm_ctx_set_projector_texture(Context.Handle(), nullptr, 0, 0));
     }
-    // the directional render states, onto the same target after the sphere ones
-    for (size_t g = 0; g < directionalGroups.size(); g++) {
-        BindRamp(directionalKeys[g]);
-        BindBlend(directionalBlend[g]);
-        IlmRenderStats gs{};
-        const IlmDistanceFieldUniforms gdfu = directionalQuality[g] ? GetDistanceFieldUniforms(*directionalQuality[g]) : dfu;
-        ThrowIfFailed(ilm_render_directional_lights(Context.Handle(), directionalGroups[g].data(), (int32_t)directionalGroups[g].size(), &env, &gdfu, gbuffer,
-                                                    Field ? Field->Texture() : 0, (groups.empty() && g == 0) ? ambient : nullptr, lightmap, rowBegin, rowEnd,
-                                                    stats ? &gs : nullptr));
-        if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
-    }
-    // the line render states: no ramp technique, the ramp binding is neither read nor changed
-    for (size_t g = 0; g < lineGroups.size(); g++) {
-        BindBlend(lineBlend[g]);
-        IlmRenderStats gs{};
-        const IlmDistanceFieldUniforms gdfu = lineQuality[g] ? GetDistanceFieldUniforms(*lineQuality[g]) : dfu;
-        ThrowIfFailed(ilm_render_line_lights(Context.Handle(), lineGroups[g].data(), (int32_t)lineGroups[g].size(), &env, &gdfu, gbuffer,
-                                             Field ? Field->Texture() : 0, nullptr, lightmap, rowBegin, rowEnd, stats ? &gs : nullptr));
-        if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
-    }
-    // the projector render states: the group's texture, then one call; the ramp binding is not theirs
-    for (size_t g = 0; g < projectorGroups.size(); g++) {
-        // (a texture with a mip chain goes through the call that takes the levels; a one-level texture makes the call it always made)
-        const RampTexture& texture = *projectorKeys[g];
-        BindBlend(projectorBlend[g]);
-        if (texture.LevelCount > 1)
-            ThrowIfFailed(ilm_ctx_set_projector_texture_mips(Context.Handle(), texture.Texels.data(), texture.Width, texture.Height, texture.LevelCount));
-        else
-            ThrowIfFailed(ilm_ctx_set_projector_texture(Context.Handle(), texture.Texels.data(), texture.Width, texture.Height));
-        IlmRenderStats gs{};
-        const IlmDistanceFieldUniforms gdfu = projectorQuality[g] ? GetDistanceFieldUniforms(*projectorQuality[g]) : dfu;
-        ThrowIfFailed(ilm_render_projector_lights(Context.Handle(), projectorGroups[g].data(), (int32_t)projectorGroups[g].size(), &env, &gdfu, gbuffer,
-                                                  Field ? Field->Texture() : 0, nullptr, lightmap, rowBegin, rowEnd, stats ? &gs : nullptr));
-        if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
-    }
-    if (!projectorGroups.empty()) ThrowIfFailed(ilm_ctx_set_projector_texture(Context.Handle(), nullptr, 0, 0));
-    // the volumetric render states, last: no ramp technique, neither binding is read
-    for (size_t g = 0; g < volumetricGroups.size(); g++) {
-        BindBlend(volumetricBlend[g]);
-        IlmRenderStats gs{};
-        const IlmDistanceFieldUniforms gdfu = volumetricQuality[g] ? GetDistanceFieldUniforms(*volumetricQuality[g]) : dfu;
-        ThrowIfFailed(ilm_render_volumetric_lights(Context.Handle(), volumetricGroups[g].data(), (int32_t)volumetricGroups[g].size(), &env, &gdfu, gbuffer,
-                                                   Field ? Field->Texture() : 0, nullptr, lightmap, rowBegin, rowEnd, stats ? &gs : nullptr));
-        if (stats) { stats->SdfSamples += gs.SdfSamples; stats->PixelLightPairs += gs.PixelLightPairs; stats->TracedPairs += gs.TracedPairs; }
-    }
+
+    // ---- particle lights ---------------------------------------------------------------------------------------------------------------
     BindRamp(nullptr);         // particle lights have no ramp technique (:176-178)
     // particle light sources: one more light-type render state each, blended on top (:1126-1141)
     for (const ParticleLightSource& pls : Environment->ParticleLights) {
         if (!pls.Enabled || !pls.IsActive || !pls.System)
             continue;
-        const IlmParticleLightParams p = PackParticleLight(pls, Field != nullptr);
+        const IlmParticleLightParams p = PackParticleLight(pls, haveField);
         // RenderChunk, ParticleSystem.cs:880: quadCount = min(ChunkMaximumCount, chunk.TotalSpawned + 1)
         std::vector<int32_t> quads;
         for (const Particles::ParticleSystem::Chunk& c : pls.System->Chunks())
             quads.push_back(std::min(pls.System->ChunkMaximumCount(), c.TotalSpawned + 1));
         if (quads.empty())
             continue;
-        BindBlend(blendOf(pls.Template));      // a particle light source's template carries its blend functions
-        IlmRenderStats ps{};
+        BindBlend({ pls.Template.BlendColorFunction, pls.Template.BlendAlphaFunction });      // a particle light source's template carries its blend functions
+        IlmRenderStats part{};
         ThrowIfFailed(ilm_render_particle_lights(Context.Handle(), pls.System->Handle(), quads.data(), (int32_t)quads.size(), &p, &env, &dfu,
-                                                 gbuffer, Field ? Field->Texture() : 0, lightmap, rowBegin, rowEnd, stats ? &ps : nullptr));
-        if (stats) { stats->SdfSamples += ps.SdfSamples; stats->PixelLightPairs += ps.PixelLightPairs; stats->TracedPairs += ps.TracedPairs; }
+                                                 gbuffer, field, lightmap, rowBegin, rowEnd, stats ? &part : nullptr));
+        AddStats(stats, part);
     }
     lastInverseScaleFactor = 1.0f / intensityScale;      // new RenderedLighting(this, lightmap.Buffer, 1.0f / intensityScale, ...), :963-966
     BindBlend({ ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD });
+
+    // ---- probes ------------------------------------------------------------------------------------------------------------------------
     if (Probes.Count() > 0)      // :1176-1182 (the probe target is always blended additively, LightingRenderer.LightProbes.cs:27)
         UpdateLightProbes(intensityScale);
 }
@@ -1774,12 +1739,14 @@ void LightingRenderer::UpdateLightProbes(float intensityScale) {
     const IlmDistanceFieldUniforms dfu = GetDistanceFieldUniforms(Configuration.DefaultQuality);
     // the light vertices of this frame were packed with intensityScale folded into Color1.a (RenderSphereLightSource, :1203); every
     // render state draws its lights onto the probe target with its own probe material (with or without a ramp, :159-164): summed here
-    for (size_t g = 0; g < groups.size(); g++) {
-        if (groups[g].empty() && g > 0) continue;
-        BindRamp(groupKeys[g]);
+    const std::vector<LightRenderState>& sphereStates = renderStates[(size_t)LightKind::Sphere];
+    for (size_t g = 0; g < sphereStates.size(); g++) {
+        const LightRenderState& state = sphereStates[g];
+        if (state.vertices.empty() && g > 0) continue;
+        BindRamp(state.texture);
         std::vector<IlmFloat4> part((size_t)n);
-        const IlmDistanceFieldUniforms gdfu = groupQuality[g] ? GetDistanceFieldUniforms(*groupQuality[g]) : dfu;
-        ThrowIfFailed(ilm_render_light_probes(Context.Handle(), groups[g].empty() ? nullptr : groups[g].data(), (int32_t)groups[g].size(),
+        const IlmDistanceFieldUniforms gdfu = state.quality ? GetDistanceFieldUniforms(*state.quality) : dfu;
+        ThrowIfFailed(ilm_render_light_probes(Context.Handle(), state.vertices.empty() ? nullptr : state.vertices.data(), (int32_t)state.vertices.size(),
                                               positions.data(), normals.data(), n, &env, &gdfu, Field ? Field->Texture() : 0, part.data()));
         for (int i = 0; i < n; i++) {
             values[(size_t)i].x += part[(size_t)i].x; values[(size_t)i].y += part[(size_t)i].y;

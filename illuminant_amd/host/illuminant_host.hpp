@@ -19,11 +19,13 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <memory>
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/illuminant_hip.h"
@@ -996,6 +998,19 @@ struct ResolveOptions {
     int RowBegin = 0, RowEnd = -1;                      // destination rows (a group member's strip); RowEnd < 0 => the destination's height
 };
 
+// The light kinds RenderLighting draws as render states, in the order it draws them: LightSourceTypeID sorts Sphere = 1 before
+// Directional = 2, Line = 4, Projector = 5 and Volumetric = 6 (particle lights follow, one state per source)
+enum class LightKind { Sphere, Directional, Line, Projector, Volumetric, Count };
+
+// LightTypeRenderState under its LightTypeRenderStateKey (LightingRenderer.cs:50-83): the lights of one kind that share a texture, quality
+// settings and blend functions, drawn with one native call
+struct LightRenderState {
+    const RampTexture* texture;                  // the ramp bound for the call, null: none; of a projector state: the projected texture
+    const RendererQualitySettings* quality;      // null => Configuration.DefaultQuality
+    std::pair<int, int> blend;                   // (BlendColorFunction, BlendAlphaFunction)
+    std::vector<IlmLightVertex> vertices;        // LightTypeRenderState.LightVertices
+};
+
 // LightingRenderer.cs (RenderLighting path only)
 class LightingRenderer {
 public:
@@ -1093,31 +1108,9 @@ private:
     int lightmapFormat = ILM_LIGHTMAP_HALF4;
     int gbufferWidth = 0, gbufferHeight = 0;
     std::vector<IlmLightVertex> vertices;
-    // the light groups of the last RenderLighting (one per ramp texture) and the ramp currently bound on the context
-    std::vector<const RampTexture*> groupKeys;
-    std::vector<const RendererQualitySettings*> groupQuality;     // null => Configuration.DefaultQuality
-    std::vector<std::pair<int, int>> groupBlend;        // (BlendColorFunction, BlendAlphaFunction) of the group: the third member of its key
-    std::vector<std::vector<IlmLightVertex>> groups;
-    // the directional groups of the last RenderLighting, drawn after the sphere groups (same keys: ramp texture, quality)
-    std::vector<const RampTexture*> directionalKeys;
-    std::vector<const RendererQualitySettings*> directionalQuality;
-    std::vector<std::pair<int, int>> directionalBlend;
-    std::vector<std::vector<IlmLightVertex>> directionalGroups;
-    // the line groups, drawn after the directional ones (LightSourceTypeID.Line = 4 sorts between Directional = 2 and Projector = 5)
-    std::vector<const RampTexture*> lineKeys;
-    std::vector<const RendererQualitySettings*> lineQuality;
-    std::vector<std::pair<int, int>> lineBlend;
-    std::vector<std::vector<IlmLightVertex>> lineGroups;
-    // the projector groups, drawn after the line ones: one per (texture, quality), the texture bound per group
-    std::vector<const RampTexture*> projectorKeys;
-    std::vector<const RendererQualitySettings*> projectorQuality;
-    std::vector<std::pair<int, int>> projectorBlend;
-    std::vector<std::vector<IlmLightVertex>> projectorGroups;
-    // the volumetric groups, drawn last (LightSourceTypeID.Volumetric = 6 sorts after Projector = 5): one per (ramp texture, quality)
-    std::vector<const RampTexture*> volumetricKeys;
-    std::vector<const RendererQualitySettings*> volumetricQuality;
-    std::vector<std::pair<int, int>> volumetricBlend;
-    std::vector<std::vector<IlmLightVertex>> volumetricGroups;
+    // the render states of the last RenderLighting by light kind, each kind's in the order their keys first appeared, and the ramp
+    // currently bound on the context
+    std::array<std::vector<LightRenderState>, (size_t)LightKind::Count> renderStates;
     const RampTexture* boundRamp = nullptr;
     std::pair<int, int> boundBlend{ ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD };      // what the context's light blend functions are set to
     void BindBlend(std::pair<int, int> functions);
