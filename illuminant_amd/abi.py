@@ -312,6 +312,14 @@ class HDRConfiguration(C.Structure):
                 ("ResolveToSRGB", i32), ("DitheringStrength", i32), ("AlbedoIsSRGB", i32)]
 
 
+class LUTBlending(C.Structure):
+    """LUTBlendingConfiguration (LightingRenderer.HDR.cs:260-273) as SetLUTBlending binds it (IlluminantMaterials.cs:139-147); the LUT
+    textures are lightmap objects of width N * N and height N * RowCount.  60 bytes of fields, 64 with C's tail padding."""
+    _fields_ = [("DarkLUT", Handle), ("BrightLUT", Handle), ("DarkResolution", i32), ("BrightResolution", i32),
+                ("DarkRowCount", i32), ("BrightRowCount", i32), ("DarkRow", i32), ("BrightRow", i32),
+                ("DarkLevel", f32), ("NeutralBandSize", f32), ("BrightLevel", f32), ("PerChannel", i32), ("LUTOnly", i32)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [("SdfSamples", C.c_uint64), ("PixelLightPairs", C.c_uint64), ("TracedPairs", C.c_uint64)]
 
@@ -368,4 +376,5 @@ EXPECTED_SIZES = {
     "IlmBillboardRun": (BillboardRun, 24), "IlmGBufferMeshDesc": (GBufferMeshDesc, 64),
     "IlmHistogramBucket": (HistogramBucket, 16), "IlmHistogramParams": (HistogramParams, 24), "IlmHistogramResult": (HistogramResult, 36),
     "IlmVisualizeVertex": (VisualizeVertex, 52), "IlmVisualizeParams": (VisualizeParams, 80),
+    "IlmLUTBlending": (LUTBlending, 64),
 }

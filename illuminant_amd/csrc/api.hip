@@ -3676,17 +3676,14 @@ int32_t ilm_resolve_lighting_with_albedo(IlmHandle hsrc, IlmHandle halbedo, IlmH
     return ILM_OK;
 }
 
-int32_t ilm_resolve_lighting_scaled(IlmHandle hsrc, IlmHandle halbedo, IlmHandle hdst, const IlmHDRConfiguration* hdr, const float quad[4],
-                                    const float lightmap_region[4], const float albedo_region[4], const float uv_offset[2],
-                                    int32_t lightmap_filter, int32_t albedo_filter, int32_t row_begin, int32_t row_end) {
-    ILM_TRACE_RANGE("ilm_resolve_lighting_scaled");
-    Lightmap* src = from_handle<Lightmap>(hsrc, kMagicLightmap);
-    Lightmap* dst = from_handle<Lightmap>(hdst, kMagicLightmap);
-    if (!src || !dst) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
-    Lightmap* albedo = nullptr;
-    if (halbedo) {
-        albedo = from_handle<Lightmap>(halbedo, kMagicLightmap);
-        if (!albedo) return fail(ILM_ERR_INVALID_HANDLE, "albedo is not a texture (lightmap) handle");
+namespace {
+// What ilm_resolve_lighting_scaled and ilm_resolve_lighting_lut share once their handles are looked up: the refusals of the scaled
+// resolve's contract in its order, the pixel ranges and the launch descriptor.  *empty: the call succeeds and writes nothing.
+int32_t plan_scaled_resolve(const Lightmap* src, const Lightmap* albedo, const Lightmap* dst, const IlmHDRConfiguration* hdr, const float quad[4],
+                            const float lightmap_region[4], const float albedo_region[4], const float uv_offset[2],
+                            int32_t lightmap_filter, int32_t albedo_filter, int32_t row_begin, int32_t row_end, ResolveScaledLaunch& a, bool* empty) {
+    *empty = false;
+    if (albedo) {
         if (albedo->ctx != src->ctx) return fail(ILM_ERR_INVALID_ARGUMENT, "the albedo texture must share its context with the lightmap");
         if (hdr && hdr->AlbedoIsSRGB != 0)
             return fail(ILM_ERR_INVALID_ARGUMENT, "AlbedoIsSRGB needs Fracture's pSRGBToPLinear (sRGBCommon.fxh), which is outside the reference tree");
@@ -3724,10 +3721,9 @@ int32_t ilm_resolve_lighting_scaled(IlmHandle hsrc, IlmHandle halbedo, IlmHandle
     // the pixels whose centre the quad contains: i + 0.5 >= p  <=>  i >= ceil(p - 0.5), i + 0.5 < q  <=>  i < ceil(q - 0.5), exact in
     // double for float arguments; clamped to the target (and the rows) BEFORE the conversion to int
     auto edge = [](double p, int lo, int hi) { return (int)std::min(std::max(std::ceil(p - 0.5), (double)lo), (double)hi); };
-    ResolveScaledLaunch a;
     a.x0 = edge((double)quad[0], 0, dst->width);         a.x1 = edge((double)quad[0] + (double)quad[2], 0, dst->width);
     a.y0 = edge((double)quad[1], row_begin, row_end);    a.y1 = edge((double)quad[1] + (double)quad[3], row_begin, row_end);
-    if (a.x0 >= a.x1 || a.y0 >= a.y1) return ILM_OK;             // an empty quad, or one that misses the target or the rows
+    if (a.x0 >= a.x1 || a.y0 >= a.y1) { *empty = true; return ILM_OK; }      // an empty quad, or one that misses the target or the rows
     if (a.y1 - a.y0 > 65535) return fail(ILM_ERR_OUT_OF_RANGE, "more than 65535 destination rows in one call");
     a.r.src = src->texels; a.r.src_format = src->format; a.r.dst = dst->texels; a.r.dst_format = dst->format;
     a.r.albedo = albedo ? albedo->texels : nullptr; a.r.albedo_format = albedo ? albedo->format : 0;
@@ -3742,9 +3738,92 @@ int32_t ilm_resolve_lighting_scaled(IlmHandle hsrc, IlmHandle halbedo, IlmHandle
     }
     a.uv_offset[0] = uv_offset ? uv_offset[0] : 0.0f; a.uv_offset[1] = uv_offset ? uv_offset[1] : 0.0f;
     a.lightmap_filter = lightmap_filter; a.albedo_filter = albedo_filter;
+    return ILM_OK;
+}
+}  // namespace
+
+int32_t ilm_resolve_lighting_scaled(IlmHandle hsrc, IlmHandle halbedo, IlmHandle hdst, const IlmHDRConfiguration* hdr, const float quad[4],
+                                    const float lightmap_region[4], const float albedo_region[4], const float uv_offset[2],
+                                    int32_t lightmap_filter, int32_t albedo_filter, int32_t row_begin, int32_t row_end) {
+    ILM_TRACE_RANGE("ilm_resolve_lighting_scaled");
+    Lightmap* src = from_handle<Lightmap>(hsrc, kMagicLightmap);
+    Lightmap* dst = from_handle<Lightmap>(hdst, kMagicLightmap);
+    if (!src || !dst) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
+    Lightmap* albedo = nullptr;
+    if (halbedo) {
+        albedo = from_handle<Lightmap>(halbedo, kMagicLightmap);
+        if (!albedo) return fail(ILM_ERR_INVALID_HANDLE, "albedo is not a texture (lightmap) handle");
+    }
+    ResolveScaledLaunch a;
+    bool empty;
+    { const int32_t rc = plan_scaled_resolve(src, albedo, dst, hdr, quad, lightmap_region, albedo_region, uv_offset, lightmap_filter, albedo_filter,
+                                             row_begin, row_end, a, &empty); if (rc != ILM_OK) return rc; }
+    if (empty) return ILM_OK;
     Ctx* c = src->ctx;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_resolve_scaled(a, c->main()));
+    return ILM_OK;
+}
+
+namespace {
+// LUTBlendedResolveWithAlbedoCommon's uniform arithmetic (LUTResolve.fx:78-81,94,100-103) in fp32 in the shader's order, and the two
+// divisors as reciprocals (the header says so)
+void lut_uniforms(ResolveLutLaunch& a, const IlmLUTBlending* lut) {
+    const float band_width = fminf(fmaxf(lut->BrightLevel - lut->DarkLevel, 0.0f), 1.0f);
+    a.neutral = fminf(lut->NeutralBandSize, band_width - 0.01f);
+    a.has_band = a.neutral > 0.0f;
+    a.normalize = (lut->PerChannel == 0) || a.has_band;
+    a.transition = (band_width - a.neutral) * 0.5f;
+    a.inv_transition = 1.0f / a.transition;
+    a.ramp = lut->BrightLevel > lut->DarkLevel;
+    a.inv_range = 1.0f / (lut->BrightLevel - lut->DarkLevel);
+    a.dark_level = lut->DarkLevel;
+    a.lut_only = lut->LUTOnly != 0;
+}
+
+int32_t lut_texture(ResolveLutTexture& t, const Lightmap* m, const char* which, int32_t resolution, int32_t row_count, int32_t row) {
+    if (resolution < 2 || row_count < 1)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "%s LUT: resolution %d (< 2) or row count %d (< 1)", which, resolution, row_count);
+    if ((int64_t)m->width != (int64_t)resolution * resolution || (int64_t)m->height != (int64_t)resolution * row_count)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "%s LUT: a %d x %d texture is not resolution^2 x resolution * rows = %lld x %lld", which, m->width, m->height,
+                    (long long)resolution * resolution, (long long)resolution * row_count);
+    if (row < 0 || row >= row_count) return fail(ILM_ERR_INVALID_ARGUMENT, "%s LUT: row %d outside [0, %d)", which, row, row_count);
+    t.texels = m->texels; t.format = m->format; t.n = resolution; t.pitch = m->width; t.row0 = row * resolution;
+    return ILM_OK;
+}
+}  // namespace
+
+int32_t ilm_resolve_lighting_lut(IlmHandle hsrc, IlmHandle halbedo, IlmHandle hdst, const IlmHDRConfiguration* hdr, const IlmLUTBlending* lut,
+                                 const float quad[4], const float lightmap_region[4], const float albedo_region[4], const float uv_offset[2],
+                                 int32_t lightmap_filter, int32_t albedo_filter, int32_t row_begin, int32_t row_end) {
+    ILM_TRACE_RANGE("ilm_resolve_lighting_lut");
+    Lightmap* src = from_handle<Lightmap>(hsrc, kMagicLightmap);
+    Lightmap* dst = from_handle<Lightmap>(hdst, kMagicLightmap);
+    if (!src || !dst) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
+    if (!halbedo) return fail(ILM_ERR_INVALID_ARGUMENT, "the LUT-blended technique exists only with albedo (LightingRenderer.cs:1569-1586): albedo is 0");
+    Lightmap* albedo = from_handle<Lightmap>(halbedo, kMagicLightmap);
+    if (!albedo) return fail(ILM_ERR_INVALID_HANDLE, "albedo is not a texture (lightmap) handle");
+    if (!hdr) return fail(ILM_ERR_INVALID_ARGUMENT, "hdr is NULL");
+    if (!lut) return fail(ILM_ERR_INVALID_ARGUMENT, "lut is NULL");
+    Lightmap* dark = from_handle<Lightmap>(lut->DarkLUT, kMagicLightmap);
+    Lightmap* bright = from_handle<Lightmap>(lut->BrightLUT, kMagicLightmap);
+    if (!dark || !bright) return fail(ILM_ERR_INVALID_HANDLE, "DarkLUT or BrightLUT is not a texture (lightmap) handle");
+    if (dark->ctx != src->ctx || bright->ctx != src->ctx) return fail(ILM_ERR_INVALID_ARGUMENT, "the LUT textures must share their context with the lightmap");
+    if (hdr->Mode != ILM_HDR_NONE)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "LUT blending is not compatible with this type of lighting resolve (HDR mode %d; LightingRenderer.cs:1589-1590)", hdr->Mode);
+    ResolveLutLaunch a;
+    { const int32_t rc = lut_texture(a.dark, dark, "dark", lut->DarkResolution, lut->DarkRowCount, lut->DarkRow); if (rc != ILM_OK) return rc; }
+    { const int32_t rc = lut_texture(a.bright, bright, "bright", lut->BrightResolution, lut->BrightRowCount, lut->BrightRow); if (rc != ILM_OK) return rc; }
+    if (!std::isfinite(lut->DarkLevel) || !std::isfinite(lut->NeutralBandSize) || !std::isfinite(lut->BrightLevel))
+        return fail(ILM_ERR_INVALID_ARGUMENT, "LUT levels (%g, %g, %g) are not finite", (double)lut->DarkLevel, (double)lut->NeutralBandSize, (double)lut->BrightLevel);
+    bool empty;
+    { const int32_t rc = plan_scaled_resolve(src, albedo, dst, hdr, quad, lightmap_region, albedo_region, uv_offset, lightmap_filter, albedo_filter,
+                                             row_begin, row_end, a.s, &empty); if (rc != ILM_OK) return rc; }
+    if (empty) return ILM_OK;
+    lut_uniforms(a, lut);
+    Ctx* c = src->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_resolve_lut(a, c->main()));
     return ILM_OK;
 }
 

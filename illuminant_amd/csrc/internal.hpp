@@ -421,6 +421,27 @@ struct ResolveScaledLaunch {
 };
 hipError_t launch_resolve_scaled(const ResolveScaledLaunch& a, hipStream_t stream);
 
+// ilm_resolve_lighting_lut: the fetch and the coverage are ResolveScaledLaunch's (s.r.albedo is never NULL, s.r.mode is ILM_HDR_NONE: the
+// epilogue of resolve_texel's plain branch), the arithmetic between them is the header's.  Every decision that does not depend on the
+// pixel is taken on the host and arrives here: band or not, luminance or per-channel weight, which of the two non-band branches.
+struct ResolveLutTexture {
+    const void* texels; int32_t format;
+    int32_t n;                          // Resolution: n slices of n x n texels side by side
+    int32_t pitch;                      // texels per texture row: n * n
+    int32_t row0;                       // Row * n: the first texel row of the LUT row that is read
+};
+struct ResolveLutLaunch {
+    ResolveScaledLaunch s;
+    ResolveLutTexture dark, bright;
+    int32_t has_band, normalize, ramp, lut_only;     // ramp: BrightLevel > DarkLevel (else the shader's HACK branch)
+    float dark_level;
+    float neutral;                      // fminf(NeutralBandSize, bandWidth - 0.01f); read with has_band
+    float transition;                   // (bandWidth - neutral) * 0.5f; read with has_band
+    float inv_transition;               // 1.0f / transition
+    float inv_range;                    // 1.0f / (BrightLevel - DarkLevel); read with ramp
+};
+hipError_t launch_resolve_lut(const ResolveLutLaunch& a, hipStream_t stream);
+
 // ---- brightness estimation (brightness.hip) ---------------------------------------------------------------------
 struct LuminanceLaunch {
     const void* texels; int32_t format, pitch;      // the lightmap, pitch in texels

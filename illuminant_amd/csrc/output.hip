@@ -355,6 +355,101 @@ hipError_t launch_resolve_scaled(const ResolveScaledLaunch& a, hipStream_t strea
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// LUT-blended resolve (ilm_resolve_lighting_lut): LUTBlendedResolveWithAlbedoCommon, Illuminant/Shaders/LUTResolve.fx:61-115
+// ---------------------------------------------------------------------------------------------
+// One channel of ReadLUT's lattice fetch as the header defines it: a is saturated (a NaN became 0), so s lies in [0, n - 1], the conversion
+// is exact and both indices are inside the slice / the LUT row by integer arithmetic.
+ILM_DEV AxisTaps lut_axis(float a, int n) {
+    const float s = a * (float)(n - 1), fl = floorf(s);
+    AxisTaps t;
+    t.f = s - fl;
+    t.i0 = min((int)fl, n - 1);
+    t.i1 = min(t.i0 + 1, n - 1);
+    return t;
+}
+
+// The eight lattice points round one colour, t[ri + 2 gi + 4 bi]: column bi * n + ri, texel row row0 + gi.
+struct LutTaps { float4 t[8]; };
+
+ILM_DEV LutTaps load_lut(const ResolveLutTexture& l, const AxisTaps& r, const AxisTaps& g, const AxisTaps& b) {
+    const size_t g0 = (size_t)(l.row0 + g.i0) * (size_t)l.pitch, g1 = (size_t)(l.row0 + g.i1) * (size_t)l.pitch;
+    const size_t c00 = (size_t)(b.i0 * l.n + r.i0), c10 = (size_t)(b.i0 * l.n + r.i1);
+    const size_t c01 = (size_t)(b.i1 * l.n + r.i0), c11 = (size_t)(b.i1 * l.n + r.i1);
+    LutTaps v;
+    v.t[0] = load_tap(l.texels, l.format, g0 + c00); v.t[1] = load_tap(l.texels, l.format, g0 + c10);
+    v.t[2] = load_tap(l.texels, l.format, g1 + c00); v.t[3] = load_tap(l.texels, l.format, g1 + c10);
+    v.t[4] = load_tap(l.texels, l.format, g0 + c01); v.t[5] = load_tap(l.texels, l.format, g0 + c11);
+    v.t[6] = load_tap(l.texels, l.format, g1 + c01); v.t[7] = load_tap(l.texels, l.format, g1 + c11);
+    return v;
+}
+
+ILM_DEV f3 blend_lut(const LutTaps& v, float fr, float fg, float fb) {
+    return xyz(lerp4(lerp4(lerp4(v.t[0], v.t[1], fr), lerp4(v.t[2], v.t[3], fr), fg),
+                     lerp4(lerp4(v.t[4], v.t[5], fr), lerp4(v.t[6], v.t[7], fr), fg), fb));
+}
+
+// The shape of resolve_scaled_kernel (a span of one row per block, the row's taps wave-uniform), a kernel of its own so that that one keeps
+// its instruction stream.  Per pixel: four lightmap taps and four albedo taps, then -- once the albedo is known -- the sixteen LUT taps,
+// all issued before the first of their lerps; the light's filter and the weight are computed while they are in flight.  The two LUTs (19.6 KB
+// each at 17^3 RGBA8) are read through the caches: every wave of the frame reads the same few kilobytes.  Band, normalize, ramp, LUTOnly
+// and the formats are launch-uniform branches.  docs/experiments.md ("LUT-blended resolve") has the registers and the measurement.
+__global__ __launch_bounds__(kScaledBlock, 4) void resolve_lut_kernel(const ResolveLutLaunch a) {
+    const ResolveScaledLaunch& s = a.s;
+    const ResolveLaunch& r = s.r;
+    const int py = s.y0 + (int)blockIdx.y;
+    const int span_begin = s.x0 + (int)blockIdx.x * kScaledSpan;
+    const int span_end = min(span_begin + kScaledSpan, s.x1);
+    AxisTaps ly = scaled_axis(py, s.quad[1], s.quad[3], s.lightmap_region[1], s.lightmap_region[3], &s.uv_offset[1], s.src_h, s.lightmap_filter);
+    ly.i0 = __builtin_amdgcn_readfirstlane(ly.i0); ly.i1 = __builtin_amdgcn_readfirstlane(ly.i1);
+    AxisTaps ay = scaled_axis(py, s.quad[1], s.quad[3], s.albedo_region[1], s.albedo_region[3], nullptr, s.albedo_h, s.albedo_filter);
+    ay.i0 = __builtin_amdgcn_readfirstlane(ay.i0); ay.i1 = __builtin_amdgcn_readfirstlane(ay.i1);
+    const size_t dst_row = (size_t)py * (size_t)r.width;
+    const float k = r.inverse_scale * 2.0f;
+    const float e = r.exposure_minus_one + 1.0f, gm = r.gamma_minus_one + 1.0f;
+    for (int px = span_begin + (int)threadIdx.x; px < span_end; px += kScaledBlock) {
+        const AxisTaps lx = scaled_axis(px, s.quad[0], s.quad[2], s.lightmap_region[0], s.lightmap_region[2], &s.uv_offset[0], s.src_w, s.lightmap_filter);
+        const TexelTaps lt = load_taps(r.src, r.src_format, s.src_w, s.lightmap_filter, lx, ly);
+        const AxisTaps ax = scaled_axis(px, s.quad[0], s.quad[2], s.albedo_region[0], s.albedo_region[2], nullptr, s.albedo_w, s.albedo_filter);
+        const TexelTaps at = load_taps(r.albedo, r.albedo_format, s.albedo_w, s.albedo_filter, ax, ay);
+        const float4 albedo = filter_taps(at, s.albedo_filter, ax.f, ay.f);
+        const f3 c = mk3(sat(albedo.x), sat(albedo.y), sat(albedo.z));             // saturate3(albedo.rgb), :87
+        const AxisTaps dr = lut_axis(c.x, a.dark.n), dg = lut_axis(c.y, a.dark.n), db = lut_axis(c.z, a.dark.n);
+        const AxisTaps br = lut_axis(c.x, a.bright.n), bg = lut_axis(c.y, a.bright.n), bb = lut_axis(c.z, a.bright.n);
+        const LutTaps dt = load_lut(a.dark, dr, dg, db), bt = load_lut(a.bright, br, bg, bb);
+        const float4 tap = filter_taps(lt, s.lightmap_filter, lx.f, ly.f);
+        const f3 light = mk3(tap.x * k, tap.y * k, tap.z * k);                      // light *= InverseScaleFactor * 2, :75
+        f3 w = light;
+        if (a.normalize) w.x = w.y = w.z = (light.x * 0.299f + light.y * 0.587f) + light.z * 0.144f;     // RgbToGray, :16,82-85
+        const f3 dark = blend_lut(dt, dr.f, dg.f, db.f), bright = blend_lut(bt, br.f, bg.f, bb.f);
+        f3 blended;
+        if (a.has_band) {
+            // :93-98
+            const float v = w.x - a.dark_level, v3 = (v - a.transition) - a.neutral;
+            const float t1 = sat(v * a.inv_transition), t2 = sat(v3 * a.inv_transition);
+            blended = mk3(lerp(lerp(dark.x, c.x, t1), bright.x, t2), lerp(lerp(dark.y, c.y, t1), bright.y, t2), lerp(lerp(dark.z, c.z, t1), bright.z, t2));
+        } else {
+            // :100-110
+            if (a.ramp) w = mk3(sat(fmaxf(0.0f, w.x - a.dark_level) * a.inv_range), sat(fmaxf(0.0f, w.y - a.dark_level) * a.inv_range),
+                                sat(fmaxf(0.0f, w.z - a.dark_level) * a.inv_range));
+            else        w = mk3(sat(w.x - a.dark_level), sat(w.y - a.dark_level), sat(w.z - a.dark_level));
+            blended = mk3(lerp(dark.x, bright.x, w.x), lerp(dark.y, bright.y, w.y), lerp(dark.z, bright.z, w.z));
+        }
+        if (!a.lut_only) blended = mk3(blended.x * light.x, blended.y * light.y, blended.z * light.z);     // :113
+        // LUTBlendedLightingResolveWithAlbedoPixelShader, :129-131: resolve_texel's plain epilogue
+        const float4 out = mk4(pow_pos(fmaxf(0.0f, blended.x + r.offset) * e, gm), pow_pos(fmaxf(0.0f, blended.y + r.offset) * e, gm),
+                               pow_pos(fmaxf(0.0f, blended.z + r.offset) * e, gm), albedo.w);
+        store_lightmap_texel(r.dst, r.dst_format, dst_row + (size_t)px, out);
+    }
+}
+
+hipError_t launch_resolve_lut(const ResolveLutLaunch& a, hipStream_t stream) {
+    if (a.s.x0 >= a.s.x1 || a.s.y0 >= a.s.y1) return hipSuccess;
+    const dim3 grid((unsigned)((a.s.x1 - a.s.x0 + kScaledSpan - 1) / kScaledSpan), (unsigned)(a.s.y1 - a.s.y0));
+    hipLaunchKernelGGL(resolve_lut_kernel, grid, dim3(kScaledBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
 // Sixteen bytes written by the DEVICE at `where` (group.hip, prove_ipc_mappings: the proof goes through the same kind of access the
 // store mode's mirror stores use -- a kernel's store through the mapping -- not through a copy engine).
 __global__ void stamp16_kernel(uint4* where, uint4 stamp) { *where = stamp; }

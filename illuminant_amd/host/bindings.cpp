@@ -23,8 +23,10 @@ using farray = py::array_t<float, py::array::c_style | py::array::forcecast>;
 static Vector2 v2(const std::vector<float>& v) { return Vector2{ v.at(0), v.at(1) }; }
 // the optional arguments of ResolveTo / ResolveAt as Python passes them; `hdr` is where the configuration's bytes are kept
 static ResolveOptions resolve_options(py::object albedo, py::object albedoTextureRegion, int albedoSamplerState, int lightmapSamplerState,
-                                      const std::vector<float>& uvOffset, py::object hdrBytes, int rowBegin, int rowEnd, IlmHDRConfiguration& hdr) {
+                                      const std::vector<float>& uvOffset, py::object hdrBytes, py::object lutBlending, int rowBegin, int rowEnd,
+                                      IlmHDRConfiguration& hdr) {
     ResolveOptions o;
+    if (!lutBlending.is_none()) o.LUTBlending = lutBlending.cast<LUTBlendingConfiguration>();
     if (!albedo.is_none()) {
         const auto a = albedo.cast<std::tuple<IlmHandle, int, int>>();
         o.Albedo = ResolveTexture{ std::get<0>(a), std::get<1>(a), std::get<2>(a) };
@@ -655,6 +657,16 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("Failed", &VisualizationInfo::Failed)
         VEC_PROP(VisualizationInfo, ViewCenter, 3) VEC_PROP(VisualizationInfo, Up, 3) VEC_PROP(VisualizationInfo, Right, 3)
         VEC_PROP(VisualizationInfo, ViewDirection, 3);
+    // ColorLUT.Texture: (handle, width, height), as the other textures of the resolve
+    py::class_<ColorLUT>(m, "ColorLUT").def(py::init<>())
+        .def_property("Texture", [](const ColorLUT& l) { return std::make_tuple(l.Texture.Handle, l.Texture.Width, l.Texture.Height); },
+                      [](ColorLUT& l, const std::tuple<IlmHandle, int, int>& t) { l.Texture = ResolveTexture{ std::get<0>(t), std::get<1>(t), std::get<2>(t) }; })
+        .def_readwrite("Resolution", &ColorLUT::Resolution).def_readwrite("RowCount", &ColorLUT::RowCount);
+    py::class_<LUTBlendingConfiguration>(m, "LUTBlendingConfiguration").def(py::init<>())
+        .def_readwrite("DarkLUT", &LUTBlendingConfiguration::DarkLUT).def_readwrite("BrightLUT", &LUTBlendingConfiguration::BrightLUT)
+        .def_readwrite("PerChannel", &LUTBlendingConfiguration::PerChannel).def_readwrite("LUTOnly", &LUTBlendingConfiguration::LUTOnly)
+        .def_readwrite("DarkLevel", &LUTBlendingConfiguration::DarkLevel).def_readwrite("NeutralBandSize", &LUTBlendingConfiguration::NeutralBandSize)
+        .def_readwrite("BrightLevel", &LUTBlendingConfiguration::BrightLevel);
     py::class_<LightingRenderer>(m, "LightingRenderer")
         .def(py::init([](DeviceContext& ctx, const RendererConfiguration& cfg, LightingEnvironment* env, uintptr_t externalLightmap) {
             return new LightingRenderer(ctx, cfg, env, reinterpret_cast<void*>(externalLightmap));
@@ -723,23 +735,25 @@ PYBIND11_MODULE(_host, m) {
         // destination and albedo: (handle, width, height); albedoTextureRegion: (u0, v0, u1, v1); uvOffset in UV, as the reference's
         .def("ResolveTo", [](const LightingRenderer& r, const std::tuple<IlmHandle, int, int>& destination, float width, float height, py::object albedo,
                              py::object albedoTextureRegion, int albedoSamplerState, int lightmapSamplerState, const std::vector<float>& uvOffset,
-                             py::object hdrBytes, int rowBegin, int rowEnd) {
+                             py::object hdrBytes, int rowBegin, int rowEnd, py::object lutBlending) {
             IlmHDRConfiguration h;
-            const ResolveOptions o = resolve_options(albedo, albedoTextureRegion, albedoSamplerState, lightmapSamplerState, uvOffset, hdrBytes, rowBegin, rowEnd, h);
+            const ResolveOptions o = resolve_options(albedo, albedoTextureRegion, albedoSamplerState, lightmapSamplerState, uvOffset, hdrBytes, lutBlending, rowBegin, rowEnd, h);
             r.ResolveTo(ResolveTexture{ std::get<0>(destination), std::get<1>(destination), std::get<2>(destination) }, width, height, o);
         }, py::arg("destination"), py::arg("width"), py::arg("height"), py::arg("albedo") = py::none(), py::arg("albedoTextureRegion") = py::none(),
            py::arg("albedoSamplerState") = (int)ILM_FILTER_LINEAR, py::arg("lightmapSamplerState") = (int)ILM_FILTER_LINEAR,
-           py::arg("uvOffset") = std::vector<float>{0, 0}, py::arg("hdr") = py::none(), py::arg("rowBegin") = 0, py::arg("rowEnd") = -1)
+           py::arg("uvOffset") = std::vector<float>{0, 0}, py::arg("hdr") = py::none(), py::arg("rowBegin") = 0, py::arg("rowEnd") = -1,
+           py::arg("lutBlending") = py::none())
         .def("ResolveAt", [](const LightingRenderer& r, const std::tuple<IlmHandle, int, int>& destination, const std::vector<float>& position,
                              const std::vector<float>& scale, py::object albedo, py::object albedoTextureRegion, int albedoSamplerState,
-                             int lightmapSamplerState, const std::vector<float>& uvOffset, py::object hdrBytes, int rowBegin, int rowEnd) {
+                             int lightmapSamplerState, const std::vector<float>& uvOffset, py::object hdrBytes, int rowBegin, int rowEnd,
+                             py::object lutBlending) {
             IlmHDRConfiguration h;
-            const ResolveOptions o = resolve_options(albedo, albedoTextureRegion, albedoSamplerState, lightmapSamplerState, uvOffset, hdrBytes, rowBegin, rowEnd, h);
+            const ResolveOptions o = resolve_options(albedo, albedoTextureRegion, albedoSamplerState, lightmapSamplerState, uvOffset, hdrBytes, lutBlending, rowBegin, rowEnd, h);
             r.ResolveAt(ResolveTexture{ std::get<0>(destination), std::get<1>(destination), std::get<2>(destination) }, v2(position), v2(scale), o);
         }, py::arg("destination"), py::arg("position"), py::arg("scale") = std::vector<float>{1, 1}, py::arg("albedo") = py::none(),
            py::arg("albedoTextureRegion") = py::none(), py::arg("albedoSamplerState") = (int)ILM_FILTER_LINEAR,
            py::arg("lightmapSamplerState") = (int)ILM_FILTER_LINEAR, py::arg("uvOffset") = std::vector<float>{0, 0}, py::arg("hdr") = py::none(),
-           py::arg("rowBegin") = 0, py::arg("rowEnd") = -1)
+           py::arg("rowBegin") = 0, py::arg("rowEnd") = -1, py::arg("lutBlending") = py::none())
         .def_property_readonly("Probes", [](LightingRenderer& r) -> LightProbeCollection& { return r.Probes; }, py::return_value_policy::reference_internal)
         .def_static("PackParticleLightBytes", [](const ParticleLightSource& pls, bool haveDF) {
             auto p = LightingRenderer::PackParticleLight(pls, haveDF); return py::bytes((const char*)&p, sizeof(p)); })

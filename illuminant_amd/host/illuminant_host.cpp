@@ -2176,8 +2176,14 @@ void LightingRenderer::ResolveQuad(Vector2 position, Vector2 scale, const Resolv
     }
 }
 
-// ResolveLighting, LightingRenderer.cs:1537-1645 (screen space, no LUT, the material's own blend state)
+// ResolveLighting, LightingRenderer.cs:1537-1645 (screen space, the material's own blend state)
 void LightingRenderer::ResolveLighting(const ResolveTexture& destination, Vector2 position, Vector2 scale, const ResolveOptions& options) const {
+    // the technique, :1545-1590: with albedo, GammaCompress and ToneMap come before the LUT and then refuse it; without albedo it is ignored
+    const bool haveAlbedo = options.Albedo.Handle != 0;
+    const bool gc = options.HDR && options.HDR->Mode == ILM_HDR_GAMMA_COMPRESS, tm = options.HDR && options.HDR->Mode == ILM_HDR_TONE_MAP;
+    const bool usedLut = haveAlbedo && !gc && !tm && options.LUTBlending.has_value();
+    if (options.LUTBlending.has_value() && !usedLut && haveAlbedo)
+        throw ArgumentException("LUT blending is not compatible with this type of lighting resolve.");
     IlmHDRConfiguration plain;
     const IlmHDRConfiguration* hdr = options.HDR;
     if (!hdr) {      // hdr == null: as Resolve above
@@ -2198,6 +2204,20 @@ void LightingRenderer::ResolveLighting(const ResolveTexture& destination, Vector
     ResolveQuad(position, scale, options, quad);
     const float uvOffset[2] = { options.UVOffset.X * w, options.UVOffset.Y * h };       // the reference's is in UV: texels here
     const int rowEnd = options.RowEnd < 0 ? destination.Height : options.RowEnd;
+    if (usedLut) {
+        // SetLUTBlending, IlluminantMaterials.cs:139-147 (LUTOffsets is never set: row 0 of both textures)
+        const LUTBlendingConfiguration& c = *options.LUTBlending;
+        IlmLUTBlending lut;
+        std::memset(&lut, 0, sizeof(lut));
+        lut.DarkLUT = c.DarkLUT.Texture.Handle; lut.BrightLUT = c.BrightLUT.Texture.Handle;
+        lut.DarkResolution = c.DarkLUT.Resolution; lut.BrightResolution = c.BrightLUT.Resolution;
+        lut.DarkRowCount = c.DarkLUT.RowCount; lut.BrightRowCount = c.BrightLUT.RowCount;
+        lut.DarkLevel = c.DarkLevel; lut.NeutralBandSize = c.NeutralBandSize; lut.BrightLevel = c.BrightLevel;
+        lut.PerChannel = c.PerChannel ? 1 : 0; lut.LUTOnly = c.LUTOnly ? 1 : 0;
+        ThrowIfFailed(ilm_resolve_lighting_lut(lightmap, options.Albedo.Handle, destination.Handle, hdr, &lut, quad, lightmapRegion, albedoRegion, uvOffset,
+                                               options.LightmapSamplerState, options.AlbedoSamplerState, options.RowBegin, rowEnd));
+        return;
+    }
     ThrowIfFailed(ilm_resolve_lighting_scaled(lightmap, options.Albedo.Handle, destination.Handle, hdr, quad, lightmapRegion, albedoRegion, uvOffset,
                                               options.LightmapSamplerState, options.AlbedoSamplerState, options.RowBegin, rowEnd));
 }

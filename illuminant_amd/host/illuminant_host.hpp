@@ -986,8 +986,22 @@ struct ResolveTexture {
     IlmHandle Handle = 0;
     int Width = 0, Height = 0;
 };
+// Fracture's ColorLUT as SetLUTBlending reads it (IlluminantMaterials.cs:141-143): a texture of width Resolution^2 and height
+// Resolution * RowCount (ilm_resolve_lighting_lut defines the layout)
+struct ColorLUT {
+    ResolveTexture Texture;
+    int Resolution = 0;
+    int RowCount = 1;
+};
+// LUTBlendingConfiguration, LightingRenderer.HDR.cs:260-273 (BrightLevel is kept minus one there, so that default(...) means 1)
+struct LUTBlendingConfiguration {
+    ColorLUT DarkLUT, BrightLUT;
+    bool PerChannel = false, LUTOnly = false;
+    float DarkLevel = 0, NeutralBandSize = 0;
+    float BrightLevel = 1;
+};
 // The optional arguments of RenderedLighting.Resolve, LightingRenderer.HDR.cs:101-105, with the reference's defaults.  Not carried:
-// lutBlending, blendState and worldSpace (ilm_resolve_lighting_scaled says why).
+// blendState and worldSpace (ilm_resolve_lighting_scaled says why).
 struct ResolveOptions {
     ResolveTexture Albedo;                              // albedo = null
     std::optional<Bounds> AlbedoTextureRegion;          // in UV; albedoRegion.GetValueOrDefault(Bounds.Unit), LightingRenderer.cs:1601
@@ -995,6 +1009,7 @@ struct ResolveOptions {
     int LightmapSamplerState = ILM_FILTER_LINEAR;       // lightmapSamplerState ?? SamplerState.LinearClamp, :1622
     Vector2 UVOffset{0, 0};                             // in UV of the lightmap, as the reference's
     const IlmHDRConfiguration* HDR = nullptr;           // null: the plain LightingResolve with exposure / gamma 1
+    std::optional<LUTBlendingConfiguration> LUTBlending;   // lutBlending = null; read only with an albedo, LightingRenderer.cs:1574-1590
     int RowBegin = 0, RowEnd = -1;                      // destination rows (a group member's strip); RowEnd < 0 => the destination's height
 };
 
@@ -1051,7 +1066,8 @@ public:
     // `albedo` != 0: the ...WithAlbedo techniques over a texture of the lightmap's size (ResolveLighting with albedo != null, :1549-1580).
     void Resolve(IlmHandle destination, const IlmHDRConfiguration* hdr = nullptr, int rowBegin = 0, int rowEnd = -1, IlmHandle albedo = 0) const;
     // The two RenderedLighting.Resolve overloads at any destination size (LightingRenderer.HDR.cs:99-126 and :128-151), both ending in
-    // ResolveLighting (LightingRenderer.cs:1537-1645) over ilm_resolve_lighting_scaled -- the call a frame lit at RenderScale != 1 needs.
+    // ResolveLighting (LightingRenderer.cs:1537-1645) over ilm_resolve_lighting_scaled -- the call a frame lit at RenderScale != 1 needs --
+    // or, with options.LUTBlending, an albedo and HDR mode None, over ilm_resolve_lighting_lut (:1574-1577; GammaCompress / ToneMap throw).
     // ResolveTo: scale = (width / rw, height / rh), rw x rh the albedo's size when there is one, else the lightmap's (:115-117).
     // ResolveAt: the quad's top left corner in destination pixels and the scale itself (default Vector2.One).
     void ResolveTo(const ResolveTexture& destination, float width, float height, const ResolveOptions& options = {}) const;

@@ -120,6 +120,7 @@ SYMBOLS = {
     "ilm_resolve_lighting": (_I, [_H, _H, _P, _I, _I]),
     "ilm_resolve_lighting_with_albedo": (_I, [_H, _H, _H, _P, _I, _I]),
     "ilm_resolve_lighting_scaled": (_I, [_H, _H, _H, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    "ilm_resolve_lighting_lut": (_I, [_H, _H, _H, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "ilm_lightmap_upload": (_I, [_H, _P, _I, _I]),
     "ilm_lightmap_luminance": (_I, [_H, _I, _I, _I, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ilm_lightmap_histogram": (_I, [_H, _P, _P, _P, _P]),
@@ -993,3 +994,40 @@ def resolve_lighting_scaled(src, dst, hdr, quad, lightmap_region=None, albedo=No
     uv, uvp = floats(uv_offset, 2) if uv_offset is not None else (None, None)
     check(lib().ilm_resolve_lighting_scaled(src.handle, albedo.handle if albedo is not None else abi.Handle(0), dst.handle, _byref(hdr),
                                             qp, lrp, arp, uvp, lightmap_filter, albedo_filter, row_begin, row_end))
+
+
+def lut_blending(dark, bright, dark_level, bright_level, neutral_band_size=0.0, per_channel=False, lut_only=False, dark_row=0, bright_row=0,
+                 dark_resolution=None, bright_resolution=None):
+    """An abi.LUTBlending over two Lightmap objects holding LUT textures (width N * N, height N * rows): resolution and row count are
+    read off the texture's size unless a resolution is given."""
+    def shape(t, n):
+        n = int(round(t.width ** 0.5)) if n is None else n
+        return n, (t.height // n if n > 0 else 0)
+    b = abi.LUTBlending()
+    b.DarkLUT, b.BrightLUT = dark.handle, bright.handle
+    (b.DarkResolution, b.DarkRowCount), (b.BrightResolution, b.BrightRowCount) = shape(dark, dark_resolution), shape(bright, bright_resolution)
+    b.DarkRow, b.BrightRow = dark_row, bright_row
+    b.DarkLevel, b.NeutralBandSize, b.BrightLevel = dark_level, neutral_band_size, bright_level
+    b.PerChannel, b.LUTOnly = int(per_channel), int(lut_only)
+    return b
+
+
+def resolve_lighting_lut(src, dst, hdr, lut, quad, albedo, lightmap_region=None, albedo_region=None, uv_offset=None,
+                         lightmap_filter=abi.FILTER_LINEAR, albedo_filter=abi.FILTER_LINEAR, row_begin=0, row_end=None):
+    """ilm_resolve_lighting_lut: resolve_lighting_scaled's fetch and coverage, the albedo looked up in the dark and the bright LUT of
+    `lut` (an abi.LUTBlending) and the two blended by the light; hdr.Mode must be HDR_NONE and an albedo is required."""
+    def floats(values, n):
+        a = (C.c_float * n)(*[float(v) for v in values])
+        return a, C.cast(a, C.c_void_p)
+    if row_end is None:
+        row_end = dst.height
+    if lightmap_region is None:
+        lightmap_region = (0.0, 0.0, src.width, src.height)
+    if albedo is not None and albedo_region is None:
+        albedo_region = (0.0, 0.0, albedo.width, albedo.height)
+    q, qp = floats(quad, 4)
+    lr, lrp = floats(lightmap_region, 4)
+    ar, arp = floats(albedo_region, 4) if albedo_region is not None else (None, None)
+    uv, uvp = floats(uv_offset, 2) if uv_offset is not None else (None, None)
+    check(lib().ilm_resolve_lighting_lut(src.handle, albedo.handle if albedo is not None else abi.Handle(0), dst.handle, _byref(hdr), _byref(lut),
+                                         qp, lrp, arp, uvp, lightmap_filter, albedo_filter, row_begin, row_end))

@@ -37,7 +37,8 @@ extern "C" {
  * + ilm_render_line_lights (line lights; a LightVertex again); + ilm_render_volumetric_lights (volumetric lights; likewise);
  * + ilm_ctx_set_projector_texture_mips (a projector texture's mip chain, fetched trilinearly at the light's mip bias);
  * + ilm_ctx_set_light_blend_function, ILM_LIGHT_BLEND_* (subtractive, max and min light groups: LightSource.BlendMode);
- * + ilm_resolve_lighting_scaled, ILM_FILTER_* (the resolve onto a target of another size: RenderScale != 1).
+ * + ilm_resolve_lighting_scaled, ILM_FILTER_* (the resolve onto a target of another size: RenderScale != 1);
+ * + ilm_resolve_lighting_lut / IlmLUTBlending (the LUT-blended resolve over a dark and a bright colour LUT).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -1264,7 +1265,7 @@ int32_t ilm_resolve_lighting(IlmHandle src_lightmap, IlmHandle dst_lightmap, con
  * techniques ScreenSpaceLightingResolveWithAlbedo / GammaCompressed... / ToneMapped..., Illuminant/Shaders/Resolve.fx:43-60,141-233), 1:1:
  * light = src * (InverseScaleFactor * 2); rgb = lerp(albedo.rgb, albedo.rgb * light.rgb, saturate(light.a)); alpha = albedo.a; then the
  * HDR mode as above.  `albedo` is a texture the size of the lightmap held in a lightmap object (RGBA8 = SurfaceFormat.Color is the
- * usual case; upload with ilm_lightmap_upload); albedo == 0 is ilm_resolve_lighting.  Not bound: AlbedoIsSRGB, the LUT-blended technique. */
+ * usual case; upload with ilm_lightmap_upload); albedo == 0 is ilm_resolve_lighting.  Not bound: AlbedoIsSRGB.  The LUT-blended technique is ilm_resolve_lighting_lut. */
 int32_t ilm_resolve_lighting_with_albedo(IlmHandle src_lightmap, IlmHandle albedo, IlmHandle dst_lightmap, const IlmHDRConfiguration* hdr,
                                          int32_t row_begin, int32_t row_end);
 
@@ -1316,6 +1317,67 @@ int32_t ilm_resolve_lighting_scaled(IlmHandle src_lightmap, IlmHandle albedo /* 
                                     const float uv_offset[2],        /* LightmapUVOffset in SOURCE texels; NULL = (0, 0) */
                                     int32_t lightmap_filter, int32_t albedo_filter,
                                     int32_t row_begin, int32_t row_end);   /* destination rows; the strip of a group member */
+
+/* The LUT-blended resolve: RenderedLighting.Resolve with a LUTBlendingConfiguration (Illuminant/Lighting/LightingRenderer.HDR.cs:260-273)
+ * and an albedo -- technique ScreenSpaceLUTBlendedLightingResolveWithAlbedo (Illuminant/Shaders/LUTResolve.fx:61-144), selected at
+ * Illuminant/Lighting/LightingRenderer.cs:1574-1577, its uniforms bound by SetLUTBlending (Illuminant/Lighting/IlluminantMaterials.cs:139-147).
+ * The albedo is looked up in a dark and a bright colour LUT and the two are blended by the light's luminance (or per channel).
+ *
+ * Fetch and coverage are ilm_resolve_lighting_scaled's, word for word: quad, regions, uv_offset, filters and rows mean what they mean
+ * there, and the light texel `tap` and the albedo texel `albedo` are the ones that contract defines.  The 1:1 case is the quad of the
+ * albedo's size.
+ *
+ * Per pixel (LUTBlendedResolveWithAlbedoCommon, LUTResolve.fx:61-115), in fp32, one rounding per operation, no contraction, in this order:
+ *     light = tap * (InverseScaleFactor * 2)                                              (:75; InverseScaleFactor 0 => 1)
+ *     a = saturate(albedo.rgb)            (:87; a NaN becomes 0, as saturate does everywhere in this header); the alpha written is albedo.a
+ *   Launch-uniform, computed once on the host in fp32 in the shader's order (:78-81):
+ *     bandWidth = saturate(BrightLevel - DarkLevel);  neutral = fminf(NeutralBandSize, bandWidth - 0.01f)
+ *     hasNeutralBand = neutral > 0;  normalize = !PerChannel || hasNeutralBand
+ *   Weight (:77,82-85): under `normalize` every channel of w is (light.r * 0.299f + light.g * 0.587f) + light.b * 0.144f (0.144 is
+ *     LUTResolve.fx:16's constant, as in ilm_lightmap_luminance); otherwise w = light.rgb.
+ *   dark = ReadLUT(DarkLUT, a), bright = ReadLUT(BrightLUT, a): below.  lerp(x, y, t) = x + (y - x) * t.
+ *   With a neutral band (:93-98): t = (bandWidth - neutral) * 0.5f (0.005 less a rounding at the least: never a zero divisor), v = w.x - DarkLevel,
+ *     v3 = (v - t) - neutral;  val1 = lerp(dark, a, saturate(v * (1 / t)));  blended = lerp(val1, bright, saturate(v3 * (1 / t))).
+ *   Without one (:100-110): when BrightLevel > DarkLevel, w = saturate(fmaxf(0, w - DarkLevel) * (1 / (BrightLevel - DarkLevel))), else
+ *     (the shader's HACK branch) w = saturate(w - DarkLevel);  blended = lerp(dark, bright, w), channel by channel.
+ *   The two uniform divisors are host-side reciprocals: 1.0f / t and 1.0f / (BrightLevel - DarkLevel) are each rounded once on the host and
+ *     the pixel multiplies by them, as the resolve's other uniform divisors are taken.
+ *   rgb = LUTOnly ? blended : blended * light.rgb (:113), then the ILM_HDR_NONE epilogue of the other resolves unchanged (:129-131):
+ *     pow(max(0, rgb + Offset) * Exposure, Gamma) with their clamps of Exposure and Gamma.  Destination formats and non-finite results are
+ *     those of ilm_resolve_lighting; a non-finite light texel gives what IEEE arithmetic gives and never an index outside a LUT.
+ *
+ * DEFINED DEVIATION: ReadLUT and the texture layout.  The reference leaves both to Fracture's LUTCommon.fxh and ColorLUT, which are
+ * outside the tree.  What replaces them, in full:
+ *   Layout.  A LUT of resolution N with R rows is a texture of width N * N and height N * R: R rows of N slices of N x N texels, the
+ *     slices side by side.  Lattice point (ri, gi, bi) of row `Row` is the texel at column bi * N + ri, texel row Row * N + gi.  Only its
+ *     rgb is read.  The texture may have any format (RGBA8 is the usual one).
+ *   Per channel c of a:  s = c * (float)(N - 1), i0 = min((int)floorf(s), N - 1), i1 = min(i0 + 1, N - 1), f = s - floorf(s).
+ *   The value is the trilinear blend of the eight lattice points T[ri][gi][bi] round a:
+ *     lerp3(lerp3(lerp3(T000, T100, fr), lerp3(T010, T110, fr), fg), lerp3(lerp3(T001, T101, fr), lerp3(T011, T111, fr), fg), fb)
+ *   Indices are clamped inside the slice and the row by integer arithmetic: no tap ever comes from a neighbouring slice or row, whatever
+ *     the floats are.  This is the lattice fetch that a bilinear sampler with a half-texel inset plus a manual blue lerp approximates.
+ *   DarkRow / BrightRow choose the row; the reference never sets LUTOffsets (SetLUTBlending's "FIXME: RowIndex"), which is row 0.
+ *
+ * Refused, leaving `dst` untouched: a bad handle -- src, dst, albedo, and DarkLUT / BrightLUT once `lut` can be read
+ * (ILM_ERR_INVALID_HANDLE; src and dst before anything else); albedo == 0 (the reference has no LUT technique without albedo); hdr, lut,
+ * quad or a region NULL; hdr->Mode other than ILM_HDR_NONE (the reference throws "LUT blending is not compatible with this type of
+ * lighting resolve", LightingRenderer.cs:1589-1590); a Resolution < 2 or a RowCount < 1; a LUT texture whose size is not N * N x N * R; a
+ * row outside [0, R); a DarkLevel, NeutralBandSize or BrightLevel that is not finite; textures of different contexts; and everything
+ * ilm_resolve_lighting_scaled refuses (ResolveToSRGB, dithering, AlbedoIsSRGB, a bad filter, rows, quad or region).
+ * Asynchronous on the context's main stream. */
+typedef struct {
+    IlmHandle DarkLUT, BrightLUT;                 /* lightmap objects holding the LUT textures (any format; RGBA8 is the usual one) */
+    int32_t   DarkResolution, BrightResolution;   /* LUTResolutionsAndRowCounts.xy */
+    int32_t   DarkRowCount,  BrightRowCount;      /* LUTResolutionsAndRowCounts.zw */
+    int32_t   DarkRow, BrightRow;                 /* which row of the texture is read; the reference never sets LUTOffsets: 0 */
+    float     DarkLevel, NeutralBandSize, BrightLevel;   /* LUTLevels.xyz */
+    int32_t   PerChannel, LUTOnly;
+} IlmLUTBlending;
+int32_t ilm_resolve_lighting_lut(IlmHandle src_lightmap, IlmHandle albedo /* required */, IlmHandle dst,
+                                 const IlmHDRConfiguration* hdr, const IlmLUTBlending* lut,
+                                 const float quad[4], const float lightmap_region[4], const float albedo_region[4],
+                                 const float uv_offset[2], int32_t lightmap_filter, int32_t albedo_filter,
+                                 int32_t row_begin, int32_t row_end);
 
 /* ---- brightness estimation: the inputs of the resolve's AverageLuminance / MaximumLuminance / Exposure / WhitePoint -------
  *

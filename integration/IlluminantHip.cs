@@ -478,6 +478,23 @@ namespace Squared.Illuminant.Native {
         public int AlbedoIsSRGB;
     }
 
+    [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 64)]
+    public struct IlmLUTBlending {
+        public ulong DarkLUT;
+        public ulong BrightLUT;
+        public int DarkResolution;
+        public int BrightResolution;
+        public int DarkRowCount;
+        public int BrightRowCount;
+        public int DarkRow;
+        public int BrightRow;
+        public float DarkLevel;
+        public float NeutralBandSize;
+        public float BrightLevel;
+        public int PerChannel;
+        public int LUTOnly;
+    }
+
     [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 16)]
     public struct IlmHistogramBucket {
         public int Count;
@@ -627,6 +644,7 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_resolve_lighting (ulong srcLightmap, ulong dstLightmap, IlmHDRConfiguration* hdr, int rowBegin, int rowEnd);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_resolve_lighting_with_albedo (ulong srcLightmap, ulong albedo, ulong dstLightmap, IlmHDRConfiguration* hdr, int rowBegin, int rowEnd);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_resolve_lighting_scaled (ulong srcLightmap, ulong albedo, ulong dst, IlmHDRConfiguration* hdr, float* quad, float* lightmapRegion, float* albedoRegion, float* uvOffset, int lightmapFilter, int albedoFilter, int rowBegin, int rowEnd);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_resolve_lighting_lut (ulong srcLightmap, ulong albedo, ulong dst, IlmHDRConfiguration* hdr, IlmLUTBlending* lut, float* quad, float* lightmapRegion, float* albedoRegion, float* uvOffset, int lightmapFilter, int albedoFilter, int rowBegin, int rowEnd);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_luminance (ulong lightmap, int renderWidth, int renderHeight, int accuracyFactor, float* outValues, int capacity, int* outLevel, int* outWidth, int* outHeight);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_histogram (ulong lightmap, IlmHistogramParams* @params, float* bucketMaxValues, IlmHistogramBucket* outBuckets, IlmHistogramResult* @out);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_queue_luminance (ulong lightmap, int renderWidth, int renderHeight, int accuracyFactor);

@@ -133,7 +133,7 @@ class Layout:
             assert off % a == 0, "%s.%s would need padding: Pack = 4 sequential layout would differ from C" % (name, fname)
             off += s * self.count(dims)
             align = max(align, a)
-        assert off % align == 0, "%s has tail padding" % name
+        off = (off + align - 1) // align * align          # C's tail padding (IlmLUTBlending: 60 -> 64); StructLayout's Size carries it
         self.sizes[name], self.aligns[name] = off, align
         return off
 
