@@ -30,6 +30,8 @@ UPDATE_NONE, UPDATE_POSITIONS, UPDATE_WITH_DISTANCE_FIELD, UPDATE_ERASE = 0, 1, 
 STEP_COUNT_LIVE = 1
 
 SDF_UNORM16, SDF_FP16 = 0, 1
+# ILM_SDF_FILTER_*: the field's bilinear filter (ilm_sdf_set_filter) -- fp32 weights, or fractions of 8 bits
+SDF_FILTER_FP32, SDF_FILTER_FIXED8 = 0, 8
 GBUFFER_FLOAT4, GBUFFER_HALF4 = 0, 1
 LIGHTMAP_FLOAT4, LIGHTMAP_HALF4, LIGHTMAP_RGBA8 = 0, 1, 2
 # ILM_LIGHT_BLEND_*: a light group's blend function (ilm_ctx_set_light_blend_function), for rgb and for alpha

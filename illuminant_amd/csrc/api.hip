@@ -211,6 +211,8 @@ struct Sdf {
     Ctx* ctx = nullptr;
     Shared shared;
     uint2* texels = nullptr; int width = 0, height = 0, format = 0;
+    // The bilinear filter (ilm_sdf_set_filter): sampler state, read where a kernel is chosen -- never by make_sdf_view or the cells
+    int filter = ILM_SDF_FILTER_FP32;
     // The cone trace's view of the field (hlsl_math.hpp, SdfView::cells): built from the atlas on demand by ensure_sdf_cells and kept
     // until the atlas changes (`version` is bumped by every entry point that writes it) or is described by other uniforms (the layout
     // key).  A field whose device pointer was handed out (ilm_sdf_device_ptr) may change behind the library's back: its cells are
@@ -401,6 +403,14 @@ const char* field_uniforms_mismatch(const Sdf* f, const IlmDistanceFieldUniforms
     if (std::fabs(cols * sw - (double)f->width) <= 0.5 && std::fabs(rows * sh - (double)f->height) <= 0.5) return nullptr;
     snprintf(text, n, "the distance-field uniforms describe a %.0f x %.0f atlas (%g x %g slices of %g x %g) but the bound field is %d x %d",
              cols * sw, rows * sh, cols, rows, sw, sh, f->width, f->height);
+    return text;
+}
+
+// A field whose filter is not FP32 is sampled by ilm_sdf_sample, ilm_debug_sdf_sample_inside and ilm_render_sphere_lights alone (the
+// header, ilm_sdf_set_filter); every other entry point that would sample it refuses with this, before it queues or writes anything.
+static const char* field_filter_unsupported(const Sdf* f, const char* who, char* text, size_t n) {
+    if (!f || f->filter == ILM_SDF_FILTER_FP32) return nullptr;
+    snprintf(text, n, "%s does not honour the distance field's filter (ilm_sdf_set_filter: %d fraction bits); set it back to ILM_SDF_FILTER_FP32", who, f->filter);
     return text;
 }
 
@@ -789,6 +799,8 @@ int32_t validate_step(const System* s, const IlmStepDesc* d, int* first, int* co
     if (d->UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD) {
         char why[256];
         if (field_extent_unusable(&d->DistanceField, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why);
+        if (field_filter_unsupported(from_handle<Sdf>(s->sdf_handle, kMagicSdf), "the collision update", why, sizeof(why)))
+            return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why);
     }
     int f = d->FirstChunk, c = d->ChunkCount;
     if (c < 0) { f = 0; c = n; }
@@ -1950,6 +1962,7 @@ int32_t ilm_system_set_distance_field(IlmHandle h, IlmHandle hsdf) {
     Sdf* f = from_handle<Sdf>(hsdf, kMagicSdf);
     if (!f) return fail(ILM_ERR_INVALID_HANDLE, "not a distance field handle");
     if (f->ctx != s->engine->ctx) return fail(ILM_ERR_INVALID_ARGUMENT, "distance field belongs to another context");
+    { char why[256]; if (field_filter_unsupported(f, "a particle system", why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
     s->sdf_handle = hsdf;
     return ILM_OK;
 }
@@ -2307,7 +2320,7 @@ int32_t ilm_sdf_sample(IlmHandle h, const IlmDistanceFieldUniforms* df, const fl
         void* dv = nullptr;
         HIP_TRY(hipHostGetDevicePointer(&dv, block, 0));
         float* d_in = static_cast<float*>(dv);
-        HIP_TRY(launch_sdf_sample(make_sdf_view(f, df), *df, d_in, count, d_in + 3 * (size_t)count, c->main()));
+        HIP_TRY(launch_sdf_sample(make_sdf_view(f, df), *df, d_in, count, d_in + 3 * (size_t)count, c->main(), f->filter));
         rc = staged_small_done(c, slot);
         if (rc != ILM_OK) return rc;
         HIP_TRY(hipStreamSynchronize(c->main()));
@@ -2319,7 +2332,7 @@ int32_t ilm_sdf_sample(IlmHandle h, const IlmDistanceFieldUniforms* df, const fl
     float* d_in = c->staging.as<float>();
     float* d_out = d_in + 3 * (size_t)count;
     HIP_TRY(hipMemcpyAsync(d_in, positions, in_bytes, hipMemcpyHostToDevice, c->main()));
-    HIP_TRY(launch_sdf_sample(make_sdf_view(f, df), *df, d_in, count, d_out, c->main()));
+    HIP_TRY(launch_sdf_sample(make_sdf_view(f, df), *df, d_in, count, d_out, c->main(), f->filter));
     HIP_TRY(hipMemcpyAsync(out_distances, d_out, out_bytes, hipMemcpyDeviceToHost, c->main()));
     HIP_TRY(hipStreamSynchronize(c->main()));
     return ILM_OK;
@@ -2343,7 +2356,7 @@ int32_t ilm_debug_sdf_sample_inside(IlmHandle h, const IlmDistanceFieldUniforms*
     HIP_TRY(hipMemcpyAsync(d_in, positions, in_bytes, hipMemcpyHostToDevice, c->main()));
     TraceSdfView view;
     HIP_TRY(make_trace_view(f, df, c->main(), &view));
-    HIP_TRY(launch_sdf_sample_inside(view, *df, d_in, count, d_out, d_used, c->main()));
+    HIP_TRY(launch_sdf_sample_inside(view, *df, d_in, count, d_out, d_used, c->main(), f->filter));
     HIP_TRY(hipMemcpyAsync(out_distances, d_out, out_bytes, hipMemcpyDeviceToHost, c->main()));
     HIP_TRY(hipMemcpyAsync(out_used_table, d_used, out_bytes, hipMemcpyDeviceToHost, c->main()));
     HIP_TRY(hipStreamSynchronize(c->main()));
@@ -2465,6 +2478,23 @@ int32_t ilm_sdf_trace_info(IlmHandle h, IlmSdfTraceInfo* out) {
     out->CellRebuilds = f->cell_rebuilds; out->CellSlicesRebuilt = f->cell_slices_rebuilt;
     out->LastRebuiltSlices = f->last_rebuilt_slices; out->TableSlices = f->last_table_slices;
     out->RebuiltEveryFrame = f->escaped ? 1 : 0; out->Reserved = 0;
+    return ILM_OK;
+}
+
+int32_t ilm_sdf_set_filter(IlmHandle h, int32_t fraction_bits) {
+    Sdf* f = from_handle<Sdf>(h, kMagicSdf);
+    if (!f) return fail(ILM_ERR_INVALID_HANDLE, "not a distance field handle");
+    if (fraction_bits != ILM_SDF_FILTER_FP32 && fraction_bits != ILM_SDF_FILTER_FIXED8)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "filter of %d fraction bits: ILM_SDF_FILTER_FP32 (0) or ILM_SDF_FILTER_FIXED8 (8)", fraction_bits);
+    f->filter = fraction_bits;      // read at the next launch: nothing is queued, the atlas and the cells (taps, not weights) stay as they are
+    return ILM_OK;
+}
+
+int32_t ilm_sdf_get_filter(IlmHandle h, int32_t* out_fraction_bits) {
+    Sdf* f = from_handle<Sdf>(h, kMagicSdf);
+    if (!f) return fail(ILM_ERR_INVALID_HANDLE, "not a distance field handle");
+    if (!out_fraction_bits) return fail(ILM_ERR_INVALID_ARGUMENT, "out_fraction_bits is NULL");
+    *out_fraction_bits = f->filter;
     return ILM_OK;
 }
 
@@ -3071,13 +3101,15 @@ int32_t reserve_light_recs(Ctx* c, int light_count) {
 // (null for handle 0), for light_pass_queued() once the pass has been queued.
 int32_t fill_light_launch(Ctx* c, const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf,
                           IlmHandle hlightmap, int32_t row_begin, int32_t row_end, LightLaunch* a, Sdf** out_field, GBuffer** out_gbuffer,
-                          bool with_cells = true) {
+                          bool with_cells = true, const char* refuses_filter = "this light pass") {
     Lightmap* m = from_handle<Lightmap>(hlightmap, kMagicLightmap);
     if (!m) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
     GBuffer* g = nullptr; Sdf* f = nullptr;
     if (hgbuffer) { g = from_handle<GBuffer>(hgbuffer, kMagicGBuffer); if (!g) return fail(ILM_ERR_INVALID_HANDLE, "not a G-buffer handle"); }
     if (hsdf) { f = from_handle<Sdf>(hsdf, kMagicSdf); if (!f) return fail(ILM_ERR_INVALID_HANDLE, "not a distance field handle"); }
     if (!env || !df) return fail(ILM_ERR_INVALID_ARGUMENT, "NULL argument");
+    // (refuses_filter == nullptr: the sphere pass, which honours the field's filter)
+    { char why[256]; if (refuses_filter && field_filter_unsupported(f, refuses_filter, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
     // (the lightmap is written: the context's own; the field and the G-buffer are read: the context's or a sibling's)
     if (m->ctx != c || (g && !siblings(g->ctx, c)) || (f && !siblings(f->ctx, c))) return fail(ILM_ERR_INVALID_ARGUMENT, "resources belong to another context");
     if (row_begin < 0 || row_end > m->height || row_begin > row_end)
@@ -3130,7 +3162,7 @@ int32_t ilm_render_particle_lights(IlmHandle hctx, IlmHandle hsystem, const int3
     if (chunk_count < 0 || chunk_count > n) return fail(ILM_ERR_OUT_OF_RANGE, "chunk_count %d outside [0, %d]", chunk_count, n);
     LightLaunch a = {};
     Sdf* f = nullptr; GBuffer* g = nullptr;
-    int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, &f, &g);
+    int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, &f, &g, true, "ilm_render_particle_lights");
     if (rc != ILM_OK) return rc;
     if (chunk_count == 0) return ILM_OK;
     Engine* e = s->engine;
@@ -3185,6 +3217,7 @@ int32_t ilm_render_light_probes(IlmHandle hctx, const IlmLightVertex* lights, in
     Sdf* f = nullptr;
     if (hsdf) { f = from_handle<Sdf>(hsdf, kMagicSdf); if (!f) return fail(ILM_ERR_INVALID_HANDLE, "not a distance field handle"); }
     if (f && f->ctx != c) return fail(ILM_ERR_INVALID_ARGUMENT, "resources belong to another context");
+    { char why[256]; if (field_filter_unsupported(f, "ilm_render_light_probes", why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
     if (!env || !df) return fail(ILM_ERR_INVALID_ARGUMENT, "NULL argument");
     if (light_count < 0 || (light_count > 0 && !lights)) return fail(ILM_ERR_INVALID_ARGUMENT, "bad light array");
     if (probe_count < 0 || (probe_count > 0 && (!probe_positions || !probe_normals || !out_values))) return fail(ILM_ERR_INVALID_ARGUMENT, "bad probe arrays");
@@ -3572,6 +3605,7 @@ int32_t ilm_visualize_distance_field(IlmHandle hctx, IlmHandle hsdf, const IlmDi
     // (the target is written: the context's own; the field is read: the context's or a sibling's, as in ilm_render_sphere_lights)
     if (m->ctx != c) return fail(ILM_ERR_INVALID_ARGUMENT, "context and target belong to different contexts");
     if (!siblings(f->ctx, c)) return fail(ILM_ERR_INVALID_ARGUMENT, "resources belong to another context");
+    { char why[256]; if (field_filter_unsupported(f, "ilm_visualize_distance_field", why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
     { char why[256]; if (field_uniforms_mismatch(f, df, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
     if ((m->width + 15) / 16 > 65535 || (m->height + 15) / 16 > 65535) return fail(ILM_ERR_OUT_OF_RANGE, "target too large");
     // the quad's rectangle in pixels (the header defines the arithmetic) and the pixels of the target it can cover
@@ -3959,7 +3993,15 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     if (light_count > 65535) return fail(ILM_ERR_TOO_MANY, "at most 65535 lights per call");
     LightLaunch a = {};
     Sdf* f = nullptr; GBuffer* g = nullptr;
-    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, &f, &g); if (rc != ILM_OK) return rc; }
+    // The field's filter (ilm_sdf_set_filter) is honoured here, in the fp32 model under ADD / ADD alone: refused before anything is queued
+    if (Sdf* field = hsdf ? from_handle<Sdf>(hsdf, kMagicSdf) : nullptr; field && field->filter != ILM_SDF_FILTER_FP32) {
+        if (c->lightmap_blend == ILM_BLEND_FP16_PER_LIGHT)
+            return fail(ILM_ERR_INVALID_ARGUMENT, "the distance field's filter (ilm_sdf_set_filter: %d fraction bits) does not compose with ILM_BLEND_FP16_PER_LIGHT", field->filter);
+        if (c->light_blend_color != ILM_LIGHT_BLEND_ADD || c->light_blend_alpha != ILM_LIGHT_BLEND_ADD)
+            return fail(ILM_ERR_INVALID_ARGUMENT, "the distance field's filter (ilm_sdf_set_filter: %d fraction bits) composes with the ADD / ADD blend functions only", field->filter);
+    }
+    { const int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, &f, &g, true, nullptr); if (rc != ILM_OK) return rc; }
+    const int filter = f ? f->filter : ILM_SDF_FILTER_FP32;
 
     { const int32_t rc = reserve_light_recs(c, light_count); if (rc != ILM_OK) return rc; }
     if (light_count > 0) {
@@ -3977,10 +4019,11 @@ int32_t ilm_render_sphere_lights(IlmHandle hctx, const IlmLightVertex* lights, i
     a.accumulate = ambient ? 0 : 1;          // a further light group of the frame: added to what the lightmap holds
     a.ramp = RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h };
     HIP_TRY(launch_stats_begin(c, stats != nullptr, &a.stats));
-    { const int32_t rc = plan_light_split(c, &a); if (rc != ILM_OK) return rc; }
+    // (a filtered launch: one workgroup per tile, as fill_light_launch left it -- like the non-additive blend functions)
+    if (filter == ILM_SDF_FILTER_FP32) { const int32_t rc = plan_light_split(c, &a); if (rc != ILM_OK) return rc; }
     { const int32_t rc = plan_group_order(c, &a, lights, light_count, 16 * a.tile_macro); if (rc != ILM_OK) return rc; }
     c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
-    HIP_TRY(launch_sphere_lights_prepared(a, c->d_recs.p, c->main()));
+    HIP_TRY(launch_sphere_lights_prepared(a, c->d_recs.p, c->main(), filter));
     HIP_TRY(light_pass_queued(c, f, g));
     HIP_TRY(launch_stats_end(c, stats));
     return ILM_OK;

@@ -1076,6 +1076,12 @@ int32_t ilm_group_render_sphere_lights(IlmHandle hgroup, const IlmLightVertex* l
     if (!m) return api_fail(ILM_ERR_INVALID_HANDLE, "not a group lightmap handle");
     if (m->group != g) return api_fail(ILM_ERR_INVALID_ARGUMENT, "the lightmap belongs to another group");
     if ((gather & ~ILM_GATHER_ASYNC) < ILM_GATHER_NONE || (gather & ~ILM_GATHER_ASYNC) > ILM_GATHER_STORE) return api_fail(ILM_ERR_INVALID_ARGUMENT, "unknown gather mode %d", gather);
+    // a member's field with a filter (ilm_sdf_set_filter): the group entry does not honour it -- refused before anything is queued or exchanged
+    for (int i = 0; sdfs && i < g->n_local; i++) {
+        int32_t bits = ILM_SDF_FILTER_FP32;
+        if (sdfs[i] && ilm_sdf_get_filter(sdfs[i], &bits) == ILM_OK && bits != ILM_SDF_FILTER_FP32)
+            return api_fail(ILM_ERR_INVALID_ARGUMENT, "ilm_group_render_sphere_lights does not honour the distance field's filter (ilm_sdf_set_filter: %d fraction bits, member %d); set it back to ILM_SDF_FILTER_FP32", bits, i);
+    }
     if (stats) { stats->SdfSamples = 0; stats->PixelLightPairs = 0; stats->TracedPairs = 0; }
     // (a lightmap whose last exchange was asynchronous: the strips about to be rendered into it wait for that exchange)
     { const int32_t rc = wait_lightmap_exchange(m); if (rc != ILM_OK) return rc; }

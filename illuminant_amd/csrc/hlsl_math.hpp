@@ -244,6 +244,16 @@ ILM_DEV void sdf_unpack_word(uint32_t w, float& a, float& b) {
 // CHECK_NAN = false: the caller guarantees finite coordinates (the cone trace hoists the test out of its loop).
 ILM_DEV float lerp_fused(float a, float b, float t) { return __builtin_fmaf(t, b - a, a); }
 
+// The field's filter (ilm_sdf_set_filter; the header has the MODEL and its DEFINED DEVIATION) as a compile-time choice of both sampler
+// forms: kSdfFixed8 beside the atlas format in their FORMAT parameter.  With the bit clear nothing below is compiled in.
+// FIXED8: a bilinear fraction f in [0, 1) becomes rint(f * 256) / 256 -- both products exact, v_rndne_f32 rounds half to even, a
+// fraction of at least 255.5 / 256 becomes the weight 1.0 (the taps stay where they are).
+constexpr int kSdfFixed8 = ILM_SDF_FILTER_FIXED8;
+constexpr int kSdfFormatMask = 1;
+static_assert((ILM_SDF_UNORM16 & ~kSdfFormatMask) == 0 && (ILM_SDF_FP16 & ~kSdfFormatMask) == 0 && (kSdfFixed8 & 7) == 0,
+              "the filter bit lies above the format and above the bits estimate_normal4 and the light kernels' variants use");
+ILM_DEV float quantise_fraction8(float f) { return __builtin_rintf(f * 256.0f) * (1.0f / 256.0f); }
+
 // n / d, correctly rounded, for 2^-60 <= |d| <= 2^60 and |n| <= 2^60 (or zero / infinite / NaN): the instruction sequence the
 // compiler emits for an IEEE division without its two v_div_scale_f32 -- inside that range they do not scale (the scaled and
 // unscaled operands are the same bits, v_div_fmas_f32 applies no post-scale), so every intermediate is identical; v_div_fixup_f32
@@ -273,9 +283,12 @@ ILM_DEV float div_no_scale(float n, float d) { return div_with_rcp(n, d, refined
 // lerp(lo, hi, 0) = fma(0, hi - lo, lo) = lo for every finite lo, hi (up to the sign of a zero that `kDistanceZero - blended` does not
 // see).  The caller selects it when Packed1.y == 0 and Packed1.x, .z are finite; one channel per tap, three lerps instead of seven, no
 // slice arithmetic: a quarter of the sampler's instructions.
-template <int FORMAT, bool CHECK_NAN = true, bool SLICE0 = false, bool CELLS0 = false>
+template <int FORMAT_AND_FILTER, bool CHECK_NAN = true, bool SLICE0 = false, bool CELLS0 = false>
 ILM_DEV float sample_distance_field(f3 position, const IlmDistanceFieldUniforms& df, const SdfView& sdf) {
 #pragma clang fp contract(off)
+    constexpr int FORMAT = FORMAT_AND_FILTER & kSdfFormatMask;
+    constexpr bool FIXED8 = (FORMAT_AND_FILTER & kSdfFixed8) != 0;
+    static_assert(!FIXED8 || !SLICE0, "the particle path's slice-0 samplers have no fixed-point filter");
     static_assert(!CELLS0 || (SLICE0 && FORMAT == ILM_SDF_UNORM16), "the slice-0 cells serve the slice-0 sampler of a UNORM16 field");
     position.z -= df.ConeAndMisc.y;
     const float ex = df.Extent.x, ey = df.Extent.y, ez = df.Extent.z;
@@ -323,7 +336,8 @@ ILM_DEV float sample_distance_field(f3 position, const IlmDistanceFieldUniforms&
     const float x = __builtin_fmaf(u, sdf.wf, -0.5f);
     const float y = __builtin_fmaf(v, sdf.hf, -0.5f);
     const float x0f = floorf(x), y0f = floorf(y);
-    const float fx = x - x0f, fy = y - y0f;
+    float fx = x - x0f, fy = y - y0f;
+    if (FIXED8) { fx = quantise_fraction8(fx); fy = quantise_fraction8(fy); }      // (the z blend below is shader arithmetic: not quantised)
     // U WRAP is what folds physical slice p onto atlas column p % cols (u = p / cols + ... runs past 1 for every atlas row but
     // the first, DistanceFieldCommon.fxh:303-311): a positive modulo of x0f by the atlas width.  q may be off by one after the
     // reciprocal multiply; the remainder x0f - q * width is exact in fp32 and is folded back into [0, width).
@@ -469,9 +483,11 @@ ILM_DEV float mix_fma_lo(float t, float d, uint32_t a) { float r; asm("v_fma_mix
 ILM_DEV float mix_fma_hi(float t, float d, uint32_t a) { float r; asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(t), "v"(d), "v"(a)); return r; }
 
 // Precondition (the caller's, per sample): position inside SdfView's box.  `table` = the workgroup's LDS table.
-template <int FORMAT>
+template <int FORMAT_AND_FILTER>
 ILM_DEV float sample_inside_table(f3 position, const InsideConsts& c, const TraceSdfView& sdf, const SliceEntry* table) {
 #pragma clang fp contract(off)
+    constexpr int FORMAT = FORMAT_AND_FILTER & kSdfFormatMask;
+    constexpr bool FIXED8 = (FORMAT_AND_FILTER & kSdfFixed8) != 0;
     const float pz = position.z - c.z_offset;
     const float slice_position = pz * c.slice_scale;          // min(clamp(z), validZ) is the identity inside the box
     // Inside the box slice_position, x and y are >= 0 (z >= the offset; every tap at least 1/16 texel inside its slice), so
@@ -484,7 +500,9 @@ ILM_DEV float sample_inside_table(f3 position, const InsideConsts& c, const Trac
     const float v = __builtin_fmaf(e.row_index, c.tsy, position.y * c.tsw);
     const float x = __builtin_fmaf(u, c.wf, -0.5f);
     const float y = __builtin_fmaf(v, c.hf, -0.5f);
-    const float fx = __builtin_amdgcn_fractf(x), fy = __builtin_amdgcn_fractf(y), fz = __builtin_amdgcn_fractf(slice_position);
+    float fx = __builtin_amdgcn_fractf(x), fy = __builtin_amdgcn_fractf(y);
+    const float fz = __builtin_amdgcn_fractf(slice_position);
+    if (FIXED8) { fx = quantise_fraction8(fx); fy = quantise_fraction8(fy); }      // (fract = x - floor(x) here: the general form's fractions)
     // the sample's cell: row floor(y), unfolded column floor(x) of the atlas (no clamp, no wrap inside the box), moved to the slice's grid
     const uint32_t column16 = ((uint32_t)(int)x << 4) + e.cell_off;
     uint32_t offset;

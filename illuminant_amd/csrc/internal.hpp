@@ -237,7 +237,8 @@ TraceGate make_trace_gate(const IlmDistanceFieldUniforms& df, const SdfView& sdf
 // per-call preparation of the light records (footprint, cone config, trace flags) into `recs` (device, count * kLightRecBytes)
 hipError_t launch_prepare_lights(const IlmLightVertex* lights, int count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df,
                                  const SdfView& sdf, void* recs, hipStream_t stream);
-hipError_t launch_sphere_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream);
+// sdf_filter: the bound field's ilm_sdf_set_filter state (FIXED8: one workgroup per tile, fp32 model, ADD / ADD -- anything else is an error)
+hipError_t launch_sphere_lights_prepared(const LightLaunch& a, const void* recs, hipStream_t stream, int sdf_filter = ILM_SDF_FILTER_FP32);
 // Directional lights (DirectionalLight.fx): the records (count * kLightRecBytes) and the full-frame pass over a's rows.  Of the launch
 // descriptor the pass reads the frame, the resources, ambient / accumulate / blend_fp16, the ramp, stats and the mirrors; the sphere
 // pass's tile map and light split do not apply (a footprint is a rectangle: four compares per pixel and light).
@@ -293,11 +294,12 @@ hipError_t launch_light_probes(const void* recs, int light_count, const float4* 
                                hipStream_t stream);
 // sampleDistanceFieldEx at `count` positions (xyz triples) -- diagnostic entry point ilm_sdf_sample
 hipError_t launch_stamp16(void* where, const uint32_t stamp[4], hipStream_t stream);      // 16 bytes stored by a kernel (output.hip)
-hipError_t launch_sdf_sample(const SdfView& sdf, const IlmDistanceFieldUniforms& df, const float* positions, int count, float* out, hipStream_t stream);
+hipError_t launch_sdf_sample(const SdfView& sdf, const IlmDistanceFieldUniforms& df, const float* positions, int count, float* out, hipStream_t stream,
+                             int sdf_filter = ILM_SDF_FILTER_FP32);
 // fills the cell array of the table sampler (sdf.table_slices x sdf.slice_h x sdf.slice_w cells of 16 bytes) from the atlas
 hipError_t launch_build_sdf_cells(const TraceSdfView& sdf, void* cells, int first_slice, int slice_count, hipStream_t stream);
 hipError_t launch_sdf_sample_inside(const TraceSdfView& sdf, const IlmDistanceFieldUniforms& df, const float* positions, int count, float* out, int32_t* used,
-                                    hipStream_t stream);
+                                    hipStream_t stream, int sdf_filter = ILM_SDF_FILTER_FP32);
 hipError_t launch_divide_by_constant(float divisor, float reciprocal, unsigned long long* mismatches, hipStream_t stream);
 void light_constant_divisors(float out[2][2]);
 hipError_t launch_divide_probe(const float* n, const float* d, int count, float* out_fast, float* out_ieee, hipStream_t stream);

@@ -1196,12 +1196,16 @@ __global__ __launch_bounds__(256) void sdf_sample_inside_kernel(TraceSdfView sdf
 }
 
 hipError_t launch_sdf_sample_inside(const TraceSdfView& sdf, const IlmDistanceFieldUniforms& df, const float* positions, int count, float* out, int32_t* used,
-                                    hipStream_t stream) {
+                                    hipStream_t stream, int sdf_filter) {
     if (count <= 0) return hipSuccess;
     const dim3 grid((unsigned)((count + 255) / 256)), block(256);
-    const hipError_t general = launch_sdf_sample(sdf, df, positions, count, out, stream);
+    const hipError_t general = launch_sdf_sample(sdf, df, positions, count, out, stream, sdf_filter);
     if (general != hipSuccess) return general;
-    if (sdf.format == ILM_SDF_FP16) hipLaunchKernelGGL(sdf_sample_inside_kernel<ILM_SDF_FP16>, grid, block, 0, stream, sdf, df, positions, count, out, used);
+    if (sdf_filter == ILM_SDF_FILTER_FIXED8) {
+        if (sdf.format == ILM_SDF_FP16) hipLaunchKernelGGL(sdf_sample_inside_kernel<ILM_SDF_FP16 + kSdfFixed8>, grid, block, 0, stream, sdf, df, positions, count, out, used);
+        else hipLaunchKernelGGL(sdf_sample_inside_kernel<ILM_SDF_UNORM16 + kSdfFixed8>, grid, block, 0, stream, sdf, df, positions, count, out, used);
+    } else if (sdf_filter != ILM_SDF_FILTER_FP32) return hipErrorInvalidValue;
+    else if (sdf.format == ILM_SDF_FP16) hipLaunchKernelGGL(sdf_sample_inside_kernel<ILM_SDF_FP16>, grid, block, 0, stream, sdf, df, positions, count, out, used);
     else hipLaunchKernelGGL(sdf_sample_inside_kernel<ILM_SDF_UNORM16>, grid, block, 0, stream, sdf, df, positions, count, out, used);
     return hipGetLastError();
 }
@@ -1233,10 +1237,15 @@ hipError_t launch_build_sdf_cells(const TraceSdfView& sdf, void* cells, int firs
     return hipGetLastError();
 }
 
-hipError_t launch_sdf_sample(const SdfView& sdf, const IlmDistanceFieldUniforms& df, const float* positions, int count, float* out, hipStream_t stream) {
+hipError_t launch_sdf_sample(const SdfView& sdf, const IlmDistanceFieldUniforms& df, const float* positions, int count, float* out, hipStream_t stream,
+                             int sdf_filter) {
     if (count <= 0) return hipSuccess;
     const dim3 grid((unsigned)((count + 255) / 256)), block(256);
-    if (sdf.format == ILM_SDF_FP16) hipLaunchKernelGGL(sdf_sample_kernel<ILM_SDF_FP16>, grid, block, 0, stream, sdf, df, positions, count, out);
+    if (sdf_filter == ILM_SDF_FILTER_FIXED8) {
+        if (sdf.format == ILM_SDF_FP16) hipLaunchKernelGGL(sdf_sample_kernel<ILM_SDF_FP16 + kSdfFixed8>, grid, block, 0, stream, sdf, df, positions, count, out);
+        else hipLaunchKernelGGL(sdf_sample_kernel<ILM_SDF_UNORM16 + kSdfFixed8>, grid, block, 0, stream, sdf, df, positions, count, out);
+    } else if (sdf_filter != ILM_SDF_FILTER_FP32) return hipErrorInvalidValue;
+    else if (sdf.format == ILM_SDF_FP16) hipLaunchKernelGGL(sdf_sample_kernel<ILM_SDF_FP16>, grid, block, 0, stream, sdf, df, positions, count, out);
     else hipLaunchKernelGGL(sdf_sample_kernel<ILM_SDF_UNORM16>, grid, block, 0, stream, sdf, df, positions, count, out);
     return hipGetLastError();
 }
@@ -1280,7 +1289,7 @@ int light_launch_blocks(const LightLaunch& a) {
     return (a.taper[0] + 2 * (a.taper[1] - a.taper[0]) + 4 * (a.taper[2] - a.taper[1]) + 8 * (slots - a.taper[2])) * 8;
 }
 
-hipError_t launch_sphere_lights_prepared(const LightLaunch& launch, const void* recs, hipStream_t stream) {
+hipError_t launch_sphere_lights_prepared(const LightLaunch& launch, const void* recs, hipStream_t stream, int sdf_filter) {
     const int rows = launch.row_end - launch.row_begin;
     if (rows <= 0 || launch.width <= 0) return hipSuccess;
     LightLaunch a = launch;
@@ -1298,6 +1307,17 @@ hipError_t launch_sphere_lights_prepared(const LightLaunch& launch, const void* 
     const dim3 grid(per_xcd_blocks * 8), block(kLightThreads);
     // anything but ADD / ADD: the BLEND instantiation of the same variant
     const bool blend = a.blend_color != ILM_LIGHT_BLEND_ADD || a.blend_alpha != ILM_LIGHT_BLEND_ADD;
+    // The field's FIXED8 filter (hlsl_math.hpp, kSdfFixed8): four instantiations -- the format x counting or plain -- of the narrow-binning
+    // kernel, for launches of one workgroup per tile in the fp32 model under ADD / ADD (api.hip plans and refuses so)
+    if (sdf_filter == ILM_SDF_FILTER_FIXED8) {
+        if (a.split > 1 || blend || a.blend_fp16 != 0 || a.light_count_ptr != nullptr) return hipErrorInvalidValue;
+        if (fp16 && stats) hipLaunchKernelGGL((sphere_lights_kernel<ILM_SDF_FP16 + kSdfFixed8, true, false>), grid, block, 0, stream, a, r, tiles_x, tiles_y, tile_count);
+        else if (fp16) hipLaunchKernelGGL((sphere_lights_kernel<ILM_SDF_FP16 + kSdfFixed8, false, false>), grid, block, 0, stream, a, r, tiles_x, tiles_y, tile_count);
+        else if (stats) hipLaunchKernelGGL((sphere_lights_kernel<ILM_SDF_UNORM16 + kSdfFixed8, true, false>), grid, block, 0, stream, a, r, tiles_x, tiles_y, tile_count);
+        else hipLaunchKernelGGL((sphere_lights_kernel<ILM_SDF_UNORM16 + kSdfFixed8, false, false>), grid, block, 0, stream, a, r, tiles_x, tiles_y, tile_count);
+        return hipGetLastError();
+    }
+    if (sdf_filter != ILM_SDF_FILTER_FP32) return hipErrorInvalidValue;
 #define ILM_LAUNCH_LIGHTS(F, S, W) do { \
         if (blend) hipLaunchKernelGGL((sphere_lights_kernel<F + kBlendVariant, S, W>), grid, block, 0, stream, a, r, tiles_x, tiles_y, tile_count); \
         else hipLaunchKernelGGL((sphere_lights_kernel<F, S, W>), grid, block, 0, stream, a, r, tiles_x, tiles_y, tile_count); } while (0)

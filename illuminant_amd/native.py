@@ -88,6 +88,8 @@ SYMBOLS = {
     "ilm_sdf_device_ptr": (_I, [_H, C.POINTER(_P)]),
     "ilm_sdf_mark_dirty": (_I, [_H, _I, _I]),
     "ilm_sdf_trace_info": (_I, [_H, C.POINTER(abi.SdfTraceInfo)]),
+    "ilm_sdf_set_filter": (_I, [_H, _I]),
+    "ilm_sdf_get_filter": (_I, [_H, C.POINTER(_I)]),
     "ilm_sdf_render_slices": (_I, [_H, _H, _P, _P, _I, _P, _I, _P, _I, _P, _I]),
     "ilm_gbuffer_create": (_I, [_H, _I, _I, _I, C.POINTER(_H)]),
     "ilm_gbuffer_upload": (_I, [_H, _P]),
@@ -526,6 +528,17 @@ class DistanceFieldTexture:
         info = abi.SdfTraceInfo()
         check(lib().ilm_sdf_trace_info(self.handle, C.byref(info)))
         return info
+
+    def set_filter(self, bits):
+        """ilm_sdf_set_filter: abi.SDF_FILTER_FP32 (0, the default) or abi.SDF_FILTER_FIXED8 (8 fraction bits); read at the next launch."""
+        check(lib().ilm_sdf_set_filter(self.handle, int(bits)))
+
+    @property
+    def filter(self):
+        """ilm_sdf_get_filter: the fraction bits of the field's bilinear filter (0: fp32 weights)."""
+        bits = C.c_int32(-1)
+        check(lib().ilm_sdf_get_filter(self.handle, C.byref(bits)))
+        return bits.value
 
     def download(self):
         """ilm_sdf_download: the atlas as (H, W, 4) uint16."""

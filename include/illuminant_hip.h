@@ -38,7 +38,8 @@ extern "C" {
  * + ilm_ctx_set_projector_texture_mips (a projector texture's mip chain, fetched trilinearly at the light's mip bias);
  * + ilm_ctx_set_light_blend_function, ILM_LIGHT_BLEND_* (subtractive, max and min light groups: LightSource.BlendMode);
  * + ilm_resolve_lighting_scaled, ILM_FILTER_* (the resolve onto a target of another size: RenderScale != 1);
- * + ilm_resolve_lighting_lut / IlmLUTBlending (the LUT-blended resolve over a dark and a bright colour LUT).
+ * + ilm_resolve_lighting_lut / IlmLUTBlending (the LUT-blended resolve over a dark and a bright colour LUT);
+ * + ilm_sdf_set_filter, ilm_sdf_get_filter, ILM_SDF_FILTER_* (a fixed-point bilinear filter mode of the distance-field sampler).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -582,6 +583,46 @@ typedef struct IlmSdfTraceInfo {
     int32_t  Reserved;
 } IlmSdfTraceInfo;
 int32_t ilm_sdf_trace_info(IlmHandle sdf, IlmSdfTraceInfo* out);
+
+/* The field's bilinear filter: a per-texture sampler state, like a D3D sampler state -- a property of the texture, not of the context.
+ *
+ * Why: the reference reads the atlas through a hardware LINEAR sampler (DistanceFieldCommon.fxh:274-281, :335).  A hardware sampler
+ * converts the texel-space coordinate to fixed point before it blends; eight fractional bits are the Direct3D 10+ floor, and
+ * D3D9-class hardware is no finer.  The library's parity criterion is defined against fp32 weights (oracle/ilm_oracle.h), and the
+ * sampled value feeds coneTrace's loop exit (ConeTrace.fxh:162-170), which is discontinuous in it.
+ *
+ *   ILM_SDF_FILTER_FP32   (default) the two bilinear fractions are fp32 values: sampleDistanceFieldEx as ilm_sdf_sample states it.
+ *   ILM_SDF_FILTER_FIXED8 the two bilinear fractions carry 8 fractional bits.
+ *
+ * MODEL.  FIXED8 changes exactly one thing in sampleDistanceFieldEx as this library states it.  Everything up to and including
+ *     fx = x - floor(x),  fy = y - floor(y)          (x, y: the texel-space coordinates, texel centres at +0.5)
+ * is the FP32 arithmetic, so the four taps are the same taps.  Then, before the first lerp,
+ *     fx = rintf(fx * 256.0f) * (1.0f / 256.0f),     fy likewise.
+ * Both products are exact.  rintf rounds half to even (v_rndne_f32): 0.5 / 256 -> 0, 1.5 / 256 -> 2 / 256.  The lerp stays
+ * fma(t, b - a, a).  The z blend (slice_position - floor(slice_position)) is shader arithmetic in the reference and is NOT quantised.
+ * The clamp to the volume, the distance to the volume, the decode and the NaN rules are unchanged.
+ *
+ * DEFINED DEVIATION.  A fraction of at least 255.5 / 256 becomes the weight 1.0; the taps do NOT move to the next texel.  A true
+ * fixed-point sampler would carry into the next texel, which differs from the weight 1.0 by at most the last ulp of one lerp.  The
+ * reference text names no fraction width: FIXED8 is a model of a sampler this library cannot run, not the reference's measured behaviour.
+ *
+ * ilm_sdf_set_filter: the handle is looked up first (ILM_ERR_INVALID_HANDLE); a value other than 0 or 8 returns
+ * ILM_ERR_INVALID_ARGUMENT and the state stays as it was.  The state is read when a kernel is launched: setting it neither synchronises
+ * nor touches the atlas or the cell arrays (they hold taps, not weights; IlmSdfTraceInfo.CellRebuilds does not move).
+ *
+ * Honoured by ilm_sdf_sample, ilm_debug_sdf_sample_inside (both sampler forms) and ilm_render_sphere_lights -- counting and plain, with and
+ * without a G-buffer, every atlas and lightmap format.  A FIXED8 sphere launch is served by one workgroup per tile and composes only
+ * with ILM_BLEND_FP32_ACCUMULATE and the ADD / ADD blend functions: under the fp16-per-light model or another blend function the
+ * call is refused.
+ * Not built: every other consumer of a field.  While the field's filter is not 0, ilm_render_particle_lights, ilm_render_light_probes,
+ * the directional, line, projector and volumetric passes, ilm_group_render_sphere_lights, ilm_visualize_distance_field,
+ * ilm_system_set_distance_field, ilm_system_step with the collision update and ilm_engine_step_batch with such an item return
+ * ILM_ERR_INVALID_ARGUMENT with a message that names the filter; the target is untouched and nothing is queued.  The collision update
+ * and the other light kinds under the filter, fraction widths other than 8 and the carry into the next texel are follow-ups. */
+#define ILM_SDF_FILTER_FP32    0   /* default: fp32 weights */
+#define ILM_SDF_FILTER_FIXED8  8   /* the two bilinear fractions carry 8 fractional bits */
+int32_t ilm_sdf_set_filter(IlmHandle sdf, int32_t fraction_bits);
+int32_t ilm_sdf_get_filter(IlmHandle sdf, int32_t* out_fraction_bits);
 
 /* ---- distance field generation ------------------------------ */
 

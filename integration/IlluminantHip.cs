@@ -38,6 +38,8 @@ namespace Squared.Illuminant.Native {
         public const int OK = 0;
         public const int RANDOMNESS_HEIGHT = 653;
         public const int RANDOMNESS_WIDTH = 807;
+        public const int SDF_FILTER_FIXED8 = 8;
+        public const int SDF_FILTER_FP32 = 0;
         public const int STEP_COUNT_LIVE = 1;
         public const int STEP_KERNEL_BATCH = 5;
         public const int STEP_KERNEL_INTERPRETER = 1;
@@ -611,6 +613,8 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_sdf_device_ptr (ulong sdf, void** outPtr);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_sdf_mark_dirty (ulong sdf, int firstVirtualSlice, int sliceCount);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_sdf_trace_info (ulong sdf, IlmSdfTraceInfo* @out);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_sdf_set_filter (ulong sdf, int fractionBits);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_sdf_get_filter (ulong sdf, int* outFractionBits);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_sdf_render_slices (ulong sdf, ulong clearSource, IlmDistanceFieldRenderDesc* desc, int* firstVirtualSlices, int tripletCount, IlmObstruction* obstructions, int obstructionCount, IlmHeightVolume* volumes, int volumeCount, float* polygonXy, int polygonVertexCount);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_gbuffer_create (ulong ctx, int width, int height, int format, ulong* outGbuffer);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_gbuffer_upload (ulong gbuffer, void* texels);
