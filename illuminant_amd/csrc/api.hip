@@ -3208,16 +3208,16 @@ int32_t ilm_render_particle_lights(IlmHandle hctx, IlmHandle hsystem, const int3
     return ILM_OK;
 }
 
-int32_t ilm_render_light_probes(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count,
-                                const IlmFloat4* probe_positions, const IlmFloat4* probe_normals, int32_t probe_count,
-                                const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle hsdf, IlmFloat4* out_values) {
-    ILM_TRACE_RANGE("ilm_render_light_probes");
-    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
-    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+// What the three probe entry points share once each has looked its context up: the checks, the pinned block, the kind's records and
+// its kernels, the read-back.  The kinds differ in the vertex layout they are handed, the record preparation and the probe kernel.
+enum ProbeKind { kProbeSphere, kProbeDirectional, kProbeLine };
+static int32_t render_probes(Ctx* c, ProbeKind kind, const char* who, const IlmLightVertex* lights, int32_t light_count,
+                             const IlmFloat4* probe_positions, const IlmFloat4* probe_normals, int32_t probe_count,
+                             const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle hsdf, IlmFloat4* out_values) {
     Sdf* f = nullptr;
     if (hsdf) { f = from_handle<Sdf>(hsdf, kMagicSdf); if (!f) return fail(ILM_ERR_INVALID_HANDLE, "not a distance field handle"); }
     if (f && f->ctx != c) return fail(ILM_ERR_INVALID_ARGUMENT, "resources belong to another context");
-    { char why[256]; if (field_filter_unsupported(f, "ilm_render_light_probes", why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
+    { char why[256]; if (field_filter_unsupported(f, who, why, sizeof(why))) return fail(ILM_ERR_INVALID_ARGUMENT, "%s", why); }
     if (!env || !df) return fail(ILM_ERR_INVALID_ARGUMENT, "NULL argument");
     if (light_count < 0 || (light_count > 0 && !lights)) return fail(ILM_ERR_INVALID_ARGUMENT, "bad light array");
     if (probe_count < 0 || (probe_count > 0 && (!probe_positions || !probe_normals || !out_values))) return fail(ILM_ERR_INVALID_ARGUMENT, "bad probe arrays");
@@ -3235,13 +3235,26 @@ int32_t ilm_render_light_probes(IlmHandle hctx, const IlmLightVertex* lights, in
     int slot = -1;
     int32_t rc = upload_small_begin(c, block_bytes, reinterpret_cast<void**>(&block), &slot);
     if (rc != ILM_OK) return rc;
-    if (light_count > 0) memcpy(block, lights, sizeof(IlmLightVertex) * (size_t)light_count);
+    if (light_count > 0 && kind != kProbeLine) memcpy(block, lights, sizeof(IlmLightVertex) * (size_t)light_count);
+    // LineLightProbe.fx:9-48 is SphereLightProbe's shader at the line's start point: the line vertex becomes the sphere vertex of the
+    // four members that shader reads (no specular colour, no shadow filter, no ramp offset), and the sphere preparation does the rest
+    for (int i = 0; i < light_count && kind == kProbeLine; i++) {
+        IlmLightVertex v = {};
+        v.LightPosition1 = lights[i].LightPosition1; v.LightPosition1.w = 0.0f;
+        v.LightPosition2 = v.LightPosition3 = v.LightPosition1;
+        v.Color1 = lights[i].Color1;
+        v.LightProperties = lights[i].LightProperties; v.MoreLightProperties = lights[i].MoreLightProperties;
+        v.EvenMoreLightProperties.x = -1.0f;
+        memcpy(block + sizeof(IlmLightVertex) * (size_t)i, &v, sizeof(v));
+    }
     memcpy(block + off_pos, probe_positions, sizeof(float4) * (size_t)probe_count);
     memcpy(block + off_nrm, probe_normals, sizeof(float4) * (size_t)probe_count);
     void* dv = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dv, block, 0));
     const char* in = static_cast<const char*>(dv);
-    if (light_count > 0)
+    if (light_count > 0 && kind == kProbeDirectional)
+        HIP_TRY(launch_prepare_directional_lights(reinterpret_cast<const IlmLightVertex*>(in), light_count, *env, *df, c->d_recs.p, c->main()));
+    else if (light_count > 0)
         HIP_TRY(launch_prepare_lights(reinterpret_cast<const IlmLightVertex*>(in), light_count, *env, *df, make_sdf_view(f, df), c->d_recs.p, c->main()));
     const float4* d_pos = reinterpret_cast<const float4*>(in + off_pos);
     const float4* d_nrm = reinterpret_cast<const float4*>(in + off_nrm);
@@ -3254,13 +3267,47 @@ int32_t ilm_render_light_probes(IlmHandle hctx, const IlmLightVertex* lights, in
         if (try_reserve(c, c->d_probe_pairs, sizeof(float4) * pair_count, sizeof(float4) * (pair_count < 65536 ? 65536 : pair_count + pair_count / 2)) == hipSuccess)
             d_pairs = c->d_probe_pairs.as<float4>();
     }
-    HIP_TRY(launch_light_probes(c->d_recs.p, light_count, d_pos, d_nrm, probe_count, *env, *df, make_sdf_view(f, df),
-                                RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h }, d_val, d_pairs, c->main()));
+    // (the line kind reads no ramp: the reference has no LineLightProbeWithDistanceRamp)
+    const RampView ramp = (kind == kProbeLine) ? RampView{ nullptr, 0, 0 } : RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h };
+    if (kind == kProbeDirectional)
+        HIP_TRY(launch_directional_light_probes(c->d_recs.p, light_count, d_pos, d_nrm, probe_count, *df, make_sdf_view(f, df), ramp, d_val, d_pairs, c->main()));
+    else
+        HIP_TRY(launch_light_probes(c->d_recs.p, light_count, d_pos, d_nrm, probe_count, *env, *df, make_sdf_view(f, df), ramp, d_val, d_pairs, c->main()));
     rc = staged_small_done(c, slot);
     if (rc != ILM_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->main()));
     memcpy(out_values, block + off_val, sizeof(float4) * (size_t)probe_count);
     return ILM_OK;
+}
+
+int32_t ilm_render_light_probes(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count,
+                                const IlmFloat4* probe_positions, const IlmFloat4* probe_normals, int32_t probe_count,
+                                const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle hsdf, IlmFloat4* out_values) {
+    ILM_TRACE_RANGE("ilm_render_light_probes");
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    return render_probes(c, kProbeSphere, "ilm_render_light_probes", lights, light_count, probe_positions, probe_normals, probe_count, env, df, hsdf, out_values);
+}
+
+int32_t ilm_render_directional_light_probes(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count,
+                                            const IlmFloat4* probe_positions, const IlmFloat4* probe_normals, int32_t probe_count,
+                                            const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle hsdf, IlmFloat4* out_values) {
+    ILM_TRACE_RANGE("ilm_render_directional_light_probes");
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    // (Bounds are not read -- DirectionalLight.fx:175 -- so no light is refused for them, unlike ilm_render_directional_lights)
+    return render_probes(c, kProbeDirectional, "ilm_render_directional_light_probes", lights, light_count, probe_positions, probe_normals, probe_count, env, df,
+                         hsdf, out_values);
+}
+
+int32_t ilm_render_line_light_probes(IlmHandle hctx, const IlmLightVertex* lights, int32_t light_count,
+                                     const IlmFloat4* probe_positions, const IlmFloat4* probe_normals, int32_t probe_count,
+                                     const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle hsdf, IlmFloat4* out_values) {
+    ILM_TRACE_RANGE("ilm_render_line_light_probes");
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    return render_probes(c, kProbeLine, "ilm_render_line_light_probes", lights, light_count, probe_positions, probe_normals, probe_count, env, df, hsdf,
+                         out_values);
 }
 
 // Compacts the live particles of the first chunk_count chunks into draw-call records in c->d_rb (device) and copies the first

@@ -1616,6 +1616,95 @@ hipError_t launch_directional_lights_prepared(const LightLaunch& a, const void* 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Directional light probes -- DirectionalLightProbePixelShader / ...WithRampPixelShader, DirectionalLight.fx:163-219: the core of
+// the frame pass (shade_directional) on a Pixel built from the probe.  The launch has the shape of light_probes_kernel: one wave per
+// (block of 64 probes, light), the pair's contribution to scratch [light][probe], light_probes_sum_kernel adds them in light order;
+// `pairs` = nullptr: the one-kernel form, one lane per probe walking every record.  The records are the frame pass's
+// (prepare_directional_lights_kernel); their footprint is not read (the probe vertex shader covers the target, :39-50, "FIXME: Clip to
+// region" :175).
+// ---------------------------------------------------------------------------------------------
+template <int FMT>
+ILM_DEV bool probe_directional(const float4 pp, const float4 pn, DirectionalRec L, const TraceField& field, bool have_sdf, const RampView& ramp,
+                               float& opacity) {
+    Pixel P;
+    P.shaded = xyz(pp); P.normal = xyz(pn); P.origin_x = 0; P.origin_y = 0;
+    P.fullbright = false;
+    P.start_inside = false;
+    // lightProperties.x *= enableShadows (a float here, not the G-buffer's flag); moreLightProperties.x = .w = 0: no AO (:182-183); the
+    // probe shaders do not take evenMoreLightProperties: no shadow filter
+    L.casts_shadows *= pn.w;
+    P.enable_shadows = true;
+    L.ao_radius = 0.0f; L.ao_opacity = 0.0f;
+    L.shadow_filter = -1.0f;
+    LightStats st;
+    return shade_directional<FMT, false>(P, L, field, have_sdf, ramp, st, opacity);
+}
+
+template <int FMT>
+__global__ __launch_bounds__(64) void directional_light_probes_kernel(const DirectionalRec* __restrict__ recs, int light_count,
+                                                                       const float4* __restrict__ probe_positions, const float4* __restrict__ probe_normals,
+                                                                       int probe_count, IlmDistanceFieldUniforms df, SdfView sdf, RampView ramp,
+                                                                       float4* __restrict__ values, float4* __restrict__ pairs) {
+    const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    const bool valid = i < probe_count;
+    const float4 pp = valid ? probe_positions[i] : mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 pn = valid ? probe_normals[i] : mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    // sampleLightProbeBuffer, LightCommon.fxh:233-254
+    const float probe_opacity = pp.w;
+    const bool have_sdf = (sdf.texels != nullptr) && (df.Extent.x > 0.0f);
+    TraceSdfView trace_sdf;                                       // the general sampler, no cell array
+    static_cast<SdfView&>(trace_sdf) = sdf;
+    trace_sdf.cells = nullptr; trace_sdf.cells_bytes = 0; trace_sdf.slice_w = 0; trace_sdf.slice_h = 0;
+    const InsideConsts no_table = {};
+    const TraceField field = { df, trace_sdf, no_table, nullptr };
+    if (pairs != nullptr) {
+        const int k = (int)blockIdx.y;                            // this wave's light
+        float opacity = 0.0f;
+        bool lit = false;
+        if (valid && probe_opacity > 0.0f)
+            lit = probe_directional<FMT>(pp, pn, recs[k], field, have_sdf, ramp, opacity);
+        if (valid) {
+            const DirectionalRec& L = recs[k];
+            pairs[(size_t)k * (size_t)probe_count + (size_t)i] =
+                lit ? mk4((L.col_r * opacity) * probe_opacity, (L.col_g * opacity) * probe_opacity, (L.col_b * opacity) * probe_opacity, 1.0f) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+        return;
+    }
+    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+    for (int k = 0; k < light_count; k++) {
+        const DirectionalRec& L = recs[k];
+        if (!(valid && probe_opacity > 0.0f))
+            continue;
+        float opacity;
+        if (!probe_directional<FMT>(pp, pn, L, field, have_sdf, ramp, opacity))
+            continue;
+        acc_r += (L.col_r * opacity) * probe_opacity;
+        acc_g += (L.col_g * opacity) * probe_opacity;
+        acc_b += (L.col_b * opacity) * probe_opacity;
+        acc_a += 1.0f;
+    }
+    if (valid)
+        values[i] = mk4(acc_r, acc_g, acc_b, acc_a);
+}
+
+hipError_t launch_directional_light_probes(const void* recs, int light_count, const float4* probe_positions, const float4* probe_normals, int probe_count,
+                                           const IlmDistanceFieldUniforms& df, const SdfView& sdf, const RampView& ramp, float4* values, float4* pairs,
+                                           hipStream_t stream) {
+    if (probe_count <= 0) return hipSuccess;
+    const bool by_pair = (pairs != nullptr) && (light_count > 1) && (light_count <= 65535);
+    const dim3 grid((unsigned)((probe_count + 63) / 64), by_pair ? (unsigned)light_count : 1u), block(64);
+    const DirectionalRec* r = reinterpret_cast<const DirectionalRec*>(recs);
+    float4* p = by_pair ? pairs : nullptr;
+    if (sdf.format == ILM_SDF_FP16)
+        hipLaunchKernelGGL(directional_light_probes_kernel<ILM_SDF_FP16>, grid, block, 0, stream, r, light_count, probe_positions, probe_normals, probe_count, df, sdf, ramp, values, p);
+    else
+        hipLaunchKernelGGL(directional_light_probes_kernel<ILM_SDF_UNORM16>, grid, block, 0, stream, r, light_count, probe_positions, probe_normals, probe_count, df, sdf, ramp, values, p);
+    if (by_pair)
+        hipLaunchKernelGGL(light_probes_sum_kernel, dim3((unsigned)((probe_count + 63) / 64)), block, 0, stream, p, light_count, probe_count, values);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Projector lights -- technique ProjectorLight, ProjectorLight.fx:14-56 over ProjectorLightCore.fxh:20-151,290-302, drawn by
 // RenderProjectorLightSource (LightingRenderer.cs:1386-1446) as one quad per light: the whole frame for a wrapping light, the bounding
 // box of the projector's volume for a clamped one (ProjectorLightVertexShader, ProjectorLightCore.fxh:251-278).  The frame of the

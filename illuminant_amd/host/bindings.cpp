@@ -667,6 +667,8 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("PerChannel", &LUTBlendingConfiguration::PerChannel).def_readwrite("LUTOnly", &LUTBlendingConfiguration::LUTOnly)
         .def_readwrite("DarkLevel", &LUTBlendingConfiguration::DarkLevel).def_readwrite("NeutralBandSize", &LUTBlendingConfiguration::NeutralBandSize)
         .def_readwrite("BrightLevel", &LUTBlendingConfiguration::BrightLevel);
+    py::enum_<LightKind>(m, "LightKind").value("Sphere", LightKind::Sphere).value("Directional", LightKind::Directional).value("Line", LightKind::Line)
+        .value("Projector", LightKind::Projector).value("Volumetric", LightKind::Volumetric);
     py::class_<LightingRenderer>(m, "LightingRenderer")
         .def(py::init([](DeviceContext& ctx, const RendererConfiguration& cfg, LightingEnvironment* env, uintptr_t externalLightmap) {
             return new LightingRenderer(ctx, cfg, env, reinterpret_cast<void*>(externalLightmap));
@@ -754,6 +756,7 @@ PYBIND11_MODULE(_host, m) {
            py::arg("albedoTextureRegion") = py::none(), py::arg("albedoSamplerState") = (int)ILM_FILTER_LINEAR,
            py::arg("lightmapSamplerState") = (int)ILM_FILTER_LINEAR, py::arg("uvOffset") = std::vector<float>{0, 0}, py::arg("hdr") = py::none(),
            py::arg("rowBegin") = 0, py::arg("rowEnd") = -1, py::arg("lutBlending") = py::none())
+        .def_property("ProbeLightKinds", &LightingRenderer::GetProbeLightKinds, &LightingRenderer::SetProbeLightKinds)
         .def_property_readonly("Probes", [](LightingRenderer& r) -> LightProbeCollection& { return r.Probes; }, py::return_value_policy::reference_internal)
         .def_static("PackParticleLightBytes", [](const ParticleLightSource& pls, bool haveDF) {
             auto p = LightingRenderer::PackParticleLight(pls, haveDF); return py::bytes((const char*)&p, sizeof(p)); })

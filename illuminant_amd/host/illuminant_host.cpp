@@ -1478,6 +1478,24 @@ const LightKindInfo kLightKinds[(size_t)LightKind::Count] = {
     { "volumetric", ilm_render_volumetric_lights, false, false },       // no ramp technique either
 };
 
+// ... and about its probe technique: the three ilm_render_*_light_probes entries share one signature.  render == nullptr: the technique
+// is not built, for the reason `refusal` gives (SetProbeLightKinds)
+typedef int32_t (*RenderProbesEntry)(IlmHandle, const IlmLightVertex*, int32_t, const IlmFloat4*, const IlmFloat4*, int32_t, const IlmEnvironment*,
+                                     const IlmDistanceFieldUniforms*, IlmHandle, IlmFloat4*);
+struct ProbeKindInfo {
+    RenderProbesEntry render;
+    bool bindsRamp;            // the state's texture is the ramp of its probe technique; false: the entry reads no ramp
+    const char* refusal;
+};
+const ProbeKindInfo kProbeKinds[(size_t)LightKind::Count] = {
+    { ilm_render_light_probes, true, nullptr },
+    { ilm_render_directional_light_probes, true, nullptr },
+    { ilm_render_line_light_probes, false, nullptr },                   // no LineLightProbeWithDistanceRamp technique
+    { nullptr, false, "ProjectorLightProbe.fx's pixel shader reads a projector origin (TEXCOORD6) that its vertex shader never writes, so the "
+                      "reference's text does not define the result" },
+    { nullptr, false, "LoadMaterials.cs loads VolumetricLightProbe, but the reference tree holds no VolumetricLightProbe.fx that defines it" },
+};
+
 void AddStats(IlmRenderStats* total, const IlmRenderStats& part) {
     if (!total) return;
     total->SdfSamples += part.SdfSamples; total->PixelLightPairs += part.PixelLightPairs; total->TracedPairs += part.TracedPairs;
@@ -1487,17 +1505,17 @@ void AddStats(IlmRenderStats* total, const IlmRenderStats& part) {
 // RenderLighting, LightingRenderer.cs:917-1191 (sphere, directional, line, projector, volumetric and particle lights)
 void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int rowEnd, IlmRenderStats* stats) {
     if (rowEnd < 0) rowEnd = Configuration.RenderHeight;
-    // the probe techniques of these kinds (DirectionalLightProbe*, ProjectorLightProbe.fx, LineLightProbe.fx, VolumetricLightProbe.fx) are
-    // not built: refuse rather than leave the lights out of the probes
+    // a kind outside ProbeLightKinds (directional and line lights can be added to it; the probe techniques of projector and volumetric
+    // lights are not built): refuse rather than leave the lights out of the probes
     auto refuseWithProbes = [&](const auto& lights, LightKind kind) {
         for (const auto& l : lights)
             if (l.Enabled)
                 throw InvalidOperationException(std::string("RenderLighting: ") + kLightKinds[(size_t)kind].name + " lights do not reach light probes yet");
     };
     if (Probes.Count() > 0) {
-        refuseWithProbes(Environment->DirectionalLights, LightKind::Directional);
+        if (!probeLightKinds.count(LightKind::Directional)) refuseWithProbes(Environment->DirectionalLights, LightKind::Directional);
         refuseWithProbes(Environment->ProjectorLights, LightKind::Projector);
-        refuseWithProbes(Environment->LineLights, LightKind::Line);
+        if (!probeLightKinds.count(LightKind::Line)) refuseWithProbes(Environment->LineLights, LightKind::Line);
         refuseWithProbes(Environment->VolumetricLights, LightKind::Volumetric);
     }
 
@@ -1686,6 +1704,17 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
         UpdateLightProbes(intensityScale);
 }
 
+void LightingRenderer::SetProbeLightKinds(const std::set<LightKind>& kinds) {
+    for (const LightKind kind : kinds) {
+        if ((size_t)kind >= (size_t)LightKind::Count) throw InvalidOperationException("ProbeLightKinds: not a light kind");
+        if (!kProbeKinds[(size_t)kind].render)
+            throw InvalidOperationException(std::string("ProbeLightKinds: ") + kLightKinds[(size_t)kind].name + " lights cannot reach light probes: " +
+                                            kProbeKinds[(size_t)kind].refusal);
+    }
+    if (!kinds.count(LightKind::Sphere)) throw InvalidOperationException("ProbeLightKinds: sphere lights cannot be removed");
+    probeLightKinds = kinds;
+}
+
 // _LightBatchSetup binds the group's RampTexture (:764-766); the native layer keeps one per context
 void LightingRenderer::BindRamp(const RampTexture* ramp) {
     if (ramp == boundRamp) return;
@@ -1739,18 +1768,23 @@ void LightingRenderer::UpdateLightProbes(float intensityScale) {
     const IlmDistanceFieldUniforms dfu = GetDistanceFieldUniforms(Configuration.DefaultQuality);
     // the light vertices of this frame were packed with intensityScale folded into Color1.a (RenderSphereLightSource, :1203); every
     // render state draws its lights onto the probe target with its own probe material (with or without a ramp, :159-164): summed here
-    const std::vector<LightRenderState>& sphereStates = renderStates[(size_t)LightKind::Sphere];
-    for (size_t g = 0; g < sphereStates.size(); g++) {
-        const LightRenderState& state = sphereStates[g];
-        if (state.vertices.empty() && g > 0) continue;
-        BindRamp(state.texture);
-        std::vector<IlmFloat4> part((size_t)n);
-        const IlmDistanceFieldUniforms gdfu = state.quality ? GetDistanceFieldUniforms(*state.quality) : dfu;
-        ThrowIfFailed(ilm_render_light_probes(Context.Handle(), state.vertices.empty() ? nullptr : state.vertices.data(), (int32_t)state.vertices.size(),
-                                              positions.data(), normals.data(), n, &env, &gdfu, Field ? Field->Texture() : 0, part.data()));
-        for (int i = 0; i < n; i++) {
-            values[(size_t)i].x += part[(size_t)i].x; values[(size_t)i].y += part[(size_t)i].y;
-            values[(size_t)i].z += part[(size_t)i].z; values[(size_t)i].w += part[(size_t)i].w;
+    // -- the kinds of ProbeLightKinds, in the order RenderLighting draws them; the sums are added in fp32 here
+    for (size_t kind = 0; kind < renderStates.size(); kind++) {
+        if (!probeLightKinds.count((LightKind)kind)) continue;
+        const ProbeKindInfo& info = kProbeKinds[kind];
+        const std::vector<LightRenderState>& states = renderStates[kind];
+        for (size_t g = 0; g < states.size(); g++) {
+            const LightRenderState& state = states[g];
+            if (state.vertices.empty() && g > 0) continue;
+            if (info.bindsRamp) BindRamp(state.texture);
+            std::vector<IlmFloat4> part((size_t)n);
+            const IlmDistanceFieldUniforms gdfu = state.quality ? GetDistanceFieldUniforms(*state.quality) : dfu;
+            ThrowIfFailed(info.render(Context.Handle(), state.vertices.empty() ? nullptr : state.vertices.data(), (int32_t)state.vertices.size(),
+                                      positions.data(), normals.data(), n, &env, &gdfu, Field ? Field->Texture() : 0, part.data()));
+            for (int i = 0; i < n; i++) {
+                values[(size_t)i].x += part[(size_t)i].x; values[(size_t)i].y += part[(size_t)i].y;
+                values[(size_t)i].z += part[(size_t)i].z; values[(size_t)i].w += part[(size_t)i].w;
+            }
         }
     }
     BindRamp(nullptr);

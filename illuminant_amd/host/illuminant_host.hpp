@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <memory>
 #include <optional>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -1115,8 +1116,15 @@ public:
     IlmEnvironment GetEnvironmentUniforms() const;
     // the LightVertex stream of the last RenderLighting, in draw order (LightTypeRenderState.LightVertices)
     const std::vector<IlmLightVertex>& PackedLightVertices() const { return vertices; }
+    // The light kinds whose render states UpdateLightProbes draws onto the probes; RenderLighting refuses a frame that has probes and an
+    // enabled light of any other kind.  A switch of this mirror, not a reference member (which is why it is not on RendererConfiguration):
+    // the reference draws every kind (LightingRenderer.LightProbes.cs:63-84).  Default {Sphere}; Sphere cannot be removed; Projector and
+    // Volumetric cannot be added (their probe techniques are not defined by the reference's text): InvalidOperationException.
+    const std::set<LightKind>& GetProbeLightKinds() const { return probeLightKinds; }
+    void SetProbeLightKinds(const std::set<LightKind>& kinds);
 
 private:
+    std::set<LightKind> probeLightKinds{ LightKind::Sphere };
     void UpdateLightProbes(float intensityScale);   // LightingRenderer.LightProbes.cs:49-150 (synchronous read-back)
     void AutoInvalidateDistanceField();
     int RenderDistanceFieldPartition(int dynamicFlagFilter /* -1 = null */);

@@ -108,6 +108,8 @@ SYMBOLS = {
     "ilm_render_projector_lights": (_I, [_H, _P, _I, _P, _P, _H, _H, _P, _H, _I, _I, _P]),
     "ilm_render_particle_lights": (_I, [_H, _H, _P, _I, _P, _P, _P, _H, _H, _H, _I, _I, _P]),
     "ilm_render_light_probes": (_I, [_H, _P, _I, _P, _P, _I, _P, _P, _H, _P]),
+    "ilm_render_directional_light_probes": (_I, [_H, _P, _I, _P, _P, _I, _P, _P, _H, _P]),
+    "ilm_render_line_light_probes": (_I, [_H, _P, _I, _P, _P, _I, _P, _P, _H, _P]),
     "ilm_system_readback": (_I, [_H, _P, _I, _P, _P, _I, C.POINTER(_I)]),
     "ilm_system_readback_view": (_I, [_H, _P, _I, _P, C.POINTER(_P), C.POINTER(_I)]),
     "ilm_render_particles": (_I, [_H, _P, _I, _P, _H, _P]),
@@ -966,16 +968,30 @@ def render_particle_lights(ctx, system, params, env, df, gbuffer, sdf, lightmap,
     return stats
 
 
-def render_light_probes(ctx, lights, probe_positions, probe_normals, env, df, sdf):
-    """ilm_render_light_probes: (n, 4) float32 probe values (rgb sum, contributing light count)."""
+def _render_probes(entry, ctx, lights, probe_positions, probe_normals, env, df, sdf):
     n = len(lights) if lights is not None else 0
     pp = np.ascontiguousarray(probe_positions, dtype=np.float32).reshape(-1, 4)
     pn = np.ascontiguousarray(probe_normals, dtype=np.float32).reshape(-1, 4)
     assert pp.shape == pn.shape
     out = np.zeros_like(pp)
-    check(lib().ilm_render_light_probes(ctx.handle, C.cast(lights, C.c_void_p) if n else None, n, _ptr(pp), _ptr(pn), pp.shape[0],
-                                        _byref(env), _byref(df), sdf.handle if sdf is not None else abi.Handle(0), _ptr(out)))
+    check(entry(ctx.handle, C.cast(lights, C.c_void_p) if n else None, n, _ptr(pp), _ptr(pn), pp.shape[0],
+                _byref(env), _byref(df), sdf.handle if sdf is not None else abi.Handle(0), _ptr(out)))
     return out
+
+
+def render_light_probes(ctx, lights, probe_positions, probe_normals, env, df, sdf):
+    """ilm_render_light_probes: (n, 4) float32 probe values (rgb sum, contributing light count)."""
+    return _render_probes(lib().ilm_render_light_probes, ctx, lights, probe_positions, probe_normals, env, df, sdf)
+
+
+def render_directional_light_probes(ctx, lights, probe_positions, probe_normals, env, df, sdf):
+    """ilm_render_directional_light_probes: lights packed as RenderDirectionalLightSource packs them; values as render_light_probes."""
+    return _render_probes(lib().ilm_render_directional_light_probes, ctx, lights, probe_positions, probe_normals, env, df, sdf)
+
+
+def render_line_light_probes(ctx, lights, probe_positions, probe_normals, env, df, sdf):
+    """ilm_render_line_light_probes: lights packed as RenderLineLightSource packs them; values as render_light_probes."""
+    return _render_probes(lib().ilm_render_line_light_probes, ctx, lights, probe_positions, probe_normals, env, df, sdf)
 
 
 def resolve_lighting(src, dst, hdr, row_begin=0, row_end=None, albedo=None):

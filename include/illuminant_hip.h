@@ -845,7 +845,7 @@ int32_t ilm_render_sphere_lights(IlmHandle ctx,
  * visible pixel whose opacity is 0 still adds alpha 1.
  * Statistics: PixelLightPairs = pairs inside a footprint; TracedPairs = pairs with traceShadows (:73) and a bound field (sdf != 0,
  * Extent.x > 0); SdfSamples = ambient-occlusion + cone-trace samples.
- * Not built: the light-probe techniques (DirectionalLightProbe*), the group entry point. */
+ * The light-probe techniques (DirectionalLightProbe*) are ilm_render_directional_light_probes.  Not built: the group entry point. */
 int32_t ilm_render_directional_lights(IlmHandle ctx,
                                       const IlmLightVertex* lights, int32_t light_count,
                                       const IlmEnvironment* env,
@@ -902,7 +902,7 @@ int32_t ilm_render_directional_lights(IlmHandle ctx,
  * and the cone radius growth * position + 0.33 are fused multiply-adds, as in the other passes.
  * Statistics: PixelLightPairs = pairs that reach the opacity term (every pair of a pixel of the rows that is not fullbright);
  * TracedPairs = pairs that trace with a bound field (sdf != 0, Extent.x > 0); SdfSamples = the AO sample + 3 per loop iteration.
- * Not built: LineLightProbe, the group entry point, an in-volume fast loop. */
+ * LineLightProbe is ilm_render_line_light_probes.  Not built: the group entry point, an in-volume fast loop. */
 int32_t ilm_render_line_lights(IlmHandle ctx,
                                const IlmLightVertex* lights, int32_t light_count,
                                const IlmEnvironment* env,
@@ -986,8 +986,9 @@ int32_t ilm_ctx_set_projector_texture_mips(IlmHandle ctx, const IlmFloat4* texel
  * y padded by -/+ MaximumZ * ZToYMultiplier.  A light whose rectangle comes out NaN or inverted on an axis covers nothing.
  * Statistics: PixelLightPairs = pairs inside a footprint and the image; TracedPairs = pairs that trace with a bound field (sdf != 0,
  * Extent.x > 0); SdfSamples = ambient-occlusion + cone-trace samples.  Texture taps are not counted, with one level or many.
- * Not built: the light-probe technique (ProjectorLightProbe.fx), ProjectorLightWithoutDistanceField as a technique of its own (sdf == 0
- * is it), the group entry point. */
+ * Not built: the light-probe technique -- ProjectorLightProbe.fx's pixel shader reads projectorOrigin : TEXCOORD6 (:48), which its vertex
+ * shader never writes (:14-34), and the origin drives both the trace target and the normal term: the text does not define the result;
+ * ProjectorLightWithoutDistanceField as a technique of its own (sdf == 0 is it); the group entry point. */
 int32_t ilm_render_projector_lights(IlmHandle ctx,
                                     const IlmLightVertex* lights, int32_t light_count,
                                     const IlmEnvironment* env,
@@ -1071,7 +1072,8 @@ int32_t ilm_render_projector_lights(IlmHandle ctx,
  * NaN diffuse compares false and max(preTraceOpacity, NaN) = preTraceOpacity.
  * Statistics: PixelLightPairs = pairs inside a footprint and the image; TracedPairs = pairs with traceShadows and a bound field;
  * SdfSamples = the AO sample + every sample of every march.
- * Not built: VolumetricLightProbe, the group entry point, the dead intersection code. */
+ * Not built: VolumetricLightProbe -- Illuminant/LoadMaterials.cs:145-146 loads it, but the reference tree holds no
+ * VolumetricLightProbe.fx to define it; the group entry point; the dead intersection code. */
 int32_t ilm_render_volumetric_lights(IlmHandle ctx,
                                      const IlmLightVertex* lights, int32_t light_count,
                                      const IlmEnvironment* env,
@@ -1181,6 +1183,47 @@ int32_t ilm_render_light_probes(IlmHandle ctx, const IlmLightVertex* lights, int
                                 const IlmFloat4* probe_positions, const IlmFloat4* probe_normals, int32_t probe_count,
                                 const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle sdf,
                                 IlmFloat4* out_values);
+
+/* techniques DirectionalLightProbe / DirectionalLightProbeWithRamp (Illuminant/Shaders/DirectionalLight.fx:39-50,163-219) over
+ * DirectionalLightPixelCore (:52-93), drawn by UpdateLightProbes with the directional render state's probe material
+ * (LightingRenderer.LightProbes.cs:63-84).  Arguments and contract of ilm_render_light_probes: host arrays, probe_positions[i] =
+ * (position, opacity), probe_normals[i] = (normal or 0, enableShadows), out_values[i] = the sum over the lights in list order, alpha =
+ * the number of contributing lights; the call synchronises; light_count == 0 gives zeros; probe_count == 0 returns ILM_OK and touches
+ * nothing.  `lights` has the vertex layout of ilm_render_directional_lights.  Per (probe, light):
+ *   a probe with positions.w <= 0 receives nothing, no rgb and no alpha (sampleLightProbeBuffer discards, LightCommon.fxh:233-254);
+ *   LightProperties.x *= normals.w and MoreLightProperties.x = .w = 0 (:182-183): no ambient-occlusion sample; then the core as in the
+ *   frame pass;
+ *   the normal factor applies only when Color2.w >= 0.1 (LightCommon.fxh:227); a zero normal gives factor 1 (:154-165);
+ *   the trace runs iff the probe is visible, LightProperties.x * normals.w != 0, opacity >= 1 / 256 and the light is directed (:73);
+ *   it starts at position + 1.5 * normal (:81);
+ *   Bounds (LightPosition1.xy / LightPosition2.xy) are NOT read: the probe vertex shader covers the whole target (:48-49) and the pixel
+ *   shader carries "FIXME: Clip to region" (:175) -- a bounded light reaches every probe, and no bounds are refused;
+ *   the shadow filter is not consulted (the probe shaders do not take EvenMoreLightProperties, :163-169);
+ *   no opacity discard: a visible probe (x > -9999) with w > 0 adds alpha 1 even at opacity 0; an invisible one adds nothing (clip, :91);
+ *   value = Color1.rgb * Color1.a * opacity * positions.w (:185-189), one rounding per product, left to right;
+ *   while a ramp is bound (ilm_ctx_set_light_ramp, not 1 x 1) the technique is DirectionalLightProbeWithRamp: opacity =
+ *   SampleFromRamp(opacity) before the multiply by positions.w (:86-87,214-216).
+ * ilm_ctx_set_light_blend_function and ilm_ctx_set_lightmap_blend are ignored, as by ilm_render_light_probes (the probe target is
+ * forced to additive blending, LightProbes.cs:27).  A field whose filter is not ILM_SDF_FILTER_FP32 is refused
+ * (ILM_ERR_INVALID_ARGUMENT, out_values untouched). */
+int32_t ilm_render_directional_light_probes(IlmHandle ctx, const IlmLightVertex* lights, int32_t light_count,
+                                            const IlmFloat4* probe_positions, const IlmFloat4* probe_normals, int32_t probe_count,
+                                            const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle sdf,
+                                            IlmFloat4* out_values);
+
+/* technique LineLightProbe (Illuminant/Shaders/LineLightProbe.fx:9-48), with the arguments and contract of ilm_render_light_probes and
+ * the vertex layout of ilm_render_line_lights.  The shader is SphereLightProbe's at the line's start point ("FIXME: Why is this file
+ * sphere lights and not line lights", :4): the result is exactly what ilm_render_light_probes computes for sphere lights with centre
+ * LightPosition1.xyz, colour Color1, LightProperties and MoreLightProperties taken from the line vertex -- the line vertex is rewritten
+ * into that sphere vertex on the host and goes through the sphere preparation and kernels.  LightProperties.y, the ramp length, is 0 as
+ * RenderLineLightSource writes it (LightingRenderer.cs:1324) and is honoured as given: the distance falloff (distance - radius) / 0 is
+ * IEEE (+inf, -inf or NaN; saturate: 1, 0, 0), so such a light is full inside its radius and absent outside, and the cone growth is
+ * maxRadius / 16 (createTraceConfig's max(ramp length, 16)).  LightPosition2, Color2 and EvenMoreLightProperties are not read, and neither is a bound ramp (there is no
+ * LineLightProbeWithDistanceRamp).  A field whose filter is not ILM_SDF_FILTER_FP32 is refused as above. */
+int32_t ilm_render_line_light_probes(IlmHandle ctx, const IlmLightVertex* lights, int32_t light_count,
+                                     const IlmFloat4* probe_positions, const IlmFloat4* probe_normals, int32_t probe_count,
+                                     const IlmEnvironment* env, const IlmDistanceFieldUniforms* df, IlmHandle sdf,
+                                     IlmFloat4* out_values);
 
 /* ---- output side: particle read-back and lightmap resolve -------------------------------------- */
 
