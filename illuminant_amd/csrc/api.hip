@@ -2407,6 +2407,18 @@ int32_t ilm_debug_step_sdf_samples(IlmHandle hctx, int32_t enable, uint64_t* out
     return ILM_OK;
 }
 
+int32_t ilm_debug_step_regular_waves(IlmHandle hctx, int32_t enable, uint64_t* out_regular, uint64_t* out_selected) {
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->main()));        // main() first joins the second stream
+    unsigned long long value[2] = { 0, 0 };
+    HIP_TRY(step_regular_wave_counter(enable, value));
+    if (out_regular) *out_regular = (uint64_t)value[0];
+    if (out_selected) *out_selected = (uint64_t)value[1];
+    return ILM_OK;
+}
+
 int32_t ilm_debug_divide(IlmHandle hctx, const float* numerators, const float* denominators, int32_t count, float* out_fast, float* out_ieee) {
     Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
     if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");

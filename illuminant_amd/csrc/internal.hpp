@@ -131,6 +131,7 @@ constexpr int kCountLines = 17;      // per chunk in the step kernels' counter r
 // render-current under the key afterwards; left false by every other kernel (the records of the range must then be cleared).
 constexpr uint32_t kElideDerived = 1u;
 constexpr uint32_t kElideColor = 2u;     // (set by build_lean_step) the colour curves cannot produce a NaN factor: renderColor may be elided
+constexpr uint32_t kElideRotation = 4u;  // (set by build_lean_step) RotationFromLifeAndIndex[0] == 0 and the velocity rotation is 0: rd.y does not read a finite life
 hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide = 0u, bool* refreshed = nullptr);
 // ilm_engine_step_batch: lay a prepared StepLaunch out like launch_step does and return the batch kernel's variant for it (-1: the batch
 // kernel does not cover it -- a streaming range -- and launch_step runs it); *blocks = the blocks it takes in a launch's grid.
@@ -138,6 +139,7 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide 
 int step_batch_layout(StepLaunch& a, int* blocks);
 hipError_t launch_step_batch(int variant, const StepBatchItem* table, const int32_t* item_of_block, int blocks, hipStream_t stream);
 hipError_t step_sdf_sample_counter(int enable, unsigned long long* out);   // ilm_debug_step_sdf_samples
+hipError_t step_regular_wave_counter(int enable, unsigned long long out[2]);   // ilm_debug_step_regular_waves
 // the slice-0 cells of a UNORM16 field (SdfView::cells0): does this step's collision update use them, and their build
 bool step_wants_slice0_cells(const IlmStepDesc& d, int format);
 hipError_t launch_build_slice0_cells(const uint2* texels, int width, int height, void* cells, hipStream_t stream);

@@ -75,10 +75,12 @@ ILM_DEV float compute_weight(const IlmAreaParams& a, f3 wp) {
 }
 // weight and time factor of an area transform.  Without an area evaluateByTypeId returns 0, so
 // weight = (1 - saturate(0 / falloff)) * Strength = Strength and t = Strength * dtMs / TimeDivisor are uniform:
-// both come from the host (StepDerived), computed with the same operations.
+// both come from the host (StepDerived), computed with the same operations.  AREA = false: the caller's launches never carry an area
+// (build_lean_step), so the instantiation holds no evaluateByTypeId code.
+template <bool AREA = true>
 ILM_DEV void area_weight_and_t(const IlmAreaParams& a, const StepDerived::Op& dv, f3 wp, float dt_ms, float time_divisor, float& weight, float& t) {
 #pragma clang fp contract(off)
-    if (dv.area_none) {
+    if (!AREA || dv.area_none) {
         weight = a.Strength;
         t = dv.t;
     } else {
@@ -163,12 +165,14 @@ ILM_DEV float fma_term_exact(float v, float m, float a) {
 #pragma clang fp contract(off)
     return (v * m) + a;
 }
-// PS_FMA, FMA.fx:22-51
+// PS_FMA, FMA.fx:22-51.  FILTER = false: the caller has proven that every lane is alive and passes the category filter (the clamp
+// class's regular waves, step_lean_block).
+template <bool FILTER = true, bool AREA = true>
 ILM_DEV void apply_fma(float4& pos, float4& vel, const IlmParticleSystemUniforms& sys, const IlmFMAParams& p, const StepDerived::Op& dv) {
-    if ((pos.w <= 0.0f) || !category_ok(vel.w, p.Area.CategoryFilter))
+    if (FILTER && ((pos.w <= 0.0f) || !category_ok(vel.w, p.Area.CategoryFilter)))
         return;
     float weight, t;
-    area_weight_and_t(p.Area, dv, xyz(pos), sys.GlobalSettings.x, p.TimeDivisor, weight, t);
+    area_weight_and_t<AREA>(p.Area, dv, xyz(pos), sys.GlobalSettings.x, p.TimeDivisor, weight, t);
     float4 np = lerp4(pos, add4(mul4(pos, ld4(p.PositionMultiply)), ld4(p.PositionAdd)), t);
     np.w = lerp_exact(pos.w, fma_term_exact(pos.w, p.PositionMultiply.w, p.PositionAdd.w), t);   // life
     const float4 nv = lerp4(vel, add4(mul4(vel, ld4(p.VelocityMultiply)), ld4(p.VelocityAdd)), t);
@@ -195,14 +199,15 @@ ILM_DEV void noise_deltas(float4 p1, float4 p2, float4 v1, float4 v2, const IlmN
     velocity_delta = noise_shape(lerp4(v1, v2, p.FrequencyLerp), p.VelocityOffset, p.VelocityMinimum, p.VelocityScale);
 }
 
-// PS_Noise, Noise.fx:28-72 (no life check: dead slots go through the math, :40)
+// PS_Noise, Noise.fx:28-72 (no life check: dead slots go through the math, :40).  FILTER = false: as for apply_fma.
+template <bool FILTER = true, bool AREA = true>
 ILM_DEV void apply_noise(float4& pos, float4& vel, float x, float y, const float4* __restrict__ rnd, int rw, int rh,
                          const IlmParticleSystemUniforms& sys, const IlmNoiseParams& p, float inv_rw, float inv_rh, const StepDerived::Op& dv,
                          const NoiseDeltas& uniform) {
-    if (!category_ok(vel.w, p.Area.CategoryFilter))
+    if (FILTER && !category_ok(vel.w, p.Area.CategoryFilter))
         return;
     float weight, t;
-    area_weight_and_t(p.Area, dv, xyz(pos), sys.GlobalSettings.x, p.TimeDivisor, weight, t);
+    area_weight_and_t<AREA>(p.Area, dv, xyz(pos), sys.GlobalSettings.x, p.TimeDivisor, weight, t);
 
     float4 position_delta, velocity_delta;
     if (uniform.valid) {
@@ -734,11 +739,24 @@ ILM_DEV void update_positions_select(float4& pos, float4& vel, const IlmParticle
     pos = mk4(keep ? pos.x + velocity.x * dts : 0.0f, keep ? pos.y + velocity.y * dts : 0.0f, keep ? pos.z + velocity.z * dts : 0.0f, keep ? new_life : 0.0f);
     vel = mk4(keep ? velocity.x : 0.0f, keep ? velocity.y : 0.0f, keep ? velocity.z : 0.0f, keep ? vel.w : 0.0f);
 }
+// update_positions_select's values before its selects: what it keeps for a lane that is alive after the transforms and after the decay.
+ILM_DEV void update_positions_unselected(float4& pos, float4& vel, const IlmParticleSystemUniforms& sys, float dts) {
+#pragma clang fp contract(off)   // life arithmetic is bit-exact
+    const f3 velocity = friction_and_maximum(xyz(vel), sys, dts);
+    const float new_life = pos.w - (sys.GlobalSettings.w * dts);
+    pos = mk4(pos.x + velocity.x * dts, pos.y + velocity.y * dts, pos.z + velocity.z * dts, new_life);
+    vel = mk4(velocity.x, velocity.y, velocity.z, vel.w);
+}
 
 // Diagnostic (ilm_debug_step_sdf_samples): how many sampleDistanceFieldEx calls the collision update makes -- the unit of its roofline
 // (bench.py collision_step_1m).  The flag is read by a scalar load; the counter costs nothing while it is off.
 __device__ unsigned long long g_step_sdf_samples;
 __device__ int g_step_count_sdf_samples;
+// Diagnostic (ilm_debug_step_regular_waves): which body the waves of step_lean_clamp_kernel ran.  [0]: the regular body to its end,
+// [1]: the regular transforms, then the selecting update and tail (the second ballot failed).  Every other wave ran the selecting body
+// from the top.  The flag is read by one scalar load per wave; off, that load and a branch are the whole cost.
+__device__ unsigned long long g_step_regular_waves[2];
+__device__ int g_step_count_regular_waves;
 
 // PS_Update, UpdateParticleSystemWithDistanceField.fx:29-147, behind its first lookup: the sweep and the bounce / redirect / escape
 // arithmetic for a live slot whose life does not run out in this step, given initial_distance (the field at the particle) and, when
@@ -1285,7 +1303,8 @@ struct LeanStep {
     int64_t stride;
     int32_t upc_shift, unit_rotate, total_padded, total_units;
     int32_t first_chunk, cs_shift, zero_n; uint32_t flags;
-    uint32_t count_seq; int32_t count_buckets; int32_t _pad3[2];
+    uint32_t count_seq; int32_t count_buckets;
+    float regular_cat_lo, regular_cat_hi;       // the intersection of the transforms' category filters (NaN lo: no category passes); step_lean_clamp_kernel
     int32_t partial_chunk[kMaxPartialChunks], partial_units[kMaxPartialChunks];     // unused entries: chunk -1
     int32_t partial_count, op_count, spawn_count; uint32_t elide;      // elide: kElideDerived / kElideColor (step_lean_kernel)
     int32_t op_type[ILM_MAX_OPS];
@@ -1309,8 +1328,10 @@ struct LeanStep {
 static_assert(sizeof(LeanStep) <= 4096, "LeanStep travels in the kernarg segment (4 KB)");
 
 // PS_Gravity with the attractor records and type codes of LeanGravity: apply_gravity's terms (gravity_term), added in its order
+// FILTER = false: as for apply_fma.
+template <bool FILTER = true>
 ILM_DEV void apply_gravity_lean(float4& pos, float4& vel, const LeanGravity& g, float dt_ms, float mv) {
-    if ((pos.w <= 0.0f) || !((vel.w >= g.cat_lo) && (vel.w <= g.cat_hi)))
+    if (FILTER && ((pos.w <= 0.0f) || !((vel.w >= g.cat_lo) && (vel.w <= g.cat_hi))))
         return;
     f3 acceleration = mk3(0.0f, 0.0f, 0.0f);
     const uint32_t types = g.types;
@@ -1487,6 +1508,75 @@ ILM_DEV void store_changed_render_planes_clamp(const LeanStep& a, const UnitPlan
     if (__ballot(!rdw_same) != 0ull) st_plane<true>(up, 19, lane4, rd.w);
 }
 
+// The lanes of the wave for which p holds, as the scalar mask a compare leaves; testing it is scalar work.  p must BE one compare: the
+// ballot of anything else (and __ballot of anything at all) goes through a select and a second vector compare.  Combine masks, not
+// predicates.  (Every wave of these kernels is whole: the block is a multiple of 64 threads and no lane has left.)
+ILM_DEV uint64_t lane_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+constexpr uint64_t kAllLanes = ~0ull;
+// which body a wave of the clamp class is in (step_lean_block): the selecting one from the top, or the regular one
+constexpr int kBodySelecting = 0, kBodyRegular = 1;
+
+// The lanes that are REGULAR as loaded: alive with a finite life, a category every transform of the list accepts (and so no NaN;
+// a.regular_cat_*: build_lean_step) and no NaN in the velocity's x and y.
+ILM_DEV uint64_t regular_lanes_loaded(const LeanStep& a, const SlotIn& cur) {
+    return lane_mask(cur.life > 0.0f) & lane_mask(cur.life < __builtin_inff()) & lane_mask(cur.ct >= a.regular_cat_lo) & lane_mask(cur.ct <= a.regular_cat_hi) &
+           lane_mask(!__builtin_isunordered(cur.vx, cur.vy));
+}
+// ... and after the update: still alive with a finite life, no NaN in the new velocity's x and y.
+ILM_DEV uint64_t regular_lanes_updated(float new_life, float vx, float vy) {
+    return lane_mask(new_life > 0.0f) & lane_mask(new_life < __builtin_inff()) & lane_mask(!__builtin_isunordered(vx, vy));
+}
+// clamp_curve_t for a wave of live lanes: t for the new state, and the lanes where the proof fails (t changed its bits or is a NaN)
+ILM_DEV uint64_t clamp_curve_changed(const IlmFloat4& rc, float v0, float v1, uint32_t code, float& t1) {
+    t1 = 0.0f;      // a constant curve reads no t
+    if ((code & 3u) == 0u) return 0ull;
+    t1 = t_for_clamp_bezier(rc, v1, code);
+    return lane_mask(!same_bits(t_for_clamp_bezier(rc, v0, code), t1)) | lane_mask(t1 != t1);
+}
+
+// store_changed_render_planes_clamp for a wave whose 64 lanes are regular before and after the step (regular_lanes_*): the same stores of
+// the same bits, without what those masks decide.  Every lane is `both`, none `dead`, so each *_same is its bare proof and no value is
+// selected against zero.  The category keeps its bits and is no NaN: rd.w is never stored.  The velocity's x and y are no NaN, so
+// rotation_unscaled is 0 for both states.  With kElideRotation the host has found RotationFromLifeAndIndex[0] == 0: life x (+-0) has the
+// same bits for any two finite positive lives, rd.y's operands are the loaded state's and it keeps its bits (and, the index factor
+// being finite, is no NaN).
+// v_changed: the lanes whose velocity changed a bit (the caller's plane compares).
+ILM_DEV void store_changed_render_planes_regular(const LeanStep& a, const UnitPlanes& up, unsigned lane4, float fx, float fy, const SlotIn& cur,
+                                                 float4 pos, float4 vel, uint64_t v_changed) {
+    const IlmUpdateParams& p = a.update;
+    const uint32_t codes = a.bezier_codes & kClampCodes;
+    const uint32_t c_cl = codes & 0xFFu, c_cv = (codes >> 8) & 0xFFu, c_sl = (codes >> 16) & 0xFFu, c_sv = codes >> 24;
+    const float speed1 = fmaxf(len3_fast(xyz(vel)), 0.0001f);
+    float speed0 = 0.0f;
+    if ((codes & 0x03000300u) != 0u)        // the loaded state's speed, only where a velocity curve is not constant
+        speed0 = fmaxf(len3_fast(mk3(cur.vx, cur.vy, cur.vz)), 0.0001f);
+    float t_cl, t_cv, t_sl, t_sv;
+    const uint64_t rc_changed = clamp_curve_changed(p.ColorFromLife.RangeAndCount, cur.life, pos.w, c_cl, t_cl) |
+                                clamp_curve_changed(p.ColorFromVelocity.RangeAndCount, speed0, speed1, c_cv, t_cv);
+    const uint64_t size_changed = clamp_curve_changed(p.SizeFromLife.RangeAndCount, cur.life, pos.w, c_sl, t_sl) |
+                                  clamp_curve_changed(p.SizeFromVelocity.RangeAndCount, speed0, speed1, c_sv, t_sv);
+    if (((a.elide & kElideColor) == 0u) || rc_changed != 0ull) {
+        const float4 attr = load_attributes<true>(up, lane4);
+        const float4 color_l = ((c_cl & 3u) == 0u) ? ld4(p.ColorFromLife.A) : bezier4_at(p.ColorFromLife, t_cl, c_cl & 3u);
+        const float4 color_v = ((c_cv & 3u) == 0u) ? ld4(p.ColorFromVelocity.A) : bezier4_at(p.ColorFromVelocity, t_cv, c_cv & 3u);
+        float4 rc = mul4(attr, mul4(color_l, color_v));
+        rc.w = sat(rc.w);
+        rc.x *= rc.w; rc.y *= rc.w; rc.z *= rc.w;
+        st_plane<true>(up, 12, lane4, rc.x); st_plane<true>(up, 13, lane4, rc.y); st_plane<true>(up, 14, lane4, rc.z); st_plane<true>(up, 15, lane4, rc.w);
+    }
+    const float size_l = ((c_sl & 3u) == 0u) ? p.SizeFromLife.ABCD.x : bezier1_at(p.SizeFromLife, t_sl, c_sl & 3u);
+    const float size_v = ((c_sv & 3u) == 0u) ? p.SizeFromVelocity.ABCD.x : bezier1_at(p.SizeFromVelocity, t_sv, c_sv & 3u);
+    const float rdx = size_l * size_v;
+    if ((size_changed | lane_mask(rdx != rdx)) != 0ull) st_plane<true>(up, 16, lane4, rdx);
+    if ((a.elide & kElideRotation) == 0u) {
+        const float index = render_index(fx, fy);
+        const float rdy = render_rotation(0.0f, pos.w, index, a.sys, p);
+        const float y0 = render_rotation(0.0f, cur.life, index, a.sys, p);
+        if ((lane_mask(!same_bits(y0, rdy)) | lane_mask(rdy != rdy)) != 0ull) st_plane<true>(up, 17, lane4, rdy);
+    }
+    if (v_changed != 0ull) st_plane<true>(up, 18, lane4, speed1);
+}
+
 
 // One block of the lean step, for one curve class (the kernels below).
 template <bool SPAWN, bool STREAM, int CURVES>
@@ -1556,26 +1646,81 @@ ILM_DEV void step_lean_block() {
             const float4 zero = mk4(0.0f, 0.0f, 0.0f, 0.0f);
             float4 rc = zero, rd = zero;
             if constexpr (CURVES == kCurvesClamp) {
-                if (__ballot(process) != 0ull) {
-                    // Every lane goes through the transforms and the update, and one select at the end keeps the live ones: a slot the
-                    // step does not process comes out as zeros whatever was computed for it.  The transforms are dispatched from
-                    // unrolled positions so that position and velocity stay in their registers from one to the next.
+                // A wave of 64 regular lanes (regular_lanes_loaded) runs the transforms and the update without the tests and selects that
+                // serve dead, filtered and NaN lanes: the same operations on the same operands, so where the wave turns out not to stay
+                // regular the selects applied afterwards give the bits of the selecting body.  Only FMA can take a life to <= 0 (Gravity
+                // leaves it alone, a lean launch's Noise leaves it or makes it a NaN: noise_may_revive), and only FMA writes the category
+                // (its lerp covers the velocity's w; Gravity and Noise pass it through).  A wave where FMA does either -- a life <= 0, or a
+                // category with other bits than the loaded one, -0 to +0 and NaN included -- starts again from the loaded state in the
+                // selecting body, which filters the later transforms by the new category, skips them for a dead lane and stores the
+                // category plane and rd.w.  So in the regular body the category is the loaded one to the end.
+                int body = kBodySelecting;
+                if (regular_lanes_loaded(a, cur) == kAllLanes) {
+                    body = kBodyRegular;
 #pragma unroll
                     for (int o = 0; o < ILM_MAX_OPS; o++) {
-                        if (o < a.op_count) {
+                        if (body == kBodyRegular && o < a.op_count) {
                             const int type = a.op_type[o];
-                            if (type == ILM_OP_GRAVITY)
-                                apply_gravity_lean(pos, vel, a.op[o].gravity, a.sys.GlobalSettings.x, a.sys.GlobalSettings.z);
-                            else if (type == ILM_OP_NOISE)
-                                apply_noise(pos, vel, fx, fy, a.rnd, a.rw, a.rh, a.sys, a.op[o].noise, a.inv_rw, a.inv_rh, a.dop[o],
-                                            (o == a.noise_op) ? noise : NoiseDeltas{ false, zero, zero });
-                            else
-                                apply_fma(pos, vel, a.sys, a.op[o].fma, a.dop[o]);
+                            if (type == ILM_OP_GRAVITY) {
+                                apply_gravity_lean<false>(pos, vel, a.op[o].gravity, a.sys.GlobalSettings.x, a.sys.GlobalSettings.z);
+                            } else if (type == ILM_OP_NOISE) {
+                                apply_noise<false, false>(pos, vel, fx, fy, a.rnd, a.rw, a.rh, a.sys, a.op[o].noise, a.inv_rw, a.inv_rh, a.dop[o],
+                                                          (o == a.noise_op) ? noise : NoiseDeltas{ false, zero, zero });
+                            } else {
+                                apply_fma<false, false>(pos, vel, a.sys, a.op[o].fma, a.dop[o]);
+                                if ((lane_mask(pos.w <= 0.0f) | lane_mask(!same_bits(vel.w, cur.ct))) != 0ull) body = kBodySelecting;
+                            }
                         }
                     }
-                    update_positions_select(pos, vel, a.sys, a.dt_s, process && !(pos.w <= 0.0f));
-                } else {
-                    pos = vel = zero;
+                }
+                if (body == kBodyRegular) {
+                    update_positions_unselected(pos, vel, a.sys, a.dt_s);
+                    const bool stays = regular_lanes_updated(pos.w, vel.x, vel.y) == kAllLanes;
+                    if (__builtin_amdgcn_readfirstlane(*(CInt32*)&g_step_count_regular_waves) != 0 && lane == 0u)
+                        atomicAdd(&g_step_regular_waves[stays ? 0 : 1], 1ull);
+                    if (stays) {
+                        const uint64_t vx_changed = lane_mask(!same_bits(vel.x, cur.vx)), vy_changed = lane_mask(!same_bits(vel.y, cur.vy)), vz_changed = lane_mask(!same_bits(vel.z, cur.vz));
+                        if (lane_mask(!same_bits(pos.x, cur.px)) != 0ull) st_plane<true>(up, 0, lane4, pos.x);
+                        if (lane_mask(!same_bits(pos.y, cur.py)) != 0ull) st_plane<true>(up, 1, lane4, pos.y);
+                        if (lane_mask(!same_bits(pos.z, cur.pz)) != 0ull) st_plane<true>(up, 2, lane4, pos.z);
+                        if (lane_mask(!same_bits(pos.w, cur.life)) != 0ull) st_plane<true>(up, 3, lane4, pos.w);
+                        if (vx_changed != 0ull) st_plane<true>(up, 4, lane4, vel.x);
+                        if (vy_changed != 0ull) st_plane<true>(up, 5, lane4, vel.y);
+                        if (vz_changed != 0ull) st_plane<true>(up, 6, lane4, vel.z);
+                        // (the category keeps its bits: no store)
+                        store_changed_render_planes_regular(a, up, lane4, fx, fy, cur, pos, vel, vx_changed | vy_changed | vz_changed);
+                        n_live = 64u;
+                        goto unit_stored;       // (a flag tested at the stores below moved the general instantiations' registers)
+                    }
+                    // every lane was alive after the transforms: update_positions_select's `keep` is the new life's test alone
+                    const bool keep = !(pos.w <= 0.0f);
+                    pos = mk4(keep ? pos.x : 0.0f, keep ? pos.y : 0.0f, keep ? pos.z : 0.0f, keep ? pos.w : 0.0f);
+                    vel = mk4(keep ? vel.x : 0.0f, keep ? vel.y : 0.0f, keep ? vel.z : 0.0f, keep ? vel.w : 0.0f);
+                }
+                if (body == kBodySelecting) {
+                    pos = mk4(cur.px, cur.py, cur.pz, cur.life);
+                    vel = mk4(cur.vx, cur.vy, cur.vz, cur.ct);
+                    if (__ballot(process) != 0ull) {
+                        // Every lane goes through the transforms and the update, and one select at the end keeps the live ones: a slot the
+                        // step does not process comes out as zeros whatever was computed for it.  The transforms are dispatched from
+                        // unrolled positions so that position and velocity stay in their registers from one to the next.
+#pragma unroll
+                        for (int o = 0; o < ILM_MAX_OPS; o++) {
+                            if (o < a.op_count) {
+                                const int type = a.op_type[o];
+                                if (type == ILM_OP_GRAVITY)
+                                    apply_gravity_lean(pos, vel, a.op[o].gravity, a.sys.GlobalSettings.x, a.sys.GlobalSettings.z);
+                                else if (type == ILM_OP_NOISE)
+                                    apply_noise<true, false>(pos, vel, fx, fy, a.rnd, a.rw, a.rh, a.sys, a.op[o].noise, a.inv_rw, a.inv_rh, a.dop[o],
+                                                             (o == a.noise_op) ? noise : NoiseDeltas{ false, zero, zero });
+                                else
+                                    apply_fma<true, false>(pos, vel, a.sys, a.op[o].fma, a.dop[o]);
+                            }
+                        }
+                        update_positions_select(pos, vel, a.sys, a.dt_s, process && !(pos.w <= 0.0f));
+                    } else {
+                        pos = vel = zero;
+                    }
                 }
             } else if (__ballot(process) != 0ull) {
                 if (process) {
@@ -1619,6 +1764,10 @@ ILM_DEV void step_lean_block() {
                 store_changed_render_planes<SPAWN, STREAM>(a, up, lane4, fx, fy, cur, pos, vel, attr, spawned);
             }
             n_live = (uint32_t)__popcll(__ballot(pos.w > 0.0f));
+        // The clamp class's regular body jumps here with its planes stored and n_live set.  Everything between `process` and this label
+        // belongs to the selecting bodies alone: whatever a unit must do whichever body ran (the count below is the one such thing
+        // today) goes AFTER the label, never above it.
+        unit_stored: __attribute__((unused));
         }
     }
     if (a.flags & ILM_STEP_COUNT_LIVE)
@@ -1943,6 +2092,22 @@ static bool build_lean_step(const StepLaunch& a, LeanStep& f) {
             f.op[o].fma = op.u.FMA;
         }
     }
+    // The regular waves of the clamp class: a category passes every transform's filter exactly when it lies in their intersection (a
+    // NaN bound fails every category, like the shader's comparisons); without a transform any category that is no NaN passes.
+    float cat_lo = -INFINITY, cat_hi = INFINITY;
+    for (int o = 0; o < d.OpCount; o++) {
+        const IlmTransformOp& op = d.Ops[o];
+        const float* mm = (op.Type == ILM_OP_GRAVITY) ? op.u.Gravity.CategoryFilter : (op.Type == ILM_OP_NOISE) ? op.u.Noise.Area.CategoryFilter : op.u.FMA.Area.CategoryFilter;
+        if (std::isnan(mm[0]) || std::isnan(mm[1])) cat_lo = NAN;
+        cat_lo = (mm[0] > cat_lo) ? mm[0] : cat_lo;     // (a NaN cat_lo stays)
+        cat_hi = (mm[1] < cat_hi) ? mm[1] : cat_hi;
+    }
+    f.regular_cat_lo = cat_lo; f.regular_cat_hi = cat_hi;
+    // rd.y = rotation x getVelocityRotation() + (life x RotationFromLifeAndIndex[0] + index x [1]): with a zero factor, a finite life
+    // contributes the same +-0 whatever it is (the shader's own comparison: update_bits bit 1 is `== 0.0f` likewise).  Only with a finite
+    // index factor: rd.y is then no NaN (the index is finite), so the bit never rests on what NaN an earlier writer left in the plane --
+    // a NaN rd.y keeps both evaluations and the store the selecting tail gives it.
+    f.elide = (d.Update.RotationFromLifeAndIndex[0] == 0.0f && std::isfinite(d.Update.RotationFromLifeAndIndex[1]) && (a.derived.update_bits & 2u)) ? kElideRotation : 0u;
     f.op_count = d.OpCount;
     f.noise_op = a.derived.noise.op;
     f.noise = a.derived.noise;
@@ -2218,7 +2383,7 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide,
         } else {
             LeanStep f;
             if (build_lean_step(a, f)) {
-                f.elide = ((render_elide & kElideDerived) && a.streaming) ? (kElideDerived | (color_curves_bounded(a.desc.Update) ? kElideColor : 0u)) : 0u;
+                f.elide = ((render_elide & kElideDerived) && a.streaming) ? (kElideDerived | (color_curves_bounded(a.desc.Update) ? kElideColor : 0u) | (f.elide & kElideRotation)) : 0u;
                 const hipError_t e = launch_lean_step(f, spawning, a.streaming != 0, stream);
                 if (refreshed) *refreshed = (e == hipSuccess);
                 return e;
@@ -2388,6 +2553,19 @@ hipError_t step_sdf_sample_counter(int enable, unsigned long long* out) {
     const int flag = enable ? 1 : 0;
     e = hipMemcpyToSymbol(HIP_SYMBOL(g_step_count_sdf_samples), &flag, sizeof(flag));
     if (out) *out = value;
+    return e;
+}
+
+// ilm_debug_step_regular_waves: the same for the clamp class's two wave counts
+hipError_t step_regular_wave_counter(int enable, unsigned long long out[2]) {
+    unsigned long long value[2] = { 0, 0 }, zero[2] = { 0, 0 };
+    hipError_t e = hipMemcpyFromSymbol(value, HIP_SYMBOL(g_step_regular_waves), sizeof(value));
+    if (e != hipSuccess) return e;
+    e = hipMemcpyToSymbol(HIP_SYMBOL(g_step_regular_waves), zero, sizeof(zero));
+    if (e != hipSuccess) return e;
+    const int flag = enable ? 1 : 0;
+    e = hipMemcpyToSymbol(HIP_SYMBOL(g_step_count_regular_waves), &flag, sizeof(flag));
+    if (out) { out[0] = value[0]; out[1] = value[1]; }
     return e;
 }
 

@@ -551,6 +551,14 @@ int32_t ilm_debug_step_streams(int32_t streams);
  * the count accumulated since the previous call in *out_samples (may be NULL) and clears it.  Synchronises the context.  The count
  * costs one atomic per particle while it is on: for measurement runs only. */
 int32_t ilm_debug_step_sdf_samples(IlmHandle ctx, int32_t enable, uint64_t* out_samples);
+/* Diagnostic: ILM_STEP_KERNEL_LEAN_CLAMP has two bodies.  A wave whose 64 slots are all REGULAR as loaded -- alive with a finite life, a
+ * category that passes every transform's filter, no NaN in the velocity's x and y -- runs the transforms and the update without the tests
+ * and selects that serve other lanes, and finishes there when all 64 are still alive, finite and free of NaN afterwards; every other wave
+ * runs the selecting body.  The planes get the same bits either way.  enable != 0 makes every later step of this process that runs that
+ * kernel count, on the device, the waves that ran the regular body to its end (*out_regular) and those that ran its transforms but
+ * finished through the selects (*out_selected); the call returns the counts accumulated since the previous call (either pointer may be
+ * NULL) and clears them.  Synchronises the context.  One atomic per counted wave while it is on; one scalar load per wave while off. */
+int32_t ilm_debug_step_regular_waves(IlmHandle ctx, int32_t enable, uint64_t* out_regular, uint64_t* out_selected);
 /* The grid of the context's last light-pass launch (sphere or particle lights): workgroups of 256 threads (four waves each; exit-only
  * workgroups of partial tile groups included -- what a profiler's wave count sees), the largest number of workgroups per tile (light
  * split; 1 = none) and the edge of the tile groups dealt to the XCDs (0: another block -> tile map).  Measurement scripts price per-wave

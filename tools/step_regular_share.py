@@ -1,0 +1,41 @@
+#!/usr/bin/env python3
+"""GPU box: which body the waves of step_lean_clamp_kernel run on bench.py's headline (cfg4 whole: 64 chunks of 1024^2, Gravity x4 + Noise +
+UpdatePositions), read from ilm_debug_step_regular_waves.
+
+    python tools/step_regular_share.py [steps]
+
+The system is built by bench.build_particle_system as the headline's row builds it.  Two untimed steps first (the first step of a system
+stores everything through the general instantiation), then `steps` (default 10) counted ones."""
+import ctypes as C
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+from illuminant_amd import abi, native, scenes  # noqa: E402
+from illuminant_amd import _host as H  # noqa: E402
+
+
+def main():
+    steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+    ctx = H.DeviceContext(0)
+    F = bench.build_particle_system(H, ctx, scenes, abi, 1024, 64, 0, with_spawner=False, replicate_cfg4_images=True)
+    ps, tp = F["ps"], F["tp"]
+    lib, handle = native.lib(), C.c_uint64(ctx.Handle)
+    try:
+        for frame in range(2 + steps):
+            if frame == 2:
+                native.check(lib.ilm_debug_step_regular_waves(handle, 1, None, None))
+            tp.Advance(1.0 / 60.0); ps.Update(frame)
+        ctx.Sync()
+    finally:
+        regular, selected = C.c_uint64(0), C.c_uint64(0)
+        native.check(lib.ilm_debug_step_regular_waves(handle, 0, C.byref(regular), C.byref(selected)))
+    waves = steps * F["live"] // 64
+    print("steps 3..%d of the headline: %d waves, regular %d (%.4f %%), regular transforms then selecting tail %d, selecting body %d; last kernel %d"
+          % (2 + steps, waves, regular.value, 100.0 * regular.value / waves, selected.value, waves - regular.value - selected.value,
+             lib.ilm_debug_last_step_kernel()))
+
+
+if __name__ == "__main__":
+    main()
