@@ -9,106 +9,18 @@ that must have taken each way in each step.
 The shape: chunk size 64 (one wave per row, 64 waves per chunk), two chunks, Gravity with four attractors (linear and squared) + Noise +
 UpdatePositions, OpacityFromLife as the one clamp-linear curve.  ILM_STEP_STREAMING=1 selects the HBM-resident variant for so small a system.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from illuminant_amd import abi, native, scenes
-from tests.test_step_store_elision_gpu import Twins, update_params, P, V, A
+from tests.step_regular_common import (CountingTwins, desc, regular_particles, slot, PLACES, K, LEAN, LEAN_CLAMP, N, CHUNKS, STEPS, WAVES, NAN, INF, DECAY)
+from tests.test_step_store_elision_gpu import update_params, V
 
 pytestmark = pytest.mark.gpu
-
-LEAN, LEAN_CLAMP = 2, 3          # ILM_STEP_KERNEL_* of include/illuminant_hip.h
-CS, CHUNKS, STEPS = 64, 2, 5
-N = CS * CS
-WAVES = CHUNKS * N // 64
-NAN, INF = np.float32(np.nan), np.float32(np.inf)
-MAX_VELOCITY = 100.0
-LIFE_DECAY = 0.6
-# one step's decay as the kernels form it: LifeDecay x (dtMs / 1000), in float32
-DT_MS = np.float32(1.0 / 60 * 1000.0)
-DECAY = np.float32(np.float32(LIFE_DECAY) * np.float32(DT_MS / np.float32(1000.0)))
-GRAVITY_FILTER, NOISE_FILTER = (0.0, 1.0), (-1.0, 0.5)       # regular particles have category 0
-# (chunk, wave of the chunk, lane) of the irregular lanes: the wave's first and last lane and both sides of the middle, in waves whose
-# neighbours stay regular
-PLACES = ((0, 3, 0), (0, 17, 31), (1, 40, 32), (1, 63, 63))
 
 
 @pytest.fixture(autouse=True)
 def streaming_variant(monkeypatch):
     monkeypatch.setenv("ILM_STEP_STREAMING", "1")
-
-
-def desc(ops=("gravity", "noise"), update=None, fma_life_add=0.0, fma_category=(1.0, 0.0)):
-    d = abi.StepDesc()
-    d.FirstChunk, d.ChunkCount = 0, -1
-    d.System = scenes.system_uniforms(CS, friction=0.02, max_velocity=MAX_VELOCITY, life_decay=LIFE_DECAY)
-    # rotation from the index alone: rd.y does not read the life, the host says so and the regular body does not evaluate it
-    d.Update = update if update is not None else update_params(rotation_from_index=0.001)
-    d.OpCount = len(ops)
-    for o, kind in enumerate(ops):
-        if kind == "gravity":
-            d.Ops[o].Type = abi.OP_GRAVITY
-            d.Ops[o].u.Gravity = scenes.gravity_params([((60., 70., 0.), 40., 500., 1), ((200., 60., 10.), 90., 700., 2), ((100., 210., 0.), 120., 900., 1),
-                                                        ((30., 180., 5.), 70., 300., 2)], maximum_acceleration=64.0, category_filter=GRAVITY_FILTER)
-        elif kind == "noise":
-            d.Ops[o].Type = abi.OP_NOISE
-            d.Ops[o].u.Noise = scenes.noise_params(scenes.area_none(category_filter=NOISE_FILTER), (0.37 * 253, 0.81 * 127), (0.12 * 253, 0.55 * 127), 0.35)
-        else:
-            d.Ops[o].Type = abi.OP_FMA
-            d.Ops[o].u.FMA = scenes.fma_params(scenes.area_none(category_filter=(-1.0, 1.0)), position_add=(0.5, -0.25, 0.0), velocity_multiply=(0.98, 0.97, 1.0))
-            d.Ops[o].u.FMA.PositionAdd.w = fma_life_add
-            d.Ops[o].u.FMA.VelocityMultiply.w, d.Ops[o].u.FMA.VelocityAdd.w = fma_category
-    d.UpdateMode = abi.UPDATE_POSITIONS
-    d.Flags = abi.STEP_COUNT_LIVE
-    return d
-
-
-def regular_particles():
-    """Every slot regular and far from the end of its life."""
-    return scenes.make_particles(5, N * CHUNKS, life=(50.0, 90.0), categories=(0.0,))
-
-
-def slot(place):
-    chunk, wave, lane = place
-    return chunk * N + wave * 64 + lane
-
-
-class CountingTwins(Twins):
-    """Twins over given particles; records the kernel and the two wave counts of every step of the first (default choice) system."""
-
-    def __init__(self, ctx, pos, vel, attr):
-        self.ctx = ctx
-        self.cs, self.n = CS, N
-        self.eng = native.Engine(ctx, CS, scenes.randomness_table(11))
-        self.systems = [native.System(self.eng), native.System(self.eng)]    # [default choice, interpreter]
-        self.counts = [[], []]
-        self.kernels, self.waves = [], []
-        for s in self.systems:
-            for c in range(CHUNKS):
-                s.add_chunk()
-                sl = slice(c * N, (c + 1) * N)
-                s.upload(c, P, pos[sl]); s.upload(c, V, vel[sl]); s.upload(c, A, attr[sl])
-        self.prev = native.lib().ilm_debug_step_interpreter(0)
-        native.check(native.lib().ilm_debug_step_regular_waves(ctx.handle, 1, None, None))
-
-    def step(self, d, n=1):
-        for _ in range(n):
-            for i, s in enumerate(self.systems):
-                native.lib().ilm_debug_step_interpreter(i)
-                s.step(d)
-                if i == 0:
-                    regular, selected = C.c_uint64(0), C.c_uint64(0)
-                    native.check(native.lib().ilm_debug_step_regular_waves(self.ctx.handle, 1, C.byref(regular), C.byref(selected)))
-                    self.kernels.append(native.lib().ilm_debug_last_step_kernel())
-                    self.waves.append((int(regular.value), int(selected.value)))
-                self.counts[i].append(s.step_counts().copy())
-        native.lib().ilm_debug_step_interpreter(0)
-
-    def close(self):
-        native.check(native.lib().ilm_debug_step_regular_waves(self.ctx.handle, 0, None, None))
-        super().close()
 
 
 def run(ctx, what, particles, d, want_waves, also=None):
@@ -120,6 +32,7 @@ def run(ctx, what, particles, d, want_waves, also=None):
         t.check(what)
         assert t.kernels == [LEAN] + [LEAN_CLAMP] * (STEPS - 1), (what, t.kernels)
         assert t.waves == [(0, 0)] + list(want_waves), (what, t.waves)
+        t.check_waves(what)               # ... and what the kernel's two masks give over the twin's planes (lists without FMA)
         if also is not None:
             also(t)
     finally:
@@ -154,7 +67,6 @@ def _velocity(x, y, z):
     return fn
 
 
-K = len(PLACES)
 ALWAYS = [(WAVES - K, 0)] * 4            # the waves with such a lane run the selecting body from the top in every step of the class
 NEVER = [(WAVES, 0)] * 4                 # the lane is regular
 # kind -> (what it does to a slot, (regular, selected) waves of steps 2 .. 5[, the transforms where they are not Gravity + Noise])
