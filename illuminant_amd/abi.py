@@ -219,6 +219,11 @@ class RasterizeParams(C.Structure):
                 ("AnimationRate", f32 * 2)]
 
 
+class RasterizeItem(C.Structure):
+    """One system's draw inside ilm_engine_render_particles_batch: the arguments of ilm_render_particles."""
+    _fields_ = [("System", Handle), ("QuadCounts", C.c_void_p), ("ChunkCount", i32), ("_pad", i32), ("Params", RasterizeParams)]
+
+
 class _OpUnion(C.Union):
     _fields_ = [("Gravity", GravityParams), ("Noise", NoiseParams), ("FMA", FMAParams),
                 ("MatrixMultiply", MatrixMultiplyParams), ("SpatialNoise", SpatialNoiseParams)]
@@ -379,4 +384,5 @@ EXPECTED_SIZES = {
     "IlmHistogramBucket": (HistogramBucket, 16), "IlmHistogramParams": (HistogramParams, 24), "IlmHistogramResult": (HistogramResult, 36),
     "IlmVisualizeVertex": (VisualizeVertex, 52), "IlmVisualizeParams": (VisualizeParams, 80),
     "IlmLUTBlending": (LUTBlending, 64),
+    "IlmRasterizeItem": (RasterizeItem, 216),
 }

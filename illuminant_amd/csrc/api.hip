@@ -112,6 +112,7 @@ struct Ctx {
     int light_blend_color = ILM_LIGHT_BLEND_ADD, light_blend_alpha = ILM_LIGHT_BLEND_ADD;      // ilm_ctx_set_light_blend_function: rgb | a of the calls that follow
     RasterScratch raster;                                         // particle rasteriser buffers (raster.hip)
     DeviceScratch d_raster_quads;
+    DeviceScratch d_raster_items;                                 // ilm_engine_render_particles_batch: the RasterItem table, then every item's quad counts
     // particle read-back: draw-call records, total, block counts, per-chunk element counts
     DeviceScratch d_rb, d_rb_count, d_rb_blocks, d_rb_elems;
     IlmReadbackDrawCall* h_rb = nullptr; size_t h_rb_cap = 0;    // pinned host buffer the read-back records land in
@@ -121,9 +122,9 @@ struct Ctx {
     // parameter block of the distance-field generation pass (slice list, obstruction records, volumes, polygon vertices)
     DeviceScratch d_field_params;
     // every block `reserve` grows: what ilm_ctx_destroy frees
-    std::array<DeviceScratch*, 21> scratch() {
+    std::array<DeviceScratch*, 22> scratch() {
         return { &staging, &d_recs, &d_light_partials, &d_light_tickets, &d_group_order, &d_pl_recs, &d_pl_count, &d_pl_blocks, &d_pl_quads,
-                 &d_raster_quads, &d_rb, &d_rb_count, &d_rb_blocks, &d_rb_elems, &d_probe_pairs, &brightness.level, &brightness.mip,
+                 &d_raster_quads, &d_raster_items, &d_rb, &d_rb_count, &d_rb_blocks, &d_rb_elems, &d_probe_pairs, &brightness.level, &brightness.mip,
                  &brightness.work, &brightness.partials, &d_field_params, &d_projector_texture };
     }
 };
@@ -157,6 +158,7 @@ struct Engine {
     void* d_batch = nullptr; size_t d_batch_bytes = 0;
     std::vector<void*> d_batch_outgrown;
     int last_batch_launches = 0, last_batch_rounds = 0, last_batch_fallback = 0;      // ilm_debug_last_step_batch
+    int last_render_items = 0, last_render_sorts = 0, last_render_tile_launches = 0;  // ilm_debug_last_render_batch
 };
 
 // A distance field or G-buffer that sibling contexts read (light passes on another context's stream).  Every WRITE to it happens on its
@@ -3541,6 +3543,43 @@ int32_t ilm_lightmap_clear(IlmHandle h, const float rgba[4]) {
     return ILM_OK;
 }
 
+namespace {
+// What ilm_render_particles judges about one system's draw -- ilm_engine_render_particles_batch asks the same of every item.  Returns the
+// code and writes the sentence; nothing is changed.
+int32_t check_raster_item(const System* s, const int32_t* quad_counts, int32_t chunk_count, const IlmRasterizeParams* params, char* text, size_t n) {
+    const Engine* e = s->engine;
+    // Fracture code outside the reference tree (DitherCommon.fxh): not guessed
+    if (!(params->StippleFactor >= 1.0f)) {
+        snprintf(text, n, "StippleFactor %g < 1 needs Fracture's StippleReject, which is not part of the reference tree", (double)params->StippleFactor);
+        return ILM_ERR_INVALID_ARGUMENT;
+    }
+    if (params->BlendMode != ILM_BLEND_ALPHA && params->BlendMode != ILM_BLEND_ADDITIVE) {
+        snprintf(text, n, "unknown blend mode %d", params->BlendMode);
+        return ILM_ERR_INVALID_ARGUMENT;
+    }
+    if (params->BitmapFilter < ILM_BITMAP_NONE || params->BitmapFilter > ILM_BITMAP_LINEAR) {
+        snprintf(text, n, "unknown bitmap filter %d", params->BitmapFilter);
+        return ILM_ERR_INVALID_ARGUMENT;
+    }
+    if (params->BitmapFilter != ILM_BITMAP_NONE) {
+        if (!s->bitmap) { snprintf(text, n, "textured technique without a bitmap (ilm_system_set_bitmap)"); return ILM_ERR_STATE; }
+        const float rw = params->BitmapTextureRegion.z - params->BitmapTextureRegion.x, rh = params->BitmapTextureRegion.w - params->BitmapTextureRegion.y;
+        if (!(rw > 0.0f) || !(rh > 0.0f)) { snprintf(text, n, "empty BitmapTextureRegion"); return ILM_ERR_INVALID_ARGUMENT; }
+    }
+    const int chunks = (int)s->chunks.size();
+    if (chunk_count < 0 || chunk_count > chunks) { snprintf(text, n, "chunk_count %d outside [0, %d]", chunk_count, chunks); return ILM_ERR_OUT_OF_RANGE; }
+    for (int i = 0; i < chunk_count; i++) {
+        const int q = quad_counts ? quad_counts[i] : e->slots;
+        if (q < 0 || q > e->slots) { snprintf(text, n, "quad_counts[%d] = %d outside [0, %d]", i, q, e->slots); return ILM_ERR_OUT_OF_RANGE; }
+    }
+    if ((long long)chunk_count * (long long)e->slots > (long long)INT32_MAX) {
+        snprintf(text, n, "%d chunks of %d slots exceed the 32-bit slot index of the sort key", chunk_count, e->slots);
+        return ILM_ERR_TOO_MANY;
+    }
+    return ILM_OK;
+}
+}  // namespace
+
 int32_t ilm_render_particles(IlmHandle hsystem, const int32_t* quad_counts, int32_t chunk_count, const IlmRasterizeParams* params,
                              IlmHandle htarget, uint64_t* out_stats) {
     ILM_TRACE_RANGE("ilm_render_particles");
@@ -3552,28 +3591,10 @@ int32_t ilm_render_particles(IlmHandle hsystem, const int32_t* quad_counts, int3
     Engine* e = s->engine;
     Ctx* c = e->ctx;
     if (m->ctx != c) return fail(ILM_ERR_INVALID_ARGUMENT, "system and target belong to different contexts");
-    // Fracture code outside the reference tree (DitherCommon.fxh): not guessed
-    if (!(params->StippleFactor >= 1.0f))
-        return fail(ILM_ERR_INVALID_ARGUMENT, "StippleFactor %g < 1 needs Fracture's StippleReject, which is not part of the reference tree", (double)params->StippleFactor);
-    if (params->BlendMode != ILM_BLEND_ALPHA && params->BlendMode != ILM_BLEND_ADDITIVE)
-        return fail(ILM_ERR_INVALID_ARGUMENT, "unknown blend mode %d", params->BlendMode);
-    if (params->BitmapFilter < ILM_BITMAP_NONE || params->BitmapFilter > ILM_BITMAP_LINEAR)
-        return fail(ILM_ERR_INVALID_ARGUMENT, "unknown bitmap filter %d", params->BitmapFilter);
-    if (params->BitmapFilter != ILM_BITMAP_NONE) {
-        if (!s->bitmap) return fail(ILM_ERR_STATE, "textured technique without a bitmap (ilm_system_set_bitmap)");
-        const float rw = params->BitmapTextureRegion.z - params->BitmapTextureRegion.x, rh = params->BitmapTextureRegion.w - params->BitmapTextureRegion.y;
-        if (!(rw > 0.0f) || !(rh > 0.0f)) return fail(ILM_ERR_INVALID_ARGUMENT, "empty BitmapTextureRegion");
-    }
-    const int n = (int)s->chunks.size();
-    if (chunk_count < 0 || chunk_count > n) return fail(ILM_ERR_OUT_OF_RANGE, "chunk_count %d outside [0, %d]", chunk_count, n);
+    char why[256];
+    { const int32_t code = check_raster_item(s, quad_counts, chunk_count, params, why, sizeof(why)); if (code != ILM_OK) return fail(code, "%s", why); }
     if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = 0;
     if (chunk_count == 0) return ILM_OK;
-    for (int i = 0; i < chunk_count; i++) {
-        const int q = quad_counts ? quad_counts[i] : e->slots;
-        if (q < 0 || q > e->slots) return fail(ILM_ERR_OUT_OF_RANGE, "quad_counts[%d] = %d outside [0, %d]", i, q, e->slots);
-    }
-    if ((long long)chunk_count * (long long)e->slots > (long long)INT32_MAX)
-        return fail(ILM_ERR_TOO_MANY, "%d chunks of %d slots exceed the 32-bit slot index of the sort key", chunk_count, e->slots);
     if ((m->width + 15) / 16 > 65535 || (m->height + 15) / 16 > 65535) return fail(ILM_ERR_OUT_OF_RANGE, "target too large");
     HIP_TRY(hipSetDevice(c->device));
     int32_t rc = refresh_table(s);
@@ -3599,6 +3620,101 @@ int32_t ilm_render_particles(IlmHandle hsystem, const int32_t* quad_counts, int3
     HIP_TRY(render_particles(a, c->raster, c->main(), out_stats ? stats : nullptr, &too_many));
     if (too_many) return fail(ILM_ERR_TOO_MANY, "more than 2^28 (quad, tile) pairs: the quads are too large for this path");
     if (out_stats) { out_stats[0] = stats[0]; out_stats[1] = stats[1]; out_stats[2] = stats[2]; }
+    return ILM_OK;
+}
+
+// ilm_engine_render_particles_batch.  Every item is validated before anything is queued; then the items that have chunks become records
+// of the context's device table (RasterItem), their slot ranges laid back to back in whole setup blocks, with every item's quad counts
+// behind the table: ONE upload.  render_particles runs once over the concatenated range -- one pair count, one sort, one tile launch.
+int32_t ilm_engine_render_particles_batch(IlmHandle hengine, const IlmRasterizeItem* items, int32_t count, IlmHandle htarget, uint64_t* out_stats) {
+    ILM_TRACE_RANGE("ilm_engine_render_particles_batch");
+    Engine* e = from_handle<Engine>(hengine, kMagicEngine);
+    if (!e) return fail(ILM_ERR_INVALID_HANDLE, "not an engine handle");
+    Lightmap* m = from_handle<Lightmap>(htarget, kMagicLightmap);
+    if (!m) return fail(ILM_ERR_INVALID_HANDLE, "target is not a lightmap handle");
+    if (count < 0) return fail(ILM_ERR_INVALID_ARGUMENT, "count %d is negative", count);
+    if (count > 0 && !items) return fail(ILM_ERR_INVALID_ARGUMENT, "items is NULL");
+    Ctx* c = e->ctx;
+    if (m->ctx != c) return fail(ILM_ERR_INVALID_ARGUMENT, "engine and target belong to different contexts");
+    if ((m->width + 15) / 16 > 65535 || (m->height + 15) / 16 > 65535) return fail(ILM_ERR_OUT_OF_RANGE, "target too large");
+    std::vector<System*> systems((size_t)count);
+    long long blocks = 0;                   // setup blocks of 256 slots: each item's range is padded to whole blocks
+    size_t quad_words = 0, drawn = 0;
+    for (int i = 0; i < count; i++) {
+        const IlmRasterizeItem& it = items[i];
+        System* s = from_handle<System>(it.System, kMagicSystem);
+        if (!s) return fail(ILM_ERR_INVALID_HANDLE, "item %d: not a system handle", i);
+        if (s->engine != e) return fail(ILM_ERR_INVALID_ARGUMENT, "item %d: the system belongs to another engine", i);
+        char why[256];
+        const int32_t code = check_raster_item(s, it.QuadCounts, it.ChunkCount, &it.Params, why, sizeof(why));
+        if (code != ILM_OK) return fail(code, "item %d: %s", i, why);
+        systems[(size_t)i] = s;
+        if (it.ChunkCount == 0) continue;
+        drawn++;
+        blocks += ((long long)it.ChunkCount * (long long)e->slots + 255) / 256;
+        if (blocks * 256 > (long long)INT32_MAX)
+            return fail(ILM_ERR_TOO_MANY, "item %d: the batch's slots up to this item exceed the 32-bit slot index of the sort key", i);
+        if (it.QuadCounts) quad_words += (size_t)it.ChunkCount;
+    }
+    if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = 0;
+    if (drawn == 0) { e->last_render_items = count; e->last_render_sorts = e->last_render_tile_launches = 0; return ILM_OK; }
+    HIP_TRY(hipSetDevice(c->device));
+    for (int i = 0; i < count; i++)
+        if (items[i].ChunkCount > 0) { const int32_t rc = refresh_table(systems[(size_t)i]); if (rc != ILM_OK) return rc; }
+    // the table, then the quad counts (records are multiples of 8 bytes: the counts stay aligned)
+    const size_t table_bytes = sizeof(RasterItem) * drawn, bytes = table_bytes + sizeof(int32_t) * quad_words;
+    int32_t rc = reserve(c, c->d_raster_items, bytes, bytes * 2);
+    if (rc != ILM_OK) return rc;
+    void* host = nullptr;
+    int slot = -1;
+    rc = upload_small_begin(c, bytes, &host, &slot);
+    if (rc != ILM_OK) return rc;
+    RasterItem* records = static_cast<RasterItem*>(host);
+    int32_t* quads = reinterpret_cast<int32_t*>(static_cast<char*>(host) + table_bytes);
+    const int32_t* d_quads = reinterpret_cast<const int32_t*>(static_cast<const char*>(c->d_raster_items.p) + table_bytes);
+    size_t at = 0, quad_at = 0;
+    int32_t first_block = 0;
+    for (int i = 0; i < count; i++) {
+        const IlmRasterizeItem& it = items[i];
+        if (it.ChunkCount == 0) continue;
+        const System* s = systems[(size_t)i];
+        RasterItem& r = records[at++];
+        std::memset(&r, 0, sizeof(r));
+        r.chunk_bases = s->d_table.as<float*>();
+        if (it.QuadCounts) {
+            std::memcpy(quads + quad_at, it.QuadCounts, sizeof(int32_t) * (size_t)it.ChunkCount);
+            r.quad_counts = d_quads + quad_at;
+            quad_at += (size_t)it.ChunkCount;
+        }
+        r.bitmap = s->bitmap; r.bitmap_w = s->bitmap_w; r.bitmap_h = s->bitmap_h;
+        r.first_block = first_block; r.total_slots = it.ChunkCount * e->slots;
+        r.params = it.Params;
+        first_block += (r.total_slots + 255) / 256;
+    }
+    rc = upload_small_commit(c, c->d_raster_items.p, slot, bytes);
+    if (rc != ILM_OK) return rc;
+    RasterLaunch a;
+    std::memset(&a, 0, sizeof(a));
+    a.items = c->d_raster_items.as<RasterItem>(); a.item_count = (int32_t)drawn;
+    a.stride = e->stride; a.slots = e->slots; a.total_slots = first_block * 256;
+    a.target = m->texels; a.format = m->format; a.width = m->width; a.height = m->height;
+    a.tiles_x = (m->width + 15) / 16; a.tiles_y = (m->height + 15) / 16;
+    a.count_shaded = out_stats ? 1 : 0;
+    unsigned long long stats[3] = { 0, 0, 0 };
+    bool too_many = false;
+    HIP_TRY(render_particles(a, c->raster, c->main(), out_stats ? stats : nullptr, &too_many));
+    if (too_many) return fail(ILM_ERR_TOO_MANY, "more than 2^28 (quad, tile) pairs in the batch: the quads are too large for this path");
+    if (out_stats) { out_stats[0] = stats[0]; out_stats[1] = stats[1]; out_stats[2] = stats[2]; }
+    e->last_render_items = count;
+    e->last_render_sorts = e->last_render_tile_launches = a.pair_count > 0 ? 1 : 0;
+    return ILM_OK;
+}
+int32_t ilm_debug_last_render_batch(IlmHandle h, int32_t* out_items, int32_t* out_sorts, int32_t* out_tile_launches) {
+    Engine* e = from_handle<Engine>(h, kMagicEngine);
+    if (!e) return fail(ILM_ERR_INVALID_HANDLE, "not an engine handle");
+    if (out_items) *out_items = e->last_render_items;
+    if (out_sorts) *out_sorts = e->last_render_sorts;
+    if (out_tile_launches) *out_tile_launches = e->last_render_tile_launches;
     return ILM_OK;
 }
 

@@ -487,6 +487,16 @@ struct BrightnessScratch {
 
 // ---- particle rasterisation (raster.hip) ------------------------------------------------------------------------
 struct Sprite;
+// One item of ilm_engine_render_particles_batch as it lies in the context's device table (items without chunks are left out): what
+// RasterLaunch holds per call.  An item owns the blocks [first_block, first_block + ceil(total_slots / 256)) of the setup grid -- its slot
+// range is padded to whole blocks, so a block never straddles two items and the item of a block is one search over this column.
+struct RasterItem {
+    float* const* chunk_bases; const int32_t* quad_counts;         // as RasterLaunch
+    const float4* bitmap; int32_t bitmap_w, bitmap_h;
+    int32_t first_block, total_slots;
+    IlmRasterizeParams params;
+};
+static_assert(sizeof(RasterItem) % 8 == 0, "the quad counts behind the table stay aligned");
 struct RasterLaunch {
     float* const* chunk_bases; int64_t stride; int32_t chunk_count, slots, total_slots;
     const int32_t* quad_counts;         // device, per chunk; nullptr => every slot
@@ -503,6 +513,10 @@ struct RasterLaunch {
     uint32_t* tile_begin; uint32_t* tile_segments; uint32_t* tile_first_item; uint32_t* tile_multi; uint32_t* tile_first_partial;
     float* partials;                    // per partial slot: 256 x (premultiplied colour sum rgba, transmittance)
     int32_t work_items;                 // upper bound of the work items (grid of the shading kernel)
+    // The batch (ilm_engine_render_particles_batch): items != nullptr -- last, so that nothing the single call reads moves.  Then chunk_bases,
+    // quad_counts, params and bitmap are unused, total_slots is the padded total (256 x the setup grid) and a sprite's record carries its
+    // item's index (raster.hip, Sprite).
+    const RasterItem* items; int32_t item_count;
 };
 // device buffers the rasteriser keeps between calls (owned by the context)
 struct RasterScratch {

@@ -29,21 +29,37 @@ struct alignas(16) Sprite {
     float rounding;
     float frame_u, frame_v;     // frameTexCoord: offset of the animation frame inside the sheet
     float dither_frame;         // floor(index % 4) of premultipliedToDithered; index = the slot (ParticleEngine.cs:476-478)
+                                // (a batch's record holds the BITS item << 2 | index % 4 here: the tile kernel needs the sprite's item)
 };
 static_assert(sizeof(Sprite) == 64, "Sprite is 16 words");
 
 // VS_PosVelAttr, RasterizeParticleSystem.fx:61-148, for one slot: the sprite record and the number of tiles its clipped bounding
 // box touches (0: dead, degenerate or off-screen).
+// BATCH: the grid runs over the items' slot ranges back to back, each padded to whole blocks; the block finds its item in the table
+// (a search on blockIdx: scalar work) and takes chunk table, quad counts and params from it.  The arithmetic is the same text.
+template <bool BATCH>
 __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterLaunch a) {
     const int g = (int)blockIdx.x * 256 + (int)threadIdx.x;
     bool live = false;
     uint32_t count = 0;
-    if (g < a.total_slots) {
-        const int chunk = g / a.slots, slot = g - chunk * a.slots;
-        const int quads = a.quad_counts ? a.quad_counts[chunk] : a.slots;
-        const IlmRasterizeParams& p = a.params;
+    int item = 0, local = g, local_slots = a.total_slots;
+    if (BATCH) {
+        int hi = a.item_count;                      // the last item whose first block is <= this block
+        while (hi - item > 1) {
+            const int mid = (item + hi) >> 1;
+            if (a.items[mid].first_block <= (int)blockIdx.x) item = mid; else hi = mid;
+        }
+        local = ((int)blockIdx.x - a.items[item].first_block) * 256 + (int)threadIdx.x;
+        local_slots = a.items[item].total_slots;
+    }
+    float* const* const chunk_bases = BATCH ? a.items[item].chunk_bases : a.chunk_bases;
+    const int32_t* const quad_counts = BATCH ? a.items[item].quad_counts : a.quad_counts;
+    if (local < local_slots) {
+        const int chunk = local / a.slots, slot = local - chunk * a.slots;
+        const int quads = quad_counts ? quad_counts[chunk] : a.slots;
+        const IlmRasterizeParams& p = BATCH ? a.items[item].params : a.params;
         if (slot < quads) {
-            const float* base = a.chunk_bases[chunk];
+            const float* base = chunk_bases[chunk];
             const int64_t S = a.stride;
             const float life = base[3 * S + slot];
             if (!(life <= 0.0f)) {       // `life <= 0` rejects; a NaN life does not, as in the shader
@@ -94,7 +110,7 @@ __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterLaunch a)
                     float fy0 = floorf(sp.cy - ey - 0.5f) - 1.0f, fy1 = ceilf(sp.cy + ey - 0.5f) + 1.0f;
                     fx0 = fmaxf(fx0, 0.0f); fy0 = fmaxf(fy0, 0.0f);
                     fx1 = fminf(fx1, (float)(a.width - 1)); fy1 = fminf(fy1, (float)(a.height - 1));
-                    sp.dither_frame = (float)(slot & 3);
+                    sp.dither_frame = BATCH ? __uint_as_float(((uint32_t)item << 2) | (uint32_t)(slot & 3)) : (float)(slot & 3);
                     sp.ex = ex + 1.0f; sp.ey = ey + 1.0f;
                     uint2 rect = make_uint2(0u, 0u);
                     if ((fx0 <= fx1) && (fy0 <= fy1)) {
@@ -109,6 +125,8 @@ __global__ __launch_bounds__(256) void raster_setup_kernel(const RasterLaunch a)
             }
         }
         a.counts[g] = count;
+    } else if (BATCH) {
+        a.counts[g] = 0u;       // the padding behind an item's last slot: the scan and the emit run over it
     }
     if (a.count_shaded) {       // statistics only: 20 k same-address atomics serialise (~11 ns each)
         const unsigned long long m = __ballot(live);
@@ -235,7 +253,29 @@ __global__ __launch_bounds__(1024) void raster_tile_scan_kernel(const RasterLaun
 // (instrumentation since removed; see git history) showed 4.7 workgroups per CU in flight at 78 VGPRs and the pass waiting on LDS /
 // barriers rather than issuing: cfg2's frame 1.155 -> 1.062 ms (tools/ab_raster.sh).  Sprite records through scalar loads straight
 // from global memory instead of the LDS batch: 1.30 ms.
-template <int FORMAT>
+// BATCH: the run of a tile holds sprites of several items, each shaded and blended with its own item's state.  Every lane of a wave is at
+// the same sprite at the same step, so the state is wave-uniform: it is fetched from the item table with scalar loads when the sprite's
+// item (carried in the record's last word) differs from the previous sprite's -- once per item and tile where the items' runs follow
+// each other.  dst and the transmittance do not care whose fragment comes next: additive is the map with T = 1.
+struct ShadeState {
+    bool rounded, dithered, additive;
+    int filter;
+    float region_x, region_y, region_w, region_h;
+    float global_r, global_g, global_b, global_a;
+    const float4* bitmap; int bitmap_w, bitmap_h;
+    ILM_DEV void set(const IlmRasterizeParams& p, const float4* texels, int w, int h) {
+        rounded = p.RenderingOptions[0] != 0.0f;
+        dithered = p.RenderingOptions[1] >= 0.5f;
+        additive = p.BlendMode == ILM_BLEND_ADDITIVE;
+        filter = p.BitmapFilter;
+        region_x = p.BitmapTextureRegion.x; region_y = p.BitmapTextureRegion.y;
+        region_w = p.BitmapTextureRegion.z - region_x; region_h = p.BitmapTextureRegion.w - region_y;
+        global_r = p.GlobalColor.x; global_g = p.GlobalColor.y; global_b = p.GlobalColor.z; global_a = p.GlobalColor.w;
+        bitmap = texels; bitmap_w = w; bitmap_h = h;
+    }
+};
+
+template <int FORMAT, bool BATCH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void raster_tiles_kernel(const RasterLaunch a) {
     __shared__ Sprite batch[256];
     __shared__ uint8_t list[4][256];
@@ -274,6 +314,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const int filter = a.params.BitmapFilter;
     const float region_x = a.params.BitmapTextureRegion.x, region_y = a.params.BitmapTextureRegion.y;
     const float region_w = a.params.BitmapTextureRegion.z - region_x, region_h = a.params.BitmapTextureRegion.w - region_y;
+    // BATCH only: the state of the item whose sprite was shaded last.  (The single call keeps its own expressions above: read through this
+    // struct its registers were allocated differently and cfg2's frame read 1.5 % slower; as written its instructions are the ones it had.)
+    ShadeState st;
+    if (BATCH) st.set(a.params, a.bitmap, a.bitmap_w, a.bitmap_h);
+    uint32_t state_item = 0xFFFFFFFFu;
     uint32_t shaded = 0;
     for (int64_t base = begin; base < end; base += 256) {
         const int n = (int)((end - base < 256) ? (end - base) : 256);
@@ -331,10 +376,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 continue;
             const float4 c0 = quads[4 * here + 2], c1 = quads[4 * here + 3];
             struct { float r, g, b, a, rounding, frame_u, frame_v, dither_frame; } sp = { c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w };
+            if (BATCH) {
+                // (`here` is the same in every lane, so is the word; the whole wave is still here)
+                const uint32_t tag = (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(c1.w));
+                if ((tag >> 2) != state_item) {
+                    state_item = tag >> 2;
+                    const RasterItem& it = a.items[state_item];
+                    st.set(it.params, it.bitmap, it.bitmap_w, it.bitmap_h);
+                }
+                sp.dither_frame = (float)(tag & 3u);
+            }
             if (!covered)
                 continue;
             float alpha = 1.0f;
-            if (rounded) {
+            if (BATCH ? st.rounded : rounded) {
                 // computeCircularAlpha
                 const float distance = sqrtf((u * u) + (v * v));
                 const float power = fmaxf(sp.rounding, 0.01f);
@@ -343,16 +398,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 alpha = sat(1.0f - pow_pos(distance_from_edge, power));
             }
             float cr = sp.r, cg = sp.g, cb = sp.b, ca = sp.a;
-            if ((filter != ILM_BITMAP_NONE) && (ca > 0.0f)) {       // PS_Texture: `color.a > (1 / 512)`, an integer division
+            if (((BATCH ? st.filter : filter) != ILM_BITMAP_NONE) && (ca > 0.0f)) {       // PS_Texture: `color.a > (1 / 512)`, an integer division
                 // texCoord = lerp(region.xy, region.zw, unit / 2 + 0.5) + frameTexCoord, interpolated over the quad
-                const float tu = (region_x + (region_w * ((u / 2.0f) + 0.5f))) + sp.frame_u;
-                const float tv = (region_y + (region_h * ((v / 2.0f) + 0.5f))) + sp.frame_v;
-                const float4 t = bitmap_fetch(a.bitmap, a.bitmap_w, a.bitmap_h, tu, tv, filter);
-                cr = (cr * t.x) * a.params.GlobalColor.x; cg = (cg * t.y) * a.params.GlobalColor.y;
-                cb = (cb * t.z) * a.params.GlobalColor.z; ca = (ca * t.w) * a.params.GlobalColor.w;
+                if (BATCH) {
+                    const float tu = (st.region_x + (st.region_w * ((u / 2.0f) + 0.5f))) + sp.frame_u;
+                    const float tv = (st.region_y + (st.region_h * ((v / 2.0f) + 0.5f))) + sp.frame_v;
+                    const float4 t = bitmap_fetch(st.bitmap, st.bitmap_w, st.bitmap_h, tu, tv, st.filter);
+                    cr = (cr * t.x) * st.global_r; cg = (cg * t.y) * st.global_g;
+                    cb = (cb * t.z) * st.global_b; ca = (ca * t.w) * st.global_a;
+                } else {
+                    const float tu = (region_x + (region_w * ((u / 2.0f) + 0.5f))) + sp.frame_u;
+                    const float tv = (region_y + (region_h * ((v / 2.0f) + 0.5f))) + sp.frame_v;
+                    const float4 t = bitmap_fetch(a.bitmap, a.bitmap_w, a.bitmap_h, tu, tv, filter);
+                    cr = (cr * t.x) * a.params.GlobalColor.x; cg = (cg * t.y) * a.params.GlobalColor.y;
+                    cb = (cb * t.z) * a.params.GlobalColor.z; ca = (ca * t.w) * a.params.GlobalColor.w;
+                }
             }
             float sr = cr * alpha, sg = cg * alpha, sb = cb * alpha, sa = ca * alpha;
-            if (dithered) {
+            if (BATCH ? st.dithered : dithered) {
                 // premultipliedToDithered, RasterizeParticleSystem.fx:158-175, with Dither64 of Fracture's DitherCommon.fxh (outside the tree)
                 // = Jimenez' published frac(dot(float3(vpos, frame), uint3(33, 52, 25) / 64.0)); GET_VPOS = floor(vpos); every term is a
                 // multiple of 1/64 below 2^18, so the sum is exact in any order
@@ -368,7 +431,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             if (sa <= 0.0f)                                 // `result.a <= (1 / 512)`: an integer division in the shader, i.e. <= 0
                 continue;
             shaded++;
-            const float keep = additive ? 1.0f : (1.0f - sa);
+            const float keep = (BATCH ? st.additive : additive) ? 1.0f : (1.0f - sa);
             dst.x = sr + (dst.x * keep); dst.y = sg + (dst.y * keep);
             dst.z = sb + (dst.z * keep); dst.w = sa + (dst.w * keep);
             transmittance *= keep;
@@ -463,8 +526,23 @@ struct SaturatingAdd {
     }
 };
 
+template <bool BATCH>
+static void launch_tiles(const RasterLaunch& a, dim3 item_grid, dim3 tile_grid, dim3 block, hipStream_t stream) {
+    if (a.format == ILM_LIGHTMAP_FLOAT4) {
+        hipLaunchKernelGGL((raster_tiles_kernel<ILM_LIGHTMAP_FLOAT4, BATCH>), item_grid, block, 0, stream, a);
+        hipLaunchKernelGGL(raster_combine_kernel<ILM_LIGHTMAP_FLOAT4>, tile_grid, block, 0, stream, a);
+    } else if (a.format == ILM_LIGHTMAP_HALF4) {
+        hipLaunchKernelGGL((raster_tiles_kernel<ILM_LIGHTMAP_HALF4, BATCH>), item_grid, block, 0, stream, a);
+        hipLaunchKernelGGL(raster_combine_kernel<ILM_LIGHTMAP_HALF4>, tile_grid, block, 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((raster_tiles_kernel<ILM_LIGHTMAP_RGBA8, BATCH>), item_grid, block, 0, stream, a);
+        hipLaunchKernelGGL(raster_combine_kernel<ILM_LIGHTMAP_RGBA8>, tile_grid, block, 0, stream, a);
+    }
+}
+
 hipError_t render_particles(RasterLaunch& a, RasterScratch& s, hipStream_t stream, unsigned long long out_stats[3], bool* too_many) {
     *too_many = false;
+    const bool batch = a.items != nullptr;       // total_slots: the items' padded ranges back to back
     const size_t n = (size_t)a.total_slots;
     RASTER_TRY(grow(&s.sprites, &s.sprites_cap, n * sizeof(Sprite), stream));
     RASTER_TRY(grow(&s.counts, &s.counts_cap, n * sizeof(uint32_t), stream));
@@ -478,7 +556,8 @@ hipError_t render_particles(RasterLaunch& a, RasterScratch& s, hipStream_t strea
     a.offsets = static_cast<uint32_t*>(s.offsets);
     a.stats = static_cast<unsigned long long*>(s.stats);
     const dim3 block(256), slot_grid((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(raster_setup_kernel, slot_grid, block, 0, stream, a);
+    if (batch) hipLaunchKernelGGL(raster_setup_kernel<true>, slot_grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(raster_setup_kernel<false>, slot_grid, block, 0, stream, a);
     RASTER_TRY(hipGetLastError());
     size_t scan_bytes = 0;
     // saturating addition (associative): a total beyond 32 bits reads 0xFFFFFFFF instead of wrapping below the bound checked next
@@ -528,16 +607,8 @@ hipError_t render_particles(RasterLaunch& a, RasterScratch& s, hipStream_t strea
         RASTER_TRY(grow(&s.partials, &s.partials_cap, partial_slots * 5 * 256 * sizeof(float), stream));
         a.partials = static_cast<float*>(s.partials);
         const dim3 item_grid((unsigned)a.work_items), tile_grid((unsigned)tiles);
-        if (a.format == ILM_LIGHTMAP_FLOAT4) {
-            hipLaunchKernelGGL(raster_tiles_kernel<ILM_LIGHTMAP_FLOAT4>, item_grid, block, 0, stream, a);
-            hipLaunchKernelGGL(raster_combine_kernel<ILM_LIGHTMAP_FLOAT4>, tile_grid, block, 0, stream, a);
-        } else if (a.format == ILM_LIGHTMAP_HALF4) {
-            hipLaunchKernelGGL(raster_tiles_kernel<ILM_LIGHTMAP_HALF4>, item_grid, block, 0, stream, a);
-            hipLaunchKernelGGL(raster_combine_kernel<ILM_LIGHTMAP_HALF4>, tile_grid, block, 0, stream, a);
-        } else {
-            hipLaunchKernelGGL(raster_tiles_kernel<ILM_LIGHTMAP_RGBA8>, item_grid, block, 0, stream, a);
-            hipLaunchKernelGGL(raster_combine_kernel<ILM_LIGHTMAP_RGBA8>, tile_grid, block, 0, stream, a);
-        }
+        if (batch) launch_tiles<true>(a, item_grid, tile_grid, block, stream);
+        else launch_tiles<false>(a, item_grid, tile_grid, block, stream);
         RASTER_TRY(hipGetLastError());
     }
     if (out_stats) {

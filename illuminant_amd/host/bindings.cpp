@@ -156,7 +156,18 @@ PYBIND11_MODULE(_host, m) {
             return new ParticleEngine(ctx, cfg, rnd.data());
         }), py::keep_alive<1, 2>())
         .def_readonly("Configuration", &ParticleEngine::Configuration)
-        .def("UpdateSystems", &ParticleEngine::UpdateSystems, py::arg("systems"), py::arg("frameIndex"));
+        .def("UpdateSystems", &ParticleEngine::UpdateSystems, py::arg("systems"), py::arg("frameIndex"))
+        // RenderSystems(systems, target, blendMode, origin, scale, viewportScale, viewportPosition, wantStats) -> the systems' summed stats
+        .def("RenderSystems", [](ParticleEngine& e, const std::vector<ParticleSystem*>& systems, RenderTarget& target, int blendMode,
+                                 const std::vector<float>& origin, const std::vector<float>& scale, const std::vector<float>& viewportScale,
+                                 const std::vector<float>& viewportPosition, bool wantStats) {
+            ParticleRenderParameters rp;
+            rp.Origin = v2(origin); rp.Scale = v2(scale);
+            const ParticleRenderStats st = e.RenderSystems(systems, target, blendMode, &rp, v2(viewportScale), v2(viewportPosition), wantStats);
+            return py::make_tuple(st.LiveQuads, st.TilePairs, st.ShadedPixels);
+        }, py::arg("systems"), py::arg("target"), py::arg("blendMode") = (int)ILM_BLEND_ALPHA, py::arg("origin") = std::vector<float>{0, 0},
+           py::arg("scale") = std::vector<float>{1, 1}, py::arg("viewportScale") = std::vector<float>{1, 1},
+           py::arg("viewportPosition") = std::vector<float>{0, 0}, py::arg("wantStats") = false);
 
     py::class_<BezierF>(m, "BezierF").def(py::init<>())
         .def_readwrite("Count", &BezierF::Count).def_readwrite("Mode", &BezierF::Mode)

@@ -240,6 +240,27 @@ std::vector<UpdateResult> ParticleEngine::UpdateSystems(const std::vector<Partic
     Flush();
     return results;
 }
+ParticleRenderStats ParticleEngine::RenderSystems(const std::vector<ParticleSystem*>& systems, RenderTarget& target, int blendMode,
+                                                  const ParticleRenderParameters* rp, Vector2 viewportScale, Vector2 viewportPosition, bool wantStats) {
+    std::vector<std::vector<int32_t>> quads(systems.size());
+    std::vector<IlmRasterizeItem> items(systems.size());
+    for (size_t i = 0; i < systems.size(); i++) {
+        const ParticleSystem* s = systems[i];
+        if (&s->Engine != this) throw InvalidOperationException("RenderSystems: the system belongs to another engine");
+        quads[i] = s->GetRenderQuadCounts();
+        IlmRasterizeItem& it = items[i];
+        std::memset(&it, 0, sizeof(it));
+        it.System = s->Handle();
+        it.QuadCounts = quads[i].data();
+        it.ChunkCount = (int32_t)quads[i].size();
+        it.Params = s->GetRasterizeParams(blendMode, rp, viewportScale, viewportPosition);
+    }
+    uint64_t stats[3] = { 0, 0, 0 };
+    ThrowIfFailed(ilm_engine_render_particles_batch(handle, items.data(), (int32_t)items.size(), target.Handle(), wantStats ? stats : nullptr));
+    ParticleRenderStats st;
+    st.LiveQuads = stats[0]; st.TilePairs = stats[1]; st.ShadedPixels = stats[2];
+    return st;
+}
 
 // ClampedBezier1(BezierF), Bezier.cs:442-460
 IlmClampedBezier1 MakeClampedBezier1(const std::optional<BezierF>& src) {
@@ -1204,6 +1225,13 @@ IlmRasterizeParams ParticleSystem::GetRasterizeParams(int blendMode, const Rende
     return p;
 }
 
+std::vector<int32_t> ParticleSystem::GetRenderQuadCounts() const {
+    std::vector<int32_t> quads;
+    for (const Chunk& c : chunks)
+        quads.push_back(std::min(ChunkMaximumCount(), c.TotalSpawned + 1));      // RenderChunk, :880
+    return quads;
+}
+
 void ParticleSystem::SetBitmap(int width, int height, const IlmFloat4* texels) {
     ThrowIfFailed(ilm_system_set_bitmap(handle, texels, width, height));
 }
@@ -1213,9 +1241,7 @@ ParticleSystem::RenderStats ParticleSystem::Render(RenderTarget& target, int ble
     RenderStats st;
     if (chunks.empty())
         return st;
-    std::vector<int32_t> quads;
-    for (const Chunk& c : chunks)
-        quads.push_back(std::min(ChunkMaximumCount(), c.TotalSpawned + 1));      // RenderChunk, :880
+    const std::vector<int32_t> quads = GetRenderQuadCounts();
     const IlmRasterizeParams p = GetRasterizeParams(blendMode, rp, viewportScale, viewportPosition);
     uint64_t stats[3] = { 0, 0, 0 };
     ThrowIfFailed(ilm_render_particles(handle, quads.data(), (int32_t)quads.size(), &p, target.Handle(), wantStats ? stats : nullptr));

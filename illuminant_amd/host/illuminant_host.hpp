@@ -208,6 +208,10 @@ struct ParticleEngineConfiguration {
 // UpdateResult, ParticleSystem.cs:51-71
 struct UpdateResult { bool PerformedUpdate = false; float Timestamp = 0; };
 
+// ParticleRenderParameters, ParticleConfiguration.cs:305-312, and what a Render reports (ParticleSystem::RenderParameters / RenderStats)
+struct ParticleRenderParameters { Vector2 Origin{0, 0}, Scale{1, 1}; std::optional<float> StippleFactor; };
+struct ParticleRenderStats { uint64_t LiveQuads = 0, TilePairs = 0, ShadedPixels = 0; };
+
 // ParticleEngine.cs:24-141
 class ParticleEngine {
 public:
@@ -225,6 +229,12 @@ public:
     // the field bind, a chunk removal, a read-back -- submits the queue first (ParticleSystem::BeforeSystemChange).  The deferral
     // does not outlive the call: an exception out of an Update submits what was queued before it propagates.
     std::vector<UpdateResult> UpdateSystems(const std::vector<ParticleSystem*>& systems, int frameIndex);
+    // The same frame's Render loop (`s.Render(group, j++)`, same lines) as ONE ilm_engine_render_particles_batch: every system's item is
+    // what its Render passes -- GetRasterizeParams and the chunks' quad counts -- and the systems are blended onto `target` in the order
+    // given, as one draw list.  The stats are the sums of what the systems' Render calls report.
+    ParticleRenderStats RenderSystems(const std::vector<ParticleSystem*>& systems, RenderTarget& target, int blendMode = ILM_BLEND_ALPHA,
+                                      const ParticleRenderParameters* renderParams = nullptr, Vector2 viewportScale = Vector2{1, 1},
+                                      Vector2 viewportPosition = Vector2{0, 0}, bool wantStats = false);
 private:
     friend class ParticleSystem;
     bool deferring = false;
@@ -585,9 +595,8 @@ public:
     struct ReadbackView { const IlmReadbackDrawCall* Records = nullptr; int Count = 0; };
     ReadbackView PerformReadbackView() const;
     IlmReadbackParams GetReadbackParams() const;
-    // ParticleRenderParameters, ParticleConfiguration.cs:305-312
-    struct RenderParameters { Vector2 Origin{0, 0}, Scale{1, 1}; std::optional<float> StippleFactor; };
-    struct RenderStats { uint64_t LiveQuads = 0, TilePairs = 0, ShadedPixels = 0; };
+    using RenderParameters = ParticleRenderParameters;
+    using RenderStats = ParticleRenderStats;
     // Appearance.Texture.Instance for the textured techniques: width x height float4 texels, one level (the native layer binds
     // bitmaps without mips only); Appearance.TextureSize must say the same size
     void SetBitmap(int width, int height, const IlmFloat4* texels);
@@ -598,6 +607,8 @@ public:
                        Vector2 viewportScale = Vector2{1, 1}, Vector2 viewportPosition = Vector2{0, 0}, bool wantStats = false) const;
     // Uniforms.RasterizeParticleSystem + RenderingOptions + StippleFactor as Render binds them (Uniforms.cs:238-290, ParticleSystem.cs:254-271,1023-1032)
     IlmRasterizeParams GetRasterizeParams(int blendMode, const RenderParameters* renderParams, Vector2 viewportScale, Vector2 viewportPosition) const;
+    // quadCount of every chunk as RenderChunk draws it: min(ChunkMaximumCount, TotalSpawned + 1) (ParticleSystem.cs:880)
+    std::vector<int32_t> GetRenderQuadCounts() const;
     std::vector<IlmReadbackDrawCall> ReadbackResult;
     float ReadbackTimestamp = 0;
     IlmHandle Handle() const { return handle; }

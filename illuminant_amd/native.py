@@ -114,6 +114,8 @@ SYMBOLS = {
     "ilm_system_readback": (_I, [_H, _P, _I, _P, _P, _I, C.POINTER(_I)]),
     "ilm_system_readback_view": (_I, [_H, _P, _I, _P, C.POINTER(_P), C.POINTER(_I)]),
     "ilm_render_particles": (_I, [_H, _P, _I, _P, _H, _P]),
+    "ilm_engine_render_particles_batch": (_I, [_H, _P, _I, _H, _P]),
+    "ilm_debug_last_render_batch": (_I, [_H, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ilm_lightmap_clear": (_I, [_H, _P]),
     "ilm_ctx_set_light_ramp": (_I, [_H, _P, _I, _I]),
     "ilm_ctx_set_projector_texture": (_I, [_H, _P, _I, _I]),
@@ -319,6 +321,41 @@ class Engine:
         launches, rounds, fallback = C.c_int32(), C.c_int32(), C.c_int32()
         check(lib().ilm_debug_last_step_batch(self.handle, C.byref(launches), C.byref(rounds), C.byref(fallback)))
         return int(launches.value), int(rounds.value), int(fallback.value)
+
+    def render_particles_batch(self, items, target, want_stats=False):
+        """ilm_engine_render_particles_batch: the items' systems blended onto `target` as ONE draw list, in item / chunk / slot order.
+        `items` is a sequence of (system, params) or (system, params, quad_counts) or (system, params, quad_counts, chunk_count) -- the
+        arguments of render_particles -- or a ctypes array of abi.RasterizeItem (reusable from call to call; the caller keeps what its
+        QuadCounts point at alive).  Returns (live quads, pairs, shaded pixels) summed over the items when want_stats."""
+        if isinstance(items, C.Array):
+            packed, n, keep = items, len(items), None
+        else:
+            n, keep = len(items), []
+            packed = (abi.RasterizeItem * max(n, 1))()
+            for i, item in enumerate(items):
+                system, params = item[0], item[1]
+                q = item[2] if len(item) > 2 else None
+                chunk_count = item[3] if len(item) > 3 else None
+                if q is not None:
+                    q = np.ascontiguousarray(q, dtype=np.int32)
+                    keep.append(q)
+                    packed[i].QuadCounts = q.ctypes.data
+                if chunk_count is None:
+                    chunk_count = system.chunk_count()
+                packed[i].System = system.handle.value
+                packed[i].ChunkCount = int(chunk_count)
+                C.memmove(C.byref(packed[i], abi.RasterizeItem.Params.offset), C.byref(params), C.sizeof(abi.RasterizeParams))
+        stats = np.zeros(3, np.uint64)
+        check(lib().ilm_engine_render_particles_batch(self.handle, C.cast(packed, C.c_void_p), n, target.handle,
+                                                      _ptr(stats) if want_stats else None))
+        del keep
+        return tuple(int(x) for x in stats) if want_stats else None
+
+    def last_render_batch(self):
+        """ilm_debug_last_render_batch: (items, radix sorts, tile-kernel launches) of the engine's latest accepted batch."""
+        items, sorts, launches = C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().ilm_debug_last_render_batch(self.handle, C.byref(items), C.byref(sorts), C.byref(launches)))
+        return int(items.value), int(sorts.value), int(launches.value)
 
     def close(self):
         if self.handle.value:

@@ -39,7 +39,8 @@ extern "C" {
  * + ilm_ctx_set_light_blend_function, ILM_LIGHT_BLEND_* (subtractive, max and min light groups: LightSource.BlendMode);
  * + ilm_resolve_lighting_scaled, ILM_FILTER_* (the resolve onto a target of another size: RenderScale != 1);
  * + ilm_resolve_lighting_lut / IlmLUTBlending (the LUT-blended resolve over a dark and a bright colour LUT);
- * + ilm_sdf_set_filter, ilm_sdf_get_filter, ILM_SDF_FILTER_* (a fixed-point bilinear filter mode of the distance-field sampler).
+ * + ilm_sdf_set_filter, ilm_sdf_get_filter, ILM_SDF_FILTER_* (a fixed-point bilinear filter mode of the distance-field sampler);
+ * + ilm_engine_render_particles_batch, ilm_debug_last_render_batch / IlmRasterizeItem (a frame's particle systems rasterised as one draw list).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -1319,6 +1320,45 @@ typedef struct IlmRasterizeParams {
  * out_stats (may be NULL): [0] live quads, [1] (quad, tile) pairs, [2] shaded pixels (fragments not discarded). */
 int32_t ilm_render_particles(IlmHandle system, const int32_t* quad_counts, int32_t chunk_count, const IlmRasterizeParams* params,
                              IlmHandle target, uint64_t* out_stats);
+
+/* One system's draw inside ilm_engine_render_particles_batch: the arguments of ilm_render_particles. */
+typedef struct {
+    IlmHandle          System;
+    const int32_t*     QuadCounts;   /* ChunkCount entries, or NULL => every slot; as ilm_render_particles */
+    int32_t            ChunkCount;   /* the first ChunkCount chunks of System */
+    int32_t            _pad;
+    IlmRasterizeParams Params;       /* this item's technique, blend mode, colours, view transform */
+} IlmRasterizeItem;
+
+/* A frame's worth of ParticleSystem.Render in one call: the Render half of the loop ilm_engine_step_batch takes the Update half of
+ * (Scenes/ManySystemsManySpawners.cs:78-81, `s.Render(group, j++)` for 256 systems).  The batch is ONE draw list: the items' sprites
+ * concatenated in item, chunk, slot order.  A pixel's value: the target texel converted to fp32 once; every fragment of every item that
+ * is not discarded blended onto it in that order, in fp32, with its OWN item's state (BlendMode, RenderingOptions, BitmapFilter,
+ * BitmapTextureRegion, GlobalColor, its system's bitmap); one store conversion.  Setup, coverage, shading and discards are those of
+ * ilm_render_particles, operation for operation.  So:
+ *  - FLOAT4 target, no tile's run in the batch longer than one segment (2 048 (quad, tile) pairs): the texels are bit for bit what
+ *    ilm_render_particles(items[i] ...) for i = 0 .. count - 1 would leave.
+ *  - HALF4 / RGBA8 target: those calls round to the target format after every system, the batch rounds once -- a DEFINED difference
+ *    (the reference's ROP rounds after every quad: neither form is its bits).
+ *  - A tile whose run in the batch exceeds one segment is composed from partial results as in ilm_render_particles, the run cut every
+ *    2 048 pairs wherever item boundaries fall (additive is the partial with transmittance 1, so blend modes mix within a run).
+ *  - out_stats (may be NULL): [0..2] as ilm_render_particles, summed over the items -- exactly the sum of what those calls report.
+ * The same system may appear more than once (it is only read).  count == 0, and a batch without a live on-screen quad, succeed and
+ * leave every texel's bits alone.  One host synchronisation (the pair count) and one sort however many items there are; afterwards
+ * asynchronous on the context's stream unless out_stats is given.
+ * All items are validated before anything is queued, uploaded or changed; a refusal about an item names it in ilm_last_error() ("item 3:
+ * ...") and the target is untouched.  Engine and target handles are checked first (ILM_ERR_INVALID_HANDLE); then count < 0, items ==
+ * NULL with count > 0, a target of another context or beyond the single call's size bound; per item, a handle that is not a system
+ * (ILM_ERR_INVALID_HANDLE), a system of another engine (ILM_ERR_INVALID_ARGUMENT) and whatever ilm_render_particles refuses, with its
+ * code; over the batch, more than INT32_MAX slots -- each item's slots counted in whole blocks of 256 -- or more than 2^28 pairs
+ * (ILM_ERR_TOO_MANY). */
+int32_t ilm_engine_render_particles_batch(IlmHandle engine, const IlmRasterizeItem* items, int32_t count,
+                                          IlmHandle target, uint64_t* out_stats);
+/* Diagnostic: the engine's latest ilm_engine_render_particles_batch that was accepted -- its items (count), the radix sorts it ran and
+ * the tile-kernel launches it made: 1 and 1 for a batch that drew something, 0 and 0 for one with nothing to draw (count == 0, no
+ * chunks, nothing alive or on screen).  Any out pointer may be NULL. */
+int32_t ilm_debug_last_render_batch(IlmHandle engine, int32_t* out_items, int32_t* out_sorts, int32_t* out_tile_launches);
+
 /* Appearance.Texture for the textured techniques (PS_Texture / PS_TexturePoint, RasterizeParticleSystem.fx:191-226; frame selection
  * of VS_PosVelAttr, :112-139): width * height float4 texels, row-major, ONE level -- the reference samples with a mip filter whose
  * level comes from screen-space derivatives (hardware-defined) over a chain its texture loader builds; a bitmap without mips is

@@ -464,6 +464,15 @@ namespace Squared.Illuminant.Native {
         public fixed float AnimationRate[2];
     }
 
+    [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 216)]
+    public struct IlmRasterizeItem {
+        public ulong System;
+        public IntPtr QuadCounts;
+        public int ChunkCount;
+        public int _pad;
+        public IlmRasterizeParams Params;
+    }
+
     [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 48)]
     public struct IlmHDRConfiguration {
         public int Mode;
@@ -646,6 +655,8 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_readback (ulong system, int* elementCounts, int chunkCount, IlmReadbackParams* @params, IlmReadbackDrawCall* @out, int capacity, int* outCount);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_readback_view (ulong system, int* elementCounts, int chunkCount, IlmReadbackParams* @params, IlmReadbackDrawCall** outRecords, int* outCount);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_particles (ulong system, int* quadCounts, int chunkCount, IlmRasterizeParams* @params, ulong target, ulong* outStats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_engine_render_particles_batch (ulong engine, IlmRasterizeItem* items, int count, ulong target, ulong* outStats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_last_render_batch (ulong engine, int* outItems, int* outSorts, int* outTileLaunches);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_set_bitmap (ulong system, Vector4* texels, int width, int height);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_lightmap_clear (ulong lightmap, float* rgba);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_resolve_lighting (ulong srcLightmap, ulong dstLightmap, IlmHDRConfiguration* hdr, int rowBegin, int rowEnd);

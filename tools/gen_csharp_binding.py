@@ -19,7 +19,8 @@ HEADER = os.path.join(ROOT, "include", "illuminant_hip.h")
 OUT = os.path.join(ROOT, "integration", "IlluminantHip.cs")
 
 SCALARS = {"float": ("float", 4), "int32_t": ("int", 4), "uint32_t": ("uint", 4), "uint8_t": ("byte", 1), "uint64_t": ("ulong", 8),
-           "int64_t": ("long", 8), "IlmHandle": ("ulong", 8), "uint16_t": ("ushort", 2), "double": ("double", 8)}
+           "int64_t": ("long", 8), "IlmHandle": ("ulong", 8), "uint16_t": ("ushort", 2), "double": ("double", 8),
+           "void*": ("IntPtr", 8)}      # a pointer member, whatever it points to (IlmRasterizeItem.QuadCounts)
 # structs the reference already has: used as they are (same byte layout)
 REFERENCE_TYPES = {"IlmFloat4": ("Vector4", 16), "IlmMatrix": ("Matrix", 64), "IlmLightVertex": ("LightVertex", 128)}
 
@@ -53,6 +54,10 @@ def parse_fields(body):
     for decl in body.split(";"):
         decl = " ".join(decl.split())
         if not decl:
+            continue
+        ptr = re.match(r"(?:const )?\w+\s*\*\s*(\w+)$", decl)
+        if ptr:
+            out.append(("void*", ptr.group(1), []))
             continue
         m = re.match(r"(@UNION|[A-Za-z_]\w*)\s+(.*)$", decl)
         ctype, rest = m.group(1), m.group(2)
