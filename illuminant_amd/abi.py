@@ -21,6 +21,7 @@ MAX_ATTRACTORS = 16
 MAX_INLINE_POSITION_CONSTANTS = 4
 MAX_OPS = 4
 MAX_SPAWNS = 2
+MAX_SENSORS = 8          # ILM_MAX_SENSORS: sensors per ilm_system_sense call
 RANDOMNESS_WIDTH = 807
 RANDOMNESS_HEIGHT = 653
 

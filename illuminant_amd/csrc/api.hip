@@ -121,11 +121,12 @@ struct Ctx {
     BrightnessScratch brightness;                                  // brightness estimation: the luminance level and the statistics' scratch (brightness.hip)
     // parameter block of the distance-field generation pass (slice list, obstruction records, volumes, polygon vertices)
     DeviceScratch d_field_params;
+    DeviceScratch d_sense;                                         // ilm_system_sense: the counters [sensor][chunk], kSenseStride words apart
     // every block `reserve` grows: what ilm_ctx_destroy frees
-    std::array<DeviceScratch*, 22> scratch() {
+    std::array<DeviceScratch*, 23> scratch() {
         return { &staging, &d_recs, &d_light_partials, &d_light_tickets, &d_group_order, &d_pl_recs, &d_pl_count, &d_pl_blocks, &d_pl_quads,
                  &d_raster_quads, &d_raster_items, &d_rb, &d_rb_count, &d_rb_blocks, &d_rb_elems, &d_probe_pairs, &brightness.level, &brightness.mip,
-                 &brightness.work, &brightness.partials, &d_field_params, &d_projector_texture };
+                 &brightness.work, &brightness.partials, &d_field_params, &d_projector_texture, &d_sense };
     }
 };
 
@@ -314,6 +315,12 @@ struct System {
     uint32_t count_seq = 0; int counts_first = 0, counts_span = 0;
     int counts_n = 0; bool counts_pending = false;
     bool counts_valid = false;   // h_counts holds (or is about to receive) the counts of the last counting step
+    // Sensor counts (ilm_system_sense / _async) come back through page-locked host memory, two halves of h_sense_cap entries: the first
+    // receives the queued count ilm_system_poll_sense returns once sense_ev has passed, the second serves the blocking call, so a
+    // blocking call leaves a queued count alone.
+    uint32_t* h_sense = nullptr; size_t h_sense_cap = 0;
+    hipEvent_t sense_ev = nullptr;
+    int sense_n = 0; bool sense_pending = false;
 };
 
 SdfView make_sdf_view(const Sdf* f, const IlmDistanceFieldUniforms* df) {
@@ -1849,6 +1856,8 @@ int32_t ilm_system_destroy(IlmHandle h) {
         if (s->spawn_pattern[k]) (void)hipFree(s->spawn_pattern[k]);
     if (s->bitmap) (void)hipFree(s->bitmap);
     if (s->h_counts) (void)hipHostFree(s->h_counts);
+    if (s->h_sense) (void)hipHostFree(s->h_sense);
+    if (s->sense_ev) (void)hipEventDestroy(s->sense_ev);
     retire_handle(s);
     delete s;
     return ILM_OK;
@@ -2215,6 +2224,128 @@ int32_t ilm_system_poll_counts(IlmHandle h, uint32_t* out_counts, int32_t capaci
         out_counts[i] = (saturate16 && v > ref::kLiveCountSaturation) ? ref::kLiveCountSaturation : v;
     }
     s->counts_pending = false;
+    *out_ready = 1;
+    return ILM_OK;
+}
+
+// ---- sensors (PS_CollectParticles, CollectParticles.fx:10-38; Sensor, Transforms.cs:374-486) -----------------------------------
+
+// What ilm_system_sense and ilm_system_sense_async refuse, before anything is queued or changed; the chunk range as ilm_system_step
+// reads it (a negative count: every chunk).
+static int32_t check_sense(const System* s, int32_t first_chunk, int32_t chunk_count, const IlmAreaParams* sensors, int32_t sensor_count,
+                           int* first, int* count) {
+    if (!sensors) return fail(ILM_ERR_INVALID_ARGUMENT, "sensors is NULL");
+    if (sensor_count < 1 || sensor_count > ILM_MAX_SENSORS)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "sensor_count %d outside [1, %d]", sensor_count, ILM_MAX_SENSORS);
+    const int64_t n = (int64_t)s->chunks.size();
+    int64_t f = first_chunk, c = chunk_count;
+    if (c < 0) { f = 0; c = n; }
+    if (f < 0 || f + c > n)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "chunk range [%lld, %lld) outside [0, %lld)", (long long)f, (long long)(f + c), (long long)n);
+    for (int k = 0; k < sensor_count; k++) {
+        const IlmAreaParams& a = sensors[k];
+        if (a.AreaType < 0 || a.AreaType > 5) return fail(ILM_ERR_INVALID_ARGUMENT, "sensor %d: AreaType %d outside [0, 5]", k, a.AreaType);
+        bool finite = std::isfinite(a.AreaRotation) && std::isfinite(a.AreaFalloff);
+        for (int j = 0; j < 3; j++) finite = finite && std::isfinite(a.AreaCenter[j]) && std::isfinite(a.AreaSize[j]);
+        if (!finite) return fail(ILM_ERR_INVALID_ARGUMENT, "sensor %d: AreaCenter, AreaSize, AreaRotation or AreaFalloff is not finite", k);
+    }
+    *first = (int)f; *count = (int)c;
+    return ILM_OK;
+}
+
+// the page-locked table of a system's sensor counts, laid out like the device's (a counter every kSenseStride words): two halves of at
+// least `entries` counters; what the first half holds survives growth
+static int32_t reserve_sense_host(System* s, size_t entries) {
+    if (entries <= s->h_sense_cap) return ILM_OK;
+    Ctx* c = s->engine->ctx;
+    const size_t cap = entries < 64 ? 64 : entries * 2;
+    uint32_t* fresh = nullptr;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&fresh), sizeof(uint32_t) * 2 * cap * kSenseStride, hipHostMallocDefault));
+    if (s->h_sense) {
+        const hipError_t e = hipStreamSynchronize(c->main());      // a queued count may still be on its way into the old table
+        if (e != hipSuccess) { (void)hipHostFree(fresh); HIP_TRY(e); }
+        std::memcpy(fresh, s->h_sense, sizeof(uint32_t) * s->h_sense_cap * kSenseStride);
+        HIP_TRY(hipHostFree(s->h_sense));
+    }
+    s->h_sense = fresh; s->h_sense_cap = cap;
+    return ILM_OK;
+}
+
+// One pass of sense_kernel over chunks [first, first + count) behind everything the context has queued (main() joins the second
+// stepping stream), its table copied to `host` (page-locked).  The arguments have passed check_sense.
+static int32_t queue_sense(System* s, int first, int count, const IlmAreaParams* sensors, int sensor_count, uint32_t* host) {
+    Engine* e = s->engine; Ctx* c = e->ctx;
+    const size_t bytes = sizeof(uint32_t) * kSenseStride * (size_t)sensor_count * (size_t)count;
+    if (bytes == 0) return ILM_OK;
+    { const int32_t rc = reserve(c, c->d_sense, bytes, bytes < 65536 ? 65536 : bytes * 2); if (rc != ILM_OK) return rc; }
+    { const int32_t rc = refresh_table(s); if (rc != ILM_OK) return rc; }
+    SenseLaunch a;
+    std::memset(&a, 0, sizeof(a));
+    a.chunk_bases = s->d_table.as<float*>(); a.stride = e->stride; a.span = e->span; a.slots = e->slots;
+    a.first_chunk = first; a.chunk_count = count; a.sensor_count = sensor_count;
+    a.counts = c->d_sense.as<uint32_t>();
+    for (int k = 0; k < sensor_count; k++) a.sensors[k] = sensors[k];
+    HIP_TRY(hipMemsetAsync(a.counts, 0, bytes, c->main()));
+    HIP_TRY(launch_sense(a, c->main()));
+    HIP_TRY(hipMemcpyAsync(host, a.counts, bytes, hipMemcpyDeviceToHost, c->main()));
+    return ILM_OK;
+}
+
+int32_t ilm_system_sense(IlmHandle h, int32_t first_chunk, int32_t chunk_count, const IlmAreaParams* sensors, int32_t sensor_count,
+                         uint32_t* out_counts, int32_t capacity) {
+    ILM_TRACE_RANGE("ilm_system_sense");
+    System* s = from_handle<System>(h, kMagicSystem);
+    if (!s) return fail(ILM_ERR_INVALID_HANDLE, "not a system handle");
+    if (!out_counts) return fail(ILM_ERR_INVALID_ARGUMENT, "out_counts is NULL");
+    int first = 0, count = 0;
+    { const int32_t rc = check_sense(s, first_chunk, chunk_count, sensors, sensor_count, &first, &count); if (rc != ILM_OK) return rc; }
+    const size_t entries = (size_t)sensor_count * (size_t)count;
+    if (capacity < 0 || (size_t)capacity < entries)
+        return fail(ILM_ERR_INVALID_ARGUMENT, "capacity %d < %d sensors x %d chunks", capacity, sensor_count, count);
+    if (entries == 0) return ILM_OK;
+    Ctx* c = s->engine->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    { const int32_t rc = reserve_sense_host(s, entries); if (rc != ILM_OK) return rc; }
+    uint32_t* host = s->h_sense + s->h_sense_cap * kSenseStride;
+    { const int32_t rc = queue_sense(s, first, count, sensors, sensor_count, host); if (rc != ILM_OK) return rc; }
+    HIP_TRY(hipStreamSynchronize(c->main()));
+    for (size_t i = 0; i < entries; i++) out_counts[i] = host[i * kSenseStride];      // counts are not saturated
+    return ILM_OK;
+}
+
+int32_t ilm_system_sense_async(IlmHandle h, int32_t first_chunk, int32_t chunk_count, const IlmAreaParams* sensors, int32_t sensor_count) {
+    ILM_TRACE_RANGE("ilm_system_sense_async");
+    System* s = from_handle<System>(h, kMagicSystem);
+    if (!s) return fail(ILM_ERR_INVALID_HANDLE, "not a system handle");
+    int first = 0, count = 0;
+    { const int32_t rc = check_sense(s, first_chunk, chunk_count, sensors, sensor_count, &first, &count); if (rc != ILM_OK) return rc; }
+    const size_t entries = (size_t)sensor_count * (size_t)count;
+    Ctx* c = s->engine->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!s->sense_ev) HIP_TRY(hipEventCreateWithFlags(&s->sense_ev, hipEventDisableTiming));
+    { const int32_t rc = reserve_sense_host(s, entries); if (rc != ILM_OK) return rc; }
+    // a second queued count replaces the first: its copy into the same half is ordered behind the first one's on the stream
+    { const int32_t rc = queue_sense(s, first, count, sensors, sensor_count, s->h_sense); if (rc != ILM_OK) return rc; }
+    HIP_TRY(hipEventRecord(s->sense_ev, c->main()));
+    s->sense_n = (int)entries;
+    s->sense_pending = true;
+    return ILM_OK;
+}
+
+int32_t ilm_system_poll_sense(IlmHandle h, uint32_t* out_counts, int32_t capacity, int32_t* out_ready) {
+    ILM_TRACE_RANGE("ilm_system_poll_sense");
+    System* s = from_handle<System>(h, kMagicSystem);
+    if (!s) return fail(ILM_ERR_INVALID_HANDLE, "not a system handle");
+    if (!out_counts || !out_ready) return fail(ILM_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out_ready = 0;
+    if (!s->sense_pending) return fail(ILM_ERR_STATE, "no ilm_system_sense_async is outstanding");
+    if (capacity < s->sense_n) return fail(ILM_ERR_INVALID_ARGUMENT, "capacity %d < %d", capacity, s->sense_n);
+    HIP_TRY(hipSetDevice(s->engine->ctx->device));
+    const hipError_t e = hipEventQuery(s->sense_ev);
+    if (e == hipErrorNotReady) { (void)hipGetLastError(); return ILM_OK; }      // like Sensor.DoUpdateCount past its budget: never stall
+    HIP_TRY(e);
+    for (int i = 0; i < s->sense_n; i++) out_counts[i] = s->h_sense[(size_t)i * kSenseStride];
+    s->sense_pending = false;
     *out_ready = 1;
     return ILM_OK;
 }

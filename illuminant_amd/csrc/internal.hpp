@@ -172,6 +172,18 @@ hipError_t launch_soa_to_aos(const float* plane0, int64_t stride, float4* dst, i
 
 // standalone liveness count over the life plane of each chunk (CountLiveParticles.fx)
 hipError_t launch_count_live(float* const* chunk_bases, int64_t stride, int32_t span, int32_t slots, int32_t chunk_count, uint32_t* counts, hipStream_t stream);
+// Sensors (CollectParticles.fx:10-38; Sensor, Transforms.cs:374-486): sensor_count areas over chunks [first_chunk, first_chunk +
+// chunk_count) in ONE pass over the position plane and the category.  counts[(k * chunk_count + c) * kSenseStride] += slots of chunk
+// first_chunk + c that sensor k counts: every counter on a 128-byte line of its own, the table zero on entry.  Strength is not read.
+constexpr int kSenseStride = 32;     // in 32-bit words
+struct SenseLaunch {
+    float* const* chunk_bases; int64_t stride; int32_t span, slots;
+    int32_t first_chunk, chunk_count, sensor_count;
+    int32_t tiles_per_block;         // filled by launch_sense: consecutive 1 024-slot tiles of a chunk per workgroup
+    uint32_t* counts;
+    IlmAreaParams sensors[ILM_MAX_SENSORS];
+};
+hipError_t launch_sense(SenseLaunch& a, hipStream_t stream);
 // ordered live-slot compaction of one chunk (ballot + prefix sum); *out_count is a device counter
 hipError_t launch_live_slots(const float* life, int32_t slots, uint32_t* out_slots, uint32_t capacity, uint32_t* out_count, uint32_t* block_counts, hipStream_t stream);
 

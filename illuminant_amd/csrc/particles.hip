@@ -2485,6 +2485,107 @@ hipError_t launch_count_live(float* const* chunk_bases, int64_t stride, int32_t 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// sensors: the particles inside an area (PS_CollectParticles, CollectParticles.fx:10-38; Sensor, Transforms.cs:374-486)
+// ---------------------------------------------------------------------------------------------
+// The reference would count with an occlusion query: the pixels the shader does not discard.  A slot is kept when
+//   checkCategoryFilter(velocity.w, CategoryFilter)                                                   (:22)
+//   position.w > 1  -- life against ONE, as the text has it                                           (:32)
+//   1 - saturate(evaluateByTypeId(AreaType, position, ...) / AreaFalloff) > 0.01                      (:27-32)
+// which is count_live_kernel's reduction with a longer predicate.  One lane holds four consecutive slots, so a wave covers 256 and
+// every load is 16 bytes per lane; the life and the category are read first and x, y, z only by a wave in which some slot has a
+// life above one (20 bytes per slot at most, no other plane, no store to the state).  Every sensor of the launch is evaluated on
+// the loaded slots (the parameters are kernel arguments: scalar loads), per sensor one ballot + popcount per slot column.
+// A workgroup walks tiles_per_block consecutive 1 024-slot tiles of one chunk and keeps its waves' counts in LDS; at the end the
+// four waves meet in LDS and the workgroup issues ONE atomic add per sensor, none for a sensor it counted nothing for, into a counter
+// that has a 128-byte line of its own (kSenseStride).  Measured (tools/sensor_timing.py, docs/experiments.md 7.37): with one add per
+// wave and 256 slots into counters packed side by side, the adds alone -- 32 768 per sensor on one line at cfg4's share -- took 128 us
+// per sensor, five times the HBM floor of the whole pass.
+// AREA = false: the host has seen that no sensor of the launch has an area (AreaType 0).  evaluateByTypeId then returns 0 and
+// 1 - saturate(0 / falloff) is 1 for every finite falloff (0 / 0 = NaN, saturate(NaN) = 0, hlsl_math.hpp), so the third condition holds
+// for every slot: the instantiation holds no distance code and loads no coordinate.
+template <bool AREA>
+__global__ __launch_bounds__(256) void sense_kernel(const SenseLaunch a) {
+#pragma clang fp contract(off)
+    __shared__ uint32_t wave_counts[4][ILM_MAX_SENSORS];
+    const int chunk = (int)blockIdx.y;
+    const float* base = a.chunk_bases[a.first_chunk + chunk];
+    // a wave's counts, per sensor: touched by its first lane only until the workgroup meets (in LDS: the sensor loop stays a loop -- unrolled
+    // for counters in registers, the eight sensors' arithmetic interleaves into 155 VGPRs and three waves per SIMD)
+    if (threadIdx.x < 4 * ILM_MAX_SENSORS) (&wave_counts[0][0])[threadIdx.x] = 0u;
+    __syncthreads();
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    uint32_t* const counted = wave_counts[threadIdx.x >> 6];
+    const int tile_end = min(((int)blockIdx.x + 1) * a.tiles_per_block, a.span / 1024);
+    for (int tile = (int)blockIdx.x * a.tiles_per_block; tile < tile_end; tile++) {
+        const int i0 = (tile * 256 + (int)threadIdx.x) * 4;      // < span <= stride: the planes are padded to whole tiles
+        const float4 l4 = *reinterpret_cast<const float4*>(base + 3 * a.stride + i0);
+        const float4 c4 = *reinterpret_cast<const float4*>(base + 7 * a.stride + i0);
+        const float life[4] = { l4.x, l4.y, l4.z, l4.w }, cat[4] = { c4.x, c4.y, c4.z, c4.w };
+        // only the chunk's ChunkSize^2 slots are particles: the padding up to the stride is not counted
+        bool alive[4];
+        bool any_alive = false;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            alive[j] = (i0 + j < a.slots) && (life[j] > 1.0f);
+            any_alive = any_alive || alive[j];
+        }
+        if (__ballot(any_alive) == 0ull) continue;
+        float x[4] = {}, y[4] = {}, z[4] = {};
+        if (AREA) {
+            const float4 x4 = *reinterpret_cast<const float4*>(base + i0);
+            const float4 y4 = *reinterpret_cast<const float4*>(base + a.stride + i0);
+            const float4 z4 = *reinterpret_cast<const float4*>(base + 2 * a.stride + i0);
+            x[0] = x4.x; x[1] = x4.y; x[2] = x4.z; x[3] = x4.w;
+            y[0] = y4.x; y[1] = y4.y; y[2] = y4.z; y[3] = y4.w;
+            z[0] = z4.x; z[1] = z4.y; z[2] = z4.z; z[3] = z4.w;
+        }
+        for (int k = 0; k < a.sensor_count; k++) {
+            const IlmAreaParams& s = a.sensors[k];
+            bool pass[4];
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                pass[j] = alive[j] && category_ok(cat[j], s.CategoryFilter);
+                any = any || pass[j];
+            }
+            // a wave none of whose slots passes the filter and the life test skips the area
+            if (__ballot(any) == 0ull) continue;
+            if (AREA && s.AreaType != 0) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const float distance = evaluate_area(s.AreaType, mk3(x[j], y[j], z[j]), s);
+                    const float scaled = 1.0f - sat(distance / s.AreaFalloff);
+                    pass[j] = pass[j] && (scaled > 0.01f);
+                }
+            }
+            const uint32_t n = (uint32_t)__popcll(__ballot(pass[0])) + (uint32_t)__popcll(__ballot(pass[1])) +
+                               (uint32_t)__popcll(__ballot(pass[2])) + (uint32_t)__popcll(__ballot(pass[3]));
+            if (lane0 && n != 0u) counted[k] += n;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < a.sensor_count) {
+        const int k = (int)threadIdx.x;
+        const uint32_t total = wave_counts[0][k] + wave_counts[1][k] + wave_counts[2][k] + wave_counts[3][k];
+        if (total != 0u) atomicAdd(&a.counts[((size_t)k * (size_t)a.chunk_count + (size_t)chunk) * kSenseStride], total);
+    }
+}
+hipError_t launch_sense(SenseLaunch& a, hipStream_t stream) {
+    if (a.chunk_count <= 0 || a.sensor_count <= 0) return hipSuccess;
+    if (a.chunk_count > 65535 || a.sensor_count > ILM_MAX_SENSORS) return hipErrorInvalidValue;
+    bool area = false;
+    for (int k = 0; k < a.sensor_count; k++) area = area || (a.sensors[k].AreaType != 0);
+    // enough workgroups to fill the device (about 2 048), then up to eight tiles each: fewer, fuller atomic adds
+    const int tiles = a.span / 1024;
+    const long long total_tiles = (long long)tiles * a.chunk_count;
+    a.tiles_per_block = (int)std::min<long long>(8, std::max<long long>(1, total_tiles / 2048));
+    const dim3 grid((unsigned)((tiles + a.tiles_per_block - 1) / a.tiles_per_block), (unsigned)a.chunk_count);
+    if (area) hipLaunchKernelGGL(sense_kernel<true>, grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(sense_kernel<false>, grid, dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
 // Single workgroup of 1024 threads walks the chunk in 1024-slot tiles keeping a
 // running base, so the output is in ascending slot order (deterministic):
 // per-wave ballot -> popcount prefix inside the wave, LDS scan across the 16 waves.

@@ -229,6 +229,7 @@ PYBIND11_MODULE(_host, m) {
     py::class_<ParticleTransform>(m, "ParticleTransform")
         .def_readwrite("IsActive", &ParticleTransform::IsActive).def_readwrite("IsActive2", &ParticleTransform::IsActive2)
         .def_readwrite("Label", &ParticleTransform::Label).def_property_readonly("IsValid", &ParticleTransform::IsValid)
+        .def_readonly("IsAnalyzer", &ParticleTransform::IsAnalyzer)
         .def("Reset", &ParticleTransform::Reset);
     py::class_<ParticleAreaTransform, ParticleTransform>(m, "ParticleAreaTransform")
         .def_readwrite("Strength", &ParticleAreaTransform::Strength)
@@ -254,6 +255,10 @@ PYBIND11_MODULE(_host, m) {
 
     py::class_<SpatialNoise, Noise>(m, "SpatialNoise").def(py::init<uint64_t>(), py::arg("seed") = 1)
         VEC_PROP(SpatialNoise, SpaceScale, 2);
+    py::class_<Sensor, ParticleAreaTransform>(m, "Sensor").def(py::init<>())
+        .def_property_readonly("Count", &Sensor::Count).def_property_readonly("PreviousCount", &Sensor::PreviousCount)
+        .def("AfterFrame", &Sensor::AfterFrame)
+        .def("GetAreaParams", [](const Sensor& s) { IlmAreaParams a; s.FillSensor(a); return py::bytes((const char*)&a, sizeof(a)); });
     py::class_<MatrixMultiply, ParticleAreaTransform>(m, "MatrixMultiply").def(py::init<>())
         .def_readwrite("CyclesPerSecond", &MatrixMultiply::CyclesPerSecond)
         .def_property("Position", [](const MatrixMultiply& t) { return std::vector<float>(t.Position.m, t.Position.m + 16); },
@@ -359,6 +364,8 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("TotalSpawnCount", &ParticleSystem::TotalSpawnCount)
         .def_readwrite("DeadFrameThreshold", &ParticleSystem::DeadFrameThreshold)
         .def_readwrite("BlockingLivenessReadback", &ParticleSystem::BlockingLivenessReadback)
+        .def_readwrite("BlockingSensorReadback", &ParticleSystem::BlockingSensorReadback)
+        .def("AfterFrame", &ParticleSystem::AfterFrame)
         .def_readonly("LastDeltaTimeSeconds", &ParticleSystem::LastDeltaTimeSeconds)
         // Transforms list: the Python side keeps the objects alive (AddTransform keeps a reference)
         .def("AddTransform", [](ParticleSystem& s, ParticleTransform* t) { s.Transforms.push_back(t); }, py::keep_alive<1, 2>())

@@ -304,6 +304,16 @@ void ParticleAreaTransform::FillArea(IlmAreaParams& a) const {
     a.CategoryFilter[0] = cf.X; a.CategoryFilter[1] = cf.Y;
 }
 
+// Sensor.AfterFrame, Transforms.cs:424-441; the count that has arrived plays DoUpdateCount's sum (:443-477)
+void Sensor::AfterFrame() {
+    if (IsActive && IsActive2) {
+        if (arrived) previousCount = std::exchange(count, *arrived);       // :473
+    } else {
+        previousCount = std::exchange(count, 0);                            // :440
+    }
+    arrived.reset();
+}
+
 // FMA.SetParameters, Transforms.cs:38-45
 bool FMA::FillOp(IlmTransformOp& op, double) {
     std::memset(&op, 0, sizeof(op));
@@ -1054,7 +1064,8 @@ ParticleSystem::UpdateResult ParticleSystem::Update(int frameIndex) {
     // UpdateChunk (:791-856) for every chunk: transforms in list order, then exactly one update technique
     std::vector<IlmTransformOp> ops;
     for (Transforms::ParticleTransform* t : Transforms) {
-        const bool shouldSkip = !t->IsActive || !t->IsActive2 || t->IsSpawner() || !t->IsValid();
+        // (an analyzer changes no state: the sensors are evaluated after the step, QueueSensors)
+        const bool shouldSkip = !t->IsActive || !t->IsActive2 || t->IsSpawner() || !t->IsValid() || t->IsAnalyzer;
         if (shouldSkip) continue;
         IlmTransformOp op;
         if (t->FillOp(op, now))
@@ -1081,8 +1092,10 @@ ParticleSystem::UpdateResult ParticleSystem::Update(int frameIndex) {
     // One launch when everything fits a descriptor; otherwise earlier launches carry the surplus spawn records
     // and transforms (pass order is preserved: all spawns, then transforms in order, update last).
     size_t spawnPos = 0, opPos = 0;
-    if (chunks.empty())
+    if (chunks.empty()) {
+        QueueSensors();
         return UpdateResult{ true, (float)now };
+    }
     for (;;) {
         const size_t spawnsLeft = records.size() - spawnPos, opsLeft = ops.size() - opPos;
         const bool lastLaunch = (spawnsLeft <= ILM_MAX_SPAWNS) && (opsLeft <= ILM_MAX_OPS);
@@ -1114,6 +1127,7 @@ ParticleSystem::UpdateResult ParticleSystem::Update(int frameIndex) {
     }
     for (Chunk& c : chunks)
         c.ApproximateMaximumLife -= Configuration.LifeDecayPerSecond * (float)actualDeltaTimeSeconds;
+    QueueSensors();
 
     if (Configuration.AutoReadback) {     // MaybePerformReadback(timestamp), ParticleSystem.cs:625-628
         ReadbackTimestamp = (float)now;
@@ -1127,6 +1141,65 @@ ParticleSystem::UpdateResult ParticleSystem::Update(int frameIndex) {
         for (const Chunk& c : chunks) livenessChunkIds.push_back(c.ID);
     }
     return UpdateResult{ true, (float)now };
+}
+
+// The active sensors of the transform list on the state the update's step leaves (Transforms::Sensor's comment has the decisions):
+// groups of ILM_MAX_SENSORS, the last one queued behind the step, the ones before it counted at once.
+void ParticleSystem::QueueSensors() {
+    std::vector<Transforms::Sensor*> sensors;
+    for (Transforms::ParticleTransform* t : Transforms)
+        if (t->IsAnalyzer && t->IsActive && t->IsActive2)
+            if (auto* s = dynamic_cast<Transforms::Sensor*>(t)) sensors.push_back(s);
+    if (sensors.empty()) return;
+    queuedSensors.clear(); countedSensors.clear();
+    queuedSensorChunks = (int)chunks.size();
+    sensorsPending = true;
+    if (chunks.empty()) {       // nothing to count over
+        for (Transforms::Sensor* s : sensors) countedSensors.emplace_back(s, 0);
+        return;
+    }
+    BeforeSystemChange();       // the step may still sit in UpdateSystems' queue: it runs first
+    for (size_t first = 0; first < sensors.size(); first += ILM_MAX_SENSORS) {
+        const size_t n = std::min<size_t>(sensors.size() - first, ILM_MAX_SENSORS);
+        IlmAreaParams params[ILM_MAX_SENSORS];
+        for (size_t k = 0; k < n; k++) sensors[first + k]->FillSensor(params[k]);
+        if (first + n == sensors.size()) {
+            ThrowIfFailed(ilm_system_sense_async(handle, 0, -1, params, (int32_t)n));
+            queuedSensors.assign(sensors.begin() + (std::ptrdiff_t)first, sensors.end());
+        } else {
+            std::vector<uint32_t> table(n * chunks.size());
+            ThrowIfFailed(ilm_system_sense(handle, 0, -1, params, (int32_t)n, table.data(), (int32_t)table.size()));
+            for (size_t k = 0; k < n; k++) {
+                long total = 0;
+                for (size_t c = 0; c < chunks.size(); c++) total += table[k * chunks.size() + c];
+                countedSensors.emplace_back(sensors[first + k], (int)total);
+            }
+        }
+    }
+}
+
+// _AfterFrameHandler, ParticleSystem.cs:763-783
+void ParticleSystem::AfterFrame() {
+    if (sensorsPending) {
+        int32_t ready = 1;
+        std::vector<uint32_t> table(queuedSensors.size() * (size_t)queuedSensorChunks);
+        if (!queuedSensors.empty()) {
+            if (BlockingSensorReadback) Engine.Context.Sync();
+            ThrowIfFailed(ilm_system_poll_sense(handle, table.data(), (int32_t)table.size(), &ready));
+        }
+        if (ready) {
+            for (const auto& counted : countedSensors) counted.first->Deliver(counted.second);
+            for (size_t k = 0; k < queuedSensors.size(); k++) {
+                long total = 0;
+                for (int c = 0; c < queuedSensorChunks; c++) total += table[k * (size_t)queuedSensorChunks + (size_t)c];
+                queuedSensors[k]->Deliver((int)total);
+            }
+            sensorsPending = false;
+            queuedSensors.clear(); countedSensors.clear();
+        }
+    }
+    for (Transforms::ParticleTransform* t : Transforms)
+        t->AfterFrame();
 }
 
 // the part of FillReadbackResult that runs before its loop, ParticleReadback.cs:80-115

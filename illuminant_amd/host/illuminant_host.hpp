@@ -308,10 +308,12 @@ class ParticleTransform {
 public:
     virtual ~ParticleTransform() {}
     bool IsActive = true, IsActive2 = true;
+    bool IsAnalyzer = false;                 // ParticleTransform.cs:223: reads the state, changes none of it (Sensor)
     std::string Label;
     virtual bool IsValid() const = 0;
     virtual bool IsSpawner() const { return false; }
     virtual void Reset() {}
+    virtual void AfterFrame() {}             // ParticleTransform.cs:276, called by ParticleSystem::AfterFrame
     // the SetParameters half that fills the native op (false => not representable as an op)
     virtual bool FillOp(IlmTransformOp& op, double now) { (void)op; (void)now; return false; }
 };
@@ -535,6 +537,32 @@ public:
     bool FillOp(IlmTransformOp& op, double now) override;
 };
 
+// Sensor, Transforms.cs:374-486 (technique CollectParticles, CollectParticles.fx:10-46): how many particles of the filter's categories
+// are inside the area.  The reference never begins its occlusion query (BeforeUpdateChunk / AfterUpdateChunk return at once, :479-485;
+// ActiveQuery is never assigned), so its Count stays 0, and an analyzer pass would bind chunk.Previous without rotating the buffers
+// (ParticleSystem.cs:454-458) -- the state BEFORE the preceding pass, which a fused step never materialises.  Decisions of this mirror:
+//  * a sensor in a system's transform list is skipped when the step's op list is built (an analyzer changes no state);
+//  * after ParticleSystem::Update's step all active sensors of the system are evaluated on the state the update LEAVES, one
+//    ilm_system_sense_async per group of up to ILM_MAX_SENSORS sensors; of more than that, the groups before the last take the blocking
+//    ilm_system_sense (the native layer holds one queued count per system);
+//  * ParticleSystem::AfterFrame polls once per frame and hands each sensor what has arrived, summed over the chunks;
+//  * the category filter and the area come from ParticleAreaTransform's parameter path (FillArea); Strength is not read.
+// AfterFrame (:424-441, DoUpdateCount :443-477): an active sensor takes the count that has arrived, its old Count becoming PreviousCount
+// (:473), and keeps both when nothing has; an inactive one does PreviousCount = exchange(Count, 0) (:440).
+class Sensor : public ParticleAreaTransform {
+public:
+    Sensor() { IsAnalyzer = true; }                                    // :400-402
+    int Count() const { return count; }
+    int PreviousCount() const { return previousCount; }
+    void Reset() override { previousCount = count = 0; }               // :404-406
+    void AfterFrame() override;
+    void FillSensor(IlmAreaParams& a) const { FillArea(a); }
+    void Deliver(int arrivedCount) { arrived = arrivedCount; }         // by ParticleSystem::AfterFrame, before AfterFrame()
+private:
+    int previousCount = 0, count = 0;
+    std::optional<int> arrived;
+};
+
 }  // namespace Transforms
 
 // ParticleSystem.cs:48-1072 (update path), ParticleSpawning.cs, ParticleLiveness.cs
@@ -546,6 +574,9 @@ public:
     // true: wait for the liveness counts at the next Update (deterministic, for tests); false: poll them without
     // stalling the stream, as the reference's LivenessDataReadbackWorkItem does (ParticleWorkItems.cs:98-135)
     bool BlockingLivenessReadback = false;
+    // the same choice for the sensors' counts in AfterFrame: true waits for the queued count, false polls it once (Sensor.DoUpdateCount
+    // gives up after 5 ms, Transforms.cs:443-477)
+    bool BlockingSensorReadback = false;
 
     struct Chunk {   // ParticleSystem.cs:148-240
         int ID = 0;
@@ -584,6 +615,9 @@ public:
     int Spawn(int particleCount, const IlmFloat4* positions, const IlmFloat4* velocities, const IlmFloat4* colors);
     // Update, ParticleSystem.cs:630-761.  frameIndex plays DeviceManager.FrameIndex.
     UpdateResult Update(int frameIndex);
+    // _AfterFrameHandler, ParticleSystem.cs:763-783: once per frame after Update -- polls the sensors' queued count (ilm_system_poll_sense)
+    // and calls every transform's AfterFrame
+    void AfterFrame();
     void Clear() { isClearPending = true; }   // ParticleSystem.cs:1000-1003
     // AutoReadback / ReadbackResult (ParticleReadback.cs:21-71) reduced to a synchronous plane download
     void Readback(int chunkIndex, int plane, IlmFloat4* dst) const;
@@ -638,7 +672,13 @@ private:
     void ProcessLatestLivenessInfo(Chunk& c);
     void FillSystemUniforms(IlmStepDesc& d, double deltaTimeSeconds) const;
     void Launch(const IlmStepDesc& d);
+    void QueueSensors();
 
+    // the sensors' count in flight: the sensors of the queued (last) group, then what the blocking groups before it counted
+    std::vector<Transforms::Sensor*> queuedSensors;
+    std::vector<std::pair<Transforms::Sensor*, int>> countedSensors;
+    int queuedSensorChunks = 0;
+    bool sensorsPending = false;
     IlmHandle handle = 0;
     std::vector<Chunk> chunks;
     std::vector<int> chunksToReap;   // chunk IDs

@@ -71,6 +71,9 @@ SYMBOLS = {
     "ilm_system_live_counts": (_I, [_H, _P, _I, _I]),
     "ilm_system_step_counts": (_I, [_H, _P, _I, _I]),
     "ilm_system_poll_counts": (_I, [_H, _P, _I, _I, C.POINTER(_I)]),
+    "ilm_system_sense": (_I, [_H, _I, _I, _P, _I, _P, _I]),
+    "ilm_system_sense_async": (_I, [_H, _I, _I, _P, _I]),
+    "ilm_system_poll_sense": (_I, [_H, _P, _I, C.POINTER(_I)]),
     "ilm_chunk_live_slots": (_I, [_H, _I, _P, _I, C.POINTER(_I)]),
     "ilm_sdf_create": (_I, [_H, _I, _I, _I, C.POINTER(_H)]),
     "ilm_sdf_upload": (_I, [_H, _P]),
@@ -488,6 +491,37 @@ class System:
         ready = C.c_int32()
         check(lib().ilm_system_poll_counts(self.handle, _ptr(out), out.shape[0], 1 if saturate16 else 0, C.byref(ready)))
         return out[:n] if ready.value else None
+
+    def _sense_args(self, sensors, first_chunk, chunk_count):
+        n = len(sensors)
+        packed = (abi.AreaParams * max(n, 1))()
+        for k, a in enumerate(sensors):
+            C.memmove(C.byref(packed, k * C.sizeof(abi.AreaParams)), C.byref(a), C.sizeof(abi.AreaParams))
+        chunks = self.chunk_count() if chunk_count < 0 else chunk_count
+        return packed, n, max(chunks, 0)
+
+    def sense(self, sensors, first_chunk=0, chunk_count=-1):
+        """ilm_system_sense: (sensors, chunks of the range) uint32 -- the slots each abi.AreaParams of `sensors` counts in each chunk
+        (CollectParticles.fx: category filter, life > 1, 1 - saturate(distance / falloff) > 0.01; Strength is not read)."""
+        packed, n, chunks = self._sense_args(sensors, first_chunk, chunk_count)
+        out = np.zeros(max(n * chunks, 1), dtype=np.uint32)
+        check(lib().ilm_system_sense(self.handle, first_chunk, chunk_count, C.cast(packed, C.c_void_p), n, _ptr(out), n * chunks))
+        return out[:n * chunks].reshape(n, chunks)
+
+    def sense_async(self, sensors, first_chunk=0, chunk_count=-1):
+        """ilm_system_sense_async: the same count queued behind the system's pending work; poll_sense returns it.  A second queued
+        count replaces the first."""
+        packed, n, chunks = self._sense_args(sensors, first_chunk, chunk_count)
+        check(lib().ilm_system_sense_async(self.handle, first_chunk, chunk_count, C.cast(packed, C.c_void_p), n))
+        self._sense_shape = (n, chunks)
+
+    def poll_sense(self):
+        """ilm_system_poll_sense, non-blocking: the queued count's (sensors, chunks) table, or None while the GPU is still busy."""
+        n, chunks = self._sense_shape
+        out = np.zeros(max(n * chunks, 1), dtype=np.uint32)
+        ready = C.c_int32()
+        check(lib().ilm_system_poll_sense(self.handle, _ptr(out), n * chunks, C.byref(ready)))
+        return out[:n * chunks].reshape(n, chunks) if ready.value else None
 
     def live_slots(self, chunk):
         out = np.zeros(self.engine.slots, dtype=np.uint32)

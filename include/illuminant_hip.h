@@ -40,7 +40,8 @@ extern "C" {
  * + ilm_resolve_lighting_scaled, ILM_FILTER_* (the resolve onto a target of another size: RenderScale != 1);
  * + ilm_resolve_lighting_lut / IlmLUTBlending (the LUT-blended resolve over a dark and a bright colour LUT);
  * + ilm_sdf_set_filter, ilm_sdf_get_filter, ILM_SDF_FILTER_* (a fixed-point bilinear filter mode of the distance-field sampler);
- * + ilm_engine_render_particles_batch, ilm_debug_last_render_batch / IlmRasterizeItem (a frame's particle systems rasterised as one draw list).
+ * + ilm_engine_render_particles_batch, ilm_debug_last_render_batch / IlmRasterizeItem (a frame's particle systems rasterised as one draw list);
+ * + ilm_system_sense, ilm_system_sense_async, ilm_system_poll_sense, ILM_MAX_SENSORS (particle sensors: Transforms.Sensor counted on the device).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -487,6 +488,35 @@ int32_t ilm_system_step_counts(IlmHandle system, uint32_t* out_counts, int32_t c
  * LivenessDataReadbackWorkItem, ParticleWorkItems.cs:98-135): *out_ready = 1 and the counts are
  * written when the last counting step has finished on the GPU, else *out_ready = 0. */
 int32_t ilm_system_poll_counts(IlmHandle system, uint32_t* out_counts, int32_t capacity, int32_t saturate16, int32_t* out_ready);
+
+/* Sensors (Sensor, Illuminant/Particles/Transforms.cs:374-486; technique CollectParticles, Illuminant/Shaders/CollectParticles.fx:10-46):
+ * how many particles are inside an area.  The reference means to count with an occlusion query, i.e. the pixels PS_CollectParticles does
+ * not discard; a slot is counted if and only if (CollectParticles.fx:22-37)
+ *   checkCategoryFilter(velocity.w, CategoryFilter),
+ *   position.w > 1  (the life against ONE, as the text has it), and
+ *   1 - saturate(evaluateByTypeId(AreaType, position, AreaCenter, AreaSize, AreaRotation) / AreaFalloff) > 0.01
+ * with the scalar AreaRotation promoted to (r, r, r, r) as in FMA and saturate(NaN) = 0: AreaType 0 with the effect default AreaFalloff 0
+ * (0 / 0) counts every slot the first two conditions keep.  Strength is no uniform of that shader and is not read.
+ * The C# never begins a query (BeforeUpdateChunk / AfterUpdateChunk return at once, Transforms.cs:479-485, ActiveQuery is never
+ * assigned), so the reference's Count stays 0, and an analyzer pass would bind chunk.Previous without rotating the buffers
+ * (ParticleSystem.cs:454-458); these entries count over THE STATE THE SYSTEM HOLDS WHEN THEY RUN: behind everything queued before. */
+#define ILM_MAX_SENSORS 8
+/* CollectParticles.fx:10-46, Transforms.cs:374-486.  Blocking: up to ILM_MAX_SENSORS sensors over chunks [first_chunk, first_chunk +
+ * chunk_count) (chunk_count < 0: every chunk) in one pass that reads the position plane and the category and writes no state.
+ * out_counts (host) is laid out [sensor_count][chunks of the range]; capacity is in entries; counts are not saturated.
+ * ILM_ERR_INVALID_ARGUMENT: a NULL pointer, sensor_count outside 1..ILM_MAX_SENSORS, a chunk range outside the system, a capacity below
+ * sensor_count x chunks, an AreaType outside 0..5, or an AreaCenter, AreaSize, AreaRotation or AreaFalloff that is not finite.  A refusal
+ * leaves counts and state untouched. */
+int32_t ilm_system_sense(IlmHandle system, int32_t first_chunk, int32_t chunk_count, const IlmAreaParams* sensors, int32_t sensor_count,
+                         uint32_t* out_counts, int32_t capacity);
+/* CollectParticles.fx:10-46, Transforms.cs:374-486.  The same count queued behind the system's pending work (a step on either of the
+ * context's streams) without waiting for it -- what Sensor.AfterFrame hands to DoUpdateCount (Transforms.cs:424-477).  A second queued
+ * count replaces the first.  Refuses what ilm_system_sense refuses. */
+int32_t ilm_system_sense_async(IlmHandle system, int32_t first_chunk, int32_t chunk_count, const IlmAreaParams* sensors, int32_t sensor_count);
+/* CollectParticles.fx:10-46, Transforms.cs:443-477 (DoUpdateCount).  Non-blocking, like ilm_system_poll_counts: *out_ready = 1 and the
+ * queued count's table is written when it has finished on the GPU, else *out_ready = 0.  ILM_ERR_STATE when nothing is queued;
+ * ILM_ERR_INVALID_ARGUMENT for a NULL pointer or a capacity below the queued count's entries (it stays queued). */
+int32_t ilm_system_poll_sense(IlmHandle system, uint32_t* out_counts, int32_t capacity, int32_t* out_ready);
 
 /* Ordered live-slot list of one chunk (wave64 ballot + prefix sum): writes the
  * ascending slot indices with life > 0 to `out_slots` (host, capacity entries)

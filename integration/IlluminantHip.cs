@@ -34,6 +34,7 @@ namespace Squared.Illuminant.Native {
         public const int MAX_ATTRACTORS = 16;
         public const int MAX_INLINE_POSITION_CONSTANTS = 4;
         public const int MAX_OPS = 4;
+        public const int MAX_SENSORS = 8;
         public const int MAX_SPAWNS = 2;
         public const int OK = 0;
         public const int RANDOMNESS_HEIGHT = 653;
@@ -605,6 +606,9 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_live_counts (ulong system, uint* outCounts, int capacity, int saturate16);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_step_counts (ulong system, uint* outCounts, int capacity, int saturate16);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_poll_counts (ulong system, uint* outCounts, int capacity, int saturate16, int* outReady);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_sense (ulong system, int firstChunk, int chunkCount, IlmAreaParams* sensors, int sensorCount, uint* outCounts, int capacity);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_sense_async (ulong system, int firstChunk, int chunkCount, IlmAreaParams* sensors, int sensorCount);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_system_poll_sense (ulong system, uint* outCounts, int capacity, int* outReady);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_chunk_live_slots (ulong system, int chunkIndex, uint* outSlots, int capacity, int* outCount);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_sdf_create (ulong ctx, int atlasWidth, int atlasHeight, int format, ulong* outSdf);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_sdf_upload (ulong sdf, ushort* texels);
