@@ -289,6 +289,17 @@ struct System {
     std::vector<uint8_t> ptr_out;
     RenderKey render_key; uint64_t render_key_gen = 0;
     bool render_captured = false;
+    // Category record per chunk: cat_current[i] != 0 when the chunk's line of d_cat (internal.hpp, CategoryRecords) holds bounds {lo, hi}
+    // for which EVERY SLOT OF THE CHUNK WITH A FINITE LIFE > 0 HAS ITS CATEGORY INSIDE [lo, hi].  The clamp class of the lean step reads
+    // the line on the device and leaves the category plane alone where the step's filter contains the bounds.  Set by the scan a
+    // clamp-class launch runs first (category_bounds_kernel: the bounds of every used slot, alive or not).  Kept by a lean step with
+    // neither an FMA nor a spawner: its transforms and its update hand a live slot's category through, it zeroes a category only together
+    // with the life, and its Noise cannot bring a dead slot to a finite positive life (build_lean_step).  Cleared by every other step --
+    // the interpreter, a batched item, the collision step, a launch that spawns or has an FMA -- and by every other writer, wherever
+    // render_gen is cleared; a chunk whose pointer was handed out is never scanned (no launch over it elides), and once a step of the
+    // system has been captured no record is current.  The table grows with the chunk table; a grown table holds no record.
+    std::vector<uint8_t> cat_current;
+    DeviceScratch d_cat;
     DeviceScratch d_table; bool table_dirty = true;       // float* per chunk
     // Five counter regions of 64-bit words.  Regions 0-3 belong to the step kernels, kCountLines lines per chunk (internal.hpp),
     // index = parity * 2 + half: a counting launch of half h accumulates into (parity, h) and zeroes (parity ^ 1, h) for the next
@@ -678,6 +689,14 @@ int32_t refresh_table(System* s) {
         const int32_t rc = reserve(c, s->d_table, sizeof(float*) * (size_t)n, sizeof(float*) * (size_t)(n < 64 ? 64 : n * 2));
         if (rc != ILM_OK) return rc;
         s->table_dirty = true;
+    }
+    // the category records (System::cat_current) grow with it: a fresh table is zero -- what the scan's scratch words start from -- and
+    // holds no record
+    if (sizeof(float) * kCategoryRecordStride * (size_t)n > s->d_cat.bytes) {
+        const int32_t rc = reserve(c, s->d_cat, sizeof(float) * kCategoryRecordStride * (size_t)n, sizeof(float) * kCategoryRecordStride * (size_t)(n < 64 ? 64 : n * 2));
+        if (rc != ILM_OK) return rc;
+        HIP_TRY(hipMemsetAsync(s->d_cat.p, 0, s->d_cat.bytes, c->main()));
+        s->cat_current.assign(s->chunks.size(), 0);
     }
     if (n > s->counts_cap) {
         if (s->d_counts) { HIP_TRY(hipStreamSynchronize(c->main())); HIP_TRY(hipFree(s->d_counts)); s->d_counts = nullptr; }
@@ -1238,9 +1257,14 @@ int32_t run_step(System* s, const IlmStepDesc* d) {
     };
     const uint32_t elide_a = render_elide(first, (mid < 0) ? first + count : mid), elide_b = (mid < 0) ? 0u : render_elide(mid, first + count);
     render_refreshed(first, first + count, false);
+    // The category records of the range (System::cat_current): launch_step keeps, clears and establishes them, each half of a split
+    // step on its own stream.  A captured system has none.
+    CategoryRecords records = { s->d_cat.as<float>(), s->cat_current.data(), s->used.data() };
+    CategoryRecords* cat = &records;
+    if (s->render_captured) { s->cat_current.assign(s->chunks.size(), 0); cat = nullptr; }
     bool fresh_a = false, fresh_b = false;
     if (mid < 0) {
-        HIP_TRY(launch_step(a, c->main(), elide_a, &fresh_a));
+        HIP_TRY(launch_step(a, c->main(), elide_a, &fresh_a, cat));
         render_refreshed(first, first + count, fresh_a);
     } else {
         if (s->split_at != mid) { (void)c->main(); s->split_at = mid; }      // a chunk changes streams: join first
@@ -1261,12 +1285,12 @@ int32_t run_step(System* s, const IlmStepDesc* d) {
         bool spawn_in_b = false;
         for (int k = 0; k < d->SpawnCount; k++) spawn_in_b = spawn_in_b || (d->Spawns[k].ChunkIndex >= mid);
         if (spawn_in_b) {
-            HIP_TRY(launch_step(b, c->aux, elide_b, &fresh_b));
+            HIP_TRY(launch_step(b, c->aux, elide_b, &fresh_b, cat));
             c->aux_pending = true;
-            HIP_TRY(launch_step(a, c->stream_, elide_a, &fresh_a));
+            HIP_TRY(launch_step(a, c->stream_, elide_a, &fresh_a, cat));
         } else {
-            HIP_TRY(launch_step(a, c->stream_, elide_a, &fresh_a));
-            HIP_TRY(launch_step(b, c->aux, elide_b, &fresh_b));
+            HIP_TRY(launch_step(a, c->stream_, elide_a, &fresh_a, cat));
+            HIP_TRY(launch_step(b, c->aux, elide_b, &fresh_b, cat));
             c->aux_pending = true;
         }
         render_refreshed(first, mid, fresh_a);
@@ -1354,7 +1378,7 @@ int32_t run_step_batch(Engine* e, const IlmHandle* handles, const IlmStepDesc* d
         // the render-plane records: a batched item is "another step" (it clears its range and sets nothing)
         if (d->UpdateMode == ILM_UPDATE_POSITIONS) (void)render_key_generation(s, d);
         if (capturing) s->render_captured = true;
-        for (int ci = first; ci < first + n; ci++) s->render_gen[(size_t)ci] = 0;
+        for (int ci = first; ci < first + n; ci++) s->render_gen[(size_t)ci] = s->cat_current[(size_t)ci] = 0;
         finish_step(s, d, first, n);
 
         Planned& p = plan[(size_t)i];
@@ -1505,6 +1529,7 @@ int32_t system_chunk_view(IlmHandle system, int chunk, bool written, float** out
     if (written) {
         s->used[(size_t)chunk] = s->engine->slots;
         s->render_gen[(size_t)chunk] = 0;
+        s->cat_current[(size_t)chunk] = 0;
     }
     return ILM_OK;
 }
@@ -1848,7 +1873,7 @@ int32_t ilm_system_destroy(IlmHandle h) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->main());
     for (float* p : s->chunks) release_chunk(s->engine, p);
-    for (DeviceScratch* b : { &s->d_table, &s->d_slots, &s->d_slot_count }) release(*b);
+    for (DeviceScratch* b : { &s->d_table, &s->d_cat, &s->d_slots, &s->d_slot_count }) release(*b);
     for (DeviceScratch& b : s->spawn_positions) release(b);
     if (s->d_counts) (void)hipFree(s->d_counts);
     if (s->ramp) (void)hipFree(s->ramp);
@@ -1874,6 +1899,7 @@ int32_t ilm_system_add_chunk(IlmHandle h, int32_t* out_index) {
     s->used.push_back(0);
     s->render_gen.push_back(0);
     s->ptr_out.push_back(0);
+    s->cat_current.push_back(0);
     s->table_dirty = true;
     if (out_index) *out_index = (int32_t)s->chunks.size() - 1;
     return ILM_OK;
@@ -1892,6 +1918,7 @@ int32_t ilm_system_remove_chunk(IlmHandle h, int32_t index) {
     s->used.erase(s->used.begin() + index);
     s->render_gen.erase(s->render_gen.begin() + index);
     s->ptr_out.erase(s->ptr_out.begin() + index);
+    s->cat_current.assign(s->chunks.size(), 0);      // the later chunks' lines of the table are no longer theirs
     s->table_dirty = true;
     return ILM_OK;
 }
@@ -1928,6 +1955,7 @@ int32_t ilm_chunk_upload(IlmHandle h, int32_t chunk, int32_t plane, const IlmFlo
     HIP_TRY(hipMemcpyAsync(c->staging.p, src, bytes, hipMemcpyHostToDevice, c->main()));
     s->used[(size_t)chunk] = std::max(s->used[(size_t)chunk], first_slot + count);
     s->render_gen[(size_t)chunk] = 0;
+    s->cat_current[(size_t)chunk] = 0;
     HIP_TRY(launch_aos_to_soa(c->staging.as<const float4>(), s->chunks[(size_t)chunk] + (int64_t)plane * 4 * e->stride,
                               e->stride, first_slot, count, c->main()));
     HIP_TRY(hipStreamSynchronize(c->main()));   // staging is reused by the next call
@@ -1961,6 +1989,7 @@ int32_t ilm_chunk_device_ptr(IlmHandle h, int32_t chunk, int32_t component, void
     if (out_ptr) *out_ptr = s->chunks[(size_t)chunk] + (int64_t)component * s->engine->stride;
     s->used[(size_t)chunk] = s->engine->slots;     // the caller may write through the pointer
     s->render_gen[(size_t)chunk] = 0;
+    s->cat_current[(size_t)chunk] = 0;
     s->ptr_out[(size_t)chunk] = 1;
     if (out_stride) *out_stride = s->engine->stride;
     return ILM_OK;
@@ -2549,6 +2578,35 @@ int32_t ilm_debug_step_regular_waves(IlmHandle hctx, int32_t enable, uint64_t* o
     HIP_TRY(step_regular_wave_counter(enable, value));
     if (out_regular) *out_regular = (uint64_t)value[0];
     if (out_selected) *out_selected = (uint64_t)value[1];
+    return ILM_OK;
+}
+
+int32_t ilm_debug_step_category_waves(IlmHandle hctx, int32_t enable, uint64_t* out_skipped, uint64_t* out_late, uint64_t* out_upfront) {
+    Ctx* c = from_handle<Ctx>(hctx, kMagicCtx);
+    if (!c) return fail(ILM_ERR_INVALID_HANDLE, "not a context handle");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->main()));        // main() first joins the second stream
+    unsigned long long value[3] = { 0, 0, 0 };
+    HIP_TRY(step_category_wave_counter(enable, value));
+    if (out_skipped) *out_skipped = (uint64_t)value[0];
+    if (out_late) *out_late = (uint64_t)value[1];
+    if (out_upfront) *out_upfront = (uint64_t)value[2];
+    return ILM_OK;
+}
+
+int32_t ilm_debug_chunk_category_bounds(IlmHandle hsystem, int32_t chunk, float* out_lo, float* out_hi, int32_t* out_current) {
+    System* s = from_handle<System>(hsystem, kMagicSystem);
+    if (!s) return fail(ILM_ERR_INVALID_HANDLE, "not a system handle");
+    if (chunk < 0 || chunk >= (int)s->chunks.size()) return fail(ILM_ERR_OUT_OF_RANGE, "chunk %d outside [0, %d)", chunk, (int)s->chunks.size());
+    Ctx* c = s->engine->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->main()));        // main() first joins the second stream
+    float bounds[2] = { 0.0f, 0.0f };
+    const bool held = sizeof(float) * kCategoryRecordStride * (size_t)(chunk + 1) <= s->d_cat.bytes;      // (no step yet: no table)
+    if (held) HIP_TRY(hipMemcpy(bounds, s->d_cat.as<float>() + (size_t)chunk * kCategoryRecordStride, sizeof(bounds), hipMemcpyDeviceToHost));
+    if (out_lo) *out_lo = bounds[0];
+    if (out_hi) *out_hi = bounds[1];
+    if (out_current) *out_current = (held && s->cat_current[(size_t)chunk] && !s->render_captured && !s->ptr_out[(size_t)chunk]) ? 1 : 0;
     return ILM_OK;
 }
 

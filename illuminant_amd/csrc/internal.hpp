@@ -132,7 +132,13 @@ constexpr int kCountLines = 17;      // per chunk in the step kernels' counter r
 constexpr uint32_t kElideDerived = 1u;
 constexpr uint32_t kElideColor = 2u;     // (set by build_lean_step) the colour curves cannot produce a NaN factor: renderColor may be elided
 constexpr uint32_t kElideRotation = 4u;  // (set by build_lean_step) RotationFromLifeAndIndex[0] == 0 and the velocity rotation is 0: rd.y does not read a finite life
-hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide = 0u, bool* refreshed = nullptr);
+// The category records of a system's chunks as launch_step sees them (api.hip, System::cat_current, states the rule): `table` is device
+// memory, kCategoryRecordStride floats (one 64-byte line) per chunk -- floats 0 and 1 the {lo, hi} that category_bounds_kernel found, words
+// 4..7 that kernel's scratch; `current` and `used` are the system's host arrays, indexed by chunk.  launch_step clears `current` over the
+// range of a launch that may write a live slot's category, and has a clamp-class launch scan the chunks that are not current.
+constexpr int kCategoryRecordStride = 16;
+struct CategoryRecords { float* table; uint8_t* current; const int32_t* used; };
+hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide = 0u, bool* refreshed = nullptr, CategoryRecords* cat = nullptr);
 // ilm_engine_step_batch: lay a prepared StepLaunch out like launch_step does and return the batch kernel's variant for it (-1: the batch
 // kernel does not cover it -- a streaming range -- and launch_step runs it); *blocks = the blocks it takes in a launch's grid.
 // launch_step_batch: ONE launch over `blocks` blocks of items of one variant; item_of_block[b] indexes `table` (device memory, read-only).
@@ -140,6 +146,7 @@ int step_batch_layout(StepLaunch& a, int* blocks);
 hipError_t launch_step_batch(int variant, const StepBatchItem* table, const int32_t* item_of_block, int blocks, hipStream_t stream);
 hipError_t step_sdf_sample_counter(int enable, unsigned long long* out);   // ilm_debug_step_sdf_samples
 hipError_t step_regular_wave_counter(int enable, unsigned long long out[2]);   // ilm_debug_step_regular_waves
+hipError_t step_category_wave_counter(int enable, unsigned long long out[3]);  // ilm_debug_step_category_waves
 // the slice-0 cells of a UNORM16 field (SdfView::cells0): does this step's collision update use them, and their build
 bool step_wants_slice0_cells(const IlmStepDesc& d, int format);
 hipError_t launch_build_slice0_cells(const uint2* texels, int width, int height, void* cells, hipStream_t stream);

@@ -756,7 +756,12 @@ __device__ int g_step_count_sdf_samples;
 // [1]: the regular transforms, then the selecting update and tail (the second ballot failed).  Every other wave ran the selecting body
 // from the top.  The flag is read by one scalar load per wave; off, that load and a branch are the whole cost.
 __device__ unsigned long long g_step_regular_waves[2];
-__device__ int g_step_count_regular_waves;
+__device__ int g_step_count_regular_waves;      // bit 0: count g_step_regular_waves, bit 1: count g_step_category_waves (one flag, one load)
+// Diagnostic (ilm_debug_step_category_waves): what the waves of step_lean_clamp_kernel did about the category plane.  [0]: never loaded it
+// (the chunk's category record admits every live slot and the wave stayed regular), [1]: loaded it late (such a wave that left the
+// regular path), [2]: loaded it up front with the other planes (no record, or one the launch's filter does not contain).  Behind bit 1 of
+// the flag above: a regular wave reads that flag once, as before.
+__device__ unsigned long long g_step_category_waves[3];
 
 // PS_Update, UpdateParticleSystemWithDistanceField.fx:29-147, behind its first lookup: the sweep and the bounce / redirect / escape
 // arithmetic for a live slot whose life does not run out in this step, given initial_distance (the field at the particle) and, when
@@ -1309,7 +1314,7 @@ struct LeanStep {
     int32_t partial_count, op_count, spawn_count; uint32_t elide;      // elide: kElideDerived / kElideColor (step_lean_kernel)
     int32_t op_type[ILM_MAX_OPS];
     int32_t spawn_chunk[ILM_MAX_SPAWNS], spawn_unit_lo[ILM_MAX_SPAWNS], spawn_unit_hi[ILM_MAX_SPAWNS];   // segments of the target chunk a record touches
-    int32_t _pad1[2];
+    int32_t cat_stride, _pad1;       // cat_stride: see cat_bounds
     // update pass
     float dt_s; uint32_t bezier_codes, update_bits; int32_t noise_op;
     IlmParticleSystemUniforms sys;
@@ -1319,7 +1324,11 @@ struct LeanStep {
     LeanOp op[ILM_MAX_OPS];
     StepDerived::NoiseFast noise;
     // spawners (inline kind only) -- or, in a launch without them, the 5 x 5 noise tables (kNoiseBigClasses)
-    const float4* rnd; int32_t rw, rh; float inv_rw, inv_rh; int32_t _pad2[2];
+    const float4* rnd; int32_t rw, rh; float inv_rw, inv_rh;
+    // step_lean_clamp_kernel: the category records of the system's chunks (api.hip, System::cat_current), cat_stride = kCategoryRecordStride
+    // x 4 bytes per chunk, {lo, hi} first -- or, for a launch without records, g_no_category_record with a stride of 0: a NaN record for
+    // every chunk, which no filter contains (every wave loads the category plane up front)
+    const float* cat_bounds;
     union {
         IlmSpawnRecord spawns[ILM_MAX_SPAWNS];
         IlmFloat4 noise_big[2 * kNoiseBigClasses * kNoiseBigClasses];
@@ -1522,6 +1531,32 @@ ILM_DEV uint64_t regular_lanes_loaded(const LeanStep& a, const SlotIn& cur) {
     return lane_mask(cur.life > 0.0f) & lane_mask(cur.life < __builtin_inff()) & lane_mask(cur.ct >= a.regular_cat_lo) & lane_mask(cur.ct <= a.regular_cat_hi) &
            lane_mask(!__builtin_isunordered(cur.vx, cur.vy));
 }
+// ... in a chunk whose category record lies inside the launch's filter (category_proven): every slot with a finite life > 0 has a
+// category the transforms accept, so the two category compares are decided and the category itself is not needed.
+ILM_DEV uint64_t regular_lanes_loaded_proven(const SlotIn& cur) {
+    return lane_mask(cur.life > 0.0f) & lane_mask(cur.life < __builtin_inff()) & lane_mask(!__builtin_isunordered(cur.vx, cur.vy));
+}
+// The chunk's category record against the launch's filter: {lo, hi} is one 8-byte scalar load through the constant address space (the
+// table is written by category_bounds_kernel ahead of the launch on its stream and never during one: the chunk table's rule).  Float
+// compares, so a NaN on either side -- a chunk with a NaN category, a filter with a NaN bound -- proves nothing; no branch between
+// them.  Wave-uniform.  (Fetching the record and the chunk's base pointer by one hand-issued pair of loads measured the same:
+// docs/experiments.md 7.38.)
+typedef const uint64_t __attribute__((address_space(4))) CUint64;
+__device__ __attribute__((aligned(8))) float g_no_category_record[2] = { __builtin_nanf(""), __builtin_nanf("") };
+ILM_DEV bool category_proven(const LeanStep& a, int chunk) {
+    const uint64_t record = *(CUint64*)((const char*)a.cat_bounds + chunk * a.cat_stride);
+    const float lo = __builtin_bit_cast(float, (uint32_t)record), hi = __builtin_bit_cast(float, (uint32_t)(record >> 32));
+    return ((lo >= a.regular_cat_lo) & (hi <= a.regular_cat_hi)) != 0;
+}
+// the slot's loads without the category plane (load_slot<false, true> otherwise)
+ILM_DEV SlotIn load_slot_uncategorised(const UnitPlanes& u, unsigned lane4) {
+    SlotIn s;
+    s.life = ld_plane<true>(u, 3, lane4);
+    s.px = ld_plane<true>(u, 0, lane4); s.py = ld_plane<true>(u, 1, lane4); s.pz = ld_plane<true>(u, 2, lane4);
+    s.vx = ld_plane<true>(u, 4, lane4); s.vy = ld_plane<true>(u, 5, lane4); s.vz = ld_plane<true>(u, 6, lane4); s.ct = 0.0f;
+    s.ar = s.ag = s.ab = s.aa = 0.0f;
+    return s;
+}
 // ... and after the update: still alive with a finite life, no NaN in the new velocity's x and y.
 ILM_DEV uint64_t regular_lanes_updated(float new_life, float vx, float vy) {
     return lane_mask(new_life > 0.0f) & lane_mask(new_life < __builtin_inff()) & lane_mask(!__builtin_isunordered(vx, vy));
@@ -1609,10 +1644,16 @@ ILM_DEV void step_lean_block() {
             // volatile asm of touch_kernarg_lines it would otherwise fetch the base with a VECTOR load and wrap every plane access in
             // a waterfall loop over a "divergent" buffer resource: +160 vector instructions per wave); the table is written by a copy
             // that precedes the launch on its stream and never during one
+            // kCurvesClamp: a wave of a chunk whose category record the filter contains leaves the category plane alone until it needs it
+            bool ct_pending = false;
+            if constexpr (CURVES == kCurvesClamp) ct_pending = category_proven(a, chunk);
             const UnitPlanes up = unit_planes(((CBase*)a.chunk_bases)[chunk], a.stride, seg * 64);
             // a render-current chunk needs its attributes only where renderColor is recomputed: loaded below, by the waves that do
             const bool elide = STREAM && ((CURVES == kCurvesClamp) || (a.elide & kElideDerived) != 0u);
-            SlotIn cur = load_slot<false, STREAM>(up, lane4);
+            SlotIn cur;
+            if (CURVES == kCurvesClamp && ct_pending) cur = load_slot_uncategorised(up, lane4);
+            else cur = load_slot<false, STREAM>(up, lane4);
+            const bool ct_proven = ct_pending;
             if (!elide) {
                 const float4 stored = load_attributes<STREAM>(up, lane4);
                 cur.ar = stored.x; cur.ag = stored.y; cur.ab = stored.z; cur.aa = stored.w;
@@ -1654,8 +1695,12 @@ ILM_DEV void step_lean_block() {
                 // category with other bits than the loaded one, -0 to +0 and NaN included -- starts again from the loaded state in the
                 // selecting body, which filters the later transforms by the new category, skips them for a dead lane and stores the
                 // category plane and rd.w.  So in the regular body the category is the loaded one to the end.
+                // A wave whose chunk is proven (category_proven) carries no category: it forms the loaded mask without the category compares
+                // and, wherever it leaves the regular path -- a mask that is not full, the second mask -- loads the plane there (ct_pending)
+                // and goes on with the state a wave that loaded it up front has at that point.  No such wave meets an FMA: launch_step
+                // gives a launch with one the NaN record, so every wave of it loads the category up front.
                 int body = kBodySelecting;
-                if (regular_lanes_loaded(a, cur) == kAllLanes) {
+                if ((ct_proven ? regular_lanes_loaded_proven(cur) : regular_lanes_loaded(a, cur)) == kAllLanes) {
                     body = kBodyRegular;
 #pragma unroll
                     for (int o = 0; o < ILM_MAX_OPS; o++) {
@@ -1676,8 +1721,11 @@ ILM_DEV void step_lean_block() {
                 if (body == kBodyRegular) {
                     update_positions_unselected(pos, vel, a.sys, a.dt_s);
                     const bool stays = regular_lanes_updated(pos.w, vel.x, vel.y) == kAllLanes;
-                    if (__builtin_amdgcn_readfirstlane(*(CInt32*)&g_step_count_regular_waves) != 0 && lane == 0u)
-                        atomicAdd(&g_step_regular_waves[stays ? 0 : 1], 1ull);
+                    const int counting = __builtin_amdgcn_readfirstlane(*(CInt32*)&g_step_count_regular_waves);
+                    if (counting != 0 && lane == 0u) {
+                        if (counting & 1) atomicAdd(&g_step_regular_waves[stays ? 0 : 1], 1ull);
+                        if (counting & 2) atomicAdd(&g_step_category_waves[ct_proven ? (stays ? 0 : 1) : 2], 1ull);
+                    }
                     if (stays) {
                         const uint64_t vx_changed = lane_mask(!same_bits(vel.x, cur.vx)), vy_changed = lane_mask(!same_bits(vel.y, cur.vy)), vz_changed = lane_mask(!same_bits(vel.z, cur.vz));
                         if (lane_mask(!same_bits(pos.x, cur.px)) != 0ull) st_plane<true>(up, 0, lane4, pos.x);
@@ -1692,12 +1740,25 @@ ILM_DEV void step_lean_block() {
                         n_live = 64u;
                         goto unit_stored;       // (a flag tested at the stores below moved the general instantiations' registers)
                     }
+                    if (ct_pending) {       // the category passed through the transforms and the update: the loaded one
+                        cur.ct = ld_plane<true>(up, 7, lane4);
+                        vel.w = cur.ct;
+                        ct_pending = false;
+                    }
                     // every lane was alive after the transforms: update_positions_select's `keep` is the new life's test alone
                     const bool keep = !(pos.w <= 0.0f);
                     pos = mk4(keep ? pos.x : 0.0f, keep ? pos.y : 0.0f, keep ? pos.z : 0.0f, keep ? pos.w : 0.0f);
                     vel = mk4(keep ? vel.x : 0.0f, keep ? vel.y : 0.0f, keep ? vel.z : 0.0f, keep ? vel.w : 0.0f);
                 }
                 if (body == kBodySelecting) {
+                    if (ct_pending) {
+                        cur.ct = ld_plane<true>(up, 7, lane4);
+                        ct_pending = false;
+                    }
+                    {
+                        const int counting = __builtin_amdgcn_readfirstlane(*(CInt32*)&g_step_count_regular_waves);
+                        if ((counting & 2) != 0 && lane == 0u) atomicAdd(&g_step_category_waves[ct_proven ? 1 : 2], 1ull);
+                    }
                     pos = mk4(cur.px, cur.py, cur.pz, cur.life);
                     vel = mk4(cur.vx, cur.vy, cur.vz, cur.ct);
                     if (__ballot(process) != 0ull) {
@@ -2167,6 +2228,105 @@ static bool curves_clamp(const LeanStep& f, bool spawning, bool streaming) {
     return streaming && !spawning && (f.elide & kElideDerived) != 0u && (f.bezier_codes & ~kClampCodes) == 0u && f.update_bits == 2u;
 }
 
+// The category record of chunks [first_chunk, first_chunk + gridDim.y): {lo, hi} = the smallest and the largest category (plane 7) among
+// the chunk's first `used` slots -- the slots past them were never written and are never stepped -- into floats 0 and 1 of the chunk's
+// record; a NaN lo (which contains nobody) when one of them is a NaN.  A thread reads four slots at a time, 64 times; a wave reduces
+// by shuffles, thread 0 combines the block's four waves and folds them into words 4..6 of the record -- integer maxima over keys that
+// order like the floats (word 4 holds the complement of the smallest key, so the words start from zero) -- and the block that draws
+// the last ticket (word 7) turns the keys back into floats and zeroes the words for the next scan.  One scan per chunk at a time
+// (launch_step: on the stream that steps the chunk).  Few, long blocks: the records lie side by side, their atomics queue on one memory
+// channel at some 20 ns each, and with 4 096 slots per block they were the whole of the kernel's time (32 chunks of 1024^2: 0.69 ms for
+// 134 MB).
+constexpr int kCategoryScanSlots = 65536;     // per block
+ILM_DEV uint32_t float_order_key(float v) {
+    const uint32_t b = __builtin_bit_cast(uint32_t, v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+ILM_DEV float float_of_order_key(uint32_t k) { return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+__global__ __launch_bounds__(256) void category_bounds_kernel(float* const* __restrict__ bases, int64_t stride, int first_chunk, int used, float* __restrict__ records) {
+    __shared__ float wave_lo[4], wave_hi[4];
+    __shared__ uint32_t wave_nan[4];
+    const int chunk = first_chunk + (int)blockIdx.y;
+    const float* cat = bases[chunk] + 7 * stride;
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+    bool nan = false;
+#pragma unroll 4
+    for (int k = 0; k < kCategoryScanSlots / 1024; k++) {
+        // i0 < used <= stride, i0 and the stride multiples of four: the four slots lie inside the plane; the slots at and past `used` are
+        // read and left out below
+        const int i0 = (int)blockIdx.x * kCategoryScanSlots + k * 1024 + (int)threadIdx.x * 4;
+        if (i0 < used) {
+            const float4 c = *reinterpret_cast<const float4*>(cat + i0);
+            const float v[4] = { c.x, c.y, c.z, c.w };
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (i0 + j < used) {
+                    lo = fminf(lo, v[j]); hi = fmaxf(hi, v[j]);      // (a NaN leaves both alone)
+                    nan = nan || (v[j] != v[j]);
+                }
+            }
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, d));
+        hi = fmaxf(hi, __shfl_xor(hi, d));
+    }
+    const bool wave_has_nan = __ballot(nan) != 0ull;
+    if ((threadIdx.x & 63) == 0) { wave_lo[threadIdx.x >> 6] = lo; wave_hi[threadIdx.x >> 6] = hi; wave_nan[threadIdx.x >> 6] = wave_has_nan ? 1u : 0u; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        lo = fminf(fminf(wave_lo[0], wave_lo[1]), fminf(wave_lo[2], wave_lo[3]));
+        hi = fmaxf(fmaxf(wave_hi[0], wave_hi[1]), fmaxf(wave_hi[2], wave_hi[3]));
+        float* rec = records + (size_t)chunk * kCategoryRecordStride;
+        uint32_t* work = reinterpret_cast<uint32_t*>(rec) + 4;
+        atomicMax(&work[0], ~float_order_key(lo));
+        atomicMax(&work[1], float_order_key(hi));
+        if ((wave_nan[0] | wave_nan[1] | wave_nan[2] | wave_nan[3]) != 0u) atomicOr(&work[2], 1u);
+        __threadfence();
+        if (atomicAdd(&work[3], 1u) == gridDim.x - 1u) {
+            __threadfence();
+            const uint32_t k_lo = ~atomicOr(&work[0], 0u), k_hi = atomicOr(&work[1], 0u), any_nan = atomicOr(&work[2], 0u);
+            rec[0] = any_nan ? __builtin_nanf("") : float_of_order_key(k_lo);
+            rec[1] = float_of_order_key(k_hi);
+            work[0] = 0u; work[1] = 0u; work[2] = 0u; work[3] = 0u;
+        }
+    }
+}
+static hipError_t launch_category_bounds(float* const* chunk_bases, int64_t stride, int first_chunk, int chunk_count, int used, float* records, hipStream_t stream) {
+    const unsigned blocks = (unsigned)std::max(1, (used + kCategoryScanSlots - 1) / kCategoryScanSlots);
+    hipLaunchKernelGGL(category_bounds_kernel, dim3(blocks, (unsigned)chunk_count), dim3(256), 0, stream, chunk_bases, stride, first_chunk, used, records);
+    return hipGetLastError();
+}
+// g_no_category_record on the current device (looked up once per device)
+static const float* no_category_record() {
+    constexpr int kDevices = 64;
+    static std::atomic<const float*> found[kDevices];
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= kDevices) { (void)hipGetLastError(); return nullptr; }
+    const float* p = found[device];
+    if (p == nullptr) {
+        void* address = nullptr;
+        if (hipGetSymbolAddress(&address, HIP_SYMBOL(g_no_category_record)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        found[device] = p = static_cast<const float*>(address);
+    }
+    return p;
+}
+// The scans a clamp-class launch needs: every chunk of its range whose record is not current, one launch per run of consecutive such
+// chunks with the same number of used slots, on the launch's stream ahead of it.
+static hipError_t scan_category_records(const StepLaunch& a, CategoryRecords& cat, hipStream_t stream) {
+    const int end = a.first_chunk + a.chunk_count;
+    for (int ci = a.first_chunk; ci < end;) {
+        if (cat.current[ci]) { ci++; continue; }
+        int run = 1;
+        while (ci + run < end && !cat.current[ci + run] && cat.used[ci + run] == cat.used[ci]) run++;
+        const hipError_t e = launch_category_bounds(a.chunk_bases, a.stride, ci, run, std::min(cat.used[ci], a.slots), cat.table, stream);
+        if (e != hipSuccess) return e;
+        for (int k = 0; k < run; k++) cat.current[ci + k] = 1;
+        ci += run;
+    }
+    return hipSuccess;
+}
+
 static hipError_t launch_lean_step(const LeanStep& f, bool spawning, bool streaming, hipStream_t stream) {
     const int units_per_block = kStepThreads / 64;
     const dim3 grid((unsigned)((f.total_units + units_per_block - 1) / units_per_block), 1, 1), block(kStepThreads, 1, 1);
@@ -2366,9 +2526,17 @@ static bool layout_step(StepLaunch& a) {
     a.total_padded = l.total_padded; a.unit_rotate = l.unit_rotate; a.count_buckets = l.count_buckets;
     return spawning;
 }
-hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide, bool* refreshed) {
+// The category records of the launch's range (api.hip, System::cat_current).  A record stays current through a lean step that runs
+// neither an FMA nor a spawner: Gravity, Noise and the update pass hand a live slot's category through, and a slot they discard gets
+// its zero category together with a zero life.  Every other kernel may write a live slot's category: its range's records are cleared.
+// The clamp class is the one reader: a launch of it without an FMA scans what is not current and takes the table along.
+static void clear_category_records(const StepLaunch& a, CategoryRecords* cat) {
+    for (int ci = a.first_chunk; cat && ci < a.first_chunk + a.chunk_count; ci++) cat->current[ci] = 0;
+}
+hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide, bool* refreshed, CategoryRecords* cat) {
     if (refreshed) *refreshed = false;
     const bool spawning = layout_step(a);
+    if (spawning || (a.op_mask & (1u << ILM_OP_FMA)) != 0u) { clear_category_records(a, cat); cat = nullptr; }
     if (!step_interpreter_forced() && a.unit_end > a.unit_begin) {
         if (a.desc.UpdateMode == ILM_UPDATE_WITH_DISTANCE_FIELD) {
             const char* lean_env = getenv("ILM_DF_LEAN");                 // A/B switch, read per launch: 0 = the interpreter
@@ -2377,6 +2545,7 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide,
             if (lean_df && build_lean_step(a, f.base)) {
                 f.df = a.desc.DistanceField;
                 f.sdf = a.sdf;
+                clear_category_records(a, cat);       // (the collision update redirects and parks slots: not checked against the record's rule)
                 g_last_step_kernel = ILM_STEP_KERNEL_LEAN_DF;
                 return launch_lean_df_step(f, a, spawning, stream);
             }
@@ -2384,12 +2553,23 @@ hipError_t launch_step(StepLaunch& a, hipStream_t stream, uint32_t render_elide,
             LeanStep f;
             if (build_lean_step(a, f)) {
                 f.elide = ((render_elide & kElideDerived) && a.streaming) ? (kElideDerived | (color_curves_bounded(a.desc.Update) ? kElideColor : 0u) | (f.elide & kElideRotation)) : 0u;
+                if (curves_clamp(f, spawning, a.streaming != 0)) {
+                    if (cat) {
+                        const hipError_t scanned = scan_category_records(a, *cat, stream);
+                        if (scanned != hipSuccess) { clear_category_records(a, cat); return scanned; }
+                        f.cat_bounds = cat->table; f.cat_stride = kCategoryRecordStride * (int32_t)sizeof(float);
+                    } else {
+                        f.cat_bounds = no_category_record(); f.cat_stride = 0;
+                        if (f.cat_bounds == nullptr) return hipErrorInvalidSymbol;
+                    }
+                }
                 const hipError_t e = launch_lean_step(f, spawning, a.streaming != 0, stream);
                 if (refreshed) *refreshed = (e == hipSuccess);
                 return e;
             }
         }
     }
+    clear_category_records(a, cat);
     g_last_step_kernel = ILM_STEP_KERNEL_INTERPRETER;
     return spawning ? launch_step_variant<true>(a, stream) : launch_step_variant<false>(a, stream);
 }
@@ -2657,6 +2837,12 @@ hipError_t step_sdf_sample_counter(int enable, unsigned long long* out) {
     return e;
 }
 
+// The clamp class's two wave counters share one device flag (g_step_count_regular_waves): `bit` of it follows `enable`
+static std::atomic<int> g_step_wave_counting{0};
+static hipError_t set_step_wave_counting(int bit, int enable) {
+    const int flag = enable ? (g_step_wave_counting |= bit) : (g_step_wave_counting &= ~bit);
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_step_count_regular_waves), &flag, sizeof(flag));
+}
 // ilm_debug_step_regular_waves: the same for the clamp class's two wave counts
 hipError_t step_regular_wave_counter(int enable, unsigned long long out[2]) {
     unsigned long long value[2] = { 0, 0 }, zero[2] = { 0, 0 };
@@ -2664,9 +2850,20 @@ hipError_t step_regular_wave_counter(int enable, unsigned long long out[2]) {
     if (e != hipSuccess) return e;
     e = hipMemcpyToSymbol(HIP_SYMBOL(g_step_regular_waves), zero, sizeof(zero));
     if (e != hipSuccess) return e;
-    const int flag = enable ? 1 : 0;
-    e = hipMemcpyToSymbol(HIP_SYMBOL(g_step_count_regular_waves), &flag, sizeof(flag));
+    e = set_step_wave_counting(1, enable);
     if (out) { out[0] = value[0]; out[1] = value[1]; }
+    return e;
+}
+
+// ilm_debug_step_category_waves: the same for the three category counts
+hipError_t step_category_wave_counter(int enable, unsigned long long out[3]) {
+    unsigned long long value[3] = { 0, 0, 0 }, zero[3] = { 0, 0, 0 };
+    hipError_t e = hipMemcpyFromSymbol(value, HIP_SYMBOL(g_step_category_waves), sizeof(value));
+    if (e != hipSuccess) return e;
+    e = hipMemcpyToSymbol(HIP_SYMBOL(g_step_category_waves), zero, sizeof(zero));
+    if (e != hipSuccess) return e;
+    e = set_step_wave_counting(2, enable);
+    if (out) { out[0] = value[0]; out[1] = value[1]; out[2] = value[2]; }
     return e;
 }
 

@@ -85,6 +85,8 @@ SYMBOLS = {
     "ilm_debug_step_streams": (_I, [_I]),
     "ilm_debug_step_sdf_samples": (_I, [_H, _I, C.POINTER(C.c_uint64)]),
     "ilm_debug_step_regular_waves": (_I, [_H, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ilm_debug_chunk_category_bounds": (_I, [_H, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "ilm_debug_step_category_waves": (_I, [_H, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ilm_debug_last_light_launch": (_I, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ilm_debug_divide_by_constants": (_I, [_H, _P, _P, _I, C.POINTER(_I)]),
     "ilm_sdf_destroy": (_I, [_H]),

@@ -590,6 +590,19 @@ int32_t ilm_debug_step_sdf_samples(IlmHandle ctx, int32_t enable, uint64_t* out_
  * finished through the selects (*out_selected); the call returns the counts accumulated since the previous call (either pointer may be
  * NULL) and clears them.  Synchronises the context.  One atomic per counted wave while it is on; one scalar load per wave while off. */
 int32_t ilm_debug_step_regular_waves(IlmHandle ctx, int32_t enable, uint64_t* out_regular, uint64_t* out_selected);
+/* Diagnostic: the category record of one chunk as the library holds it.  Ahead of a launch of ILM_STEP_KERNEL_LEAN_CLAMP whose transforms
+ * hold no FMA the library scans the category plane of every chunk of the launch that has no current record: *out_lo / *out_hi are the
+ * smallest and the largest category among the chunk's used slots (a NaN lo when one of them is a NaN), and *out_current is 1 while the
+ * record is known to bound the category of every live slot of the chunk -- uploads, spawners, FMA steps, erase, chunk exchange, a
+ * handed-out chunk pointer and graph capture end that.  A wave of that kernel whose chunk's bounds lie inside the step's category
+ * filters does not read the category plane.  Before the first scan the bounds read 0.  Any pointer may be NULL.  Synchronises the
+ * context. */
+int32_t ilm_debug_chunk_category_bounds(IlmHandle system, int32_t chunk, float* out_lo, float* out_hi, int32_t* out_current);
+/* Diagnostic, as ilm_debug_step_regular_waves: the waves of ILM_STEP_KERNEL_LEAN_CLAMP counted by what they did about the category
+ * plane -- never loaded it (*out_skipped: the chunk's record lies inside the filters and the wave stayed regular), loaded it late
+ * (*out_late: such a wave that left the regular body) or loaded it up front with the other planes (*out_upfront).  The three add up to
+ * the waves of the kernel that were not skipped as never written.  Any pointer may be NULL.  Synchronises the context. */
+int32_t ilm_debug_step_category_waves(IlmHandle ctx, int32_t enable, uint64_t* out_skipped, uint64_t* out_late, uint64_t* out_upfront);
 /* The grid of the context's last light-pass launch (sphere or particle lights): workgroups of 256 threads (four waves each; exit-only
  * workgroups of partial tile groups included -- what a profiler's wave count sees), the largest number of workgroups per tile (light
  * split; 1 = none) and the edge of the tile groups dealt to the XCDs (0: another block -> tile map).  Measurement scripts price per-wave
