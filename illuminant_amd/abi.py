@@ -301,6 +301,11 @@ class ParticleLightParams(C.Structure):
                 ("StippleFactor", f32), ("_pad", f32 * 3)]
 
 
+class ParticleLightItem(C.Structure):
+    """One ParticleLightSource inside ilm_engine_render_particle_lights_batch: the system arguments of ilm_render_particle_lights."""
+    _fields_ = [("System", Handle), ("QuadCounts", C.c_void_p), ("ChunkCount", i32), ("_pad", i32), ("Params", ParticleLightParams)]
+
+
 HDR_NONE, HDR_GAMMA_COMPRESS, HDR_TONE_MAP = 0, 1, 2
 
 
@@ -386,4 +391,5 @@ EXPECTED_SIZES = {
     "IlmVisualizeVertex": (VisualizeVertex, 52), "IlmVisualizeParams": (VisualizeParams, 80),
     "IlmLUTBlending": (LUTBlending, 64),
     "IlmRasterizeItem": (RasterizeItem, 216),
+    "IlmParticleLightItem": (ParticleLightItem, 104),
 }

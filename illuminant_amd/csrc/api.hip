@@ -104,6 +104,7 @@ struct Ctx {
     DeviceScratch d_group_order; uint64_t group_order_key = 0; int group_order_groups = 0;
     // particle lights: records compacted on the device + their count, block counts, per-chunk quad counts
     DeviceScratch d_pl_recs, d_pl_count, d_pl_blocks, d_pl_quads;
+    DeviceScratch d_pl_batch;             // ilm_engine_render_particle_lights_batch: the (item, chunk) entry table, then the items' parameters
     float4* d_light_ramp = nullptr; int light_ramp_w = 0, light_ramp_h = 0;    // RampTexture of the light group being rendered
     // ProjectorLightSource.TextureRef of the projector group being rendered (ilm_ctx_set_projector_texture): a binding of its own
     DeviceScratch d_projector_texture; int projector_texture_w = 0, projector_texture_h = 0;
@@ -123,8 +124,8 @@ struct Ctx {
     DeviceScratch d_field_params;
     DeviceScratch d_sense;                                         // ilm_system_sense: the counters [sensor][chunk], kSenseStride words apart
     // every block `reserve` grows: what ilm_ctx_destroy frees
-    std::array<DeviceScratch*, 23> scratch() {
-        return { &staging, &d_recs, &d_light_partials, &d_light_tickets, &d_group_order, &d_pl_recs, &d_pl_count, &d_pl_blocks, &d_pl_quads,
+    std::array<DeviceScratch*, 24> scratch() {
+        return { &staging, &d_recs, &d_light_partials, &d_light_tickets, &d_group_order, &d_pl_recs, &d_pl_count, &d_pl_blocks, &d_pl_quads, &d_pl_batch,
                  &d_raster_quads, &d_raster_items, &d_rb, &d_rb_count, &d_rb_blocks, &d_rb_elems, &d_probe_pairs, &brightness.level, &brightness.mip,
                  &brightness.work, &brightness.partials, &d_field_params, &d_projector_texture, &d_sense };
     }
@@ -160,6 +161,10 @@ struct Engine {
     std::vector<void*> d_batch_outgrown;
     int last_batch_launches = 0, last_batch_rounds = 0, last_batch_fallback = 0;      // ilm_debug_last_step_batch
     int last_render_items = 0, last_render_sorts = 0, last_render_tile_launches = 0;  // ilm_debug_last_render_batch
+    // ilm_debug_last_particle_light_batch: what the latest batch queued, and the word its scan kernel publishes the record count to
+    // (page-locked, device-visible; read once the stream has passed the batch)
+    int last_pl_items = 0, last_pl_prepare = 0, last_pl_tile_launches = 0;
+    int32_t* h_pl_emitted = nullptr; int32_t* h_pl_emitted_dev = nullptr;
 };
 
 // A distance field or G-buffer that sibling contexts read (light passes on another context's stream).  Every WRITE to it happens on its
@@ -1848,6 +1853,7 @@ int32_t ilm_engine_destroy(IlmHandle h) {
     }
     if (e->d_batch) (void)hipFree(e->d_batch);
     for (void* p : e->d_batch_outgrown) (void)hipFree(p);
+    if (e->h_pl_emitted) (void)hipHostFree(e->h_pl_emitted);
     retire_handle(e);
     delete e;
     return ILM_OK;
@@ -3408,6 +3414,124 @@ int32_t ilm_render_particle_lights(IlmHandle hctx, IlmHandle hsystem, const int3
     HIP_TRY(launch_sphere_lights_prepared(a, c->d_pl_recs.p, c->main()));
     HIP_TRY(light_pass_queued(c, f, g));
     HIP_TRY(launch_stats_end(c, stats));
+    return ILM_OK;
+}
+
+// ilm_engine_render_particle_lights_batch.  Everything is judged before anything is queued: the handles, the items one by one (host
+// arithmetic only), then what fill_light_launch judges -- it prepares the field's view last, behind its own checks.  The chunks with a
+// quad count above 0 become entries of the context's device table, the items' parameters lie behind it: ONE upload.  Then three
+// preparation launches and the tile kernel once, as the single call queues it.
+int32_t ilm_engine_render_particle_lights_batch(IlmHandle hengine, const IlmParticleLightItem* items, int32_t count, const IlmEnvironment* env,
+                                                const IlmDistanceFieldUniforms* df, IlmHandle hgbuffer, IlmHandle hsdf, IlmHandle hlightmap,
+                                                int32_t row_begin, int32_t row_end, IlmRenderStats* stats) {
+    ILM_TRACE_RANGE("ilm_engine_render_particle_lights_batch");
+    Engine* e = from_handle<Engine>(hengine, kMagicEngine);
+    if (!e) return fail(ILM_ERR_INVALID_HANDLE, "not an engine handle");
+    if (!from_handle<Lightmap>(hlightmap, kMagicLightmap)) return fail(ILM_ERR_INVALID_HANDLE, "not a lightmap handle");
+    if (count < 0) return fail(ILM_ERR_INVALID_ARGUMENT, "count %d is negative", count);
+    if (count > 0 && !items) return fail(ILM_ERR_INVALID_ARGUMENT, "items is NULL");
+    Ctx* c = e->ctx;
+    std::vector<System*> systems((size_t)count);
+    int64_t total = 0, blocks = 0;
+    size_t entry_count = 0;
+    for (int i = 0; i < count; i++) {
+        const IlmParticleLightItem& it = items[i];
+        System* s = from_handle<System>(it.System, kMagicSystem);
+        if (!s) return fail(ILM_ERR_INVALID_HANDLE, "item %d: not a system handle", i);
+        if (s->engine != e) return fail(ILM_ERR_INVALID_ARGUMENT, "item %d: the system belongs to another engine", i);
+        if (!(it.Params.StippleFactor >= 1.0f))
+            return fail(ILM_ERR_INVALID_ARGUMENT, "item %d: StippleFactor %g < 1 needs Fracture's StippleReject, which is outside the reference tree", i,
+                        (double)it.Params.StippleFactor);
+        const int n = (int)s->chunks.size();
+        if (it.ChunkCount < 0 || it.ChunkCount > n) return fail(ILM_ERR_OUT_OF_RANGE, "item %d: chunk_count %d outside [0, %d]", i, it.ChunkCount, n);
+        for (int k = 0; k < it.ChunkCount; k++) {
+            const int q = it.QuadCounts ? it.QuadCounts[k] : e->slots;
+            if (q < 0 || q > e->slots) return fail(ILM_ERR_OUT_OF_RANGE, "item %d: quad_counts[%d] = %d outside [0, %d]", i, k, q, e->slots);
+            if (q == 0) continue;
+            total += q;
+            blocks += (q + kParticleLightBatchBlock - 1) / kParticleLightBatchBlock;
+            entry_count++;
+        }
+        if (total > (1 << 22))
+            return fail(ILM_ERR_TOO_MANY, "item %d: %lld particle lights in the batch up to this item (limit %d)", i, (long long)total, 1 << 22);
+        systems[(size_t)i] = s;
+    }
+    LightLaunch a = {};
+    Sdf* f = nullptr; GBuffer* g = nullptr;
+    int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, &f, &g, true, "ilm_engine_render_particle_lights_batch");
+    if (rc != ILM_OK) return rc;
+    e->last_pl_items = count; e->last_pl_prepare = e->last_pl_tile_launches = 0;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (total == 0) return ILM_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!e->h_pl_emitted) {
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->h_pl_emitted), sizeof(int32_t), hipHostMallocMapped));
+        *e->h_pl_emitted = 0;
+        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_pl_emitted_dev), e->h_pl_emitted, 0));
+    }
+    // (an entry carries its chunk's address: no system's chunk table is read on the device)
+    // the entries, then the parameters (entries are multiples of 8 bytes, a parameter block is floats: both stay aligned)
+    const size_t table_bytes = sizeof(ParticleLightBatchEntry) * entry_count, bytes = table_bytes + sizeof(IlmParticleLightParams) * (size_t)count;
+    rc = reserve(c, c->d_pl_recs, kLightRecBytes * (size_t)total, kLightRecBytes * (size_t)std::max<int64_t>(total, 4096));
+    if (rc == ILM_OK) rc = reserve(c, c->d_pl_count, sizeof(int32_t), sizeof(int32_t));
+    if (rc == ILM_OK) rc = reserve(c, c->d_pl_blocks, sizeof(int32_t) * (size_t)blocks, sizeof(int32_t) * (size_t)blocks * 2);
+    if (rc == ILM_OK) rc = reserve(c, c->d_pl_batch, bytes, bytes * 2);
+    if (rc != ILM_OK) return rc;
+    void* host = nullptr;
+    int slot = -1;
+    rc = upload_small_begin(c, bytes, &host, &slot);
+    if (rc != ILM_OK) return rc;
+    ParticleLightBatchEntry* entries = static_cast<ParticleLightBatchEntry*>(host);
+    IlmParticleLightParams* params = reinterpret_cast<IlmParticleLightParams*>(static_cast<char*>(host) + table_bytes);
+    size_t at = 0;
+    int32_t first_block = 0;
+    for (int i = 0; i < count; i++) {
+        const IlmParticleLightItem& it = items[i];
+        params[i] = it.Params;
+        for (int k = 0; k < it.ChunkCount; k++) {
+            const int q = it.QuadCounts ? it.QuadCounts[k] : e->slots;
+            if (q == 0) continue;
+            ParticleLightBatchEntry& r = entries[at++];
+            r.base = systems[(size_t)i]->chunks[(size_t)k]; r.quads = q; r.item = i; r.first_block = first_block; r._pad = 0;
+            first_block += (q + kParticleLightBatchBlock - 1) / kParticleLightBatchBlock;
+        }
+    }
+    rc = upload_small_commit(c, c->d_pl_batch.p, slot, bytes);
+    if (rc != ILM_OK) return rc;
+    ParticleLightBatchLaunch pl;
+    pl.entries = c->d_pl_batch.as<ParticleLightBatchEntry>(); pl.entry_count = (int32_t)entry_count; pl.block_count = (int32_t)blocks;
+    pl.params = reinterpret_cast<const IlmParticleLightParams*>(static_cast<const char*>(c->d_pl_batch.p) + table_bytes);
+    pl.stride = e->stride; pl.env = *env; pl.max_cone_radius = df->ConeAndMisc.x;
+    pl.gate = make_trace_gate(*df, a.sdf);
+    pl.block_counts = c->d_pl_blocks.as<int32_t>(); pl.recs = c->d_pl_recs.p; pl.capacity = (int32_t)(c->d_pl_recs.bytes / kLightRecBytes);
+    pl.out_count = c->d_pl_count.as<int32_t>(); pl.out_count_host = e->h_pl_emitted_dev;
+    HIP_TRY(launch_prepare_particle_lights_batch(pl, c->main()));
+    e->last_pl_prepare = 3;
+
+    a.light_count = 0;
+    a.light_count_ptr = c->d_pl_count.as<int32_t>();
+    a.accumulate = 1;
+    HIP_TRY(launch_stats_begin(c, stats != nullptr, &a.stats));
+    c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
+    HIP_TRY(launch_sphere_lights_prepared(a, c->d_pl_recs.p, c->main()));
+    e->last_pl_tile_launches = 1;
+    HIP_TRY(light_pass_queued(c, f, g));
+    HIP_TRY(launch_stats_end(c, stats));
+    return ILM_OK;
+}
+int32_t ilm_debug_last_particle_light_batch(IlmHandle h, int32_t* out_items, int32_t* out_prepare_launches, int32_t* out_tile_launches) {
+    Engine* e = from_handle<Engine>(h, kMagicEngine);
+    if (!e) return fail(ILM_ERR_INVALID_HANDLE, "not an engine handle");
+    int prepare = e->last_pl_prepare, tile = e->last_pl_tile_launches;
+    if (tile > 0) {
+        // whether the batch's list held a record is the device's knowledge: behind the stream, in the word the scan kernel published
+        HIP_TRY(hipSetDevice(e->ctx->device));
+        HIP_TRY(hipStreamSynchronize(e->ctx->main()));
+        if (*e->h_pl_emitted == 0) prepare = tile = 0;
+    }
+    if (out_items) *out_items = e->last_pl_items;
+    if (out_prepare_launches) *out_prepare_launches = prepare;
+    if (out_tile_launches) *out_tile_launches = tile;
     return ILM_OK;
 }
 

@@ -309,6 +309,26 @@ struct ParticleLightLaunch {
     int32_t* out_count;
 };
 hipError_t launch_prepare_particle_lights(const ParticleLightLaunch& a, hipStream_t stream);
+// The same compaction over the chunks of many systems (ilm_engine_render_particle_lights_batch): one entry per (item, chunk) with a quad
+// count above 0, in batch order.  An entry owns the ceil(quads / kParticleLightBatchBlock) workgroups from first_block on; `item` indexes
+// the table of the items' parameters.  Records come out in entry / slot order -- item, chunk, slot.
+constexpr int kParticleLightBatchBlock = 256;
+struct ParticleLightBatchEntry { const float* base; int32_t quads, item, first_block, _pad; };
+static_assert(sizeof(ParticleLightBatchEntry) == 24, "the entry table is laid out on the host");
+struct ParticleLightBatchLaunch {
+    const ParticleLightBatchEntry* entries; int32_t entry_count;     // device
+    int32_t block_count;                                             // workgroups of all entries
+    const IlmParticleLightParams* params;                            // device, one per item
+    int64_t stride;
+    IlmEnvironment env;
+    float max_cone_radius;
+    TraceGate gate;
+    int32_t* block_counts;          // block_count ints: the workgroups' counts, then their exclusive bases
+    void* recs; int32_t capacity;   // LightRec array
+    int32_t* out_count;             // device: the record count, for the tile kernel
+    int32_t* out_count_host;        // device-visible host word that receives it too (the diagnostic reads it after the stream)
+};
+hipError_t launch_prepare_particle_lights_batch(const ParticleLightBatchLaunch& a, hipStream_t stream);
 // Light probes (SphereLightProbe.fx): every prepared light record on every probe; values = float4 per probe (device)
 hipError_t launch_light_probes(const void* recs, int light_count, const float4* probe_positions, const float4* probe_normals, int probe_count,
                                const IlmEnvironment& env, const IlmDistanceFieldUniforms& df, const SdfView& sdf, const RampView& ramp, float4* values, float4* pairs,

@@ -1061,6 +1061,156 @@ hipError_t launch_prepare_particle_lights(const ParticleLightLaunch& a, hipStrea
 }
 
 // ---------------------------------------------------------------------------------------------
+// Particle lights of MANY systems as one record list (ilm_engine_render_particle_lights_batch): the compaction above over a table of
+// (item, chunk) entries, every record built from its own item's parameters with the single call's operations.  A workgroup is 256 slots
+// of ONE entry, so its entry and its item's parameters are wave-uniform (scalar loads); an entry owns ceil(quads / 256) consecutive
+// workgroups from first_block on, found by a uniform bisection of the table.  Three launches whatever the number of items: the
+// workgroups' counts, ONE workgroup that turns them into exclusive bases (a frame of many systems has more counts than the single
+// call's "every block sums what lies before it" is meant for), the ordered emit.  No workgroup waits for another.
+// ---------------------------------------------------------------------------------------------
+constexpr int kPlBatchBlock = 256;
+constexpr int kPlScanBlock = 1024;
+static_assert(kPlBatchBlock == kParticleLightBatchBlock, "the host counts an entry's workgroups in kParticleLightBatchBlock slots");
+
+// the last entry whose first_block <= block (first_block rises strictly: every entry has at least one workgroup)
+ILM_DEV int particle_light_batch_entry(const ParticleLightBatchEntry* __restrict__ entries, int entry_count, int block) {
+    int lo = 0, hi = entry_count - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (entries[mid].first_block <= block) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// particle_emits_light for a slot of an entry: the same loads, the same un-premultiply, the same product, the same predicate
+ILM_DEV bool particle_light_batch_emits(const ParticleLightBatchEntry& e, int64_t S, int slot, const IlmFloat4& item_color, float4& position,
+                                        float4& light_color) {
+    if (slot >= e.quads)      // (quads <= slots: the entry point's check)
+        return false;
+    const float* base = e.base;
+    position = mk4(base[slot], base[S + slot], base[2 * S + slot], base[3 * S + slot]);
+    float4 rc = mk4(base[12 * S + slot], base[13 * S + slot], base[14 * S + slot], base[15 * S + slot]);   // Chunk.RenderColor
+    if (rc.w > 0.0f) {   // unpremultiply, :43-45
+        rc.x /= rc.w; rc.y /= rc.w; rc.z /= rc.w;
+    }
+    if (position.w <= 0.0f)
+        return false;
+    light_color = mul4(rc, ld4(item_color));
+    return light_color.w > 0.0f;
+}
+
+__global__ __launch_bounds__(kPlBatchBlock) void particle_light_batch_count_kernel(const ParticleLightBatchLaunch a,
+                                                                                   const ParticleLightBatchEntry* __restrict__ entries,
+                                                                                   const IlmParticleLightParams* __restrict__ params,
+                                                                                   int32_t* __restrict__ block_counts) {
+    __shared__ int wave_counts[kPlBatchBlock / 64];
+    const ParticleLightBatchEntry e = entries[particle_light_batch_entry(entries, a.entry_count, (int)blockIdx.x)];
+    const int slot = ((int)blockIdx.x - e.first_block) * kPlBatchBlock + (int)threadIdx.x;
+    float4 pos, col;
+    const bool emit = particle_light_batch_emits(e, a.stride, slot, params[e.item].LightColor, pos, col);
+    const unsigned long long m = __ballot(emit);
+    if ((threadIdx.x & 63u) == 0u) wave_counts[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (int w = 0; w < kPlBatchBlock / 64; w++) n += wave_counts[w];
+        block_counts[blockIdx.x] = n;
+    }
+}
+
+// counts[0 .. n) -> their exclusive prefix sums, in place; the total (at most `capacity`) -> *out_count and *out_count_host.  One
+// workgroup walks the array 1 024 counts at a time: a wave's inclusive scan by shuffles, the sixteen wave totals through LDS, the
+// carry in a register every lane keeps alike.
+__global__ __launch_bounds__(kPlScanBlock) void particle_light_batch_scan_kernel(int32_t* __restrict__ counts, int n, int capacity,
+                                                                                 int32_t* __restrict__ out_count, int32_t* __restrict__ out_count_host) {
+    __shared__ int wave_sums[kPlScanBlock / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    int carry = 0;
+    for (int first = 0; first < n; first += kPlScanBlock) {
+        const int i = first + (int)threadIdx.x;
+        const int v = (i < n) ? counts[i] : 0;
+        int x = v;
+        for (int off = 1; off < 64; off <<= 1) {
+            const int y = __shfl_up(x, off);
+            if (lane >= off) x += y;
+        }
+        if (lane == 63) wave_sums[wave] = x;
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < kPlScanBlock / 64; w++) {
+            const int s = wave_sums[w];
+            if (w < wave) before += s;
+            total += s;
+        }
+        if (i < n) counts[i] = carry + before + x - v;
+        carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const int total = min(carry, capacity);
+        *out_count = total;
+        *out_count_host = total;
+    }
+}
+
+__global__ __launch_bounds__(kPlBatchBlock) void particle_light_batch_emit_kernel(const ParticleLightBatchLaunch a,
+                                                                                  const ParticleLightBatchEntry* __restrict__ entries,
+                                                                                  const IlmParticleLightParams* __restrict__ params,
+                                                                                  const int32_t* __restrict__ block_bases, LightRec* __restrict__ recs) {
+    __shared__ int wave_counts[kPlBatchBlock / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const ParticleLightBatchEntry e = entries[particle_light_batch_entry(entries, a.entry_count, (int)blockIdx.x)];
+    const IlmParticleLightParams& P = params[e.item];
+    const int slot = ((int)blockIdx.x - e.first_block) * kPlBatchBlock + (int)threadIdx.x;
+    float4 pos, col;
+    const bool emit = particle_light_batch_emits(e, a.stride, slot, P.LightColor, pos, col);
+    const unsigned long long m = __ballot(emit);
+    if (lane == 0) wave_counts[wave] = __popcll(m);
+    __syncthreads();
+    if (!emit)
+        return;
+    int index = block_bases[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; w++) index += wave_counts[w];
+    if (index >= a.capacity)
+        return;
+    // the record: particle_light_emit_kernel's statements, with the item's parameters for the call's
+    LightRec r;
+    r.cx = pos.x; r.cy = pos.y; r.cz = pos.z;
+    r.radius = P.LightProperties.x; r.ramp = P.LightProperties.y; r.falloff_mode = P.LightProperties.z; r.casts_shadows = P.LightProperties.w;
+    r.ao_radius = P.MoreLightProperties.x; r.falloff_y = P.MoreLightProperties.z; r.ao_opacity = P.MoreLightProperties.w;
+    r.shadow_filter = -1.0f;
+    r.col_r = col.x * col.w; r.col_g = col.y * col.w; r.col_b = col.z * col.w;
+    r.spec_r = P.LightSpecularColor.x; r.spec_g = P.LightSpecularColor.y; r.spec_b = P.LightSpecularColor.z; r.spec_power = P.LightSpecularColor.w;
+    const float radius = P.LightProperties.x + P.LightProperties.y + 1.0f;
+    const float tlx = r.cx - radius, brx = r.cx + radius, bry = r.cy + radius;
+    float tly = r.cy - radius;
+    tly -= radius * a.env.ZToY.y;
+    tly -= r.cz * a.env.ZToY.x;
+    const float sx = a.env.GBufferTexelSizeAndMisc.z * a.env.ZAndScale.z, sy = a.env.GBufferTexelSizeAndMisc.w * a.env.ZAndScale.w;
+    r.fx0 = r.fx1 = (tlx - a.env.ViewportPosition[0]) * sx;
+    r.fx2 = r.fx3 = (brx - a.env.ViewportPosition[0]) * sx;
+    r.fy0 = r.fy1 = (tly - a.env.ViewportPosition[1]) * sy;
+    r.fy2 = r.fy3 = (bry - a.env.ViewportPosition[1]) * sy;
+    const float max_radius = clampf(r.radius, ref::kMinConeRadius, a.max_cone_radius);
+    r.cfg_x = max_radius;
+    r.cfg_y = max_radius / fmaxf(r.ramp, 16.0f) * 1.0f;
+    r.ramp_offset = r.ramp_rate = 0.0f;
+    const int flags = light_flags(r, a.gate);
+    r.flags = (float)flags;
+    r.ramp_rcp = (flags & kLightFastDivide) ? refined_rcp(r.ramp) : 0.0f;
+    recs[index] = r;
+}
+
+hipError_t launch_prepare_particle_lights_batch(const ParticleLightBatchLaunch& a, hipStream_t stream) {
+    hipLaunchKernelGGL(particle_light_batch_count_kernel, dim3(a.block_count), dim3(kPlBatchBlock), 0, stream, a, a.entries, a.params, a.block_counts);
+    hipLaunchKernelGGL(particle_light_batch_scan_kernel, dim3(1), dim3(kPlScanBlock), 0, stream, a.block_counts, a.block_count, a.capacity, a.out_count,
+                       a.out_count_host);
+    hipLaunchKernelGGL(particle_light_batch_emit_kernel, dim3(a.block_count), dim3(kPlBatchBlock), 0, stream, a, a.entries, a.params, a.block_counts,
+                       reinterpret_cast<LightRec*>(a.recs));
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Light probes -- SphereLightProbePixelShader, SphereLightProbe.fx:19-44: one lane per probe walks every light record
 // (uniform index -> scalar loads), fp32 accumulation in light order.
 // ---------------------------------------------------------------------------------------------

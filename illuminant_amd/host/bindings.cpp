@@ -100,6 +100,7 @@ PYBIND11_MODULE(_host, m) {
         .def(py::init<DeviceContext&, int, int, float, int, double, int, int>(), py::arg("ctx"), py::arg("virtualWidth"), py::arg("virtualHeight"),
              py::arg("virtualDepth"), py::arg("requestedSliceCount"), py::arg("requestedResolution") = 1.0,
              py::arg("maximumEncodedDistance") = 128, py::arg("format") = 0, py::keep_alive<1, 2>())
+        .def_property_readonly("TextureHandle", &DistanceField::Texture)
         .def_readonly("VirtualWidth", &DistanceField::VirtualWidth).def_readonly("VirtualHeight", &DistanceField::VirtualHeight)
         .def_readonly("VirtualDepth", &DistanceField::VirtualDepth).def_readonly("Resolution", &DistanceField::Resolution)
         .def_readonly("SliceWidth", &DistanceField::SliceWidth).def_readonly("SliceHeight", &DistanceField::SliceHeight)
@@ -156,6 +157,7 @@ PYBIND11_MODULE(_host, m) {
             return new ParticleEngine(ctx, cfg, rnd.data());
         }), py::keep_alive<1, 2>())
         .def_readonly("Configuration", &ParticleEngine::Configuration)
+        .def_property_readonly("Handle", &ParticleEngine::Handle)
         .def("UpdateSystems", &ParticleEngine::UpdateSystems, py::arg("systems"), py::arg("frameIndex"))
         // RenderSystems(systems, target, blendMode, origin, scale, viewportScale, viewportPosition, wantStats) -> the systems' summed stats
         .def("RenderSystems", [](ParticleEngine& e, const std::vector<ParticleSystem*>& systems, RenderTarget& target, int blendMode,
@@ -647,7 +649,8 @@ PYBIND11_MODULE(_host, m) {
         .def_readwrite("EnableGBuffer", &RendererConfiguration::EnableGBuffer).def_readwrite("RenderGroundPlane", &RendererConfiguration::RenderGroundPlane)
         .def_readwrite("HighQualityGBuffer", &RendererConfiguration::HighQualityGBuffer)
         .def_readwrite("FloatLightmap", &RendererConfiguration::FloatLightmap)
-        .def_readwrite("EnableBrightnessEstimation", &RendererConfiguration::EnableBrightnessEstimation);
+        .def_readwrite("EnableBrightnessEstimation", &RendererConfiguration::EnableBrightnessEstimation)
+        .def_readwrite("BatchParticleLights", &RendererConfiguration::BatchParticleLights);
     py::class_<Histogram>(m, "Histogram")
         .def(py::init<float, float, int, bool>(), py::arg("maxValue"), py::arg("power"), py::arg("bucketCount") = 64, py::arg("ignoreZeroes") = false)
         .def_readonly("BucketCount", &Histogram::BucketCount).def_readonly("MaxInputValue", &Histogram::MaxInputValue)
@@ -805,6 +808,7 @@ PYBIND11_MODULE(_host, m) {
             return std::move(out);
         }, py::arg("firstRow") = 0, py::arg("rowCount") = -1)
         .def_property_readonly("LightmapHandle", &LightingRenderer::Lightmap)
+        .def_property_readonly("GBufferHandle", &LightingRenderer::GBuffer)
         .def("TryComputeHistogram", &LightingRenderer::TryComputeHistogram, py::arg("histogram"), py::arg("accuracyFactor") = 3)
         // rectangle = (left, top, right, bottom); returns (VisualizationInfo, stats tuple or None)
         .def("VisualizeDistanceField", [](LightingRenderer& r, IlmHandle target, const std::vector<float>& rectangle, const std::vector<float>& viewDirection,

@@ -1779,22 +1779,46 @@ void LightingRenderer::RenderLighting(float intensityScale, int rowBegin, int ro
     // ---- particle lights ---------------------------------------------------------------------------------------------------------------
     BindRamp(nullptr);         // particle lights have no ramp technique (:176-178)
     // particle light sources: one more light-type render state each, blended on top (:1126-1141)
+    // Configuration.BatchParticleLights: a run of consecutive sources with the same blend functions over systems of one engine is ONE
+    // ilm_engine_render_particle_lights_batch; a run of one source (every run, with the option off) is the single call
+    struct RunSource { const ParticleLightSource* source; std::vector<int32_t> quads; };
+    std::vector<RunSource> run;
+    const auto blendOf = [](const ParticleLightSource& pls) { return std::pair<int, int>(pls.Template.BlendColorFunction, pls.Template.BlendAlphaFunction); };
+    const auto flushRun = [&]() {
+        if (run.empty()) return;
+        BindBlend(blendOf(*run[0].source));      // a particle light source's template carries its blend functions
+        IlmRenderStats part{};
+        if (run.size() == 1) {
+            const ParticleLightSource& pls = *run[0].source;
+            const IlmParticleLightParams p = PackParticleLight(pls, haveField);
+            ThrowIfFailed(ilm_render_particle_lights(Context.Handle(), pls.System->Handle(), run[0].quads.data(), (int32_t)run[0].quads.size(), &p, &env, &dfu,
+                                                     gbuffer, field, lightmap, rowBegin, rowEnd, stats ? &part : nullptr));
+        } else {
+            std::vector<IlmParticleLightItem> items(run.size());
+            for (size_t i = 0; i < run.size(); i++)
+                items[i] = IlmParticleLightItem{ run[i].source->System->Handle(), run[i].quads.data(), (int32_t)run[i].quads.size(), 0,
+                                                 PackParticleLight(*run[i].source, haveField) };
+            ThrowIfFailed(ilm_engine_render_particle_lights_batch(run[0].source->System->Engine.Handle(), items.data(), (int32_t)items.size(), &env, &dfu,
+                                                                  gbuffer, field, lightmap, rowBegin, rowEnd, stats ? &part : nullptr));
+        }
+        AddStats(stats, part);
+        run.clear();
+    };
     for (const ParticleLightSource& pls : Environment->ParticleLights) {
         if (!pls.Enabled || !pls.IsActive || !pls.System)
             continue;
-        const IlmParticleLightParams p = PackParticleLight(pls, haveField);
         // RenderChunk, ParticleSystem.cs:880: quadCount = min(ChunkMaximumCount, chunk.TotalSpawned + 1)
         std::vector<int32_t> quads;
         for (const Particles::ParticleSystem::Chunk& c : pls.System->Chunks())
             quads.push_back(std::min(pls.System->ChunkMaximumCount(), c.TotalSpawned + 1));
         if (quads.empty())
             continue;
-        BindBlend({ pls.Template.BlendColorFunction, pls.Template.BlendAlphaFunction });      // a particle light source's template carries its blend functions
-        IlmRenderStats part{};
-        ThrowIfFailed(ilm_render_particle_lights(Context.Handle(), pls.System->Handle(), quads.data(), (int32_t)quads.size(), &p, &env, &dfu,
-                                                 gbuffer, field, lightmap, rowBegin, rowEnd, stats ? &part : nullptr));
-        AddStats(stats, part);
+        if (!Configuration.BatchParticleLights ||
+            (!run.empty() && (blendOf(pls) != blendOf(*run[0].source) || &pls.System->Engine != &run[0].source->System->Engine)))
+            flushRun();
+        run.push_back(RunSource{ &pls, std::move(quads) });
     }
+    flushRun();
     lastInverseScaleFactor = 1.0f / intensityScale;      // new RenderedLighting(this, lightmap.Buffer, 1.0f / intensityScale, ...), :963-966
     BindBlend({ ILM_LIGHT_BLEND_ADD, ILM_LIGHT_BLEND_ADD });
 

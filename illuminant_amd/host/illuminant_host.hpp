@@ -1012,6 +1012,9 @@ struct RendererConfiguration {
     bool EnableBrightnessEstimation = false;   // LightingRenderer.Configuration.cs: RenderLighting keeps what TryComputeHistogram reads
     std::shared_ptr<RampTexture> DefaultRampTexture;   // LightingRenderer.Configuration.cs:78
     float ProjectorMipBias = -0.33f;       // LightingRenderer.Configuration.cs:164
+    // extension: RenderLighting makes one ilm_engine_render_particle_lights_batch of each run of consecutive particle light sources with
+    // equal blend functions over systems of one engine (one light list and one tile pass per run; sums differ in order from the loop's)
+    bool BatchParticleLights = false;
     RendererConfiguration(int w, int h) : RenderWidth(w), RenderHeight(h) {}
 };
 

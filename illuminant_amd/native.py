@@ -121,6 +121,8 @@ SYMBOLS = {
     "ilm_render_particles": (_I, [_H, _P, _I, _P, _H, _P]),
     "ilm_engine_render_particles_batch": (_I, [_H, _P, _I, _H, _P]),
     "ilm_debug_last_render_batch": (_I, [_H, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "ilm_engine_render_particle_lights_batch": (_I, [_H, _P, _I, _P, _P, _H, _H, _H, _I, _I, _P]),
+    "ilm_debug_last_particle_light_batch": (_I, [_H, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ilm_lightmap_clear": (_I, [_H, _P]),
     "ilm_ctx_set_light_ramp": (_I, [_H, _P, _I, _I]),
     "ilm_ctx_set_projector_texture": (_I, [_H, _P, _I, _I]),
@@ -361,6 +363,47 @@ class Engine:
         items, sorts, launches = C.c_int32(), C.c_int32(), C.c_int32()
         check(lib().ilm_debug_last_render_batch(self.handle, C.byref(items), C.byref(sorts), C.byref(launches)))
         return int(items.value), int(sorts.value), int(launches.value)
+
+    def render_particle_lights_batch(self, items, env, df, gbuffer, sdf, lightmap, row_begin=0, row_end=None, want_stats=False):
+        """ilm_engine_render_particle_lights_batch: the items' live particles as ONE light list, in item / chunk / slot order, through one
+        launch of the tile kernel onto the lightmap's contents.  `items` is a sequence of (system, params) or (system, params,
+        quad_counts) or (system, params, quad_counts, chunk_count) -- the arguments of render_particle_lights -- or a ctypes array of
+        abi.ParticleLightItem (reusable from call to call; the caller keeps what its QuadCounts point at alive).  Returns the
+        abi.RenderStats summed over the items when want_stats."""
+        if isinstance(items, C.Array):
+            packed, n, keep = items, len(items), None
+        else:
+            n, keep = len(items), []
+            packed = (abi.ParticleLightItem * max(n, 1))()
+            for i, item in enumerate(items):
+                system, params = item[0], item[1]
+                q = item[2] if len(item) > 2 else None
+                chunk_count = item[3] if len(item) > 3 else None
+                if q is not None:
+                    q = np.ascontiguousarray(q, dtype=np.int32)
+                    keep.append(q)
+                    packed[i].QuadCounts = q.ctypes.data
+                if chunk_count is None:
+                    chunk_count = system.chunk_count()
+                packed[i].System = system.handle.value
+                packed[i].ChunkCount = int(chunk_count)
+                C.memmove(C.byref(packed[i], abi.ParticleLightItem.Params.offset), C.byref(params), C.sizeof(abi.ParticleLightParams))
+        if row_end is None:
+            row_end = lightmap.height
+        stats = abi.RenderStats() if want_stats else None
+        check(lib().ilm_engine_render_particle_lights_batch(
+            self.handle, C.cast(packed, C.c_void_p), n, _byref(env), _byref(df),
+            gbuffer.handle if gbuffer is not None else abi.Handle(0), sdf.handle if sdf is not None else abi.Handle(0),
+            lightmap.handle, row_begin, row_end, _byref(stats)))
+        del keep
+        return stats
+
+    def last_particle_light_batch(self):
+        """ilm_debug_last_particle_light_batch: (items, preparation launches, tile-kernel launches) of the engine's latest accepted batch;
+        waits for the context's stream when the batch queued anything."""
+        items, prepare, launches = C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().ilm_debug_last_particle_light_batch(self.handle, C.byref(items), C.byref(prepare), C.byref(launches)))
+        return int(items.value), int(prepare.value), int(launches.value)
 
     def close(self):
         if self.handle.value:

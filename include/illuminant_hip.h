@@ -41,7 +41,8 @@ extern "C" {
  * + ilm_resolve_lighting_lut / IlmLUTBlending (the LUT-blended resolve over a dark and a bright colour LUT);
  * + ilm_sdf_set_filter, ilm_sdf_get_filter, ILM_SDF_FILTER_* (a fixed-point bilinear filter mode of the distance-field sampler);
  * + ilm_engine_render_particles_batch, ilm_debug_last_render_batch / IlmRasterizeItem (a frame's particle systems rasterised as one draw list);
- * + ilm_system_sense, ilm_system_sense_async, ilm_system_poll_sense, ILM_MAX_SENSORS (particle sensors: Transforms.Sensor counted on the device).
+ * + ilm_system_sense, ilm_system_sense_async, ilm_system_poll_sense, ILM_MAX_SENSORS (particle sensors: Transforms.Sensor counted on the device);
+ * + ilm_engine_render_particle_lights_batch, ilm_debug_last_particle_light_batch / IlmParticleLightItem (a frame's particle light sources as one light list).
  * 10: + ilm_lightmap_luminance, ilm_lightmap_histogram, ilm_debug_queue_luminance / IlmHistogramBucket, IlmHistogramParams,
  * IlmHistogramResult (brightness estimation on the device).  Nothing removed or changed in layout.
  * 9 (r06): + ilm_group_gather_chunks (the sharded particle state made whole on every member: Pos+Life for global consumers, Pos+Life
@@ -1226,6 +1227,53 @@ int32_t ilm_render_particle_lights(IlmHandle ctx, IlmHandle system, const int32_
                                    IlmHandle gbuffer, IlmHandle sdf,
                                    IlmHandle lightmap, int32_t row_begin, int32_t row_end,
                                    IlmRenderStats* stats);
+
+/* One ParticleLightSource inside ilm_engine_render_particle_lights_batch: the system arguments of ilm_render_particle_lights. */
+typedef struct {
+    IlmHandle              System;
+    const int32_t*         QuadCounts;  /* ChunkCount entries, or NULL => every slot; as ilm_render_particle_lights */
+    int32_t                ChunkCount;  /* the first ChunkCount chunks of System */
+    int32_t                _pad;
+    IlmParticleLightParams Params;      /* this item's template light */
+} IlmParticleLightItem;                 /* 104 bytes */
+
+/* A frame's particle light sources in one call: the loop of one render state per ParticleLightSource (LightingRenderer.cs:1126-1141) over
+ * the systems of one engine.  The batch is ONE light list: the items' live, visible particles in item, chunk, slot order, each record
+ * built from its OWN item's Params exactly as ilm_render_particle_lights builds it, operation for operation (the emit predicate, the
+ * un-premultiply, the quad, the light's flags under the frame's trace gate).  That list goes through ONE launch of the particle-light
+ * tile kernel onto what the lightmap holds, under the context's current blend function and blend model, over rows [row_begin, row_end).
+ * The context is the engine's.  The same system may appear more than once, with different Params.  Systems, G-buffer, field and
+ * lightmap are read and written as in the single call; store-mode mirrors of a group lightmap receive the same texels.  So:
+ *  - a batch of one item leaves the bits ilm_render_particle_lights leaves, on every lightmap format;
+ *  - items with equal Params whose chunks, concatenated, are the chunks of one system Z leave the bits of one
+ *    ilm_render_particle_lights call on Z (the same list, hence the same parts and the same tree);
+ *  - ADD under fp32 accumulation, items that differ: the K single calls add K tree roots one after the other, the batch forms one tree --
+ *    a DEFINED difference in the order of the sum.  On HALF4 / RGBA8 lightmaps those calls also round after every system, the batch once;
+ *  - MAX / MIN under fp32 accumulation: bit for bit the K single calls on a FLOAT4 lightmap (the order does not matter);
+ *  - ILM_BLEND_FP16_PER_LIGHT: one chain of roundings in list order -- on a HALF4 lightmap, or a FLOAT4 one whose contents are
+ *    half-representable, bit for bit the K single calls in item order;
+ *  - stats (may be NULL) are exactly the sums of what the K single calls report: a (pixel, light) pair's shading does not depend on
+ *    the rest of the list.
+ * count == 0, items without chunks, all-dead systems, quad counts of 0 and a batch in which no particle emits succeed and leave every
+ * texel's bits alone.  Three preparation launches however many items there are; asynchronous on the context's stream unless stats is
+ * given.
+ * Every check runs before anything is queued, uploaded or reserved; a refusal about an item names it in ilm_last_error() ("item 3:
+ * ...") and the lightmap is untouched.  Engine and lightmap handles first (ILM_ERR_INVALID_HANDLE); then count < 0, items == NULL with
+ * count > 0; per item, a handle that is not a system (ILM_ERR_INVALID_HANDLE), a system of another engine (ILM_ERR_INVALID_ARGUMENT),
+ * StippleFactor < 1 (as the single call), ChunkCount outside the system's, a quad count outside [0, slots] (ILM_ERR_OUT_OF_RANGE); over
+ * the batch, more than 2^22 quads in sum (ILM_ERR_TOO_MANY, the single call's bound); and whatever the single call refuses about env,
+ * df, the G-buffer, the field (a filter other than ILM_SDF_FILTER_FP32 included), the lightmap and the rows, with its code. */
+int32_t ilm_engine_render_particle_lights_batch(IlmHandle engine, const IlmParticleLightItem* items, int32_t count,
+                                                const IlmEnvironment* env, const IlmDistanceFieldUniforms* df,
+                                                IlmHandle gbuffer, IlmHandle sdf, IlmHandle lightmap,
+                                                int32_t row_begin, int32_t row_end, IlmRenderStats* stats);
+/* Diagnostic: the engine's latest ilm_engine_render_particle_lights_batch that was accepted -- its items (count), the preparation
+ * launches and the tile-kernel launches its list took: 3 and 1 for a batch that emitted a record, whatever its items; 0 and 0 for one
+ * that had nothing to add.  Without a quad the call queues nothing; with quads of which none emits, what it queued finds an empty list
+ * and changes no texel, which only the device knows: this call waits for the context's stream and reads the record count the
+ * preparation published.  Any out pointer may be NULL. */
+int32_t ilm_debug_last_particle_light_batch(IlmHandle engine, int32_t* out_items, int32_t* out_prepare_launches,
+                                            int32_t* out_tile_launches);
 
 /* technique SphereLightProbe (Illuminant/Shaders/SphereLightProbe.fx:19-44) for `probe_count` probes
  * (UpdateLightProbes, Illuminant/Lighting/LightingRenderer.LightProbes.cs:49-110): probe_positions[i] = (position, 1),

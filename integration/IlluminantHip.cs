@@ -421,6 +421,15 @@ namespace Squared.Illuminant.Native {
         public fixed float _pad[3];
     }
 
+    [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 104)]
+    public struct IlmParticleLightItem {
+        public ulong System;
+        public IntPtr QuadCounts;
+        public int ChunkCount;
+        public int _pad;
+        public IlmParticleLightParams Params;
+    }
+
     [StructLayout(LayoutKind.Sequential, Pack = 4, Size = 48)]
     public unsafe struct IlmReadbackDrawCall {
         public fixed float Position[2];
@@ -655,6 +664,8 @@ namespace Squared.Illuminant.Native {
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_ctx_set_light_blend_function (ulong ctx, int colorFunction, int alphaFunction);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_ctx_set_light_split (ulong ctx, int workgroups);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_particle_lights (ulong ctx, ulong system, int* quadCounts, int chunkCount, IlmParticleLightParams* @params, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong gbuffer, ulong sdf, ulong lightmap, int rowBegin, int rowEnd, IlmRenderStats* stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_engine_render_particle_lights_batch (ulong engine, IlmParticleLightItem* items, int count, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong gbuffer, ulong sdf, ulong lightmap, int rowBegin, int rowEnd, IlmRenderStats* stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_debug_last_particle_light_batch (ulong engine, int* outItems, int* outPrepareLaunches, int* outTileLaunches);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_light_probes (ulong ctx, LightVertex* lights, int lightCount, Vector4* probePositions, Vector4* probeNormals, int probeCount, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong sdf, Vector4* outValues);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_directional_light_probes (ulong ctx, LightVertex* lights, int lightCount, Vector4* probePositions, Vector4* probeNormals, int probeCount, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong sdf, Vector4* outValues);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int ilm_render_line_light_probes (ulong ctx, LightVertex* lights, int lightCount, Vector4* probePositions, Vector4* probeNormals, int probeCount, IlmEnvironment* env, IlmDistanceFieldUniforms* df, ulong sdf, Vector4* outValues);
