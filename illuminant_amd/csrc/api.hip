@@ -2731,6 +2731,9 @@ int32_t ilm_sdf_render_slices(IlmHandle h, IlmHandle hclear, const IlmDistanceFi
     if (d->SliceWidth <= 0 || d->SliceHeight <= 0 || d->ColumnCount <= 0 || d->RowCount <= 0 || d->SliceCount <= 0 ||
         d->VirtualWidth <= 0 || d->VirtualHeight <= 0 || !(d->MaximumEncodedDistance > 0.0f))
         return fail(ILM_ERR_INVALID_ARGUMENT, "bad distance field layout");
+    // a NaN scale factor makes every tile centre, and with it every key of the kernel's nearest-first sort, a NaN (fields.hip)
+    if (!std::isfinite(d->InvScaleFactorX) || !std::isfinite(d->InvScaleFactorY) || !std::isfinite(d->VirtualDepth) || !std::isfinite(d->ZOffset))
+        return fail(ILM_ERR_INVALID_ARGUMENT, "InvScaleFactorX, InvScaleFactorY, VirtualDepth and ZOffset must be finite");
     if (d->SliceWidth * d->ColumnCount != f->width || d->SliceHeight * d->RowCount != f->height)
         return fail(ILM_ERR_INVALID_ARGUMENT, "layout %dx%d slices of %dx%d does not match the %dx%d atlas",
                     d->ColumnCount, d->RowCount, d->SliceWidth, d->SliceHeight, f->width, f->height);
@@ -2897,7 +2900,10 @@ int32_t ilm_gbuffer_render(IlmHandle h, const IlmGBufferRenderDesc* d, const Ilm
     if (!d) return fail(ILM_ERR_INVALID_ARGUMENT, "desc is NULL");
     if (volume_count < 0 || polygon_vertex_count < 0 || (volume_count > 0 && (!volumes || !polygon_xy)))
         return fail(ILM_ERR_INVALID_ARGUMENT, "bad array argument");
-    if (!(d->ViewportScale[0] > 0.0f) || !(d->ViewportScale[1] > 0.0f)) return fail(ILM_ERR_INVALID_ARGUMENT, "ViewportScale must be positive");
+    // Coverage is decided per pixel centre (no quad whose vertex order a mirrored view could change, unlike ilm_gbuffer_render_meshes),
+    // so either sign of the scale is a view; a NaN scale puts every pixel centre outside every volume, in the kernel as in the oracle
+    // (fields.hip lists every volume for every tile then).  Only zero has no inverse.
+    if (d->ViewportScale[0] == 0.0f || d->ViewportScale[1] == 0.0f) return fail(ILM_ERR_INVALID_ARGUMENT, "ViewportScale must not be zero");
     { const int32_t rc = check_volume_ranges(volumes, volume_count, polygon_vertex_count); if (rc != ILM_OK) return rc; }
     Ctx* c = g->ctx;
     HIP_TRY(hipSetDevice(c->device));

@@ -725,7 +725,9 @@ typedef struct IlmDistanceFieldRenderDesc {
  * rasterised into it with the analytic distance functions of DistanceFunction.fx:33-115 (quad of half-size
  * max|Size| + MaximumEncodedDistance + 4, :24-25) / DistanceField.fx:75-115, encoded (DistanceFieldCommon.fxh:264-266)
  * and MAX-blended (LoadMaterials.cs:164-176); texel RGBA = virtual slices s .. s+3.
- * `obstructions`, `volumes`, `polygon_xy` (x,y pairs) and `first_virtual_slices` are host arrays.  Asynchronous. */
+ * `obstructions`, `volumes`, `polygon_xy` (x,y pairs) and `first_virtual_slices` are host arrays.  Asynchronous.
+ * InvScaleFactorX, InvScaleFactorY, VirtualDepth and ZOffset of `desc` must be finite: ILM_ERR_INVALID_ARGUMENT otherwise, with
+ * nothing queued and the atlas untouched. */
 int32_t ilm_sdf_render_slices(IlmHandle sdf, IlmHandle clear_source, const IlmDistanceFieldRenderDesc* desc,
                               const int32_t* first_virtual_slices, int32_t triplet_count,
                               const IlmObstruction* obstructions, int32_t obstruction_count,
@@ -755,7 +757,9 @@ typedef struct IlmGBufferRenderDesc {
  * material from the lowest to the highest (RenderGBufferVolumes, :205-219), encoded by encodeGBufferSample
  * (Illuminant/Shaders/GBufferShaderCommon.fxh:10-35).  The top-face meshes come from Fracture's Geometry.Triangulate
  * (SDF/HeightVolume.cs:126-133), which is outside the tree; a triangulation covers exactly the polygon's interior, so coverage
- * is decided per pixel centre with an even-odd point-in-polygon test instead.  Host arrays; asynchronous. */
+ * is decided per pixel centre with an even-odd point-in-polygon test instead.  Host arrays; asynchronous.
+ * ViewportScale may be negative (a mirrored view); a zero component is ILM_ERR_INVALID_ARGUMENT.  A NaN scale leaves every pixel
+ * centre outside every volume: the ground plane alone. */
 int32_t ilm_gbuffer_render(IlmHandle gbuffer, const IlmGBufferRenderDesc* desc,
                            const IlmHeightVolume* volumes, int32_t volume_count,
                            const float* polygon_xy, int32_t polygon_vertex_count);

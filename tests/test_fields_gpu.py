@@ -153,6 +153,21 @@ def test_argument_validation(ctx):
         sdf.render_slices(d, [0], None)
     assert e.value.code == abi.ERR_INVALID_ARGUMENT
     sdf.close()
+    # a desc float that is not finite is refused before anything is queued (a NaN scale factor would make every key of the kernel's
+    # nearest-first sort a NaN): the atlas keeps what it held
+    sentinel = np.full((layout.atlas_height, layout.atlas_width, 4), 7, np.uint16)
+    sdf = native.DistanceFieldTexture(ctx, sentinel)
+    obs = scenes.obstruction_array(scenes.random_obstructions(3, 6, (96, 64), 6.0, 20.0, 30.0))
+    for field in ("InvScaleFactorX", "InvScaleFactorY", "VirtualDepth", "ZOffset"):
+        d = scenes.render_desc(layout)
+        setattr(d, field, float("nan"))
+        with pytest.raises(native.IlluminantError) as e:
+            sdf.render_slices(d, fc.all_triplets(layout), obs)
+        assert e.value.code == abi.ERR_INVALID_ARGUMENT, field
+        assert (sdf.download() == 7).all(), field
+    sdf.render_slices(scenes.render_desc(layout), fc.all_triplets(layout), obs)         # the same call with a finite desc renders
+    assert (sdf.download() != 7).any()
+    sdf.close()
 
 
 def test_full_size_field_of_the_lighting_configs(ctx, oracle):
