@@ -3356,6 +3356,53 @@ int32_t fill_light_launch(Ctx* c, const IlmEnvironment* env, const IlmDistanceFi
     *out_field = f; *out_gbuffer = g;
     return ILM_OK;
 }
+
+// What ilm_render_particle_lights judges about one system -- ilm_engine_render_particle_lights_batch asks the same of every item -- in
+// check_raster_item's shape: the code is returned and the sentence written, nothing is changed.  Two halves, because the single call
+// judges the quad counts behind fill_light_launch and the batch judges everything before it.
+int32_t check_particle_light_item(const System* s, int32_t chunk_count, const IlmParticleLightParams* params, char* text, size_t n) {
+    // StippleReject (Fracture DitherCommon.fxh) is not in the reference tree: only "reject nothing" is defined here
+    if (!(params->StippleFactor >= 1.0f)) {
+        snprintf(text, n, "StippleFactor %g < 1 needs Fracture's StippleReject, which is outside the reference tree", (double)params->StippleFactor);
+        return ILM_ERR_INVALID_ARGUMENT;
+    }
+    const int chunks = (int)s->chunks.size();
+    if (chunk_count < 0 || chunk_count > chunks) { snprintf(text, n, "chunk_count %d outside [0, %d]", chunk_count, chunks); return ILM_ERR_OUT_OF_RANGE; }
+    return ILM_OK;
+}
+// ... and the chunks' quad counts (nullptr: every slot); *total = their sum
+int32_t check_particle_light_quads(const System* s, const int32_t* quad_counts, int32_t chunk_count, int64_t* total, char* text, size_t n) {
+    const int slots = s->engine->slots;
+    *total = 0;
+    for (int i = 0; i < chunk_count; i++) {
+        const int q = quad_counts ? quad_counts[i] : slots;
+        if (q < 0 || q > slots) { snprintf(text, n, "quad_counts[%d] = %d outside [0, %d]", i, q, slots); return ILM_ERR_OUT_OF_RANGE; }
+        *total += q;
+    }
+    return ILM_OK;
+}
+
+// room for `total` particle-light records, their count and the counts of `blocks` workgroups
+int32_t reserve_particle_light_scratch(Ctx* c, int64_t total, int64_t blocks) {
+    int32_t rc = reserve(c, c->d_pl_recs, kLightRecBytes * (size_t)total, kLightRecBytes * (size_t)std::max<int64_t>(total, 4096));
+    if (rc == ILM_OK) rc = reserve(c, c->d_pl_count, sizeof(int32_t), sizeof(int32_t));
+    if (rc == ILM_OK) rc = reserve(c, c->d_pl_blocks, sizeof(int32_t) * (size_t)blocks, sizeof(int32_t) * (size_t)blocks * 2);
+    return rc;
+}
+
+// Both particle-light entries end here: the tile pass over the records a preparation has left in c->d_pl_recs, their number in
+// c->d_pl_count (the device's knowledge: a.light_count stays 0), added to the lightmap.  `a` is fill_light_launch's.
+int32_t queue_particle_light_tiles(Ctx* c, LightLaunch& a, Sdf* f, GBuffer* g, IlmRenderStats* stats) {
+    a.light_count = 0;
+    a.light_count_ptr = c->d_pl_count.as<int32_t>();
+    a.accumulate = 1;
+    HIP_TRY(launch_stats_begin(c, stats != nullptr, &a.stats));
+    c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
+    HIP_TRY(launch_sphere_lights_prepared(a, c->d_pl_recs.p, c->main()));
+    HIP_TRY(light_pass_queued(c, f, g));
+    HIP_TRY(launch_stats_end(c, stats));
+    return ILM_OK;
+}
 }  // namespace
 
 
@@ -3370,11 +3417,8 @@ int32_t ilm_render_particle_lights(IlmHandle hctx, IlmHandle hsystem, const int3
     if (!s) return fail(ILM_ERR_INVALID_HANDLE, "not a system handle");
     if (s->engine->ctx != c) return fail(ILM_ERR_INVALID_ARGUMENT, "the particle system belongs to another context");
     if (!params) return fail(ILM_ERR_INVALID_ARGUMENT, "params is NULL");
-    // StippleReject (Fracture DitherCommon.fxh) is not in the reference tree: only "reject nothing" is defined here
-    if (!(params->StippleFactor >= 1.0f))
-        return fail(ILM_ERR_INVALID_ARGUMENT, "StippleFactor %g < 1 needs Fracture's StippleReject, which is outside the reference tree", (double)params->StippleFactor);
-    const int n = (int)s->chunks.size();
-    if (chunk_count < 0 || chunk_count > n) return fail(ILM_ERR_OUT_OF_RANGE, "chunk_count %d outside [0, %d]", chunk_count, n);
+    char why[256];
+    { const int32_t code = check_particle_light_item(s, chunk_count, params, why, sizeof(why)); if (code != ILM_OK) return fail(code, "%s", why); }
     LightLaunch a = {};
     Sdf* f = nullptr; GBuffer* g = nullptr;
     int32_t rc = fill_light_launch(c, env, df, hgbuffer, hsdf, hlightmap, row_begin, row_end, &a, &f, &g, true, "ilm_render_particle_lights");
@@ -3386,18 +3430,11 @@ int32_t ilm_render_particle_lights(IlmHandle hctx, IlmHandle hsystem, const int3
     if (rc != ILM_OK) return rc;
 
     int64_t total = 0;
-    for (int i = 0; i < chunk_count; i++) {
-        const int q = quad_counts ? quad_counts[i] : e->slots;
-        if (q < 0 || q > e->slots) return fail(ILM_ERR_OUT_OF_RANGE, "quad_counts[%d] = %d outside [0, %d]", i, q, e->slots);
-        total += q;
-    }
+    { const int32_t code = check_particle_light_quads(s, quad_counts, chunk_count, &total, why, sizeof(why)); if (code != ILM_OK) return fail(code, "%s", why); }
     if (total > (1 << 22)) return fail(ILM_ERR_TOO_MANY, "%lld particle lights in one call (limit %d)", (long long)total, 1 << 22);
     if (total == 0) return ILM_OK;
     const int blocks_per_chunk = (e->slots + 1023) / 1024;
-    const int blocks = chunk_count * blocks_per_chunk;
-    rc = reserve(c, c->d_pl_recs, kLightRecBytes * (size_t)total, kLightRecBytes * (size_t)std::max<int64_t>(total, 4096));
-    if (rc == ILM_OK) rc = reserve(c, c->d_pl_count, sizeof(int32_t), sizeof(int32_t));
-    if (rc == ILM_OK) rc = reserve(c, c->d_pl_blocks, sizeof(int32_t) * (size_t)blocks, sizeof(int32_t) * (size_t)blocks * 2);
+    rc = reserve_particle_light_scratch(c, total, chunk_count * blocks_per_chunk);
     if (rc == ILM_OK) rc = reserve(c, c->d_pl_quads, sizeof(int32_t) * (size_t)chunk_count, sizeof(int32_t) * (size_t)chunk_count * 2);
     if (rc != ILM_OK) return rc;
     if (quad_counts) {
@@ -3411,16 +3448,7 @@ int32_t ilm_render_particle_lights(IlmHandle hctx, IlmHandle hsystem, const int3
     pl.gate = make_trace_gate(*df, a.sdf);
     pl.block_counts = c->d_pl_blocks.as<int32_t>(); pl.recs = c->d_pl_recs.p; pl.capacity = (int32_t)(c->d_pl_recs.bytes / kLightRecBytes); pl.out_count = c->d_pl_count.as<int32_t>();
     HIP_TRY(launch_prepare_particle_lights(pl, c->main()));
-
-    a.light_count = 0;
-    a.light_count_ptr = c->d_pl_count.as<int32_t>();
-    a.accumulate = 1;
-    HIP_TRY(launch_stats_begin(c, stats != nullptr, &a.stats));
-    c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
-    HIP_TRY(launch_sphere_lights_prepared(a, c->d_pl_recs.p, c->main()));
-    HIP_TRY(light_pass_queued(c, f, g));
-    HIP_TRY(launch_stats_end(c, stats));
-    return ILM_OK;
+    return queue_particle_light_tiles(c, a, f, g, stats);
 }
 
 // ilm_engine_render_particle_lights_batch.  Everything is judged before anything is queued: the handles, the items one by one (host
@@ -3445,16 +3473,15 @@ int32_t ilm_engine_render_particle_lights_batch(IlmHandle hengine, const IlmPart
         System* s = from_handle<System>(it.System, kMagicSystem);
         if (!s) return fail(ILM_ERR_INVALID_HANDLE, "item %d: not a system handle", i);
         if (s->engine != e) return fail(ILM_ERR_INVALID_ARGUMENT, "item %d: the system belongs to another engine", i);
-        if (!(it.Params.StippleFactor >= 1.0f))
-            return fail(ILM_ERR_INVALID_ARGUMENT, "item %d: StippleFactor %g < 1 needs Fracture's StippleReject, which is outside the reference tree", i,
-                        (double)it.Params.StippleFactor);
-        const int n = (int)s->chunks.size();
-        if (it.ChunkCount < 0 || it.ChunkCount > n) return fail(ILM_ERR_OUT_OF_RANGE, "item %d: chunk_count %d outside [0, %d]", i, it.ChunkCount, n);
+        char why[256];
+        int64_t item_total = 0;
+        int32_t code = check_particle_light_item(s, it.ChunkCount, &it.Params, why, sizeof(why));
+        if (code == ILM_OK) code = check_particle_light_quads(s, it.QuadCounts, it.ChunkCount, &item_total, why, sizeof(why));
+        if (code != ILM_OK) return fail(code, "item %d: %s", i, why);
+        total += item_total;
         for (int k = 0; k < it.ChunkCount; k++) {
             const int q = it.QuadCounts ? it.QuadCounts[k] : e->slots;
-            if (q < 0 || q > e->slots) return fail(ILM_ERR_OUT_OF_RANGE, "item %d: quad_counts[%d] = %d outside [0, %d]", i, k, q, e->slots);
             if (q == 0) continue;
-            total += q;
             blocks += (q + kParticleLightBatchBlock - 1) / kParticleLightBatchBlock;
             entry_count++;
         }
@@ -3478,9 +3505,7 @@ int32_t ilm_engine_render_particle_lights_batch(IlmHandle hengine, const IlmPart
     // (an entry carries its chunk's address: no system's chunk table is read on the device)
     // the entries, then the parameters (entries are multiples of 8 bytes, a parameter block is floats: both stay aligned)
     const size_t table_bytes = sizeof(ParticleLightBatchEntry) * entry_count, bytes = table_bytes + sizeof(IlmParticleLightParams) * (size_t)count;
-    rc = reserve(c, c->d_pl_recs, kLightRecBytes * (size_t)total, kLightRecBytes * (size_t)std::max<int64_t>(total, 4096));
-    if (rc == ILM_OK) rc = reserve(c, c->d_pl_count, sizeof(int32_t), sizeof(int32_t));
-    if (rc == ILM_OK) rc = reserve(c, c->d_pl_blocks, sizeof(int32_t) * (size_t)blocks, sizeof(int32_t) * (size_t)blocks * 2);
+    rc = reserve_particle_light_scratch(c, total, blocks);
     if (rc == ILM_OK) rc = reserve(c, c->d_pl_batch, bytes, bytes * 2);
     if (rc != ILM_OK) return rc;
     void* host = nullptr;
@@ -3513,17 +3538,9 @@ int32_t ilm_engine_render_particle_lights_batch(IlmHandle hengine, const IlmPart
     pl.out_count = c->d_pl_count.as<int32_t>(); pl.out_count_host = e->h_pl_emitted_dev;
     HIP_TRY(launch_prepare_particle_lights_batch(pl, c->main()));
     e->last_pl_prepare = 3;
-
-    a.light_count = 0;
-    a.light_count_ptr = c->d_pl_count.as<int32_t>();
-    a.accumulate = 1;
-    HIP_TRY(launch_stats_begin(c, stats != nullptr, &a.stats));
-    c->last_light_blocks = light_launch_blocks(a); c->last_light_split = a.split; c->last_light_macro = a.tile_macro;
-    HIP_TRY(launch_sphere_lights_prepared(a, c->d_pl_recs.p, c->main()));
-    e->last_pl_tile_launches = 1;
-    HIP_TRY(light_pass_queued(c, f, g));
-    HIP_TRY(launch_stats_end(c, stats));
-    return ILM_OK;
+    rc = queue_particle_light_tiles(c, a, f, g, stats);
+    if (rc == ILM_OK) e->last_pl_tile_launches = 1;
+    return rc;
 }
 int32_t ilm_debug_last_particle_light_batch(IlmHandle h, int32_t* out_items, int32_t* out_prepare_launches, int32_t* out_tile_launches) {
     Engine* e = from_handle<Engine>(h, kMagicEngine);
@@ -3602,10 +3619,7 @@ static int32_t render_probes(Ctx* c, ProbeKind kind, const char* who, const IlmL
     }
     // (the line kind reads no ramp: the reference has no LineLightProbeWithDistanceRamp)
     const RampView ramp = (kind == kProbeLine) ? RampView{ nullptr, 0, 0 } : RampView{ c->d_light_ramp, c->light_ramp_w, c->light_ramp_h };
-    if (kind == kProbeDirectional)
-        HIP_TRY(launch_directional_light_probes(c->d_recs.p, light_count, d_pos, d_nrm, probe_count, *df, make_sdf_view(f, df), ramp, d_val, d_pairs, c->main()));
-    else
-        HIP_TRY(launch_light_probes(c->d_recs.p, light_count, d_pos, d_nrm, probe_count, *env, *df, make_sdf_view(f, df), ramp, d_val, d_pairs, c->main()));
+    HIP_TRY(launch_light_probes(kind == kProbeDirectional, c->d_recs.p, light_count, d_pos, d_nrm, probe_count, *env, *df, make_sdf_view(f, df), ramp, d_val, d_pairs, c->main()));
     rc = staged_small_done(c, slot);
     if (rc != ILM_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->main()));

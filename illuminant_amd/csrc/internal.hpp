@@ -329,15 +329,12 @@ struct ParticleLightBatchLaunch {
     int32_t* out_count_host;        // device-visible host word that receives it too (the diagnostic reads it after the stream)
 };
 hipError_t launch_prepare_particle_lights_batch(const ParticleLightBatchLaunch& a, hipStream_t stream);
-// Light probes (SphereLightProbe.fx): every prepared light record on every probe; values = float4 per probe (device)
-hipError_t launch_light_probes(const void* recs, int light_count, const float4* probe_positions, const float4* probe_normals, int probe_count,
-                               const IlmEnvironment& env, const IlmDistanceFieldUniforms& df, const SdfView& sdf, const RampView& ramp, float4* values, float4* pairs,
-                               hipStream_t stream);
-// Directional light probes (DirectionalLight.fx:163-219): the directional pass's records (launch_prepare_directional_lights) on every
-// probe, in launch_light_probes's shape; their footprint is not read
-hipError_t launch_directional_light_probes(const void* recs, int light_count, const float4* probe_positions, const float4* probe_normals, int probe_count,
-                                           const IlmDistanceFieldUniforms& df, const SdfView& sdf, const RampView& ramp, float4* values, float4* pairs,
-                                           hipStream_t stream);
+// Light probes: every prepared light record on every probe; values = float4 per probe (device).  directional = false: sphere records
+// (launch_prepare_lights; SphereLightProbe.fx, and LineLightProbe.fx through them); true: the directional pass's records
+// (launch_prepare_directional_lights; DirectionalLight.fx:163-219), whose footprint is not read and which do not read `env`
+hipError_t launch_light_probes(bool directional, const void* recs, int light_count, const float4* probe_positions, const float4* probe_normals,
+                               int probe_count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df, const SdfView& sdf, const RampView& ramp,
+                               float4* values, float4* pairs, hipStream_t stream);
 // sampleDistanceFieldEx at `count` positions (xyz triples) -- diagnostic entry point ilm_sdf_sample
 hipError_t launch_stamp16(void* where, const uint32_t stamp[4], hipStream_t stream);      // 16 bytes stored by a kernel (output.hip)
 hipError_t launch_sdf_sample(const SdfView& sdf, const IlmDistanceFieldUniforms& df, const float* positions, int count, float* out, hipStream_t stream,

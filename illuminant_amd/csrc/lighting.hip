@@ -958,12 +958,11 @@ tile_done:
 // ---------------------------------------------------------------------------------------------
 constexpr int kPlBlock = 1024;
 
-ILM_DEV bool particle_emits_light(const ParticleLightLaunch& a, int chunk, int slot, float4& position, float4& light_color) {
-    const int quads = (a.quad_counts != nullptr) ? a.quad_counts[chunk] : a.slots;
-    if (slot >= quads || slot >= a.slots)
-        return false;
-    const float* base = a.chunk_bases[chunk];
-    const int64_t S = a.stride;
+// What makes a slot a light source once its chunk's base pointer is known and the slot lies below the quad count: the eight loads, the
+// un-premultiply, life > 0, the product with the call's or the item's LightColor, alpha > 0.  Called by particle_emits_light (the single
+// call's front end over the chunk table) and by both batch kernels (front end: slot >= e.quads); the order of the statements is the order
+// of the shader's (:43-45 before the life test) and stays.
+ILM_DEV bool particle_slot_emits_light(const float* base, int64_t S, int slot, const IlmFloat4& item_color, float4& position, float4& light_color) {
     position = mk4(base[slot], base[S + slot], base[2 * S + slot], base[3 * S + slot]);
     float4 rc = mk4(base[12 * S + slot], base[13 * S + slot], base[14 * S + slot], base[15 * S + slot]);   // Chunk.RenderColor
     if (rc.w > 0.0f) {   // unpremultiply, :43-45
@@ -971,8 +970,48 @@ ILM_DEV bool particle_emits_light(const ParticleLightLaunch& a, int chunk, int s
     }
     if (position.w <= 0.0f)
         return false;
-    light_color = mul4(rc, ld4(a.params.LightColor));
+    light_color = mul4(rc, ld4(item_color));
     return light_color.w > 0.0f;
+}
+
+ILM_DEV bool particle_emits_light(const ParticleLightLaunch& a, int chunk, int slot, float4& position, float4& light_color) {
+    const int quads = (a.quad_counts != nullptr) ? a.quad_counts[chunk] : a.slots;
+    if (slot >= quads || slot >= a.slots)
+        return false;
+    return particle_slot_emits_light(a.chunk_bases[chunk], a.stride, slot, a.params.LightColor, position, light_color);
+}
+
+// The record of one emitting particle, for particle_light_emit_kernel (P = the call's parameters) and particle_light_batch_emit_kernel
+// (P = params[e.item], a reference into the table: wave-uniform, so its loads stay scalar).  Every operation stays as it is written and
+// in this order, the `* 1.0f` included: contraction is off and the records' bits are what the tile pass and the oracle tests see.
+ILM_DEV LightRec particle_light_record(const float4& pos, const float4& col, const IlmParticleLightParams& P, const IlmEnvironment& env,
+                                       float max_cone_radius, const TraceGate& gate) {
+    LightRec r;
+    r.cx = pos.x; r.cy = pos.y; r.cz = pos.z;
+    r.radius = P.LightProperties.x; r.ramp = P.LightProperties.y; r.falloff_mode = P.LightProperties.z; r.casts_shadows = P.LightProperties.w;
+    r.ao_radius = P.MoreLightProperties.x; r.falloff_y = P.MoreLightProperties.z; r.ao_opacity = P.MoreLightProperties.w;
+    r.shadow_filter = -1.0f;                                                   // ParticleLightPixelShader has no shadow filter
+    r.col_r = col.x * col.w; r.col_g = col.y * col.w; r.col_b = col.z * col.w; // lightColor.rgb * lightColor.a, :113-116
+    r.spec_r = P.LightSpecularColor.x; r.spec_g = P.LightSpecularColor.y; r.spec_b = P.LightSpecularColor.z; r.spec_power = P.LightSpecularColor.w;
+    // the quad, :55-70: a plain rectangle (fx1 = fx0, fx2 = fx3 collapse the sphere light's cross shape onto it)
+    const float radius = P.LightProperties.x + P.LightProperties.y + 1.0f;
+    const float tlx = r.cx - radius, brx = r.cx + radius, bry = r.cy + radius;
+    float tly = r.cy - radius;
+    tly -= radius * env.ZToY.y;
+    tly -= r.cz * env.ZToY.x;
+    const float sx = env.GBufferTexelSizeAndMisc.z * env.ZAndScale.z, sy = env.GBufferTexelSizeAndMisc.w * env.ZAndScale.w;
+    r.fx0 = r.fx1 = (tlx - env.ViewportPosition[0]) * sx;
+    r.fx2 = r.fx3 = (brx - env.ViewportPosition[0]) * sx;
+    r.fy0 = r.fy1 = (tly - env.ViewportPosition[1]) * sy;
+    r.fy2 = r.fy3 = (bry - env.ViewportPosition[1]) * sy;
+    const float max_radius = clampf(r.radius, ref::kMinConeRadius, max_cone_radius);
+    r.cfg_x = max_radius;
+    r.cfg_y = max_radius / fmaxf(r.ramp, 16.0f) * 1.0f;
+    r.ramp_offset = r.ramp_rate = 0.0f;
+    const int flags = light_flags(r, gate);
+    r.flags = (float)flags;
+    r.ramp_rcp = (flags & kLightFastDivide) ? refined_rcp(r.ramp) : 0.0f;
+    return r;
 }
 
 __global__ __launch_bounds__(kPlBlock) void particle_light_count_kernel(const ParticleLightLaunch a, int blocks_per_chunk) {
@@ -1022,33 +1061,7 @@ __global__ __launch_bounds__(kPlBlock) void particle_light_emit_kernel(const Par
     for (int w = 0; w < wave; w++) index += wave_counts[w];
     if (index >= a.capacity)
         return;
-    const IlmParticleLightParams& P = a.params;
-    LightRec r;
-    r.cx = pos.x; r.cy = pos.y; r.cz = pos.z;
-    r.radius = P.LightProperties.x; r.ramp = P.LightProperties.y; r.falloff_mode = P.LightProperties.z; r.casts_shadows = P.LightProperties.w;
-    r.ao_radius = P.MoreLightProperties.x; r.falloff_y = P.MoreLightProperties.z; r.ao_opacity = P.MoreLightProperties.w;
-    r.shadow_filter = -1.0f;                                                   // ParticleLightPixelShader has no shadow filter
-    r.col_r = col.x * col.w; r.col_g = col.y * col.w; r.col_b = col.z * col.w; // lightColor.rgb * lightColor.a, :113-116
-    r.spec_r = P.LightSpecularColor.x; r.spec_g = P.LightSpecularColor.y; r.spec_b = P.LightSpecularColor.z; r.spec_power = P.LightSpecularColor.w;
-    // the quad, :55-70: a plain rectangle (fx1 = fx0, fx2 = fx3 collapse the sphere light's cross shape onto it)
-    const float radius = P.LightProperties.x + P.LightProperties.y + 1.0f;
-    const float tlx = r.cx - radius, brx = r.cx + radius, bry = r.cy + radius;
-    float tly = r.cy - radius;
-    tly -= radius * a.env.ZToY.y;
-    tly -= r.cz * a.env.ZToY.x;
-    const float sx = a.env.GBufferTexelSizeAndMisc.z * a.env.ZAndScale.z, sy = a.env.GBufferTexelSizeAndMisc.w * a.env.ZAndScale.w;
-    r.fx0 = r.fx1 = (tlx - a.env.ViewportPosition[0]) * sx;
-    r.fx2 = r.fx3 = (brx - a.env.ViewportPosition[0]) * sx;
-    r.fy0 = r.fy1 = (tly - a.env.ViewportPosition[1]) * sy;
-    r.fy2 = r.fy3 = (bry - a.env.ViewportPosition[1]) * sy;
-    const float max_radius = clampf(r.radius, ref::kMinConeRadius, a.max_cone_radius);
-    r.cfg_x = max_radius;
-    r.cfg_y = max_radius / fmaxf(r.ramp, 16.0f) * 1.0f;
-    r.ramp_offset = r.ramp_rate = 0.0f;
-    const int flags = light_flags(r, a.gate);
-    r.flags = (float)flags;
-    r.ramp_rcp = (flags & kLightFastDivide) ? refined_rcp(r.ramp) : 0.0f;
-    reinterpret_cast<LightRec*>(a.recs)[index] = r;
+    reinterpret_cast<LightRec*>(a.recs)[index] = particle_light_record(pos, col, a.params, a.env, a.max_cone_radius, a.gate);
 }
 
 hipError_t launch_prepare_particle_lights(const ParticleLightLaunch& a, hipStream_t stream) {
@@ -1062,7 +1075,7 @@ hipError_t launch_prepare_particle_lights(const ParticleLightLaunch& a, hipStrea
 
 // ---------------------------------------------------------------------------------------------
 // Particle lights of MANY systems as one record list (ilm_engine_render_particle_lights_batch): the compaction above over a table of
-// (item, chunk) entries, every record built from its own item's parameters with the single call's operations.  A workgroup is 256 slots
+// (item, chunk) entries, every record built from its own item's parameters by particle_light_record.  A workgroup is 256 slots
 // of ONE entry, so its entry and its item's parameters are wave-uniform (scalar loads); an entry owns ceil(quads / 256) consecutive
 // workgroups from first_block on, found by a uniform bisection of the table.  Three launches whatever the number of items: the
 // workgroups' counts, ONE workgroup that turns them into exclusive bases (a frame of many systems has more counts than the single
@@ -1082,21 +1095,12 @@ ILM_DEV int particle_light_batch_entry(const ParticleLightBatchEntry* __restrict
     return lo;
 }
 
-// particle_emits_light for a slot of an entry: the same loads, the same un-premultiply, the same product, the same predicate
+// particle_emits_light's counterpart for a slot of an entry: the front end is the entry's quad count (quads <= slots: the entry point's check)
 ILM_DEV bool particle_light_batch_emits(const ParticleLightBatchEntry& e, int64_t S, int slot, const IlmFloat4& item_color, float4& position,
                                         float4& light_color) {
-    if (slot >= e.quads)      // (quads <= slots: the entry point's check)
+    if (slot >= e.quads)
         return false;
-    const float* base = e.base;
-    position = mk4(base[slot], base[S + slot], base[2 * S + slot], base[3 * S + slot]);
-    float4 rc = mk4(base[12 * S + slot], base[13 * S + slot], base[14 * S + slot], base[15 * S + slot]);   // Chunk.RenderColor
-    if (rc.w > 0.0f) {   // unpremultiply, :43-45
-        rc.x /= rc.w; rc.y /= rc.w; rc.z /= rc.w;
-    }
-    if (position.w <= 0.0f)
-        return false;
-    light_color = mul4(rc, ld4(item_color));
-    return light_color.w > 0.0f;
+    return particle_slot_emits_light(e.base, S, slot, item_color, position, light_color);
 }
 
 __global__ __launch_bounds__(kPlBatchBlock) void particle_light_batch_count_kernel(const ParticleLightBatchLaunch a,
@@ -1173,32 +1177,7 @@ __global__ __launch_bounds__(kPlBatchBlock) void particle_light_batch_emit_kerne
     for (int w = 0; w < wave; w++) index += wave_counts[w];
     if (index >= a.capacity)
         return;
-    // the record: particle_light_emit_kernel's statements, with the item's parameters for the call's
-    LightRec r;
-    r.cx = pos.x; r.cy = pos.y; r.cz = pos.z;
-    r.radius = P.LightProperties.x; r.ramp = P.LightProperties.y; r.falloff_mode = P.LightProperties.z; r.casts_shadows = P.LightProperties.w;
-    r.ao_radius = P.MoreLightProperties.x; r.falloff_y = P.MoreLightProperties.z; r.ao_opacity = P.MoreLightProperties.w;
-    r.shadow_filter = -1.0f;
-    r.col_r = col.x * col.w; r.col_g = col.y * col.w; r.col_b = col.z * col.w;
-    r.spec_r = P.LightSpecularColor.x; r.spec_g = P.LightSpecularColor.y; r.spec_b = P.LightSpecularColor.z; r.spec_power = P.LightSpecularColor.w;
-    const float radius = P.LightProperties.x + P.LightProperties.y + 1.0f;
-    const float tlx = r.cx - radius, brx = r.cx + radius, bry = r.cy + radius;
-    float tly = r.cy - radius;
-    tly -= radius * a.env.ZToY.y;
-    tly -= r.cz * a.env.ZToY.x;
-    const float sx = a.env.GBufferTexelSizeAndMisc.z * a.env.ZAndScale.z, sy = a.env.GBufferTexelSizeAndMisc.w * a.env.ZAndScale.w;
-    r.fx0 = r.fx1 = (tlx - a.env.ViewportPosition[0]) * sx;
-    r.fx2 = r.fx3 = (brx - a.env.ViewportPosition[0]) * sx;
-    r.fy0 = r.fy1 = (tly - a.env.ViewportPosition[1]) * sy;
-    r.fy2 = r.fy3 = (bry - a.env.ViewportPosition[1]) * sy;
-    const float max_radius = clampf(r.radius, ref::kMinConeRadius, a.max_cone_radius);
-    r.cfg_x = max_radius;
-    r.cfg_y = max_radius / fmaxf(r.ramp, 16.0f) * 1.0f;
-    r.ramp_offset = r.ramp_rate = 0.0f;
-    const int flags = light_flags(r, a.gate);
-    r.flags = (float)flags;
-    r.ramp_rcp = (flags & kLightFastDivide) ? refined_rcp(r.ramp) : 0.0f;
-    recs[index] = r;
+    recs[index] = particle_light_record(pos, col, P, a.env, a.max_cone_radius, a.gate);
 }
 
 hipError_t launch_prepare_particle_lights_batch(const ParticleLightBatchLaunch& a, hipStream_t stream) {
@@ -1235,8 +1214,24 @@ ILM_DEV bool probe_light(const float4 pp, const float4 pn, LightRec L, const Ilm
     return shade_light<FMT, false>(P, L, env, field, have_sdf, ramp, st, cr, cg, cb);
 }
 
-template <int FMT>
-__global__ __launch_bounds__(64) void light_probes_kernel(const LightRec* __restrict__ recs, int light_count,
+// What a probe kind supplies to light_probes_kernel: its record type, whether the field's InsideConsts are made (false: they stay {}),
+// and shade(): whether the record lights the probe, and its contribution before the factor probe_opacity.
+struct SphereProbes {      // ilm_render_light_probes, and ilm_render_line_light_probes through the sphere vertices the host makes
+    using Rec = LightRec;
+    static constexpr bool kInsideConsts = true;
+    template <int FMT>
+    static ILM_DEV bool shade(const float4 pp, const float4 pn, const LightRec& L, const IlmEnvironment& env, const TraceField& field, bool have_sdf,
+                              const RampView& ramp, float& cr, float& cg, float& cb) {
+        return probe_light<FMT>(pp, pn, L, env, field, have_sdf, ramp, cr, cg, cb);
+    }
+};
+
+// The frame of every probe kind (KIND: SphereProbes above, DirectionalProbes below; launch_light_probes picks it): one lane per probe,
+// the plain trace view without the cell array, then one contribution per wave in the pair form, or the one-kernel loop in light order.
+// Both forms multiply the kind's contribution by probe_opacity afterwards -- (col * opacity) * probe_opacity -- and add in light order:
+// neither the association nor the order may change, light_probes_sum_kernel and the oracle tests hold the two forms to the same bits.
+template <int FMT, typename KIND>
+__global__ __launch_bounds__(64) void light_probes_kernel(const typename KIND::Rec* __restrict__ recs, int light_count,
                                                            const float4* __restrict__ probe_positions, const float4* __restrict__ probe_normals,
                                                            int probe_count, IlmEnvironment env, IlmDistanceFieldUniforms df, SdfView sdf,
                                                            RampView ramp, float4* __restrict__ values, float4* __restrict__ pairs) {
@@ -1250,25 +1245,26 @@ __global__ __launch_bounds__(64) void light_probes_kernel(const LightRec* __rest
     TraceSdfView trace_sdf;                                       // probes are few: the general sampler, no cell array
     static_cast<SdfView&>(trace_sdf) = sdf;
     trace_sdf.cells = nullptr; trace_sdf.cells_bytes = 0; trace_sdf.slice_w = 0; trace_sdf.slice_h = 0;
-    const InsideConsts inside = make_inside_consts(df, trace_sdf);
+    InsideConsts inside = {};
+    if (KIND::kInsideConsts) inside = make_inside_consts(df, trace_sdf);
     const TraceField field = { df, trace_sdf, inside, nullptr };
     if (pairs != nullptr) {
         const int k = (int)blockIdx.y;                            // this wave's light
         float cr = 0.0f, cg = 0.0f, cb = 0.0f;
         bool lit = false;
         if (valid && probe_opacity > 0.0f)
-            lit = probe_light<FMT>(pp, pn, recs[k], env, field, have_sdf, ramp, cr, cg, cb);
+            lit = KIND::template shade<FMT>(pp, pn, recs[k], env, field, have_sdf, ramp, cr, cg, cb);
         if (valid)
             pairs[(size_t)k * (size_t)probe_count + (size_t)i] = lit ? mk4(cr * probe_opacity, cg * probe_opacity, cb * probe_opacity, 1.0f) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
     float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
     for (int k = 0; k < light_count; k++) {
-        const LightRec L = recs[k];
+        const typename KIND::Rec& L = recs[k];
         if (!(valid && probe_opacity > 0.0f))
             continue;
         float cr, cg, cb;
-        if (!probe_light<FMT>(pp, pn, L, env, field, have_sdf, ramp, cr, cg, cb))
+        if (!KIND::template shade<FMT>(pp, pn, L, env, field, have_sdf, ramp, cr, cg, cb))
             continue;
         acc_r += cr * probe_opacity;
         acc_g += cg * probe_opacity;
@@ -1294,23 +1290,6 @@ __global__ __launch_bounds__(64) void light_probes_sum_kernel(const float4* __re
             if ((k0 + u < light_count) && (c[u].w != 0.0f)) { acc_r += c[u].x; acc_g += c[u].y; acc_b += c[u].z; acc_a += 1.0f; }
     }
     values[i] = mk4(acc_r, acc_g, acc_b, acc_a);
-}
-
-hipError_t launch_light_probes(const void* recs, int light_count, const float4* probe_positions, const float4* probe_normals, int probe_count,
-                               const IlmEnvironment& env, const IlmDistanceFieldUniforms& df, const SdfView& sdf, const RampView& ramp, float4* values,
-                               float4* pairs, hipStream_t stream) {
-    if (probe_count <= 0) return hipSuccess;
-    const bool by_pair = (pairs != nullptr) && (light_count > 1) && (light_count <= 65535);
-    const dim3 grid((unsigned)((probe_count + 63) / 64), by_pair ? (unsigned)light_count : 1u), block(64);
-    const LightRec* r = reinterpret_cast<const LightRec*>(recs);
-    float4* p = by_pair ? pairs : nullptr;
-    if (sdf.format == ILM_SDF_FP16)
-        hipLaunchKernelGGL(light_probes_kernel<ILM_SDF_FP16>, grid, block, 0, stream, r, light_count, probe_positions, probe_normals, probe_count, env, df, sdf, ramp, values, p);
-    else
-        hipLaunchKernelGGL(light_probes_kernel<ILM_SDF_UNORM16>, grid, block, 0, stream, r, light_count, probe_positions, probe_normals, probe_count, env, df, sdf, ramp, values, p);
-    if (by_pair)
-        hipLaunchKernelGGL(light_probes_sum_kernel, dim3((unsigned)((probe_count + 63) / 64)), block, 0, stream, p, light_count, probe_count, values);
-    return hipGetLastError();
 }
 
 template <int FMT>
@@ -1767,11 +1746,9 @@ hipError_t launch_directional_lights_prepared(const LightLaunch& a, const void* 
 
 // ---------------------------------------------------------------------------------------------
 // Directional light probes -- DirectionalLightProbePixelShader / ...WithRampPixelShader, DirectionalLight.fx:163-219: the core of
-// the frame pass (shade_directional) on a Pixel built from the probe.  The launch has the shape of light_probes_kernel: one wave per
-// (block of 64 probes, light), the pair's contribution to scratch [light][probe], light_probes_sum_kernel adds them in light order;
-// `pairs` = nullptr: the one-kernel form, one lane per probe walking every record.  The records are the frame pass's
-// (prepare_directional_lights_kernel); their footprint is not read (the probe vertex shader covers the target, :39-50, "FIXME: Clip to
-// region" :175).
+// the frame pass (shade_directional) on a Pixel built from the probe, inside light_probes_kernel's frame (DirectionalProbes below).
+// The records are the frame pass's (prepare_directional_lights_kernel); their footprint is not read (the probe vertex shader covers
+// the target, :39-50, "FIXME: Clip to region" :175).
 // ---------------------------------------------------------------------------------------------
 template <int FMT>
 ILM_DEV bool probe_directional(const float4 pp, const float4 pn, DirectionalRec L, const TraceField& field, bool have_sdf, const RampView& ramp,
@@ -1790,68 +1767,45 @@ ILM_DEV bool probe_directional(const float4 pp, const float4 pn, DirectionalRec 
     return shade_directional<FMT, false>(P, L, field, have_sdf, ramp, st, opacity);
 }
 
-template <int FMT>
-__global__ __launch_bounds__(64) void directional_light_probes_kernel(const DirectionalRec* __restrict__ recs, int light_count,
-                                                                       const float4* __restrict__ probe_positions, const float4* __restrict__ probe_normals,
-                                                                       int probe_count, IlmDistanceFieldUniforms df, SdfView sdf, RampView ramp,
-                                                                       float4* __restrict__ values, float4* __restrict__ pairs) {
-    const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
-    const bool valid = i < probe_count;
-    const float4 pp = valid ? probe_positions[i] : mk4(0.0f, 0.0f, 0.0f, 0.0f);
-    const float4 pn = valid ? probe_normals[i] : mk4(0.0f, 0.0f, 0.0f, 0.0f);
-    // sampleLightProbeBuffer, LightCommon.fxh:233-254
-    const float probe_opacity = pp.w;
-    const bool have_sdf = (sdf.texels != nullptr) && (df.Extent.x > 0.0f);
-    TraceSdfView trace_sdf;                                       // the general sampler, no cell array
-    static_cast<SdfView&>(trace_sdf) = sdf;
-    trace_sdf.cells = nullptr; trace_sdf.cells_bytes = 0; trace_sdf.slice_w = 0; trace_sdf.slice_h = 0;
-    const InsideConsts no_table = {};
-    const TraceField field = { df, trace_sdf, no_table, nullptr };
-    if (pairs != nullptr) {
-        const int k = (int)blockIdx.y;                            // this wave's light
-        float opacity = 0.0f;
-        bool lit = false;
-        if (valid && probe_opacity > 0.0f)
-            lit = probe_directional<FMT>(pp, pn, recs[k], field, have_sdf, ramp, opacity);
-        if (valid) {
-            const DirectionalRec& L = recs[k];
-            pairs[(size_t)k * (size_t)probe_count + (size_t)i] =
-                lit ? mk4((L.col_r * opacity) * probe_opacity, (L.col_g * opacity) * probe_opacity, (L.col_b * opacity) * probe_opacity, 1.0f) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
-        return;
-    }
-    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
-    for (int k = 0; k < light_count; k++) {
-        const DirectionalRec& L = recs[k];
-        if (!(valid && probe_opacity > 0.0f))
-            continue;
+struct DirectionalProbes {      // ilm_render_directional_light_probes; env is not read, and shade_directional reads no InsideConsts
+    using Rec = DirectionalRec;
+    static constexpr bool kInsideConsts = false;
+    template <int FMT>
+    static ILM_DEV bool shade(const float4 pp, const float4 pn, const DirectionalRec& L, const IlmEnvironment&, const TraceField& field, bool have_sdf,
+                              const RampView& ramp, float& cr, float& cg, float& cb) {
         float opacity;
         if (!probe_directional<FMT>(pp, pn, L, field, have_sdf, ramp, opacity))
-            continue;
-        acc_r += (L.col_r * opacity) * probe_opacity;
-        acc_g += (L.col_g * opacity) * probe_opacity;
-        acc_b += (L.col_b * opacity) * probe_opacity;
-        acc_a += 1.0f;
+            return false;
+        cr = L.col_r * opacity; cg = L.col_g * opacity; cb = L.col_b * opacity;
+        return true;
     }
-    if (valid)
-        values[i] = mk4(acc_r, acc_g, acc_b, acc_a);
-}
+};
 
-hipError_t launch_directional_light_probes(const void* recs, int light_count, const float4* probe_positions, const float4* probe_normals, int probe_count,
-                                           const IlmDistanceFieldUniforms& df, const SdfView& sdf, const RampView& ramp, float4* values, float4* pairs,
-                                           hipStream_t stream) {
-    if (probe_count <= 0) return hipSuccess;
+// The launcher of every probe kind (the line kind's records are sphere records): the pair form when there is scratch, more than one light
+// and a grid for them, then the sum in light order; else the one-kernel form.  `env` is not read by the directional kind.
+template <typename KIND>
+static hipError_t launch_light_probes_of(const void* recs, int light_count, const float4* probe_positions, const float4* probe_normals, int probe_count,
+                                         const IlmEnvironment& env, const IlmDistanceFieldUniforms& df, const SdfView& sdf, const RampView& ramp,
+                                         float4* values, float4* pairs, hipStream_t stream) {
     const bool by_pair = (pairs != nullptr) && (light_count > 1) && (light_count <= 65535);
     const dim3 grid((unsigned)((probe_count + 63) / 64), by_pair ? (unsigned)light_count : 1u), block(64);
-    const DirectionalRec* r = reinterpret_cast<const DirectionalRec*>(recs);
+    const typename KIND::Rec* r = reinterpret_cast<const typename KIND::Rec*>(recs);
     float4* p = by_pair ? pairs : nullptr;
     if (sdf.format == ILM_SDF_FP16)
-        hipLaunchKernelGGL(directional_light_probes_kernel<ILM_SDF_FP16>, grid, block, 0, stream, r, light_count, probe_positions, probe_normals, probe_count, df, sdf, ramp, values, p);
+        hipLaunchKernelGGL((light_probes_kernel<ILM_SDF_FP16, KIND>), grid, block, 0, stream, r, light_count, probe_positions, probe_normals, probe_count, env, df, sdf, ramp, values, p);
     else
-        hipLaunchKernelGGL(directional_light_probes_kernel<ILM_SDF_UNORM16>, grid, block, 0, stream, r, light_count, probe_positions, probe_normals, probe_count, df, sdf, ramp, values, p);
+        hipLaunchKernelGGL((light_probes_kernel<ILM_SDF_UNORM16, KIND>), grid, block, 0, stream, r, light_count, probe_positions, probe_normals, probe_count, env, df, sdf, ramp, values, p);
     if (by_pair)
         hipLaunchKernelGGL(light_probes_sum_kernel, dim3((unsigned)((probe_count + 63) / 64)), block, 0, stream, p, light_count, probe_count, values);
     return hipGetLastError();
+}
+
+hipError_t launch_light_probes(bool directional, const void* recs, int light_count, const float4* probe_positions, const float4* probe_normals,
+                               int probe_count, const IlmEnvironment& env, const IlmDistanceFieldUniforms& df, const SdfView& sdf, const RampView& ramp,
+                               float4* values, float4* pairs, hipStream_t stream) {
+    if (probe_count <= 0) return hipSuccess;
+    return directional ? launch_light_probes_of<DirectionalProbes>(recs, light_count, probe_positions, probe_normals, probe_count, env, df, sdf, ramp, values, pairs, stream)
+                       : launch_light_probes_of<SphereProbes>(recs, light_count, probe_positions, probe_normals, probe_count, env, df, sdf, ramp, values, pairs, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -3,7 +3,8 @@
 Criterion: tests.util.assert_close with its defaults on the whole value (the call tests/test_directional_gpu.py makes), and alpha -- the
 number of contributing lights -- exactly equal; no element is exempted.  The probes are the committed list pk.probes(), which
 tests/test_probe_kinds_kat.py holds off the trace's knife edges on the CPU.  Counts sit at the kernels' edges: 1, 64, 65 and 129 probes
-(one lane per probe, 64 per block) under 0, 1, 8, 9 and 17 lights (the sum kernel reads eight contributions at a time).
+(one lane per probe, 64 per block) under 0, 1, 8, 9 and 17 lights (the sum kernel reads eight contributions at a time), and 3 probes
+under 65 536 lights of the sphere and the directional kind: the one-kernel form's loop, past the pair form's grid.
 """
 import ctypes as C
 
@@ -242,6 +243,62 @@ def test_line_probes_read_four_members_and_no_ramp(worlds, ctx):
     finally:
         ctx.set_light_ramp(None)
     assert_bits_equal(w.line(lines, pp, pn), got, "the same call again")
+
+
+# ---- the one-kernel form under more than one light ---------------------------------------------------------------------------------------
+
+MANY = 65536                 # the pair form's grid ends at 65 535 lights: from here on one lane per probe walks every record
+AT = (0, 1, 31999, 32768, 65533, 65534)      # where the lights that reach the probes lie; every other record adds nothing, the last included
+
+
+def many_lights(dark, bright):
+    lights = (abi.LightVertex * MANY).from_buffer_copy(bytes(dark) * MANY)
+    for at, light in zip(AT, bright):
+        lights[at] = light
+    return lights
+
+
+def test_sphere_probes_in_one_kernel_under_65536_lights(worlds, ctx, oracle):
+    """65 536 sphere lights on 3 probes (one ragged wave): the loop of the one-kernel form against the pair-and-sum form of the first
+    65 535, bit for bit -- both add the same contributions in the same order, the last light is out of range.  Six lights reach the
+    probes (one is shadowed on one of them), the others lie 5 000 px away.  Measured once on an MI355X: 0.08 s for the test's call."""
+    w = worlds()
+    pp, pn = (a[[2, 4, 10]] for a in pk.probes(11))
+    lights = many_lights(scenes.sphere_light((5000.0, 5000.0, 10.0), 4.0, 2.0), [pk.sphere_vertex_of(l) for l in pk.line_lights(8)[1:4] + pk.line_lights(8)[5:8]])
+    got = native.render_light_probes(ctx, lights, pp, pn, ENV, w.dfu, w.sdf)
+    fewer = native.render_light_probes(ctx, (abi.LightVertex * (MANY - 1)).from_buffer(lights), pp, pn, ENV, w.dfu, w.sdf)
+    assert np.array_equal(got, fewer), "65 536 lights in one kernel against 65 535 as pairs"
+    want = oracle.render_light_probes(lights, pp, pn, ENV, w.dfu, w.otex)
+    hold(got, want, "3 probes under 65 536 sphere lights")
+    assert tuple(want[:, 3]) == (1.0, 3.0, 3.0) and (want[1:, :3] > 0).all()
+    flat = pn.copy()
+    flat[:, 3] = 0.0
+    assert (want[:, 0] < oracle.render_light_probes(lights, pp, flat, ENV, w.dfu, w.otex)[:, 0] - 0.01).any(), "a shadow shows"
+
+
+def test_directional_probes_in_one_kernel_under_65536_lights(worlds):
+    """The same under directional lights.  No directional light misses a visible probe, so the 65 530 others are the black, undirected
+    light of test_scratch_is_reused_after_a_larger_call: they add 0 to the colours and 1 to alpha.  The colours are compared bit for
+    bit with the pair-and-sum form of the first 65 535 lights, and each call's alpha is its number of lights.  Measured once on an
+    MI355X: 0.05 s for the test's call."""
+    w = worlds()
+    pp, pn = (a[[1, 2, 4]] for a in pk.probes(5))
+    black = dc.directional_light(direction=None, color=(0, 0, 0, 1), casts_shadows=False)
+    mixed = pk.mixed_lights(9, 2)
+    bright = [mixed[k] for k in (0, 1, 2, 5, 4, 3)]      # (1 and 5 cast shadows)
+    lights = many_lights(black, bright)
+    got = native.render_directional_light_probes(w.ctx, lights, pp, pn, ENV, w.dfu, w.sdf)
+    fewer = native.render_directional_light_probes(w.ctx, (abi.LightVertex * (MANY - 1)).from_buffer(lights), pp, pn, ENV, w.dfu, w.sdf)
+    assert np.array_equal(got[:, :3], fewer[:, :3]), "65 536 lights in one kernel against 65 535 as pairs"
+    pairs = w.want_pairs(bright + [black], pp, pn)
+    assert (pairs[:, :, 3] == 1).all(), "every light reaches every probe"
+    want = pk.sum_pairs(pairs)              # (the black lights between the six add +0 to a sum that is not -0: no bit moves)
+    want[:, 3] = MANY
+    hold(got, want, "3 probes under 65 536 directional lights")
+    assert np.array_equal(fewer[:, 3], want[:, 3] - 1)
+    flat = pn.copy()
+    flat[:, 3] = 0.0
+    assert (want[:, 0] > 0).all() and (want[:, 0] < pk.sum_pairs(w.want_pairs(bright, pp, flat))[:, 0] - 0.01).any(), "a shadow shows"
 
 
 # ---- the frame pass and the probes agree -----------------------------------------------------------------------------------------------
